@@ -14,33 +14,6 @@ kernels behind `extern "C"` entry points).  Names follow the reference's objects
 There is no CPU fallback: importing works anywhere (so the CPU test tier can check the library
 loads and exports every symbol), but creating a Context without a usable GPU raises.
 """
-import os as _os
-# HIP maps a process's streams onto GPU_MAX_HW_QUEUES hardware queues (default 4), read once when the runtime starts.  A context of this
-# library owns up to a dozen streams (lanes, side and tail streams, the standard branch, the regions' Forward, the clusters' envelopes),
-# and a host may run several contexts: with 4 queues, streams that are meant to run side by side end up one behind the other (two worker
-# contexts on whole --fs passes: 53-58 ms per block with 4, 49-51 with 16; nine contexts on configs[3]: 18.0 -> 14.5 ms per database
-# pass; one context alone: no difference).  Set before the first HIP call of the process; a value chosen by the caller is respected.
-def _hip_runtime_initialised():
-    """True only when this process has already made a HIP call that started the runtime (the case in which GPU_MAX_HW_QUEUES comes too
-    late).  A mapped libamdhip64 says nothing -- `import torch` maps it long before any HIP call -- so the question goes to torch, the
-    only way the runtime starts in a Python host before this module: torch.cuda.is_initialized() does not itself touch the GPU."""
-    import sys as _sys
-    t = _sys.modules.get("torch")
-    try:
-        return bool(t is not None and t.cuda.is_initialized())
-    except Exception:
-        return False
-
-
-HW_QUEUES_SET_BY_IMPORT = "GPU_MAX_HW_QUEUES" not in _os.environ
-if HW_QUEUES_SET_BY_IMPORT:
-    # (the variable is inherited by child processes; a host that wants another value sets it before importing this module)
-    if _hip_runtime_initialised():
-        import warnings as _warnings
-        _warnings.warn("bath_amd: the HIP runtime is already initialised in this process, so GPU_MAX_HW_QUEUES=16 comes too late to take effect "
-                       "(set it in the environment before the first HIP call: several worker contexts share 4 hardware queues otherwise; "
-                       "INTEGRATION.md, 'Several contexts on one GPU')", RuntimeWarning, stacklevel=2)
-    _os.environ["GPU_MAX_HW_QUEUES"] = "16"
 import ctypes as C
 import os
 import subprocess

@@ -28,11 +28,6 @@ are reduced and the ORF records gathered on rank 0 (point to point, nothing repl
 import argparse
 import json
 import os
-# HIP maps a process's streams onto GPU_MAX_HW_QUEUES hardware queues (default 4), read once when the runtime starts.  The legs with
-# many worker contexts launching small kernels at the same time (c4.concurrent_queries, c4.full_job: 9 host threads, a dozen streams)
-# queue up behind one another on 4: 18.0 -> 14.5 ms per configs[3] database pass with 16; the cascade, the --fs pass and its two-worker
-# leg are unchanged (10.7 / 67-68 / 57-59 ms with either).  INTEGRATION.md recommends the same to a host that runs several contexts.
-os.environ.setdefault("GPU_MAX_HW_QUEUES", "16")
 import socket
 import subprocess
 import sys
@@ -237,12 +232,23 @@ DB = os.path.join(ROOT, "tests", "golden", "tRNA-proteins.bhmm")      # the refe
 C5_M = 1024
 
 
+_C5_PATH = None
+
+
 def c5_model_path():
-    from bath_amd import synth
-    path = "/tmp/bath_bench_synth%d.bhmm" % C5_M
-    if not os.path.exists(path):
+    """The synthetic 1024-node model, written once per process to a file of its own (removed at exit): the model is seeded, so
+    every process writes the same one, and the ranks of one launch never read a file another rank is still writing."""
+    global _C5_PATH
+    if _C5_PATH is None:
+        import atexit
+        import tempfile
+        from bath_amd import synth
+        fd, path = tempfile.mkstemp(prefix="bath_bench_synth%d_" % C5_M, suffix=".bhmm")
+        os.close(fd)
+        atexit.register(os.unlink, path)
         synth.write_synthetic_bhmm(path, C5_M, seed=C5_M, name="synth%d" % C5_M)
-    return path
+        _C5_PATH = path
+    return _C5_PATH
 
 
 def c4_genome(ba, synth, n_nt):
@@ -750,6 +756,47 @@ def c5_size_sweep(ba, synth, bdist, ctx, sizes_mb):
 GPU = 0          # the device this rank's contexts live on (main() sets it: LOCAL_RANK, or 0 under BATH_BENCH_SHARE_DEVICE=1)
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+DUMP_WINDOWS = 200_000
+
+
+def dump_outputs(path, counters, records, n_windows):
+    """--dump-outputs: the cascade's outputs as <path>/<name>.npy, float64 (integers) or float32 (the f32 scores), every value finite.
+      counter_<name>  the pipeline counters (bath_pipeline_stats) of the last timed step, summed over the ranks: what the timed
+                      call returns (pipe.run(want_results=False) leaves the records on the device);
+      record_<field>  the records of the surviving ORFs (bath_orf_result) of the same block, from the copy-out pass that follows the
+                      timed steps, in (window, strand, frame, start) order.  Only the ORFs of every stride-th window are kept: the
+                      stride starts at n_windows / DUMP_WINDOWS and doubles until the dump fits in DUMP_LIMIT_BYTES (record_stride.npy).
+                      The library marks a score it did not compute with an infinity (vfsc / fwdsc -inf: the ORF stopped before that
+                      filter; usc / vfsc +inf: the filter overflowed, msv_status / vit_status ERANGE), so a score field holds its
+                      finite values only and record_<field>_rows the record rows they belong to: a row missing there is +inf where
+                      the stage's status is ERANGE and -inf otherwise."""
+    os.makedirs(path, exist_ok=True)
+    arrays = {"counter_" + f: np.array([counters[f]], dtype=np.float64) for f in counters}
+    fields = {f: (np.float32 if records.dtype[f] == np.float32 else np.float64) for f in records.dtype.names}
+    scores = [f for f in records.dtype.names if records.dtype[f].kind == "f"]
+    per_record = sum(np.dtype(t).itemsize for t in fields.values()) + 8 * len(scores)
+    rec = records[np.lexsort((records["start"], records["frame"], records["strand"], records["window"]))]
+    stride = max(1, -(-n_windows // DUMP_WINDOWS))
+    while True:
+        keep = rec[rec["window"] % stride == 0]
+        if len(keep) * per_record <= DUMP_LIMIT_BYTES - (1 << 20):
+            break
+        stride *= 2
+    arrays["record_stride"] = np.array([stride], dtype=np.float64)
+    for f, t in fields.items():
+        v = np.ascontiguousarray(keep[f]).astype(t)
+        if f in scores:
+            rows = np.flatnonzero(np.isfinite(v))
+            arrays["record_%s_rows" % f] = rows.astype(np.float64)
+            v = v[rows]
+        arrays["record_" + f] = v
+    for name, a in arrays.items():
+        if not np.isfinite(a).all():
+            raise SystemExit("--dump-outputs: %s holds a value that is not finite" % name)
+        np.save(os.path.join(path, name + ".npy"), a)
+
+
 # ------------------------------------------------------------------------------------------------ launcher
 
 def free_port():
@@ -800,7 +847,12 @@ def main():
                     help="skip the whole-block-as-one-part passes behind roofline.valu (profiling: every ssv_orf_kernel launch is then a timed-step launch)")
     ap.add_argument("--plumbing-only", action="store_true",
                     help="CPU test hook: launcher, broadcast, reduce and gather over gloo with fabricated counters; no kernels, value 0")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the timed cascade computed as DIR/<name>.npy (see dump_outputs): the counters of the last timed step "
+                         "and a fixed sample of the surviving ORFs' records; the inputs are seeded, so two builds can be compared array by array")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.gpus > 1 and "RANK" not in os.environ:
         sys.exit(launch_ranks(args.gpus, sys.argv[1:]))
@@ -917,6 +969,7 @@ def main():
                 stage_launches[name] = nl
         sync()
         elapsed = bdist.max_over_ranks(time.perf_counter() - t0, dev)
+        step_stats = stats                                     # the counters the last timed step returned
         # one more pass with the copy-out, to gather the records on rank 0 (outside the timed region; timed on its own below)
         pipe.run(dna, want_results=True, copy=False)           # first call sizes the page-locked result array
         t1 = time.perf_counter()
@@ -930,8 +983,13 @@ def main():
         res = np.zeros(min(n_mine, 64), dtype=ba.ORF_RESULT_DTYPE)
         res["window"] = np.arange(len(res))
         ms_with_results = 0.0
+        step_stats = stats
     merged = bdist.reduce_stats(stats, dev)
     hits = bdist.gather_results(res, lo, 0, dev)
+    if args.dump_outputs:
+        step_counters = bdist.reduce_stats(step_stats, dev)        # a collective: every rank takes part
+        if rank == 0:
+            dump_outputs(args.dump_outputs, step_counters, hits, args.windows if args.scaling == "strong" else args.windows * world)
     strong_check = None
     if on_gpu and world > 1 and args.scaling == "strong" and rank == 0:
         # one block over N ranks must be the block on one rank (p7_pipeline_Merge, p7_tophits_Merge: bathsearch.c:884-893): rank 0 runs

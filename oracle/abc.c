@@ -1,7 +1,7 @@
 /* abc.c -- digital alphabets and genetic codes.  ORACLE (test infrastructure only).
  *
  * The reference takes these from easel (esl_alphabet.c, esl_gencode.c), which is NOT in
- * /root/reference (INSTALL:7-8). They are restated here from easel's published conventions as
+ * the reference tree (INSTALL:7-8). They are restated here from easel's published conventions as
  * the reference uses them:
  *   amino  "ACDEFGHIKLMNPQRSTVWY-BJZOUX*~"  K=20 Kp=29  (modelconfig.c:139-141 uses K, Kp-2, Kp-1;
  *                                                          modelconfig.c:406,522 use Kp-2='*', Kp-3='X')

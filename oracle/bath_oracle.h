@@ -1,7 +1,7 @@
 /* bath_oracle.h -- CPU restatement of the bathsearch DP hot path (TEST INFRASTRUCTURE ONLY).
  *
  * This directory is the parity ORACLE for bath_amd. It is a plain-C, scalar restatement of the
- * reference algorithms (TravisWheelerLab/BATH, /root/reference/src). Nothing in the shipped
+ * reference algorithms (TravisWheelerLab/BATH, its src/). Nothing in the shipped
  * product (bath_amd/, include/) may call into it; only tests/, __graft_entry__.smoke() and the
  * cpu_baseline leg of bench.py do.
  *

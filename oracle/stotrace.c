@@ -9,7 +9,7 @@
  *   p7_spensemble_Add / _Cluster, link_spsamples   src/p7_spensemble.c:100-170, 189-217, 300-440
  *   the parameters of p7_domaindef_Create_BATH     src/p7_domaindef.c:83-97
  *
- * PARITY UNPINNED for this file.  It depends on easel routines that are absent from /root/reference (easel is an un-pinned
+ * PARITY UNPINNED for this file.  It depends on easel routines that are absent from the reference tree (easel is an un-pinned
  * submodule, branch BATH): esl_randomness_CreateFast / esl_random (the "fast" linear congruential generator, re-seeded with
  * 42 before every region, p7_pipeline.c:135-143), esl_rnd_FChoose, esl_vec_FNorm, esl_cluster_SingleLinkage.  They are
  * restated here from easel's published algorithms (esl_random.c: x = 69069 x + 1 on a Jenkins-mixed seed, u = x / 2^32;

@@ -136,6 +136,22 @@ def test_bench_launcher_starts_the_ranks(scaling):
     assert c5["n_gpus"] == 2 and c5["domains_gathered"] == 4 and c5["windows_of_gathered_domains_are_global"]
 
 
+def test_bench_dump_outputs(tmp_path):
+    """--dump-outputs DIR: the counters and the records the cascade leg gathered, one finite float32 / float64 .npy per array; --steps is
+    the number of timed steps the line reports (the arrays themselves are the GPU tier's test_bench_dump_gpu.py)."""
+    import json
+    import subprocess
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--plumbing-only", "--windows", "1001", "--no-fs", "--no-c45",
+                        "--steps", "3", "--dump-outputs", str(tmp_path)], stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=300)
+    assert p.returncode == 0, p.stderr[-2000:]
+    line = json.loads([l for l in p.stdout.splitlines() if l.startswith("{")][-1])
+    assert line["steps"] == 3 and "ms_per_step" in line
+    d = {f[:-4]: np.load(os.path.join(str(tmp_path), f)) for f in os.listdir(str(tmp_path))}
+    assert all(a.dtype in (np.float32, np.float64) and np.isfinite(a).all() for a in d.values())
+    assert d["counter_nres"][0] == 2 * 1001 * 1000 and d["counter_n_past_msv"][0] == 1001
+    assert list(d["record_window"]) == list(range(64)) and d["record_stride"][0] == 1 and d["record_usc"].dtype == np.float32
+
+
 def _query_worker(rank, world, port, q):
     sys.path.insert(0, ROOT)
     import torch.distributed as dist

@@ -1,5 +1,5 @@
 """The pieces of easel that the multi-domain branch restates, held against INDEPENDENT implementations of the
-published algorithms.  easel itself is absent from /root/reference (an un-vendored submodule), so no easel-produced vector
+published algorithms.  easel itself is absent from the reference tree (an un-vendored submodule), so no easel-produced vector
 exists to compare with; what can be checked without it is that both restatements -- the product's (bath_ensemble.hip, through
 the bath_selftest_* hooks of include/bath_hip.h) and the oracle's (oracle/stotrace.c) -- compute exactly what the published
 definitions say:

@@ -150,7 +150,7 @@ def test_targets_block_matches_recorded_output(outfile, hmmfile, fasta, fs):
 @pytest.mark.parametrize("outfile,hmmfile,fasta,fs", [("PTH2.out", "PTH2.bhmm", "target-PTH2.fa", False), ("AMP_N-fs.out", "AMP_N.bhmm", "target-AMP_N.fa", True)])
 def test_annotation_heads_match_recorded_output(outfile, hmmfile, fasta, fs):
     """'>> seq1', header lines and the hit line of each entry under 'Annotation for each hit', byte for byte, for the two
-    recorded outputs written by the reference version in /root/reference (the other two predate a column change)."""
+    recorded outputs written by the reference version this project follows (the other two predate a column change)."""
     m = ol.Model(ol.GOLDEN + "/" + hmmfile, 0)
     hmm = ba.HMM(ol.GOLDEN + "/" + hmmfile, 0)
     recs = ol.read_fasta(ol.GOLDEN + "/" + fasta)
