@@ -225,6 +225,7 @@ ABI = {
     "bath_hip_fwdback_parser": (C.c_int, [_vp, _vp, _vp, _i64p, _f32p, _f32p, _i32p, _i32p, _f32p, _f32p]),
     "bath_hip_translate_orfs": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.POINTER(C.POINTER(Orf)), _i64p, C.POINTER(_u8p)]),
     "bath_hip_translate_orfs_opts": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(C.POINTER(Orf)), _i64p, C.POINTER(_u8p)]),
+    "bath_hip_orf_worklist": (C.c_int, [_vp, C.c_void_p, _i64p]),
     "bath_gencode_initiators": (C.c_int, [C.c_int, C.c_int, _u8p]),
     "bath_tophits_set_score_thresholds": (None, [_vp, C.c_int, C.c_double, C.c_int, C.c_double]),
     "bath_search_space_residues": (C.c_int64, [C.c_int, C.c_double, C.c_int, C.c_int64]),
@@ -635,6 +636,21 @@ def translate_orfs(ctx, dna, ncbi_table=1, min_orf_len=20, strands=STRAND_BOTH, 
         o = orfs[i]
         out.append((o.window, o.strand, o.frame, o.start, o.end, pool[o.aa_off:o.aa_off + o.n].copy()))
     return out
+
+
+ORF_WORK_DTYPE = np.dtype([("aa_off", np.int64), ("window", np.int32), ("len_sf", np.int32)])   # bath_orf_work
+
+
+def orf_worklist(ctx):
+    """The length-sorted ORF work list the last translate_orfs call built on the device, in list order (bath_orf_work records:
+    aa_off into the device's amino-acid stream pool, window, len_sf = residues | (strand*3 + frame) << 28)."""
+    p = C.c_void_p()
+    n = C.c_int64(0)
+    ctx._check(lib().bath_hip_orf_worklist(ctx._h, C.byref(p), C.byref(n)), "orf_worklist")
+    if n.value == 0:
+        return np.zeros(0, ORF_WORK_DTYPE)
+    buf = (C.c_char * (n.value * ORF_WORK_DTYPE.itemsize)).from_address(p.value)
+    return np.frombuffer(buf, ORF_WORK_DTYPE).copy()
 
 
 def _score_call(fn, what, ctx, om, sq):

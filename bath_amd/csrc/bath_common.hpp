@@ -46,6 +46,8 @@ constexpr int kSsvRows = 30;
 constexpr int kStop = 27;                // '*'
 constexpr int kXaa = 26;                 // 'X'
 constexpr int kOrfBins = 2048;           // ORF length histogram of the work-list sort (longer ORFs share the last bin)
+constexpr int kOrfCursorStride = 32;     // the sort's per-bin cursors, one 128-byte line each: every block adds to every busy bin
+constexpr int kOrfMiscInts = (1 + kOrfCursorStride) * kOrfBins + 64;   // histogram, cursors, total, spare: the misc buffer past 5*nent
 
 #define BATH_HIP_TRY(ctx, call)                                                            \
   do {                                                                                     \
@@ -255,6 +257,7 @@ struct bath_hip_ctx {
   std::vector<bath::PipelineSurvivor> fs_std_orfs;   // ORFs of the windows that take the standard branch (p7_pipeline.c:1479-1510)
   const uint8_t *fs_std_pool = nullptr;              // their residues: the amino-acid streams of the last cascade
   std::vector<uint8_t> orf_aa;
+  std::vector<bath_orf_work> orf_work;    // the device work list of the last bath_hip_translate_orfs call, in list order
   std::vector<bath_hmm_window> hmm_windows;   // bath_hip_vitfilter_bath / bath_hip_ssvfilter_bath output
   std::vector<bath::StageTiming> timings;
   std::vector<hipEvent_t> ev_pool;

@@ -165,10 +165,10 @@ struct OrfBuffers {               // device buffers of one translation pass
   void *slots;                    // ntiles*orf_slot_cap() records of 8 bytes
   void *cross;                    // ntiles*6 records of 8 bytes: ORFs crossing tile edges
   int32_t *cnt, *prefix, *suffix; // ntiles*6 each (cnt uses ntiles)
-  int *hist, *cursor, *ntotal;    // kOrfBins, kOrfBins, 1
+  int *hist, *cursor, *ntotal;    // kOrfBins, kOrfBins*kOrfCursorStride (bin b at b*kOrfCursorStride), 1
   OrfRec *sorted;                 // the work list, longest ORFs first; *ntotal entries
 };
-void orf_buffers_carve(OrfBuffers *ob, void *aa, void *slots, void *sorted, void *misc /* (5*nent + 2*kOrfBins + 64) ints */, size_t nent);
+void orf_buffers_carve(OrfBuffers *ob, void *aa, void *slots, void *sorted, void *misc /* 5*nent + kOrfMiscInts ints */, size_t nent);
 int launch_orf_scan(bath_hip_ctx *ctx, const bath_hip_seqs *dna, const OrfTablesDev &tt, int minlen, const OrfBuffers &b,
                     unsigned long long *d_n_orfs, unsigned long long *d_orf_res, int strands = 0);
 

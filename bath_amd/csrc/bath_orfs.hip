@@ -20,7 +20,7 @@
 //   orf_stitch_kernel one lane per (window, frame) walks the tile summaries and records the ORFs that cross tiles.
 //   orf_scan_bins     turns the ORF length histogram into start offsets, longest ORFs first.
 //   orf_sort_kernel   compacts the per-tile records into the dense work list ordered by length (block-local counting
-//                     sort: one global atomic per block and non-empty length bin).
+//                     sort over a block's records read once by the whole block: one global atomic per block and non-empty bin).
 // Amino stream of (w, sf):  aa + 2*off[w] + 96*w + sf*pitch(n),  pitch(n) = (n/3 + 16) & ~15   (closed form: no prefix sums)
 #include <algorithm>
 #include <climits>
@@ -448,61 +448,120 @@ __global__ __launch_bounds__(256) void orf_filter_kernel(SeqView dna, OrfTiles t
   if (threadIdx.x == 0 && s_red[0]) { atomicAdd(out.n_orfs, (unsigned long long)s_red[0]); atomicAdd(out.orf_res, (unsigned long long)s_red[1]); }
 }
 
-// counts -> start offsets, longest first; cursor[] is the copy the sort kernel advances; total ORFs -> *n_total
-__global__ void orf_scan_bins(const int *__restrict__ hist, int *__restrict__ cursor, int *__restrict__ n_total) {
-  __shared__ int tmp[kOrfBins];
-  for (int i = threadIdx.x; i < kOrfBins; i += blockDim.x) tmp[i] = hist[i];
+// counts -> start offsets, longest first; cursor[b * kOrfCursorStride] is the copy the sort kernel advances; total ORFs -> *n_total.
+// One block of 256 threads, each owning 8 consecutive bins in longest-first order: a parallel scan, not a serial walk of the 2048
+// bins (this single-block kernel waits for a CU beside the other part's SSV, and a serial chain there stretched it to over a ms).
+__global__ __launch_bounds__(256) void orf_scan_bins(const int *__restrict__ hist, int *__restrict__ cursor, int *__restrict__ n_total) {
+  constexpr int kPer = kOrfBins / 256;
+  __shared__ int s_wsum[4];
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  int c[kPer], sum = 0;
+#pragma unroll
+  for (int k = 0; k < kPer; k++) { c[k] = hist[kOrfBins - 1 - (kPer * tid + k)]; sum += c[k]; }
+  int x = sum;
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) { const int y = __shfl_up(x, d, 64); if (lane >= d) x += y; }
+  if (lane == 63) s_wsum[wv] = x;
   __syncthreads();
-  if (threadIdx.x == 0) {
-    int run = 0;
-    for (int b = kOrfBins - 1; b >= 0; b--) { const int c = tmp[b]; tmp[b] = run; run += c; }
-    *n_total = run;
-  }
-  __syncthreads();
-  for (int i = threadIdx.x; i < kOrfBins; i += blockDim.x) cursor[i] = tmp[i];
+  int run = x - sum;
+#pragma unroll
+  for (int u = 0; u < 4; u++) run += u < wv ? s_wsum[u] : 0;
+#pragma unroll
+  for (int k = 0; k < kPer; k++) { cursor[(kOrfBins - 1 - (kPer * tid + k)) * kOrfCursorStride] = run; run += c[k]; }
+  if (tid == 255) *n_total = run;
 }
 
-constexpr int kSortTilesPerThread = 8;
+// The work list: a counting sort by length bin, longest first, in blocks of kSortTiles consecutive tiles.  A block's records are
+// one flat sequence -- tile by tile, its cnt[t] slot records then its six crossing records -- that the block's lanes walk
+// together: consecutive lanes take consecutive records, so the slot regions and the crossing records are read by coalesced loads,
+// once.  Each lane keeps its kSortRegs records in registers while a returning LDS atomic ranks them within their bin; the block
+// then reserves its range in every non-empty bin with one global atomic and writes the records there.  A block whose records do
+// not fit in kSortThreads * kSortRegs takes several rounds (a reservation per round).  Cleared records (length 0: crossing
+// records without an ORF, and what orf_filter_kernel dropped) are skipped.
+constexpr int kSortThreads = 1024;
+constexpr int kSortTiles = 768;                                   // ~17 records per tile at the bench shape: one round per block
+constexpr int kSortRegs = 16;
+constexpr int kSortRound = kSortThreads * kSortRegs;
 
-__global__ __launch_bounds__(256) void orf_sort_kernel(SeqView dna, OrfTiles tiles, const uint2 *__restrict__ slots, int cap, const int32_t *__restrict__ cnt,
-                                                       const uint2 *__restrict__ cross, int *__restrict__ cursor, OrfRec *__restrict__ sorted) {
-  __shared__ int s_cnt[kOrfBins];
-  for (int i = threadIdx.x; i < kOrfBins; i += blockDim.x) s_cnt[i] = 0;
-  __syncthreads();
-  const int64_t base = (int64_t)blockIdx.x * (256 * kSortTilesPerThread);
-  // pass 1: this block's ORFs per length bin
-  for (int i = 0; i < kSortTilesPerThread; i++) {
-    const int64_t t = base + (int64_t)i * 256 + threadIdx.x;
-    if (t >= tiles.ntiles) break;
-    const int c = cnt[t];
-    const uint2 *sl = slots + t * cap;
-    for (int k = 0; k < c; k++) { const unsigned y = sl[k].y & 0x0fffffffu; if (y) atomicAdd(&s_cnt[orf_bin((int)y)], 1); }   // (0: cleared by orf_filter_kernel)
-    for (int f = 0; f < 6; f++) { const unsigned y = cross[t * 6 + f].y & 0x0fffffffu; if (y) atomicAdd(&s_cnt[orf_bin((int)y)], 1); }
-  }
-  __syncthreads();
-  // reserve this block's range in every non-empty bin
-  for (int i = threadIdx.x; i < kOrfBins; i += blockDim.x) {
-    const int c = s_cnt[i];
-    if (c) s_cnt[i] = atomicAdd(&cursor[i], c);
-  }
-  __syncthreads();
-  // pass 2: scatter
-  for (int i = 0; i < kSortTilesPerThread; i++) {
-    const int64_t t = base + (int64_t)i * 256 + threadIdx.x;
-    if (t >= tiles.ntiles) break;
-    const int c = cnt[t];
+__global__ __launch_bounds__(kSortThreads) void orf_sort_kernel(OrfTiles tiles, const uint2 *__restrict__ slots, int cap, const int32_t *__restrict__ cnt,
+                                                                const uint2 *__restrict__ cross, int *__restrict__ cursor, OrfRec *__restrict__ sorted) {
+  __shared__ int s_bin[kOrfBins];                                 // per round: records per bin, then the block's start in that bin
+  __shared__ int s_pre[kSortTiles + 1];                           // tile i's records are flat positions s_pre[i] .. s_pre[i+1]-1
+  __shared__ int64_t s_wbase[kSortTiles];                         // amino-acid pool offset of the tile's window
+  __shared__ int2 s_wp[kSortTiles];                               // {window, stream pitch}
+  __shared__ uint16_t s_own[kSortRound];                          // flat position within the round -> tile
+  __shared__ int s_wsum[kSortThreads / 64];
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  const int64_t t0 = (int64_t)blockIdx.x * kSortTiles;
+  int e = 0;
+  if (tid < kSortTiles && t0 + tid < tiles.ntiles) {
+    const int64_t t = t0 + tid;
     const int4 dsc = tiles.desc[t];
-    const int w = dsc.z;
-    const int64_t wbase = 2 * ((int64_t)(uint32_t)dsc.x << 4) + 96 * (int64_t)w;
-    const int pitch = orf_stream_pitch(dsc.y);
-    const uint2 *sl = slots + t * cap;
-    for (int k = 0; k < c + 6; k++) {
-      const uint2 r = k < c ? sl[k] : cross[t * 6 + (k - c)];
-      if ((r.y & 0x0fffffffu) == 0u) continue;
-      const int pos = atomicAdd(&s_cnt[orf_bin((int)(r.y & 0x0fffffffu))], 1);
+    e = cnt[t] + 6;
+    s_wbase[tid] = 2 * ((int64_t)(uint32_t)dsc.x << 4) + 96 * (int64_t)dsc.z;
+    s_wp[tid] = make_int2(dsc.z, orf_stream_pitch(dsc.y));
+  }
+  for (int i = tid; i < kOrfBins; i += kSortThreads) s_bin[i] = 0;
+  // block-wide exclusive prefix sum of the per-tile record counts
+  int x = e;
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) { const int y = __shfl_up(x, d, 64); if (lane >= d) x += y; }
+  if (lane == 63) s_wsum[wv] = x;
+  __syncthreads();
+  int before = 0, total = 0;
+#pragma unroll
+  for (int u = 0; u < kSortThreads / 64; u++) { const int s = s_wsum[u]; before += u < wv ? s : 0; total += s; }
+  const int pre = before + x - e;
+  if (tid < kSortTiles) s_pre[tid] = pre;
+  if (tid == 0) s_pre[kSortTiles] = total;
+  for (int r0 = 0; r0 < total; r0 += kSortRound) {
+    // owner of every flat position of the round: each tile's lane marks its own span
+    if (tid < kSortTiles) {
+      const int lo = max(pre, r0) - r0, hi = min(pre + e, r0 + kSortRound) - r0;
+      for (int j = lo; j < hi; j++) s_own[j] = (uint16_t)tid;
+    }
+    __syncthreads();
+    uint2 r[kSortRegs];
+    int ti[kSortRegs];
+#pragma unroll
+    for (int k = 0; k < kSortRegs; k++) {
+      const int j = r0 + k * kSortThreads + tid;
+      r[k] = make_uint2(0u, 0u);
+      ti[k] = -1;
+      if (j < total) {
+        const int i = s_own[j - r0];
+        const int loc = j - s_pre[i], c = s_pre[i + 1] - s_pre[i] - 6;
+        const int64_t t = t0 + i;
+        r[k] = loc < c ? slots[t * cap + loc] : cross[t * 6 + (loc - c)];
+        ti[k] = i;
+      }
+    }
+    // rank within the block's share of the bin
+#pragma unroll
+    for (int k = 0; k < kSortRegs; k++) {
+      const int len = (int)(r[k].y & 0x0fffffffu);
+      if (len) ti[k] |= atomicAdd(&s_bin[orf_bin(len)], 1) << 10;
+      else ti[k] = -1;
+    }
+    __syncthreads();
+    for (int i = tid; i < kOrfBins; i += kSortThreads) {
+      const int c = s_bin[i];
+      if (c) s_bin[i] = atomicAdd(&cursor[i * kOrfCursorStride], c);
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < kSortRegs; k++) {
+      if (ti[k] < 0) continue;
+      const int i = ti[k] & 1023, rank = ti[k] >> 10;
+      const int2 wp = s_wp[i];
+      const int pos = s_bin[orf_bin((int)(r[k].y & 0x0fffffffu))] + rank;
       OrfRec rec;
-      rec.aa_off = wbase + (int64_t)(r.y >> 28) * pitch + (int64_t)r.x; rec.w = w; rec.len_sf = (int32_t)r.y;
+      rec.aa_off = s_wbase[i] + (int64_t)(r[k].y >> 28) * wp.y + (int64_t)r[k].x; rec.w = wp.x; rec.len_sf = (int32_t)r[k].y;
       sorted[pos] = rec;
+    }
+    if (r0 + kSortRound < total) {                                // another round reuses s_bin and s_own
+      __syncthreads();
+      for (int i = tid; i < kOrfBins; i += kSortThreads) s_bin[i] = 0;
     }
   }
 }
@@ -513,7 +572,7 @@ void orf_buffers_carve(OrfBuffers *ob, void *aa, void *slots, void *sorted, void
   ob->aa = static_cast<uint8_t *>(aa); ob->slots = slots; ob->sorted = static_cast<OrfRec *>(sorted);
   ob->cross = misc;                                           // nent records of 8 bytes first (keeps them 8-byte aligned)
   ob->cnt = static_cast<int32_t *>(misc) + 2 * nent; ob->prefix = ob->cnt + nent; ob->suffix = ob->prefix + nent;
-  ob->hist = reinterpret_cast<int *>(ob->suffix + nent); ob->cursor = ob->hist + kOrfBins; ob->ntotal = ob->cursor + kOrfBins;
+  ob->hist = reinterpret_cast<int *>(ob->suffix + nent); ob->cursor = ob->hist + kOrfBins; ob->ntotal = ob->cursor + kOrfBins * kOrfCursorStride;
 }
 
 int orf_slot_cap(int minlen) { return 6 * (kTileCodons / (std::max(minlen, 0) + 1) + 2); }   // six frames share a tile's record region
@@ -624,8 +683,7 @@ int launch_orf_scan(bath_hip_ctx *ctx, const bath_hip_seqs *dna, const OrfTables
     hipLaunchKernelGGL(orf_filter_kernel, dim3(fblocks), dim3(256), 0, ctx->stream, dna->view(), tiles, out, flt, minlen);
   }
   hipLaunchKernelGGL(orf_scan_bins, dim3(1), dim3(256), 0, ctx->stream, b.hist, b.cursor, b.ntotal);
-  const int per_block = 256 * kSortTilesPerThread;
-  hipLaunchKernelGGL(orf_sort_kernel, dim3((unsigned)std::max<int64_t>(1, (ntiles + per_block - 1) / per_block)), dim3(256), 0, ctx->stream, dna->view(), tiles,
+  hipLaunchKernelGGL(orf_sort_kernel, dim3((unsigned)std::max<int64_t>(1, (ntiles + kSortTiles - 1) / kSortTiles)), dim3(kSortThreads), 0, ctx->stream, tiles,
                      reinterpret_cast<const uint2 *>(b.slots), out.cap, b.cnt, reinterpret_cast<const uint2 *>(b.cross), b.cursor, b.sorted);
   BATH_HIP_TRY(ctx, hipGetLastError());
   return BATH_OK;
@@ -647,7 +705,7 @@ extern "C" int bath_hip_translate_orfs_opts(bath_hip_ctx *ctx, const bath_hip_se
   BATH_HIP_TRY(ctx, hipSetDevice(ctx->device));
   *orfs = nullptr; *n_orfs = 0;
   if (aa) *aa = nullptr;
-  ctx->orfs.clear(); ctx->orf_aa.clear();
+  ctx->orfs.clear(); ctx->orf_aa.clear(); ctx->orf_work.clear();
   if (dna->n == 0) return BATH_OK;
   int st;
   OrfTablesDev tt{};
@@ -660,7 +718,7 @@ extern "C" int bath_hip_translate_orfs_opts(bath_hip_ctx *ctx, const bath_hip_se
   BATH_HIP_TRY(ctx, b_aa.reserve(orf_aa_bytes(dna)));
   BATH_HIP_TRY(ctx, b_slots.reserve(((size_t)dna->ntiles * (size_t)orf_slot_cap(min_orf_len) + 64) * 8));
   BATH_HIP_TRY(ctx, b_orfs.reserve((size_t)(max_orfs + 64) * sizeof(OrfRec)));
-  BATH_HIP_TRY(ctx, b_misc.reserve((5 * nent + 2 * kOrfBins + 64) * sizeof(int32_t) + 64));
+  BATH_HIP_TRY(ctx, b_misc.reserve((5 * nent + kOrfMiscInts) * sizeof(int32_t) + 64));
   OrfBuffers ob{};
   orf_buffers_carve(&ob, b_aa.p, b_slots.p, b_orfs.p, b_misc.p, nent);
   unsigned long long *d_ctr = reinterpret_cast<unsigned long long *>(ob.ntotal + 2);   // two counters nobody reads here
@@ -672,6 +730,9 @@ extern "C" int bath_hip_translate_orfs_opts(bath_hip_ctx *ctx, const bath_hip_se
   std::vector<OrfRec> recs((size_t)total);
   std::vector<uint8_t> pool(orf_aa_bytes(dna));
   if (total > 0) BATH_HIP_TRY(ctx, hipMemcpy(recs.data(), ob.sorted, recs.size() * sizeof(OrfRec), hipMemcpyDeviceToHost));
+  static_assert(sizeof(OrfRec) == sizeof(bath_orf_work), "bath_orf_work mirrors OrfRec");
+  ctx->orf_work.resize((size_t)total);
+  if (total > 0) std::memcpy(ctx->orf_work.data(), recs.data(), recs.size() * sizeof(OrfRec));
   BATH_HIP_TRY(ctx, hipMemcpy(pool.data(), ob.aa, pool.size(), hipMemcpyDeviceToHost));
   ctx->orfs.resize((size_t)total);
   for (int i = 0; i < total; i++) {
@@ -697,5 +758,11 @@ extern "C" int bath_hip_translate_orfs_opts(bath_hip_ctx *ctx, const bath_hip_se
   }
   *orfs = ctx->orfs.data(); *n_orfs = total;
   if (aa) *aa = ctx->orf_aa.data();
+  return BATH_OK;
+}
+
+extern "C" int bath_hip_orf_worklist(bath_hip_ctx *ctx, const bath_orf_work **list, int64_t *n) {
+  if (!ctx || !list || !n) return BATH_EINVAL;
+  *list = ctx->orf_work.data(); *n = (int64_t)ctx->orf_work.size();
   return BATH_OK;
 }

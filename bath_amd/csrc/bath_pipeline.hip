@@ -708,7 +708,7 @@ static int run_filters(bath_hip_ctx *ctx, const bath_hip_oprofile *om, const bat
   BATH_HIP_TRY(ctx, b_aa.reserve(orf_aa_bytes(dna)));
   BATH_HIP_TRY(ctx, b_slots.reserve(((size_t)dna->ntiles * (size_t)orf_slot_cap(prm->min_orf_len) + 64) * 8));
   BATH_HIP_TRY(ctx, b_orfs.reserve((size_t)(max_orfs + 64) * sizeof(OrfRec)));
-  BATH_HIP_TRY(ctx, b_misc.reserve((5 * nent + 2 * kOrfBins + 64) * sizeof(int32_t)));
+  BATH_HIP_TRY(ctx, b_misc.reserve((5 * nent + kOrfMiscInts) * sizeof(int32_t)));
   OrfBuffers ob{};
   orf_buffers_carve(&ob, b_aa.p, b_slots.p, b_orfs.p, b_misc.p, nent);
 

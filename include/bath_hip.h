@@ -285,6 +285,15 @@ int  bath_hip_translate_orfs(bath_hip_ctx *ctx, const bath_hip_seqs *dna, int nc
 /* ... for one strand only and / or with initiation codons (bath_pipeline_params.strands, .initiator) */
 int  bath_hip_translate_orfs_opts(bath_hip_ctx *ctx, const bath_hip_seqs *dna, int ncbi_table, int min_orf_len, int strands, int initiator,
                                   const bath_orf **orfs, int64_t *n_orfs, const uint8_t **aa);
+/* The length-sorted ORF work list the last bath_hip_translate_orfs[_opts] call built on the device, as the sort left it: longest
+ * first (lengths from 2047 up share the first bin), the order within a bin not defined.  aa_off is the ORF's offset in the
+ * device's amino-acid stream pool, len_sf = residues | (strand*3 + frame) << 28.  Owned by ctx, valid until the next call. */
+typedef struct {
+  int64_t aa_off;
+  int32_t window;
+  int32_t len_sf;
+} bath_orf_work;
+int  bath_hip_orf_worklist(bath_hip_ctx *ctx, const bath_orf_work **list, int64_t *n);
 /* gcode->is_initiator[16 a + 4 b + c] (easel codes A C G T = 0..3) under <initiator>; the table's own start codons are NCBI's
  * (gc.prt "sncbieaa" line); easel's copy is not in the reference tree, so BATH_INIT_TABLE is parity-unpinned */
 int  bath_gencode_initiators(int ncbi_table, int initiator, uint8_t is_init[64]);
