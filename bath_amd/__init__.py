@@ -27,6 +27,7 @@ LIB_PATH = os.environ.get("BATH_HIP_LIBRARY") or os.path.join(_HERE, "libbathhip
 OK, ERANGE, ENORESULT = 0, 16, 19
 KP, K, NEVPARAM = 29, 20, 8
 LOGSUM_TABLE, LOGSUM_EXACT, LOGSUM_TABLE_SERIAL, LOGSUM_CONTEXT = 0, 1, 2, 3
+LOGSUM_ODDS = 4                                     # 3-codon parsers in odds-ratio space (what the reference's --fs runs)
 
 DNA_SYMS = "ACGT-RYMKSWHBVDN*~"
 AMINO_SYMS = "ACDEFGHIKLMNPQRSTVWY-BJZOUX*~"
@@ -199,6 +200,7 @@ ABI = {
     "bath_hip_stream": (_vp, [_vp]),
     "bath_hip_set_fs_strict": (C.c_int, [_vp, C.c_int]),
     "bath_hip_set_fs_serial": (C.c_int, [_vp, C.c_int]),
+    "bath_hip_set_fs_odds": (C.c_int, [_vp, C.c_int]),
     "bath_hip_trim": (C.c_int, [_vp]),
     "bath_hip_kernel_times": (C.c_int, [_vp, C.c_int, C.POINTER(KernelTime)]),
     "bath_hip_oprofile_convert": (C.c_int, [_vp, C.POINTER(_Profile), C.POINTER(_vp)]),
@@ -448,6 +450,12 @@ class Context:
         """True (the library's default): frameshift log-sums along the model in the reference's serial order, bit-identical to the
         generic reference.  False: the fast mode (wavefront scans, scores within O(1e-3) nats)."""
         self._check(lib().bath_hip_set_fs_strict(self._h, 1 if on else 0), "set_fs_strict")
+
+    def set_fs_odds(self, on=True):
+        """True: the pipeline's 3-codon Forward and Backward parsers run in odds-ratio space (LOGSUM_ODDS, what the reference's
+        --fs runs), and LOGSUM_CONTEXT on FS3ForwardParser / FS3BackwardParser means LOGSUM_ODDS.  False (the default): no change.
+        The other frameshift stages follow set_fs_strict either way."""
+        self._check(lib().bath_hip_set_fs_odds(self._h, 1 if on else 0), "set_fs_odds")
 
     def set_fs_serial(self, on):
         """Measurement aid: the envelopes' Backward wavefront after the Forward one instead of beside it (bath_hip_set_fs_serial)."""

@@ -1656,7 +1656,7 @@ int bath_hip_fsprofile::ensure_len(int maxL_amino) const {
 extern "C" void bath_hip_fsprofile_destroy(bath_hip_fsprofile *om) {
   if (!om) return;
   for (void *p : {(void *)om->d_codons, (void *)om->d_indel, (void *)om->d_rsc, (void *)om->d_tf, (void *)om->d_tb, (void *)om->d_logsum, (void *)om->d_loop[0], (void *)om->d_loop[1],
-                  (void *)om->d_move[0], (void *)om->d_move[1]})
+                  (void *)om->d_move[0], (void *)om->d_move[1], (void *)om->d_odds_rsc, (void *)om->d_odds_tf, (void *)om->d_odds_tb})
     if (p) (void)hipFree(p);
   for (void *p : om->retired) (void)hipFree(p);
   delete om;
@@ -1742,6 +1742,11 @@ static int fs_columns(int M) {
     default: { constexpr int MD = 0; BODY } break;        \
   }
 
+// what BATH_LOGSUM_CONTEXT means for the 3-codon parsers: odds ratios when bath_hip_set_fs_odds switched them on, else strict / fast
+static int fs3_ctx_mode(const bath_hip_ctx *ctx) {
+  return ctx->fs_odds ? BATH_LOGSUM_ODDS : (ctx->fs_strict ? BATH_LOGSUM_TABLE_SERIAL : BATH_LOGSUM_TABLE);
+}
+
 static FsDev fsdev(const bath_hip_fsprofile *om) { return FsDev{om->M, om->pitch, om->maxcodons, om->d_rsc, om->d_tf, om->d_tb, om->d_logsum}; }
 
 static int fs_grid(bath_hip_ctx *ctx, int64_t n) {
@@ -1787,7 +1792,7 @@ static int fs3_parser(bath_hip_ctx *ctx, const bath_hip_fsprofile *om, const bat
                       const std::function<int()> *after_launch = nullptr /* runs between the kernel's launch and the wait for it */) {
   if (!ctx || !om || !dna || om->codon_lengths != 3) { if (ctx) ctx->set_error("fs3 parser needs a 3-codon profile"); return BATH_EINVAL; }
   BATH_HIP_TRY(ctx, hipSetDevice(ctx->device));
-  if (logsum_mode == BATH_LOGSUM_CONTEXT) logsum_mode = ctx->fs_strict ? BATH_LOGSUM_TABLE_SERIAL : BATH_LOGSUM_TABLE;
+  if (logsum_mode == BATH_LOGSUM_CONTEXT) logsum_mode = fs3_ctx_mode(ctx);
   const int64_t n = dna->n;
   if (n == 0) return BATH_OK;
   int st = om->ensure_len(dna->maxlen / 3 + 1);
@@ -1810,8 +1815,12 @@ static int fs3_parser(bath_hip_ctx *ctx, const bath_hip_fsprofile *om, const bat
   if ((st = fs_schedule(ctx, dna, 1, jq)) != BATH_OK) return st;
   const bool chain = logsum_mode == BATH_LOGSUM_TABLE_SERIAL && fs_chain_enabled();
   StageGate gate(chain ? ctx->device : -1, backward ? StageGate::kBwdChain : StageGate::kFwdChain);   // held until this stage's kernels have finished (the synchronize below)
-  const int sp = ctx->span_begin(backward ? "fs_bwd_kernel<3>" : "fs3_fwd_kernel", ctx->stream, (double)dna->total * om->M, (double)dna->total * ((xmx || keep) ? 21.0 : 1.0));
-  if (logsum_mode == BATH_LOGSUM_TABLE_SERIAL && fs_chain_enabled()) {
+  const bool odds = logsum_mode == BATH_LOGSUM_ODDS;
+  const int sp = ctx->span_begin(odds ? (backward ? "fs3_bwd_odds_kernel" : "fs3_fwd_odds_kernel") : (backward ? "fs_bwd_kernel<3>" : "fs3_fwd_kernel"), ctx->stream,
+                                 (double)dna->total * om->M, (double)dna->total * ((xmx || keep) ? 21.0 : 1.0));
+  if (odds) {
+    if ((st = launch_fs3_odds(ctx, ctx->stream, om, dna, backward, b_sc.as<float>(), d_x, b_off.as<int64_t>(), jq[0])) != BATH_OK) return st;
+  } else if (logsum_mode == BATH_LOGSUM_TABLE_SERIAL && fs_chain_enabled()) {
     if (!backward) st = launch_fs3_fwd_chain(ctx, ctx->stream, om, dna, Cv, tE, tE, b_sc.as<float>(), d_x, b_off.as<int64_t>(), jq[0]);
     else st = launch_fs3_bwd_chain(ctx, ctx->stream, om, dna, Cv, tE, tE, b_sc.as<float>(), d_x, b_off.as<int64_t>(), jq[0]);
     if (st != BATH_OK) return st;
@@ -1963,7 +1972,7 @@ __global__ void fs_rows_copy_kernel(int n, const int32_t *__restrict__ len, cons
 int fs3_backward_spec(bath_hip_ctx *ctx, const bath_hip_fsprofile *om, const bath_hip_seqs *dna, int k) {
   ctx->fs_spec_valid = false;
   const int64_t n = dna->n;
-  if (n == 0 || k <= 0 || !ctx->fs_strict || !fs_chain_enabled() || om->codon_lengths != 3) return BATH_OK;
+  if (n == 0 || k <= 0 || !ctx->fs_strict || ctx->fs_odds || !fs_chain_enabled() || om->codon_lengths != 3) return BATH_OK;   // (odds mode: its Backward rows would be strict-mode rows)
   int st = om->ensure_len(dna->maxlen / 3 + 1);
   if (st != BATH_OK) return st;
   if (!ctx->spec_stream) {
@@ -2057,7 +2066,7 @@ int fs3_regions(bath_hip_ctx *ctx, const bath_hip_fsprofile *om, const bath_hip_
   // Speculative rows (fs3_backward_spec): window q of <dna> is window kept[q] of the decision stage's block; when its Backward rows are
   // already in scratch[53] the parser below skips it (a job list of the OTHER windows, longest first; the launcher sees a shadow of
   // <dna> that holds only those) and a copy kernel puts the rows where the region heuristics read them
-  const bool spec = reuse && ctx->fs_spec_valid && ctx->fs_strict && fs_chain_enabled();
+  const bool spec = reuse && ctx->fs_spec_valid && ctx->fs_strict && !ctx->fs_odds && fs_chain_enabled();
   std::vector<int64_t> spec_src;
   bath_hip_seqs rest;
   const bath_hip_seqs *bwd_dna = dna;
@@ -2088,12 +2097,20 @@ int fs3_regions(bath_hip_ctx *ctx, const bath_hip_fsprofile *om, const bath_hip_
     bwd_dna = &rest;
   }
   struct Borrowed { bath_hip_seqs &v; ~Borrowed() { v.d_data = nullptr; v.d_off = nullptr; v.d_len = nullptr; } } rest_guard{rest};
-  const int mode = ctx->fs_strict ? BATH_LOGSUM_TABLE_SERIAL : BATH_LOGSUM_TABLE;
+  const int mode = fs3_ctx_mode(ctx);
   static const int spec_share = [] { const char *e = std::getenv("BATH_HIP_FS_SPEC_SHARE"); return e ? std::max(1, std::atoi(e)) : 2; }();   // (probe) CUs each parser's launch is sized for: all / this
   StageGate gate((mode == BATH_LOGSUM_TABLE_SERIAL && fs_chain_enabled()) ? ctx->device : -1, reuse ? StageGate::kBwdChain : StageGate::kFwdChain);   // held until the synchronize below
   if ((st = fs_fork(ctx)) != BATH_OK) return st;
   const double cells3 = (double)(xoff[(size_t)n] / 5) * om->M;                // rows x nodes; algorithmic HBM bytes: 1 B/nt in + 20 B/row out
   const double bytes3 = (double)(xoff[(size_t)n] / 5) * 21.0;
+  if (mode == BATH_LOGSUM_ODDS) {
+    const int s1 = reuse ? -1 : ctx->span_begin("fs3_fwd_odds_kernel", ctx->stream, cells3, bytes3);
+    if (!reuse && (st = launch_fs3_odds(ctx, ctx->stream, om, dna, false, b_sc.as<float>(), b_fx.as<float>(), b_off.as<int64_t>(), jq[0])) != BATH_OK) return st;
+    ctx->span_end(s1, ctx->stream);
+    const int s2 = ctx->span_begin("fs3_bwd_odds_kernel", ctx->side_stream, cells3, bytes3);
+    if ((st = launch_fs3_odds(ctx, ctx->side_stream, om, dna, true, b_sc.as<float>() + n, b_bx.as<float>(), b_off.as<int64_t>(), jq[1])) != BATH_OK) return st;
+    ctx->span_end(s2, ctx->side_stream);
+  } else
   BATH_FS_SWITCH(Cv, BATH_FS_MODE(mode, {
     if ((st = fs_set_shmem(ctx, fs3_fwd_kernel<CC, MD>, shmem)) != BATH_OK) return st;
     const int s1 = reuse ? -1 : ctx->span_begin("fs3_fwd_kernel", ctx->stream, cells3, bytes3);
@@ -2136,7 +2153,7 @@ namespace bath {
 // used by the pipeline's frameshift stage (bath_pipeline.hip)
 int fs3_forward_scores(bath_hip_ctx *ctx, const bath_hip_fsprofile *om3, const bath_hip_seqs *dna, float *sc, const std::function<int()> *after_launch) {
   ctx->fs_keep_xoff.clear();
-  const int mode = ctx->fs_strict ? BATH_LOGSUM_TABLE_SERIAL : BATH_LOGSUM_TABLE;
+  const int mode = fs3_ctx_mode(ctx);
   if (!ctx->fs_want_regions) return fs3_parser(ctx, om3, dna, mode, sc, nullptr, nullptr, false, nullptr, after_launch);
   // the domain stage follows: the special-state rows of every window stay on the device (20 B per nucleotide), so that the
   // windows that take the frameshift branch need the Backward parser only
@@ -2198,6 +2215,7 @@ int bath::fs5_envelopes_ex(bath_hip_ctx *ctx, const bath_hip_fsprofile *om, cons
                            bath_fs5_result *res, float *pp, float *oa, float *ppx, float *oax, FsTraceOut *trace,
                            const uint8_t *cons, std::vector<uint16_t> *steps, std::vector<int64_t> *step_off, std::vector<float> *step_pp) {
   if (!ctx || !om || !dna || om->codon_lengths != 5) { if (ctx) ctx->set_error("fs5 envelopes need a 5-codon profile"); return BATH_EINVAL; }
+  if (logsum_mode == BATH_LOGSUM_ODDS) { ctx->set_error("the 5-codon kernels have no odds-ratio mode"); return BATH_EINVAL; }
   BATH_HIP_TRY(ctx, hipSetDevice(ctx->device));
   const int64_t n = dna->n;
   if (n == 0) return BATH_OK;

@@ -33,6 +33,12 @@ struct bath_hip_fsprofile {
   mutable std::mutex grow_mu;
   mutable std::vector<void *> retired;
   int ensure_len(int maxL_amino) const;
+  // odds-ratio tables of a 3-codon profile (BATH_LOGSUM_ODDS, bath_fs_odds.hip): expf of d_rsc's codon rows, d_tf and d_tb, padded
+  // to the nodes of every lane, built on the first odds-mode call
+  mutable float *d_odds_rsc = nullptr, *d_odds_tf = nullptr, *d_odds_tb = nullptr;
+  mutable int odds_pitch = 0;    // floats per odds emission row
+  mutable std::mutex odds_mu;
+  int ensure_odds() const;
 };
 
 namespace bath {
@@ -192,6 +198,9 @@ int launch_fs3_bwd_chain(bath_hip_ctx *ctx, hipStream_t stream, const bath_hip_f
                          int bst_slot = 48, int stage_slot = 2 /* scratch / staging slots of the launch's batch starts */);
 int launch_fs5_fwd_chain(bath_hip_ctx *ctx, hipStream_t stream, const bath_hip_fsprofile *om, const bath_hip_seqs *dna, int Cv, float tEL, float tEM, int c5_compat,
                          float *d_sc, float *d_fwd, const int64_t *d_foff, float *d_xmx, const int64_t *d_xoff, int cfg_len, FsJobs jobs, int *d_done);
+// ---- the 3-codon parsers in odds-ratio space (bath_fs_odds.hip)
+int launch_fs3_odds(bath_hip_ctx *ctx, hipStream_t stream, const bath_hip_fsprofile *om, const bath_hip_seqs *dna, bool backward,
+                    float *d_sc, float *d_xmx, const int64_t *d_xoff, FsJobs jobs);
 inline bool fs_chain_enabled() { static const bool off = [] { const char *e = std::getenv("BATH_HIP_FS_HANDOFF"); return e && e[0] == '1'; }(); return !off; }   // BATH_HIP_FS_HANDOFF=1: the 64-step lane hand-off kernels, for A/B runs
 
 }  // namespace bath

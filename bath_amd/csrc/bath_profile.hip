@@ -238,6 +238,13 @@ extern "C" int bath_hip_set_fs_strict(bath_hip_ctx *ctx, int on) {
   return BATH_OK;
 }
 
+extern "C" int bath_hip_set_fs_odds(bath_hip_ctx *ctx, int on) {
+  if (!ctx) return BATH_EINVAL;
+  ctx->fs_odds = on ? 1 : 0;
+  for (bath_hip_ctx *l : ctx->lanes) l->fs_odds = ctx->fs_odds;
+  return BATH_OK;
+}
+
 // ------------------------------------------------------------------------------------------ oprofile
 
 extern "C" void bath_hip_oprofile_destroy(bath_hip_oprofile *om) {

@@ -125,6 +125,11 @@ void       *bath_hip_stream(bath_hip_ctx *ctx);                      /* hipStrea
  * strict_mode).  Use it for throughput estimates or pre-screening, never where hit lists are compared with the reference's.
  * Applies to the pipeline entry points and to BATH_LOGSUM_CONTEXT. */
 int         bath_hip_set_fs_strict(bath_hip_ctx *ctx, int on);
+/* Odds-ratio mode of the 3-codon parsers.  1: the pipeline entry points (bath_hip_pipeline_frameshift, _frameshift_domains) run their
+ * 3-codon Forward and Backward parsers in BATH_LOGSUM_ODDS, and BATH_LOGSUM_CONTEXT on the fs3 entry points means BATH_LOGSUM_ODDS;
+ * every other stage (envelopes, the regions' Forward, decoding, optimal accuracy) runs as bath_hip_set_fs_strict selects.
+ * 0 (the default): no change.  The first odds-mode call for a 3-codon profile builds its odds-ratio tables on the device. */
+int         bath_hip_set_fs_odds(bath_hip_ctx *ctx, int on);
 /* Measurement aid: 1 = the envelope stage (bath_hip_fs5_envelopes and the domain stage's batches) runs its Backward wavefront AFTER the
  * Forward wavefront on the same stream instead of beside it, so that a kernel's HIP-event span is its time alone on the chip
  * (bench.py: fs.roofline.alone); 0 = side by side (the default); -1 = whatever BATH_HIP_FS_SERIAL says.  Results do not change. */
@@ -555,7 +560,18 @@ int     bath_dist_deal(const double *costs, int64_t n_items, int world, int32_t 
 #define BATH_LOGSUM_TABLE 0   /* emulate p7_FLogsum's 0.001-nat truncating table (logsum.c:105) */
 #define BATH_LOGSUM_EXACT 1   /* exact log(1+exp(x))                                            */
 #define BATH_LOGSUM_TABLE_SERIAL 2 /* the table, sums along the model in the reference's serial order: bit-identical to generic_fwdback_frameshift.c */
-#define BATH_LOGSUM_CONTEXT 3 /* whatever bath_hip_set_fs_strict selected for the context: TABLE_SERIAL unless switched to the fast mode */
+#define BATH_LOGSUM_CONTEXT 3 /* whatever bath_hip_set_fs_strict selected for the context: TABLE_SERIAL unless switched to the fast mode
+                                 (fs3 entry points: ODDS when bath_hip_set_fs_odds switched it on) */
+/* BATH_LOGSUM_ODDS (3-codon parsers only; the fs5 entry points answer BATH_EINVAL): what the reference's bathsearch --fs runs,
+ * p7_{Forward,Backward}Parser_Frameshift_3Codons (impl_sse/fwdback_fs.c:97, :565) -- the recursion in fp32 odds ratios (expf of the
+ * profile's scores), no log-sum table, every value of the recursion rescaled together when E(i) (Backward: B(i)) passes 1e4.
+ * Contract: scores within 1e-3 + 1e-4 |s| nats of EXACT log-space arithmetic (the reference's own SIMD-vs-generic bar with exact
+ * log-sums, fwdback_fs.c:3189-3191), the special-state rows (log value + the accumulated scale, the layout of every mode) within
+ * 2e-3 + 2e-4 |v| where the exact value is above -60 (Backward: within 40 nats of its row's largest value); values that far below
+ * the scale flush to zero in fp32 and come back as -inf.  A window whose C(L) terms underflow (the reference's eslERANGE) scores -inf.
+ * NOT bit-identical to the generic reference: against the strict mode's table log-sums scores differ by up to ~1e-2 nats on long
+ * windows, so a window at a threshold may take the other branch and a domain may move. */
+#define BATH_LOGSUM_ODDS 4
 
 int  bath_hip_fsprofile_convert(bath_hip_ctx *ctx, const bath_fs_profile *gm_fs, bath_hip_fsprofile **ret); /* p7_fs_oprofile_Convert, p7_fs_oprofile.c:221 */
 void bath_hip_fsprofile_destroy(bath_hip_fsprofile *om);
