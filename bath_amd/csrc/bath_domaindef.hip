@@ -188,6 +188,7 @@ static int fs_branch_domains(bath_hip_ctx *ctx, const bath_hip_oprofile *om, con
                              const bath_fs_domain **domains, int64_t *n_domains, int64_t *n_clustered_regions, int64_t *std_clustered) {
   if (!ctx || !om || !om_fs3 || !om_fs5 || !dna || !prm || !domains || !n_domains) return BATH_EINVAL;
   if (fsprofile_codon_lengths(om_fs5) != 5) { ctx->set_error("domain definition needs the 5-codon frameshift profile"); return BATH_EINVAL; }
+  if (fs_model_ok(ctx, om_fs3) != BATH_OK || fs_model_ok(ctx, om_fs5) != BATH_OK) return BATH_EINVAL;
   *domains = nullptr; *n_domains = 0;
   if (n_clustered_regions) *n_clustered_regions = 0;
   ctx->fs_domains.clear();

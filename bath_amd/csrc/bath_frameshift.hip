@@ -1792,6 +1792,7 @@ static int fs3_parser(bath_hip_ctx *ctx, const bath_hip_fsprofile *om, const bat
                       const std::function<int()> *after_launch = nullptr /* runs between the kernel's launch and the wait for it */) {
   if (!ctx || !om || !dna || om->codon_lengths != 3) { if (ctx) ctx->set_error("fs3 parser needs a 3-codon profile"); return BATH_EINVAL; }
   BATH_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  if (fs_model_ok(ctx, om) != BATH_OK) return BATH_EINVAL;
   if (logsum_mode == BATH_LOGSUM_CONTEXT) logsum_mode = fs3_ctx_mode(ctx);
   const int64_t n = dna->n;
   if (n == 0) return BATH_OK;
@@ -2027,6 +2028,7 @@ int fs3_backward_spec(bath_hip_ctx *ctx, const bath_hip_fsprofile *om, const bat
 int fs3_regions(bath_hip_ctx *ctx, const bath_hip_fsprofile *om, const bath_hip_seqs *dna, float loop, int32_t *regions_out, float *fwd_sc_out, const int32_t *kept) {
   if (!ctx || !om || !dna || om->codon_lengths != 3) { if (ctx) ctx->set_error("fs3 parser needs a 3-codon profile"); return BATH_EINVAL; }
   BATH_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  if (fs_model_ok(ctx, om) != BATH_OK) return BATH_EINVAL;
   const int64_t n = dna->n;
   if (n == 0) return BATH_OK;
   int st = om->ensure_len(dna->maxlen / 3 + 1);
@@ -2165,6 +2167,11 @@ int fs3_forward_scores(bath_hip_ctx *ctx, const bath_hip_fsprofile *om3, const b
 }
 const float *fsprofile_evparam(const bath_hip_fsprofile *om) { return om->evparam; }
 int fsprofile_codon_lengths(const bath_hip_fsprofile *om) { return om->codon_lengths; }
+int fs_model_ok(bath_hip_ctx *ctx, const bath_hip_fsprofile *om) {
+  if (om->M <= kFsMaxNodes) return BATH_OK;
+  ctx->set_error("frameshift kernels support models up to " + std::to_string(kFsMaxNodes) + " nodes (this one has " + std::to_string(om->M) + ")");
+  return BATH_EINVAL;
+}
 }  // namespace bath
 
 extern "C" int bath_hip_fs3_forward_parser(bath_hip_ctx *ctx, const bath_hip_fsprofile *om3, const bath_hip_seqs *dna, int logsum_mode,
@@ -2196,6 +2203,7 @@ extern "C" int bath_hip_fs5_envelopes_x(bath_hip_ctx *ctx, const bath_hip_fsprof
 extern "C" int bath_hip_fs5_forward_full(bath_hip_ctx *ctx, const bath_hip_fsprofile *om, const bath_hip_seqs *dna, int cfg_len_amino,
                                          float *sc, float *fwd, float *xmx) {
   if (!ctx || !om || !dna || !sc || om->codon_lengths != 5) { if (ctx) ctx->set_error("needs a 5-codon profile"); return BATH_EINVAL; }
+  if (bath::fs_model_ok(ctx, om) != BATH_OK) return BATH_EINVAL;
   BATH_HIP_TRY(ctx, hipSetDevice(ctx->device));
   if (dna->n == 0) return BATH_OK;
   const float *h_f = nullptr, *h_x = nullptr;
@@ -2216,6 +2224,7 @@ int bath::fs5_envelopes_ex(bath_hip_ctx *ctx, const bath_hip_fsprofile *om, cons
                            const uint8_t *cons, std::vector<uint16_t> *steps, std::vector<int64_t> *step_off, std::vector<float> *step_pp) {
   if (!ctx || !om || !dna || om->codon_lengths != 5) { if (ctx) ctx->set_error("fs5 envelopes need a 5-codon profile"); return BATH_EINVAL; }
   if (logsum_mode == BATH_LOGSUM_ODDS) { ctx->set_error("the 5-codon kernels have no odds-ratio mode"); return BATH_EINVAL; }
+  if (fs_model_ok(ctx, om) != BATH_OK) return BATH_EINVAL;
   BATH_HIP_TRY(ctx, hipSetDevice(ctx->device));
   const int64_t n = dna->n;
   if (n == 0) return BATH_OK;

@@ -341,7 +341,8 @@ int bath_hip_fsprofile::ensure_odds() const {
   std::lock_guard<std::mutex> lock(odds_mu);
   if (d_odds_rsc) return BATH_OK;
   const int Cv = bath::odds_columns(M);
-  if (codon_lengths != 3 || Cv < 0) { ctx->set_error("odds-ratio mode needs a 3-codon profile of at most 1280 nodes"); return BATH_EINVAL; }
+  if (codon_lengths != 3) { ctx->set_error("odds-ratio mode needs a 3-codon profile"); return BATH_EINVAL; }
+  if (Cv < 0) return bath::fs_model_ok(ctx, this);
   const int nodes = 64 * Cv + 2, opitch = 64 * Cv + 4;
   const size_t nt = (size_t)(M + 2) * 8;
   std::vector<float> r((size_t)bath::kDegen3 * pitch), tf(nt), tb(nt);

@@ -122,6 +122,7 @@ const float *fsprofile_evparam(const bath_hip_fsprofile *om);
 int fs_max_regions();
 int fs3_regions(bath_hip_ctx *ctx, const bath_hip_fsprofile *om3, const bath_hip_seqs *dna, float loop, int32_t *regions_out, float *fwd_sc_out = nullptr, const int32_t *kept = nullptr);   // parsers + domain decoding + region heuristics (+ the Forward scores)
 int fsprofile_codon_lengths(const bath_hip_fsprofile *om);
+int fs_model_ok(bath_hip_ctx *ctx, const bath_hip_fsprofile *om);   // BATH_EINVAL with the context's error set beyond kFsMaxNodes
 int fs3_backward_spec(bath_hip_ctx *ctx, const bath_hip_fsprofile *om3, const bath_hip_seqs *dna, int k);   // speculative Backward of the k longest windows, on ctx->spec_stream
 struct FsHostTables { int M, max_length, maxcodons; const float *tsc; const uint8_t *codons; const float *evparam; };
 const FsHostTables fsprofile_host(const bath_hip_fsprofile *om);

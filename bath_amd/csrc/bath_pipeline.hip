@@ -636,10 +636,19 @@ __global__ __launch_bounds__(64) void fwd_keep_offsets_kernel(const int32_t *__r
   }
 }
 
+// The cascade's wave kernels (columns_per_lane) stop at kCascadeMaxNodes, below what an OProfile holds (the SSV tiles go to 3328
+// nodes): a longer model is refused here, before any kernel of the call runs, and not by the Viterbi stage halfway through a block.
+static int cascade_model_ok(bath_hip_ctx *ctx, const bath_hip_oprofile *om) {
+  if (om->M <= kCascadeMaxNodes) return BATH_OK;
+  ctx->set_error("the filter cascade supports models up to " + std::to_string(kCascadeMaxNodes) + " nodes (this one has " + std::to_string(om->M) + ")");
+  return BATH_EINVAL;
+}
+
 static int run_filters(bath_hip_ctx *ctx, const bath_hip_oprofile *om, const bath_hip_seqs *dna,
                        const bath_pipeline_params *prm, bath_pipeline_stats *stats,
                        const bath_orf_result **results, int64_t *n_results, FilterState *state) {
   if (!ctx || !om || !dna || !prm) return BATH_EINVAL;
+  if (cascade_model_ok(ctx, om) != BATH_OK) return BATH_EINVAL;
   BATH_HIP_TRY(ctx, hipSetDevice(ctx->device));
   if (n_results) *n_results = 0;
   if (results) *results = nullptr;
@@ -985,6 +994,7 @@ static int run_filters_lanes(bath_hip_ctx *ctx, const bath_hip_oprofile *om, con
                              const bath_pipeline_params *prm, bath_pipeline_stats *stats,
                              const bath_orf_result **results, int64_t *n_results, std::vector<FilterState> *states, After after) {
   if (!ctx || !om || !dna || !prm) return BATH_EINVAL;
+  if (cascade_model_ok(ctx, om) != BATH_OK) return BATH_EINVAL;
   const int K = pipeline_lane_count(dna);
   if (K <= 1) {
     states->assign(1, FilterState{});
@@ -1403,6 +1413,7 @@ extern "C" int bath_hip_pipeline_frameshift(bath_hip_ctx *ctx, const bath_hip_op
                                             const bath_fs_window **fs_windows, int64_t *n_fs_windows) {
   if (!ctx || !om || !om_fs3 || !dna || !prm_in || !fs_windows || !n_fs_windows) return BATH_EINVAL;
   if (fsprofile_codon_lengths(om_fs3) != 3) { ctx->set_error("the frameshift stage needs the 3-codon frameshift profile"); return BATH_EINVAL; }
+  if (fs_model_ok(ctx, om_fs3) != BATH_OK) return BATH_EINVAL;
   *fs_windows = nullptr; *n_fs_windows = 0;
   ctx->fs_windows.clear();
   if (ctx->spec_stream) BATH_HIP_TRY(ctx, hipStreamSynchronize(ctx->spec_stream));   // (a speculative Backward of the previous call that nothing waited for)

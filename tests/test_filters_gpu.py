@@ -14,7 +14,8 @@ import oracle_lib as ol
 pytestmark = pytest.mark.gpu
 
 MODELS = [("Caudal_act.bhmm", 0), ("PTH2.bhmm", 0), ("2OG-FeII_Oxy_3.bhmm", 0), ("MET-ct4.bhmm", 0), ("MET-ct4.bhmm", 1),
-          ("synthetic:1024", 0), ("synthetic:700", 0), ("synthetic:7", 0)]   # M=458: 2 lanes/target; M=1024: 4 lanes/target
+          ("synthetic:1024", 0), ("synthetic:700", 0), ("synthetic:7", 0),   # M=458: 2 lanes/target; M=1024: 4 lanes/target
+          ("synthetic:256", 0), ("synthetic:300", 0), ("synthetic:1025", 0), ("synthetic:2048", 0)]   # wave filters at 4, 6, 24 and 32 nodes per lane (C > 16: tables in global memory)
 
 
 @pytest.fixture(scope="module", params=MODELS, ids=[m[0] + "#" + str(m[1]) for m in MODELS])
@@ -187,3 +188,43 @@ def test_empty_block(gpu_ctx, setup):
     empty = ba.SeqBlock(ctx, [])
     sc, st = ba.MSVFilter(ctx, om, empty)
     assert sc.shape == (0,) and st.shape == (0,)
+
+
+SSV_BATH_COLUMNS = [1, 2, 3, 4, 6, 8, 12, 16, 24, 32, 52]
+SSV_BATH_M = [1, 65, 129, 193, 300, 512, 768, 1024, 1025, 2048, 2049, 3328]
+
+
+@pytest.mark.parametrize("M", SSV_BATH_M, ids=["C%d-M%d" % (next(c for c in SSV_BATH_COLUMNS if (m + 63) // 64 <= c), m) for m in SSV_BATH_M])
+def test_ssv_bath_windows_every_tiling(gpu_ctx, tmp_path, M):
+    """p7_SSVFilter_BATH (bath_hip_ssvfilter_bath: ssv_bath_kernel<C>, C = ceil(M / 64) rounded up to the next instantiation) at
+    every tiling, up to the 3328 nodes an OProfile holds (C = 52: beyond the cascade's 2048, only this entry point reaches it): every
+    hit window (position, node, length) and its score against the oracle's, target by target."""
+    import ctypes as C
+    path = common.write_synthetic_bhmm(str(tmp_path / ("s%d.bhmm" % M)), M, seed=M)
+    model = ol.Model(path, 0)
+    om = ba.OProfile(gpu_ctx, ba.Profile(ba.HMM(path, 0)))
+    rng = np.random.default_rng(M)
+    seqs = common.random_aa(rng, 40, 20, 400) + common.emit_from_model(rng, model, 12, sharpen=2.0) + common.emit_from_model(rng, model, 4, flank=5)
+    seqs += [np.concatenate(common.emit_from_model(rng, model, 2, sharpen=3.0)), seqs[0][:1]]
+    P = 0.02
+    w = C.POINTER(ba.HmmWindow)()
+    nw = C.c_int64(0)
+    blk = ba.SeqBlock(gpu_ctx, seqs)                 # (held: the block must outlive the call)
+    gpu_ctx._check(ba.lib().bath_hip_ssvfilter_bath(gpu_ctx._h, om._h, blk._h, C.c_double(P), C.byref(w), C.byref(nw)), "ssvfilter_bath")
+    got = {}
+    for i in range(nw.value):
+        got.setdefault(int(w[i].target), []).append((w[i].n, w[i].k, w[i].length, w[i].score))
+    L_ = ol.lib()
+    n_windows = 0
+    for t, s_ in enumerate(seqs):
+        L = len(s_)
+        L_.bo_oprofile_reconfig_length(model.om, L)
+        owl = ol.WindowList(); L_.bo_windowlist_init(C.byref(owl))
+        L_.bo_ssvfilter_bath(ol.u8(ol.dsq_from(s_)), L, model.om, model.sd, C.byref(model.bg), C.c_double(P), C.byref(owl))
+        want = [(owl.w[i].n, owl.w[i].k, owl.w[i].length, owl.w[i].score) for i in range(owl.count)]
+        L_.bo_windowlist_free(C.byref(owl))
+        g = got.get(t, [])
+        assert [x[:3] for x in g] == [x[:3] for x in want], t
+        assert all(abs(a[3] - b[3]) <= 1e-5 * max(1.0, abs(b[3])) for a, b in zip(g, want)), t
+        n_windows += len(want)
+    assert n_windows >= 10

@@ -196,11 +196,9 @@ def oa_matrices_agree(g, o, atol, rtol):
     return bool(np.all(np.abs(g - o) <= atol + rtol * np.abs(o)))
 
 
-@pytest.mark.parametrize("c5_compat", [False, True])
-@pytest.mark.parametrize("mode", [ba.LOGSUM_TABLE, ba.LOGSUM_TABLE_SERIAL], ids=["scan", "strict"])
-def test_fs5_envelopes(setup, c5_compat, mode, request):
-    ctx, model, om3, om5, wins, blk = setup
-    env = [w for w in wins if len(w) >= 15]
+def check_fs5_envelopes(ctx, model, om5, env, mode, c5_compat, name=None):
+    """FS5Envelopes on <env> against the oracle: strict scores bit-identical (scan: within 1e-4 |s| + 5e-3, errors recorded under
+    <name>), then the posteriors, the whole optimal-accuracy matrix, its score and null2 of every envelope."""
     eb = ba.SeqBlock(ctx, env)
     got = ba.FS5Envelopes(ctx, om5, eb, logsum=mode, c5_compat=c5_compat, want_pp=True, want_oa=True)
     ref = oracle_fs5(model, env, c5_compat)
@@ -209,8 +207,9 @@ def test_fs5_envelopes(setup, c5_compat, mode, request):
     if strict:                                      # row a7: p7_Forward_Frameshift / p7_Backward_Frameshift, bit for bit
         assert identical(got["fwdsc"], fwd) and identical(got["bcksc"], bwd)
     else:
-        record_errors("fs5_forward/" + request.node.callspec.id, got["fwdsc"], fwd)
-        record_errors("fs5_backward/" + request.node.callspec.id, got["bcksc"], bwd)
+        if name:
+            record_errors("fs5_forward/" + name, got["fwdsc"], fwd)
+            record_errors("fs5_backward/" + name, got["bcksc"], bwd)
         assert close(got["fwdsc"], fwd, 1e-4, 5e-3), np.abs(got["fwdsc"] - fwd).max()
         assert close(got["bcksc"], bwd, 1e-4, 5e-3), np.abs(got["bcksc"] - bwd).max()
     # strict: Forward and Backward matrices are the oracle's, so posteriors differ only by expf's last bit and the division
@@ -223,6 +222,15 @@ def test_fs5_envelopes(setup, c5_compat, mode, request):
         assert np.allclose(got["null2"][i], r[3], rtol=2e-3 if strict else 5e-3, atol=1e-4)        # null2_fs.c:193 uses 0.001..0.2; its log-sums run over column sums whose last bits differ (expf), so a table index may flip
     if not c5_compat:
         assert close(got["fwdsc"], got["bcksc"], 1e-4, 2e-2)                   # Forward == Backward
+    return got
+
+
+@pytest.mark.parametrize("c5_compat", [False, True])
+@pytest.mark.parametrize("mode", [ba.LOGSUM_TABLE, ba.LOGSUM_TABLE_SERIAL], ids=["scan", "strict"])
+def test_fs5_envelopes(setup, c5_compat, mode, request):
+    ctx, model, om3, om5, wins, blk = setup
+    env = [w for w in wins if len(w) >= 15]
+    check_fs5_envelopes(ctx, model, om5, env, mode, c5_compat, request.node.callspec.id)
 
 
 def test_fs_serial_switch_changes_nothing_but_the_order_of_the_launches(setup):
@@ -240,23 +248,17 @@ def test_fs_serial_switch_changes_nothing_but_the_order_of_the_launches(setup):
     assert all(identical(x, y) for x, y in zip(a["oa"], b["oa"]))
 
 
-def test_fs5_multihit_forward_strict_is_bit_identical(setup):
-    """p7_Forward_Frameshift in the MULTIHIT configuration of the model's saved length -- what p7_domaindef.c:411-414 runs on a
-    multi-domain region before the stochastic tracebacks -- with strict log-sums: score, the whole matrix (8 cells per node) and
-    the special-state rows must be the oracle's bit for bit, so that both sides draw the same samples."""
-    ctx, model, om3, om5, wins, blk = setup
-    env = [w for w in wins if len(w) >= 15]
+def check_fs5_forward_full(ctx, model, om5, env):
+    """bath_hip_fs5_forward_full (multihit, strict log-sums) on <env>: score, the whole matrix and the special-state rows of every
+    envelope, bit for bit against the oracle."""
     eb = ba.SeqBlock(ctx, env)
     M = model.M
     foff = np.zeros(len(env) + 1, np.int64); np.cumsum([(len(w) + 1) * (M + 1) * 8 for w in env], out=foff[1:])
     xoff = np.zeros(len(env) + 1, np.int64); np.cumsum([(len(w) + 1) * 5 for w in env], out=xoff[1:])
     sc = np.zeros(len(env), np.float32); fwd = np.zeros(int(foff[-1]), np.float32); xmx = np.zeros(int(xoff[-1]), np.float32)
     fp = lambda a: a.ctypes.data_as(C.POINTER(C.c_float))
-    ctx.set_fs_strict(True)
-    try:
-        ctx._check(ba.lib().bath_hip_fs5_forward_full(ctx._h, om5._h, eb._h, 100, fp(sc), fp(fwd), fp(xmx)), "fs5_forward_full")
-    finally:
-        ctx.set_fs_strict(False)
+    ctx.set_fs_strict(True)                         # (the library's default, which the session's context keeps: no switching back)
+    ctx._check(ba.lib().bath_hip_fs5_forward_full(ctx._h, om5._h, eb._h, 100, fp(sc), fp(fwd), fp(xmx)), "fs5_forward_full")
     L_ = ol.lib()
     gm5 = model.fs(5)
     L_.bo_fs_profile_reconfig_multihit(gm5, 100)
@@ -272,6 +274,14 @@ def test_fs5_multihit_forward_strict_is_bit_identical(setup):
         assert identical(xmx[xoff[e]:xoff[e + 1]].reshape(L + 1, 5), ox), e
         got = fwd[foff[e]:foff[e + 1]].reshape(L + 1, M + 1, 8)
         assert identical(got[1:, 1:, :], dp[1:, 1:, :]), e
+
+
+def test_fs5_multihit_forward_strict_is_bit_identical(setup):
+    """p7_Forward_Frameshift in the MULTIHIT configuration of the model's saved length -- what p7_domaindef.c:411-414 runs on a
+    multi-domain region before the stochastic tracebacks -- with strict log-sums: score, the whole matrix (8 cells per node) and
+    the special-state rows must be the oracle's bit for bit, so that both sides draw the same samples."""
+    ctx, model, om3, om5, wins, blk = setup
+    check_fs5_forward_full(ctx, model, om5, [w for w in wins if len(w) >= 15])
 
 
 def test_fs5_envelopes_with_the_multiwave_decode_oa_kernel():

@@ -136,6 +136,45 @@ def test_cascade_long_synthetic_model(gpu_ctx, tmp_path):
     assert stats.n_past_fwd > 0
 
 
+CASCADE_COLUMNS = [1, 2, 3, 4, 6, 8, 12, 16, 24, 32]
+CASCADE_M = [300, 768, 1025, 2048]
+CASCADE_MAX_NODES = 2048
+
+
+@pytest.mark.parametrize("M", CASCADE_M, ids=["C%d-M%d" % (next(c for c in CASCADE_COLUMNS if (m + 63) // 64 <= c), m) for m in CASCADE_M])
+def test_cascade_every_wave_tiling(gpu_ctx, tmp_path, M):
+    """The cascade at the tilings no other test reaches: the wave filters and ssv_bath_kernel (the SSV windows of the candidates
+    with P <= F2) at 6, 12, 24 and 32 nodes per lane.  ORF by ORF against the oracle."""
+    rng = np.random.default_rng(M)
+    path = common.write_synthetic_bhmm(str(tmp_path / ("s%d.bhmm" % M)), M, seed=M)
+    wins = make_windows(rng, ol.Model(path, 0), 30, 16, L=1500)
+    stats, res, pli, ores, per_seq, _ = run_both(gpu_ctx, path, 0, wins, False)
+    compare(stats, res, pli, ores, per_seq)
+    assert stats.n_past_fwd > 0 and stats.n_past_msv > stats.n_past_fwd
+
+
+@pytest.mark.parametrize("M", [CASCADE_MAX_NODES + 1, 3328])
+def test_cascade_refuses_models_beyond_its_wave_kernels(gpu_ctx, tmp_path, M):
+    """An OProfile holds up to 3328 nodes (the SSV tiles), the cascade's MSV / Viterbi / Forward wave kernels 2048: a longer model
+    is refused before any kernel of the call runs, with the limit in the message, and the context goes on giving the oracle's
+    results."""
+    path = common.write_synthetic_bhmm(str(tmp_path / ("s%d.bhmm" % M)), M, seed=M)
+    hmm = ba.HMM(path, 0)
+    om = ba.OProfile(gpu_ctx, ba.Profile(hmm))
+    rng = np.random.default_rng(M)
+    dna = ba.SeqBlock(gpu_ctx, common.random_dna(rng, 8, 600))
+    for fs in (False, True):
+        with pytest.raises(ba.BathError, match="up to %d nodes" % CASCADE_MAX_NODES):
+            ba.Pipeline(gpu_ctx, om, fs_pipe=fs).run(dna)
+    with pytest.raises(ba.BathError, match="up to %d nodes" % CASCADE_MAX_NODES):
+        ba.Pipeline(gpu_ctx, om).run_hits(dna)
+    path = ol.GOLDEN + "/Caudal_act.bhmm"
+    wins = make_windows(np.random.default_rng(7), ol.Model(path, 0), 40, 20)
+    stats, res, pli, ores, per_seq, _ = run_both(gpu_ctx, path, 0, wins, False)
+    compare(stats, res, pli, ores, per_seq)
+    assert stats.n_past_fwd > 0
+
+
 @pytest.mark.parametrize("lanes", [2, 3])
 def test_concurrent_lanes_give_identical_results(gpu_ctx, lanes, monkeypatch):
     """A block cut into parts that run the cascade concurrently on separate streams (bath_hip_pipeline_filters does this
