@@ -201,6 +201,7 @@ ABI = {
     "bath_hip_set_fs_strict": (C.c_int, [_vp, C.c_int]),
     "bath_hip_set_fs_serial": (C.c_int, [_vp, C.c_int]),
     "bath_hip_set_fs_odds": (C.c_int, [_vp, C.c_int]),
+    "bath_hip_set_fs5_odds": (C.c_int, [_vp, C.c_int]),
     "bath_hip_trim": (C.c_int, [_vp]),
     "bath_hip_kernel_times": (C.c_int, [_vp, C.c_int, C.POINTER(KernelTime)]),
     "bath_hip_oprofile_convert": (C.c_int, [_vp, C.POINTER(_Profile), C.POINTER(_vp)]),
@@ -456,6 +457,13 @@ class Context:
         --fs runs), and LOGSUM_CONTEXT on FS3ForwardParser / FS3BackwardParser means LOGSUM_ODDS.  False (the default): no change.
         The other frameshift stages follow set_fs_strict either way."""
         self._check(lib().bath_hip_set_fs_odds(self._h, 1 if on else 0), "set_fs_odds")
+
+    def set_fs5_odds(self, on=True):
+        """True: the 5-codon Forward and Backward of the envelopes and the regions' multihit Forward run in odds-ratio space (what
+        the reference's --fs runs there), ahead of set_fs_strict, and LOGSUM_CONTEXT on FS5Envelopes means those kernels (c5_compat
+        must be 0).  Decoding and optimal accuracy read their matrices unchanged.  False (the default): no change.  With
+        set_fs_odds(True) as well, a --fs pass runs the reference's arithmetic everywhere but decoding and optimal accuracy."""
+        self._check(lib().bath_hip_set_fs5_odds(self._h, 1 if on else 0), "set_fs5_odds")
 
     def set_fs_serial(self, on):
         """Measurement aid: the envelopes' Backward wavefront after the Forward one instead of beside it (bath_hip_set_fs_serial)."""

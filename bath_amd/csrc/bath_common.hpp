@@ -195,6 +195,7 @@ struct bath_hip_ctx {
   hipDeviceProp_t prop{};
   int fs_strict = 1;                    // frameshift log-sums along the model in the reference's serial order (bit-identical); bath_hip_set_fs_strict(ctx, 0): wavefront scans
   int fs_odds = 0;                      // bath_hip_set_fs_odds(ctx, 1): the 3-codon parsers of the pipeline in odds-ratio space (BATH_LOGSUM_ODDS)
+  int fs5_odds = 0;                     // bath_hip_set_fs5_odds(ctx, 1): the 5-codon Forward / Backward (envelopes, regions) in odds-ratio space
   int fs_serial = -1;                   // envelopes' Backward after Forward on one stream instead of beside it (timing probes); -1: BATH_HIP_FS_SERIAL decides
   uint64_t tabs_uid = 0;                // whose SSV score table sits in scratch[8] (bath_pipeline.hip: uploaded once per profile, not per call)
   const void *tabs_ptr = nullptr;

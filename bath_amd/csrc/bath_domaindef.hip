@@ -417,7 +417,7 @@ static int fs_branch_domains(bath_hip_ctx *ctx, const bath_hip_oprofile *om, con
         }
       }
       rctx = ctx->fs_strict ? ctx->aux2 : ctx;
-      if (rctx != ctx) { rctx->fs_strict = ctx->fs_strict; rctx->fs_odds = ctx->fs_odds; rctx->spans_reset(); }
+      if (rctx != ctx) { rctx->fs_strict = ctx->fs_strict; rctx->fs_odds = ctx->fs_odds; rctx->fs5_odds = ctx->fs5_odds; rctx->spans_reset(); }
       bath_hip_seqs view;
       if ((st = fs_gather_view(rctx, dna, rregs, tt.comp, &view, nullptr)) != BATH_OK) { if (rctx != ctx) ctx->set_error(rctx->err); return st; }
       // returns after the launch: a region's ensemble starts as soon as ITS matrix has landed in host memory (h_done[e]), so the
@@ -461,7 +461,7 @@ static int fs_branch_domains(bath_hip_ctx *ctx, const bath_hip_oprofile *om, con
         if (own_ctx) {
           if (!ctx->aux3 && bath_hip_init(ctx->device, &ctx->aux3) != BATH_OK) { cl_rc = BATH_EFAIL; cl_err = "cannot create the context of the clusters' envelopes"; return; }
           mark_internal(ctx->aux3);
-          cctx = ctx->aux3; cctx->fs_strict = ctx->fs_strict; cctx->fs_odds = ctx->fs_odds; cctx->spans_reset();
+          cctx = ctx->aux3; cctx->fs_strict = ctx->fs_strict; cctx->fs_odds = ctx->fs_odds; cctx->fs5_odds = ctx->fs5_odds; cctx->spans_reset();
         } else if (hipStreamSynchronize(rctx->stream) != hipSuccess) { cl_rc = BATH_EFAIL; cl_err = "the regions' stream failed"; return; }
         for (size_t e = 0; e < mregs.size(); e++) cl_envs.insert(cl_envs.end(), found[e].begin(), found[e].end());
         if (!cl_envs.empty() && (cl_rc = run_env_batch(cctx, cl_envs.data(), (int)cl_envs.size(), cl_batch)) != BATH_OK) cl_err = cctx->err;

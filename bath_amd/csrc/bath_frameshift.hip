@@ -2255,6 +2255,10 @@ int bath::fs5_envelopes_ex(bath_hip_ctx *ctx, const bath_hip_fsprofile *om, cons
   const int Cv = fs_columns(M);
   const size_t oa_shmem = (size_t)(M + 2) * 8 * sizeof(float);
   [[maybe_unused]] const int grid = fs_grid(ctx, n);
+  // BATH_LOGSUM_CONTEXT: the odds-ratio kernels while bath_hip_set_fs5_odds is on (before fs_strict), else strict / fast
+  const bool odds5 = logsum_mode == BATH_LOGSUM_CONTEXT && ctx->fs5_odds;
+  if (odds5 && c5_compat) { ctx->set_error("the 5-codon odds-ratio mode implements c5_compat = 0 only (fwdback_fs.c:1464)"); return BATH_EINVAL; }
+  if (odds5 && (st = om->ensure_odds()) != BATH_OK) return st;                  // (the first call builds the tables: before the streams fork)
   if (logsum_mode == BATH_LOGSUM_CONTEXT) logsum_mode = ctx->fs_strict ? BATH_LOGSUM_TABLE_SERIAL : BATH_LOGSUM_TABLE;
   const double cells5 = (double)(foff[(size_t)n] / 8);                          // (L+1) x (M+1) cells of all envelopes
   // The posterior matrix (32 B per cell) is written only when the caller wants it back (<pp>) or the unfused A/B kernels run: the
@@ -2276,14 +2280,19 @@ int bath::fs5_envelopes_ex(bath_hip_ctx *ctx, const bath_hip_fsprofile *om, cons
       // Forward and Backward: the row-per-lane wavefronts (bath_fs_wavefront.hip), the reference's order of every sum, in EVERY mode --
       // the unihit recursion has no sum that a scan could shorten, so the fast mode's envelopes are the strict ones (the node-per-lane
       // scan kernels this replaced in fast mode were 13 times slower at 1024 nodes and are gone)
-      const int s1 = ctx->span_begin("fs5_fwd_kernel", ctx->stream, cells5, cells5 * 32.0);
-      if ((st = launch_fs5_fwd_wf(ctx, ctx->stream, om, dna, MD == 1, c5_compat, d_fsc, b_f.as<float>(), d_foff, b_fx.as<float>(), d_xoff, ctx->scratch[41], jq[0])) != BATH_OK) return st;
+      // (odds5: the odds-ratio kernels of bath_fs5_odds.hip, node per lane; Backward with scales of its own, so still beside Forward)
+      const int s1 = ctx->span_begin(odds5 ? "fs5_fwd_odds_kernel" : "fs5_fwd_kernel", ctx->stream, cells5, cells5 * 32.0);
+      if (odds5) st = launch_fs5_odds(ctx, ctx->stream, om, dna, kFs5OddsEnvFwd, d_fsc, b_f.as<float>(), d_foff, b_fx.as<float>(), d_xoff, -1, jq[0], nullptr);
+      else st = launch_fs5_fwd_wf(ctx, ctx->stream, om, dna, MD == 1, c5_compat, d_fsc, b_f.as<float>(), d_foff, b_fx.as<float>(), d_xoff, ctx->scratch[41], jq[0]);
+      if (st != BATH_OK) return st;
       ctx->span_end(s1, ctx->stream);
       static const bool serial_env = [] { const char *e = std::getenv("BATH_HIP_FS_SERIAL"); return e && e[0] == '1'; }();   // timing probes: Backward after Forward
       const bool serial = ctx->fs_serial >= 0 ? ctx->fs_serial != 0 : serial_env;                                           // (bath_hip_set_fs_serial)
       hipStream_t bs = serial ? ctx->stream : ctx->side_stream;
-      const int s2 = ctx->span_begin("fs_bwd_kernel<5>", bs, cells5, cells5 * 12.0);
-      if ((st = launch_fs5_bwd_wf(ctx, bs, om, dna, MD == 1, d_bsc, b_b.as<float>(), d_boff, b_bx.as<float>(), d_xoff, ctx->scratch[42], ctx->scratch[43], ctx->scratch[44], jq[1], jq[3])) != BATH_OK) return st;
+      const int s2 = ctx->span_begin(odds5 ? "fs5_bwd_odds_kernel" : "fs_bwd_kernel<5>", bs, cells5, cells5 * 12.0);
+      if (odds5) st = launch_fs5_odds(ctx, bs, om, dna, kFs5OddsEnvBwd, d_bsc, b_b.as<float>(), d_boff, b_bx.as<float>(), d_xoff, -1, jq[1], nullptr);
+      else st = launch_fs5_bwd_wf(ctx, bs, om, dna, MD == 1, d_bsc, b_b.as<float>(), d_boff, b_bx.as<float>(), d_xoff, ctx->scratch[42], ctx->scratch[43], ctx->scratch[44], jq[1], jq[3]);
+      if (st != BATH_OK) return st;
       ctx->span_end(s2, bs);
     })
     if ((st = fs_join(ctx)) != BATH_OK) return st;
@@ -2445,7 +2454,11 @@ int bath::fs5_region_forward(bath_hip_ctx *ctx, const bath_hip_fsprofile *om, co
   const int mode = ctx->fs_strict ? BATH_LOGSUM_TABLE_SERIAL : BATH_LOGSUM_TABLE;
   FsJobs jq[1];
   if ((st = fs_schedule(ctx, dna, 1, jq)) != BATH_OK) return st;
-  if (mode == BATH_LOGSUM_TABLE_SERIAL && fs_chain_enabled()) {
+  if (ctx->fs5_odds) {                                                         // bath_hip_set_fs5_odds: before fs_strict
+    const int s1 = ctx->span_begin("fs5_fwd_odds_kernel(regions)", ctx->stream, (double)(foff[(size_t)n] / 8), (double)(foff[(size_t)n] / 8) * 32.0);
+    if ((st = launch_fs5_odds(ctx, ctx->stream, om, dna, kFs5OddsRegionFwd, d_sc_out, d_f, d_foff, d_fx, d_xoff, cfg_len_amino, jq[0], d_done)) != BATH_OK) return st;
+    ctx->span_end(s1, ctx->stream);
+  } else if (mode == BATH_LOGSUM_TABLE_SERIAL && fs_chain_enabled()) {
     const int s1 = ctx->span_begin("fs5_fwd_kernel(regions)", ctx->stream, (double)(foff[(size_t)n] / 8), (double)(foff[(size_t)n] / 8) * 32.0);
     if ((st = launch_fs5_fwd_chain(ctx, ctx->stream, om, dna, Cv, tE, tE, 0, d_sc_out, d_f, d_foff, d_fx, d_xoff, cfg_len_amino, jq[0], d_done)) != BATH_OK) return st;
     ctx->span_end(s1, ctx->stream);

@@ -1,5 +1,5 @@
-// bath_fs_device.hpp -- device helpers shared by the frameshift kernels (bath_frameshift.hip, bath_fs_wavefront.hip):
-// p7_FLogsum with its table in LDS (logsum.c:105), DPP lane moves, the longest-first job queue, the device profile.
+// bath_fs_device.hpp -- device helpers shared by the frameshift kernels (bath_frameshift.hip, bath_fs_wavefront.hip, the odds-ratio
+// kernels): p7_FLogsum with its table in LDS (logsum.c:105), DPP lane moves and scans, the longest-first job queue, the device profile.
 #pragma once
 #include <algorithm>
 #include <vector>
@@ -33,10 +33,10 @@ struct bath_hip_fsprofile {
   mutable std::mutex grow_mu;
   mutable std::vector<void *> retired;
   int ensure_len(int maxL_amino) const;
-  // odds-ratio tables of a 3-codon profile (BATH_LOGSUM_ODDS, bath_fs_odds.hip): expf of d_rsc's codon rows, d_tf and d_tb, padded
-  // to the nodes of every lane, built on the first odds-mode call
+  // odds-ratio tables (BATH_LOGSUM_ODDS, bath_fs_odds.hip; the 5-codon odds mode, bath_fs5_odds.hip): expf of d_rsc's codon rows,
+  // d_tf and d_tb, padded to the nodes of every lane, built on the first odds-mode call
   mutable float *d_odds_rsc = nullptr, *d_odds_tf = nullptr, *d_odds_tb = nullptr;
-  mutable int odds_pitch = 0;    // floats per odds emission row
+  mutable int odds_pitch = 0;    // floats per odds emission row; node k sits at column k (3-codon) or k-1 (5-codon: 16-byte aligned lane blocks)
   mutable std::mutex odds_mu;
   int ensure_odds() const;
 };
@@ -138,6 +138,46 @@ __device__ __forceinline__ float wave_logsum(float v, const float *tbl) {
 
 __device__ __forceinline__ int imin(int a, int b) { return a < b ? a : b; }
 
+// ---- shared by the odds-ratio kernels (bath_fs_odds.hip, bath_fs5_odds.hip)
+constexpr float kOddsRescale = 1.0e4f;   // fwdback_fs.c:472: every value a later row reads is rescaled when E(i) (Backward: B(i)) passes it
+
+// x -> m x + a composed over the lanes below (DPP row_shr 1/2/4/8, row_bcast 15/31: the scan of d_chain_fwd); returns the
+// composition's offset EXCLUSIVE of this lane: the value entering the lane's first node when the chain starts at 0.
+// Lanes without a source see the identity map (m = 1, a = 0).
+__device__ __forceinline__ float affine_scan_excl(float m, float a) {
+#define BATH_ODDS_STEP(CTRL, MASK) { const float mp = dpp_f<CTRL, MASK>(m, 1.f), ap = dpp_f<CTRL, MASK>(a, 0.f); a = a + m * ap; m = m * mp; }
+  BATH_ODDS_STEP(0x111, 0xf) BATH_ODDS_STEP(0x112, 0xf) BATH_ODDS_STEP(0x114, 0xf) BATH_ODDS_STEP(0x118, 0xf)
+  BATH_ODDS_STEP(0x142, 0xa) BATH_ODDS_STEP(0x143, 0xc)
+#undef BATH_ODDS_STEP
+  return wave_shr1(a, 0.f);
+}
+
+// sum of a value per lane, in every lane
+__device__ __forceinline__ float wave_sum(float v) {
+  v = v + dpp_f<0x111>(v, 0.f);
+  v = v + dpp_f<0x112>(v, 0.f);
+  v = v + dpp_f<0x114>(v, 0.f);
+  v = v + dpp_f<0x118>(v, 0.f);
+  v = v + dpp_f<0x142, 0xa>(v, 0.f);
+  v = v + dpp_f<0x143, 0xc>(v, 0.f);
+  return wave_bcast_last(v);
+}
+
+// the transition rows are read again every row, from L1: held in registers across the row loop (where the compiler hoists them
+// to) they take 8 C VGPRs, which halves the waves per SIMD at C = 4 and spills from C = 16 on.  The empty asm makes the pointer
+// opaque to that hoisting.
+__device__ __forceinline__ const float *per_row(const float *p) {
+  asm volatile("" : "+s"(p));
+  return p;
+}
+
+// row i of the special-state matrix, log value + running scale (logf(0) = -inf)
+__device__ __forceinline__ void put_row(float *xo, int i, float E, float N, float J, float B, float Cc, double ts) {
+  const float s = (float)ts;
+  xo[i * 5 + 0] = logf(E) + s; xo[i * 5 + 1] = logf(N) + s; xo[i * 5 + 2] = logf(J) + s; xo[i * 5 + 3] = logf(B) + s; xo[i * 5 + 4] = logf(Cc) + s;
+}
+
+
 // Work distribution of the wave-per-window kernels.  Their duration is the longest chain of rows any one wave walks, so the
 // windows are handed out longest first from a shared counter (<order> lists them by decreasing length): a wave that drew a
 // long window early draws fewer later, instead of every wave taking windows wid, wid + nwaves, ... whatever their lengths.
@@ -201,6 +241,10 @@ int launch_fs5_fwd_chain(bath_hip_ctx *ctx, hipStream_t stream, const bath_hip_f
 // ---- the 3-codon parsers in odds-ratio space (bath_fs_odds.hip)
 int launch_fs3_odds(bath_hip_ctx *ctx, hipStream_t stream, const bath_hip_fsprofile *om, const bath_hip_seqs *dna, bool backward,
                     float *d_sc, float *d_xmx, const int64_t *d_xoff, FsJobs jobs);
+// ---- the 5-codon Forward (envelopes: unihit; regions: multihit) and Backward (envelopes) in odds-ratio space (bath_fs5_odds.hip)
+enum Fs5OddsKind { kFs5OddsEnvFwd = 0, kFs5OddsEnvBwd = 1, kFs5OddsRegionFwd = 2 };
+int launch_fs5_odds(bath_hip_ctx *ctx, hipStream_t stream, const bath_hip_fsprofile *om, const bath_hip_seqs *dna, Fs5OddsKind kind,
+                    float *d_sc, float *d_mx, const int64_t *d_moff, float *d_xmx, const int64_t *d_xoff, int cfg_len, FsJobs jobs, int *d_done);
 inline bool fs_chain_enabled() { static const bool off = [] { const char *e = std::getenv("BATH_HIP_FS_HANDOFF"); return e && e[0] == '1'; }(); return !off; }   // BATH_HIP_FS_HANDOFF=1: the 64-step lane hand-off kernels, for A/B runs
 
 }  // namespace bath

@@ -36,46 +36,9 @@ namespace bath {
 
 constexpr int kOddsBlock = 256;          // 4 waves, one window each; nothing is shared inside a block
 constexpr int kDegen3 = 338;             // p7P_MAXCODONS3: marks a degenerate nucleotide (rows 336 / 337 are the degenerate codons)
-constexpr float kRescale = 1.0e4f;       // fwdback_fs.c:472
-
-// x -> m x + a composed over the lanes below (DPP row_shr 1/2/4/8, row_bcast 15/31: the scan of d_chain_fwd); returns the
-// composition's offset EXCLUSIVE of this lane: the value entering the lane's first node when the chain starts at 0.
-// Lanes without a source see the identity map (m = 1, a = 0).
-__device__ __forceinline__ float affine_scan_excl(float m, float a) {
-#define BATH_ODDS_STEP(CTRL, MASK) { const float mp = dpp_f<CTRL, MASK>(m, 1.f), ap = dpp_f<CTRL, MASK>(a, 0.f); a = a + m * ap; m = m * mp; }
-  BATH_ODDS_STEP(0x111, 0xf) BATH_ODDS_STEP(0x112, 0xf) BATH_ODDS_STEP(0x114, 0xf) BATH_ODDS_STEP(0x118, 0xf)
-  BATH_ODDS_STEP(0x142, 0xa) BATH_ODDS_STEP(0x143, 0xc)
-#undef BATH_ODDS_STEP
-  return wave_shr1(a, 0.f);
-}
-
-// sum of a value per lane, in every lane
-__device__ __forceinline__ float wave_sum(float v) {
-  v = v + dpp_f<0x111>(v, 0.f);
-  v = v + dpp_f<0x112>(v, 0.f);
-  v = v + dpp_f<0x114>(v, 0.f);
-  v = v + dpp_f<0x118>(v, 0.f);
-  v = v + dpp_f<0x142, 0xa>(v, 0.f);
-  v = v + dpp_f<0x143, 0xc>(v, 0.f);
-  return wave_bcast_last(v);
-}
-
-// the transition rows are read again every row, from L1: held in registers across the row loop (where the compiler hoists them
-// to) they take 8 C VGPRs, which halves the waves per SIMD at C = 4 and spills from C = 16 on.  The empty asm makes the pointer
-// opaque to that hoisting.
-__device__ __forceinline__ const float *per_row(const float *p) {
-  asm volatile("" : "+s"(p));
-  return p;
-}
 
 // (wave-uniform: the emission rows' addresses stay in scalar registers)
 __device__ __forceinline__ int nuc3(uint8_t c) { return __builtin_amdgcn_readfirstlane(c < 4 ? (int)c : kDegen3); }
-
-// row i of the special-state matrix, log value + running scale (logf(0) = -inf)
-__device__ __forceinline__ void put_row(float *xo, int i, float E, float N, float J, float B, float Cc, double ts) {
-  const float s = (float)ts;
-  xo[i * 5 + 0] = logf(E) + s; xo[i * 5 + 1] = logf(N) + s; xo[i * 5 + 2] = logf(J) + s; xo[i * 5 + 3] = logf(B) + s; xo[i * 5 + 4] = logf(Cc) + s;
-}
 
 // The tables cover every node a lane of the C-column kernel owns, 1 .. 64 C, with zeros beyond M: a lane's loads are one vector
 // offset plus immediates, and nodes beyond M come out 0 without a branch or a clamp.
@@ -168,7 +131,7 @@ __global__ __launch_bounds__(kOddsBlock) void fs3_fwd_odds_kernel(SeqView dna, F
       if (i == 2) { nN = 1.f; nJ = xE * tEL; nC = xE * tEM; }
       else { nN = xN[2] * tNL; nJ = xJ[2] * tJL + xE * tEL; nC = xC[2] * tCL + xE * tEM; }
       float nB = nN * tNM + nJ * tJM;
-      if (xE > kRescale) {                                   // wave-uniform
+      if (xE > kOddsRescale) {                                   // wave-uniform
         const float f = 1.0f / xE;
 #pragma unroll
         for (int c = 0; c < C; c++) {
@@ -290,7 +253,7 @@ __global__ __launch_bounds__(kOddsBlock) void fs3_bwd_odds_kernel(SeqView dna, F
         dn = dn * tdd[c] + bd[c];
         Dc[c] = dn;
       }
-      if (xB > kRescale) {                                   // wave-uniform
+      if (xB > kOddsRescale) {                                   // wave-uniform
         const float f = 1.0f / xB;
 #pragma unroll
         for (int c = 0; c < C; c++) {
@@ -341,17 +304,20 @@ int bath_hip_fsprofile::ensure_odds() const {
   std::lock_guard<std::mutex> lock(odds_mu);
   if (d_odds_rsc) return BATH_OK;
   const int Cv = bath::odds_columns(M);
-  if (codon_lengths != 3) { ctx->set_error("odds-ratio mode needs a 3-codon profile"); return BATH_EINVAL; }
+  if (codon_lengths != 3 && codon_lengths != 5) { ctx->set_error("odds-ratio mode needs a 3- or 5-codon profile"); return BATH_EINVAL; }
   if (Cv < 0) return bath::fs_model_ok(ctx, this);
   const int nodes = 64 * Cv + 2, opitch = 64 * Cv + 4;
+  // every codon, quasi-codon and degenerate row the kernels index (p7P_MAXCODONS3 / p7P_MAXCODONS5); the 5-codon kernels read node k
+  // at column k-1, so that a lane's C nodes start on a 16-byte boundary when 4 divides C
+  const int nrows = codon_lengths == 5 ? 1367 : bath::kDegen3, col0 = codon_lengths == 5 ? 1 : 0;
   const size_t nt = (size_t)(M + 2) * 8;
-  std::vector<float> r((size_t)bath::kDegen3 * pitch), tf(nt), tb(nt);
+  std::vector<float> r((size_t)nrows * pitch), tf(nt), tb(nt);
   BATH_HIP_TRY(ctx, hipMemcpy(r.data(), d_rsc, r.size() * sizeof(float), hipMemcpyDeviceToHost));
   BATH_HIP_TRY(ctx, hipMemcpy(tf.data(), d_tf, nt * sizeof(float), hipMemcpyDeviceToHost));
   BATH_HIP_TRY(ctx, hipMemcpy(tb.data(), d_tb, nt * sizeof(float), hipMemcpyDeviceToHost));
-  std::vector<float> ro((size_t)bath::kDegen3 * opitch, 0.f), tfo((size_t)nodes * 8, 0.f), tbo((size_t)nodes * 8, 0.f);
-  for (int row = 0; row < bath::kDegen3; row++)
-    for (int k = 1; k <= M; k++) ro[(size_t)row * opitch + k] = std::exp(r[(size_t)row * pitch + k]);      // exp(-inf) = 0
+  std::vector<float> ro((size_t)nrows * opitch, 0.f), tfo((size_t)nodes * 8, 0.f), tbo((size_t)nodes * 8, 0.f);
+  for (int row = 0; row < nrows; row++)
+    for (int k = 1; k <= M; k++) ro[(size_t)row * opitch + k - col0] = std::exp(r[(size_t)row * pitch + k]);      // exp(-inf) = 0
   for (size_t a = 8; a < (size_t)(M + 1) * 8; a++) { tfo[a] = std::exp(tf[a]); tbo[a] = std::exp(tb[a]); }
   float *dr = nullptr, *dtf = nullptr, *dtb = nullptr;
   BATH_HIP_TRY(ctx, hipMalloc((void **)&dr, ro.size() * sizeof(float) + 64));

@@ -1029,7 +1029,7 @@ static int run_filters_lanes(bath_hip_ctx *ctx, const bath_hip_oprofile *om, con
     }
     ctx->lanes.push_back(lane);
   }
-  for (bath_hip_ctx *lane : ctx->lanes) { lane->fs_strict = ctx->fs_strict; lane->fs_odds = ctx->fs_odds; }
+  for (bath_hip_ctx *lane : ctx->lanes) { lane->fs_strict = ctx->fs_strict; lane->fs_odds = ctx->fs_odds; lane->fs5_odds = ctx->fs5_odds; }
   if ((st = ensure_parts(ctx, dna, K)) != BATH_OK) return st;
   std::vector<bath_pipeline_stats> pst((size_t)K);
   std::vector<const bath_orf_result *> pres((size_t)K, nullptr);

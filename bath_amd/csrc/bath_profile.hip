@@ -245,6 +245,13 @@ extern "C" int bath_hip_set_fs_odds(bath_hip_ctx *ctx, int on) {
   return BATH_OK;
 }
 
+extern "C" int bath_hip_set_fs5_odds(bath_hip_ctx *ctx, int on) {
+  if (!ctx) return BATH_EINVAL;
+  ctx->fs5_odds = on ? 1 : 0;
+  for (bath_hip_ctx *l : ctx->lanes) l->fs5_odds = ctx->fs5_odds;
+  return BATH_OK;
+}
+
 // ------------------------------------------------------------------------------------------ oprofile
 
 extern "C" void bath_hip_oprofile_destroy(bath_hip_oprofile *om) {

@@ -130,6 +130,17 @@ int         bath_hip_set_fs_strict(bath_hip_ctx *ctx, int on);
  * every other stage (envelopes, the regions' Forward, decoding, optimal accuracy) runs as bath_hip_set_fs_strict selects.
  * 0 (the default): no change.  The first odds-mode call for a 3-codon profile builds its odds-ratio tables on the device. */
 int         bath_hip_set_fs_odds(bath_hip_ctx *ctx, int on);
+/* Odds-ratio mode of the 5-codon Forward and Backward.  1: the envelopes' Forward and Backward (bath_hip_fs5_envelopes[_x] with
+ * BATH_LOGSUM_CONTEXT, the pipeline's envelope batches) and the regions' multihit Forward (the domain stage, bath_hip_fs5_forward_full)
+ * run in fp32 odds ratios with sparse rescaling, as the reference's p7_Forward_Frameshift / p7_Backward_Frameshift (impl_sse/
+ * fwdback_fs.c:2054, :2634); it takes precedence over bath_hip_set_fs_strict for these stages.  Decoding, optimal accuracy, null2 and
+ * the traces read the matrices as before (log value + the running scale).  c5_compat = 1 is refused (BATH_EINVAL) while it is on.
+ * Contract: scores within 1e-3 + 1e-4 |s| nats of EXACT log-space arithmetic, matrix cells and special-state rows within 2e-3 +
+ * 2e-4 |v| where the exact value is above -60 and within 60 nats of its row's largest; values about 87 nats below the running scale
+ * flush to zero in fp32 and come back as -inf.  NOT bit-identical to strict: a domain at a threshold may move.
+ * 0 (the default): no change.  An explicit BATH_LOGSUM_ODDS on the fs5 entry points stays refused.  The reference's whole --fs
+ * arithmetic is bath_hip_set_fs_odds(ctx, 1) plus bath_hip_set_fs5_odds(ctx, 1).  A null ctx returns BATH_EINVAL. */
+int         bath_hip_set_fs5_odds(bath_hip_ctx *ctx, int on);
 /* Measurement aid: 1 = the envelope stage (bath_hip_fs5_envelopes and the domain stage's batches) runs its Backward wavefront AFTER the
  * Forward wavefront on the same stream instead of beside it, so that a kernel's HIP-event span is its time alone on the chip
  * (bench.py: fs.roofline.alone); 0 = side by side (the default); -1 = whatever BATH_HIP_FS_SERIAL says.  Results do not change. */
@@ -561,7 +572,8 @@ int     bath_dist_deal(const double *costs, int64_t n_items, int world, int32_t 
 #define BATH_LOGSUM_EXACT 1   /* exact log(1+exp(x))                                            */
 #define BATH_LOGSUM_TABLE_SERIAL 2 /* the table, sums along the model in the reference's serial order: bit-identical to generic_fwdback_frameshift.c */
 #define BATH_LOGSUM_CONTEXT 3 /* whatever bath_hip_set_fs_strict selected for the context: TABLE_SERIAL unless switched to the fast mode
-                                 (fs3 entry points: ODDS when bath_hip_set_fs_odds switched it on) */
+                                 (fs3 entry points: ODDS when bath_hip_set_fs_odds switched it on; fs5 entry points: the
+                                 5-codon odds-ratio kernels when bath_hip_set_fs5_odds switched them on) */
 /* BATH_LOGSUM_ODDS (3-codon parsers only; the fs5 entry points answer BATH_EINVAL): what the reference's bathsearch --fs runs,
  * p7_{Forward,Backward}Parser_Frameshift_3Codons (impl_sse/fwdback_fs.c:97, :565) -- the recursion in fp32 odds ratios (expf of the
  * profile's scores), no log-sum table, every value of the recursion rescaled together when E(i) (Backward: B(i)) passes 1e4.
