@@ -220,6 +220,18 @@ ABI = {
     "bath_hip_seqs_create_packed": (C.c_int, [_vp, _i64p, C.c_int64, C.POINTER(_vp)]),
     "bath_hip_seqs_upload_packed": (C.c_int, [_vp, C.c_void_p, _i64p, _i32p, _u8p, C.c_int64]),
     "bath_hip_seqs_upload_wait": (C.c_int, [_vp]),
+    "bath_hip_fasta_create": (C.c_int, [_vp, C.POINTER(_vp)]),
+    "bath_hip_fasta_destroy": (None, [_vp]),
+    "bath_hip_fasta_feed": (C.c_int, [_vp, C.c_void_p, C.c_int64]),
+    "bath_hip_fasta_finish": (C.c_int, [_vp]),
+    "bath_hip_fasta_count": (C.c_int64, [_vp]),
+    "bath_hip_fasta_symbols": (C.c_int64, [_vp]),
+    "bath_hip_fasta_records": (C.c_int, [_vp, C.c_int64, C.c_int64, C.c_void_p]),
+    "bath_hip_fasta_error": (C.c_int, [_vp, _i64p, _i64p, _i64p, _i32p]),
+    "bath_hip_fasta_windows": (C.c_int64, [_vp, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_int64]),
+    "bath_hip_fasta_seqs": (C.c_int, [_vp, C.c_void_p, C.c_int64, C.POINTER(_vp)]),
+    "bath_hip_fasta_codes": (C.c_int, [_vp, C.c_int64, C.c_int64, C.c_int64, _u8p]),
+    "bath_hip_fasta_release": (C.c_int, [_vp, C.c_int64]),
     "bath_hip_ssvfilter": (C.c_int, [_vp, _vp, _vp, _f32p, _i32p]),
     "bath_hip_msvfilter": (C.c_int, [_vp, _vp, _vp, _f32p, _i32p]),
     "bath_hip_vitfilter": (C.c_int, [_vp, _vp, _vp, _f32p, _i32p]),
@@ -633,6 +645,131 @@ class StreamedBlock(SeqBlock):
     def wait(self):
         """Order the cascade after the upload and expand the block on the device."""
         self.ctx._check(lib().bath_hip_seqs_upload_wait(self._h), "seqs_upload_wait")
+
+
+FASTA_RECORD_DTYPE = np.dtype([("hdr_begin", "<i8"), ("hdr_end", "<i8"), ("sym_start", "<i8"), ("length", "<i8")])   # bath_fasta_record
+FASTA_WINDOW_DTYPE = np.dtype([("target", "<i8"), ("start0", "<i8"), ("n", "<i4"), ("context", "<i4")])             # bath_fasta_window
+
+
+class FastaFormatError(BathError):
+    """A byte the FASTA rules do not allow: .offset (in the file), .line (1-based), .record (0-based; -1: before the first header)."""
+
+    def __init__(self, msg, offset, line, record, byte):
+        super().__init__(msg)
+        self.offset, self.line, self.record, self.byte = offset, line, record, byte
+
+
+class FastaTargets:
+    """The targets of a FASTA file parsed and digitised on the device (bath_hip_fasta_*): feed() the file's bytes in chunks of any
+    size (page-locked ones upload asynchronously), finish(), then records() / windows() / seqs() / codes().  The codes of every
+    record stay in device memory until release()."""
+
+    def __init__(self, ctx):
+        h = _vp()
+        ctx._check(lib().bath_hip_fasta_create(ctx._h, C.byref(h)), "fasta_create")
+        self.ctx, self._h, self.nbytes = ctx, h, 0
+        self._recs = None
+
+    def feed(self, buf, n=None):
+        """The next bytes of the file: a PinnedBuffer (its first <n> bytes), bytes or a uint8 array."""
+        if isinstance(buf, PinnedBuffer):
+            ptr, n = buf.ptr, int(buf.array.size if n is None else n)
+        else:
+            arr = np.frombuffer(buf, dtype=np.uint8) if isinstance(buf, (bytes, bytearray, memoryview)) else np.ascontiguousarray(buf, dtype=np.uint8)
+            arr = arr[:n] if n is not None else arr
+            ptr, n = arr.ctypes.data, int(arr.size)
+        if n == 0:
+            return
+        st = lib().bath_hip_fasta_feed(self._h, ptr, n)
+        self.nbytes += n
+        self._recs = None
+        if st != OK:
+            self._raise(st, "fasta_feed")
+
+    def _raise(self, st, what):
+        off, line, rec, byte = C.c_int64(0), C.c_int64(0), C.c_int64(0), C.c_int32(0)
+        if lib().bath_hip_fasta_error(self._h, C.byref(off), C.byref(line), C.byref(rec), C.byref(byte)) == OK:
+            if rec.value < 0:
+                msg = "FASTA format error, line %d: sequence data before the first header" % line.value
+            else:
+                msg = "FASTA format error, line %d: illegal character %r in record %d" % (line.value, chr(byte.value), rec.value + 1)
+            raise FastaFormatError(msg, off.value, line.value, rec.value, byte.value)
+        self.ctx._check(st, what)
+
+    def finish(self):
+        st = lib().bath_hip_fasta_finish(self._h)
+        self._recs = None
+        if st != OK:
+            self._raise(st, "fasta_finish")
+
+    def __len__(self):
+        return int(lib().bath_hip_fasta_count(self._h))
+
+    def records(self):
+        """The record table (FASTA_RECORD_DTYPE): header byte range in the file, first symbol, length."""
+        if self._recs is None:
+            n = len(self)
+            out = np.zeros(n, dtype=FASTA_RECORD_DTYPE)
+            if n:
+                self.ctx._check(lib().bath_hip_fasta_records(self._h, 0, n, out.ctypes.data), "fasta_records")
+            self._recs = out
+        return self._recs
+
+    @property
+    def lengths(self):
+        return self.records()["length"].copy()
+
+    def windows(self, max_length, block_length, lo=0, hi=None):
+        """The windows of records [lo, hi) (FASTA_WINDOW_DTYPE), as dist.split_targets lists them."""
+        hi = len(self) if hi is None else hi
+        n = lib().bath_hip_fasta_windows(self._h, lo, hi, int(max_length), int(block_length), None, 0)
+        if n < 0:
+            raise BathError("fasta_windows failed: %s" % lib().bath_hip_last_error(self.ctx._h).decode())
+        out = np.zeros(n, dtype=FASTA_WINDOW_DTYPE)
+        if n:
+            lib().bath_hip_fasta_windows(self._h, lo, hi, int(max_length), int(block_length), out.ctypes.data, n)
+        return out
+
+    def seqs(self, windows):
+        """A SeqBlock of the given windows (laid out by the device, contexts set)."""
+        w = np.ascontiguousarray(windows, dtype=FASTA_WINDOW_DTYPE)
+        h = _vp()
+        self.ctx._check(lib().bath_hip_fasta_seqs(self._h, w.ctypes.data if len(w) else None, len(w), C.byref(h)), "fasta_seqs")
+        blk = SeqBlock.__new__(SeqBlock)
+        blk.ctx, blk._h, blk.n = self.ctx, h, len(w)
+        blk.lengths = w["n"].astype(np.int64)
+        return blk
+
+    def codes(self, target, start=0, n=None):
+        """Codes [start, start + n) of a record, copied to the host."""
+        if n is None:
+            n = int(self.records()["length"][target]) - start
+        out = np.zeros(max(n, 1), dtype=np.uint8)
+        self.ctx._check(lib().bath_hip_fasta_codes(self._h, int(target), int(start), int(n), _u8(out)), "fasta_codes")
+        return out[:n]
+
+    def release(self, lo):
+        self.ctx._check(lib().bath_hip_fasta_release(self._h, int(lo)), "fasta_release")
+
+    def close(self):
+        if getattr(self, "_h", None) and getattr(self.ctx, "_h", None):
+            lib().bath_hip_fasta_destroy(self._h)
+        self._h = None
+
+    def __del__(self):
+        self.close()
+
+
+def fasta_headers(path, records):
+    """(name, description) of every record, split from the header bytes of the file (host side: no sequence byte is read)."""
+    out = []
+    with open(path, "rb") as fh:
+        for r in records:
+            fh.seek(int(r["hdr_begin"]))
+            h = fh.read(int(r["hdr_end"] - r["hdr_begin"])).decode("latin-1").strip()
+            parts = h.split(None, 1)
+            out.append((parts[0] if parts else "", parts[1].strip() if len(parts) > 1 else ""))
+    return out
 
 
 def translate_orfs(ctx, dna, ncbi_table=1, min_orf_len=20, strands=STRAND_BOTH, initiator=INIT_ANY):

@@ -200,6 +200,47 @@ int   bath_hip_seqs_upload_packed(bath_hip_seqs *sq, const uint8_t *packed, cons
 int   bath_hip_seqs_upload_wait(bath_hip_seqs *sq);
 
 /* ------------------------------------------------------------------------------------------
+ * FASTA ingest on the device (bath_fasta.hip).  The raw bytes of a FASTA file go to HBM as they are, in chunks that may end
+ * anywhere; kernels find the records, drop line breaks, digitise (the product's DNA alphabet, as bath_amd.digitize) and keep the
+ * codes of every record resident.  Windows of the records (esl_sqio_ReadWindow: block_length new nucleotides after a context of
+ * 3 * max_length) are then gathered from those codes into a bath_hip_seqs with its ESL_SQ.C context set.
+ *
+ * Rules: a record starts at a '>' that is the first byte of its line other than space, \t, \r, \v, \f; its header runs to the
+ * end of that line.  In sequence lines those bytes and \n are skipped; ACGT-RYMKSWHBVDN*~ in either case are symbols, U reads T
+ * and X reads N; any other byte, and anything but blank lines before the first record, is an error (bath_hip_fasta_error).
+ * ------------------------------------------------------------------------------------------ */
+typedef struct bath_hip_fasta bath_hip_fasta;
+typedef struct {
+  int64_t hdr_begin, hdr_end;   /* header bytes [hdr_begin, hdr_end) in the file: after the '>', up to the line's \n (excluded) */
+  int64_t sym_start;            /* the record's first symbol in the stream of all the file's symbols */
+  int64_t length;               /* nucleotides */
+} bath_fasta_record;
+typedef struct {
+  int64_t target, start0;       /* window = record <target>[start0 : start0 + n] (0-based) */
+  int32_t n, context;           /* its first <context> nucleotides are the previous window's (ESL_SQ.C) */
+} bath_fasta_window;
+int     bath_hip_fasta_create(bath_hip_ctx *ctx, bath_hip_fasta **ret);
+void    bath_hip_fasta_destroy(bath_hip_fasta *f);
+/* the next <n> bytes of the file: uploaded on the context's copy stream (asynchronously from page-locked memory), parsed on its
+ * stream.  <bytes> may be reused when the call returns.  BATH_EINVAL on a format error: see bath_hip_fasta_error; the context
+ * stays usable, the handle takes no more bytes. */
+int     bath_hip_fasta_feed(bath_hip_fasta *f, const void *bytes, int64_t n);
+int     bath_hip_fasta_finish(bath_hip_fasta *f);                       /* end of file: closes the last record */
+int64_t bath_hip_fasta_count(bath_hip_fasta *f);                        /* records so far (the last may still be open) */
+int64_t bath_hip_fasta_symbols(bath_hip_fasta *f);                      /* symbols so far */
+int     bath_hip_fasta_records(bath_hip_fasta *f, int64_t lo, int64_t n, bath_fasta_record *out);
+/* the first format error: its byte offset in the file, 1-based line, 0-based record (-1: before the first record), the byte */
+int     bath_hip_fasta_error(const bath_hip_fasta *f, int64_t *offset, int64_t *line, int64_t *record, int32_t *byte);
+/* the windows of records [lo, hi) (dist.split_targets): their number; written to <out> when <cap> allows */
+int64_t bath_hip_fasta_windows(bath_hip_fasta *f, int64_t lo, int64_t hi, int32_t max_length, int32_t block_length, bath_fasta_window *out, int64_t cap);
+/* a block of the given windows, laid out as bath_hip_seqs_create lays out sequences, with their contexts set */
+int     bath_hip_fasta_seqs(bath_hip_fasta *f, const bath_fasta_window *w, int64_t n, bath_hip_seqs **ret);
+/* codes [start, start + n) of record <target> to the host (the windows of reported hits, for their alignments) */
+int     bath_hip_fasta_codes(bath_hip_fasta *f, int64_t target, int64_t start, int64_t n, uint8_t *out);
+/* drop the codes of the records before <lo> from device memory (a file streamed through a budget); their windows are gone */
+int     bath_hip_fasta_release(bath_hip_fasta *f, int64_t lo);
+
+/* ------------------------------------------------------------------------------------------
  * Filter kernels, batched.  Each target i is scored exactly as the reference would after
  * p7_oprofile_ReconfigLength(om, L_i) (p7_pipeline.c:1644).  sc[n] nats, status[n] easel codes.
  * ------------------------------------------------------------------------------------------ */
