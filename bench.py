@@ -20,6 +20,11 @@ cascade over the block, with the DNA already resident in HBM.
              stops: whole path to hits; per-kernel device times and HBM fractions of the frameshift
              kernels (bath_hip_kernel_times).
 
+A plain run does only what the headline needs: it sets up, warms up, times the steps, writes --dump-outputs and prints the line
+(value, ms_per_step, the timed steps' stage_ms and roofline HBM figures).  Everything else -- cpu_baseline and every parity check,
+roofline.valu's one-part passes, the streamed, concurrent, fs, c4 and c5 legs, the records copy-out pass, the N-rank comparisons
+with the single-rank search -- runs under --full.
+
 N>1: `python bench.py --gpus N` starts N ranks itself (a fresh torch.distributed.run child, never a re-exec); under the
 driver's own torch.distributed.run launch RANK is already set and this process is one rank.  The model is broadcast from
 rank 0 over RCCL, every rank scores its own windows (weak: 10^6 per GPU; --scaling strong: 10^6 in total, sharded), counters
@@ -850,9 +855,16 @@ def main():
     ap.add_argument("--dump-outputs", metavar="DIR",
                     help="write what the timed cascade computed as DIR/<name>.npy (see dump_outputs): the counters of the last timed step "
                          "and a fixed sample of the surviving ORFs' records; the inputs are seeded, so two builds can be compared array by array")
+    ap.add_argument("--full", action="store_true",
+                    help="also run what the headline does not need: the CPU baselines and parity checks, the streamed, concurrent, --fs and "
+                         "configs[3] / configs[4] legs, the one-part passes of roofline.valu, the records copy-out pass and, under --gpus N, "
+                         "the comparisons with the single-rank search (the --no-* switches then skip single legs)")
     args = ap.parse_args()
     if args.steps < 1 or args.warmup < 0:
         ap.error("--steps must be at least 1 and --warmup at least 0")
+    if not args.full:                 # a plain run: set-up, warm-up, the timed steps, --dump-outputs and the line, nothing else
+        args.no_cpu_baseline = args.no_fs = args.no_c45 = args.no_streamed = args.no_concurrent = args.no_one_part = True
+    want_records = args.full or bool(args.dump_outputs)      # the copy-out pass after the timed steps
 
     if args.gpus > 1 and "RANK" not in os.environ:
         sys.exit(launch_ranks(args.gpus, sys.argv[1:]))
@@ -970,12 +982,14 @@ def main():
         sync()
         elapsed = bdist.max_over_ranks(time.perf_counter() - t0, dev)
         step_stats = stats                                     # the counters the last timed step returned
-        # one more pass with the copy-out, to gather the records on rank 0 (outside the timed region; timed on its own below)
-        pipe.run(dna, want_results=True, copy=False)           # first call sizes the page-locked result array
-        t1 = time.perf_counter()
-        stats, res = pipe.run(dna, want_results=True, copy=False)
-        ms_with_results = (time.perf_counter() - t1) * 1e3
-        res = res.copy()
+        res, ms_with_results = None, None
+        if want_records:
+            # one more pass with the copy-out, to gather the records on rank 0 (outside the timed region; timed on its own below)
+            pipe.run(dna, want_results=True, copy=False)       # first call sizes the page-locked result array
+            t1 = time.perf_counter()
+            stats, res = pipe.run(dna, want_results=True, copy=False)
+            ms_with_results = (time.perf_counter() - t1) * 1e3
+            res = res.copy()
     else:                                                  # --plumbing-only: fabricated counters, the collectives are what runs
         elapsed = bdist.max_over_ranks(1e-3, dev)
         stats = ba.PipelineStats()
@@ -985,13 +999,13 @@ def main():
         ms_with_results = 0.0
         step_stats = stats
     merged = bdist.reduce_stats(stats, dev)
-    hits = bdist.gather_results(res, lo, 0, dev)
+    hits = bdist.gather_results(res, lo, 0, dev) if want_records else None
     if args.dump_outputs:
         step_counters = bdist.reduce_stats(step_stats, dev)        # a collective: every rank takes part
         if rank == 0:
             dump_outputs(args.dump_outputs, step_counters, hits, args.windows if args.scaling == "strong" else args.windows * world)
     strong_check = None
-    if on_gpu and world > 1 and args.scaling == "strong" and rank == 0:
+    if on_gpu and world > 1 and args.scaling == "strong" and rank == 0 and args.full:
         # one block over N ranks must be the block on one rank (p7_pipeline_Merge, p7_tophits_Merge: bathsearch.c:884-893): rank 0 runs
         # the WHOLE block alone, outside the timed region, and compares the reduced counters and the gathered records with its own
         full, _, _ = synth.dna_windows(args.windows, args.length, seed=42, hmm=hmm0)
@@ -1022,11 +1036,12 @@ def main():
             "gcells_per_s": cells_step / (elapsed / args.steps) / 1e9 if on_gpu else 0.0,
             "cells_per_step": cells_step, "residues_per_step": nres_step,
             "survivors": {k: tot[k] for k in ("n_orfs", "n_past_msv", "n_past_bias", "n_past_vit", "n_past_fwd")},
-            "hits_gathered": int(len(hits)) if hits is not None else 0,
             "timed_region": "DNA resident in HBM (1 byte per nucleotide); counters only -- the surviving ORFs' records stay on the device; "
-                            "a pass that also copies them to the host takes ms_per_step_with_records",
-            "ms_per_step_with_records": ms_with_results,
+                            "a pass that also copies them to the host takes ms_per_step_with_records (--full or --dump-outputs)",
         }
+        if hits is not None:
+            out["hits_gathered"] = int(len(hits))
+            out["ms_per_step_with_records"] = ms_with_results
         if args.plumbing_only:
             out["plumbing_only"] = True
         if strong_check is not None:

@@ -103,7 +103,7 @@ def test_bench_launcher_starts_the_ranks(scaling):
     import json
     import subprocess
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--plumbing-only", "--windows", "1001", "--fs-windows", "1001", "--scaling", scaling,
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--plumbing-only", "--full", "--windows", "1001", "--fs-windows", "1001", "--scaling", scaling,
                         "--c4-total-mb", "3", "--c5-total-mb", "3"],
                        env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=300)
     assert p.returncode == 0, p.stderr[-2000:]
@@ -134,6 +134,29 @@ def test_bench_launcher_starts_the_ranks(scaling):
     assert c4["hits_per_query"] == [1, 1, 1, 2] + [1] * 8 and c4["hits"] == 13
     c5 = out["c5"]
     assert c5["n_gpus"] == 2 and c5["domains_gathered"] == 4 and c5["windows_of_gathered_domains_are_global"]
+
+
+def test_bench_plain_run_is_the_headline_alone():
+    """Without --full a run does only what the headline needs: the same contract keys and counters as under --full, and none of the
+    other legs (fs, c4, c5), the records copy-out or its gather to rank 0."""
+    import json
+    import subprocess
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--plumbing-only", "--windows", "1001", "--fs-windows", "1001",
+                        "--c4-total-mb", "3", "--c5-total-mb", "3"], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=300)
+    assert p.returncode == 0, p.stderr[-2000:]
+    lines = [l for l in p.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1 and p.stdout.rstrip().endswith(lines[0])
+    line = json.loads(lines[0])
+    for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config"):
+        assert key in line, key
+    assert line["n_gpus"] == 2 and line["plumbing_only"] is True
+    full = [l for l in p.stderr.splitlines() if l.startswith("{") and '"residues_per_step"' in l]
+    assert len(full) == 1
+    out = json.loads(full[0])
+    assert out["residues_per_step"] == 2 * 1000 * 2002 and out["survivors"]["n_past_msv"] == 2002
+    for key in ("fs", "c4", "c5", "cpu_baseline", "hits_gathered", "ms_per_step_with_records", "strong_scaling_check"):
+        assert key not in out and key not in line, key
 
 
 def test_bench_dump_outputs(tmp_path):

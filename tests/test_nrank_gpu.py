@@ -24,7 +24,7 @@ def run_ranks(n, scaling, extra=()):
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
     env.update(BATH_BENCH_BACKEND="gloo", BATH_BENCH_SHARE_DEVICE="1", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--steps", "2", "--warmup", "1", "--scaling", scaling,
-           "--windows", "20000", "--fs-windows", "20000", "--c4-total-mb", "12", "--c5-total-mb", "30", "--no-cpu-baseline"] + list(extra)
+           "--windows", "20000", "--fs-windows", "20000", "--c4-total-mb", "12", "--c5-total-mb", "30", "--full", "--no-cpu-baseline"] + list(extra)
     p = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=1500, cwd=ROOT)
     assert p.returncode == 0, (p.stdout[-1500:], p.stderr[-3000:])
     lines = [l for l in p.stdout.splitlines() if l.startswith('{"metric"')]

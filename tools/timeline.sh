@@ -5,7 +5,7 @@ cd $GRAFT_REPO_ROOT
 export TMPDIR=/tmp
 OUT=$GRAFT_REPO_ROOT/gpurun_out/timeline
 rm -rf $OUT; mkdir -p $OUT
-rocprofv3 --kernel-trace --output-format csv -d $OUT/tr -o t -- python3 bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-fs --no-streamed --no-one-part > $OUT/log.txt 2>&1
+rocprofv3 --kernel-trace --output-format csv -d $OUT/tr -o t -- python3 bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-fs --no-streamed --no-one-part > $OUT/log.txt 2>&1
 python3 - <<PY
 import csv, glob
 f = glob.glob("$OUT/tr/**/*kernel_trace.csv", recursive=True)[0]

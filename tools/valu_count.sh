@@ -6,7 +6,7 @@ export TMPDIR=/tmp
 OUT=$GRAFT_REPO_ROOT/gpurun_out/valu_count
 rm -rf $OUT; mkdir -p $OUT
 export BATH_HIP_LANES=1
-rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAVES --output-format csv -d $OUT/pmc -- python3 bench.py --steps 1 --warmup 0 --no-cpu-baseline --no-fs --no-streamed --no-one-part --windows 200000 > $OUT/log.txt 2>&1
+rocprofv3 --pmc SQ_INSTS_VALU SQ_INSTS_SALU SQ_INSTS_LDS SQ_WAVES --output-format csv -d $OUT/pmc -- python3 bench.py --full --steps 1 --warmup 0 --no-cpu-baseline --no-fs --no-streamed --no-one-part --windows 200000 > $OUT/log.txt 2>&1
 python3 - <<PY
 import csv, glob, collections
 acc = collections.defaultdict(lambda: collections.defaultdict(float)); n = collections.Counter()
