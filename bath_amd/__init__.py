@@ -1034,19 +1034,65 @@ class HitArray:
     def __len__(self):
         return len(self.rec)
 
-    def to_bytes(self):
+    def to_bytes(self, traces=None):
         """The library's hit stream (bath_hits_serialize: self-delimiting records in network byte order, after p7_hit_Serialize):
-        what dist.gather_query_hits ships and what a C host would ship."""
+        what dist.gather_query_hits ships and what a C host would ship.  traces: one entry of Pipeline.traces() per hit, carried
+        in the stream (what the alignment blocks of the main output need; read back by HitArray.traces_from_bytes)."""
         rec = np.ascontiguousarray(self.rec)
         pool = self.pool if self.pool else None
-        args = (rec.ctypes.data, len(rec), pool, None, None, None, None, None, None)
+        keep = ()
+        if traces is not None and len(rec):
+            if len(traces) != len(rec):
+                raise BathError("hits_serialize: %d traces for %d hits" % (len(traces), len(rec)))
+            tr = (DomainTrace * len(rec))()
+            off = 0
+            for h, (t, *_a) in enumerate(traces):
+                tr[h] = DomainTrace(off, int(t.N), int(t.win_start), int(t.orf_start), int(t.frameshift))
+                off += int(t.N)
+            cat = [np.ascontiguousarray(np.concatenate([x[j] for x in traces]) if off else np.zeros(1, dt), dt)
+                   for j, dt in ((1, np.int8), (2, np.int32), (3, np.int32), (4, np.int8), (5, np.float32))]
+            p8 = lambda a: a.ctypes.data_as(C.POINTER(C.c_int8))
+            keep = (tr, cat)
+            args = (rec.ctypes.data, len(rec), pool, tr, p8(cat[0]), cat[1].ctypes.data_as(_i32p), cat[2].ctypes.data_as(_i32p), p8(cat[3]),
+                    _f32(cat[4]))
+        else:
+            args = (rec.ctypes.data, len(rec), pool, None, None, None, None, None, None)
         n = lib().bath_hits_serialize(*args, None, 0)
         if n < 0:
             raise BathError("hits_serialize failed")
         buf = C.create_string_buffer(n)
         if lib().bath_hits_serialize(*args, C.addressof(buf), n) != n:
             raise BathError("hits_serialize failed")
+        del keep
         return buf.raw
+
+    @staticmethod
+    def traces_from_bytes(buf):
+        """[(FsDomain, trace)] of a stream written with traces (bath_hits_deserialize, bath_hits_traces): every hit with its
+        trace in the form of Pipeline.traces(), as alidisplay_print takes it."""
+        h = _vp()
+        if lib().bath_hits_deserialize(bytes(buf), len(buf), C.byref(h)) != OK:
+            raise BathError("hits_deserialize failed")
+        try:
+            n = lib().bath_hits_count(h)
+            if n == 0:
+                return []
+            tr = C.POINTER(DomainTrace)(); st = C.POINTER(C.c_int8)(); k = _i32p(); i = _i32p(); c = C.POINTER(C.c_int8)(); pp = _f32p()
+            if lib().bath_hits_traces(h, C.byref(tr), C.byref(st), C.byref(k), C.byref(i), C.byref(c), C.byref(pp)) != OK:
+                raise BathError("the hit stream carries no traces")
+            dom = lib().bath_hits_domains(h)
+            out = []
+            for d in range(n):
+                x = FsDomain()
+                C.memmove(C.byref(x), C.byref(dom[d]), C.sizeof(FsDomain))
+                t = DomainTrace()
+                C.memmove(C.byref(t), C.byref(tr[d]), C.sizeof(DomainTrace))
+                sl = slice(t.off, t.off + t.N)
+                grab = lambda p, dt: np.ctypeslib.as_array(p, shape=(t.off + t.N,))[sl].astype(dt).copy() if t.N else np.zeros(0, dt)
+                out.append((x, (t, grab(st, np.int8), grab(k, np.int32), grab(i, np.int32), grab(c, np.int8), grab(pp, np.float32))))
+            return out
+        finally:
+            lib().bath_hits_destroy(h)
 
     @staticmethod
     def from_bytes(buf, p=0):
@@ -1133,6 +1179,23 @@ class TopHits:
         st = lib().bath_tophits_add(self._h, rec.ctypes.data_as(C.POINTER(FsDomain)), n, C.cast(pool, C.c_void_p), seqidx0, a, None, None, lens)
         if st != OK:
             raise BathError("tophits_add failed (%d)" % st)
+
+    def add_serialized(self, buf, names, lengths, descs=None, accs=None, window_shift=0, seqidx0=0):
+        """add() for a hit stream from another process (bath_tophits_add_serialized): the stream's window fields, plus
+        <window_shift>, index <names>; a hit outside them is refused (BathError) and nothing is added."""
+        def strs(v):
+            if v is None:
+                return None
+            a = (C.c_char_p * max(len(v), 1))()
+            for i, x in enumerate(v):
+                a[i] = x.encode() if x else None
+            return a
+        lens = (C.c_int64 * max(len(lengths), 1))(*[int(x) for x in lengths])
+        raw = bytes(buf)
+        st = lib().bath_tophits_add_serialized(self._h, raw, len(raw), int(window_shift), len(names), int(seqidx0), strs(names), strs(accs),
+                                               strs(descs), lens)
+        if st != OK:
+            raise BathError("tophits_add_serialized failed (%d)" % st)
 
     def reported(self):
         return int(lib().bath_tophits_reported(self._h))

@@ -1,16 +1,27 @@
-"""bathsearch on one GPU: search the profile HMMs of a model file against the DNA targets of a FASTA file.
+"""bathsearch on one GPU or several: search the profile HMMs of a model file against the DNA targets of a FASTA file.
 
-    python -m bath_amd.bathsearch [options] <hmmfile> <seqfile>
+    python -m bath_amd.bathsearch [--gpus N] [options] <hmmfile> <seqfile>
 
 The FASTA file's bytes go to the device as they are (bath_amd.FastaTargets: records, digitising and the windows of
 esl_sqio_ReadWindow are found there); per query the windows run through the pipeline in blocks of at most <block_nt>
 nucleotides, and the hits are finished, sorted and printed as bathsearch.c does (main output and --tblout).
 
 Every option the library implements is mapped; every other bathsearch option, a sequence or alignment query and a target file that
-is not plain FASTA are refused (exit status 1, a message naming it).  Multi-GPU sharding is not here (bath_amd.dist has the pieces).
+is not plain FASTA are refused (exit status 1, a message naming it).
+
+--gpus N (1..16) runs one search over N ranks, one process per GPU (rank r on device r): the parent checks the command line and the
+inputs, opens no GPU and starts N fresh children (launch_ranks).  Every rank ingests the whole target file, the (query, window group)
+items of every query are cut and dealt the same way on every rank (search_plan), each query's hits with their traces travel to its
+owner rank, which merges them in item order and renders the query, and rank 0 writes the queries in order; the output does not
+depend on N.  BATH_SEARCH_SHARE_DEVICE=1 puts every rank on device 0 and BATH_SEARCH_BACKEND=gloo runs the collectives on CPU
+tensors (default nccl); each rank gets an equal share of the parent's CPUs as BATH_HIP_HOST_THREADS unless that is set.
 """
+import codecs
 import os
+import socket
+import subprocess
 import sys
+import threading
 import time
 
 import numpy as np
@@ -29,7 +40,8 @@ OPTIONS = {"-o": str, "--tblout": str, "--fs": "flag", "--cigar": "flag", "--fra
            "--ct": int, "-l": int, "-m": "flag", "-M": "flag", "--strand": str,
            "-E": float, "-T": float, "--incT": float, "-Z": float, "--seed": int,
            "--F1": float, "--F2": float, "--F3": float, "--F4": float, "--max": "flag", "--nobias": "flag", "--nonull2": "flag", "--fsonly": "flag",
-           "--block_length": int}
+           "--block_length": int, "--gpus": int}
+MAX_GPUS = 16
 # bathsearch options this driver does not implement: refused, never ignored
 REFUSED = ["-h", "--splice", "--exontblout", "--fstblout", "--hmmout", "--acc", "--noali", "--notrans", "--min_intron", "--max_intron",
            "--incE", "--qformat", "--tformat", "--singlemx", "--popen", "--pextend", "--mx", "--mxfile", "--w_beta", "--w_length", "--cpu",
@@ -38,6 +50,10 @@ REFUSED = ["-h", "--splice", "--exontblout", "--fstblout", "--hmmout", "--acc", 
 EXCLUSIVE = [("-m", "-M"), ("--textw", "--notextw"), ("-E", "-T"), ("--max", "--F1"), ("--max", "--F2"), ("--max", "--F3"), ("--max", "--F4"),
              ("--max", "--nobias")]
 REQUIRES = {"--frameline": "--fs", "--cigar": "--tblout", "--F4": "--fs"}
+
+
+CT_MISMATCH = ("Error: Requested codon translation tabel ID %d does not match the codon translation tabel ID of the HMM file %s. "
+               "Please either run bathsearch with option '--ct %d' or run bathconvert with option '--ct %d'.\n")
 
 
 class UsageError(Exception):
@@ -87,6 +103,8 @@ def parse_args(argv):
         raise UsageError("option --textw: n >= 120")
     if opts.get("--block_length", 50000) < 50000:
         raise UsageError("option --block_length: n >= 50000")
+    if not 1 <= opts.get("--gpus", 1) <= MAX_GPUS:
+        raise UsageError("option --gpus: 1 <= n <= %d" % MAX_GPUS)
     if opts.get("-E", 1.0) <= 0:
         raise UsageError("option -E: x > 0")
     if opts.get("-Z", 0.0) < 0 or opts.get("--seed", 0) < 0:
@@ -246,12 +264,20 @@ class Hit:
     __slots__ = ("trace", "target", "start0", "n")
 
 
-def search_query(ctx, hmm, targets, opts, block_nt, names_out):
-    """One query: (TopHits, summed PipelineStats, Pipeline, trace map, number of targets, target names, ...)."""
-    fs = "--fs" in opts
-    ct = opts.get("--ct", 1)
-    gm = ba.Profile(hmm)
-    om = ba.OProfile(ctx, gm)
+def block_cuts(ns, block_nt):
+    """Boundaries of the blocks of at most <block_nt> nucleotides that windows of lengths <ns> run in (a window is never cut)."""
+    cut = [0]
+    acc = 0
+    for i, n in enumerate(ns):
+        if acc and acc + int(n) > block_nt:
+            cut.append(i); acc = 0
+        acc += int(n)
+    cut.append(len(ns))
+    return cut
+
+
+def pipeline_overrides(opts):
+    """The Pipeline parameters the options set (every rank of a --gpus N search sets the same)."""
     over = {}
     if "--max" in opts:
         over.update(F1=1.0, F2=1.0, F3=1.0, F4=1.0, do_biasfilter=0)
@@ -277,6 +303,16 @@ def search_query(ctx, hmm, targets, opts, block_nt, names_out):
         over["T"] = opts["-T"]
     if "--seed" in opts:
         over["seed"] = opts["--seed"]
+    return over
+
+
+def search_query(ctx, hmm, targets, opts, block_nt, names_out):
+    """One query: (TopHits, summed PipelineStats, Pipeline, trace map, number of targets, target names, ...)."""
+    fs = "--fs" in opts
+    ct = opts.get("--ct", 1)
+    gm = ba.Profile(hmm)
+    om = ba.OProfile(ctx, gm)
+    over = pipeline_overrides(opts)
     pipe = ba.Pipeline(ctx, om, fs_pipe=fs, ncbi_table=ct, **over)
     if fs:
         om3 = ba.FSOProfile(ctx, ba.FSProfile(hmm, 3, ncbi_table=ct))
@@ -297,14 +333,7 @@ def search_query(ctx, hmm, targets, opts, block_nt, names_out):
             names.append(name); descs.append(desc)
         lengths.extend(int(x) for x in recs["length"])
         wins = ft.windows(hmm.max_length, block_length, lo, hi)
-        # blocks of at most block_nt nucleotides (a window is never cut)
-        cut = [0]
-        acc = 0
-        for i, n in enumerate(wins["n"]):
-            if acc and acc + int(n) > block_nt:
-                cut.append(i); acc = 0
-            acc += int(n)
-        cut.append(len(wins))
+        cut = block_cuts(wins["n"], block_nt)
         for a, b in zip(cut[:-1], cut[1:]):
             if a == b:
                 continue
@@ -328,14 +357,19 @@ def search_query(ctx, hmm, targets, opts, block_nt, names_out):
                 traces.setdefault(_key(d), h)
             th.add(dm, names, lengths, descs=descs) if dm else None
             del blk
+    finish_tophits(th, opts, nres, hmm.max_length, E)
+    return dict(th=th, stats=total, pipe=pipe, traces=traces, nseqs=len(names), gm=gm, gm5=gm5, names=names, nres=nres)
+
+
+def finish_tophits(th, opts, nres, max_length, E):
+    """The end of a query's search: -T / --incT thresholds, E-values over the whole search's residues (or -Z), duplicates, sorting."""
     if "--incT" in opts or "-T" in opts:
         th.set_score_thresholds(by_E="-T" not in opts, T=opts.get("-T", 0.0), inc_by_E="--incT" not in opts, incT=opts.get("--incT", 0.0))
     if "-Z" in opts:
         search_nres = int(1e6 * opts["-Z"]) * (2 if opts.get("--strand", "both") == "both" else 1)
     else:
         search_nres = nres
-    th.finalize(search_nres, hmm.max_length, E)
-    return dict(th=th, stats=total, pipe=pipe, traces=traces, nseqs=len(names), gm=gm, gm5=gm5, names=names, nres=nres)
+    th.finalize(search_nres, max_length, E)
 
 
 def _key(d):
@@ -397,6 +431,402 @@ class _CodesSource:
         return self._ft.codes(target, start0, n)
 
 
+# ---------------------------------------------------------------------------------------------------------------------------
+# --gpus N: one search over N ranks, one process per GPU.  The parent checks the command line and the inputs, opens no GPU and
+# starts N fresh children (rank_main).  Every rank ingests the whole target file, cuts every query's windows into (query, window
+# group) items the same way (search_plan), searches the items dealt to it, and ships each item's hits -- with their CIGARs and
+# traces, in the library's hit stream -- and counters to the query's owner (dist.query_owner), which merges them in item order,
+# finishes the query over the whole search's residues and renders its main-output block and --tblout rows.  Rank 0 writes the
+# blocks in query order and the [ok] line last.
+# ---------------------------------------------------------------------------------------------------------------------------
+
+BATCH_QUERIES = 256         # queries planned and merged together: what a rank holds of the hits at once
+STOP_GRACE_S = 5.0          # a failed search: SIGTERM to the other ranks, SIGKILL after this long
+STAT_FIELDS = [f for f, _ in ba.PipelineStats._fields_]
+
+
+class Item:
+    __slots__ = ("query", "lo", "hi", "owner", "nres_before")
+
+    def __init__(self, query, lo, hi, owner, nres_before):
+        self.query, self.lo, self.hi, self.owner, self.nres_before = query, lo, hi, owner, nres_before
+
+    def __repr__(self):
+        return "Item(%d, %d, %d, owner=%d, nres_before=%d)" % (self.query, self.lo, self.hi, self.owner, self.nres_before)
+
+
+def window_nres(windows, strand="both"):
+    """stats.nres of every window (FASTA_WINDOW_DTYPE): its new nucleotides (length minus context), once per strand searched."""
+    w = np.asarray(windows)
+    return (w["n"].astype(np.int64) - w["context"].astype(np.int64)) * (2 if strand == "both" else 1)
+
+
+def search_plan(windows_by_query, M_by_query, world, strand="both"):
+    """[Item] of one batch of queries, the same on every rank without communication: query q's windows cut into consecutive groups
+    in proportion to its share of the work (dist.query_items_weighted, cost windows' nucleotides x (M + 150)), dealt to the ranks
+    longest first (dist.deal, dist.item_cost).  nres_before: the residues the single-GPU loop has counted before the item's first
+    window (the summed stats.nres of the query's earlier windows)."""
+    ns = [np.asarray(w)["n"].astype(np.int64) for w in windows_by_query]
+    items = dist.query_items_weighted([len(n) for n in ns], [float(n.sum()) * (M + 150.0) for n, M in zip(ns, M_by_query)], world)
+    owner = dist.deal([dist.item_cost(M_by_query[q], int(ns[q][lo:hi].sum())) for q, lo, hi in items], world)
+    before = [np.concatenate([[0], np.cumsum(window_nres(w, strand))]) for w in windows_by_query]
+    return [Item(q, lo, hi, o, int(before[q][lo])) for (q, lo, hi), o in zip(items, owner)]
+
+
+def host_threads_per_rank(n, environ=None, affinity=None):
+    """BATH_HIP_HOST_THREADS for each of <n> ranks: the CPUs this process may run on (its affinity set, lowered to OMP_NUM_THREADS
+    when that is set) split evenly, at least one each; None when the user has set it (it is then left as it is)."""
+    env = os.environ if environ is None else environ
+    if env.get("BATH_HIP_HOST_THREADS"):
+        return None
+    budget = len(os.sched_getaffinity(0) if affinity is None else affinity)
+    try:
+        omp = int(env.get("OMP_NUM_THREADS", "0"))
+    except ValueError:
+        omp = 0
+    if omp > 0:
+        budget = min(budget, omp)
+    return max(1, budget // int(n))
+
+
+def rank_env(n, rank, port, environ=None, threads=None):
+    """The environment of rank <rank> of <n>: torch.distributed's rendezvous variables and the host-thread share."""
+    env = {k: v for k, v in (os.environ if environ is None else environ).items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "LOCAL_WORLD_SIZE")}
+    env.update(RANK=str(rank), LOCAL_RANK=str(rank), WORLD_SIZE=str(n), LOCAL_WORLD_SIZE=str(n), MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
+    if threads is not None:
+        env["BATH_HIP_HOST_THREADS"] = str(threads)
+    env.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env["PYTHONPATH"] = root + (os.pathsep + env["PYTHONPATH"] if env.get("PYTHONPATH") else "")
+    return env
+
+
+def _free_port():
+    s = socket.socket()
+    s.bind(("127.0.0.1", 0))
+    p = s.getsockname()[1]
+    s.close()
+    return p
+
+
+def _drain(pipe, sink):
+    """Copies a child's pipe into <sink> (a list of bytes, or a text stream) until it closes."""
+    dec = codecs.getincrementaldecoder("utf-8")("replace")
+    for chunk in iter(lambda: pipe.read1(1 << 16), b""):
+        if isinstance(sink, list):
+            sink.append(chunk)
+        else:
+            sink.write(dec.decode(chunk))
+            sink.flush()
+    pipe.close()
+
+
+def _stop(procs, grace=STOP_GRACE_S):
+    for p in procs:
+        if p.poll() is None:
+            p.terminate()
+    end = time.time() + grace
+    for p in procs:
+        try:
+            p.wait(max(0.0, end - time.time()))
+        except subprocess.TimeoutExpired:
+            pass
+    for p in procs:
+        if p.poll() is None:
+            p.kill()
+    for p in procs:
+        p.wait()
+
+
+def launch_ranks(n, argv, stdout, run_kw):
+    """Starts the <n> ranks as fresh child processes, relays rank 0's standard output, and waits for them.  When a rank fails the
+    others are stopped, its error message is printed once and the status is 1.  No child outlives this call."""
+    code = "import sys; from bath_amd import bathsearch as b; sys.exit(b.rank_main(sys.argv[1:], **%r))" % (run_kw,)
+    cmd = [sys.executable] + (["-s"] if sys.flags.no_user_site else []) + ["-c", code] + list(argv)
+    port, threads = _free_port(), host_threads_per_rank(n)
+    procs, errs, readers = [], [], []
+    t0 = "%.6f" % time.time()
+    try:
+        for r in range(n):
+            env = rank_env(n, r, port, threads=threads)
+            env["BATH_SEARCH_T0"] = t0
+            p = subprocess.Popen(cmd, env=env, stdin=subprocess.DEVNULL,
+                                 stdout=subprocess.PIPE if r == 0 else subprocess.DEVNULL, stderr=subprocess.PIPE)
+            procs.append(p)
+            errs.append([])
+            readers.append(threading.Thread(target=_drain, args=(p.stderr, errs[-1]), daemon=True))
+            readers[-1].start()
+            if r == 0:
+                readers.append(threading.Thread(target=_drain, args=(p.stdout, stdout), daemon=True))
+                readers[-1].start()
+        failed = None
+        while failed is None:
+            codes = [p.poll() for p in procs]
+            bad = [r for r, c in enumerate(codes) if c not in (None, 0)]
+            if bad:
+                failed = bad[0]
+            elif all(c == 0 for c in codes):
+                break
+            else:
+                time.sleep(0.02)
+    finally:
+        _stop(procs)
+        for t in readers:
+            t.join()
+    if failed is None:
+        sys.stderr.write("".join(ln for ln in b"".join(errs[0]).decode("utf-8", "replace").splitlines(True) if not ln.startswith("[Gloo] ")))
+        return 0
+    msg = b"".join(errs[failed]).decode("utf-8", "replace")
+    sys.stderr.write(msg if msg.strip() else "Error: rank %d of the --gpus %d search exited with status %d\n" % (failed, n, procs[failed].returncode))
+    return 1
+
+
+def _pack_item(q, piece, lo, stats, geometry, stream):
+    """One item's result as it travels to the query's owner: ids, counters, each hit's window (start, length), the hit stream."""
+    head = np.array([q, piece, lo] + [int(getattr(stats, f)) for f in STAT_FIELDS] + [len(geometry), len(stream)], dtype="<i8")
+    return head.tobytes() + np.asarray(geometry, dtype="<i8").reshape(-1, 2).tobytes() + stream
+
+
+def _unpack_items(buf):
+    p, nh = 0, 3 + len(STAT_FIELDS) + 2
+    while p < len(buf):
+        head = np.frombuffer(buf, dtype="<i8", count=nh, offset=p); p += 8 * nh
+        nhit, nstream = int(head[-2]), int(head[-1])
+        geometry = np.frombuffer(buf, dtype="<i8", count=2 * nhit, offset=p).reshape(-1, 2); p += 16 * nhit
+        yield int(head[0]), int(head[1]), int(head[2]), dict(zip(STAT_FIELDS, (int(x) for x in head[3:3 + len(STAT_FIELDS)]))), geometry, buf[p:p + nstream]
+        p += nstream
+
+
+def _send_text(text, dst, dev):
+    import torch
+    import torch.distributed as tdist
+    b = text.encode()
+    tdist.send(torch.tensor([len(b)], dtype=torch.int64, device=dev), dst)
+    if b:
+        tdist.send(torch.frombuffer(bytearray(b), dtype=torch.uint8).to(dev), dst)
+
+
+def _recv_text(src, dev):
+    import torch
+    import torch.distributed as tdist
+    n = torch.zeros(1, dtype=torch.int64, device=dev)
+    tdist.recv(n, src)
+    if not int(n.item()):
+        return ""
+    buf = torch.empty(int(n.item()), dtype=torch.uint8, device=dev)
+    tdist.recv(buf, src)
+    return bytes(buf.cpu().numpy().tobytes()).decode()
+
+
+def _search_items(ctx, hmm, ft, wins, items, opts, block_nt):
+    """This rank's items of one query in one piece of the targets: [(item, stats, hit window geometry, hit stream)]."""
+    fs = "--fs" in opts
+    ct = opts.get("--ct", 1)
+    om = ba.OProfile(ctx, ba.Profile(hmm))
+    pipe = ba.Pipeline(ctx, om, fs_pipe=fs, ncbi_table=ct, **pipeline_overrides(opts))
+    if fs:
+        om3 = ba.FSOProfile(ctx, ba.FSProfile(hmm, 3, ncbi_table=ct))
+        om5 = ba.FSOProfile(ctx, ba.FSProfile(hmm, 5, ncbi_table=ct))
+    E = opts.get("-E", 10.0)
+    out = []
+    for it in items:
+        iw = wins[it.lo:it.hi]
+        total, nres = ba.PipelineStats(), it.nres_before
+        doms, trs, geometry = [], [], []
+        cut = block_cuts(iw["n"], block_nt)
+        for a, b in zip(cut[:-1], cut[1:]):
+            w = iw[a:b]
+            blk = ft.seqs(w)
+            if fs:
+                stats, _, dm, _ = pipe.run_frameshift_domains(om3, om5, blk, E_report=E, nres_before=nres)
+            else:
+                stats, dm, _ = pipe.run_hits(blk, E_report=E, nres_before=nres)
+            for f in STAT_FIELDS:
+                setattr(total, f, getattr(total, f) + getattr(stats, f))
+            nres += stats.nres
+            for d in dm:                                 # window -> target coordinates, as search_query does
+                win = w[d.window]
+                off = int(win["start0"])
+                d.ienv += off; d.jenv += off; d.iali += off; d.jali += off
+                d.window = int(win["target"])
+                geometry.append((off, int(win["n"])))
+            doms.extend(dm)
+            trs.extend(pipe.traces())
+            del blk
+        stream = ba.HitArray.from_domains(doms).to_bytes(traces=trs)
+        out.append((it, total, geometry, stream))
+    return out
+
+
+def _render_query(q, hmm, desc, parts, opts, names, descs, lengths, src, t0, c0):
+    """The owner's end of query <q>: its items' hits added in item order, counters summed, the query finished as search_query
+    finishes it, and its main-output block and --tblout rows rendered."""
+    fs = "--fs" in opts
+    ct = opts.get("--ct", 1)
+    th = ba.TopHits()
+    total = ba.PipelineStats()
+    traces = {}
+    for _key_, stats, geometry, stream in sorted(parts, key=lambda x: x[0]):
+        for f in STAT_FIELDS:
+            setattr(total, f, getattr(total, f) + stats[f])
+        if len(geometry) == 0:
+            continue
+        th.add_serialized(stream, names, lengths, descs=descs)
+        for (d, tr), (off, n) in zip(ba.HitArray.traces_from_bytes(stream), geometry):
+            h = Hit()
+            h.trace, h.target, h.start0, h.n = tr, int(d.window), int(off), int(n)
+            traces.setdefault(_key(d), h)
+    finish_tophits(th, opts, total.nres, hmm.max_length, opts.get("-E", 10.0))
+    r = dict(th=th, stats=total, pipe=ba.Pipeline(None, None, fs_pipe=fs, ncbi_table=ct, **pipeline_overrides(opts)), traces=traces,
+             nseqs=len(names), gm=ba.Profile(hmm), gm5=ba.FSProfile(hmm, 5, ncbi_table=ct), names=names, nres=total.nres)
+    c1 = os.times()
+    block = main_output_query(hmm, desc, r, opts, src, time.time() - t0, (c1.user - c0.user, c1.system - c0.system))
+    tbl = th.tblout(hmm.name, hmm.acc, hmm.M, fs_pipe=fs, show_cigar="--cigar" in opts, show_header=(q == 0)) if "--tblout" in opts else ""
+    return block, tbl
+
+
+def _rank_search(argv, opts, hmmfile, seqfile, rank, world, device, dev, chunk_bytes, block_nt, resident_bytes, laps):
+    nq = ba.HMM.count(hmmfile)
+    qdescs = model_descriptions(hmmfile)
+    strand = opts.get("--strand", "both")
+    block_length = opts.get("--block_length", dist.BLOCK_LENGTH)
+    ofp = tblfp = None
+    if rank == 0:
+        ofp = open(opts["-o"], "w") if "-o" in opts else sys.stdout
+        tblfp = open(opts["--tblout"], "w") if "--tblout" in opts else None
+    try:
+        if ofp:
+            ofp.write(output_header(opts, hmmfile, seqfile))
+            ofp.flush()
+        t = time.perf_counter()
+        ctx = ba.Context(device)
+        ctx.set_fs_strict(True)
+        laps["context_s"] = time.perf_counter() - t
+        targets = Targets(ctx, seqfile, chunk_bytes, resident_bytes)
+        src = _CodesSource(targets)
+        for b0 in range(0, nq, BATCH_QUERIES):
+            qs = list(range(b0, min(nq, b0 + BATCH_QUERIES)))
+            t0, c0 = time.time(), os.times()
+            hmms = [ba.HMM(hmmfile, q) for q in qs]
+            names, descs, lengths = [], [], []
+            base = [0] * len(qs)                         # residues of the earlier pieces, per query
+            n_items = [0] * len(qs)
+            by_dest = {}
+            tb = time.perf_counter()
+            for piece, (ft, lo, hi) in enumerate(targets.pieces()):
+                laps["ingest_s"] += time.perf_counter() - tb
+                recs = ft.records()[lo:hi]
+                for name, desc in ba.fasta_headers(targets.path, recs):
+                    names.append(name); descs.append(desc)
+                lengths.extend(int(x) for x in recs["length"])
+                wins = [ft.windows(h.max_length, block_length, lo, hi) for h in hmms]
+                plan = search_plan(wins, [h.M for h in hmms], world, strand)
+                ts = time.perf_counter()
+                for k, h in enumerate(hmms):
+                    n_items[k] += sum(1 for it in plan if it.query == k)
+                    mine = [it for it in plan if it.query == k and it.owner == rank]
+                    for it in mine:
+                        it.nres_before += base[k]
+                    for it, stats, geometry, stream in (_search_items(ctx, h, ft, wins[k], mine, opts, block_nt) if mine else []):
+                        by_dest.setdefault(dist.query_owner(qs[k], world), bytearray()).extend(
+                            _pack_item(k, piece, it.lo, stats, geometry, stream))
+                    base[k] += int(window_nres(wins[k], strand).sum())
+                laps["items"] += sum(1 for it in plan if it.owner == rank)
+                laps["search_s"] += time.perf_counter() - ts
+                tb = time.perf_counter()
+            tm = time.perf_counter()
+            got = dist.exchange_bytes({d: bytes(b) for d, b in by_dest.items()}, dev)
+            parts = {}
+            for srank in sorted(got):
+                for k, piece, lo, stats, geometry, stream in _unpack_items(got[srank]):
+                    parts.setdefault(k, []).append(((piece, lo), stats, geometry, stream))
+            for k, q in enumerate(qs):
+                owner = dist.query_owner(q, world)
+                text = None
+                if owner == rank:
+                    if len(parts.get(k, ())) != n_items[k]:
+                        raise RuntimeError("query %d: %d of its %d items arrived" % (q, len(parts.get(k, ())), n_items[k]))
+                    text = _render_query(q, hmms[k], qdescs[q] if q < len(qdescs) else None, parts.pop(k, []), opts, names, descs, lengths,
+                                         src, t0, c0)
+                    if rank != 0:
+                        _send_text("%d\n%s%s" % (len(text[0]), text[0], text[1]), 0, dev)
+                elif rank == 0:
+                    msg = _recv_text(owner, dev)
+                    head, rest = msg.split("\n", 1)
+                    text = (rest[:int(head)], rest[int(head):])
+                if rank == 0:
+                    ofp.write(text[0])
+                    if tblfp:
+                        tblfp.write(text[1])
+                    ofp.flush()
+            laps["merge_write_s"] += time.perf_counter() - tm
+        if rank == 0:
+            if tblfp:
+                tblfp.write(tabular_tail(hmmfile, seqfile, argv))
+            ofp.write("[ok]\n")
+    finally:
+        if ofp is not None and ofp is not sys.stdout:
+            ofp.close()
+        elif ofp is not None:
+            ofp.flush()
+        if tblfp:
+            tblfp.close()
+    return 0
+
+
+def rank_main(argv, chunk_bytes=64 << 20, block_nt=256_000_000, resident_bytes=8 << 30):
+    """One rank of a --gpus N search (a child of launch_ranks: RANK, WORLD_SIZE and the rendezvous address in its environment).
+    BATH_SEARCH_SHARE_DEVICE=1: every rank on device 0; BATH_SEARCH_BACKEND: nccl (default) or gloo (collectives on CPU tensors)."""
+    t_main = time.perf_counter()
+    laps = dict(launch_s=0.0, context_s=0.0, ingest_s=0.0, search_s=0.0, merge_write_s=0.0, items=0)
+    rank, world = int(os.environ["RANK"]), int(os.environ["WORLD_SIZE"])
+    opts, hmmfile, seqfile = parse_args(argv)
+    share = os.environ.get("BATH_SEARCH_SHARE_DEVICE") == "1"
+    backend = os.environ.get("BATH_SEARCH_BACKEND") or "nccl"
+    if backend not in ("nccl", "gloo"):
+        sys.stderr.write("Error: BATH_SEARCH_BACKEND must be nccl or gloo\n")
+        return 1
+    if share and backend == "nccl":
+        sys.stderr.write("Error: BATH_SEARCH_SHARE_DEVICE=1 needs BATH_SEARCH_BACKEND=gloo (RCCL does not run two ranks on one device)\n")
+        return 1
+    sys.stdout.flush()
+    sys.stdout = os.fdopen(os.dup(1), "w")              # the main output's own stream: what libraries print to fd 1 (gloo's
+    os.dup2(2, 1)                                       # connection notes) goes to stderr instead of into the output
+    import torch
+    import torch.distributed as tdist
+    device = 0 if share else int(os.environ.get("LOCAL_RANK", rank))
+    ndev = torch.cuda.device_count()
+    if (not share and world > ndev) or ndev < 1:
+        sys.stderr.write("Error: option --gpus %d: %d GPU(s) visible\n" % (world, ndev))
+        return 1
+    t = time.perf_counter()
+    if backend == "nccl":
+        torch.cuda.set_device(device)
+        dev = torch.device("cuda", device)
+        tdist.init_process_group("nccl", device_id=dev)
+    else:
+        dev = torch.device("cpu")
+        tdist.init_process_group("gloo")
+    laps["rendezvous_s"] = time.perf_counter() - t
+    t_start = float(os.environ.get("BATH_SEARCH_T0", "0") or 0)
+    if t_start:
+        laps["launch_s"] = time.time() - t_start
+    try:
+        status = _rank_search(argv, opts, hmmfile, seqfile, rank, world, device, dev, chunk_bytes, block_nt, resident_bytes, laps)
+    except ba.FastaFormatError as e:
+        sys.stderr.write("Error: %s: %s\n" % (seqfile, e))
+        status = 1
+    if status == 0:
+        tdist.barrier()
+        tdist.destroy_process_group()
+    laps["rank_main_s"] = time.perf_counter() - t_main
+    if os.environ.get("BATH_SEARCH_LAPS"):                 # tools/bathsearch_multi_profile.py: every rank's phase times
+        import json
+        with open("%s.rank%d.json" % (os.environ["BATH_SEARCH_LAPS"], rank), "w") as fh:
+            json.dump(dict(laps, rank=rank, world=world, status=status), fh)
+    return status
+
+
 def run(argv, stdout=None, chunk_bytes=64 << 20, block_nt=256_000_000, resident_bytes=8 << 30, device=0):
     """The whole search; returns the exit status.  chunk_bytes: FASTA bytes per upload; block_nt: nucleotides per pipeline call;
     resident_bytes: the device-memory budget for the digitised targets kept across queries."""
@@ -413,6 +843,18 @@ def run(argv, stdout=None, chunk_bytes=64 << 20, block_nt=256_000_000, resident_
         sys.stderr.write("Error: %s\n" % e)
         return 1
     ct = opts.get("--ct", 1)
+    if opts.get("--gpus", 1) > 1:
+        for q in range(nq):                      # the ranks start only on inputs the single-GPU search would not refuse
+            hmm = ba.HMM(hmmfile, q)
+            if hmm.ct != ct:
+                if "-o" in opts:
+                    with open(opts["-o"], "w") as fh:
+                        fh.write(output_header(opts, hmmfile, seqfile))
+                else:
+                    stdout.write(output_header(opts, hmmfile, seqfile))
+                sys.stderr.write(CT_MISMATCH % (ct, hmmfile, hmm.ct, ct))
+                return 1
+        return launch_ranks(opts["--gpus"], argv, stdout, dict(chunk_bytes=chunk_bytes, block_nt=block_nt, resident_bytes=resident_bytes))
     descs = model_descriptions(hmmfile)
     ofp = open(opts["-o"], "w") if "-o" in opts else stdout
     tblfp = open(opts["--tblout"], "w") if "--tblout" in opts else None
@@ -425,8 +867,7 @@ def run(argv, stdout=None, chunk_bytes=64 << 20, block_nt=256_000_000, resident_
         for q in range(nq):
             hmm = ba.HMM(hmmfile, q)
             if hmm.ct != ct:
-                sys.stderr.write("Error: Requested codon translation tabel ID %d does not match the codon translation tabel ID of the HMM file %s. "
-                                 "Please either run bathsearch with option '--ct %d' or run bathconvert with option '--ct %d'.\n" % (ct, hmmfile, hmm.ct, ct))
+                sys.stderr.write(CT_MISMATCH % (ct, hmmfile, hmm.ct, ct))
                 return 1
             t0, c0 = time.time(), os.times()
             r = search_query(ctx, hmm, targets, opts, block_nt, None)
