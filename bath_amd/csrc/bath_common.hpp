@@ -12,7 +12,6 @@
 #include <condition_variable>
 #include <functional>
 #include <mutex>
-#include <shared_mutex>
 #include <string>
 #include <thread>
 #include <vector>
@@ -135,32 +134,6 @@ struct LanePool {
   }
 };
 
-// Worker contexts that run whole --fs passes on one GPU (the reference's worker threads, bathsearch.c:1119-1290) meet at the strict
-// 3-codon parsers: a chain block (bath_fs_chain.hip) takes a CU's whole register file and most of its LDS, the Forward parser's
-// launch takes nearly every CU, and whatever holds CUs when it starts pushes part of its blocks into a second round (a launch
-// lasts as long as its longest window: a second round doubles it).  BATH_HIP_FS_GATE makes the turn-taking explicit, per device:
-//   0 (default)  no gate: the hardware queues interleave the workers' kernels
-//   1            one chain stage (Forward or Backward parser) at a time
-//   2            one Forward parser at a time; the Backward parser (half the CUs or fewer) runs beside anything
-//   3            the Forward parser alone on the chip: it waits for the other workers' cascades and envelope stages, and they for it
-// Measured with the bench's --fs block (tools/fs_workers_probe.py), ms per block: DESIGN.md 4.6c.
-inline std::shared_mutex &stage_gate_mutex(int device) { static std::shared_mutex g[16]; return g[device & 15]; }
-inline int stage_gate_mode() { static const int m = [] { const char *e = std::getenv("BATH_HIP_FS_GATE"); return e ? std::atoi(e) : 0; }(); return m; }
-struct StageGate {
-  enum Kind { kFwdChain, kBwdChain, kCascade, kEnvelopes, kNone };
-  std::unique_lock<std::shared_mutex> ex;
-  std::shared_lock<std::shared_mutex> sh;
-  StageGate(int device, Kind kind) {
-    const int m = stage_gate_mode();
-    if (device < 0 || m <= 0 || kind == kNone) return;
-    const bool exclusive = (kind == kFwdChain) || (kind == kBwdChain && m == 1);
-    const bool shared = m == 3 && (kind == kCascade || kind == kEnvelopes);
-    if (exclusive) ex = std::unique_lock<std::shared_mutex>(stage_gate_mutex(device));
-    else if (shared) sh = std::shared_lock<std::shared_mutex>(stage_gate_mutex(device));
-  }
-  void release() { if (ex.owns_lock()) ex.unlock(); if (sh.owns_lock()) sh.unlock(); }
-};
-
 struct StageTiming { const char *name; float ms; int64_t launches; };
 // one kernel launch of the frameshift / domain stages, timed with HIP events on the stream it was launched on
 struct KernelSpan { const char *name; hipEvent_t a, b; double cells, bytes; };
@@ -229,14 +202,6 @@ struct bath_hip_ctx {
   const float *fwd_rows_kept = nullptr;
   const int64_t *fwd_rows_off = nullptr;
   bool fs_want_regions = false;           // set by the domain stage: the decision stage also runs the Backward parser and the region heuristics
-  // Speculative Backward (bath_frameshift.hip: fs3_backward_spec): the 3-codon Backward parser of the LONGEST DNA windows runs beside the
-  // Forward parser of all of them, before the branch is known -- the two parsers of a window do not read each other, and the pass lasts
-  // as long as its longest window's Forward, then Backward, then regions' Forward.  fs_spec_rows[w] >= 0: window w's special-state rows
-  // lie at that offset (floats) of scratch[53]; the domain stage runs the parser for the other frameshift-branch windows only.
-  hipStream_t spec_stream = nullptr;
-  hipEvent_t ev_spec = nullptr;
-  bool fs_spec_valid = false;
-  std::vector<int64_t> fs_spec_rows;
   std::vector<int64_t> fs_keep_xoff;      // the decision stage's Forward parser rows stay on the device (scratch[45]): offsets per DNA window, in floats
   std::vector<int32_t> fs_regions_all;    // ... for every DNA window: 1 + 3*fs_max_regions() ints each (bath_frameshift.hip: fs3_regions)
   std::vector<bath_fs_domain> fs_domains; // bath_hip_pipeline_frameshift_domains output

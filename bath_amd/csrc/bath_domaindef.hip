@@ -455,14 +455,11 @@ static int fs_branch_domains(bath_hip_ctx *ctx, const bath_hip_oprofile *om, con
       const bool clusters_beside = beside_env >= 0 ? beside_env == 1 : host_contexts() == 1;      // default: when this is the host's only context
       if (rctx != ctx && clusters_beside) {
         cl_ran = true;
-        static const bool own_ctx = [] { const char *e = std::getenv("BATH_HIP_FS_CLUSTERS_CTX"); return !(e && e[0] == '2'); }();   // 2: on the regions' context
         if (hipSetDevice(ctx->device) != hipSuccess) { cl_rc = BATH_EFAIL; cl_err = "hipSetDevice failed on the clusters' thread"; return; }
-        bath_hip_ctx *cctx = rctx;
-        if (own_ctx) {
-          if (!ctx->aux3 && bath_hip_init(ctx->device, &ctx->aux3) != BATH_OK) { cl_rc = BATH_EFAIL; cl_err = "cannot create the context of the clusters' envelopes"; return; }
-          mark_internal(ctx->aux3);
-          cctx = ctx->aux3; cctx->fs_strict = ctx->fs_strict; cctx->fs_odds = ctx->fs_odds; cctx->fs5_odds = ctx->fs5_odds; cctx->spans_reset();
-        } else if (hipStreamSynchronize(rctx->stream) != hipSuccess) { cl_rc = BATH_EFAIL; cl_err = "the regions' stream failed"; return; }
+        if (!ctx->aux3 && bath_hip_init(ctx->device, &ctx->aux3) != BATH_OK) { cl_rc = BATH_EFAIL; cl_err = "cannot create the context of the clusters' envelopes"; return; }
+        mark_internal(ctx->aux3);
+        bath_hip_ctx *cctx = ctx->aux3;                                         // the clusters' envelopes on a context of their own
+        cctx->fs_strict = ctx->fs_strict; cctx->fs_odds = ctx->fs_odds; cctx->fs5_odds = ctx->fs5_odds; cctx->spans_reset();
         for (size_t e = 0; e < mregs.size(); e++) cl_envs.insert(cl_envs.end(), found[e].begin(), found[e].end());
         if (!cl_envs.empty() && (cl_rc = run_env_batch(cctx, cl_envs.data(), (int)cl_envs.size(), cl_batch)) != BATH_OK) cl_err = cctx->err;
         eclk.lap("fs:   (clusters' envelope kernels + traces, same thread)");

@@ -6,8 +6,8 @@
 //   fs_bwd_kernel<3> <- p7_BackwardParser_Frameshift_3Codons impl_sse/fwdback_fs.c:565  / generic :1422
 //   fs5_fwd_kernel   <- p7_Forward_Frameshift                impl_sse/fwdback_fs.c:2054 / generic :64
 //   fs_bwd_kernel<5> <- p7_Backward_Frameshift               impl_sse/fwdback_fs.c:2634 / generic :1035
-//   fs5_decode_kernel<- p7_Decoding_Frameshift               generic_decoding_frameshift.c:36
-//   fs5_oa_kernel    <- p7_OptimalAccuracy_Frameshift (fill) generic_optacc_frameshift.c:53
+//   fs5_decode_oa_kernel <- p7_Decoding_Frameshift + p7_OptimalAccuracy_Frameshift (fill)
+//                       generic_decoding_frameshift.c:36, generic_optacc_frameshift.c:53
 //   fs5_null2_kernel <- p7_Null2_fs_ByExpectation            generic_null2_frameshift.c:46
 //
 // One wavefront owns one DNA window; lanes own contiguous blocks of model nodes; the nucleotide
@@ -35,107 +35,20 @@ namespace bath {
 // md[c] = M(i,node_c)+tMD(node_c) and dd[c] = tDD(node_c) describe the step OUT of node c.
 // Returns D at the lane's nodes in Dout[]; the step into the lane's first node comes from the previous lane.
 template <int C, bool EXACT>
-__device__ __forceinline__ void d_chain_fwd(const float (&md)[C], const float (&dd)[C], float (&Dout)[C], int lane, const float *tbl) {
+__device__ __forceinline__ void d_chain_fwd(const float (&md)[C], const float (&dd)[C], float (&Dout)[C], const float *tbl) {
   // lane function f(x) = LS(A, x + B): value handed to the next lane's first node
   float A = -INFINITY, B = 0.f;
 #pragma unroll
   for (int c = 0; c < C; c++) { A = flogsum<EXACT>(md[c], A + dd[c], tbl); B += dd[c]; }
-#ifdef BATH_FS_BPERMUTE
-#pragma unroll
-  for (int d = 1; d < 64; d <<= 1) {
-    const float Ap = __shfl_up(A, d, 64), Bp = __shfl_up(B, d, 64);
-    const float An = flogsum<EXACT>(A, Ap + B, tbl);
-    A = (lane >= d) ? An : A; B = (lane >= d) ? B + Bp : B;
-  }
-  float din = __shfl_up(A, 1, 64);
-  if (lane == 0) din = -INFINITY;
-#else
   // lanes without a source see the identity map (A = -inf, B = 0): LS(A, -inf + B) = A, B + 0 = B
 #define BATH_DCHAIN_STEP(CTRL, MASK) { const float Ap = dpp_f<CTRL, MASK>(A, -INFINITY), Bp = dpp_f<CTRL, MASK>(B, 0.f); A = flogsum<EXACT>(A, Ap + B, tbl); B = B + Bp; }
   BATH_DCHAIN_STEP(0x111, 0xf) BATH_DCHAIN_STEP(0x112, 0xf) BATH_DCHAIN_STEP(0x114, 0xf) BATH_DCHAIN_STEP(0x118, 0xf)
   BATH_DCHAIN_STEP(0x142, 0xa) BATH_DCHAIN_STEP(0x143, 0xc)
 #undef BATH_DCHAIN_STEP
   const float din = wave_shr1(A, -INFINITY);
-  (void)lane;
-#endif
   Dout[0] = din;
 #pragma unroll
   for (int c = 1; c < C; c++) Dout[c] = flogsum<EXACT>(md[c - 1], Dout[c - 1] + dd[c - 1], tbl);
-}
-
-// BATH_LOGSUM_TABLE_SERIAL ("strict"): the reference's own order of the sums along the model (generic_fwdback_frameshift.c:
-// 340-365, 577-590): D(i,k) from D(i,k-1) node by node and E(i) accumulated in the same walk, one lane after the other.
-// With the truncating table every log-sum is then the reference's log-sum of the reference's operands: results are
-// bit-identical to the generic reference, at the cost of a 64-step hand-off per row.  Returns E(i).
-template <int C>
-__device__ __forceinline__ float fwd_chain_strict(const float (&Mc)[C], const float (&md)[C], const float (&dd)[C], float (&Dout)[C], int lane, int M,
-                                                  bool pair_first_at_M, const float *tbl) {
-  const int nl = (M + C - 1) / C;                         // lanes that hold nodes
-  float dnext = -INFINITY, e = -INFINITY;                 // D at the first node of the next lane; E after this lane's nodes
-#pragma unroll
-  for (int c = 0; c < C; c++) Dout[c] = -INFINITY;
-  for (int l = 0; l < nl; l++) {
-    const float din = (l == 0) ? -INFINITY : __shfl(dnext, l - 1, 64);
-    const float ein = (l == 0) ? -INFINITY : __shfl(e, l - 1, 64);
-    if (lane == l) {
-      float dcur = din, ecur = ein;
-#pragma unroll
-      for (int c = 0; c < C; c++) {
-        const int node = l * C + c + 1;
-        if (node <= M) {
-          Dout[c] = dcur;
-          if (node == M && pair_first_at_M) ecur = flogsum<false>(flogsum<false>(Mc[c], dcur, tbl), ecur, tbl);   // :392
-          else ecur = flogsum<false>(Mc[c], flogsum<false>(dcur, ecur, tbl), tbl);
-          dcur = flogsum<false>(md[c], dcur + dd[c], tbl);
-        }
-      }
-      dnext = dcur; e = ecur;
-    }
-  }
-  return __shfl(e, nl - 1, 64);
-}
-
-// Backward, strict order: B(i) = a(1)+tBM(0), then LS(B, a(k)+tBM(k-1)) for k = 2..M (generic_fwdback_frameshift.c:1279-1283)
-template <int C>
-__device__ __forceinline__ float bwd_bsum_strict(const float (&term)[C], int lane, int M, const float *tbl) {
-  const int nl = (M + C - 1) / C;
-  float b = -INFINITY;
-  for (int l = 0; l < nl; l++) {
-    const float bin = (l == 0) ? -INFINITY : __shfl(b, 63 - (l - 1), 64);      // (Backward's lanes are in descending order: logical l = physical 63 - l)
-    if (lane == l) {
-      float cur = bin;
-#pragma unroll
-      for (int c = 0; c < C; c++) {
-        const int node = l * C + c + 1;
-        if (node <= M) cur = (node == 1) ? term[c] : flogsum<false>(cur, term[c], tbl);
-      }
-      b = cur;
-    }
-  }
-  return __shfl(b, 63 - (nl - 1), 64);
-}
-
-// ... and the descending D chain: dstep(c, node, D(node+1)) -> D(node) is the row's own formula; returns D at the first node of
-// the NEXT lane (what the lane's last node needs), every value computed in the reference's order.
-template <int C, class F>
-__device__ __forceinline__ float bwd_dnext_strict(F &&dstep, int lane, int M) {
-  const int nl = (M + C - 1) / C;
-  float dfirst = -INFINITY;
-  for (int l = nl - 1; l >= 0; l--) {
-    const float dn_in = (l == nl - 1) ? -INFINITY : __shfl(dfirst, 63 - (l + 1), 64);
-    if (lane == l) {
-      float dn = dn_in;
-#pragma unroll
-      for (int c = C - 1; c >= 0; c--) {
-        const int node = l * C + c + 1;
-        if (node <= M) dn = dstep(c, node, dn);
-      }
-      dfirst = dn;
-    }
-  }
-  float dnext = wave_shr1(dfirst, -INFINITY);                                 // from the logical lane above = the physical lane below
-  if (lane >= nl - 1) dnext = -INFINITY;
-  return dnext;
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -146,7 +59,7 @@ __device__ __forceinline__ float bwd_dnext_strict(F &&dstep, int lane, int M) {
 template <int C, int MODE>
 __global__ __launch_bounds__(kFsBlock, fs_min_waves(C)) void fs3_fwd_kernel(SeqView dna, FsDev p, const float *__restrict__ loop_tab, const float *__restrict__ move_tab,
                                                       float tEL, float tEM, float *__restrict__ sc, float *__restrict__ xmx, const int64_t *__restrict__ xmx_off, FsJobs jobs) {
-  constexpr bool EXACT = (MODE == 1), STRICT = (MODE == 2);   // 0: table + scans, 1: exact log-sums, 2: table in the reference's serial order
+  constexpr bool EXACT = (MODE == 1);   // 0: table + scans, 1: exact log-sums (strict mode runs the chain kernels, bath_fs_chain.hip)
   extern __shared__ __attribute__((aligned(16))) char lds[];
   float *s_tbl = reinterpret_cast<float *>(lds);
   float *s_tf = s_tbl + kLogsumTbl;
@@ -222,18 +135,14 @@ __global__ __launch_bounds__(kFsBlock, fs_min_waves(C)) void fs3_fwd_kernel(SeqV
         md[c] = mv + tb.x; dd[c] = tb.y;
       }
       float Dc[C];
-      float xE;
-      if constexpr (STRICT) xE = fwd_chain_strict<C>(Mc, md, dd, Dc, lane, M, false, s_tbl);
-      else {
-        d_chain_fwd<C, EXACT>(md, dd, Dc, lane, s_tbl);
+      d_chain_fwd<C, EXACT>(md, dd, Dc, s_tbl);
 #pragma unroll
-        for (int c = 0; c < C; c++) {
-          const int node = lane * C + c + 1;
-          Dc[c] = (node <= M) ? Dc[c] : -INFINITY;
-          eloc = LS(Mc[c], LS(Dc[c], eloc));                        // nodes beyond M hold -inf: the sum is unchanged
-        }
-        xE = wave_logsum<EXACT>(eloc, s_tbl);
+      for (int c = 0; c < C; c++) {
+        const int node = lane * C + c + 1;
+        Dc[c] = (node <= M) ? Dc[c] : -INFINITY;
+        eloc = LS(Mc[c], LS(Dc[c], eloc));                          // nodes beyond M hold -inf: the sum is unchanged
       }
+      const float xE = wave_logsum<EXACT>(eloc, s_tbl);
       float nN, nJ, nC, nB;
       if (i == 2) { nN = 0.f; nJ = xE + tEL; nC = xE + tEM; }
       else { nN = xN[2] + tNL; nJ = LS(xJ[2] + tJL, xE + tEL); nC = LS(xC[2] + tCL, xE + tEM); }
@@ -268,7 +177,7 @@ __global__ __launch_bounds__(kFsBlock) void fs5_fwd_kernel(SeqView dna, FsDev p,
                                                       float *__restrict__ fwd, const int64_t *__restrict__ fwd_off, float *__restrict__ xmx, const int64_t *__restrict__ xmx_off,
                                                       int cfg_len /* >= 0: the amino length the model is configured for, instead of L/3 */, FsJobs jobs,
                                                       int *__restrict__ done = nullptr /* host-visible: done[job] = 1 once the job's matrix and score have landed */) {
-  constexpr bool EXACT = (MODE == 1), STRICT = (MODE == 2);   // 0: table + scans, 1: exact log-sums, 2: table in the reference's serial order
+  constexpr bool EXACT = (MODE == 1);   // 0: table + scans, 1: exact log-sums (strict mode runs the chain kernels, bath_fs_chain.hip)
   extern __shared__ __attribute__((aligned(16))) char lds[];
   float *s_tbl = reinterpret_cast<float *>(lds);
   float *s_tf = s_tbl + kLogsumTbl;
@@ -358,30 +267,20 @@ __global__ __launch_bounds__(kFsBlock) void fs5_fwd_kernel(SeqView dna, FsDev p,
         }
       }
       float Dc[C];
-      float xE;
-      if constexpr (STRICT) {
-        xE = fwd_chain_strict<C>(Mc, md, dd, Dc, lane, M, i >= 5, s_tbl);
+      d_chain_fwd<C, EXACT>(md, dd, Dc, s_tbl);
+      float eloc = -INFINITY;
 #pragma unroll
-        for (int c = 0; c < C; c++) {
-          const int node = lane * C + c + 1;
-          if (node <= M) row[(size_t)node * 8] = Dc[c];
-        }
-      } else {
-        d_chain_fwd<C, EXACT>(md, dd, Dc, lane, s_tbl);
-        float eloc = -INFINITY;
-#pragma unroll
-        for (int c = 0; c < C; c++) {
-          const int node = lane * C + c + 1;
-          Dc[c] = (node <= M) ? Dc[c] : -INFINITY;
-          eloc = LS(Mc[c], LS(Dc[c], eloc));
-        }
-#pragma unroll
-        for (int c = 0; c < C; c++) {
-          const int node = lane * C + c + 1;
-          if (node <= M) row[(size_t)node * 8] = Dc[c];
-        }
-        xE = wave_logsum<EXACT>(eloc, s_tbl);
+      for (int c = 0; c < C; c++) {
+        const int node = lane * C + c + 1;
+        Dc[c] = (node <= M) ? Dc[c] : -INFINITY;
+        eloc = LS(Mc[c], LS(Dc[c], eloc));
       }
+#pragma unroll
+      for (int c = 0; c < C; c++) {
+        const int node = lane * C + c + 1;
+        if (node <= M) row[(size_t)node * 8] = Dc[c];
+      }
+      const float xE = wave_logsum<EXACT>(eloc, s_tbl);
       float nN, nJ, nC, nB;
       if (i <= 2) { nN = 0.f; nJ = xE + tEL; nC = xE + tEM; nB = tNM; }           // :126-132, :166-167
       else {
@@ -418,25 +317,23 @@ __global__ __launch_bounds__(kFsBlock) void fs5_fwd_kernel(SeqView dna, FsDev p,
 }
 
 // ---------------------------------------------------------------------------------------------
-// Backward, both codon systems (NCOD = 3: parser, no matrix stored; NCOD = 5: full, 3 cells per node).
-// Only NCOD = 3 is instantiated since round 4: the envelopes' Backward is fs5_bwd_wf_kernel (bath_fs_wavefront.hip) in every mode.
+// 3-codon Backward parser (the envelopes' 5-codon Backward is fs5_bwd_wf_kernel, bath_fs_wavefront.hip).
 // tb[node] = {tMD(k), tMI(k), tMM(k), tDD(k), tDM(k), tII(k), tIM(k), tBM(k-1)}
 // Row types follow the reference: rows without an emitted codon, "tail" rows with no i+3 row,
 // accumulate-left-to-right rows (L-3, L-4) and the main recursion (generic_fwdback_frameshift.c:1054-1323, 1442-1677).
 // ---------------------------------------------------------------------------------------------
-template <int C, int NCOD, int MODE>
+template <int C, int MODE>
 __global__ __launch_bounds__(kFsBlock, fs_min_waves(C)) void fs_bwd_kernel(SeqView dna, FsDev p, const float *__restrict__ loop_tab, const float *__restrict__ move_tab,
                                                      float tEL, float tEM, float *__restrict__ sc,
                                                      float *__restrict__ bck, const int64_t *__restrict__ bck_off, float *__restrict__ xmx, const int64_t *__restrict__ xmx_off, FsJobs jobs) {
-  constexpr bool EXACT = (MODE == 1), STRICT = (MODE == 2);   // 0: table + scans, 1: exact log-sums, 2: table in the reference's serial order
+  constexpr bool EXACT = (MODE == 1);   // 0: table + scans, 1: exact log-sums (strict mode runs the chain kernels, bath_fs_chain.hip)
   extern __shared__ __attribute__((aligned(16))) char lds[];
   float *s_tbl = reinterpret_cast<float *>(lds);
   float *s_tb = s_tbl + kLogsumTbl;
   fs_load_logsum_table(s_tbl, p.logsum);
   for (int i = threadIdx.x; i < (p.M + 2) * 8; i += blockDim.x) s_tb[i] = p.tb[i];
   __syncthreads();
-  constexpr bool FIVE = (NCOD == 5);
-  constexpr int DEG = FIVE ? 1367 : 338;
+  constexpr int DEG = 338;
   constexpr int NR = 5;                             // rows i+1..i+5 of M kept in registers
   const int M = p.M;
   // Lanes own their nodes in DESCENDING order (logical lane = 63 - physical lane): Backward's chains run from node M down, and with
@@ -462,9 +359,8 @@ __global__ __launch_bounds__(kFsBlock, fs_min_waves(C)) void fs_bwd_kernel(SeqVi
       for (int c = 0; c < C; c++) Ir3[r][c] = -INFINITY;
     float xN3[3] = {-INFINITY, -INFINITY, -INFINITY}, xJ3[3] = {-INFINITY, -INFINITY, -INFINITY}, xC3[3] = {-INFINITY, -INFINITY, -INFINITY};
     float n0 = -INFINITY, n1 = -INFINITY, n2 = -INFINITY;           // N(0), N(1), N(2)
-    const int first_emit = FIVE ? L - 1 : L - 2;
-    int t = DEG, u = DEG, v = DEG, w = DEG, x = DEG;
-    if (!FIVE) w = (d[L - 1] < 4) ? d[L - 1] : DEG;
+    const int first_emit = L - 2;
+    int u = DEG, v = DEG, w = (d[L - 1] < 4) ? d[L - 1] : DEG, x = DEG;
 
     for (int i = L; i >= 0; i--) {
       float Mc[C], Ic[C], Dc[C];
@@ -475,27 +371,22 @@ __global__ __launch_bounds__(kFsBlock, fs_min_waves(C)) void fs_bwd_kernel(SeqVi
         xJn = xNn = -INFINITY;
         xE = xCn + tEM;
         // D(i,k) = LS(E, D(i,k+1)+tDD(k)), M(i,k) = LS(E, D(i,k+1)+tMD(k)): reverse chain
-        float dnext;
-        if constexpr (STRICT) {
-          dnext = bwd_dnext_strict<C>([&](int, int node, float dn) { return (node == M) ? xE : LS(xE, dn + s_tb[node * 8 + 3]); }, lane, M);
-        } else {
-          float A = -INFINITY, B = 0.f;              // lane function applied to D(i, last node of lane + 1)
-          // node M's and node M+1's transition rows are -inf: node M falls out of the general formula (LS(E, -inf) = E) and
-          // nodes beyond M are deselected, without a branch per node
+        float A = -INFINITY, B = 0.f;                // lane function applied to D(i, last node of lane + 1)
+        // node M's and node M+1's transition rows are -inf: node M falls out of the general formula (LS(E, -inf) = E) and
+        // nodes beyond M are deselected, without a branch per node
 #pragma unroll
-          for (int c = C - 1; c >= 0; c--) {
-            const int node = lane * C + c + 1;
-            const float tdd = s_tb[imin(node, M + 1) * 8 + 3];
-            const float An = LS(xE, A + tdd);
-            A = (node <= M) ? An : A; B = (node <= M) ? B + tdd : B;
-          }
-          // lanes without a source see the identity map (A = -inf, B = 0)
-#define BATH_BCHAIN_STEP(CTRL, MASK) { const float An = dpp_f<CTRL, MASK>(A, -INFINITY), Bn = dpp_f<CTRL, MASK>(B, 0.f); A = LS(A, An + B); B = B + Bn; }
-          BATH_BCHAIN_STEP(0x111, 0xf) BATH_BCHAIN_STEP(0x112, 0xf) BATH_BCHAIN_STEP(0x114, 0xf) BATH_BCHAIN_STEP(0x118, 0xf)
-          BATH_BCHAIN_STEP(0x142, 0xa) BATH_BCHAIN_STEP(0x143, 0xc)
-#undef BATH_BCHAIN_STEP
-          dnext = wave_shr1(A, -INFINITY);
+        for (int c = C - 1; c >= 0; c--) {
+          const int node = lane * C + c + 1;
+          const float tdd = s_tb[imin(node, M + 1) * 8 + 3];
+          const float An = LS(xE, A + tdd);
+          A = (node <= M) ? An : A; B = (node <= M) ? B + tdd : B;
         }
+        // lanes without a source see the identity map (A = -inf, B = 0)
+#define BATH_BCHAIN_STEP(CTRL, MASK) { const float An = dpp_f<CTRL, MASK>(A, -INFINITY), Bn = dpp_f<CTRL, MASK>(B, 0.f); A = LS(A, An + B); B = B + Bn; }
+        BATH_BCHAIN_STEP(0x111, 0xf) BATH_BCHAIN_STEP(0x112, 0xf) BATH_BCHAIN_STEP(0x114, 0xf) BATH_BCHAIN_STEP(0x118, 0xf)
+        BATH_BCHAIN_STEP(0x142, 0xa) BATH_BCHAIN_STEP(0x143, 0xc)
+#undef BATH_BCHAIN_STEP
+        const float dnext = wave_shr1(A, -INFINITY);
 #pragma unroll
         for (int c = C - 1; c >= 0; c--) {
           const int node = lane * C + c + 1, nd = imin(node, M + 1);
@@ -505,55 +396,33 @@ __global__ __launch_bounds__(kFsBlock, fs_min_waves(C)) void fs_bwd_kernel(SeqVi
           Ic[c] = -INFINITY;
         }
       } else {
-        if (FIVE || i < first_emit) { t = u; u = v; v = w; w = x; }
+        if (i < first_emit) { u = v; v = w; w = x; }
         x = (d[i] < 4) ? d[i] : DEG;                // x_{i+1}
         const int avail = L - i;
         const bool mainrow = (i <= L - 5);
         const bool tail = (avail < 3);
-        const float *r1 = nullptr, *r2 = nullptr, *r3 = nullptr, *r4 = nullptr, *r5 = nullptr;
-        if (FIVE) {
-          r1 = p.rsc + (size_t)imin(x * 341, 1366) * p.pitch;                                          // C1(x): x is the only (and last) base
-          // reversed argument order: the codon's LAST base is the oldest one in the window (:1260-1270)
-          if (avail >= 2) r2 = p.rsc + (size_t)imin(w * 341 + x * 85 + 1, 1365) * p.pitch;
-          if (avail >= 3) r3 = p.rsc + (size_t)imin(v * 341 + w * 85 + x * 21 + 2, 1364) * p.pitch;
-          if (avail >= 4) r4 = p.rsc + (size_t)imin(u * 341 + v * 85 + w * 21 + x * 5 + 3, 1365) * p.pitch;
-          if (avail >= 5) r5 = p.rsc + (size_t)imin(t * 341 + u * 85 + v * 21 + w * 5 + x + 4, 1366) * p.pitch;
-        } else {
-          if (avail >= 2) r2 = p.rsc + (size_t)imin(w * 84 + x * 21, 337) * p.pitch;
-          if (avail >= 3) r3 = p.rsc + (size_t)imin(v * 84 + w * 21 + x * 5 + 1, 336) * p.pitch;
-          if (avail >= 4) r4 = p.rsc + (size_t)imin(u * 84 + v * 21 + w * 5 + x + 2, 337) * p.pitch;
-        }
+        const float *r2 = nullptr, *r3 = nullptr, *r4 = nullptr;
+        if (avail >= 2) r2 = p.rsc + (size_t)imin(w * 84 + x * 21, 337) * p.pitch;
+        if (avail >= 3) r3 = p.rsc + (size_t)imin(v * 84 + w * 21 + x * 5 + 1, 336) * p.pitch;
+        if (avail >= 4) r4 = p.rsc + (size_t)imin(u * 84 + v * 21 + w * 5 + x + 2, 337) * p.pitch;
         // ivx[k] = logsum_c M(i+c,k)+e_c(k);  B(i) = logsum_k ivx[k]+tBM(k-1)
         float ivx[C];
-        [[maybe_unused]] float bterm[C];
         float bloc = -INFINITY;
 #pragma unroll
         for (int c = 0; c < C; c++) {
           // nodes beyond M: their M rows are -inf, so ivx comes out -inf and the B term (transition row M+1 = -inf) drops out
           const int node = lane * C + c + 1, ne = imin(node, M), nd = imin(node, M + 1);
           float a;
-          if (FIVE) {
-            if (mainrow) a = LS(Mr[0][c] + r1[ne], LS(Mr[1][c] + r2[ne], LS(Mr[2][c] + r3[ne], LS(Mr[3][c] + r4[ne], Mr[4][c] + r5[ne]))));
-            else {
-              a = Mr[0][c] + r1[ne];
-              if (avail >= 2) a = LS(a, Mr[1][c] + r2[ne]);
-              if (avail >= 3) a = LS(a, Mr[2][c] + r3[ne]);
-              if (avail >= 4) a = LS(a, Mr[3][c] + r4[ne]);
-            }
-          } else {
-            if (mainrow) a = LS(Mr[1][c] + r2[ne], LS(Mr[2][c] + r3[ne], Mr[3][c] + r4[ne]));
-            else {
-              a = Mr[1][c] + r2[ne];
-              if (avail >= 3) a = LS(a, Mr[2][c] + r3[ne]);
-              if (avail >= 4) a = LS(a, Mr[3][c] + r4[ne]);
-            }
+          if (mainrow) a = LS(Mr[1][c] + r2[ne], LS(Mr[2][c] + r3[ne], Mr[3][c] + r4[ne]));
+          else {
+            a = Mr[1][c] + r2[ne];
+            if (avail >= 3) a = LS(a, Mr[2][c] + r3[ne]);
+            if (avail >= 4) a = LS(a, Mr[3][c] + r4[ne]);
           }
           ivx[c] = a;
-          if constexpr (STRICT) bterm[c] = a + s_tb[nd * 8 + 7];
-          else bloc = LS(bloc, a + s_tb[nd * 8 + 7]);
+          bloc = LS(bloc, a + s_tb[nd * 8 + 7]);
         }
-        if constexpr (STRICT) xBn = bwd_bsum_strict<C>(bterm, lane, M, s_tbl);
-        else xBn = wave_logsum<EXACT>(bloc, s_tbl);
+        xBn = wave_logsum<EXACT>(bloc, s_tbl);
         if (i == 0) {
           n0 = LS(xN3[2] + tNL, xBn + tNM);
           if (xo && lane == 0) { xo[0] = -INFINITY; xo[1] = n0; xo[2] = -INFINITY; xo[3] = xBn; xo[4] = -INFINITY; }
@@ -562,10 +431,7 @@ __global__ __launch_bounds__(kFsBlock, fs_min_waves(C)) void fs_bwd_kernel(SeqVi
         }
         if (tail) { xJn = xBn + tJM; xNn = xBn + tNM; xCn = tCL + tCM; }
         else { xJn = LS(xJ3[2] + tJL, xBn + tJM); xCn = xC3[2] + tCL; xNn = LS(xN3[2] + tNL, xBn + tNM); }
-        // NCOD = 5 is the envelopes' kernel, always unihit (tEL = -inf): E(i) = C(i) + tEM, said without reading J(i) -- so the row's
-        // B reduction feeds N(i) and J(i) only and leaves the chain M/D/I wait for
-        if constexpr (FIVE) xE = xCn + tEM;
-        else xE = LS(xJn + tEL, xCn + tEM);
+        xE = LS(xJn + tEL, xCn + tEM);
         // ivx at node+1 for every node of the lane
         const float ivNext = wave_shr1(ivx[0], -INFINITY);
         // D chain (descending): D(k) = LS(LS(E, D(k+1)+tDD(k)), ivx(k+1)+tDM(k)); a(k) := LS(E, ivx(k+1)+tDM(k)) up to association
@@ -579,25 +445,15 @@ __global__ __launch_bounds__(kFsBlock, fs_min_waves(C)) void fs_bwd_kernel(SeqVi
           const float ivn = (c == C - 1) ? ivNext : ivx[c + 1];
           const float tdd = s_tb[nd * 8 + 3], tdm = s_tb[nd * 8 + 4];
           base[c] = ivn + tdm;
-          if constexpr (!STRICT) {
-            const float An = (!FIVE && !mainrow && !tail) ? LS(A + tdd, LS(xE, base[c])) : LS(LS(xE, A + tdd), base[c]);
-            A = (node <= M) ? An : A; B = (node <= M) ? B + tdd : B;
-          }
+          const float An = (!mainrow && !tail) ? LS(A + tdd, LS(xE, base[c])) : LS(LS(xE, A + tdd), base[c]);
+          A = (node <= M) ? An : A; B = (node <= M) ? B + tdd : B;
         }
-        float dnext;
-        if constexpr (STRICT) {
-          dnext = bwd_dnext_strict<C>([&](int c, int node, float dn) {
-            const float tdd = s_tb[node * 8 + 3];                // node M: tdd = -inf, base = -inf: the formula gives E
-            return (!FIVE && !mainrow && !tail) ? LS(dn + tdd, LS(xE, base[c])) : LS(LS(xE, dn + tdd), base[c]);
-          }, lane, M);
-        } else {
-          // lanes without a source see the identity map (A = -inf, B = 0)
+        // lanes without a source see the identity map (A = -inf, B = 0)
 #define BATH_BCHAIN_STEP(CTRL, MASK) { const float An = dpp_f<CTRL, MASK>(A, -INFINITY), Bn = dpp_f<CTRL, MASK>(B, 0.f); A = LS(A, An + B); B = B + Bn; }
-          BATH_BCHAIN_STEP(0x111, 0xf) BATH_BCHAIN_STEP(0x112, 0xf) BATH_BCHAIN_STEP(0x114, 0xf) BATH_BCHAIN_STEP(0x118, 0xf)
-          BATH_BCHAIN_STEP(0x142, 0xa) BATH_BCHAIN_STEP(0x143, 0xc)
+        BATH_BCHAIN_STEP(0x111, 0xf) BATH_BCHAIN_STEP(0x112, 0xf) BATH_BCHAIN_STEP(0x114, 0xf) BATH_BCHAIN_STEP(0x118, 0xf)
+        BATH_BCHAIN_STEP(0x142, 0xa) BATH_BCHAIN_STEP(0x143, 0xc)
 #undef BATH_BCHAIN_STEP
-          dnext = wave_shr1(A, -INFINITY);
-        }
+        const float dnext = wave_shr1(A, -INFINITY);
 #pragma unroll
         for (int c = C - 1; c >= 0; c--) {
           const int node = lane * C + c + 1, nd = imin(node, M + 1);
@@ -611,7 +467,7 @@ __global__ __launch_bounds__(kFsBlock, fs_min_waves(C)) void fs_bwd_kernel(SeqVi
             mv = LS(dn + tmd, LS(ivn + tmm, xE));
             dv = LS(LS(xE, dn + tdd), base[c]);
             iv_ = ivn + tim;
-          } else if (!FIVE && !mainrow) {
+          } else if (!mainrow) {
             mv = LS(dn + tmd, LS(Ir3[2][c] + tmi, LS(ivn + tmm, xE)));
             dv = LS(dn + tdd, LS(xE, base[c]));
             iv_ = LS(Ir3[2][c] + tii, ivn + tim);
@@ -654,198 +510,10 @@ __global__ __launch_bounds__(kFsBlock, fs_min_waves(C)) void fs_bwd_kernel(SeqVi
 }
 
 // ---------------------------------------------------------------------------------------------
-// Posterior decoding in place on the Forward matrix (generic_decoding_frameshift.c:36-156), plus the
-// column sums null2 needs (generic_null2_frameshift.c:62-68) accumulated in the same pass.
-// One wave per envelope, rows in order.
-// ---------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void fs5_decode_kernel(SeqView dna, int M, const float *__restrict__ loop_tab, const float *__restrict__ bcksc,
-                                                         float *__restrict__ fwd, const int64_t *__restrict__ fwd_off, float *__restrict__ fx, const int64_t *__restrict__ fx_off,
-                                                         const float *__restrict__ bck, const int64_t *__restrict__ bck_off, const float *__restrict__ bx,
-                                                         float *__restrict__ colsum /* [n][(M+1)*8 + 8] */) {
-  const int lane = threadIdx.x & 63;
-  const int64_t wid = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-  const int64_t nw = ((int64_t)gridDim.x * blockDim.x) >> 6;
-  for (int64_t job = wid; job < dna.n; job += nw) {
-    const int L = dna.len[job];
-    if (L < 5) continue;
-    float *f = fwd + fwd_off[job];
-    float *x = fx + fx_off[job];
-    const float *b = bck + bck_off[job];
-    const float *y = bx + fx_off[job];
-    float *cs = colsum + (size_t)job * ((size_t)(M + 1) * 8 + 8);
-    const float overall = bcksc[job];
-    const float tL = loop_tab[L / 3];
-    float N0 = x[1], J0 = x[2], C0 = x[4], N1 = 0, N2 = 0, N3 = 0, J1 = 0, J2 = 0, J3 = 0, C1 = 0, C2 = 0, C3 = 0;
-    for (int k = lane; k < (M + 1) * 8; k += 64) f[k] = 0.f;
-    if (lane < 5) x[lane] = 0.f;
-    for (int i = 1; i <= L; i++) {
-      N3 = N2; N2 = N1; N1 = N0; J3 = J2; J2 = J1; J1 = J0; C3 = C2; C2 = C1; C1 = C0;
-      float *fr = f + (size_t)i * (M + 1) * 8;
-      const float *br = b + (size_t)i * (M + 1) * 3;
-      float dloc = 0.f;
-      if (lane == 0) for (int s = 0; s < 8; s++) fr[s] = 0.f;
-      for (int k = 1 + lane; k <= M; k += 64) {
-        const float bm = br[(size_t)k * 3 + 2], bi = br[(size_t)k * 3 + 1];
-        float *cell = fr + (size_t)k * 8;
-#pragma unroll
-        for (int c = 2; c < 8; c++) cell[c] = expf(cell[c] + bm - overall);
-        dloc += cell[2];
-        if (k < M) { cell[1] = expf(cell[1] + bi - overall); dloc += cell[1]; } else cell[1] = 0.f;
-        cell[0] = 0.f;
-      }
-      N0 = x[i * 5 + 1]; J0 = x[i * 5 + 2]; C0 = x[i * 5 + 4];
-      float pn, pc, pj;
-      if (i > 2) {
-        pn = expf(N3 + y[i * 5 + 1] + tL - overall);
-        pc = expf(C3 + y[i * 5 + 4] + tL - overall);
-        pj = expf(J3 + y[i * 5 + 2] + tL - overall);
-      } else { pn = expf(y[i * 5 + 1] - overall); pc = 0.f; pj = 0.f; }
-      float denom = wave_sum_f32(dloc) + ((i > 2) ? (pn + pj + pc) : pn);
-      denom = (float)(1.0 / (double)denom);
-      for (int k = 1 + lane; k <= M; k += 64) {
-        float *cell = fr + (size_t)k * 8;
-#pragma unroll
-        for (int c = 2; c < 8; c++) { cell[c] *= denom; cs[(size_t)k * 8 + c] += cell[c]; }
-        if (k < M) { cell[1] *= denom; cs[(size_t)k * 8 + 1] += cell[1]; }
-      }
-      pn *= denom; pc *= denom; pj *= denom;
-      if (lane == 0) {
-        x[i * 5 + 0] = 0.f; x[i * 5 + 3] = 0.f; x[i * 5 + 1] = pn; x[i * 5 + 4] = pc; x[i * 5 + 2] = pj;
-        float *xs = cs + (size_t)(M + 1) * 8;
-        xs[1] += pn; xs[2] += pj; xs[4] += pc;
-      }
-    }
-  }
-}
-
-// ---------------------------------------------------------------------------------------------
-// Optimal-accuracy fill (generic_optacc_frameshift.c:53-324): max-sum over posteriors.  TSCDELTA is 1 for a
-// possible transition and FLT_MIN for an impossible one.  oa[(i*(M+1)+k)*3 + {D,I,M}], xmx in ox.
-// The D row is a running maximum along the model: an exact wavefront scan (max is associative).
-// ---------------------------------------------------------------------------------------------
-template <int C>
-__global__ __launch_bounds__(256) void fs5_oa_kernel(SeqView dna, int M, const float *__restrict__ tf /* forward-ordered log transitions */,
-                                                     const float *__restrict__ pp, const int64_t *__restrict__ pp_off, const float *__restrict__ px, const int64_t *__restrict__ px_off,
-                                                     float *__restrict__ oa, const int64_t *__restrict__ oa_off, float *__restrict__ oasc, float ej, float ec,
-                                                     float *__restrict__ ox /* optional: OA special-state rows (L+1) x {E,N,J,B,C} at px_off */) {
-  extern __shared__ __attribute__((aligned(16))) char lds[];
-  float *s_dl = reinterpret_cast<float *>(lds);                 // [(M+2)][8] deltas, same order as tf
-  for (int i = threadIdx.x; i < (M + 2) * 8; i += blockDim.x) s_dl[i] = (tf[i] == -INFINITY) ? 1.17549435e-38f : 1.0f;
-  __syncthreads();
-  const int lane = threadIdx.x & 63;
-  const int64_t wid = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-  const int64_t nw = ((int64_t)gridDim.x * blockDim.x) >> 6;
-  for (int64_t job = wid; job < dna.n; job += nw) {
-    const int L = dna.len[job];
-    if (L < 5) { if (lane == 0) oasc[job] = -INFINITY; continue; }
-    const float *P = pp + pp_off[job];
-    const float *X = px + px_off[job];
-    float *O = oa + oa_off[job];
-    float *OX = ox ? ox + px_off[job] : nullptr;
-    if (OX && lane == 0) { OX[0] = -INFINITY; OX[1] = 0.f; OX[2] = -INFINITY; OX[3] = 0.f; OX[4] = -INFINITY; }
-    // rows i-1..i-5 of M, I, D and B; rows i-1..i-3 of N, J, C
-    float Mr[5][C], Ir[5][C], Dr[5][C];
-#pragma unroll
-    for (int r = 0; r < 5; r++)
-#pragma unroll
-      for (int c = 0; c < C; c++) Mr[r][c] = Ir[r][c] = Dr[r][c] = -INFINITY;
-    float Bh[5] = {0.f, -INFINITY, -INFINITY, -INFINITY, -INFINITY};      // B(i-1) ... ; B(0) = 0
-    float Nh[3] = {0.f, 0.f, 0.f}, Jh[3] = {-INFINITY, -INFINITY, -INFINITY}, Ch[3] = {-INFINITY, -INFINITY, -INFINITY};
-    float cL = -INFINITY, cL1 = -INFINITY, cL2 = -INFINITY;
-    for (int k = lane; k <= M; k += 64) { O[(size_t)k * 3] = O[(size_t)k * 3 + 1] = O[(size_t)k * 3 + 2] = -INFINITY; }
-    for (int i = 1; i <= L; i++) {
-      const float *pr = P + (size_t)i * (M + 1) * 8;
-      float *orow = O + (size_t)i * (M + 1) * 3;
-      if (lane == 0) orow[0] = orow[1] = orow[2] = -INFINITY;
-      float mIn[5], iIn[5], dIn[5];
-#pragma unroll
-      for (int r = 0; r < 5; r++) {
-        mIn[r] = wave_shr1(Mr[r][C - 1], -INFINITY); iIn[r] = wave_shr1(Ir[r][C - 1], -INFINITY); dIn[r] = wave_shr1(Dr[r][C - 1], -INFINITY);
-      }
-      float Mc[C], Ic[C], am[C], bm[C];
-      float eloc = -INFINITY;
-#pragma unroll
-      for (int c = 0; c < C; c++) {
-        const int node = lane * C + c + 1;
-        if (node > M) { Mc[c] = Ic[c] = -INFINITY; am[c] = -INFINITY; bm[c] = 1.0f; continue; }
-        const float dMM = s_dl[node * 8 + 0], dIM = s_dl[node * 8 + 1], dDM = s_dl[node * 8 + 2], dBM = s_dl[node * 8 + 3];
-        const float dMD = s_dl[node * 8 + 4], dDD = s_dl[node * 8 + 5], dMI = s_dl[node * 8 + 6], dII = s_dl[node * 8 + 7];
-        const float *cell = pr + (size_t)node * 8;
-        float best;
-        if (i == 1) best = dBM * cell[3];
-        else {
-          float mx[6];
-          const int cmax = (i >= 5) ? 5 : (i == 2 ? 2 : (i == 4 ? 4 : 3));
-#pragma unroll
-          for (int cl = 1; cl <= 5; cl++) {
-            if (cl > cmax) { mx[cl] = -INFINITY; continue; }
-            const float pv = cell[2 + cl];
-            if ((i == 2 && cl == 2) || (i == 4 && cl == 4)) mx[cl] = dBM * (0.0f + pv);     // only B(0)=0 can precede
-            else {
-              const int r = cl - 1;
-              const float m1 = (c == 0) ? mIn[r] : Mr[r][c - 1], i1 = (c == 0) ? iIn[r] : Ir[r][c - 1], d1 = (c == 0) ? dIn[r] : Dr[r][c - 1];
-              mx[cl] = fmaxf(dMM * (m1 + pv), fmaxf(dIM * (i1 + pv), fmaxf(dDM * (d1 + pv), dBM * (Bh[r] + pv))));
-            }
-          }
-          if (i == 2) best = fmaxf(mx[1], mx[2]);
-          else if (i < 5) best = fmaxf(fmaxf(mx[1], mx[2]), fmaxf(mx[3], mx[4]));
-          else best = fmaxf(fmaxf(mx[1], mx[2]), fmaxf(fmaxf(mx[3], mx[4]), mx[5]));
-        }
-        Mc[c] = best;
-        Ic[c] = (i >= 3 && node < M) ? fmaxf(dMI * (Mr[2][c] + cell[1]), dII * (Ir[2][c] + cell[1])) : -INFINITY;
-        am[c] = dMD * best;                       // contribution to D(node+1) from M(node)
-        bm[c] = dDD;                              // multiplier on D(node) into D(node+1)
-        // NB tf[node] holds the transitions OUT of node for MD,DD (k) and INTO node for MM.. (k-1); the reference's
-        // D(i,k) uses TSCDELTA(MD,k-1), (DD,k-1): i.e. the out-of-(k-1) deltas, which is what am/bm of node k-1 are.
-      }
-      // D(node+1) = max(am(node), bm(node) * D(node)): scan of x -> max(A, B*x)
-      float A = -INFINITY, Bm = 1.0f;
-#pragma unroll
-      for (int c = 0; c < C; c++) { A = fmaxf(am[c], bm[c] * A); Bm *= bm[c]; }
-      // lanes without a source see the identity map (A = -inf, B = 1); fmaxf ignores the NaN of 0 * -inf when B has underflowed
-#define BATH_OA_STEP(CTRL, MASK) { const float Ap = dpp_f<CTRL, MASK>(A, -INFINITY), Bp = dpp_f<CTRL, MASK>(Bm, 1.0f); A = fmaxf(A, Bm * Ap); Bm *= Bp; }
-      BATH_OA_STEP(0x111, 0xf) BATH_OA_STEP(0x112, 0xf) BATH_OA_STEP(0x114, 0xf) BATH_OA_STEP(0x118, 0xf) BATH_OA_STEP(0x142, 0xa) BATH_OA_STEP(0x143, 0xc)
-#undef BATH_OA_STEP
-      const float din = wave_shr1(A, -INFINITY);
-      float Dc[C];
-      Dc[0] = din;
-#pragma unroll
-      for (int c = 1; c < C; c++) Dc[c] = fmaxf(am[c - 1], bm[c - 1] * Dc[c - 1]);
-#pragma unroll
-      for (int c = 0; c < C; c++) {
-        const int node = lane * C + c + 1;
-        if (node > M) { Dc[c] = -INFINITY; continue; }
-        orow[(size_t)node * 3 + 0] = Dc[c]; orow[(size_t)node * 3 + 1] = Ic[c]; orow[(size_t)node * 3 + 2] = Mc[c];
-        eloc = fmaxf(eloc, (node < M) ? Mc[c] : fmaxf(Mc[c], Dc[c]));
-      }
-      float xE = eloc;                                      // wave maximum: running maximum by DPP, last lane broadcast (max is exact in any order)
-      xE = fmaxf(xE, dpp_f<0x111>(xE, -INFINITY)); xE = fmaxf(xE, dpp_f<0x112>(xE, -INFINITY)); xE = fmaxf(xE, dpp_f<0x114>(xE, -INFINITY));
-      xE = fmaxf(xE, dpp_f<0x118>(xE, -INFINITY)); xE = fmaxf(xE, dpp_f<0x142, 0xa>(xE, -INFINITY)); xE = fmaxf(xE, dpp_f<0x143, 0xc>(xE, -INFINITY));
-      xE = wave_bcast_last(xE);
-      float nN, nJ, nC;
-      if (i <= 2) { nJ = ej * xE; nC = ec * xE; nN = X[i * 5 + 1]; }
-      else { nJ = fmaxf(Jh[2] + X[i * 5 + 2], ej * xE); nC = fmaxf(Ch[2] + X[i * 5 + 4], ec * xE); nN = Nh[2] + X[i * 5 + 1]; }
-      const float nB = fmaxf(nN, nJ);
-      if (OX && lane == 0) { float *r = OX + (size_t)i * 5; r[0] = xE; r[1] = nN; r[2] = nJ; r[3] = nB; r[4] = nC; }
-      Nh[2] = Nh[1]; Nh[1] = Nh[0]; Nh[0] = nN;
-      Jh[2] = Jh[1]; Jh[1] = Jh[0]; Jh[0] = nJ;
-      Ch[2] = Ch[1]; Ch[1] = Ch[0]; Ch[0] = nC;
-      Bh[4] = Bh[3]; Bh[3] = Bh[2]; Bh[2] = Bh[1]; Bh[1] = Bh[0]; Bh[0] = nB;
-      cL2 = cL1; cL1 = cL; cL = nC;
-#pragma unroll
-      for (int c = 0; c < C; c++) {
-#pragma unroll
-        for (int r = 4; r > 0; r--) { Mr[r][c] = Mr[r - 1][c]; Ir[r][c] = Ir[r - 1][c]; Dr[r][c] = Dr[r - 1][c]; }
-        Mr[0][c] = Mc[c]; Ir[0][c] = Ic[c]; Dr[0][c] = Dc[c];
-      }
-    }
-    if (lane == 0) oasc[job] = cL + cL1 + cL2;
-  }
-}
-
-// ---------------------------------------------------------------------------------------------
-// Posterior decoding AND the optimal-accuracy fill in one walk over the rows (fs5_decode_kernel + fs5_oa_kernel fused).
-// Both go through the rows in ascending order and the OA row needs exactly the posteriors decoding has just produced, so the
+// Posterior decoding (generic_decoding_frameshift.c:36-156, with the column sums null2 needs, generic_null2_frameshift.c:62-68)
+// AND the optimal-accuracy fill (generic_optacc_frameshift.c:53-324; TSCDELTA is 1 for a possible transition, FLT_MIN for an
+// impossible one) in one walk over the rows.  Both go through the rows in ascending order and the OA row needs exactly the
+// posteriors decoding has just produced, so the
 // posteriors are taken from registers instead of being written (32 B/cell) and read back (32 B/cell) by a second kernel: the
 // pass reads Forward (32 B) and Backward (12 B) and writes the posteriors (32 B, for the traceback) and the OA cells (12 B),
 // 88 B/cell instead of 120, and -- what matters more for these latency-bound kernels -- one chain of dependent rows instead of
@@ -1734,11 +1402,11 @@ static int fs_columns(int M) {
     default: ctx->set_error("frameshift kernels support models up to 1280 nodes"); return BATH_EINVAL; \
   }
 
-// logsum_mode -> kernel MODE: 0 table + wavefront scans, 1 exact log-sums, 2 table in the reference's serial order ("strict")
+// logsum_mode -> kernel MODE: 0 table + wavefront scans, 1 exact log-sums (BATH_LOGSUM_TABLE_SERIAL, "strict", runs the chain
+// kernels of bath_fs_chain.hip instead)
 #define BATH_FS_MODE(modev, BODY)                         \
   switch (modev) {                                        \
     case 1: { constexpr int MD = 1; BODY } break;         \
-    case 2: { constexpr int MD = 2; BODY } break;         \
     default: { constexpr int MD = 0; BODY } break;        \
   }
 
@@ -1749,9 +1417,6 @@ static int fs3_ctx_mode(const bath_hip_ctx *ctx) {
 
 static FsDev fsdev(const bath_hip_fsprofile *om) { return FsDev{om->M, om->pitch, om->maxcodons, om->d_rsc, om->d_tf, om->d_tb, om->d_logsum}; }
 
-static int fs_grid(bath_hip_ctx *ctx, int64_t n) {
-  return (int)std::max<int64_t>(1, std::min<int64_t>((n + 3) / 4, (int64_t)ctx->prop.multiProcessorCount * 2));
-}
 static int fs_grid_dp(bath_hip_ctx *ctx, int64_t n) {           // blocks of kFsBlock threads, two per CU
   const int wpb = kFsBlock / 64;
   return (int)std::max<int64_t>(1, std::min<int64_t>((n + wpb - 1) / wpb, (int64_t)ctx->prop.multiProcessorCount * 2));
@@ -1788,8 +1453,7 @@ static int fs_schedule(bath_hip_ctx *ctx, const bath_hip_seqs *dna, int k, FsJob
 }  // namespace bath
 
 static int fs3_parser(bath_hip_ctx *ctx, const bath_hip_fsprofile *om, const bath_hip_seqs *dna, int logsum_mode, float *sc, float *xmx,
-                      const int64_t *xmx_off, bool backward, DevBuf *keep = nullptr /* the rows stay in this device buffer instead of going to <xmx> */,
-                      const std::function<int()> *after_launch = nullptr /* runs between the kernel's launch and the wait for it */) {
+                      const int64_t *xmx_off, bool backward, DevBuf *keep = nullptr /* the rows stay in this device buffer instead of going to <xmx> */) {
   if (!ctx || !om || !dna || om->codon_lengths != 3) { if (ctx) ctx->set_error("fs3 parser needs a 3-codon profile"); return BATH_EINVAL; }
   BATH_HIP_TRY(ctx, hipSetDevice(ctx->device));
   if (fs_model_ok(ctx, om) != BATH_OK) return BATH_EINVAL;
@@ -1810,18 +1474,15 @@ static int fs3_parser(bath_hip_ctx *ctx, const bath_hip_fsprofile *om, const bat
   const int Cv = fs_columns(om->M);
   const size_t shmem = (size_t)(kLogsumTbl + (om->M + 2) * 8) * sizeof(float);
   const float tE = (float)-0.69314718055994529;
-  [[maybe_unused]] const int grid = fs_grid(ctx, n);
   const int grid_dp = fs_grid_dp(ctx, n);
   FsJobs jq[1];
   if ((st = fs_schedule(ctx, dna, 1, jq)) != BATH_OK) return st;
-  const bool chain = logsum_mode == BATH_LOGSUM_TABLE_SERIAL && fs_chain_enabled();
-  StageGate gate(chain ? ctx->device : -1, backward ? StageGate::kBwdChain : StageGate::kFwdChain);   // held until this stage's kernels have finished (the synchronize below)
   const bool odds = logsum_mode == BATH_LOGSUM_ODDS;
   const int sp = ctx->span_begin(odds ? (backward ? "fs3_bwd_odds_kernel" : "fs3_fwd_odds_kernel") : (backward ? "fs_bwd_kernel<3>" : "fs3_fwd_kernel"), ctx->stream,
                                  (double)dna->total * om->M, (double)dna->total * ((xmx || keep) ? 21.0 : 1.0));
   if (odds) {
     if ((st = launch_fs3_odds(ctx, ctx->stream, om, dna, backward, b_sc.as<float>(), d_x, b_off.as<int64_t>(), jq[0])) != BATH_OK) return st;
-  } else if (logsum_mode == BATH_LOGSUM_TABLE_SERIAL && fs_chain_enabled()) {
+  } else if (logsum_mode == BATH_LOGSUM_TABLE_SERIAL) {
     if (!backward) st = launch_fs3_fwd_chain(ctx, ctx->stream, om, dna, Cv, tE, tE, b_sc.as<float>(), d_x, b_off.as<int64_t>(), jq[0]);
     else st = launch_fs3_bwd_chain(ctx, ctx->stream, om, dna, Cv, tE, tE, b_sc.as<float>(), d_x, b_off.as<int64_t>(), jq[0]);
     if (st != BATH_OK) return st;
@@ -1831,13 +1492,12 @@ static int fs3_parser(bath_hip_ctx *ctx, const bath_hip_fsprofile *om, const bat
       if ((st = fs_set_shmem(ctx, fs3_fwd_kernel<CC, MD>, shmem)) != BATH_OK) return st;
       hipLaunchKernelGGL((fs3_fwd_kernel<CC, MD>), dim3(grid_dp), dim3(kFsBlock), shmem, ctx->stream, dna->view(), fsdev(om), om->d_loop[0], om->d_move[0], tE, tE, b_sc.as<float>(), d_x, b_off.as<int64_t>(), jq[0]);
     } else {
-      if ((st = fs_set_shmem(ctx, fs_bwd_kernel<CC, 3, MD>, shmem)) != BATH_OK) return st;
-      hipLaunchKernelGGL((fs_bwd_kernel<CC, 3, MD>), dim3(grid_dp), dim3(kFsBlock), shmem, ctx->stream, dna->view(), fsdev(om), om->d_loop[0], om->d_move[0], tE, tE, b_sc.as<float>(), (float *)nullptr, (const int64_t *)nullptr, d_x, b_off.as<int64_t>(), jq[0]);
+      if ((st = fs_set_shmem(ctx, fs_bwd_kernel<CC, MD>, shmem)) != BATH_OK) return st;
+      hipLaunchKernelGGL((fs_bwd_kernel<CC, MD>), dim3(grid_dp), dim3(kFsBlock), shmem, ctx->stream, dna->view(), fsdev(om), om->d_loop[0], om->d_move[0], tE, tE, b_sc.as<float>(), (float *)nullptr, (const int64_t *)nullptr, d_x, b_off.as<int64_t>(), jq[0]);
     }
   }))
   ctx->span_end(sp, ctx->stream);
   BATH_HIP_TRY(ctx, hipGetLastError());
-  if (after_launch && *after_launch && (st = (*after_launch)()) != BATH_OK) return st;
   BATH_HIP_TRY(ctx, hipMemcpyAsync(sc, b_sc.p, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
   if (xmx) BATH_HIP_TRY(ctx, hipMemcpyAsync(xmx, d_x, (size_t)xmx_off[n] * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
   BATH_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
@@ -1931,12 +1591,6 @@ int fs_max_regions() { return kMaxRegions; }
 // row chain: run Backward on the context's side stream while Forward runs on the main one.
 int fs_fork(bath_hip_ctx *ctx) {
   if (!ctx->side_stream) {
-    static const bool lowprio = [] { const char *e = std::getenv("BATH_HIP_FS_SIDE_LOWPRIO"); return e && e[0] == '1'; }();   // (probe)
-    if (lowprio) {
-      int lo = 0, hi = 0;
-      BATH_HIP_TRY(ctx, hipDeviceGetStreamPriorityRange(&lo, &hi));
-      BATH_HIP_TRY(ctx, hipStreamCreateWithPriority(&ctx->side_stream, hipStreamNonBlocking, lo));
-    } else
     BATH_HIP_TRY(ctx, hipStreamCreateWithFlags(&ctx->side_stream, hipStreamNonBlocking));
     BATH_HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_fork, hipEventDisableTiming));
     BATH_HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_join, hipEventDisableTiming));
@@ -1948,80 +1602,6 @@ int fs_fork(bath_hip_ctx *ctx) {
 int fs_join(bath_hip_ctx *ctx) {
   BATH_HIP_TRY(ctx, hipEventRecord(ctx->ev_join, ctx->side_stream));
   BATH_HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_join, 0));
-  return BATH_OK;
-}
-
-// rows of the selected windows from one buffer into another: (len + 1) x 5 floats each, a block per window
-__global__ void fs_rows_copy_kernel(int n, const int32_t *__restrict__ len, const int64_t *__restrict__ src_off /* -1: nothing to copy */, const float *__restrict__ src,
-                                    const int64_t *__restrict__ dst_off, float *__restrict__ dst) {
-  const int w = blockIdx.x;
-  if (w >= n || src_off[w] < 0) return;
-  const int cnt = (len[w] + 1) * 5;
-  const float *a = src + src_off[w];
-  float *b = dst + dst_off[w];
-  for (int i = threadIdx.x; i < cnt; i += blockDim.x) b[i] = a[i];
-}
-
-// Speculative Backward (strict mode, a host with ONE context at work): the 3-codon Backward parser of the <k> longest windows of
-// <dna> on the context's speculation stream, beside whatever follows on the main stream -- the Forward parser of all windows.
-// The pass is a chain of stages each as long as its longest window (Forward 9.4 ms, then Backward 14.2 ms on the bench block);
-// the two parsers of a window do not read each other, only the DECISION to run Backward reads Forward's score (p7_pipeline.c:1464-1470).
-// Rows go to scratch[53] at the offsets fs_spec_rows records; fs3_regions (the domain stage) waits for the stream, runs the parser
-// for the frameshift-branch windows that were not among the <k>, and takes the others' rows from here.  What the speculation computes
-// for windows that turn out to take the standard branch is thrown away: CU time nothing else of this context could use, which is
-// why a host running several worker contexts does not speculate (bath_pipeline.hip).
-int fs3_backward_spec(bath_hip_ctx *ctx, const bath_hip_fsprofile *om, const bath_hip_seqs *dna, int k) {
-  ctx->fs_spec_valid = false;
-  const int64_t n = dna->n;
-  if (n == 0 || k <= 0 || !ctx->fs_strict || ctx->fs_odds || !fs_chain_enabled() || om->codon_lengths != 3) return BATH_OK;   // (odds mode: its Backward rows would be strict-mode rows)
-  int st = om->ensure_len(dna->maxlen / 3 + 1);
-  if (st != BATH_OK) return st;
-  if (!ctx->spec_stream) {
-    BATH_HIP_TRY(ctx, hipStreamCreateWithFlags(&ctx->spec_stream, hipStreamNonBlocking));
-    BATH_HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_spec, hipEventDisableTiming));
-  }
-  std::vector<int32_t> order((size_t)n);
-  for (int64_t i = 0; i < n; i++) order[(size_t)i] = (int32_t)i;
-  std::stable_sort(order.begin(), order.end(), [&](int32_t a, int32_t b) { return dna->h_len[(size_t)a] > dna->h_len[(size_t)b]; });
-  k = (int)std::min<int64_t>(k, n);
-  order.resize((size_t)k);
-  // rows of the chosen windows back to back; every other window: -1
-  ctx->fs_spec_rows.assign((size_t)n, -1);
-  std::vector<int64_t> xoff((size_t)n, 0);
-  int64_t tot = 0;
-  for (int32_t w : order) { ctx->fs_spec_rows[(size_t)w] = tot; xoff[(size_t)w] = tot; tot += ((int64_t)dna->h_len[(size_t)w] + 1) * 5; }
-  DevBuf &b_rows = ctx->scratch[53], &b_aux = ctx->scratch[54];
-  BATH_HIP_TRY(ctx, b_rows.reserve((size_t)tot * sizeof(float) + 64));
-  // aux: job counter (256 B), order list, per-window row offsets, scores
-  const size_t o_ord = 256, o_xoff = o_ord + (((size_t)k * 4 + 255) & ~(size_t)255), o_sc = o_xoff + (((size_t)n * 8 + 255) & ~(size_t)255);
-  BATH_HIP_TRY(ctx, b_aux.reserve(o_sc + (size_t)n * 4 + 64));
-  hipStream_t s = ctx->spec_stream;
-  // (the windows' pool was gathered on ctx->stream BEFORE the Forward parser's launch, and the side stream was forked behind the
-  // gather: ev_fork is that point, so the speculation does not wait for Forward)
-  BATH_HIP_TRY(ctx, hipStreamWaitEvent(s, ctx->ev_fork, 0));
-  BATH_HIP_TRY(ctx, hipMemsetAsync(b_aux.p, 0, 256, s));
-  if (ctx->stage[8].reserve((size_t)k * 4 + (size_t)n * 8 + 64) != hipSuccess) { ctx->set_error("cannot allocate page-locked staging memory"); return BATH_EFAIL; }
-  char *hs = static_cast<char *>(ctx->stage[8].p);
-  std::memcpy(hs, order.data(), (size_t)k * 4);
-  std::memcpy(hs + (size_t)k * 4, xoff.data(), (size_t)n * 8);
-  BATH_HIP_TRY(ctx, hipMemcpyAsync(b_aux.as<char>() + o_ord, hs, (size_t)k * 4, hipMemcpyHostToDevice, s));
-  BATH_HIP_TRY(ctx, hipMemcpyAsync(b_aux.as<char>() + o_xoff, hs + (size_t)k * 4, (size_t)n * 8, hipMemcpyHostToDevice, s));
-  // the launcher sizes its blocks and batches from a block's host arrays: a shadow of <dna> that holds the chosen windows only
-  // (the kernel addresses windows by their index in <dna> through the order list; n = the length of that list)
-  bath_hip_seqs shadow;
-  shadow.ctx = ctx; shadow.is_part = true; shadow.n = k; shadow.d_data = dna->d_data; shadow.d_off = dna->d_off; shadow.d_len = dna->d_len;
-  shadow.h_len.resize((size_t)k);
-  shadow.maxlen = 0; shadow.total = 0;
-  for (int i = 0; i < k; i++) { const int32_t L = dna->h_len[(size_t)order[(size_t)i]]; shadow.h_len[(size_t)i] = L; shadow.maxlen = std::max(shadow.maxlen, L); shadow.total += L; }
-  const FsJobs jq{reinterpret_cast<const int32_t *>(b_aux.as<char>() + o_ord), b_aux.as<unsigned>()};
-  const float tE = (float)-0.69314718055994529;
-  const int sp = ctx->span_begin("fs_bwd_kernel<3> (speculative)", s, (double)(tot / 5) * om->M, (double)(tot / 5) * 21.0);
-  st = launch_fs3_bwd_chain(ctx, s, om, &shadow, fs_columns(om->M), tE, tE, reinterpret_cast<float *>(b_aux.as<char>() + o_sc), b_rows.as<float>(),
-                            reinterpret_cast<const int64_t *>(b_aux.as<char>() + o_xoff), jq, 4, 57, 9);
-  ctx->span_end(sp, s);
-  shadow.d_data = nullptr; shadow.d_off = nullptr; shadow.d_len = nullptr;   // borrowed
-  if (st != BATH_OK) return st;
-  ctx->fs_spec_valid = true;
   return BATH_OK;
 }
 
@@ -2060,48 +1640,14 @@ int fs3_regions(bath_hip_ctx *ctx, const bath_hip_fsprofile *om, const bath_hip_
   const int Cv = fs_columns(om->M);
   const size_t shmem = (size_t)(kLogsumTbl + (om->M + 2) * 8) * sizeof(float);
   const float tE = (float)-0.69314718055994529;
-  [[maybe_unused]] const int grid = fs_grid(ctx, n);
   const int grid_dp = fs_grid_dp(ctx, n);
   BATH_HIP_TRY(ctx, b_sc.reserve((size_t)n * 2 * sizeof(float)));
   FsJobs jq[2];
   if ((st = fs_schedule(ctx, dna, 2, jq)) != BATH_OK) return st;
-  // Speculative rows (fs3_backward_spec): window q of <dna> is window kept[q] of the decision stage's block; when its Backward rows are
-  // already in scratch[53] the parser below skips it (a job list of the OTHER windows, longest first; the launcher sees a shadow of
-  // <dna> that holds only those) and a copy kernel puts the rows where the region heuristics read them
-  const bool spec = reuse && ctx->fs_spec_valid && ctx->fs_strict && !ctx->fs_odds && fs_chain_enabled();
-  std::vector<int64_t> spec_src;
-  bath_hip_seqs rest;
-  const bath_hip_seqs *bwd_dna = dna;
-  int64_t n_rest = n;
-  if (spec) {
-    spec_src.assign((size_t)n, -1);
-    std::vector<int32_t> ord;
-    for (int64_t q = 0; q < n; q++) {
-      const int64_t at = ctx->fs_spec_rows[(size_t)kept[q]];
-      if (at >= 0) spec_src[(size_t)q] = at; else ord.push_back((int32_t)q);
-    }
-    std::stable_sort(ord.begin(), ord.end(), [&](int32_t a, int32_t b) { return dna->h_len[(size_t)a] > dna->h_len[(size_t)b]; });
-    n_rest = (int64_t)ord.size();
-    DevBuf &b_sp = ctx->scratch[55];                                          // counter, the rest's job list, the speculative rows' offsets
-    const size_t o_ord = 256, o_src = o_ord + (((size_t)std::max<int64_t>(n_rest, 1) * 4 + 255) & ~(size_t)255);
-    BATH_HIP_TRY(ctx, b_sp.reserve(o_src + (size_t)n * 8 + 64));
-    BATH_HIP_TRY(ctx, hipMemsetAsync(b_sp.p, 0, 256, ctx->stream));
-    if (ctx->stage[10].reserve((size_t)n_rest * 4 + (size_t)n * 8 + 64) != hipSuccess) { ctx->set_error("cannot allocate page-locked staging memory"); return BATH_EFAIL; }
-    char *hs = static_cast<char *>(ctx->stage[10].p);
-    if (n_rest) std::memcpy(hs, ord.data(), (size_t)n_rest * 4);
-    std::memcpy(hs + (size_t)n_rest * 4, spec_src.data(), (size_t)n * 8);
-    if (n_rest) BATH_HIP_TRY(ctx, hipMemcpyAsync(b_sp.as<char>() + o_ord, hs, (size_t)n_rest * 4, hipMemcpyHostToDevice, ctx->stream));
-    BATH_HIP_TRY(ctx, hipMemcpyAsync(b_sp.as<char>() + o_src, hs + (size_t)n_rest * 4, (size_t)n * 8, hipMemcpyHostToDevice, ctx->stream));
-    jq[1] = FsJobs{reinterpret_cast<const int32_t *>(b_sp.as<char>() + o_ord), b_sp.as<unsigned>()};
-    rest.ctx = ctx; rest.is_part = true; rest.n = n_rest; rest.d_data = dna->d_data; rest.d_off = dna->d_off; rest.d_len = dna->d_len;
-    rest.h_len.resize((size_t)n_rest); rest.maxlen = 0; rest.total = 0;
-    for (int64_t i = 0; i < n_rest; i++) { const int32_t L = dna->h_len[(size_t)ord[(size_t)i]]; rest.h_len[(size_t)i] = L; rest.maxlen = std::max(rest.maxlen, L); rest.total += L; }
-    bwd_dna = &rest;
-  }
-  struct Borrowed { bath_hip_seqs &v; ~Borrowed() { v.d_data = nullptr; v.d_off = nullptr; v.d_len = nullptr; } } rest_guard{rest};
   const int mode = fs3_ctx_mode(ctx);
-  static const int spec_share = [] { const char *e = std::getenv("BATH_HIP_FS_SPEC_SHARE"); return e ? std::max(1, std::atoi(e)) : 2; }();   // (probe) CUs each parser's launch is sized for: all / this
-  StageGate gate((mode == BATH_LOGSUM_TABLE_SERIAL && fs_chain_enabled()) ? ctx->device : -1, reuse ? StageGate::kBwdChain : StageGate::kFwdChain);   // held until the synchronize below
+  // strict mode: CUs each parser's launch is sized for when both run side by side -- half the chip each; Backward alone when the
+  // Forward rows are reused
+  constexpr int kParserCuShare = 2;
   if ((st = fs_fork(ctx)) != BATH_OK) return st;
   const double cells3 = (double)(xoff[(size_t)n] / 5) * om->M;                // rows x nodes; algorithmic HBM bytes: 1 B/nt in + 20 B/row out
   const double bytes3 = (double)(xoff[(size_t)n] / 5) * 21.0;
@@ -2112,33 +1658,26 @@ int fs3_regions(bath_hip_ctx *ctx, const bath_hip_fsprofile *om, const bath_hip_
     const int s2 = ctx->span_begin("fs3_bwd_odds_kernel", ctx->side_stream, cells3, bytes3);
     if ((st = launch_fs3_odds(ctx, ctx->side_stream, om, dna, true, b_sc.as<float>() + n, b_bx.as<float>(), b_off.as<int64_t>(), jq[1])) != BATH_OK) return st;
     ctx->span_end(s2, ctx->side_stream);
+  } else if (mode == BATH_LOGSUM_TABLE_SERIAL) {
+    const int s1 = reuse ? -1 : ctx->span_begin("fs3_fwd_kernel", ctx->stream, cells3, bytes3);
+    if (!reuse && (st = launch_fs3_fwd_chain(ctx, ctx->stream, om, dna, Cv, tE, tE, b_sc.as<float>(), b_fx.as<float>(), b_off.as<int64_t>(), jq[0], kParserCuShare)) != BATH_OK) return st;
+    ctx->span_end(s1, ctx->stream);
+    const int s2 = ctx->span_begin("fs_bwd_kernel<3>", ctx->side_stream, cells3, bytes3);
+    if ((st = launch_fs3_bwd_chain(ctx, ctx->side_stream, om, dna, Cv, tE, tE, b_sc.as<float>() + n, b_bx.as<float>(), b_off.as<int64_t>(), jq[1], reuse ? 1 : kParserCuShare)) != BATH_OK) return st;
+    ctx->span_end(s2, ctx->side_stream);
   } else
   BATH_FS_SWITCH(Cv, BATH_FS_MODE(mode, {
     if ((st = fs_set_shmem(ctx, fs3_fwd_kernel<CC, MD>, shmem)) != BATH_OK) return st;
     const int s1 = reuse ? -1 : ctx->span_begin("fs3_fwd_kernel", ctx->stream, cells3, bytes3);
-    if (reuse) {
-    } else if (MD == 2 && fs_chain_enabled()) {
-      if ((st = launch_fs3_fwd_chain(ctx, ctx->stream, om, dna, Cv, tE, tE, b_sc.as<float>(), b_fx.as<float>(), b_off.as<int64_t>(), jq[0], spec_share)) != BATH_OK) return st;
-    } else
+    if (!reuse)
     hipLaunchKernelGGL((fs3_fwd_kernel<CC, MD>), dim3(grid_dp), dim3(kFsBlock), shmem, ctx->stream, dna->view(), fsdev(om), om->d_loop[0], om->d_move[0], tE, tE, b_sc.as<float>(), b_fx.as<float>(), b_off.as<int64_t>(), jq[0]);
     ctx->span_end(s1, ctx->stream);
-    if ((st = fs_set_shmem(ctx, fs_bwd_kernel<CC, 3, MD>, shmem)) != BATH_OK) return st;
+    if ((st = fs_set_shmem(ctx, fs_bwd_kernel<CC, MD>, shmem)) != BATH_OK) return st;
     const int s2 = ctx->span_begin("fs_bwd_kernel<3>", ctx->side_stream, cells3, bytes3);
-    if (MD == 2 && fs_chain_enabled()) {
-      if (n_rest > 0 && (st = launch_fs3_bwd_chain(ctx, ctx->side_stream, om, bwd_dna, Cv, tE, tE, b_sc.as<float>() + n, b_bx.as<float>(), b_off.as<int64_t>(), jq[1], reuse ? 1 : spec_share)) != BATH_OK) return st;
-    } else
-    hipLaunchKernelGGL((fs_bwd_kernel<CC, 3, MD>), dim3(grid_dp), dim3(kFsBlock), shmem, ctx->side_stream, dna->view(), fsdev(om), om->d_loop[0], om->d_move[0], tE, tE, b_sc.as<float>() + n, (float *)nullptr, (const int64_t *)nullptr, b_bx.as<float>(), b_off.as<int64_t>(), jq[1]);
+    hipLaunchKernelGGL((fs_bwd_kernel<CC, MD>), dim3(grid_dp), dim3(kFsBlock), shmem, ctx->side_stream, dna->view(), fsdev(om), om->d_loop[0], om->d_move[0], tE, tE, b_sc.as<float>() + n, (float *)nullptr, (const int64_t *)nullptr, b_bx.as<float>(), b_off.as<int64_t>(), jq[1]);
     ctx->span_end(s2, ctx->side_stream);
   }))
   if ((st = fs_join(ctx)) != BATH_OK) return st;
-  if (spec) {                                                                  // the speculative rows of this call's windows into place
-    BATH_HIP_TRY(ctx, hipEventRecord(ctx->ev_spec, ctx->spec_stream));
-    BATH_HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_spec, 0));
-    const size_t o_src = 256 + (((size_t)std::max<int64_t>(n_rest, 1) * 4 + 255) & ~(size_t)255);
-    hipLaunchKernelGGL(fs_rows_copy_kernel, dim3((unsigned)n), dim3(256), 0, ctx->stream, (int)n, dna->d_len, reinterpret_cast<const int64_t *>(ctx->scratch[55].as<char>() + o_src),
-                       ctx->scratch[53].as<float>(), b_off.as<int64_t>(), b_bx.as<float>());
-    BATH_HIP_TRY(ctx, hipGetLastError());
-  }
   const int s3 = ctx->span_begin("fs_regions_kernel", ctx->stream, (double)(xoff[(size_t)n] / 5), (double)(xoff[(size_t)n] / 5) * 52.0);
   hipLaunchKernelGGL(fs_regions_kernel, dim3((unsigned)n), dim3(64), 0, ctx->stream, n, dna->d_len, d_fx, b_bx.as<float>(), b_off.as<int64_t>(), d_fxoff, om->d_logsum, loop,
                      b_work.as<float>(), b_reg.as<int32_t>());
@@ -2153,15 +1692,15 @@ int fs3_regions(bath_hip_ctx *ctx, const bath_hip_fsprofile *om, const bath_hip_
 
 namespace bath {
 // used by the pipeline's frameshift stage (bath_pipeline.hip)
-int fs3_forward_scores(bath_hip_ctx *ctx, const bath_hip_fsprofile *om3, const bath_hip_seqs *dna, float *sc, const std::function<int()> *after_launch) {
+int fs3_forward_scores(bath_hip_ctx *ctx, const bath_hip_fsprofile *om3, const bath_hip_seqs *dna, float *sc) {
   ctx->fs_keep_xoff.clear();
   const int mode = fs3_ctx_mode(ctx);
-  if (!ctx->fs_want_regions) return fs3_parser(ctx, om3, dna, mode, sc, nullptr, nullptr, false, nullptr, after_launch);
+  if (!ctx->fs_want_regions) return fs3_parser(ctx, om3, dna, mode, sc, nullptr, nullptr, false);
   // the domain stage follows: the special-state rows of every window stay on the device (20 B per nucleotide), so that the
   // windows that take the frameshift branch need the Backward parser only
   std::vector<int64_t> xoff((size_t)dna->n + 1, 0);
   for (int64_t i = 0; i < dna->n; i++) xoff[(size_t)i + 1] = xoff[(size_t)i] + ((int64_t)dna->h_len[(size_t)i] + 1) * 5;
-  const int st = fs3_parser(ctx, om3, dna, mode, sc, nullptr, xoff.data(), false, &ctx->scratch[45], after_launch);
+  const int st = fs3_parser(ctx, om3, dna, mode, sc, nullptr, xoff.data(), false, &ctx->scratch[45]);
   if (st == BATH_OK) ctx->fs_keep_xoff = std::move(xoff);
   return st;
 }
@@ -2254,60 +1793,53 @@ int bath::fs5_envelopes_ex(bath_hip_ctx *ctx, const bath_hip_fsprofile *om, cons
   float *d_fsc = b_sc.as<float>(), *d_bsc = d_fsc + n, *d_osc = d_bsc + n;
   const int Cv = fs_columns(M);
   const size_t oa_shmem = (size_t)(M + 2) * 8 * sizeof(float);
-  [[maybe_unused]] const int grid = fs_grid(ctx, n);
   // BATH_LOGSUM_CONTEXT: the odds-ratio kernels while bath_hip_set_fs5_odds is on (before fs_strict), else strict / fast
   const bool odds5 = logsum_mode == BATH_LOGSUM_CONTEXT && ctx->fs5_odds;
   if (odds5 && c5_compat) { ctx->set_error("the 5-codon odds-ratio mode implements c5_compat = 0 only (fwdback_fs.c:1464)"); return BATH_EINVAL; }
   if (odds5 && (st = om->ensure_odds()) != BATH_OK) return st;                  // (the first call builds the tables: before the streams fork)
   if (logsum_mode == BATH_LOGSUM_CONTEXT) logsum_mode = ctx->fs_strict ? BATH_LOGSUM_TABLE_SERIAL : BATH_LOGSUM_TABLE;
   const double cells5 = (double)(foff[(size_t)n] / 8);                          // (L+1) x (M+1) cells of all envelopes
-  // The posterior matrix (32 B per cell) is written only when the caller wants it back (<pp>) or the unfused A/B kernels run: the
-  // pipeline reads posteriors along the optimal-accuracy trace only (O(L + M) cells of (L+1)(M+1)), and fs5_trace_kernel forms those
+  // The posterior matrix (32 B per cell) is written only when the caller wants it back (<pp>): the pipeline reads posteriors along the optimal-accuracy trace only (O(L + M) cells of (L+1)(M+1)), and fs5_trace_kernel forms those
   // from the Forward and Backward matrices -- which then stay as they are -- and the rows' normalising factors (4 B per ROW) with the
   // decoding kernels' own arithmetic, value for value
-  static const bool unfused_env = [] { const char *e = std::getenv("BATH_HIP_FS_UNFUSED"); return e && e[0] == '1'; }();
-  static const bool always_pp = [] { const char *e = std::getenv("BATH_HIP_FS_STORE_PP"); return e && e[0] == '1'; }();          // A/B: the round-4 behaviour
-  const bool store_pp = pp != nullptr || unfused_env || always_pp;
+  const bool store_pp = pp != nullptr;
   DevBuf &b_rowden = ctx->scratch[37];
   BATH_HIP_TRY(ctx, b_rowden.reserve((size_t)(xoff[(size_t)n] / 5 + 8) * sizeof(float)));
   float *d_rowden = store_pp ? nullptr : b_rowden.as<float>();
   FsJobs jq[4];
   if ((st = fs_schedule(ctx, dna, 4, jq)) != BATH_OK) return st;
-  StageGate gate(ctx->device, StageGate::kEnvelopes);                           // (BATH_HIP_FS_GATE=3: not while another worker's Forward parser has the chip)
   if ((st = fs_fork(ctx)) != BATH_OK) return st;                                // Backward on the side stream, concurrently with Forward
+  const bool exact = logsum_mode == BATH_LOGSUM_EXACT;
+  // Forward and Backward: the row-per-lane wavefronts (bath_fs_wavefront.hip), the reference's order of every sum, in EVERY mode --
+  // the unihit recursion has no sum that a scan could shorten, so the fast mode's envelopes are the strict ones (the node-per-lane
+  // scan kernels this replaced in fast mode were 13 times slower at 1024 nodes and are gone)
+  // (odds5: the odds-ratio kernels of bath_fs5_odds.hip, node per lane; Backward with scales of its own, so still beside Forward)
+  const int s1 = ctx->span_begin(odds5 ? "fs5_fwd_odds_kernel" : "fs5_fwd_kernel", ctx->stream, cells5, cells5 * 32.0);
+  if (odds5) st = launch_fs5_odds(ctx, ctx->stream, om, dna, kFs5OddsEnvFwd, d_fsc, b_f.as<float>(), d_foff, b_fx.as<float>(), d_xoff, -1, jq[0], nullptr);
+  else st = launch_fs5_fwd_wf(ctx, ctx->stream, om, dna, exact, c5_compat, d_fsc, b_f.as<float>(), d_foff, b_fx.as<float>(), d_xoff, ctx->scratch[41], jq[0]);
+  if (st != BATH_OK) return st;
+  ctx->span_end(s1, ctx->stream);
+  static const bool serial_env = [] { const char *e = std::getenv("BATH_HIP_FS_SERIAL"); return e && e[0] == '1'; }();   // timing probes: Backward after Forward
+  const bool serial = ctx->fs_serial >= 0 ? ctx->fs_serial != 0 : serial_env;                                           // (bath_hip_set_fs_serial)
+  hipStream_t bs = serial ? ctx->stream : ctx->side_stream;
+  const int s2 = ctx->span_begin(odds5 ? "fs5_bwd_odds_kernel" : "fs_bwd_kernel<5>", bs, cells5, cells5 * 12.0);
+  if (odds5) st = launch_fs5_odds(ctx, bs, om, dna, kFs5OddsEnvBwd, d_bsc, b_b.as<float>(), d_boff, b_bx.as<float>(), d_xoff, -1, jq[1], nullptr);
+  else st = launch_fs5_bwd_wf(ctx, bs, om, dna, exact, d_bsc, b_b.as<float>(), d_boff, b_bx.as<float>(), d_xoff, ctx->scratch[42], ctx->scratch[43], ctx->scratch[44], jq[1], jq[3]);
+  if (st != BATH_OK) return st;
+  ctx->span_end(s2, bs);
+  if ((st = fs_join(ctx)) != BATH_OK) return st;
+  BATH_HIP_TRY(ctx, hipMemsetAsync(b_cs.p, 0, (size_t)n * cs_stride * sizeof(float), ctx->stream));
   BATH_FS_SWITCH(Cv, {
-    BATH_FS_MODE(logsum_mode, {
-      // Forward and Backward: the row-per-lane wavefronts (bath_fs_wavefront.hip), the reference's order of every sum, in EVERY mode --
-      // the unihit recursion has no sum that a scan could shorten, so the fast mode's envelopes are the strict ones (the node-per-lane
-      // scan kernels this replaced in fast mode were 13 times slower at 1024 nodes and are gone)
-      // (odds5: the odds-ratio kernels of bath_fs5_odds.hip, node per lane; Backward with scales of its own, so still beside Forward)
-      const int s1 = ctx->span_begin(odds5 ? "fs5_fwd_odds_kernel" : "fs5_fwd_kernel", ctx->stream, cells5, cells5 * 32.0);
-      if (odds5) st = launch_fs5_odds(ctx, ctx->stream, om, dna, kFs5OddsEnvFwd, d_fsc, b_f.as<float>(), d_foff, b_fx.as<float>(), d_xoff, -1, jq[0], nullptr);
-      else st = launch_fs5_fwd_wf(ctx, ctx->stream, om, dna, MD == 1, c5_compat, d_fsc, b_f.as<float>(), d_foff, b_fx.as<float>(), d_xoff, ctx->scratch[41], jq[0]);
-      if (st != BATH_OK) return st;
-      ctx->span_end(s1, ctx->stream);
-      static const bool serial_env = [] { const char *e = std::getenv("BATH_HIP_FS_SERIAL"); return e && e[0] == '1'; }();   // timing probes: Backward after Forward
-      const bool serial = ctx->fs_serial >= 0 ? ctx->fs_serial != 0 : serial_env;                                           // (bath_hip_set_fs_serial)
-      hipStream_t bs = serial ? ctx->stream : ctx->side_stream;
-      const int s2 = ctx->span_begin(odds5 ? "fs5_bwd_odds_kernel" : "fs_bwd_kernel<5>", bs, cells5, cells5 * 12.0);
-      if (odds5) st = launch_fs5_odds(ctx, bs, om, dna, kFs5OddsEnvBwd, d_bsc, b_b.as<float>(), d_boff, b_bx.as<float>(), d_xoff, -1, jq[1], nullptr);
-      else st = launch_fs5_bwd_wf(ctx, bs, om, dna, MD == 1, d_bsc, b_b.as<float>(), d_boff, b_bx.as<float>(), d_xoff, ctx->scratch[42], ctx->scratch[43], ctx->scratch[44], jq[1], jq[3]);
-      if (st != BATH_OK) return st;
-      ctx->span_end(s2, bs);
-    })
-    if ((st = fs_join(ctx)) != BATH_OK) return st;
-    BATH_HIP_TRY(ctx, hipMemsetAsync(b_cs.p, 0, (size_t)n * cs_stride * sizeof(float), ctx->stream));
-    // decoding + optimal-accuracy fill, one walk over the rows (BATH_HIP_FS_UNFUSED=1: the two separate kernels, for A/B runs)
-    static const bool unfused = [] { const char *e = std::getenv("BATH_HIP_FS_UNFUSED"); return e && e[0] == '1'; }();
+    // decoding + optimal-accuracy fill, one walk over the rows
     int mw_nodes = 0;
     // reads Forward 32 + Backward 12, writes OA 12 B/cell -- and the posteriors, 32 more, only when the caller asked for the matrix
     const double oa_bytes = cells5 * (store_pp ? 88.0 : 56.0);
-    if (!unfused && fs5_decode_oa_mw_shape(M, &mw_nodes) > 0) {        // long models: a block of waves per envelope (bath_fs_decode.hip)
+    if (fs5_decode_oa_mw_shape(M, &mw_nodes) > 0) {        // long models: a block of waves per envelope (bath_fs_decode.hip)
       const int s3 = ctx->span_begin("fs5_decode_oa_kernel", ctx->stream, cells5, oa_bytes);
       if ((st = launch_fs5_decode_oa_mw(ctx, ctx->stream, om, dna, d_bsc, b_f.as<float>(), d_foff, b_fx.as<float>(), d_xoff, b_b.as<float>(), d_boff, b_bx.as<float>(),
                                         b_cs.as<float>(), b_o.as<float>(), d_osc, (oax || trace) ? b_ox.as<float>() : nullptr, jq[2], store_pp ? 1 : 0, d_rowden)) != BATH_OK) return st;
       ctx->span_end(s3, ctx->stream);
-    } else if (!unfused) {
+    } else {
       if ((st = fs_set_shmem(ctx, fs5_decode_oa_kernel<CC>, oa_shmem)) != BATH_OK) return st;
       const int s3 = ctx->span_begin("fs5_decode_oa_kernel", ctx->stream, cells5, oa_bytes);
       const int oa_grid = (int)std::max<int64_t>(1, std::min<int64_t>((n + 3) / 4, (int64_t)ctx->prop.multiProcessorCount * (CC <= 3 ? BATH_FS_OA_WAVES : 1)));
@@ -2316,16 +1848,6 @@ int bath::fs5_envelopes_ex(bath_hip_ctx *ctx, const bath_hip_fsprofile *om, cons
                          1.17549435e-38f /* E->J impossible in unihit mode: TSCDELTA = FLT_MIN */, 1.0f, (oax || trace) ? b_ox.as<float>() : nullptr, jq[2],
                          store_pp ? 1 : 0, d_rowden);
       ctx->span_end(s3, ctx->stream);
-    } else {
-    const int s3 = ctx->span_begin("fs5_decode_kernel", ctx->stream, cells5, cells5 * 76.0);     // reads Forward 32 + Backward 12, rewrites 32 B/cell
-    hipLaunchKernelGGL(fs5_decode_kernel, dim3(grid), dim3(256), 0, ctx->stream, dna->view(), M, om->d_loop[1], d_bsc, b_f.as<float>(), d_foff, b_fx.as<float>(), d_xoff,
-                       b_b.as<float>(), d_boff, b_bx.as<float>(), b_cs.as<float>());
-    ctx->span_end(s3, ctx->stream);
-    if ((st = fs_set_shmem(ctx, fs5_oa_kernel<CC>, oa_shmem)) != BATH_OK) return st;
-    const int s4 = ctx->span_begin("fs5_oa_kernel", ctx->stream, cells5, cells5 * 44.0);         // reads posteriors 32, writes OA 12 B/cell
-    hipLaunchKernelGGL((fs5_oa_kernel<CC>), dim3(grid), dim3(256), oa_shmem, ctx->stream, dna->view(), M, om->d_tf, b_f.as<float>(), d_foff, b_fx.as<float>(), d_xoff, b_o.as<float>(), d_boff, d_osc,
-                       1.17549435e-38f /* E->J impossible in unihit mode: TSCDELTA = FLT_MIN */, 1.0f, (oax || trace) ? b_ox.as<float>() : nullptr);
-    ctx->span_end(s4, ctx->stream);
     }
   })
   const int s5 = ctx->span_begin("fs5_null2_kernel", ctx->stream, (double)n * M, (double)n * M * 32.0);
@@ -2448,7 +1970,6 @@ int bath::fs5_region_forward(bath_hip_ctx *ctx, const bath_hip_fsprofile *om, co
   BATH_HIP_TRY(ctx, hipMemcpyAsync(d_xoff, xoff.data(), (size_t)(n + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
   const int Cv = fs_columns(M);
   const size_t shmem = (size_t)(kLogsumTbl + (M + 2) * 8) * sizeof(float);
-  [[maybe_unused]] const int grid = fs_grid(ctx, n);
   const int grid_dp = fs_grid_dp(ctx, n);
   const float tE = (float)-0.69314718055994529;                               // multihit: E->C and E->J both log 1/2 (modelconfig.c:825-831)
   const int mode = ctx->fs_strict ? BATH_LOGSUM_TABLE_SERIAL : BATH_LOGSUM_TABLE;
@@ -2458,7 +1979,7 @@ int bath::fs5_region_forward(bath_hip_ctx *ctx, const bath_hip_fsprofile *om, co
     const int s1 = ctx->span_begin("fs5_fwd_odds_kernel(regions)", ctx->stream, (double)(foff[(size_t)n] / 8), (double)(foff[(size_t)n] / 8) * 32.0);
     if ((st = launch_fs5_odds(ctx, ctx->stream, om, dna, kFs5OddsRegionFwd, d_sc_out, d_f, d_foff, d_fx, d_xoff, cfg_len_amino, jq[0], d_done)) != BATH_OK) return st;
     ctx->span_end(s1, ctx->stream);
-  } else if (mode == BATH_LOGSUM_TABLE_SERIAL && fs_chain_enabled()) {
+  } else if (mode == BATH_LOGSUM_TABLE_SERIAL) {
     const int s1 = ctx->span_begin("fs5_fwd_kernel(regions)", ctx->stream, (double)(foff[(size_t)n] / 8), (double)(foff[(size_t)n] / 8) * 32.0);
     if ((st = launch_fs5_fwd_chain(ctx, ctx->stream, om, dna, Cv, tE, tE, 0, d_sc_out, d_f, d_foff, d_fx, d_xoff, cfg_len_amino, jq[0], d_done)) != BATH_OK) return st;
     ctx->span_end(s1, ctx->stream);

@@ -49,20 +49,13 @@ __device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(
 // slower, by an amount that differs from block to block and from launch to launch (tools/lsbench7.hip: 198-267 clocks per Forward
 // node, median 213, beside parked waves; 199-203 beside pollers that sleep 64 clocks per poll; 226-231 beside waves that spin on
 // the VALU).  The word counts row pairs: the chain wave stores the pair's number when its serial part is done.
-#ifndef BATH_CHAIN_KEEPALIVE
-#define BATH_CHAIN_KEEPALIVE 1
-#endif
-constexpr int kChainAwakeWaves = BATH_CHAIN_KEEPALIVE ? 4 : 1;   // the chain wave and its pollers
+constexpr int kChainAwakeWaves = 4;   // the chain wave and its pollers
 __device__ __forceinline__ void chain_keepalive(const int *flag, int pair) {
-#if BATH_CHAIN_KEEPALIVE
   const volatile int *f = flag;
   while (*f != pair) __builtin_amdgcn_s_sleep(1);
-#endif
 }
 __device__ __forceinline__ void chain_done(int *flag, int pair) {
-#if BATH_CHAIN_KEEPALIVE
   *reinterpret_cast<volatile int *>(flag) = pair;
-#endif
 }
 __device__ __forceinline__ bool chain_poller(int wv) { return wv >= 1 && wv < kChainAwakeWaves; }
 
@@ -82,19 +75,9 @@ __host__ __device__ inline int fs_chain_stride(int C) { return C * 64 + 1; }
 //   tp        LDS byte address of {tMD, tDD}(k+1)
 //   set A     M_k, tMD(k), tDD(k) on entry; the asm covers TWO nodes and leaves set A for node k+2
 // ---------------------------------------------------------------------------------------------------------------------------
-// nodes per trip of the chain loops (pairs of nodes repeated)
-#ifndef BATH_CHAIN_UNROLL
-#define BATH_CHAIN_UNROLL 16
-#endif
-#if BATH_CHAIN_UNROLL == 8
-#define BATH_CHAIN_REPEAT(P) P P P P
-#elif BATH_CHAIN_UNROLL == 4
-#define BATH_CHAIN_REPEAT(P) P P
-#elif BATH_CHAIN_UNROLL == 16
+// nodes per trip of the chain loops: eight pairs of nodes
+constexpr int kChainUnroll = 16;
 #define BATH_CHAIN_REPEAT(P) P P P P P P P P
-#else
-#define BATH_CHAIN_REPEAT(P) P
-#endif
 #define BATH_LS_INDEX(a, x, y)                      \
   "v_sub_f32 " a ", " x ", " y "\n\t"               \
   "v_min_f32_e64 " a ", |" a "|, %[c15]\n\t"        \
@@ -141,7 +124,7 @@ __device__ __forceinline__ void fwd_chain_nodes(FwdChainRegs &r, int n, unsigned
   // per node at two nodes per trip.  M = 1024, clocks per node at 2 / 16 nodes per trip: Forward 224 -> 200, B sum 120 -> 92,
   // D chain 250 -> 212; profiles/r06_chain_loops_ab.txt)
 #define BATH_FWD_PAIR BATH_FWD_NODE("%[Mk]", "%[tx]", "%[ty]", "%[Mn]", "%[ux]", "%[uy]") BATH_FWD_NODE("%[Mn]", "%[ux]", "%[uy]", "%[Mk]", "%[tx]", "%[ty]")
-  for (; k + BATH_CHAIN_UNROLL <= n; k += BATH_CHAIN_UNROLL)
+  for (; k + kChainUnroll <= n; k += kChainUnroll)
     asm volatile("s_waitcnt lgkmcnt(0)\n\t"
                  BATH_CHAIN_REPEAT(BATH_FWD_PAIR)
                  "s_waitcnt lgkmcnt(0)"
@@ -184,7 +167,7 @@ __device__ __forceinline__ void fwd_chain_nodes_compact(FwdChainRegs &r, int n, 
   // per node at two nodes per trip.  M = 1024, clocks per node at 2 / 16 nodes per trip: Forward 224 -> 200, B sum 120 -> 92,
   // D chain 250 -> 212; profiles/r06_chain_loops_ab.txt)
 #define BATH_FWD_PAIR BATH_FWD_NODE("%[Mk]", "%[tx]", "%[ty]", "%[Mn]", "%[ux]", "%[uy]") BATH_FWD_NODE("%[Mn]", "%[ux]", "%[uy]", "%[Mk]", "%[tx]", "%[ty]")
-  for (; k + BATH_CHAIN_UNROLL <= n; k += BATH_CHAIN_UNROLL)
+  for (; k + kChainUnroll <= n; k += kChainUnroll)
     asm volatile("s_waitcnt lgkmcnt(0)\n\t"
                  BATH_CHAIN_REPEAT(BATH_FWD_PAIR)
                  "s_waitcnt lgkmcnt(0)"
@@ -241,7 +224,7 @@ __device__ __forceinline__ float bwd_bsum_nodes(float b, float v, float sN, floa
   float vn, a1, mx;
   int k = 0;
 #define BATH_BSUM_PAIR(TS, TS2)                                                                                                          \
-  for (; k + BATH_CHAIN_UNROLL <= n; k += BATH_CHAIN_UNROLL)                                                                            \
+  for (; k + kChainUnroll <= n; k += kChainUnroll)                                                                            \
     asm volatile("s_waitcnt lgkmcnt(0)\n\t"                                                                                             \
                  BATH_CHAIN_REPEAT(BATH_BSUM_NODE("%[v]", "%[vn]", TS, TS2) BATH_BSUM_NODE("%[vn]", "%[v]", TS, TS2))                    \
                  "s_waitcnt lgkmcnt(0)"                                                                                                 \
@@ -306,7 +289,7 @@ __device__ __forceinline__ void bwd_d_nodes(BwdChainRegs &r, float xE, unsigned 
   float ivq, ux, uy, u, bs, p1, p2, a1, mx1, x;
   int k = 0;
 #define BATH_BWD_D_PAIR(NTS, H)                                                                                                          \
-  for (; k + BATH_CHAIN_UNROLL <= n; k += BATH_CHAIN_UNROLL)                                                                            \
+  for (; k + kChainUnroll <= n; k += kChainUnroll)                                                                            \
     asm volatile("s_waitcnt lgkmcnt(0)\n\t"                                                                                             \
                  BATH_CHAIN_REPEAT(BATH_BWD_D_NODE(H, "%[ivn]", "%[tx]", "%[ty]", "%[ivq]", "%[ux]", "%[uy]", NTS)                          \
                                    BATH_BWD_D_NODE(H, "%[ivk]", "%[ux]", "%[uy]", "%[ivk]", "%[tx]", "%[ty]", NTS)                          \
@@ -369,9 +352,6 @@ __global__ __launch_bounds__(chain_threads(C)) void fs3_fwd_chain_kernel(SeqView
   for (int i = threadIdx.x; i < (M + 2) * 8; i += blockDim.x) s_tf[i] = p.tf[i];
   __syncthreads();
   const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#ifdef BATH_CHAIN_CLOCK
-  long long dbg_cyc = 0, dbg_wall = 0, dbg_n = 0;
-#endif
 #define LS(a, b) flogsum<false>((a), (b), s_tbl)
   for (;;) {
     if (threadIdx.x == 0) s_ctl[0] = (int)atomicAdd(jobs.counter, (unsigned)W);
@@ -450,13 +430,7 @@ __global__ __launch_bounds__(chain_threads(C)) void fs3_fwd_chain_kernel(SeqView
         // the loop's own loads (M(i,k), the transitions) are a node ahead: what a node waits for is the chain's log-sums only
         // (slot M+1 of the row and of the transitions exists: the loads run a node ahead)
         FwdChainRegs r{ech, dch, st[1], s_tf[1 * 8 + 4], s_tf[1 * 8 + 5], lds_addr(st + 1), lds_addr(s_tf + 2 * 8 + 4)};   // tMD(k), tDD(k)
-#ifdef BATH_CHAIN_CLOCK
-        const long long cc0 = clock64(), ww0 = wall_clock64();
-#endif
         fwd_chain_nodes(r, M, lds_addr(s_tbl), 15.999f);
-#ifdef BATH_CHAIN_CLOCK
-        dbg_cyc += clock64() - cc0; dbg_wall += wall_clock64() - ww0; dbg_n += M;
-#endif
         ech = r.e; dch = r.d;
         s_e[lane] = ech;
       }
@@ -493,9 +467,6 @@ __global__ __launch_bounds__(chain_threads(C)) void fs3_fwd_chain_kernel(SeqView
       }
     }
     if (job >= 0 && lane == 0) sc[job] = (L >= 3) ? LS(C1, LS(C2 + tCL, C3 + tCL)) + tCM : -INFINITY;
-#ifdef BATH_CHAIN_CLOCK
-    if (wv == 0 && lane == 0 && blockIdx.x == 0 && dbg_n > 0) printf("fwd chain: %.1f clock64 ticks per node, %.1f ns per node (%lld nodes)\n", (double)dbg_cyc / dbg_n, (double)dbg_wall / dbg_n * 10.0, dbg_n);
-#endif
     __syncthreads();                                            // s_ctl is rewritten at the top
   }
 #undef LS
@@ -540,9 +511,6 @@ __global__ __launch_bounds__(512) void fs3_fwd_chain_mem_kernel(SeqView dna, FsD
   int *s_ctl = reinterpret_cast<int *>(s_e + 2 * kChainMaxWaves);   // [0]: first job of the block's batch; [4]: the row pair whose serial part is done
   if (threadIdx.x == 0) s_ctl[4] = 0;
   int pair = 0;
-#ifdef BATH_CHAIN_CLOCK
-  long long dbg_t[5] = {0, 0, 0, 0, 0}, dbg_n = 0;
-#endif
   fs_load_logsum_table(s_tbl, p.logsum);
   for (int n = threadIdx.x; n < HP; n += blockDim.x) {
     const int nd = imin(n + 1, M + 1);                          // (the nodes past the model's end read row M + 1, as the kernel above does)
@@ -597,9 +565,6 @@ __global__ __launch_bounds__(512) void fs3_fwd_chain_mem_kernel(SeqView dna, FsD
       // the records: <prev> holds the rows i-2 (its A rows) and i-1 (its B rows), <cur> -- until this pair overwrites it -- the rows
       // i-4 and i-3.  A window that has stored no pair (one pair) yet reads -inf instead (every row before row 2 is -inf).
       const bool h1 = np >= 1, h2 = np >= 2;
-#ifdef BATH_CHAIN_CLOCK
-      const long long t0 = clock64();
-#endif
       __threadfence_block();                                    // the previous pairs' rows, stored by other lanes of this wave, before they are read
       float *const cur = rec0 + (size_t)(np & 1) * kChainHistRows * HP;
       const float *const prev = rec0 + (size_t)((np + 1) & 1) * kChainHistRows * HP;
@@ -663,13 +628,7 @@ __global__ __launch_bounds__(512) void fs3_fwd_chain_mem_kernel(SeqView dna, FsD
         }
         gc = gn;
       }
-#ifdef BATH_CHAIN_CLOCK
-      const long long t1 = clock64();
-#endif
       lds_barrier();
-#ifdef BATH_CHAIN_CLOCK
-      const long long t2 = clock64();
-#endif
       // ---- 2. the serial part, a lane per row (as in fs3_fwd_chain_kernel; the transitions are the compact pairs)
       if (wv == 0 && lane < 2 * W) {
         float *st = s_stage + (size_t)lane * stride;
@@ -678,13 +637,7 @@ __global__ __launch_bounds__(512) void fs3_fwd_chain_mem_kernel(SeqView dna, FsD
         s_e[lane] = r.e;
       }
       if (wv == 0) chain_done(s_ctl + 4, pair); else if (chain_poller(wv)) chain_keepalive(s_ctl + 4, pair);
-#ifdef BATH_CHAIN_CLOCK
-      const long long t3 = clock64();
-#endif
       lds_barrier();
-#ifdef BATH_CHAIN_CLOCK
-      const long long t4 = clock64();
-#endif
       // ---- 3. D of both rows into the pair's record; special states of both rows (:592-603)
       if (actB) {
 #pragma unroll 1
@@ -717,15 +670,7 @@ __global__ __launch_bounds__(512) void fs3_fwd_chain_mem_kernel(SeqView dna, FsD
       } else if (actA) {                                        // the window's last row: only C(L), C(L-1), C(L-2) are still needed
         C3 = C2; C2 = C1; C1 = CA;
       }
-#ifdef BATH_CHAIN_CLOCK
-      dbg_t[0] += t1 - t0; dbg_t[1] += t2 - t1; dbg_t[2] += t3 - t2; dbg_t[3] += t4 - t3; dbg_t[4] += clock64() - t4; dbg_n++;
-#endif
     }
-#ifdef BATH_CHAIN_CLOCK
-    if (lane == 0 && blockIdx.x == 0 && (wv == 0 || wv == W - 1) && dbg_n > 0)
-      printf("fwd mem wave %d: per pair, clocks: parallel part %.0f, wait %.0f, chain (wave 0) or poll %.0f, wait %.0f, D rows + special states %.0f\n", wv,
-             (double)dbg_t[0] / dbg_n, (double)dbg_t[1] / dbg_n, (double)dbg_t[2] / dbg_n, (double)dbg_t[3] / dbg_n, (double)dbg_t[4] / dbg_n);
-#endif
     if (job >= 0 && lane == 0) sc[job] = (L >= 3) ? LS(C1, LS(C2 + tCL, C3 + tCL)) + tCM : -INFINITY;
     __syncthreads();                                            // s_ctl is rewritten at the top
   }
@@ -947,9 +892,6 @@ __global__ __launch_bounds__(WPW == 1 ? bwd_chain_threads(C) : MAXT) void fs3_bw
   // next nodes" is then the physical lane below and the neighbour move is the same wave_shr1
   const int win = wv / WPW, half = wv % WPW;                    // the wave's window slot; its place among the window's waves (0: the highest nodes)
   const int ll = 64 * WPW - 1 - (half * 64 + lane);
-#ifdef BATH_CHAIN_CLOCK
-  long long dbgb_cyc = 0, dbgd_cyc = 0, dbgb_n = 0;
-#endif
 #define LS(a, b) flogsum<false>((a), (b), s_tbl)
   for (;;) {                                                    // batches dealt longest first, on request (see fs3_fwd_chain_half_kernel)
     if (threadIdx.x == 0) s_ctl[0] = (int)atomicAdd(jobs.counter, 1u);
@@ -1015,14 +957,8 @@ __global__ __launch_bounds__(WPW == 1 ? bwd_chain_threads(C) : MAXT) void fs3_bw
         float *st = s_stage + (size_t)lane * stride;
         const int avail = 2 * q + cs, irow = cL - avail;
         // (the terms are read two nodes ahead of the chain: the slots M+1, M+2 of the row and of the transitions are inside the block's LDS)
-#ifdef BATH_CHAIN_CLOCK
-        const long long bc0 = clock64();
-#endif
         const float b = bwd_bsum_nodes<kCompact>(st[1] + *TBM(1), st[2] + *TBM(2), st[3], *TBM(3), lds_addr(st + 2), lds_addr(TBM(2)),
                                                  M - 1, lds_addr(s_tbl), 15.999f);
-#ifdef BATH_CHAIN_CLOCK
-        dbgb_cyc += clock64() - bc0; dbgb_n += M;
-#endif
         // N, J, C of row i+3: the other slot's row of two pairs ago (slot 0) or of the previous pair (slot 1)
         const float pN1 = __shfl_xor(hN1, 1, 64), pN2 = __shfl_xor(hN2, 1, 64), pJ1 = __shfl_xor(hJ1, 1, 64), pJ2 = __shfl_xor(hJ2, 1, 64);
         const float pC1 = __shfl_xor(hC1, 1, 64), pC2 = __shfl_xor(hC2, 1, 64);
@@ -1035,13 +971,7 @@ __global__ __launch_bounds__(WPW == 1 ? bwd_chain_threads(C) : MAXT) void fs3_bw
         // D(i,k) = LS(LS(E, D(i,k+1) + tDD), ivx(i,k+1) + tDM); the rows L-3, L-4 pair E with the ivx term first (:1524-1526).
         // Log-sum is symmetric, so both are LS(LS(E, p1), p2) with the operands swapped: no branch in the loop
         BwdChainRegs r{-INFINITY, -INFINITY, st[M], TDD(M)[0], TDD(M)[1], lds_addr(st + M - 1), lds_addr(TDD(M - 1))};   // ivx(i,M), tDD(M), tDM(M)
-#ifdef BATH_CHAIN_CLOCK
-        const long long dc0 = clock64();
-#endif
         bwd_d_nodes<kCompact>(r, xE, __builtin_amdgcn_ballot_w64(mid), M, lds_addr(s_tbl), 15.999f);
-#ifdef BATH_CHAIN_CLOCK
-        dbgd_cyc += clock64() - dc0;
-#endif
         s_e[lane] = xE;
         const float partnerN = __shfl_xor(xN, 1, 64);
         if (clive && irow >= 0) {
@@ -1089,9 +1019,6 @@ __global__ __launch_bounds__(WPW == 1 ? bwd_chain_threads(C) : MAXT) void fs3_bw
         for (int c = 0; c < C; c++) { R4[c] = R2[c]; R3[c] = R1[c]; R2[c] = MA[c]; R1[c] = MB[c]; J3[c] = J1[c]; J2[c] = IA[c]; J1[c] = IB[c]; }
       }
     }
-#ifdef BATH_CHAIN_CLOCK
-    if (wv == 0 && lane == 0 && blockIdx.x == 0 && dbgb_n > 0) printf("bwd chain: B sum %.1f ticks per node, D chain %.1f ticks per node (%lld nodes)\n", (double)dbgb_cyc / dbgb_n, (double)dbgd_cyc / dbgb_n, dbgb_n);
-#endif
     if (job >= 0 && !live && lane == 0 && half == 0) sc[job] = -INFINITY;
     __syncthreads();
   }
@@ -1476,9 +1403,8 @@ static int chain_waves(bath_hip_ctx *ctx, int64_t n, int M, int C, size_t *shmem
   // couple of hundred) a block holds one or two.  Two blocks on one CU is worse than one twice the size: the chain wave of one
   // then shares its SIMD with the other's parallel part and every dependent log-sum waits for an issue slot (measured: the
   // Backward parser of 2.5 k windows 14.8 ms as 157 blocks of 16, 17.8 ms as 313 blocks of 8).
-  // <cu_share>: the launch is to leave the rest of the chip to kernels running beside it (the regions' Forward: the envelope
-  // kernels of the single-domain regions run on another stream, and their blocks -- a 64 KB table and the rings -- do not fit
-  // into a CU's LDS next to a block of this kernel: spread over every CU it would hold them back until it ends)
+  // <cu_share>: the launch is to leave the rest of the chip to another chain kernel running beside it (the two 3-codon parsers of
+  // fs3_regions): the blocks of the two do not fit into one CU's LDS together
   const int64_t slots = std::max<int64_t>(1, (int64_t)ctx->prop.multiProcessorCount / cu_share);
   while (W > 1 && (int64_t)(W / 2) * slots >= n) W >>= 1;
   *shmem_out = fixed + (size_t)W * 2 * fs_chain_stride(C) * sizeof(float);
@@ -1569,9 +1495,7 @@ int launch_fs3_fwd_chain(bath_hip_ctx *ctx, hipStream_t stream, const bath_hip_f
 }
 
 int launch_fs3_bwd_chain(bath_hip_ctx *ctx, hipStream_t stream, const bath_hip_fsprofile *om, const bath_hip_seqs *dna, int Cv, float tEL, float tEM,
-                         float *d_sc, float *d_xmx, const int64_t *d_xoff, FsJobs jobs, int cu_share, int bst_slot, int stage_slot) {
-  // <bst_slot>, <stage_slot>: where the launch keeps its batch starts (device scratch, page-locked staging).  A second launch that
-  // may run while the first is still pulling batches (the speculative Backward of the longest windows) brings its own.
+                         float *d_sc, float *d_xmx, const int64_t *d_xoff, FsJobs jobs, int cu_share) {
   const int M = om->M;
   size_t shmem = 0;
   // half a wave per window when the model fits 32 lanes x 6 nodes and the windows would otherwise take more than half the chip:
@@ -1583,8 +1507,8 @@ int launch_fs3_bwd_chain(bath_hip_ctx *ctx, hipStream_t stream, const bath_hip_f
     if (half_env != 0 && CH <= 6 && (half_env == 1 || n > (int64_t)ctx->prop.multiProcessorCount * 8)) {
       const size_t hs = (size_t)(kLogsumTbl + (M + 2) * 8 + 32 * 2 * (CH * 32 + 1) + 64 + 16) * sizeof(float);
       int nbat = 0;
-      DevBuf &b_bst = ctx->scratch[bst_slot];
-      const int stb = chain_batches(ctx, stream, dna, 0.128 * M + 6.6 + 0.5 * CH, 0.03 * CH, 32, b_bst, stage_slot, &nbat, cu_share);
+      DevBuf &b_bst = ctx->scratch[48];
+      const int stb = chain_batches(ctx, stream, dna, 0.128 * M + 6.6 + 0.5 * CH, 0.03 * CH, 32, b_bst, 2, &nbat, cu_share);
       if (stb != BATH_OK) return stb;
       const int hgrid = std::max(1, std::min(nbat, (int)ctx->prop.multiProcessorCount));
       FsDev dev{om->M, om->pitch, om->maxcodons, om->d_rsc, om->d_tf, om->d_tb, om->d_logsum};
@@ -1601,8 +1525,8 @@ int launch_fs3_bwd_chain(bath_hip_ctx *ctx, hipStream_t stream, const bath_hip_f
   const int W = chain_waves(ctx, dna->n, M, Cv, &shmem, cu_share, bwd_chain_threads(Cv), chain_compact(Cv) ? (M + 3) * 4 : 0);
   // batches by length (chain_batches); t(w) measured at M = 145 (C = 3): 25.4 us per row pair at one window, 28.5 at 16
   int nbat = 0;
-  DevBuf &b_bst = ctx->scratch[bst_slot];                          // (its own buffer: Forward's launch may be running on another stream)
-  const int stb = chain_batches(ctx, stream, dna, 0.128 * M + 6.6, 0.067 * Cv, W, b_bst, stage_slot, &nbat, cu_share);
+  DevBuf &b_bst = ctx->scratch[48];                                // (its own buffer: Forward's launch may be running on another stream)
+  const int stb = chain_batches(ctx, stream, dna, 0.128 * M + 6.6, 0.067 * Cv, W, b_bst, 2, &nbat, cu_share);
   if (stb != BATH_OK) return stb;
   const int grid = std::max(1, std::min(nbat, (int)ctx->prop.multiProcessorCount));
   FsDev dev{om->M, om->pitch, om->maxcodons, om->d_rsc, om->d_tf, om->d_tb, om->d_logsum};
@@ -1633,16 +1557,14 @@ int launch_fs5_fwd_chain(bath_hip_ctx *ctx, hipStream_t stream, const bath_hip_f
                          float *d_sc, float *d_fwd, const int64_t *d_foff, float *d_xmx, const int64_t *d_xoff, int cfg_len, FsJobs jobs, int *d_done) {
   const int M = om->M;
   size_t shmem = 0;
-  static const int share = [] { const char *e = std::getenv("BATH_HIP_FS_REGION_CU_SHARE"); return e ? std::max(1, std::atoi(e)) : 1; }();
-  const int W = chain_waves(ctx, dna->n, M, Cv, &shmem, share);
+  const int W = chain_waves(ctx, dna->n, M, Cv, &shmem);
   const int64_t n = dna->n;
   const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((n + W - 1) / W, (int64_t)ctx->prop.multiProcessorCount));
   // A block of one or two regions needs ~75 KB of LDS: two of them, or one and a 74 KB block of the envelope wavefronts running beside
   // this kernel, fit into one CU -- and a chain wave that shares its SIMD with another block's waves waits for issue slots at every
   // dependent log-sum (the kernel then lasts 18 ms instead of 16, in the passes where the dispatcher happens to pair blocks up).  With
-  // fewer blocks than CUs every block asks for enough LDS to have its CU to itself (BATH_HIP_FS_REGION_LDS_KB, 0: only what it needs).
-  static const int lds_kb = [] { const char *e = std::getenv("BATH_HIP_FS_REGION_LDS_KB"); return e ? std::atoi(e) : 100; }();
-  if (grid < ctx->prop.multiProcessorCount && 64 * W <= 256) shmem = std::max(shmem, std::min<size_t>((size_t)lds_kb * 1024, (size_t)160 * 1024));
+  // fewer blocks than CUs every block asks for enough LDS (100 KB) to have its CU to itself.
+  if (grid < ctx->prop.multiProcessorCount && 64 * W <= 256) shmem = std::max(shmem, (size_t)100 * 1024);
   FsDev dev{om->M, om->pitch, om->maxcodons, om->d_rsc, om->d_tf, om->d_tb, om->d_logsum};
   // a couple of hundred regions are one or two per block: then the kernel built for 256 threads, whose lanes have registers for
   // the row's cells and the next row's emission scores without spilling (a 1024-thread block leaves a lane 128)

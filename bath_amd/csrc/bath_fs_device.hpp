@@ -118,14 +118,9 @@ __device__ __forceinline__ float wave_shr1(float v, float fill) { return dpp_f<0
 __device__ __forceinline__ float wave_bcast_last(float v) { return __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, v), 63)); }
 
 // log-sum of a value per lane, result in every lane: an inclusive scan in lane order (row_shr 1/2/4/8, row_bcast 15/31), lane 63
-// broadcast.  BATH_FS_BPERMUTE: the xor butterfly through ds_bpermute this replaced.
+// broadcast.
 template <bool EXACT>
 __device__ __forceinline__ float wave_logsum(float v, const float *tbl) {
-#ifdef BATH_FS_BPERMUTE
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) v = flogsum<EXACT>(v, __shfl_xor(v, d, 64), tbl);
-  return v;
-#else
   v = flogsum<EXACT>(v, dpp_f<0x111>(v, -INFINITY), tbl);
   v = flogsum<EXACT>(v, dpp_f<0x112>(v, -INFINITY), tbl);
   v = flogsum<EXACT>(v, dpp_f<0x114>(v, -INFINITY), tbl);
@@ -133,7 +128,6 @@ __device__ __forceinline__ float wave_logsum(float v, const float *tbl) {
   v = flogsum<EXACT>(v, dpp_f<0x142, 0xa>(v, -INFINITY), tbl);
   v = flogsum<EXACT>(v, dpp_f<0x143, 0xc>(v, -INFINITY), tbl);
   return wave_bcast_last(v);
-#endif
 }
 
 __device__ __forceinline__ int imin(int a, int b) { return a < b ? a : b; }
@@ -234,8 +228,7 @@ int launch_fs5_decode_oa_mw(bath_hip_ctx *ctx, hipStream_t stream, const bath_hi
 int launch_fs3_fwd_chain(bath_hip_ctx *ctx, hipStream_t stream, const bath_hip_fsprofile *om, const bath_hip_seqs *dna, int Cv, float tEL, float tEM,
                          float *d_sc, float *d_xmx, const int64_t *d_xoff, FsJobs jobs, int cu_share = 1);
 int launch_fs3_bwd_chain(bath_hip_ctx *ctx, hipStream_t stream, const bath_hip_fsprofile *om, const bath_hip_seqs *dna, int Cv, float tEL, float tEM,
-                         float *d_sc, float *d_xmx, const int64_t *d_xoff, FsJobs jobs, int cu_share = 1 /* 2: the Forward parser runs beside it */,
-                         int bst_slot = 48, int stage_slot = 2 /* scratch / staging slots of the launch's batch starts */);
+                         float *d_sc, float *d_xmx, const int64_t *d_xoff, FsJobs jobs, int cu_share = 1 /* 2: the Forward parser runs beside it */);
 int launch_fs5_fwd_chain(bath_hip_ctx *ctx, hipStream_t stream, const bath_hip_fsprofile *om, const bath_hip_seqs *dna, int Cv, float tEL, float tEM, int c5_compat,
                          float *d_sc, float *d_fwd, const int64_t *d_foff, float *d_xmx, const int64_t *d_xoff, int cfg_len, FsJobs jobs, int *d_done);
 // ---- the 3-codon parsers in odds-ratio space (bath_fs_odds.hip)
@@ -245,6 +238,5 @@ int launch_fs3_odds(bath_hip_ctx *ctx, hipStream_t stream, const bath_hip_fsprof
 enum Fs5OddsKind { kFs5OddsEnvFwd = 0, kFs5OddsEnvBwd = 1, kFs5OddsRegionFwd = 2 };
 int launch_fs5_odds(bath_hip_ctx *ctx, hipStream_t stream, const bath_hip_fsprofile *om, const bath_hip_seqs *dna, Fs5OddsKind kind,
                     float *d_sc, float *d_mx, const int64_t *d_moff, float *d_xmx, const int64_t *d_xoff, int cfg_len, FsJobs jobs, int *d_done);
-inline bool fs_chain_enabled() { static const bool off = [] { const char *e = std::getenv("BATH_HIP_FS_HANDOFF"); return e && e[0] == '1'; }(); return !off; }   // BATH_HIP_FS_HANDOFF=1: the 64-step lane hand-off kernels, for A/B runs
 
 }  // namespace bath

@@ -47,19 +47,11 @@ template <bool EXACT, bool RING_G, int W>
 __global__ __launch_bounds__(W == 1 ? kWfBlock : 64 * W) void fs5_fwd_wf_kernel(SeqView dna, FsDev p, const float *__restrict__ loop_tab, const float *__restrict__ move_tab,
                                                               int c5_compat, float *__restrict__ sc, float *__restrict__ fwd, const int64_t *__restrict__ fwd_off,
                                                               float *__restrict__ xmx, const int64_t *__restrict__ xmx_off,
-                                                              float *ring_g /* [waves][(M+2)*8] or null: the ring lives in LDS */, FsJobs jobs, int dbg) {
+                                                              float *ring_g /* [waves][(M+2)*8] or null: the ring lives in LDS */, FsJobs jobs) {
   extern __shared__ __attribute__((aligned(16))) char lds[];
   float *s_tbl = reinterpret_cast<float *>(lds);
-#ifdef BATH_WF_PROBES
-  // (dbg & 8, a timing probe with wrong results: a table of 8000 entries, so that three blocks fit a CU -- what a compressed table would buy)
-  const int tbl_n = (dbg & 8) ? 8000 : kLogsumTbl;
-  for (int i = threadIdx.x; i < tbl_n; i += blockDim.x) s_tbl[i] = (i < 15700) ? p.logsum[i] : 0.f;
-#else
-  dbg = 0;                                        // the timing probes (WRONG results) exist only in a -DBATH_WF_PROBES build: their branches fold away here
-  constexpr int tbl_n = kLogsumTbl;
   fs_load_logsum_table(s_tbl, p.logsum);
-#endif
-  float *s_tf = s_tbl + tbl_n;
+  float *s_tf = s_tbl + kLogsumTbl;
   const int M = p.M;
   for (int i = threadIdx.x; i < (M + 2) * 8; i += blockDim.x) s_tf[i] = p.tf[i];
   __syncthreads();
@@ -172,10 +164,10 @@ __global__ __launch_bounds__(W == 1 ? kWfBlock : 64 * W) void fs5_fwd_wf_kernel(
       }
     };
     cu1 = cu2 = cu3 = cu4 = cu5 = make_float4(0.f, 0.f, 0.f, 0.f);
-    if (!(dbg & 1)) load_block(k, cu1, cu2, cu3, cu4, cu5);
+    load_block(k, cu1, cu2, cu3, cu4, cu5);
     for (int t0 = 0; t0 < T; t0 += 4) {
      nx1 = cu1; nx2 = cu2; nx3 = cu3; nx4 = cu4; nx5 = cu5;
-     if (!(dbg & 1)) load_block(k + 4, nx1, nx2, nx3, nx4, nx5);
+     load_block(k + 4, nx1, nx2, nx3, nx4, nx5);
 #pragma unroll
      for (int ts = 0; ts < 4; ts++) {
       const int t = t0 + ts;
@@ -217,21 +209,13 @@ __global__ __launch_bounds__(W == 1 ? kWfBlock : 64 * W) void fs5_fwd_wf_kernel(
         prefetch_row(rown + RW);
       }
       // the cell goes out after the loads above were issued: what the next step waits for is then a step old
-      if (act && !(dbg & 2)) {
+      // (the cells' address shape -- 16 B in four rows per lane quad -- is most of the stores' cost with a wave per envelope; staging
+      // them through LDS for a contiguous shape was measured and not kept: DESIGN.md 4.6.1)
+      if (act) {
         float4 *cell = reinterpret_cast<float4 *>(fo + ((size_t)row * (M + 1) + k) * 8);
         if (k == 1) { cell[-2] = make_float4(-INFINITY, -INFINITY, -INFINITY, -INFINITY); cell[-1] = cell[-2]; }
-        if (dbg & 4) {
-          // BATH_HIP_WF_DBG=4, a timing probe (the results are wrong): the four lanes of a quad write 64 contiguous bytes instead of 16
-          // bytes in four rows.  Round 4, 4800 envelopes, a wave each (16 waves per CU): 4.7 -> 2.5 ms (1.9 without any store) --
-          // the address shape is most of the stores' cost there; 2400 envelopes, two waves each (4 waves per CU): 2.49 -> 2.47, the
-          // step's latency is what counts.  Staging the cells through LDS to get that shape (80 B per lane: the ring must then move
-          // to global memory) was built and measured: 4.6 -> 4.1 ms a wave each, 2.5 -> 2.85 two waves each; not kept.
-          float4 *q = reinterpret_cast<float4 *>(fo + ((size_t)(row - (lane & 3)) * (M + 1) + (k + (lane & 3))) * 8) + (lane & 3);
-          q[0] = make_float4(Dk, Ik, Mk, c1); q[4] = make_float4(c2, c3, c4, c5);
-        } else {
         cell[0] = make_float4(Dk, Ik, Mk, c1);
         cell[1] = make_float4(c2, c3, c4, c5);
-        }
       }
       // E(i) <- LS(M, LS(D, E)) for k < M and for rows 1..4; rows >= 5 pair M and D first at node M (:392-394)
       const bool pairMD = (k == M) && (row >= 5);
@@ -295,18 +279,11 @@ __host__ __device__ inline int64_t fs_bwd_wf_steps(int L, int M, int RW) { retur
 template <bool EXACT, bool RING_G, int W>
 __global__ __launch_bounds__(W == 1 ? kWfBlock : 64 * W) void fs5_bwd_wf_kernel(SeqView dna, FsDev p, const float *__restrict__ loop_tab, const float *__restrict__ move_tab,
                                                               float *__restrict__ bck, const int64_t *__restrict__ bck_off, float *__restrict__ xmx, const int64_t *__restrict__ xmx_off,
-                                                              float *__restrict__ terms, const int64_t *__restrict__ term_off, float *ring_g, FsJobs jobs, int dbg) {
+                                                              float *__restrict__ terms, const int64_t *__restrict__ term_off, float *ring_g, FsJobs jobs) {
   extern __shared__ __attribute__((aligned(16))) char lds[];
   float *s_tbl = reinterpret_cast<float *>(lds);
-#ifdef BATH_WF_PROBES
-  const int tbl_n = (dbg & 8) ? 8000 : kLogsumTbl;                     // (the timing probe of fs5_fwd_wf_kernel)
-  for (int i = threadIdx.x; i < tbl_n; i += blockDim.x) s_tbl[i] = (i < 15700) ? p.logsum[i] : 0.f;
-#else
-  dbg = 0;
-  constexpr int tbl_n = kLogsumTbl;
   fs_load_logsum_table(s_tbl, p.logsum);
-#endif
-  float *s_tb = s_tbl + tbl_n;
+  float *s_tb = s_tbl + kLogsumTbl;
   const int M = p.M;
   for (int i = threadIdx.x; i < (M + 2) * 8; i += blockDim.x) s_tb[i] = p.tb[i];
   __syncthreads();
@@ -569,13 +546,8 @@ static int fs_wf_waves(bath_hip_ctx *ctx, int64_t n, int M) {
 struct WfGeom { int W, grid, block; bool lds_ring; size_t shmem; float *ring_g; };
 static int fs_wf_geometry(bath_hip_ctx *ctx, int64_t n, int M, DevBuf &ring_scratch, WfGeom *g) {
   static const bool ring_global = [] { const char *e = std::getenv("BATH_HIP_WF_RING_G"); return e && e[0] == '1'; }();
-#ifdef BATH_WF_PROBES
-  static const int dbg = [] { const char *e = std::getenv("BATH_HIP_WF_DBG"); return e ? std::atoi(e) : 0; }();   // timing probes, wrong results: probe builds only
-#else
-  constexpr int dbg = 0;
-#endif
   const int W = fs_wf_waves(ctx, n, M);
-  const size_t base = (size_t)(((dbg & 8) ? 8000 : kLogsumTbl) + (M + 2) * 8) * sizeof(float);
+  const size_t base = (size_t)(kLogsumTbl + (M + 2) * 8) * sizeof(float);
   const int nrings = (W == 1) ? kWfWaves : 1;
   const size_t ring_b = fs_wf_ring_floats(M) * sizeof(float) * nrings;
   const size_t extra = (W == 1) ? 0 : (size_t)W * 64 + (size_t)W * 16 + (size_t)64 * W * 4 + 64;      // mailboxes, C values, job
@@ -583,7 +555,7 @@ static int fs_wf_geometry(bath_hip_ctx *ctx, int64_t n, int M, DevBuf &ring_scra
   g->lds_ring = !ring_global && base + ring_b + extra <= 160 * 1024;
   g->shmem = base + (g->lds_ring ? ring_b : 0) + extra;
   g->block = (W == 1) ? kWfBlock : 64 * W;
-  const int per_cu = (W == 1) ? ((kWfBlock <= 512) ? 2 : 1) : (int)std::max<size_t>(1, std::min<size_t>((dbg & 8) ? 4 : 2, (160 * 1024) / g->shmem));
+  const int per_cu = (W == 1) ? ((kWfBlock <= 512) ? 2 : 1) : (int)std::max<size_t>(1, std::min<size_t>(2, (160 * 1024) / g->shmem));
   const int64_t jobs_per_block = (W == 1) ? kWfWaves : 1;
   g->grid = (int)std::max<int64_t>(1, std::min<int64_t>((n + jobs_per_block - 1) / jobs_per_block, (int64_t)ctx->prop.multiProcessorCount * per_cu));
   g->ring_g = nullptr;
@@ -622,16 +594,11 @@ static int fs_wf_geometry(bath_hip_ctx *ctx, int64_t n, int M, DevBuf &ring_scra
 int launch_fs5_fwd_wf(bath_hip_ctx *ctx, hipStream_t stream, const bath_hip_fsprofile *om, const bath_hip_seqs *dna, int exact, int c5_compat,
                       float *d_sc, float *d_fwd, const int64_t *d_foff, float *d_xmx, const int64_t *d_xoff, DevBuf &ring_scratch, FsJobs jobs) {
   const int M = om->M;
-#ifdef BATH_WF_PROBES
-  static const int dbg = [] { const char *e = std::getenv("BATH_HIP_WF_DBG"); return e ? std::atoi(e) : 0; }();   // timing probes, wrong results: probe builds only
-#else
-  constexpr int dbg = 0;
-#endif
   WfGeom g{};
   int st = fs_wf_geometry(ctx, dna->n, M, ring_scratch, &g);
   if (st != BATH_OK) return st;
   FsDev dev{om->M, om->pitch, om->maxcodons, om->d_rsc, om->d_tf, om->d_tb, om->d_logsum};
-  BATH_WF_DISPATCH(fs5_fwd_wf_kernel, dna->view(), dev, om->d_loop[1], om->d_move[1], c5_compat, d_sc, d_fwd, d_foff, d_xmx, d_xoff, g.ring_g, jobs, dbg);
+  BATH_WF_DISPATCH(fs5_fwd_wf_kernel, dna->view(), dev, om->d_loop[1], om->d_move[1], c5_compat, d_sc, d_fwd, d_foff, d_xmx, d_xoff, g.ring_g, jobs);
   BATH_HIP_TRY(ctx, hipGetLastError());
   return BATH_OK;
 }
@@ -643,11 +610,6 @@ int launch_fs5_bwd_wf(bath_hip_ctx *ctx, hipStream_t stream, const bath_hip_fspr
                       FsJobs jobs_sweep, FsJobs jobs_x) {
   const int M = om->M;
   const int64_t n = dna->n;
-#ifdef BATH_WF_PROBES
-  static const int dbg = [] { const char *e = std::getenv("BATH_HIP_WF_DBG"); return e ? std::atoi(e) : 0; }();   // timing probes, wrong results: probe builds only
-#else
-  constexpr int dbg = 0;
-#endif
   WfGeom g{};
   int st = fs_wf_geometry(ctx, n, M, ring_scratch, &g);
   if (st != BATH_OK) return st;
@@ -658,7 +620,7 @@ int launch_fs5_bwd_wf(bath_hip_ctx *ctx, hipStream_t stream, const bath_hip_fspr
   BATH_HIP_TRY(ctx, toff_scratch.reserve((size_t)(n + 1) * sizeof(int64_t)));
   if (ctx->stage_upload(3, toff_scratch.p, toff.data(), (size_t)(n + 1), stream) != BATH_OK) return BATH_EFAIL;   // through page-locked staging: no synchronize
   FsDev dev{om->M, om->pitch, om->maxcodons, om->d_rsc, om->d_tf, om->d_tb, om->d_logsum};
-  BATH_WF_DISPATCH(fs5_bwd_wf_kernel, dna->view(), dev, om->d_loop[1], om->d_move[1], d_bck, d_boff, d_xmx, d_xoff, terms_scratch.as<float>(), toff_scratch.as<int64_t>(), g.ring_g, jobs_sweep, dbg);
+  BATH_WF_DISPATCH(fs5_bwd_wf_kernel, dna->view(), dev, om->d_loop[1], om->d_move[1], d_bck, d_boff, d_xmx, d_xoff, terms_scratch.as<float>(), toff_scratch.as<int64_t>(), g.ring_g, jobs_sweep);
   BATH_HIP_TRY(ctx, hipGetLastError());
   const int xwaves = kFsBlock / 64;
   // few envelopes (a wave each would leave most CUs without a block): a block per envelope, its waves sharing the rows

@@ -48,8 +48,6 @@ python3 tools/fs_workers_probe.py --workers 1,2,3 --passes 6 > $OUT/fs_workers.t
 bash tools/c4_query_timeline.sh 3 > $OUT/c4_query_timeline_RtcB.txt 2>&1
 bash tools/c4_query_timeline.sh 2 > $OUT/c4_query_timeline_PTH2.txt 2>&1
 python3 tools/c4_items_probe.py 100 6 2>&1 | grep -v amdgpu.ids > $OUT/c4_items.txt
-# 5: A/B of the posterior-matrix store in the envelope stage (same box)
-for v in 0 1 0 1; do echo "== BATH_HIP_FS_STORE_PP=$v"; BATH_HIP_FS_STORE_PP=$v python3 tools/fs_strict_probe.py --steps 6 2>&1 | tail -1; done > $OUT/fs_store_pp_ab.txt
 python3 tools/chain_long_probe.py > $OUT/chain_long_probe.txt 2>&1
 python3 tools/pmc_summary.py $OUT/pmc_by_kernel.json $OUT/pmc_fetch $OUT/pmc_write $OUT/pmc_sq1 $OUT/pmc_sq2 $OUT/pmc_grbm > $OUT/pmc_summary.txt
 rm -rf $OUT/pmc_fetch $OUT/pmc_write $OUT/pmc_sq1 $OUT/pmc_sq2 $OUT/pmc_grbm
