@@ -1,31 +1,34 @@
-// bath_fs_windows.hip -- p7_pli_BuildDNAWindows and the per-window ORF summary of p7_pli_Frameshift ON THE DEVICE, and the
-// branch decision that follows the 3-codon Forward parser (p7_pipeline.c:462-572, :1364-1415, :1425-1465).
+// bath_fs_windows.hip -- p7_pli_BuildDNAWindows, the per-window ORF summary of p7_pli_Frameshift and the branch decision that
+// follows the 3-codon Forward parser (p7_pipeline.c:462-572, :1364-1415, :1425-1465): ONE set of rules, two drivers.
 //
-// Rounds 1-5 built the DNA windows on the host: the ORFs that passed F4 and their hit windows came back over PCIe, were sorted
-// and merged by host threads, the window descriptors went up again, and after the Forward parser the scores came back for a host
-// loop of three exp() per window -- 2.4 + 1.0 ms of a 60 ms pass in which nothing ran on the GPU (profiles/r05_fs_pass_timeline.txt).
-// Here the same steps are kernels on the context's stream, fed by what the cascade's lanes left in device memory:
-//   merge     the lanes' F4 survivors and hit windows, ids made the block's own, sort keys formed
-//   rank      the ORFs ordered by counting (keys are unique: rank = number of smaller keys; a few thousand records, tiled through
-//             LDS, the comparisons spread over the chip) by (sequence, strand, the order esl_gencode emits a strand's ORFs)
-//   hits      per hit window: its ORF's best window (highest score, then longest, then first) and k_min / k_max by atomics on the
-//             ORF's slot -- the hit windows need no order of their own
-//   orf       per ORF: its best hit window -> the DNA window it asks for (:486-527)
-//   group     per (sequence, strand): windows ordered by start (p7_hmmwindow_SortByStart) ...
-//   fuse      ... and overlapping ones fused, serially within the group as the reference does (:541-566)
-//   summary   per fused window: the ORFs inside it -- count, k_min / k_max, the table log-sum of their Forward scores in the
-//             reference's order, P_min, P_tot (:1376-1415, :1457)
-//   layout    the pool offsets of the windows' copies and the sequence-block view the parsers read
-//   decide    (after the parsers) null / bias / Forward scores -> P-values -> which branch each window takes (:1425-1465)
-// The host reads the result ONCE (the window records with their branch, and the ordered ORF list it needs for the standard
-// branch's ORF lists) through page-locked memory.  Same records as the host path (BATH_HIP_FS_WINDOWS_HOST=1 keeps that path for
-// A/B; it is also the fallback for inputs this path does not take: more than 32768 surviving ORFs or 65536 hit windows in a block,
-// or more than 1024 surviving ORFs on one strand of one sequence).
+// The rules (the ORFs' order on a strand, ORF -> the DNA window it asks for, fusing overlapping windows, a window's span and the
+// ORFs inside it, the window's summary with P_tot, the branch decision) are the __host__ __device__ functions at the top of this file.
+//   fs_build_windows_device   the default: kernels on the context's stream, fed by what the cascade's lanes left in device memory
+//     merge     the lanes' F4 survivors and hit windows, ids made the block's own, sort keys formed
+//     rank      the ORFs ordered by counting (keys are unique: rank = number of smaller keys; a few thousand records, tiled through
+//               LDS, the comparisons spread over the chip) by (sequence, strand, the order esl_gencode emits a strand's ORFs)
+//     hits      per hit window: its ORF's best window (highest score, then longest, then first) and k_min / k_max by atomics on the
+//               ORF's slot -- the hit windows need no order of their own
+//     orf       per ORF: its best hit window -> the DNA window it asks for (:486-527)
+//     group     per (sequence, strand): windows ordered by start (p7_hmmwindow_SortByStart) ...
+//     fuse      ... and overlapping ones fused, serially within the group as the reference does (:541-566)
+//     summary   per fused window: the ORFs inside it -- count, k_min / k_max, the table log-sum of their Forward scores in the
+//               reference's order, P_min, P_tot (:1376-1415, :1457)
+//     layout    the pool offsets of the windows' copies and the sequence-block view the parsers read
+//   fs_build_windows_host     the fallback for inputs the kernels do not take (more than 32768 surviving ORFs or 65536 hit windows
+//     in a block, more than 16 cascade lanes, more than 1024 surviving ORFs on one strand of one sequence; BATH_HIP_FS_WINDOWS_HOST=1
+//     sends every block here): the same steps as loops over the same rules, from the survivor lists fetched to the host, the
+//     (sequence, strand) groups spread over up to four threads
+// Both leave the same product (FsWinBuild): the ordered ORFs, the windows' records, gather descriptors, pool offsets and lengths, on
+// the host (page-locked) and in the same device buffers.  After the parsers fs_decide forms null / bias / Forward scores -> P-values ->
+// the branch of each window (:1425-1465) by the same rule where the windows were built: fsw_decide_kernel, the host reading the
+// completed records once, or a host loop with libm's exp / log for a block of the host build.
 #include <algorithm>
 #include <cmath>
 #include <cstdint>
 #include <cstdlib>
 #include <cstring>
+#include <thread>
 #include <vector>
 
 #include "bath_common.hpp"
@@ -41,7 +44,155 @@ constexpr int kMaxOrfs = 32768, kMaxHitWins = 65536, kMaxGroup = 1024;
 // BATH_HIP_FSW_MAX_GROUP=g (tests): groups of more than g ORFs send the block to the host path, so that the fallback runs on small inputs
 static int max_group() { static const int g = [] { const char *e = std::getenv("BATH_HIP_FSW_MAX_GROUP"); return e ? std::max(1, std::min(std::atoi(e), kMaxGroup)) : kMaxGroup; }(); return g; }
 struct Key { uint64_t hi, lo; };
-__device__ __forceinline__ bool key_less(const Key &a, const Key &b) { return a.hi < b.hi || (a.hi == b.hi && a.lo < b.lo); }
+__host__ __device__ __forceinline__ bool key_less(const Key &a, const Key &b) { return a.hi < b.hi || (a.hi == b.hi && a.lo < b.lo); }
+
+struct DnaWinDev { int32_t n, k, length; };
+struct BuildParams {
+  int M, max_length;
+  const float *prefix, *suffix;       // [M+1] P7_SCOREDATA window padding fractions (device or host arrays, as the caller's side reads them)
+  double F3, ftau, flambda;
+  int std_pipe;
+  const float *tbl;                   // p7_FLogsum's table on the device (the host has flogsum_host)
+};
+
+// ================================================================================================================================
+// The rules of p7_pli_BuildDNAWindows and of p7_pli_Frameshift's window summary, each stated once for the kernels and the host path.
+// ================================================================================================================================
+
+// min / max of 64-bit integers (host code resolves the unqualified names to the 32-bit overloads)
+__host__ __device__ inline int64_t min64(int64_t a, int64_t b) { return (a < b) ? a : b; }
+__host__ __device__ inline int64_t max64(int64_t a, int64_t b) { return (a > b) ? a : b; }
+
+// an F4 survivor as a cascade lane left it -> the ORF record, ids and offsets made the block's own; no hit window seen yet
+__host__ __device__ inline FsOrfDev fsw_orf_init(const FsCandRec &q, int64_t first_window, int64_t dpool, int32_t cand_base) {
+  FsOrfDev o;
+  o.w = q.window + first_window; o.aa_off = q.aa_off + dpool; o.P = q.P; o.cand = q.cand + cand_base;
+  o.strand = q.sf / 3; o.n = q.len; o.start = q.sf % 3 + 3 * q.startj + 1; o.end = o.start + 3 * o.n - 1;
+  o.fwd_null = q.fwdsc - q.nullsc;                                   // pli_tmp->fwdsc (p7_pipeline.c:1782)
+  o.wb = -1; o.we = 0; o.dw_n = 0; o.dw_len = 0; o.dw_k = 0; o.kmin = 0x7fffffff; o.kmax = 0; o.g0 = o.g1 = 0; o.pad_ = 0;
+  return o;
+}
+
+// the key that orders the ORFs: (sequence, strand), then the order esl_gencode emits a strand's ORFs -- when their closing stop
+// codon is read; ORFs still open at the end follow, frame by frame.  The candidate id makes the keys pairwise different.
+__host__ __device__ inline Key fsw_orf_key(const FsOrfDev &o, int n_seq) {
+  const uint64_t ea = (o.end + 3 > n_seq) ? 1 : 0;
+  const uint64_t val = ea ? (uint64_t)((o.start - 1) % 3) : (uint64_t)o.end;
+  return Key{((uint64_t)o.w << 1) | (uint64_t)o.strand, (ea << 62) | (val << 31) | (uint64_t)(uint32_t)o.cand};
+}
+
+// the ORF's best hit window (o.wb: its index in <wins>, -1: none) says which DNA window the ORF asks for (p7_pipeline.c:486-527)
+__host__ __device__ inline void fsw_orf_window(FsOrfDev &o, const WindowRec *wins, int n_seq, const BuildParams &p) {
+  const int best = o.wb;
+  int32_t cn, ck, cl;
+  if (best >= 0) { cn = wins[best].n; ck = wins[best].k; cl = wins[best].length; o.we = best + 1; }
+  else if (o.n >= p.M) { cn = (o.n - p.M) / 2 + 1; ck = p.M; cl = p.M; }            // :500-510: no window, centre of the model
+  else { cn = 1; ck = p.M - ((p.M - o.n) / 2); cl = o.n; }
+  if (best < 0) { o.wb = 0; o.we = 0; o.kmin = p.M; o.kmax = 0; }
+  int64_t ws = (int64_t)((double)(uint32_t)cn - ((double)p.max_length * (0.1 + (double)p.prefix[ck - cl + 1])) + 1);     // :513
+  int64_t wend = (int64_t)((double)((uint32_t)cn + (uint32_t)cl) + ((double)p.max_length * (0.1 + (double)p.suffix[ck])) - 2);   // :514
+  ws = min64(0, ws);                                            // :516-517 (sic)
+  wend = max64(o.n, wend);
+  ws = max64(1, (int64_t)o.start + ws * 3);                     // :520-527, o.start already on the strand being read
+  wend = min64(n_seq, (int64_t)o.start + wend * 3);
+  o.dw_n = (int32_t)ws; o.dw_k = ck; o.dw_len = (int32_t)(wend - ws + 1);
+}
+
+// a group's windows wl[g0, g1), ordered by start: overlapping ones fused, left to right (:541-566, pct_overlap = 0); returns the windows left
+__host__ __device__ inline int fsw_fuse(DnaWinDev *wl, int g0, int g1, int max_length) {
+  int keep = g0;
+  for (int i = g0 + 1; i < g1; i++) {
+    DnaWinDev prev = wl[keep];
+    const DnaWinDev cur = wl[i];
+    const int64_t pe = (int64_t)prev.n + prev.length - 1, ce = (int64_t)cur.n + cur.length - 1;
+    const int32_t ov = (int32_t)(min64(pe, ce) - max64(prev.n, cur.n) + 1);
+    const int64_t ms = min64(prev.n, cur.n), me = max64(pe, ce);
+    const int32_t ml = (int32_t)(me - ms + 1);
+    if (((float)ov / (float)min(prev.length, cur.length) > 0.f) && ml < (2 * (max_length * 3))) { prev.n = (int32_t)ms; prev.length = ml; wl[keep] = prev; }
+    else wl[++keep] = cur;
+  }
+  return keep - g0 + 1;
+}
+
+// a window's span in the coordinates of its sequence (:1373-1374), and whether an ORF of that strand lies inside it (:1405)
+struct WinSpan { int64_t dstart, wstart, wend; };
+__host__ __device__ inline WinSpan fsw_span(int strand, int n_seq, int32_t dw_n, int32_t dw_len) {
+  WinSpan sp;
+  sp.dstart = strand ? n_seq : 1;                                      // dnasq->start of a whole sequence
+  sp.wstart = strand ? sp.dstart - ((int64_t)dw_n + dw_len) : sp.dstart + dw_n - 1;
+  sp.wend = strand ? sp.dstart - dw_n + 1 : sp.wstart + dw_len - 1;
+  return sp;
+}
+__host__ __device__ inline bool fsw_orf_inside(const FsOrfDev &o, int strand, int n_seq, const WinSpan &sp) {
+  int64_t os, oe;
+  if (strand) { const int64_t rs = (int64_t)n_seq - o.start + 1, re = (int64_t)n_seq - o.end + 1; os = sp.dstart - (n_seq - re + 1) + 1; oe = sp.dstart - (n_seq - rs + 1) + 1; }
+  else { os = sp.dstart + o.start - 1; oe = sp.dstart + o.end - 1; }
+  return os >= sp.wstart && oe <= sp.wend;
+}
+
+// a fused window <dw> of the group orfs[g0, g1): the summary of the ORFs that lie inside it (p7_pipeline.c:1376-1415) -> the record
+// and the gather descriptor.  <seq_off>: the sequences' offsets in the DNA block; <logsum>: p7_FLogsum as the caller's side has it.
+template <class LogSum>
+__host__ __device__ inline void fsw_summarize(const FsOrfDev *orfs, int g0, int g1, const DnaWinDev &dw, int n_seq, const int64_t *seq_off, const BuildParams &p,
+                                              LogSum logsum, bath_fs_window *out, FsWinDev *desc) {
+  const int64_t w = orfs[g0].w;
+  const int strand = orfs[g0].strand;
+  const WinSpan sp = fsw_span(strand, n_seq, dw.n, dw.length);
+  int orf_cnt = 0, k_min = p.M, k_max = 0;
+  float tot = -INFINITY;
+  double P_min = INFINITY;
+  for (int b = g0; b < g1; b++) {
+    const FsOrfDev &o = orfs[b];
+    if (!fsw_orf_inside(o, strand, n_seq, sp)) continue;
+    P_min = fmin(P_min, o.P);
+    tot = logsum(tot, o.fwd_null);
+    orf_cnt++;
+    if (o.we > o.wb) { k_min = min(k_min, o.kmin); k_max = max(k_max, o.kmax); }
+  }
+  bath_fs_window r;
+  memset(&r, 0, sizeof r);
+  r.window = w; r.strand = strand; r.n = dw.n; r.length = dw.length;
+  r.orf_cnt = orf_cnt; r.k_min = k_min; r.k_max = k_max; r.tot_orfsc = tot; r.P_min = P_min;
+  const double x = (double)tot / 0.69314718055994529;
+  r.P_tot = p.std_pipe ? ((x < p.ftau) ? 1.0 : exp(-p.flambda * (x - p.ftau))) : 1.0;              // :1457; --fsonly: 1
+  *out = r;
+  FsWinDev d;
+  d.src_off = seq_off[w]; d.dst_off = 0; d.seq_n = n_seq; d.start = dw.n; d.len = dw.length; d.strand = strand; d.kmin = k_min; d.kmax = k_max;
+  *desc = d;
+}
+
+// p7_pipeline.c:1425-1465 for one window: null score (p7_bg_fs_NullOne), bias filter score (p7_bg_fs_FilterScore: the three frames'
+// Forward scores of the 2-state filter HMM from fs_bias_kernel, <bias>[2][3], summed with the table, plus the length term), Forward
+// score -> P-values -> branch
+template <class LogSum>
+__host__ __device__ inline void fsw_decide(bath_fs_window &r, const float *bias, float fwdsc, LogSum logsum, int do_biasfilter, int std_pipe, double F3, double tau3, double lambda) {
+  const double kLn2 = 0.69314718055994529;
+  const int L3 = r.length / 3;
+  const float p1 = (float)L3 / (float)(L3 + 1);
+  const float per_frame = (float)((float)L3 * log((double)p1) + log(1. - p1));                        // p7_bg_fs_NullOne, p7_bg.c:380
+  r.nullsc = (float)(per_frame + log(3.0));
+  if (do_biasfilter) {
+    float f2[2];
+    for (int pass = 0; pass < 2; pass++) {
+      const float *b = &bias[pass * 3];
+      float sum = -INFINITY;
+      for (int f = 0; f < 3; f++) sum = logsum(sum, b[f]);
+      f2[pass] = (float)((double)sum + ((double)((float)L3 * logf(p1) + logf((float)(1. - p1))) + log(3.0)));   // p7_bg.c:561
+    }
+    r.filtersc = f2[0];
+    if (r.k_min <= r.k_max && f2[1] > r.filtersc) r.filtersc = f2[1];                                  // :1432-1440
+  } else r.filtersc = r.nullsc;
+  r.fwdsc = fwdsc;
+  const float seqscore = (float)((r.fwdsc - r.filtersc) / kLn2);
+  const double x1 = (double)seqscore, x2 = (r.fwdsc - r.nullsc) / kLn2;
+  r.P_fs = (x1 < tau3) ? 1.0 : exp(-lambda * (x1 - tau3));
+  r.P_null = (x2 < tau3) ? 1.0 : exp(-lambda * (x2 - tau3));
+  if (r.P_fs <= F3 && (r.P_null < r.P_tot || (r.P_null == r.P_tot && r.orf_cnt > 1) || r.P_min > F3)) r.branch = 1;
+  else r.branch = std_pipe ? 2 : 0;                                                                    // :1480: --fsonly has no standard branch
+}
+
+// a window's copy in the pool: padded to 16 bytes + 16
+__host__ __device__ inline long long fsw_pool_pitch(int len) { return ((long long)len + 15) / 16 * 16 + 16; }
 
 struct LaneArgs { FsLaneSurv l[16]; int n; int c_begin[17], w_begin[17]; };
 
@@ -54,17 +205,9 @@ __global__ void fsw_merge_kernel(LaneArgs L, const int32_t *__restrict__ seq_len
     int k = 0;
     while (t >= L.c_begin[k + 1]) k++;
     const FsCandRec q = L.l[k].d_c[t - L.c_begin[k]];
-    FsOrfDev o;
-    o.w = q.window + L.l[k].first_window; o.aa_off = q.aa_off + L.l[k].dpool; o.P = q.P; o.cand = q.cand + L.l[k].cand_base;
-    o.strand = q.sf / 3; o.n = q.len; o.start = q.sf % 3 + 3 * q.startj + 1; o.end = o.start + 3 * o.n - 1;
-    o.fwd_null = q.fwdsc - q.nullsc;                                   // pli_tmp->fwdsc (p7_pipeline.c:1782)
-    o.wb = -1; o.we = 0; o.dw_n = 0; o.dw_len = 0; o.dw_k = 0; o.kmin = 0x7fffffff; o.kmax = 0; o.g0 = o.g1 = 0; o.pad_ = 0;
+    const FsOrfDev o = fsw_orf_init(q, L.l[k].first_window, L.l[k].dpool, L.l[k].cand_base);
     orfs[t] = o;
-    // esl_gencode emits a strand's ORFs when their closing stop codon is read; ORFs still open at the end follow, frame by frame
-    const int n_seq = seq_len[o.w];
-    const uint64_t ea = (o.end + 3 > n_seq) ? 1 : 0;
-    const uint64_t val = ea ? (uint64_t)((o.start - 1) % 3) : (uint64_t)o.end;
-    okey[t] = Key{((uint64_t)o.w << 1) | (uint64_t)o.strand, (ea << 62) | (val << 31) | (uint64_t)(uint32_t)o.cand};
+    okey[t] = fsw_orf_key(o, seq_len[o.w]);
   }
   if (t < n_w) {
     int k = 0;
@@ -133,37 +276,14 @@ __global__ void fsw_scatter_kernel(const T *__restrict__ in, const int32_t *__re
   if (i < n) out[rank[i]] = in[i];
 }
 
-struct BuildParams {
-  int M, max_length;
-  const float *prefix, *suffix;       // [M+1] P7_SCOREDATA window padding fractions
-  double F3, ftau, flambda;
-  int std_pipe;
-  const float *tbl;                   // p7_FLogsum's table
-};
-
-// per ORF (in order): its best hit window says which DNA window the ORF asks for (p7_pipeline.c:486-527)
+// per ORF (in order): its best hit window says which DNA window the ORF asks for
 __global__ void fsw_orf_kernel(FsOrfDev *__restrict__ orfs, int n, const WindowRec *__restrict__ wins, const int32_t *__restrict__ seq_len, BuildParams p) {
   const int s = blockIdx.x * blockDim.x + threadIdx.x;
   if (s >= n) return;
   FsOrfDev o = orfs[s];
-  const int best = o.wb;
-  int32_t cn, ck, cl;
-  if (best >= 0) { cn = wins[best].n; ck = wins[best].k; cl = wins[best].length; o.we = best + 1; }
-  else if (o.n >= p.M) { cn = (o.n - p.M) / 2 + 1; ck = p.M; cl = p.M; }            // :500-510: no window, centre of the model
-  else { cn = 1; ck = p.M - ((p.M - o.n) / 2); cl = o.n; }
-  if (best < 0) { o.wb = 0; o.we = 0; o.kmin = p.M; o.kmax = 0; }
-  const int n_seq = seq_len[o.w];
-  int64_t ws = (int64_t)((double)(uint32_t)cn - ((double)p.max_length * (0.1 + (double)p.prefix[ck - cl + 1])) + 1);     // :513
-  int64_t wend = (int64_t)((double)((uint32_t)cn + (uint32_t)cl) + ((double)p.max_length * (0.1 + (double)p.suffix[ck])) - 2);   // :514
-  ws = min((int64_t)0, ws);                                            // :516-517 (sic)
-  wend = max((int64_t)o.n, wend);
-  ws = max((int64_t)1, (int64_t)o.start + ws * 3);                     // :520-527, o.start already on the strand being read
-  wend = min((int64_t)n_seq, (int64_t)o.start + wend * 3);
-  o.dw_n = (int32_t)ws; o.dw_k = ck; o.dw_len = (int32_t)(wend - ws + 1);
+  fsw_orf_window(o, wins, seq_len[o.w], p);
   orfs[s] = o;
 }
-
-struct DnaWinDev { int32_t n, k, length; };
 
 // per ORF: the bounds of its (sequence, strand) group, and its window's place in the group's list ordered by start
 // (p7_hmmwindow_SortByStart; equal starts keep the ORFs' order)
@@ -183,24 +303,12 @@ __global__ void fsw_group_kernel(FsOrfDev *__restrict__ orfs, int n, DnaWinDev *
   orfs[s].g0 = g0; orfs[s].g1 = g1;
 }
 
-// per group (its first ORF's thread): overlapping windows fused, left to right (:541-566, pct_overlap = 0); cnt[g0] = windows left
+// per group (its first ORF's thread): overlapping windows fused; cnt[g0] = windows left
 __global__ void fsw_fuse_kernel(const FsOrfDev *__restrict__ orfs, int n, DnaWinDev *__restrict__ wl, int32_t *__restrict__ cnt, int max_length) {
   const int s = blockIdx.x * blockDim.x + threadIdx.x;
   if (s >= n) return;
   const int g0 = orfs[s].g0, g1 = orfs[s].g1;
-  if (s != g0) { cnt[s] = 0; return; }
-  int keep = g0;
-  for (int i = g0 + 1; i < g1; i++) {
-    DnaWinDev prev = wl[keep];
-    const DnaWinDev cur = wl[i];
-    const int64_t pe = (int64_t)prev.n + prev.length - 1, ce = (int64_t)cur.n + cur.length - 1;
-    const int32_t ov = (int32_t)(min(pe, ce) - max((int64_t)prev.n, (int64_t)cur.n) + 1);
-    const int64_t ms = min((int64_t)prev.n, (int64_t)cur.n), me = max(pe, ce);
-    const int32_t ml = (int32_t)(me - ms + 1);
-    if (((float)ov / (float)min(prev.length, cur.length) > 0.f) && ml < (2 * (max_length * 3))) { prev.n = (int32_t)ms; prev.length = ml; wl[keep] = prev; }
-    else wl[++keep] = cur;
-  }
-  cnt[s] = keep - g0 + 1;
+  cnt[s] = (s != g0) ? 0 : fsw_fuse(wl, g0, g1, max_length);
 }
 
 // exclusive prefix sums of cnt[0..n) by one block; total -> hdr[0]
@@ -223,7 +331,7 @@ __global__ __launch_bounds__(1024) void fsw_scan_kernel(const int32_t *__restric
   if (threadIdx.x == 1023) hdr[0] = part[1023];
 }
 
-// per fused window: the summary of the ORFs that lie inside it (p7_pipeline.c:1376-1415), the record and the gather descriptor
+// per fused window: its summary, the record and the gather descriptor
 __global__ void fsw_summary_kernel(const FsOrfDev *__restrict__ orfs, int n, const DnaWinDev *__restrict__ wl, const int32_t *__restrict__ cnt,
                                    const int32_t *__restrict__ base, const int64_t *__restrict__ seq_off, const int32_t *__restrict__ seq_len, BuildParams p,
                                    bath_fs_window *__restrict__ out, FsWinDev *__restrict__ desc, int32_t *__restrict__ grp) {
@@ -231,38 +339,9 @@ __global__ void fsw_summary_kernel(const FsOrfDev *__restrict__ orfs, int n, con
   if (s >= n) return;
   const int g0 = orfs[s].g0, g1 = orfs[s].g1;
   if (s - g0 >= cnt[g0]) return;
-  const DnaWinDev dw = wl[s];
   const int64_t w = orfs[g0].w;
-  const int strand = orfs[g0].strand;
-  const int n_seq = seq_len[w];
-  const int64_t dstart = strand ? n_seq : 1;                           // dnasq->start of a whole sequence
-  const int64_t wstart = strand ? dstart - ((int64_t)dw.n + dw.length) : dstart + dw.n - 1;       // :1373-1374
-  const int64_t wend = strand ? dstart - dw.n + 1 : wstart + dw.length - 1;
-  int orf_cnt = 0, k_min = p.M, k_max = 0;
-  float tot = -INFINITY;
-  double P_min = INFINITY;
-  for (int b = g0; b < g1; b++) {
-    const FsOrfDev &o = orfs[b];
-    int64_t os, oe;
-    if (strand) { const int64_t rs = (int64_t)n_seq - o.start + 1, re = (int64_t)n_seq - o.end + 1; os = dstart - (n_seq - re + 1) + 1; oe = dstart - (n_seq - rs + 1) + 1; }
-    else { os = dstart + o.start - 1; oe = dstart + o.end - 1; }
-    if (!(os >= wstart && oe <= wend)) continue;                       // :1405
-    P_min = fmin(P_min, o.P);
-    tot = flogsum_g(tot, o.fwd_null, p.tbl);
-    orf_cnt++;
-    if (o.we > o.wb) { k_min = min(k_min, o.kmin); k_max = max(k_max, o.kmax); }
-  }
   const int idx = base[g0] + (s - g0);
-  bath_fs_window r;
-  memset(&r, 0, sizeof r);
-  r.window = w; r.strand = strand; r.n = dw.n; r.length = dw.length;
-  r.orf_cnt = orf_cnt; r.k_min = k_min; r.k_max = k_max; r.tot_orfsc = tot; r.P_min = P_min;
-  const double x = (double)tot / 0.69314718055994529;
-  r.P_tot = p.std_pipe ? ((x < p.ftau) ? 1.0 : exp(-p.flambda * (x - p.ftau))) : 1.0;              // :1457; --fsonly: 1
-  out[idx] = r;
-  FsWinDev d;
-  d.src_off = seq_off[w]; d.dst_off = 0; d.seq_n = n_seq; d.start = dw.n; d.len = dw.length; d.strand = strand; d.kmin = k_min; d.kmax = k_max;
-  desc[idx] = d;
+  fsw_summarize(orfs, g0, g1, wl[s], seq_len[w], seq_off, p, [tbl = p.tbl](float a, float b) { return flogsum_g(a, b, tbl); }, &out[idx], &desc[idx]);
   grp[2 * idx] = g0; grp[2 * idx + 1] = g1;
 }
 
@@ -276,7 +355,7 @@ __global__ __launch_bounds__(1024) void fsw_layout_kernel(FsWinDev *__restrict__
   const int b = threadIdx.x * per, e = min(nw, b + per);
   long long s = 0, tot = 0;
   int mx = 0;
-  for (int i = b; i < e; i++) { const int len = desc[i].len; s += ((long long)len + 15) / 16 * 16 + 16; tot += len; mx = max(mx, len); }
+  for (int i = b; i < e; i++) { const int len = desc[i].len; s += fsw_pool_pitch(len); tot += len; mx = max(mx, len); }
   part[threadIdx.x] = s; pmax[threadIdx.x] = mx;
   __syncthreads();
   for (int d = 1; d < 1024; d <<= 1) {
@@ -290,7 +369,7 @@ __global__ __launch_bounds__(1024) void fsw_layout_kernel(FsWinDev *__restrict__
   for (int i = b; i < e; i++) {
     const int len = desc[i].len;
     desc[i].dst_off = run; voff[i] = run; vlen[i] = len;
-    run += ((long long)len + 15) / 16 * 16 + 16;
+    run += fsw_pool_pitch(len);
   }
   // total nucleotides: a second, tiny reduction through the same array
   __syncthreads();
@@ -308,41 +387,39 @@ __global__ __launch_bounds__(1024) void fsw_layout_kernel(FsWinDev *__restrict__
   }
 }
 
-// p7_pipeline.c:1425-1465 per window: null score (p7_bg_fs_NullOne), bias filter score (p7_bg_fs_FilterScore: the three frames'
-// Forward scores of the 2-state filter HMM from fs_bias_kernel, summed with the table, plus the length term), Forward score ->
-// P-values -> branch
+// per window, after the parsers: the branch decision
 __global__ void fsw_decide_kernel(bath_fs_window *__restrict__ out, int nw, const float *__restrict__ bias /* [nw][2][3] */, const float *__restrict__ fsc,
                                   const float *__restrict__ tbl, int do_biasfilter, int std_pipe, double F3, double tau3, double lambda) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= nw) return;
   bath_fs_window r = out[i];
-  const double kLn2 = 0.69314718055994529;
-  const int L3 = r.length / 3;
-  const float p1 = (float)L3 / (float)(L3 + 1);
-  const float per_frame = (float)((float)L3 * log((double)p1) + log(1. - p1));                        // p7_bg_fs_NullOne, p7_bg.c:380
-  r.nullsc = (float)(per_frame + log(3.0));
-  if (do_biasfilter) {
-    float f2[2];
-    for (int pass = 0; pass < 2; pass++) {
-      const float *b = &bias[((size_t)i * 2 + pass) * 3];
-      float sum = -INFINITY;
-      for (int f = 0; f < 3; f++) sum = flogsum_g(sum, b[f], tbl);
-      f2[pass] = (float)((double)sum + ((double)((float)L3 * logf(p1) + logf((float)(1. - p1))) + log(3.0)));   // p7_bg.c:561
-    }
-    r.filtersc = f2[0];
-    if (r.k_min <= r.k_max && f2[1] > r.filtersc) r.filtersc = f2[1];                                  // :1432-1440
-  } else r.filtersc = r.nullsc;
-  r.fwdsc = fsc[i];
-  const float seqscore = (float)((r.fwdsc - r.filtersc) / kLn2);
-  const double x1 = (double)seqscore, x2 = (r.fwdsc - r.nullsc) / kLn2;
-  r.P_fs = (x1 < tau3) ? 1.0 : exp(-lambda * (x1 - tau3));
-  r.P_null = (x2 < tau3) ? 1.0 : exp(-lambda * (x2 - tau3));
-  if (r.P_fs <= F3 && (r.P_null < r.P_tot || (r.P_null == r.P_tot && r.orf_cnt > 1) || r.P_min > F3)) r.branch = 1;
-  else r.branch = std_pipe ? 2 : 0;                                                                    // :1480: --fsonly has no standard branch
+  fsw_decide(r, &bias[(size_t)i * 6], fsc[i], [tbl](float a, float b) { return flogsum_g(a, b, tbl); }, do_biasfilter, std_pipe, F3, tau3, lambda);
   out[i] = r;
 }
 
 }  // namespace
+
+// What a build leaves in scratch[51] and (regions A and B) in the page-locked stage[6], records back to back.  Two regions for the
+// device path's read-back: A = what the host needs BEFORE it can launch the parsers (header, the windows' pool offsets and lengths),
+// B = what it reads after the branch decision (ordered ORFs, group bounds; the records travel then, completed).
+struct ResLayout { size_t hdr, voff, vlen, a_bytes, orf, grp, b_end, out, desc, bytes; };
+static size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
+static ResLayout res_layout(int n) {
+  static_assert(sizeof(FsOrfDev) % 8 == 0 && sizeof(bath_fs_window) % 8 == 0 && sizeof(FsWinDev) % 8 == 0, "records are laid out back to back");
+  ResLayout r;
+  r.hdr = 0; r.voff = 256; r.vlen = r.voff + al256((size_t)n * 8); r.a_bytes = r.vlen + al256((size_t)n * 4);
+  r.orf = r.a_bytes; r.grp = r.orf + al256((size_t)n * sizeof(FsOrfDev)); r.b_end = r.grp + al256((size_t)n * 8);
+  r.out = r.b_end; r.desc = r.out + al256((size_t)n * sizeof(bath_fs_window)); r.bytes = r.desc + al256((size_t)n * sizeof(FsWinDev));
+  return r;
+}
+// the product's pointers into the two buffers
+static void res_bind(const ResLayout &r, char *h, char *d, FsWinBuild *B) {
+  B->h_orfs = reinterpret_cast<const FsOrfDev *>(h + r.orf); B->h_grp = reinterpret_cast<const int32_t *>(h + r.grp);
+  B->h_voff = reinterpret_cast<const int64_t *>(h + r.voff); B->h_vlen = reinterpret_cast<const int32_t *>(h + r.vlen);
+  B->h_out = reinterpret_cast<const bath_fs_window *>(h + r.out);
+  B->d_out = reinterpret_cast<bath_fs_window *>(d + r.out); B->d_desc = reinterpret_cast<const FsWinDev *>(d + r.desc);
+  B->d_voff = reinterpret_cast<const int64_t *>(d + r.voff); B->d_vlen = reinterpret_cast<const int32_t *>(d + r.vlen);
+}
 
 bool fs_windows_on_device() {
   static const bool host = [] { const char *e = std::getenv("BATH_HIP_FS_WINDOWS_HOST"); return e && e[0] == '1'; }();
@@ -362,7 +439,6 @@ int fs_build_windows_device(bath_hip_ctx *ctx, const bath_hip_oprofile *om, cons
   const int M = om->M;
   // the window padding fractions of P7_SCOREDATA, once per profile and context
   DevBuf &b_pad = ctx->scratch[52];
-  static_assert(sizeof(FsOrfDev) % 8 == 0 && sizeof(bath_fs_window) % 8 == 0 && sizeof(FsWinDev) % 8 == 0, "records are laid out back to back");
   if (ctx->fsw_pad_uid != om->uid || !b_pad.p) {
     BATH_HIP_TRY(ctx, b_pad.reserve((size_t)(M + 1) * 2 * sizeof(float) + 64));
     BATH_HIP_TRY(ctx, hipMemcpyAsync(b_pad.p, om->prefix_lengths.data(), (size_t)(M + 1) * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
@@ -370,33 +446,29 @@ int fs_build_windows_device(bath_hip_ctx *ctx, const bath_hip_oprofile *om, cons
     BATH_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     ctx->fsw_pad_uid = om->uid;
   }
-  // workspace: the unordered ORFs, their keys and ranks, the hit windows, candidate -> slot, best keys, the groups' window lists,
-  // counts.  Results, two regions: A = what the host needs BEFORE it can launch the parsers (header, the windows' pool offsets and
-  // lengths), B = what it reads after the branch decision (ordered ORFs, group bounds; the records travel then, completed).
-  auto al = [](size_t x) { return (x + 255) & ~(size_t)255; };
+  // workspace: the unordered ORFs, their keys and ranks, the hit windows, candidate -> slot, best keys, the groups' window lists, counts
+  auto al = al256;
   const size_t o_orf0 = 0, o_okey = o_orf0 + al((size_t)n * sizeof(FsOrfDev)), o_orank = o_okey + al((size_t)n * sizeof(Key)),
                o_win = o_orank + al((size_t)n * 4), o_slot = o_win + al((size_t)std::max(nhw, 1) * sizeof(WindowRec)), o_best = o_slot + al((size_t)std::max(nc_total, 1) * 4),
                o_wl = o_best + al((size_t)n * 8), o_cnt = o_wl + al((size_t)n * sizeof(DnaWinDev)), o_base = o_cnt + al((size_t)n * 4), ws_bytes = o_base + al((size_t)n * 4);
-  const size_t r_hdr = 0, r_voff = 256, r_vlen = r_voff + al((size_t)n * 8), a_bytes = r_vlen + al((size_t)n * 4),
-               r_orf = a_bytes, r_grp = r_orf + al((size_t)n * sizeof(FsOrfDev)), b_end = r_grp + al((size_t)n * 8),
-               r_out = b_end, r_desc = r_out + al((size_t)n * sizeof(bath_fs_window)), res_bytes = r_desc + al((size_t)n * sizeof(FsWinDev));
+  const ResLayout R = res_layout(n);
   DevBuf &b_ws = ctx->scratch[50], &b_res = ctx->scratch[51];
   BATH_HIP_TRY(ctx, b_ws.reserve(ws_bytes + 256));
-  BATH_HIP_TRY(ctx, b_res.reserve(res_bytes + 256));
-  if (ctx->stage[6].reserve(b_end + 256) != hipSuccess) { ctx->set_error("cannot allocate page-locked staging memory"); return BATH_EFAIL; }
+  BATH_HIP_TRY(ctx, b_res.reserve(R.bytes + 256));
+  if (ctx->stage[6].reserve(R.b_end + 256) != hipSuccess) { ctx->set_error("cannot allocate page-locked staging memory"); return BATH_EFAIL; }
   char *ws = b_ws.as<char>(), *rs = b_res.as<char>();
-  FsOrfDev *d_orf0 = reinterpret_cast<FsOrfDev *>(ws + o_orf0), *d_orf = reinterpret_cast<FsOrfDev *>(rs + r_orf);
+  FsOrfDev *d_orf0 = reinterpret_cast<FsOrfDev *>(ws + o_orf0), *d_orf = reinterpret_cast<FsOrfDev *>(rs + R.orf);
   Key *d_okey = reinterpret_cast<Key *>(ws + o_okey);
   int32_t *d_orank = reinterpret_cast<int32_t *>(ws + o_orank), *d_slot = reinterpret_cast<int32_t *>(ws + o_slot);
   WindowRec *d_win = reinterpret_cast<WindowRec *>(ws + o_win);
   unsigned long long *d_best = reinterpret_cast<unsigned long long *>(ws + o_best);
   DnaWinDev *d_wl = reinterpret_cast<DnaWinDev *>(ws + o_wl);
   int32_t *d_cnt = reinterpret_cast<int32_t *>(ws + o_cnt), *d_base = reinterpret_cast<int32_t *>(ws + o_base);
-  int32_t *d_hdr = reinterpret_cast<int32_t *>(rs + r_hdr), *d_grp = reinterpret_cast<int32_t *>(rs + r_grp);
-  bath_fs_window *d_out = reinterpret_cast<bath_fs_window *>(rs + r_out);
-  FsWinDev *d_desc = reinterpret_cast<FsWinDev *>(rs + r_desc);
-  int64_t *d_voff = reinterpret_cast<int64_t *>(rs + r_voff);
-  int32_t *d_vlen = reinterpret_cast<int32_t *>(rs + r_vlen);
+  int32_t *d_hdr = reinterpret_cast<int32_t *>(rs + R.hdr), *d_grp = reinterpret_cast<int32_t *>(rs + R.grp);
+  bath_fs_window *d_out = reinterpret_cast<bath_fs_window *>(rs + R.out);
+  FsWinDev *d_desc = reinterpret_cast<FsWinDev *>(rs + R.desc);
+  int64_t *d_voff = reinterpret_cast<int64_t *>(rs + R.voff);
+  int32_t *d_vlen = reinterpret_cast<int32_t *>(rs + R.vlen);
   hipStream_t s = ctx->stream;
   BATH_HIP_TRY(ctx, hipMemsetAsync(d_hdr, 0, 256, s));
   BATH_HIP_TRY(ctx, hipMemsetAsync(d_orank, 0, (size_t)n * 4, s));
@@ -424,25 +496,129 @@ int fs_build_windows_device(bath_hip_ctx *ctx, const bath_hip_oprofile *om, cons
   // region A now (the one synchronize of this stage), region B behind it on the same stream: it is complete long before the
   // decision's synchronize, which is the next time the host looks
   char *h = static_cast<char *>(ctx->stage[6].p);
-  BATH_HIP_TRY(ctx, hipMemcpyAsync(h, rs, a_bytes, hipMemcpyDeviceToHost, s));
+  BATH_HIP_TRY(ctx, hipMemcpyAsync(h, rs, R.a_bytes, hipMemcpyDeviceToHost, s));
   BATH_HIP_TRY(ctx, hipStreamSynchronize(s));
-  BATH_HIP_TRY(ctx, hipMemcpyAsync(h + a_bytes, rs + a_bytes, b_end - a_bytes, hipMemcpyDeviceToHost, s));
-  const int32_t *hdr = reinterpret_cast<const int32_t *>(h + r_hdr);
+  BATH_HIP_TRY(ctx, hipMemcpyAsync(h + R.a_bytes, rs + R.a_bytes, R.b_end - R.a_bytes, hipMemcpyDeviceToHost, s));
+  const int32_t *hdr = reinterpret_cast<const int32_t *>(h + R.hdr);
   if (hdr[1] != 0) { BATH_HIP_TRY(ctx, hipStreamSynchronize(s)); return BATH_ENORESULT; }      // a group beyond kMaxGroup: the host path
   B->n_orfs = n; B->nw = hdr[0]; B->maxlen = hdr[2];
   std::memcpy(&B->pool_bytes, &hdr[4], 8); std::memcpy(&B->total, &hdr[6], 8);
-  B->h_orfs = reinterpret_cast<const FsOrfDev *>(h + r_orf); B->h_grp = reinterpret_cast<const int32_t *>(h + r_grp);
-  B->h_voff = reinterpret_cast<const int64_t *>(h + r_voff); B->h_vlen = reinterpret_cast<const int32_t *>(h + r_vlen);
-  B->d_out = d_out; B->d_desc = d_desc; B->d_voff = d_voff; B->d_vlen = d_vlen;
+  res_bind(R, h, rs, B);
   return BATH_OK;
 }
 
-int fs_decide_device(bath_hip_ctx *ctx, const bath_hip_fsprofile *om_fs3, const bath_pipeline_params *prm, const FsWinBuild &B, const float *d_bias,
-                     const float *d_fsc, bath_fs_window *h_out) {
+// The same product from the survivor lists on the host: <sel> in ascending candidate id, <wins> by (candidate id, start), ids the block's own.
+int fs_build_windows_host(bath_hip_ctx *ctx, const bath_hip_oprofile *om, const bath_hip_seqs *dna, const bath_pipeline_params *prm,
+                          const FsCandRec *sel, int n, const WindowRec *wins, int nhw, FsWinBuild *B) {
+  *B = FsWinBuild{};
+  if (n == 0) return BATH_OK;
+  const ResLayout R = res_layout(n);
+  DevBuf &b_res = ctx->scratch[51];
+  BATH_HIP_TRY(ctx, b_res.reserve(R.bytes + 256));
+  if (ctx->stage[6].reserve(R.bytes + 256) != hipSuccess) { ctx->set_error("cannot allocate page-locked staging memory"); return BATH_EFAIL; }
+  char *h = static_cast<char *>(ctx->stage[6].p);
+  FsOrfDev *orfs = reinterpret_cast<FsOrfDev *>(h + R.orf);
+  int32_t *grp = reinterpret_cast<int32_t *>(h + R.grp), *vlen = reinterpret_cast<int32_t *>(h + R.vlen);
+  int64_t *voff = reinterpret_cast<int64_t *>(h + R.voff);
+  bath_fs_window *out = reinterpret_cast<bath_fs_window *>(h + R.out);
+  FsWinDev *desc = reinterpret_cast<FsWinDev *>(h + R.desc);
+  const BuildParams p{om->M, om->max_length, om->prefix_lengths.data(), om->suffix_lengths.data(), prm->F3, (double)om->evparam[BATH_FTAU], (double)om->evparam[BATH_FLAMBDA],
+                      prm->std_pipe, nullptr};
+
+  // ---- the ORFs with their best hit window (highest score, then longest, then first: :486-495) and k_min / k_max, then in the reference's order
+  struct Keyed { Key key; FsOrfDev o; };
+  std::vector<Keyed> keyed((size_t)n);
+  for (int i = 0, wi = 0; i < n; i++) {
+    FsOrfDev o = fsw_orf_init(sel[i], 0, 0, 0);
+    while (wi < nhw && wins[wi].cand < o.cand) wi++;
+    for (; wi < nhw && wins[wi].cand == o.cand; wi++) {
+      const WindowRec &x = wins[wi];
+      if (o.wb < 0 || x.score > wins[o.wb].score || (x.score == wins[o.wb].score && x.length > wins[o.wb].length)) o.wb = wi;
+      o.kmin = std::min(o.kmin, x.k - x.length + 1); o.kmax = std::max(o.kmax, x.k);
+    }
+    keyed[(size_t)i] = Keyed{fsw_orf_key(o, dna->h_len[(size_t)o.w]), o};
+  }
+  std::sort(keyed.begin(), keyed.end(), [](const Keyed &a, const Keyed &b) { return key_less(a.key, b.key); });
+  std::vector<int> gstart;                                                   // first ORF of every (sequence, strand) group, and the end
+  for (int s = 0; s < n; s++) {
+    orfs[s] = keyed[(size_t)s].o;
+    if (s == 0 || orfs[s].w != orfs[s - 1].w || orfs[s].strand != orfs[s - 1].strand) gstart.push_back(s);
+  }
+  gstart.push_back(n);
+  const size_t ngroups = gstart.size() - 1;
+
+  // ---- per group: the ORFs' windows, ordered by start (p7_hmmwindow_SortByStart) and fused, and the summary of every window that is
+  // left, at the slot of the group's ORF of the same rank.  The groups are independent: host threads take contiguous runs of them.
+  std::vector<DnaWinDev> wl((size_t)n);
+  std::vector<bath_fs_window> out_slot((size_t)n);
+  std::vector<FsWinDev> desc_slot((size_t)n);
+  std::vector<int> cnt(ngroups);
+  const int nparts = (int)std::max<size_t>(1, std::min<size_t>(4, ngroups / 256));
+  auto build = [&](int part) {
+    const size_t gb = ngroups * (size_t)part / (size_t)nparts, ge = ngroups * (size_t)(part + 1) / (size_t)nparts;
+    for (size_t gi = gb; gi < ge; gi++) {
+      const int g0 = gstart[gi], g1 = gstart[gi + 1];
+      const int64_t w = orfs[g0].w;
+      const int n_seq = dna->h_len[(size_t)w];
+      for (int s = g0; s < g1; s++) {
+        FsOrfDev &o = orfs[s];
+        fsw_orf_window(o, wins, n_seq, p);
+        o.g0 = g0; o.g1 = g1;
+        wl[(size_t)s] = DnaWinDev{o.dw_n, o.dw_k, o.dw_len};
+      }
+      std::stable_sort(wl.begin() + g0, wl.begin() + g1, [](const DnaWinDev &a, const DnaWinDev &b) { return a.n < b.n; });
+      cnt[gi] = fsw_fuse(wl.data(), g0, g1, p.max_length);
+      for (int s = g0; s < g0 + cnt[gi]; s++)
+        fsw_summarize(orfs, g0, g1, wl[(size_t)s], n_seq, dna->h_off.data(), p, flogsum_host, &out_slot[(size_t)s], &desc_slot[(size_t)s]);
+    }
+  };
+  std::vector<std::thread> th;
+  for (int t = 1; t < nparts; t++) th.emplace_back(build, t);
+  build(0);
+  for (std::thread &t : th) t.join();
+
+  // ---- the windows in order, their pool offsets, the view's off[] / len[]
+  int nw = 0;
+  for (size_t gi = 0; gi < ngroups; gi++)
+    for (int s = gstart[gi]; s < gstart[gi] + cnt[gi]; s++, nw++) {
+      out[nw] = out_slot[(size_t)s]; desc[nw] = desc_slot[(size_t)s];
+      grp[2 * nw] = gstart[gi]; grp[2 * nw + 1] = gstart[gi + 1];
+      const int len = desc[nw].len;
+      desc[nw].dst_off = B->pool_bytes; voff[nw] = B->pool_bytes; vlen[nw] = len;
+      B->pool_bytes += fsw_pool_pitch(len); B->total += len; B->maxlen = std::max(B->maxlen, len);
+    }
+  B->n_orfs = n; B->nw = nw;
+  char *rs = b_res.as<char>();
+  for (const auto &[off, bytes] : {std::pair<size_t, size_t>{R.voff, (size_t)nw * 8}, {R.vlen, (size_t)nw * 4}, {R.desc, (size_t)nw * sizeof(FsWinDev)}})
+    BATH_HIP_TRY(ctx, hipMemcpyAsync(rs + off, h + off, bytes, hipMemcpyHostToDevice, ctx->stream));
+  res_bind(R, h, rs, B);
+  B->host_built = true;
+  return BATH_OK;
+}
+
+bool fs_orf_in_window(const FsOrfDev &o, const bath_fs_window &r, int n_seq) {
+  return fsw_orf_inside(o, r.strand, n_seq, fsw_span(r.strand, n_seq, r.n, r.length));
+}
+
+int fs_decide(bath_hip_ctx *ctx, const bath_hip_fsprofile *om_fs3, const bath_pipeline_params *prm, const FsWinBuild &B, const float *d_bias,
+              const float *d_fsc, const float *h_fsc, bath_fs_window *h_out) {
   if (B.nw == 0) return BATH_OK;
   const float *ev3 = om_fs3->evparam;
+  const double tau3 = (double)ev3[BATH_FTAUFS3], lambda = (double)ev3[BATH_FLAMBDA];
+  if (B.host_built) {
+    // the host build decides on the host: libm's exp() and log(), whose last bit the kernel's need not share
+    if (ctx->stage[7].reserve((size_t)B.nw * 6 * sizeof(float) + 64) != hipSuccess) { ctx->set_error("cannot allocate page-locked staging memory"); return BATH_EFAIL; }
+    const float *h_bias = static_cast<const float *>(ctx->stage[7].p);
+    BATH_HIP_TRY(ctx, hipMemcpyAsync(ctx->stage[7].p, d_bias, (size_t)B.nw * 6 * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    BATH_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    for (int i = 0; i < B.nw; i++) {
+      h_out[i] = B.h_out[i];
+      fsw_decide(h_out[i], &h_bias[(size_t)i * 6], h_fsc[i], flogsum_host, prm->do_biasfilter, prm->std_pipe, prm->F3, tau3, lambda);
+    }
+    return BATH_OK;
+  }
   hipLaunchKernelGGL(fsw_decide_kernel, dim3((unsigned)((B.nw + 255) / 256)), dim3(256), 0, ctx->stream, B.d_out, B.nw, d_bias, d_fsc, om_fs3->d_logsum,
-                     prm->do_biasfilter, prm->std_pipe, prm->F3, (double)ev3[BATH_FTAUFS3], (double)ev3[BATH_FLAMBDA]);
+                     prm->do_biasfilter, prm->std_pipe, prm->F3, tau3, lambda);
   BATH_HIP_TRY(ctx, hipGetLastError());
   if (ctx->stage[7].reserve((size_t)B.nw * sizeof(bath_fs_window) + 64) != hipSuccess) { ctx->set_error("cannot allocate page-locked staging memory"); return BATH_EFAIL; }
   BATH_HIP_TRY(ctx, hipMemcpyAsync(ctx->stage[7].p, B.d_out, (size_t)B.nw * sizeof(bath_fs_window), hipMemcpyDeviceToHost, ctx->stream));

@@ -76,7 +76,7 @@ struct FsWinDev {                  // one DNA window / envelope, device view
 };
 int fs_gather_view(bath_hip_ctx *ctx, const bath_hip_seqs *dna, std::vector<FsWinDev> &regs, const uint8_t *d_comp, bath_hip_seqs *view, const FsWinDev **d_desc_out);
 
-// ---- the DNA windows of the frameshift stage built on the device (bath_fs_windows.hip)
+// ---- the DNA windows of the frameshift stage (bath_fs_windows.hip): built by kernels, or on the host for the blocks they do not take
 struct WindowRec;                  // bath_kernels.hpp
 struct FsCandRec { int64_t window, aa_off; double P; int32_t cand, sf, startj, len; float fwdsc, nullsc; int64_t fxoff; };   // an ORF that passed F4, as a cascade lane leaves it
 struct FsLaneSurv {                // one cascade lane's F4 survivors and their hit windows, in the lane's device memory
@@ -93,23 +93,29 @@ struct FsOrfDev {                  // an ORF that passed F4, in the order esl_ge
   int32_t g0, g1;                  // its (sequence, strand) group, a range of the ordered ORF list
   int32_t pad_;
 };
-struct FsWinBuild {                // fs_build_windows_device's result: host copies (page-locked, valid until the next build) and device arrays
+struct FsWinBuild {                // what either build leaves: host copies (page-locked, valid until the next build) and device arrays
   int32_t n_orfs = 0, nw = 0, maxlen = 0;
   int64_t pool_bytes = 0, total = 0;
   const int64_t *h_voff = nullptr; const int32_t *h_vlen = nullptr;   // [nw] the windows' pool offsets and lengths: valid when the build returns
-  const FsOrfDev *h_orfs = nullptr;         // [n_orfs]  } in flight when the build returns: valid after the next synchronize of
-  const int32_t *h_grp = nullptr;           // [2 nw]    } the context's stream (fs_decide_device); a window's group = a range of h_orfs
-  bath_fs_window *d_out = nullptr;          // the records on the device (fs_decide_device completes them)
+  const FsOrfDev *h_orfs = nullptr;         // [n_orfs]  } the device build: in flight when it returns, valid after the next synchronize of
+  const int32_t *h_grp = nullptr;           // [2 nw]    } the context's stream (fs_decide); a window's group = a range of h_orfs
+  bool host_built = false;                  // the host build: the records wait on the host (h_out) for a decision taken there
+  const bath_fs_window *h_out = nullptr;
+  bath_fs_window *d_out = nullptr;          // the device build: the records on the device (fs_decide completes them)
   const FsWinDev *d_desc = nullptr;         // the gather kernel's descriptors
   const int64_t *d_voff = nullptr; const int32_t *d_vlen = nullptr;   // the view's off[] / len[]
 };
-bool fs_windows_on_device();       // false under BATH_HIP_FS_WINDOWS_HOST=1 (A/B: the host path of rounds 1-5)
-// BATH_OK; BATH_ENORESULT: an input this path does not take (the caller runs the host path); an error
+bool fs_windows_on_device();       // false under BATH_HIP_FS_WINDOWS_HOST=1: every block takes the host build
+// BATH_OK; BATH_ENORESULT: an input the kernels do not take (the caller runs the host build); an error
 int fs_build_windows_device(bath_hip_ctx *ctx, const bath_hip_oprofile *om, const bath_hip_fsprofile *om_fs3, const bath_hip_seqs *dna,
                             const bath_pipeline_params *prm, const FsLaneSurv *lanes, int nlanes, int nc_total, FsWinBuild *out);
-// after the parsers: scores -> P-values -> branch on the device, the completed records into h_out[nw]
-int fs_decide_device(bath_hip_ctx *ctx, const bath_hip_fsprofile *om_fs3, const bath_pipeline_params *prm, const FsWinBuild &B, const float *d_bias,
-                     const float *d_fsc, bath_fs_window *h_out);
+// the same from the survivor lists on the host: sel[n] by candidate id, wins[nhw] by (candidate id, start), ids the block's own
+int fs_build_windows_host(bath_hip_ctx *ctx, const bath_hip_oprofile *om, const bath_hip_seqs *dna, const bath_pipeline_params *prm,
+                          const FsCandRec *sel, int n, const WindowRec *wins, int nhw, FsWinBuild *out);
+bool fs_orf_in_window(const FsOrfDev &o, const bath_fs_window &r, int n_seq);   // the ORF lies inside the window of its strand (p7_pipeline.c:1405)
+// after the parsers: scores -> P-values -> branch, where the windows were built; the completed records into h_out[nw]
+int fs_decide(bath_hip_ctx *ctx, const bath_hip_fsprofile *om_fs3, const bath_pipeline_params *prm, const FsWinBuild &B, const float *d_bias,
+              const float *d_fsc, const float *h_fsc, bath_fs_window *h_out);
 float flogsum_host(float a, float b);                          // p7_FLogsum with its table, on the host
 
 // ---- frameshift helpers for the pipeline (bath_frameshift.hip)

@@ -1255,18 +1255,6 @@ __global__ void fs_select_wins_kernel(const WindowRec *__restrict__ wins, int nw
   }
 }
 
-struct FsOrf {                      // an ORF that passed F4, host side
-  int cand;
-  int64_t w = 0;                    // its sequence in the block
-  int strand = 0;
-  int64_t aa_off = 0;               // its residues in the amino-acid stream pool
-  int32_t start, end, n;            // nt coordinates on the strand being read, residues
-  double P;
-  float fwd_null;                   // fwdsc - nullsc (pli_tmp->fwdsc, p7_pipeline.c:1782)
-  int32_t wb = 0, we = 0;           // its hit windows, a range of the window list (ordered by start)
-};
-struct DnaWin { int64_t n; int32_t k, length; };
-
 // The ORFs that passed F4 and (frameshift pipeline) their hit windows, from every lane of the cascade: candidate ids are made
 // unique over the lanes, windows are the block's, and aa_off addresses the residues relative to <pool> (the first lane's pool;
 // another lane's pool is another allocation in the same flat address space, its ORFs carry the distance between the two).
@@ -1426,186 +1414,29 @@ extern "C" int bath_hip_pipeline_frameshift(bath_hip_ctx *ctx, const bath_hip_op
   const FilterState &S = sv.S0;
   const int nc = sv.nc_total;
   const int M = om->M;
-  const double kLn2 = 0.69314718055994529;
 
-  // ---- p7_pli_BuildDNAWindows + the per-window ORF summary of p7_pli_Frameshift: on the device (bath_fs_windows.hip), from the
-  // lists the cascade's lanes left there; the host path below is the A/B twin (BATH_HIP_FS_WINDOWS_HOST=1) and the fallback
-  std::vector<bath_fs_window> out;
-  std::vector<FsWinDev> dev;
-  std::vector<PipelineSurvivor> std_all;                                      // the ORFs the standard branch would take (:1479-1487) ...
-  std::vector<int32_t> std_begin;                                            // ... of window i: [std_begin[i], std_begin[i+1])
+  // ---- p7_pli_BuildDNAWindows + the per-window ORF summary of p7_pli_Frameshift (bath_fs_windows.hip): by kernels, from the lists the
+  // cascade's lanes left on the device; on the host, from the lists fetched after all, for the blocks the kernels hand back
   FsWinBuild B;
-  bool built = false;
-  if (try_device) {
-    st = fs_build_windows_device(ctx, om, om_fs3, dna, &prm, sv.lanes.data(), sv.n_states, nc, &B);
-    if (st == BATH_OK) {
-      built = true;
-      out.assign((size_t)B.nw, bath_fs_window{});                           // (the records arrive completed, after the branch decision)
-      clk.lap("fs:   DNA windows (device)");
-    } else if (st != BATH_ENORESULT) return st;
-    else if ((st = survivors_to_host(&sv)) != BATH_OK) return st;
-  }
-  if (!built) {
-  // ---- the ORFs that passed F4, grouped by (sequence, strand) in the order esl_gencode emits a strand's ORFs: when the closing
-  // stop codon is read; ORFs still open at the end of the sequence follow, frame by frame.  Each ORF's hit windows are a range
-  // of <h_wins> (sorted by candidate, then start).
-  const std::vector<WindowRec> &h_wins = sv.wins;
-  std::vector<FsOrf> orfs_all;
-  orfs_all.reserve(sv.sel.size());
-  {
-    size_t wi = 0;
-    for (const FsCandRec &q : sv.sel) {                                      // ascending candidate id, like h_wins
-      const int strand = q.sf / 3, frame = q.sf % 3;
-      FsOrf o;
-      o.cand = q.cand; o.w = q.window; o.strand = strand; o.aa_off = q.aa_off; o.n = q.len; o.start = frame + 3 * q.startj + 1; o.end = o.start + 3 * o.n - 1; o.P = q.P; o.fwd_null = q.fwdsc - q.nullsc;
-      while (wi < h_wins.size() && h_wins[wi].cand < q.cand) wi++;
-      o.wb = (int32_t)wi;
-      while (wi < h_wins.size() && h_wins[wi].cand == q.cand) wi++;
-      o.we = (int32_t)wi;
-      orfs_all.push_back(o);
-    }
-  }
-  std::stable_sort(orfs_all.begin(), orfs_all.end(), [dna](const FsOrf &a, const FsOrf &b) {
-    if (a.w != b.w) return a.w < b.w;
-    if (a.strand != b.strand) return a.strand < b.strand;
-    const int n_seq = dna->h_len[(size_t)a.w];
-    const bool ea = a.end + 3 > n_seq, eb = b.end + 3 > n_seq;
-    if (ea != eb) return !ea;
-    if (!ea) return a.end < b.end;
-    return (a.start - 1) % 3 < (b.start - 1) % 3;
-  });
-
-  // ---- p7_pli_BuildDNAWindows + the per-window ORF summary of p7_pli_Frameshift (host path)
-  // The groups (sequence, strand) are independent: host threads take contiguous runs of groups and their outputs are joined in
-  // order (the GPU waits for this step: 1.6 -> 1.2 ms for the bench block's 8 k ORFs, the sort of the ORFs included).
-  std::vector<size_t> gstart;                                                // first ORF of every group, and the end
-  for (size_t g0 = 0; g0 < orfs_all.size();) {
-    gstart.push_back(g0);
-    size_t g1 = g0;
-    while (g1 < orfs_all.size() && orfs_all[g1].w == orfs_all[g0].w && orfs_all[g1].strand == orfs_all[g0].strand) g1++;
-    g0 = g1;
-  }
-  gstart.push_back(orfs_all.size());
-  const size_t ngroups = gstart.size() - 1;
-  struct WinPart { std::vector<bath_fs_window> out; std::vector<FsWinDev> dev; std::vector<PipelineSurvivor> std_all; std::vector<int32_t> std_begin; };
-  static const int wthreads = [] { const char *e = std::getenv("BATH_HIP_WINDOW_THREADS"); return e ? std::max(1, std::atoi(e)) : 4; }();
-  const int nparts = (int)std::max<size_t>(1, std::min<size_t>((size_t)wthreads, ngroups / 256));
-  std::vector<WinPart> parts((size_t)nparts);
-  auto build = [&](int part) {
-    WinPart &P = parts[(size_t)part];
-    std::vector<bath_fs_window> &out = P.out;
-    std::vector<FsWinDev> &dev = P.dev;
-    std::vector<PipelineSurvivor> &std_all = P.std_all;
-    std::vector<int32_t> &std_begin = P.std_begin;
-    const size_t gb = ngroups * (size_t)part / (size_t)nparts, ge = ngroups * (size_t)(part + 1) / (size_t)nparts;
-    std::vector<DnaWin> wl;
-    for (size_t gi = gb; gi < ge; gi++) {
-    const size_t g0 = gstart[gi], g1 = gstart[gi + 1];
-    const int64_t w = orfs_all[g0].w;
-    const int strand = orfs_all[g0].strand;
-    const int n_seq = dna->h_len[(size_t)w];
-    const FsOrf *orfs = orfs_all.data() + g0, *orfs_end = orfs_all.data() + g1;
-    wl.clear();
-    for (const FsOrf *po = orfs; po != orfs_end; po++) {
-      const FsOrf &o = *po;
-      int best = -1;
-      float best_score = -INFINITY;
-      for (int i = o.wb; i < o.we; i++) {                                    // :486-495
-        const WindowRec &x = h_wins[(size_t)i];
-        if (x.score > best_score || (x.score == best_score && x.length > (best >= 0 ? h_wins[(size_t)best].length : 0))) { best_score = x.score; best = i; }
-      }
-      int32_t cn, ck, cl;
-      if (best >= 0) { cn = h_wins[(size_t)best].n; ck = h_wins[(size_t)best].k; cl = h_wins[(size_t)best].length; }
-      else if (o.n >= M) { cn = (o.n - M) / 2 + 1; ck = M; cl = M; }        // :500-510: no window, centre of the model
-      else { cn = 1; ck = M - ((M - o.n) / 2); cl = o.n; }
-      int64_t ws = (int64_t)((double)(uint32_t)cn - (om->max_length * (0.1 + om->prefix_lengths[(size_t)(ck - cl + 1)])) + 1);      // :513
-      int64_t we = (int64_t)((double)((uint32_t)cn + (uint32_t)cl) + (om->max_length * (0.1 + om->suffix_lengths[(size_t)ck])) - 2);   // :514
-      ws = std::min<int64_t>(0, ws);                                        // :516-517 (sic)
-      we = std::max<int64_t>(o.n, we);
-      ws = std::max<int64_t>(1, (int64_t)o.start + ws * 3);                 // :520-527, o.start already on the strand being read
-      we = std::min<int64_t>(n_seq, (int64_t)o.start + we * 3);
-      wl.push_back(DnaWin{ws, ck, (int32_t)(we - ws + 1)});
-    }
-    std::stable_sort(wl.begin(), wl.end(), [](const DnaWin &a, const DnaWin &b) { return a.n < b.n; });      // p7_hmmwindow_SortByStart
-    size_t keep = 0;
-    for (size_t i = 1; i < wl.size(); i++) {                                // :541-566, pct_overlap = 0
-      DnaWin &prev = wl[keep];
-      const DnaWin &cur = wl[i];
-      const int64_t pe = prev.n + prev.length - 1, ce = cur.n + cur.length - 1;
-      const int32_t ov = (int32_t)(std::min(pe, ce) - std::max(prev.n, cur.n) + 1);
-      const int64_t ms = std::min(prev.n, cur.n), me = std::max(pe, ce);
-      const int32_t ml = (int32_t)(me - ms + 1);
-      if (((float)ov / std::min(prev.length, cur.length) > 0.f) && ml < (2 * (om->max_length * 3))) { prev.n = ms; prev.length = ml; }
-      else wl[++keep] = wl[i];
-    }
-    wl.resize(wl.empty() ? 0 : keep + 1);
-
-    const int64_t dstart = strand ? n_seq : 1;                             // dnasq->start of a whole sequence
-    for (const DnaWin &dw : wl) {
-      bath_fs_window r{};
-      r.window = w; r.strand = strand; r.n = (int32_t)dw.n; r.length = dw.length;
-      const int64_t wstart = strand ? dstart - (dw.n + dw.length) : dstart + dw.n - 1;       // :1373-1374
-      const int64_t wend = strand ? dstart - dw.n + 1 : wstart + dw.length - 1;
-      int orf_cnt = 0, k_min = M, k_max = 0;
-      float tot = -INFINITY;
-      double P_min = INFINITY;
-      std_begin.push_back((int32_t)std_all.size());
-      for (const FsOrf *po = orfs; po != orfs_end; po++) {
-        const FsOrf &o = *po;
-        int64_t os, oe;
-        if (strand) { const int64_t rs = (int64_t)n_seq - o.start + 1, re = (int64_t)n_seq - o.end + 1; os = dstart - (n_seq - re + 1) + 1; oe = dstart - (n_seq - rs + 1) + 1; }
-        else { os = dstart + o.start - 1; oe = dstart + o.end - 1; }
-        if (!(os >= wstart && oe <= wend)) continue;                        // :1405
-        P_min = std::min(P_min, o.P);
-        tot = flogsum_host(tot, o.fwd_null);
-        orf_cnt++;
-        for (int i = o.wb; i < o.we; i++) { const WindowRec &x = h_wins[(size_t)i]; k_min = std::min(k_min, x.k - x.length + 1); k_max = std::max(k_max, x.k); }
-        if (!(o.P > prm.F3)) {                                              // :1483-1487
-          PipelineSurvivor ps;
-          ps.window = w; ps.aa_off = o.aa_off; ps.strand = strand; ps.start = o.start; ps.n = o.n; ps.win_start = (int32_t)dw.n; ps.fs_window = o.cand;
-          std_all.push_back(ps);                                            // fs_window carries the candidate id until the branch is known
-        }
-      }
-      r.orf_cnt = orf_cnt; r.k_min = k_min; r.k_max = k_max; r.tot_orfsc = tot; r.P_min = P_min;
-      r.P_tot = prm.std_pipe ? exp_surv((double)tot / kLn2, om->evparam[BATH_FTAU], om->evparam[BATH_FLAMBDA]) : 1.0;    // :1457: --fsonly
-      out.push_back(r);
-      FsWinDev d{};
-      d.src_off = dna->h_off[w]; d.dst_off = 0; d.seq_n = n_seq; d.start = (int32_t)dw.n; d.len = dw.length; d.strand = strand;
-      d.kmin = k_min; d.kmax = k_max;
-      dev.push_back(d);
-    }
-  }
-  };
-  if (nparts == 1) build(0);
+  st = try_device ? fs_build_windows_device(ctx, om, om_fs3, dna, &prm, sv.lanes.data(), sv.n_states, nc, &B) : (int)BATH_ENORESULT;
+  if (st == BATH_OK) clk.lap("fs:   DNA windows (device)");
+  else if (st != BATH_ENORESULT) return st;
   else {
-    std::vector<std::thread> th;
-    for (int t = 1; t < nparts; t++) th.emplace_back(build, t);
-    build(0);
-    for (std::thread &t : th) t.join();
+    if ((st = survivors_to_host(&sv)) != BATH_OK) return st;
+    if ((st = fs_build_windows_host(ctx, om, dna, &prm, sv.sel.data(), (int)sv.sel.size(), sv.wins.data(), (int)sv.wins.size(), &B)) != BATH_OK) return st;
+    clk.lap("fs:   DNA windows (host)");
   }
-  for (WinPart &P : parts) {
-    const int32_t shift = (int32_t)std_all.size();
-    out.insert(out.end(), P.out.begin(), P.out.end());
-    dev.insert(dev.end(), P.dev.begin(), P.dev.end());
-    for (int32_t b : P.std_begin) std_begin.push_back(b + shift);
-    std_all.insert(std_all.end(), P.std_all.begin(), P.std_all.end());
-  }
-  std_begin.push_back((int32_t)std_all.size());
-  clk.lap("fs:   DNA windows (host)");
-  }   // !built
-  const int nw = (int)out.size();
+  const int nw = B.nw;
+  std::vector<bath_fs_window> out((size_t)nw);                              // (the records arrive completed, after the branch decision)
   int64_t pos_fwd = 0;
   ctx->fs_std_orfs.clear();
   ctx->fs_std_pool = sv.pool;
-  std::vector<char> aligned((size_t)std::max(nc, 1), 0);                   // oxf_holder[i] == NULL: an overlapping window already took the ORF (:1485)
   if (nw > 0) {
-    // ---- windows -> device, bias filter and 3-codon frameshift Forward for all of them
+    // ---- the windows' copies, bias filter and 3-codon frameshift Forward for all of them
     DevBuf &b_out = ctx->scratch[31];
     bath_hip_seqs view;
     const FsWinDev *d_desc = nullptr;
-    if (built) st = fs_gather_view_built(ctx, dna, B, S.tt.comp, &view, &d_desc);      // descriptors, offsets and lengths are already on the device
-    else st = fs_gather_view(ctx, dna, dev, S.tt.comp, &view, &d_desc);
-    if (st != BATH_OK) return st;
+    if ((st = fs_gather_view_built(ctx, dna, B, S.tt.comp, &view, &d_desc)) != BATH_OK) return st;   // descriptors, offsets and lengths are on the device
     BATH_HIP_TRY(ctx, b_out.reserve((size_t)nw * 6 * sizeof(float) + 64));
     // the bias filter (a lane per window and pass, serial over the window) and the Forward parser are independent: the bias
     // kernel goes to the side stream, behind the gather
@@ -1613,7 +1444,6 @@ extern "C" int bath_hip_pipeline_frameshift(bath_hip_ctx *ctx, const bath_hip_op
     hipLaunchKernelGGL(fs_bias_kernel, dim3((unsigned)((2 * nw + 63) / 64)), dim3(64), 0, ctx->side_stream, view.d_data, d_desc, nw, S.tt.full, M, om->d_bias_eo,
                        S.d_ssvsc, (int)om->base_b, om->scale_b, S.d_bgf, b_out.as<float>());
     BATH_HIP_TRY(ctx, hipGetLastError());
-    std::vector<float> h_bias((size_t)nw * 6);
     std::vector<float> h_fsc((size_t)nw);
     ctx->fs_regions_all.clear();
     ctx->fs_keep_xoff.clear();
@@ -1634,78 +1464,28 @@ extern "C" int bath_hip_pipeline_frameshift(bath_hip_ctx *ctx, const bath_hip_op
     }
     view.d_data = nullptr; view.d_off = nullptr; view.d_len = nullptr;     // borrowed pointers: nothing for a destructor to free
     if (st != BATH_OK) return st;
-    if (built) {
-      // ---- scores -> P-values -> branch on the device (fsw_decide_kernel); the host reads the completed records once and keeps the
-      // bookkeeping: pos_past_fwd, and the ORFs of the windows that take the standard branch (:1479-1487), from the ordered ORF list
-      if ((st = fs_join(ctx)) != BATH_OK) return st;                          // the bias kernel's side stream
-      if ((st = fs_decide_device(ctx, om_fs3, &prm, B, b_out.as<float>(), ctx->scratch[12].as<float>(), out.data())) != BATH_OK) return st;
-      clk.lap("fs:   gather + bias + 3-codon Forward + branch decision (device)");
-      for (int i = 0; i < nw; i++) {
-        const bath_fs_window &r = out[(size_t)i];
-        if (r.branch == 1) { pos_fwd += r.length; continue; }
-        if (r.branch != 2) continue;
-        const int n_seq = dna->h_len[(size_t)r.window];
-        const int64_t dstart = r.strand ? n_seq : 1;
-        const int64_t wstart = r.strand ? dstart - ((int64_t)r.n + r.length) : dstart + r.n - 1;
-        const int64_t wend = r.strand ? dstart - r.n + 1 : wstart + r.length - 1;
-        for (int32_t z = B.h_grp[2 * i]; z < B.h_grp[2 * i + 1]; z++) {
-          const FsOrfDev &o = B.h_orfs[z];
-          int64_t os, oe;
-          if (r.strand) { const int64_t rs = (int64_t)n_seq - o.start + 1, re = (int64_t)n_seq - o.end + 1; os = dstart - (n_seq - re + 1) + 1; oe = dstart - (n_seq - rs + 1) + 1; }
-          else { os = dstart + o.start - 1; oe = dstart + o.end - 1; }
-          if (!(os >= wstart && oe <= wend) || o.P > prm.F3) continue;        // :1405, :1483
-          if (aligned[(size_t)o.cand]) continue;                               // oxf_holder[i] == NULL: an overlapping window already took the ORF (:1485)
-          aligned[(size_t)o.cand] = 1;
-          pos_fwd += (int64_t)o.n * 3;
-          PipelineSurvivor ps;
-          ps.window = r.window; ps.aa_off = o.aa_off; ps.strand = r.strand; ps.start = o.start; ps.n = o.n; ps.win_start = r.n; ps.fs_window = i;
-          ctx->fs_std_orfs.push_back(ps);
-        }
-      }
-    } else {
-    BATH_HIP_TRY(ctx, hipMemcpyAsync(h_bias.data(), b_out.p, h_bias.size() * sizeof(float), hipMemcpyDeviceToHost, ctx->side_stream));
-    BATH_HIP_TRY(ctx, hipStreamSynchronize(ctx->side_stream));
-    BATH_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    clk.lap("fs:   gather + bias + 3-codon Forward");
-
-    // ---- scores -> P-values -> which branch each window takes (:1425-1464)
-    const float *ev3 = fsprofile_evparam(om_fs3);
+    // ---- scores -> P-values -> branch (fsw_decide_kernel); the host reads the completed records once and keeps the bookkeeping:
+    // pos_past_fwd, and the ORFs of the windows that take the standard branch (:1479-1487), from the ordered ORF list
+    if ((st = fs_join(ctx)) != BATH_OK) return st;                            // the bias kernel's side stream
+    if ((st = fs_decide(ctx, om_fs3, &prm, B, b_out.as<float>(), ctx->scratch[12].as<float>(), h_fsc.data(), out.data())) != BATH_OK) return st;
+    clk.lap("fs:   gather + bias + 3-codon Forward + branch decision (device)");
+    std::vector<char> aligned((size_t)std::max(nc, 1), 0);                   // oxf_holder[i] == NULL: an overlapping window already took the ORF (:1485)
     for (int i = 0; i < nw; i++) {
-      bath_fs_window &r = out[(size_t)i];
-      const int L = r.length, L3 = L / 3;
-      const float p1 = (float)L3 / (float)(L3 + 1);
-      const float per_frame = (float)((float)L3 * std::log((double)p1) + std::log(1. - p1));           // p7_bg_fs_NullOne, p7_bg.c:380
-      r.nullsc = (float)(per_frame + std::log(3.0));
-      if (prm.do_biasfilter) {
-        float fsc[2];
-        for (int pass = 0; pass < 2; pass++) {
-          const float *b = &h_bias[((size_t)i * 2 + pass) * 3];
-          float sum = -INFINITY;
-          for (int f = 0; f < 3; f++) sum = flogsum_host(sum, b[f]);
-          fsc[pass] = (float)((double)sum + ((double)((float)L3 * logf(p1) + logf((float)(1. - p1))) + std::log(3.0)));   // p7_bg.c:561
-        }
-        r.filtersc = fsc[0];
-        if (r.k_min <= r.k_max && fsc[1] > r.filtersc) r.filtersc = fsc[1];                             // :1432-1440
-      } else r.filtersc = r.nullsc;
-      r.fwdsc = h_fsc[(size_t)i];
-      const float seqscore = (float)((r.fwdsc - r.filtersc) / kLn2);
-      r.P_fs = exp_surv(seqscore, ev3[BATH_FTAUFS3], ev3[BATH_FLAMBDA]);
-      r.P_null = exp_surv((r.fwdsc - r.nullsc) / kLn2, ev3[BATH_FTAUFS3], ev3[BATH_FLAMBDA]);
-      if (r.P_fs <= prm.F3 && (r.P_null < r.P_tot || (r.P_null == r.P_tot && r.orf_cnt > 1) || r.P_min > prm.F3)) { r.branch = 1; pos_fwd += L; }
-      else if (!prm.std_pipe) r.branch = 0;                                                             // :1480: --fsonly has no standard branch
-      else {
-        r.branch = 2;
-        for (int32_t z = std_begin[(size_t)i]; z < std_begin[(size_t)i + 1]; z++) {
-          PipelineSurvivor ps = std_all[(size_t)z];
-          if (aligned[(size_t)ps.fs_window]) continue;
-          aligned[(size_t)ps.fs_window] = 1;
-          pos_fwd += (int64_t)ps.n * 3;
-          ps.fs_window = i;
-          ctx->fs_std_orfs.push_back(ps);
-        }
+      const bath_fs_window &r = out[(size_t)i];
+      if (r.branch == 1) { pos_fwd += r.length; continue; }
+      if (r.branch != 2) continue;
+      const int n_seq = dna->h_len[(size_t)r.window];
+      for (int32_t z = B.h_grp[2 * i]; z < B.h_grp[2 * i + 1]; z++) {
+        const FsOrfDev &o = B.h_orfs[z];
+        if (!fs_orf_in_window(o, r, n_seq) || o.P > prm.F3) continue;         // :1405, :1483
+        if (aligned[(size_t)o.cand]) continue;
+        aligned[(size_t)o.cand] = 1;
+        pos_fwd += (int64_t)o.n * 3;
+        PipelineSurvivor ps;
+        ps.window = r.window; ps.aa_off = o.aa_off; ps.strand = r.strand; ps.start = o.start; ps.n = o.n; ps.win_start = r.n; ps.fs_window = i;
+        ctx->fs_std_orfs.push_back(ps);
       }
     }
-    }   // host decision
   }
   clk.lap("fs:   branch decision");
   st_local.pos_past_fwd = pos_fwd;                                         // in the fs pipeline only this stage counts it (:1468, :1490)

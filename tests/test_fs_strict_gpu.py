@@ -230,9 +230,9 @@ def _rerun(env_extra, select):
 
 
 def test_host_window_path_agrees_with_the_oracle_too():
-    """The DNA windows are built and the branch decided on the device by default (bath_fs_windows.hip); the host path of rounds 1-5
-    (p7_pli_BuildDNAWindows restated in C++, bath_pipeline.hip) stays as the fallback for blocks the device path does not take and as
-    the A/B twin: BATH_HIP_FS_WINDOWS_HOST=1 runs the strict pipeline tests and the window-level tests through it."""
+    """The DNA windows are built and the branch decided on the device by default (bath_fs_windows.hip); the host path
+    (fs_build_windows_host, bath_fs_windows.hip: the same rules from the survivor lists on the host) stays as the fallback for blocks the
+    device path does not take: BATH_HIP_FS_WINDOWS_HOST=1 runs the strict pipeline tests and the window-level tests through it."""
     _rerun({"BATH_HIP_FS_WINDOWS_HOST": "1"}, "strict_pipeline_is_exact or planted_frameshifted or cascade_lanes or recorded_fs")
 
 
