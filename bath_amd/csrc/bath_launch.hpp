@@ -61,6 +61,11 @@ int launch_len_sort(bath_hip_ctx *ctx, const int32_t *d_todo, const int *d_ntodo
 int launch_vit_lane(bath_hip_ctx *ctx, const bath_hip_oprofile *om, SeqView v, const int32_t *d_todo, int64_t ntodo, const int *ntodo_dev,
                     float *d_sc, int32_t *d_status, const VitWindowArgs *wa, const int *skip_dev = nullptr);
 const int *len_sort_count_longer(const int *d_bins, int T);     // device pointer: after launch_len_sort, the number of targets longer than T
+int64_t lane_min_nt();                                           // blocks of fewer nucleotides keep the wave-per-target kernels (BATH_HIP_LANE_MIN_NT)
+const char *vit_lane_kernel_name(const bath_hip_oprofile *om);   // "vit_lane_kernel<NR>" with the NR launch_vit_lane dispatches to
+// length sort, the long targets to launch_vit_wave on the side stream (then <beside>, if any, behind it), the rest to launch_vit_lane, join
+int launch_vit_sorted(bath_hip_ctx *ctx, const bath_hip_oprofile *om, SeqView v, const int32_t *d_todo, int64_t cap, const int *d_ntodo, const int32_t *d_len,
+                      int *d_bins, int32_t *d_sorted, float *d_sc, int32_t *d_status, const VitWindowArgs *wa, const std::function<int(hipStream_t)> &beside);
 struct MsvConsts;
 MsvConsts msv_consts(const bath_hip_oprofile *om);
 

@@ -31,7 +31,6 @@ using namespace bath;
 namespace bath {
 
 static const double kLog2 = 0.69314718055994529;
-constexpr int kVitLongOrf = 128;         // ORFs longer than this take the wave-per-ORF Viterbi kernel (see the pipeline)
 
 // ---------------------------------------------------------------------------------------------
 // candidate storage (structure of arrays, indexed by candidate id)
@@ -779,8 +778,7 @@ static int run_filters(bath_hip_ctx *ctx, const bath_hip_oprofile *om, const bat
     // their number) where the wave-per-ORF kernel takes 0.2 ms.  The candidate counts live on the device; the block's size is the
     // host's proxy.  tools/lane_crossover.py, M = 145, windows of 1 kb: Viterbi 0.72 (lane) / 0.19 (wave) ms at 12.5 k windows,
     // 0.71 / 0.63 at 100 k, 0.75 / 1.11 at 200 k; MSV 0.19 / 0.08, 0.22 / 0.10, 0.23 / 0.13, and 1.08 / 1.41 at 400 k.
-    static const int64_t lane_min_nt = [] { const char *e = std::getenv("BATH_HIP_LANE_MIN_NT"); return e ? std::atoll(e) : (int64_t)150'000'000; }();
-    const bool few_cands = dna->total < lane_min_nt, few_msv = dna->total < 2 * lane_min_nt;
+    const bool few_cands = dna->total < lane_min_nt(), few_msv = dna->total < 2 * lane_min_nt();
     // 3. SSV status; full MSV for the undecided
     hipLaunchKernelGGL(classify_kernel, dim3(dec_blocks), dim3(256), 0, ctx->stream, W.cand, W.cand_cap, W.ctr, om->lt.d_tjb, mc, W.todo_msv);
     BATH_HIP_TRY(ctx, hipGetLastError());
@@ -814,32 +812,10 @@ static int run_filters(bath_hip_ctx *ctx, const bath_hip_oprofile *om, const bat
       return BATH_OK;
     };
     bool ssvb_done = false;
-    if (vit_lane_supported(om) && !few_cands) {       // lane per ORF, ORFs bucketed by length (bath_viterbi.hip)
-      if ((st = launch_len_sort(ctx, W.todo_vit, &W.ctr->todo_vit, W.cand.len, W.len_bins, W.todo_sorted)) != BATH_OK) return st;
-      // The lane kernel runs one wave per SIMD and a wave takes as long as its longest ORF (3.6 us per residue): the few
-      // long ORFs at the head of the sorted list would set the duration of the whole stage.  They go to the
-      // wave-per-ORF kernel on a side stream instead, concurrently with the lane kernel on the rest.
-      if (!ctx->side_stream) {
-        BATH_HIP_TRY(ctx, hipStreamCreateWithFlags(&ctx->side_stream, hipStreamNonBlocking));
-        BATH_HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_fork, hipEventDisableTiming));
-        BATH_HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_join, hipEventDisableTiming));
-      }
-      static const int long_orf = [] { const char *e = std::getenv("BATH_HIP_VIT_LONG"); return e ? std::atoi(e) : kVitLongOrf; }();
-      const int *d_nlong = len_sort_count_longer(W.len_bins, long_orf);
-      BATH_HIP_TRY(ctx, hipEventRecord(ctx->ev_fork, ctx->stream));
-      BATH_HIP_TRY(ctx, hipStreamWaitEvent(ctx->side_stream, ctx->ev_fork, 0));
-      {
-        hipStream_t main_stream = ctx->stream;
-        ctx->stream = ctx->side_stream;
-        st = launch_vit_wave(ctx, om, cv, W.todo_sorted, cap, W.cand.vfsc, W.cand.vit_status, &wa, d_nlong);
-        ctx->stream = main_stream;
-        if (st != BATH_OK) return st;
-        if ((st = launch_ssvb(ctx->side_stream)) != BATH_OK) return st;      // ... and the SSV windows, all under the lane kernel
-        ssvb_done = true;
-      }
-      BATH_HIP_TRY(ctx, hipEventRecord(ctx->ev_join, ctx->side_stream));
-      if ((st = launch_vit_lane(ctx, om, cv, W.todo_sorted, cap, &W.ctr->todo_vit, W.cand.vfsc, W.cand.vit_status, &wa, d_nlong)) != BATH_OK) return st;
-      BATH_HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_join, 0));
+    if (vit_lane_supported(om) && !few_cands) {       // lane per ORF, ORFs bucketed by length, the long ones to the wave kernel (bath_viterbi.hip)
+      if ((st = launch_vit_sorted(ctx, om, cv, W.todo_vit, cap, &W.ctr->todo_vit, W.cand.len, W.len_bins, W.todo_sorted, W.cand.vfsc, W.cand.vit_status, &wa,
+                                  launch_ssvb)) != BATH_OK) return st;      // ... and the SSV windows, all under the lane kernel
+      ssvb_done = true;
     } else if ((st = launch_vit_wave(ctx, om, cv, W.todo_vit, cap, W.cand.vfsc, W.cand.vit_status, &wa, &W.ctr->todo_vit)) != BATH_OK) return st;
     BATH_HIP_TRY(ctx, hipEventRecord(ev[e++], ctx->stream));
     if (!ssvb_done && (st = launch_ssvb(ctx->stream)) != BATH_OK) return st;
@@ -1530,7 +1506,13 @@ extern "C" int bath_hip_vitfilter_bath(bath_hip_ctx *ctx, const bath_hip_oprofil
   bath_hip_oprofile_get_ssv_scores(om, ssv_scores.data());
   const int cap = (int)std::min<int64_t>((int64_t)1 << 26, sq->total / 2 + 16 * n + 1024);      // a window ends at least one residue after the last
   DevBuf &b = ctx->scratch[9];
-  const size_t o_sc = 0, o_st = o_sc + (size_t)n * 4, o_f = o_st + (size_t)n * 4, o_km = o_f + (size_t)n * 4, o_cnt = o_km + (size_t)n * 8, o_ssv = o_cnt + 256,
+  // The cascade's switch (run_filters): a batch as large as the ORFs of a block of lane_min_nt() nucleotides takes the lane-per-target
+  // kernel through launch_vit_sorted, on an identity work list whose count lives on the device like the cascade's; smaller ones the
+  // wave-per-target kernel.  Which one ran is left as the call's one kernel span (bath_hip_kernel_times).
+  const bool lane = vit_lane_supported(om) && 3 * sq->total >= lane_min_nt() && n < (int64_t)INT32_MAX;
+  const size_t n_list = lane ? (size_t)n : 0;
+  const size_t o_sc = 0, o_st = o_sc + (size_t)n * 4, o_f = o_st + (size_t)n * 4, o_km = o_f + (size_t)n * 4, o_todo = o_km + (size_t)n * 8, o_sorted = o_todo + n_list * 4,
+               o_bins = o_sorted + n_list * 4, o_cnt = (o_bins + (lane ? 2048 * sizeof(int) : 0) + 255) / 256 * 256, o_ssv = o_cnt + 256,
                o_w = (o_ssv + ssv_scores.size() + 255) / 256 * 256, total = o_w + (size_t)cap * sizeof(WindowRec);
   BATH_HIP_TRY(ctx, b.reserve(total + 256));
   char *p = b.as<char>();
@@ -1542,7 +1524,22 @@ extern "C" int bath_hip_vitfilter_bath(bath_hip_ctx *ctx, const bath_hip_oprofil
   wa.invP_msv = (double)(float)gumbel_invsurv(P, om->evparam[0], om->evparam[1]);          // vitfilter.c:319
   wa.d_filtersc = reinterpret_cast<const float *>(p + o_f); wa.d_ssv_scores = reinterpret_cast<const uint8_t *>(p + o_ssv);
   wa.d_wins = p + o_w; wa.d_win_count = reinterpret_cast<int *>(p + o_cnt); wa.win_cap = cap; wa.d_kminmax = reinterpret_cast<int32_t *>(p + o_km);
-  if ((st = launch_vit_wave(ctx, om, sq->view(), nullptr, n, reinterpret_cast<float *>(p + o_sc), reinterpret_cast<int32_t *>(p + o_st), &wa, nullptr)) != BATH_OK) return st;
+  float *d_sc = reinterpret_cast<float *>(p + o_sc);
+  int32_t *d_st = reinterpret_cast<int32_t *>(p + o_st);
+  std::vector<int32_t> todo(n_list);                  // (alive until windows_out has synchronized the stream)
+  const int n32 = (int)n;
+  ctx->spans_reset();
+  const int span = ctx->span_begin(lane ? vit_lane_kernel_name(om) : "vit_wave_kernel", ctx->stream, (double)sq->total * M, 0.0);
+  if (lane) {
+    for (int64_t i = 0; i < n; i++) todo[(size_t)i] = (int32_t)i;
+    int *d_ntodo = reinterpret_cast<int *>(p + o_cnt) + 16;            // behind the window count, in the same zeroed 256 bytes
+    BATH_HIP_TRY(ctx, hipMemcpyAsync(p + o_todo, todo.data(), (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
+    BATH_HIP_TRY(ctx, hipMemcpyAsync(d_ntodo, &n32, sizeof(int), hipMemcpyHostToDevice, ctx->stream));
+    st = launch_vit_sorted(ctx, om, sq->view(), reinterpret_cast<const int32_t *>(p + o_todo), n, d_ntodo, sq->d_len, reinterpret_cast<int *>(p + o_bins),
+                           reinterpret_cast<int32_t *>(p + o_sorted), d_sc, d_st, &wa, nullptr);
+  } else st = launch_vit_wave(ctx, om, sq->view(), nullptr, n, d_sc, d_st, &wa, nullptr);
+  if (st != BATH_OK) return st;
+  ctx->span_end(span, ctx->stream);
   BATH_HIP_TRY(ctx, hipMemcpyAsync(sc, p + o_sc, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
   if (status) BATH_HIP_TRY(ctx, hipMemcpyAsync(status, p + o_st, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
   return windows_out(ctx, reinterpret_cast<const WindowRec *>(p + o_w), wa.d_win_count, cap, wins, nwins);

@@ -19,6 +19,8 @@
 // The D row is evaluated exactly on every row; the reference's lazy-F test only skips D->D work that
 // cannot reach any M cell (vitfilter.c:183-196), so M rows, xE and the score are identical.
 #include <algorithm>
+#include <cstdlib>
+#include <functional>
 
 #include "bath_common.hpp"
 #include "bath_kernels.hpp"
@@ -220,6 +222,7 @@ __global__ __launch_bounds__(256, (NR <= 76 ? BATH_VIT_WAVES : 1)) void vit_lane
 // Global atomics on a few hot addresses serialise (~3 ns each on MI355X), so both passes count in LDS first and
 // touch each global bin once per block.
 constexpr int kLenBins = 2048;
+constexpr int kVitLongTarget = 128;      // targets longer than this take the wave-per-target Viterbi kernel (launch_vit_sorted)
 __device__ __forceinline__ void len_block_range(int n, int &lo, int &hi) {
   const int per = (n + (int)gridDim.x - 1) / (int)gridDim.x;
   lo = min(n, (int)blockIdx.x * per); hi = min(n, lo + per);
@@ -301,6 +304,53 @@ int launch_vit_lane(bath_hip_ctx *ctx, const bath_hip_oprofile *om, SeqView v, c
 #undef BATH_VITL_CASE
   if (!launched) { ctx->set_error("lane-per-target Viterbi kernel: unsupported model length"); return BATH_EINVAL; }
   BATH_HIP_TRY(ctx, hipGetLastError());
+  return BATH_OK;
+}
+
+// The lane-per-target kernels pay off when the targets fill the chip's lanes; a block's size in nucleotides is the host's proxy for
+// their number (see the cascade, bath_pipeline.hip).  BATH_HIP_LANE_MIN_NT is read once per process.
+int64_t lane_min_nt() {
+  static const int64_t v = [] { const char *e = std::getenv("BATH_HIP_LANE_MIN_NT"); return e ? std::atoll(e) : (int64_t)150'000'000; }();
+  return v;
+}
+
+const char *vit_lane_kernel_name(const bath_hip_oprofile *om) {
+#define BATH_VITL_NAME(N) if (om->vit_NR == N) return "vit_lane_kernel<" #N ">";
+  BATH_VITL_NAME(16) BATH_VITL_NAME(32) BATH_VITL_NAME(48) BATH_VITL_NAME(64) BATH_VITL_NAME(68) BATH_VITL_NAME(72) BATH_VITL_NAME(76) BATH_VITL_NAME(80)
+  BATH_VITL_NAME(96) BATH_VITL_NAME(112)
+#undef BATH_VITL_NAME
+  return "vit_lane_kernel<?>";
+}
+
+// The Viterbi stage with a lane per target: the work list sorted by length, longest first.  The lane kernel runs one wave per SIMD
+// and a wave takes as long as its longest target (3.6 us per residue): the few long targets at the head of the sorted list would set
+// the duration of the whole stage.  They go to the wave-per-target kernel on a side stream instead, concurrently with the lane
+// kernel on the rest.  <beside>, if given, is launched on the side stream behind the wave kernel: work on other targets that also
+// fits under the lane kernel.  <d_bins>: 2048 ints of scratch; <d_sorted>: as many entries as the list.
+int launch_vit_sorted(bath_hip_ctx *ctx, const bath_hip_oprofile *om, SeqView v, const int32_t *d_todo, int64_t cap, const int *d_ntodo, const int32_t *d_len,
+                      int *d_bins, int32_t *d_sorted, float *d_sc, int32_t *d_status, const VitWindowArgs *wa, const std::function<int(hipStream_t)> &beside) {
+  int st;
+  if ((st = launch_len_sort(ctx, d_todo, d_ntodo, d_len, d_bins, d_sorted)) != BATH_OK) return st;
+  if (!ctx->side_stream) {
+    BATH_HIP_TRY(ctx, hipStreamCreateWithFlags(&ctx->side_stream, hipStreamNonBlocking));
+    BATH_HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_fork, hipEventDisableTiming));
+    BATH_HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_join, hipEventDisableTiming));
+  }
+  static const int long_orf = [] { const char *e = std::getenv("BATH_HIP_VIT_LONG"); return e ? std::atoi(e) : kVitLongTarget; }();
+  const int *d_nlong = len_sort_count_longer(d_bins, long_orf);
+  BATH_HIP_TRY(ctx, hipEventRecord(ctx->ev_fork, ctx->stream));
+  BATH_HIP_TRY(ctx, hipStreamWaitEvent(ctx->side_stream, ctx->ev_fork, 0));
+  {
+    hipStream_t main_stream = ctx->stream;
+    ctx->stream = ctx->side_stream;
+    st = launch_vit_wave(ctx, om, v, d_sorted, cap, d_sc, d_status, wa, d_nlong);
+    ctx->stream = main_stream;
+    if (st != BATH_OK) return st;
+    if (beside && (st = beside(ctx->side_stream)) != BATH_OK) return st;
+  }
+  BATH_HIP_TRY(ctx, hipEventRecord(ctx->ev_join, ctx->side_stream));
+  if ((st = launch_vit_lane(ctx, om, v, d_sorted, cap, d_ntodo, d_sc, d_status, wa, d_nlong)) != BATH_OK) return st;
+  BATH_HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, ctx->ev_join, 0));
   return BATH_OK;
 }
 

@@ -261,7 +261,11 @@ int bath_hip_fwdback_parser(bath_hip_ctx *ctx, const bath_hip_oprofile *om, cons
  * (P7_HMM_WINDOW, hmmer.h:998: position n in the target, last model node k, length; score only from the SSV variant) that
  * p7_pli_BuildDNAWindows and the local-composition re-filter read.  filtersc[n]: the bias-filter score of every target;
  * P: the P-value threshold (pli->F2 / pli->F1).  *wins is owned by ctx (valid until the next call), ordered by target, then
- * by position.  As in the pipeline each target is scored with the profile configured for its own length. */
+ * by position.  As in the pipeline each target is scored with the profile configured for its own length.
+ * bath_hip_vitfilter_bath takes the cascade's own path: a batch of at least BATH_HIP_LANE_MIN_NT / 3 residues (default 150 M nt) of a
+ * model of up to 224 nodes is sorted by length and scored by the lane-per-target kernel, its targets beyond 128 residues by the
+ * wave-per-target kernel beside it; smaller batches by the wave-per-target kernel.  bath_hip_kernel_times then holds one span,
+ * named after the kernel that ran: "vit_lane_kernel<NR>" or "vit_wave_kernel". */
 typedef struct {
   int64_t target;                  /* index of the sequence in the block */
   int32_t n, k, length;

@@ -111,6 +111,198 @@ def test_msv_lane_every_register_tiling(gpu_ctx, tmp_path, M):
     assert (sst != 0).sum() >= 5                             # targets SSV could not decide: they went through the lane kernel
 
 
+VIT_LANE_NR = [16, 32, 48, 64, 68, 72, 76, 80, 96, 112]
+# per instantiation the smallest and the largest model that selects it; 16 | 17: the high half of every register is padding | holds
+# one node (M <= NR | M = NR + 1); 31: an odd M, the last slot padded; 32, 64, ...: M = 2 NR, no padding; 225: the wave kernel
+VIT_LANE_M = [1, 16, 17, 31, 32, 33, 64, 65, 96, 97, 128, 129, 136, 137, 144, 145, 152, 153, 160, 161, 192, 193, 224, 225]
+ESL_ERANGE = 16
+
+
+def vit_lane_nr(M):
+    """Node pairs per lane of vit_lane_kernel<NR> for a model of M nodes, None beyond its range (bath_profile.hip: NRv)."""
+    nr = ((M + 1) // 2 + 15) // 16 * 16
+    if nr == 80:
+        nr = max(68, ((M + 1) // 2 + 3) // 4 * 4)
+    return nr if nr <= 112 else None
+
+
+def vit_lane_targets(model, M):
+    """The targets of the lane-per-target Viterbi sweeps, seeded by M: every length from 1 to 9 and either side of multiples of 4
+    (the kernel reads residues four to a word and pads the last word with code 29) and of 128 (the cascade's long-ORF split),
+    background with degenerate residues, homologs plain and sharpened, several sharpened domains in a row (overflow, the J state),
+    and targets of '*' residues (the lowest scores a target can get).  325 targets: the second block of 256 lanes has one full wave,
+    one partly live wave (5 lanes) and two idle ones."""
+    rng = np.random.default_rng(2000 + M)
+    seqs = []
+    for L in list(range(1, 10)) + [11, 12, 13, 15, 16, 17, 63, 64, 65, 127, 128, 129, 130]:
+        seqs += common.random_aa(rng, 2, L, L)
+    seqs += common.random_aa(rng, 99, 20, 300)
+    seqs += common.emit_from_model(rng, model, 100) + common.emit_from_model(rng, model, 50, sharpen=3.0)
+    seqs += [np.concatenate(common.emit_from_model(rng, model, int(rng.integers(2, 6)), sharpen=3.0)) for _ in range(24)]
+    seqs += common.random_aa(rng, 6, 400, 900)
+    seqs += [np.full(1, 27, np.uint8), np.full(5, 27, np.uint8)]
+    assert len(seqs) == 325
+    return seqs
+
+
+@pytest.mark.parametrize("M", VIT_LANE_M, ids=["NR%s-M%d" % (vit_lane_nr(m) or "wave", m) for m in VIT_LANE_M])
+def test_vit_lane_every_register_tiling(gpu_ctx, tmp_path, M):
+    """vit_lane_kernel<NR> (bath_viterbi.hip: a lane per target, node pairs r+1 | NR+r+1 packed per register, models up to 224 nodes)
+    at every instantiation, at the smallest and the largest model each serves, and the first model beyond them (225: vit_wave_kernel):
+    score and status of every target bit-exact against the oracle.  The conditions on the target set are the oracle's results
+    alone.  The oracle scores no target -inf at any M of the list, '*' residues included (they score about -50 nats): the
+    special states start at base 12000 of the 16-bit range, and neither B->M of a model this short nor any emission the profile holds
+    takes xE down to -32768.  The count is printed; the branch stays compiled in and unreached here, as it is in the oracle."""
+    path = common.write_synthetic_bhmm(str(tmp_path / ("s%d.bhmm" % M)), M, seed=M)
+    model = ol.Model(path, 0)
+    om = ba.OProfile(gpu_ctx, ba.Profile(ba.HMM(path, 0)))
+    seqs = vit_lane_targets(model, M)
+    osc, ost = common.oracle_scores(model, seqs, "bo_vitfilter")
+    n_erange, n_ok, n_neginf = int((ost == ESL_ERANGE).sum()), int((ost == 0).sum()), int(np.isneginf(osc).sum())
+    print("M=%d NR=%s targets=%d ERANGE=%d OK=%d -inf=%d" % (M, vit_lane_nr(M), len(seqs), n_erange, n_ok, n_neginf))
+    assert len(seqs) % 64 != 0 and 0 < len(seqs) % 256 <= 192          # a partly live wave and an idle one in the last block
+    if M >= 65:
+        assert n_erange >= 5 and n_ok >= 100
+    sc, st = ba.ViterbiFilter(gpu_ctx, om, ba.SeqBlock(gpu_ctx, seqs))
+    assert np.array_equal(st, ost)
+    assert _same_scores(sc, osc)
+    for t in (0, len(seqs) // 2):                                       # one target per call: one live lane in the grid
+        sc1, st1 = ba.ViterbiFilter(gpu_ctx, om, ba.SeqBlock(gpu_ctx, seqs[t:t + 1]))
+        assert st1[0] == ost[t] and _same_scores(sc1, osc[t:t + 1])
+
+
+VIT_WINDOWS_P = 1e-3
+VIT_LONG_TARGET = 128          # bath_viterbi.hip, kVitLongTarget: longer targets of a sorted list go to the wave-per-target kernel
+
+
+def vit_window_targets(model, M):
+    """Targets for the window sweeps, seeded by M: homologs plain and sharpened, homologs cut off inside the domain (a window that
+    runs into the target's end), several domains in a row (several windows per target: skip_until; the long side of the split),
+    background, and the short lengths of vit_lane_targets."""
+    rng = np.random.default_rng(3000 + M)
+    seqs = []
+    for L in list(range(1, 10)) + [11, 12, 13, 127, 128, 129]:
+        seqs += common.random_aa(rng, 1, L, L)
+    seqs += common.random_aa(rng, 40, 20, 300)
+    seqs += common.emit_from_model(rng, model, 40, flank=12) + common.emit_from_model(rng, model, 40, flank=12, sharpen=2.0)
+    cut = common.emit_from_model(rng, model, 20, flank=6, sharpen=2.0)
+    seqs += [s[:max(1, len(s) - int(rng.integers(1, max(2, len(s) // 2))))] for s in cut]
+    seqs += [np.concatenate([d if rng.random() < 0.5 else np.concatenate([d, common.random_aa(rng, 1, 10, 40)[0]])
+                             for d in common.emit_from_model(rng, model, int(rng.integers(2, 5)), flank=8, sharpen=1.5)]) for _ in range(20)]
+    seqs += common.random_aa(rng, 4, 300, 600)
+    # the model's last nodes, most probable residue each, behind a random flank: a window whose extension runs to node M
+    h = model.hmm.contents
+    mat = np.ctypeslib.as_array(h.mat, shape=((M + 1) * 20,)).reshape(M + 1, 20)
+    for _ in range(6):
+        a = int(rng.integers(max(1, M - 60), max(2, M - 8)))
+        seqs.append(np.concatenate([common.random_aa(rng, 1, 5, 30, with_degenerate=False)[0], mat[a:M + 1].argmax(axis=1).astype(np.uint8)]))
+    return seqs
+
+
+def oracle_vit_windows(model, seqs, filtersc, P):
+    """bo_vitfilter_bath per target: (scores, statuses, [(target, n, k, length, score)])."""
+    import ctypes as C
+    L_ = ol.lib()
+    sc, st, wins = np.zeros(len(seqs), np.float32), np.zeros(len(seqs), np.int32), []
+    out = C.c_float()
+    for t, s_ in enumerate(seqs):
+        L_.bo_oprofile_reconfig_length(model.om, len(s_))
+        owl = ol.WindowList(); L_.bo_windowlist_init(C.byref(owl))
+        st[t] = L_.bo_vitfilter_bath(ol.u8(ol.dsq_from(s_)), len(s_), model.om, model.sd, C.c_float(filtersc[t]), C.c_double(P), C.byref(owl), C.byref(out))
+        sc[t] = out.value
+        wins += [(t, owl.w[i].n, owl.w[i].k, owl.w[i].length, owl.w[i].score) for i in range(owl.count)]
+        L_.bo_windowlist_free(C.byref(owl))
+    return sc, st, wins
+
+
+def gpu_vit_windows(ctx, om, seqs, filtersc, P):
+    """bath_hip_vitfilter_bath: (scores, statuses, [(target, n, k, length, score)], name of the Viterbi kernel that ran)."""
+    import ctypes as C
+    blk = ba.SeqBlock(ctx, seqs)                     # (held: the block must outlive the call)
+    sc, st = np.zeros(len(seqs), np.float32), np.zeros(len(seqs), np.int32)
+    fsc = np.ascontiguousarray(filtersc, np.float32)
+    w, nw = C.POINTER(ba.HmmWindow)(), C.c_int64(0)
+    f32p, i32p = C.POINTER(C.c_float), C.POINTER(C.c_int32)
+    ctx._check(ba.lib().bath_hip_vitfilter_bath(ctx._h, om._h, blk._h, fsc.ctypes.data_as(f32p), C.c_double(P), sc.ctypes.data_as(f32p), st.ctypes.data_as(i32p),
+                                                C.byref(w), C.byref(nw)), "vitfilter_bath")
+    wins = [(int(w[i].target), w[i].n, w[i].k, w[i].length, w[i].score) for i in range(nw.value)]
+    arr = (ba.KernelTime * 32)()
+    names = [arr[i].name.decode() for i in range(ba.lib().bath_hip_kernel_times(ctx._h, 32, arr))]
+    vit = [n for n in names if n.startswith("vit_")]        # (the call also lists what the domain stage's own contexts last ran)
+    assert len(vit) == 1, names
+    return sc, st, wins, vit[0]
+
+
+@pytest.fixture(scope="module")
+def lane_forced_windows(tmp_path_factory):
+    """The window sweep again in a fresh process with BATH_HIP_LANE_MIN_NT=0 (read once per process): bath_hip_vitfilter_bath then takes
+    the lane-per-target kernel with the length sort and the long-target split, as the cascade does on blocks of 150 M nt.  The
+    child asserts the oracle comparison and the kernel's name itself and leaves its arrays per M in the directory returned."""
+    import os, subprocess, sys
+    if os.environ.get("BATH_TEST_VIT_WINDOWS_DUMP"):
+        return None                                  # this is the child
+    out = str(tmp_path_factory.mktemp("vit_lane_windows"))
+    env = dict(os.environ, BATH_HIP_LANE_MIN_NT="0", BATH_TEST_VIT_WINDOWS_DUMP=out)
+    p = subprocess.run([sys.executable, "-m", "pytest", os.path.abspath(__file__), "-q", "-x", "-s", "-m", "gpu", "-p", "no:cacheprovider",
+                        "-k", "test_vit_lane_windows_every_register_tiling"],
+                       env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=1500,
+                       cwd=os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+    print(p.stdout[-6000:])
+    assert p.returncode == 0 and "%d passed" % len(VIT_LANE_WINDOWS_M) in p.stdout and "failed" not in p.stdout, p.stdout[-3000:]
+    return out
+
+
+VIT_LANE_WINDOWS_M = [m for m in VIT_LANE_M if vit_lane_nr(m) is not None]
+
+
+@pytest.mark.parametrize("M", VIT_LANE_WINDOWS_M, ids=["NR%d-M%d" % (vit_lane_nr(m), m) for m in VIT_LANE_WINDOWS_M])
+def test_vit_lane_windows_every_register_tiling(gpu_ctx, tmp_path, lane_forced_windows, M):
+    """p7_ViterbiFilter_BATH's hit windows (vitfilter.c:386-424) from vit_lane_kernel<NR> at every instantiation: the visiting-rank
+    table, k_start, the diagonal extension, skip_until.  bath_hip_vitfilter_bath runs the cascade's own Viterbi step
+    (launch_vit_sorted: length sort, targets beyond 128 residues to the wave kernel on the side stream, the rest to the lane kernel)
+    when the batch is large enough or BATH_HIP_LANE_MIN_NT=0.  This test runs twice: here, where the small batch takes
+    vit_wave_kernel, and in a child process with the variable set, where it must take vit_lane_kernel<NR> with the NR the rule of
+    bath_profile.hip gives (the kernel's name is read back: a forced run that took the wave kernel fails).  Both runs hold status,
+    score bits and every target's windows (n, k, length exactly; the score is 0.0 on both sides: only p7_SSVFilter_BATH scores its
+    windows, hmmer.h:998) against the oracle, and the two runs' arrays must be identical.
+    The oracle's records tell how an extension ended: k == M means it ran to the model's last node (kk == M), n + length - 1 == L
+    that it ran to the target's last residue (nn == L); both are required of the set from M = 33 on."""
+    import os
+    dump = os.environ.get("BATH_TEST_VIT_WINDOWS_DUMP")
+    forced = os.environ.get("BATH_HIP_LANE_MIN_NT") == "0"
+    assert bool(dump) == forced
+    path = common.write_synthetic_bhmm(str(tmp_path / ("s%d.bhmm" % M)), M, seed=M)
+    model = ol.Model(path, 0)
+    om = ba.OProfile(gpu_ctx, ba.Profile(ba.HMM(path, 0)))
+    seqs = vit_window_targets(model, M)
+    _, filtersc = common.oracle_bias(model, seqs)
+    osc, ost, owins = oracle_vit_windows(model, seqs, filtersc, VIT_WINDOWS_P)
+    # the input set, judged on the oracle's results alone
+    per_target = np.bincount([w[0] for w in owins], minlength=len(seqs))
+    lens = np.array([len(s) for s in seqs])
+    to_model_end = sum(1 for w in owins if w[2] == M)
+    to_target_end = sum(1 for w in owins if w[1] + w[3] - 1 == lens[w[0]])
+    print("M=%d NR=%d targets=%d long=%d ERANGE=%d windows=%d multi-window targets=%d to-model-end=%d to-target-end=%d" %
+          (M, vit_lane_nr(M), len(seqs), (lens > VIT_LONG_TARGET).sum(), (ost == ESL_ERANGE).sum(), len(owins), (per_target >= 2).sum(), to_model_end, to_target_end))
+    assert (lens > VIT_LONG_TARGET).sum() >= 5 and (lens <= VIT_LONG_TARGET).sum() >= 50
+    if M >= 33:
+        assert len(owins) >= 20 and (per_target >= 2).sum() >= 3
+        assert to_model_end >= 1 and to_target_end >= 1
+    sc, st, wins, kernel = gpu_vit_windows(gpu_ctx, om, seqs, filtersc, VIT_WINDOWS_P)
+    print("M=%d kernel=%s" % (M, kernel))
+    assert kernel == ("vit_lane_kernel<%d>" % vit_lane_nr(M) if forced else "vit_wave_kernel")
+    assert np.array_equal(st, ost)
+    assert _same_scores(sc, osc)
+    assert [w[:4] for w in wins] == [w[:4] for w in owins]
+    assert all(a[4] == b[4] == 0.0 for a, b in zip(wins, owins))
+    flat = np.array(wins, np.float64).reshape(-1, 5)
+    if dump:
+        np.savez(os.path.join(dump, "M%d.npz" % M), sc=sc, st=st, wins=flat)
+    else:
+        lane = np.load(os.path.join(lane_forced_windows, "M%d.npz" % M))
+        assert np.array_equal(lane["st"], st) and _same_scores(lane["sc"], sc) and np.array_equal(lane["wins"], flat)
+
+
 def test_msv_bit_exact(setup):
     ctx, model, om, seqs, sq = setup
     sc, st = ba.MSVFilter(ctx, om, sq)

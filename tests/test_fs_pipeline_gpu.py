@@ -125,6 +125,17 @@ def test_planted_frameshifted_genes(gpu_ctx, name):
     assert any(w.strand == 1 for w in fw) and any(w.orf_cnt > 1 for w in fw)
 
 
+def test_planted_frameshifted_genes_model_of_200_nodes(gpu_ctx, tmp_path):
+    """The same for a synthetic model of 200 nodes: with the lane-per-ORF kernels forced (test_pipeline_gpu.py: test_dna_windows_with_lane_kernels_forced) the Viterbi windows that
+    p7_pli_BuildDNAWindows reads come from vit_lane_kernel<112>, which no golden model selects."""
+    path = common.write_synthetic_bhmm(str(tmp_path / "s200.bhmm"), 200, seed=200)
+    rng = np.random.default_rng(31)
+    wins = frameshifted_windows(rng, ol.Model(path, 0))
+    model, stats, res, fw, pli, ores, per_seq, ofw, per_seq_w = run_both(gpu_ctx, path, 0, wins)
+    assert len(ofw) >= 20 and pli.n_past_vit >= 20 and any(o.orf_cnt > 1 for o in ofw)      # the oracle's own counts
+    assert compare(model, stats, fw, pli, ofw, per_seq_w) == len(ofw)
+
+
 def compare_domains(model, gdm, odm, per_d, nclustered=0):
     """Domain by domain.  Three grades of agreement, because three kinds of arithmetic feed the envelopes:
 

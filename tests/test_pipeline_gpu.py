@@ -86,6 +86,21 @@ def test_cascade_with_lane_kernels_forced(monkeypatch):
     assert p.returncode == 0 and " passed" in p.stdout and "failed" not in p.stdout, p.stdout[-3000:]
 
 
+def test_dna_windows_with_lane_kernels_forced():
+    """The same for the --fs pipeline's DNA windows.  Their records (window, strand, n, length, orf_cnt, k_min, k_max) are built from
+    the Viterbi filter's hit windows, and the blocks of test_fs_pipeline_gpu.py take the wave-per-ORF kernel, so the lane-per-ORF
+    kernel's windows, which production-sized --fs blocks use, are never held against the oracle's there.  With BATH_HIP_LANE_MIN_NT=0
+    the length sort, the long-ORF split and vit_lane_kernel run on those blocks: the record comparisons again in a fresh process, for
+    Caudal_act and for a synthetic model of 200 nodes (vit_lane_kernel<112>, which no golden model selects), in both frameshift modes."""
+    import os, subprocess, sys
+    env = dict(os.environ, BATH_HIP_LANE_MIN_NT="0")
+    here = os.path.dirname(os.path.abspath(__file__))
+    p = subprocess.run([sys.executable, "-m", "pytest", os.path.join(here, "test_fs_pipeline_gpu.py"), "-q", "-x", "-m", "gpu", "-p", "no:cacheprovider",
+                        "-k", "(test_planted_frameshifted_genes and Caudal_act) or test_planted_frameshifted_genes_model_of_200_nodes"],
+                       env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=1500, cwd=os.path.dirname(here))
+    assert p.returncode == 0 and "4 passed" in p.stdout and "failed" not in p.stdout, p.stdout[-3000:]
+
+
 GOLDEN_RUNS = [  # (model file, index, target fasta, counters printed by the reference: p7_pli_Statistics)
     ("PTH2.bhmm", 0, "target-PTH2.fa", (6000, 1503, 1503, 1401, 1287)),
     ("AMP_N.bhmm", 0, "target-AMP_N.fa", (822, 537, 537, 393, 237)),

@@ -89,6 +89,44 @@ def test_standard_filter_tests_reach_every_tiling():
     assert reached == set(opts), "wave-filter tilings without a test: %s" % sorted(set(opts) - reached)
 
 
+def test_vit_lane_tests_reach_every_instantiation():
+    """vit_lane_kernel<NR> (BATH_VITL_CASE) and msv_lane_kernel<NR> (BATH_MSV_CASE): every instantiation has a test model, the Viterbi
+    ones at the smallest and the largest model that selects them, and the first model beyond the kernel's range is there too."""
+    import test_filters_gpu as t
+    vit = src("bath_viterbi.hip")
+    nrs = [int(x) for x in re.findall(r"BATH_VITL_CASE\((\d+)\)", vit)]
+    assert nrs and nrs == sorted(set(nrs)) and t.VIT_LANE_NR == nrs
+    assert [int(x) for x in re.findall(r"BATH_VITL_NAME\((\d+)\)", vit)] == nrs            # the names the window sweep reads back
+    # the rule that picks NR for a model (bath_profile.hip), restated by t.vit_lane_nr: tied to the source's text here, and on the GPU
+    # by the window sweep, which holds the name of the kernel that ran against it
+    prof = src("bath_profile.hip")
+    assert "int NRv = ((M + 1) / 2 + 15) / 16 * 16;" in prof
+    assert "if (NRv == 80) NRv = std::max(68, ((M + 1) / 2 + 3) / 4 * 4);" in prof
+    assert "if (NRv <= 112) {" in prof and max(nrs) == 112
+    limit = 2 * max(nrs)
+    by_nr = {}
+    for m in range(1, limit + 1):
+        by_nr.setdefault(t.vit_lane_nr(m), []).append(m)
+    assert sorted(by_nr) == nrs, "the rule selects an NR that is not instantiated, or never selects one that is"
+    missing = [(nr, m) for nr, ms in by_nr.items() for m in (ms[0], ms[-1]) if m not in t.VIT_LANE_M]
+    assert not missing, "vit_lane_kernel instantiations without a test at this model length: %s" % missing
+    assert t.vit_lane_nr(limit + 1) is None and limit + 1 in t.VIT_LANE_M
+    assert t.VIT_LANE_WINDOWS_M == [m for m in t.VIT_LANE_M if m <= limit]
+    # M <= NR (an empty high half), M = NR + 1 (one node in the high chain), an odd M (a padded last slot)
+    assert any(m <= t.vit_lane_nr(m) for m in t.VIT_LANE_WINDOWS_M) and any(m == t.vit_lane_nr(m) + 1 for m in t.VIT_LANE_WINDOWS_M)
+    assert any(m % 2 and m < 2 * t.vit_lane_nr(m) for m in t.VIT_LANE_WINDOWS_M)
+    # msv_lane_kernel: NR is the SSV tile's -- ceil(M / 2) pairs in steps of 4, one lane per target, at most 76 pairs (152 nodes)
+    import oracle_lib as ol
+    msv = [int(x) for x in re.findall(r"BATH_MSV_CASE\((\d+)\)", src("bath_msv_lane.hip"))]
+    assert msv and msv == sorted(set(msv)) and msv[-1] == 76
+    assert "int NR = ((M + G - 1) / G + 1) / 2;" in prof and "if (G == 1 && NR <= 112) NR = (NR + 3) / 4 * 4;" in prof and "NR = std::max(NR, 16);" in prof
+    assert "om->G != 1 || om->NR > 76" in src("bath_msv_lane.hip")
+    ms = set(int(x) for x in re.search(r'parametrize\("M", \[([0-9, ]+)\]\)\ndef test_msv_lane_every_register_tiling', open(t.__file__).read()).group(1).split(","))
+    ms |= {int(n.split(":")[1]) if n.startswith("synthetic:") else ba.HMM(ol.GOLDEN + "/" + n, i).M for n, i in t.MODELS}     # test_msv_bit_exact
+    reached = {max(16, ((m + 1) // 2 + 3) // 4 * 4) for m in ms if m <= 152}
+    assert reached == set(msv), "msv_lane_kernel instantiations without a test: %s" % sorted(set(msv) - reached)
+
+
 def test_cascade_and_ssv_window_tests_reach_every_tiling():
     import test_filters_gpu as tf
     import test_pipeline_gpu as tp
