@@ -5,6 +5,7 @@
 
 #include <cstdint>
 
+#include "bath_common.hpp"
 #include "bath_hip.h"
 
 namespace bath {
@@ -187,6 +188,73 @@ __device__ __forceinline__ int ssv_classify(int v, int tjb, const MsvConsts &c, 
   r = (float)((double)r - 3.0);
   *sc = r;
   return BATH_OK;
+}
+
+// ---- MSV with the J state, a lane per target (bath_msv_lane.hip): the row loop, shared by msv_lane_kernel and msv_stage_kernel ----
+__device__ __forceinline__ s16x2 msv_pkmax(s16x2 a, s16x2 b) {
+  s16x2 r;
+  asm("v_pk_max_f16 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
+  return r;
+}
+// The target's <L> rows over the MSV increment table in LDS (<lds>, rows of <row_bytes>), <Lw> rows in all: the wave's longest
+// target (wave-uniform; a lane with L = 0 only keeps the wave company).  Returns xJ after the last row; <overflow>: msvfilter.c:172.
+template <int NR>
+__device__ __forceinline__ int msv_lane_rows(const char *lds, int row_bytes, const uint8_t *s, int L, int Lw, int tjbm, const MsvConsts &c, bool *overflow) {
+  typedef _Float16 h16x2 __attribute__((ext_vector_type(2)));
+  s16x2 reg[NR];
+  const s16x2 zero = {0, 0};
+#pragma unroll
+  for (int r = 0; r < NR; r++) reg[r] = zero;
+  int xJ = 0, xB = satu8(c.base - tjbm);
+  bool over = false;
+  uint2 res = make_uint2(0u, 0u);
+  for (int i = 0; i < Lw; i++) {
+    // residues eight at a time while at least eight remain (the candidates' residues sit in the amino-acid streams: any alignment)
+    if ((i & 7) == 0) {
+      if (i + 8 <= L) __builtin_memcpy(&res, s + i, 8);
+      else {
+        res = make_uint2(0u, 0u);
+        for (int j = 0; j < 8 && i + j < L; j++) {
+          const unsigned b = s[i + j];
+          if (j < 4) res.x |= b << (8 * j); else res.y |= b << (8 * (j - 4));
+        }
+      }
+    }
+    const unsigned byte = (((i & 4) ? res.y : res.x) >> (8 * (i & 3))) & 0xffu;
+    const int x = (i < L) ? min((int)byte, kKp - 1) : kRowReset;       // past the target's end: the reset row (every cell back to 0, xE = 0: xJ and B keep their values)
+    const ssv_i4 *row = reinterpret_cast<const ssv_i4 *>(lds + (size_t)x * row_bytes);
+    const h16x2 bh = {(_Float16)((float)xB * (1.0f / 2048.0f)), (_Float16)((float)xB * (1.0f / 2048.0f))};
+    const s16x2 xBv = __builtin_bit_cast(s16x2, bh);
+    // register 0: its low half takes node 0 (dp[0] stays 0: max(0, B) = B), its high half the old low half of register NR-1
+    const s16x2 wrap = __builtin_bit_cast(s16x2, __builtin_amdgcn_alignbit(__builtin_bit_cast(unsigned, reg[NR - 1]), 0u, 16));
+    s16x2 xE = zero, xE2 = zero;
+#pragma unroll
+    for (int g = NR / 4 - 1; g >= 0; g--) {                           // descending, in place: reg[r] <- f(reg[r-1] of the previous row)
+      const ssv_i4 inc = row[g];
+      const int r = 4 * g;
+      const s16x2 v3 = ssv_add(msv_pkmax(reg[r + 2], xBv), inc.w);
+      const s16x2 v2 = ssv_add(msv_pkmax(reg[r + 1], xBv), inc.z);
+      const s16x2 v1 = ssv_add(msv_pkmax(reg[r], xBv), inc.y);
+      const s16x2 v0 = ssv_add(msv_pkmax((r > 0) ? reg[r - 1] : wrap, xBv), inc.x);
+      reg[r + 3] = v3; reg[r + 2] = v2; reg[r + 1] = v1; reg[r] = v0;
+      xE = ssv_max3(xE, v3, v2);
+      xE2 = ssv_max3(xE2, v1, v0);
+    }
+    const h16x2 e1 = __builtin_bit_cast(h16x2, xE), e2 = __builtin_bit_cast(h16x2, xE2);
+    int xEi = (int)(fmaxf(fmaxf((float)e1.x, (float)e1.y), fmaxf((float)e2.x, (float)e2.y)) * 2048.0f);
+    if (xEi + c.bias >= 255) over = true;                              // msvfilter.c:172-178: sticky, the score is +inf
+    xEi = max(xEi - c.tec, 0);
+    xJ = max(xJ, xEi);
+    xB = max(max(c.base, xJ) - tjbm, 0);
+  }
+  *overflow = over;
+  return xJ;
+}
+// the score of a target that did not overflow (msvfilter.c:196-200)
+__device__ __forceinline__ float msv_lane_score(int xJ, int tjb, const MsvConsts &c) {
+  float r = ((float)(xJ - tjb) - (float)c.base);
+  r /= c.scale_b;
+  return (float)((double)r - 3.0);
 }
 
 struct WindowRec { int32_t cand, n, k, length; float score; };   // P7_HMM_WINDOW fields used on the path (hmmer.h:998)

@@ -46,6 +46,7 @@ int launch_ssv_classify(bath_hip_ctx *ctx, const bath_hip_oprofile *om, int64_t 
 int launch_msv_wave(bath_hip_ctx *ctx, const bath_hip_oprofile *om, SeqView v, const int32_t *d_todo, int64_t ntodo, float *d_sc, int32_t *d_status, const int *ntodo_dev, bool lane_ok = true);
 // the same with a lane per target (bath_msv_lane.hip): BATH_OK, an error, or BATH_ENORESULT when the model does not fit a lane's tile
 int launch_msv_lane(bath_hip_ctx *ctx, const bath_hip_oprofile *om, SeqView v, const int32_t *d_todo, int64_t ntodo, float *d_sc, int32_t *d_status, const int *ntodo_dev);
+bool msv_stage_supported(const bath_hip_oprofile *om);          // the model fits a lane's tile: launch_msv_lane and the cascade's msv_stage_kernel apply
 int launch_vit_wave(bath_hip_ctx *ctx, const bath_hip_oprofile *om, SeqView v, const int32_t *d_todo, int64_t ntodo, float *d_sc, int32_t *d_status,
                     const VitWindowArgs *wa, const int *ntodo_dev);
 int launch_fwd_wave(bath_hip_ctx *ctx, const bath_hip_oprofile *om, SeqView v, const int32_t *d_todo, int64_t ntodo, float *d_sc, int32_t *d_status, const int *ntodo_dev,

@@ -25,12 +25,6 @@ using namespace bath;
 
 namespace bath {
 
-__device__ __forceinline__ s16x2 msv_pkmax(s16x2 a, s16x2 b) {
-  s16x2 r;
-  asm("v_pk_max_f16 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-  return r;
-}
-
 template <int NR>
 __global__ __launch_bounds__(256, NR <= 76 ? 4 : 1) void msv_lane_kernel(SeqView sq, const int16_t *__restrict__ cost_tab /* the MSV increment table */, int row_bytes,
                                                                         const uint8_t *__restrict__ tjb_tab, MsvConsts c,
@@ -47,7 +41,6 @@ __global__ __launch_bounds__(256, NR <= 76 ? 4 : 1) void msv_lane_kernel(SeqView
   if (ntodo_dev) ntodo = *ntodo_dev;
   const int lane = threadIdx.x & 63;
   const int64_t nwaves = ((int64_t)gridDim.x * blockDim.x) >> 6;
-  typedef _Float16 h16x2 __attribute__((ext_vector_type(2)));
   for (int64_t w = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6; w * 64 < ntodo; w += nwaves) {
     const int64_t job = w * 64 + lane;
     const bool live = job < ntodo;
@@ -57,69 +50,27 @@ __global__ __launch_bounds__(256, NR <= 76 ? 4 : 1) void msv_lane_kernel(SeqView
     const int Lw = wave_max_i32(L);
     const int tjb = tjb_tab[L];
     const int tjbm = (uint8_t)((int8_t)tjb + (int8_t)c.tbm);
-    s16x2 reg[NR];
-    const s16x2 zero = {0, 0};
-#pragma unroll
-    for (int r = 0; r < NR; r++) reg[r] = zero;
-    int xJ = 0, xB = satu8(c.base - tjbm);
     bool overflow = false;
-    uint2 res = make_uint2(0u, 0u);
-    for (int i = 0; i < Lw; i++) {
-      // residues eight at a time while at least eight remain (the candidates' residues sit in the amino-acid streams: any alignment)
-      if ((i & 7) == 0) {
-        if (i + 8 <= L) __builtin_memcpy(&res, s + i, 8);
-        else {
-          res = make_uint2(0u, 0u);
-          for (int j = 0; j < 8 && i + j < L; j++) {
-            const unsigned b = s[i + j];
-            if (j < 4) res.x |= b << (8 * j); else res.y |= b << (8 * (j - 4));
-          }
-        }
-      }
-      const unsigned byte = (((i & 4) ? res.y : res.x) >> (8 * (i & 3))) & 0xffu;
-      const int x = (i < L) ? min((int)byte, kKp - 1) : kRowReset;       // past the target's end: the reset row (every cell back to 0, xE = 0: xJ and B keep their values)
-      const ssv_i4 *row = reinterpret_cast<const ssv_i4 *>(lds + (size_t)x * row_bytes);
-      const h16x2 bh = {(_Float16)((float)xB * (1.0f / 2048.0f)), (_Float16)((float)xB * (1.0f / 2048.0f))};
-      const s16x2 xBv = __builtin_bit_cast(s16x2, bh);
-      // register 0: its low half takes node 0 (dp[0] stays 0: max(0, B) = B), its high half the old low half of register NR-1
-      const s16x2 wrap = __builtin_bit_cast(s16x2, __builtin_amdgcn_alignbit(__builtin_bit_cast(unsigned, reg[NR - 1]), 0u, 16));
-      s16x2 xE = zero, xE2 = zero;
-#pragma unroll
-      for (int g = NR / 4 - 1; g >= 0; g--) {                           // descending, in place: reg[r] <- f(reg[r-1] of the previous row)
-        const ssv_i4 inc = row[g];
-        const int r = 4 * g;
-        const s16x2 v3 = ssv_add(msv_pkmax(reg[r + 2], xBv), inc.w);
-        const s16x2 v2 = ssv_add(msv_pkmax(reg[r + 1], xBv), inc.z);
-        const s16x2 v1 = ssv_add(msv_pkmax(reg[r], xBv), inc.y);
-        const s16x2 v0 = ssv_add(msv_pkmax((r > 0) ? reg[r - 1] : wrap, xBv), inc.x);
-        reg[r + 3] = v3; reg[r + 2] = v2; reg[r + 1] = v1; reg[r] = v0;
-        xE = ssv_max3(xE, v3, v2);
-        xE2 = ssv_max3(xE2, v1, v0);
-      }
-      const h16x2 e1 = __builtin_bit_cast(h16x2, xE), e2 = __builtin_bit_cast(h16x2, xE2);
-      int xEi = (int)(fmaxf(fmaxf((float)e1.x, (float)e1.y), fmaxf((float)e2.x, (float)e2.y)) * 2048.0f);
-      if (xEi + c.bias >= 255) overflow = true;                          // msvfilter.c:172-178: sticky, the score is +inf
-      xEi = max(xEi - c.tec, 0);
-      xJ = max(xJ, xEi);
-      xB = max(max(c.base, xJ) - tjbm, 0);
-    }
+    const int xJ = msv_lane_rows<NR>(lds, row_bytes, s, L, Lw, tjbm, c, &overflow);
     if (live) {
       if (overflow) { sc[sid] = INFINITY; status[sid] = BATH_ERANGE; }
-      else {
-        float r = ((float)(xJ - tjb) - (float)c.base);
-        r /= c.scale_b;
-        r = (float)((double)r - 3.0);
-        sc[sid] = r; status[sid] = BATH_OK;
-      }
+      else { sc[sid] = msv_lane_score(xJ, tjb, c); status[sid] = BATH_OK; }
     }
   }
 }
 
 // The lane-per-target MSV for models that fit one lane's tile of at most 76 registers (152 nodes); longer models and
-// BATH_HIP_MSV_WAVE=1 keep the wave-per-target kernel.  Returns BATH_ENORESULT when this kernel does not apply.
-int launch_msv_lane(bath_hip_ctx *ctx, const bath_hip_oprofile *om, SeqView v, const int32_t *d_todo, int64_t ntodo, float *d_sc, int32_t *d_status, const int *ntodo_dev) {
+// BATH_HIP_MSV_WAVE=1 keep the wave-per-target kernel.  The same condition admits the cascade's fused MSV stage (msv_stage_kernel,
+// bath_pipeline.hip), which runs this kernel's rows between the SSV classification and the F1 / bias decisions of a candidate.
+// launch_msv_lane returns BATH_ENORESULT when the kernel does not apply.
+bool msv_stage_supported(const bath_hip_oprofile *om) {
   static const bool off = [] { const char *e = std::getenv("BATH_HIP_MSV_WAVE"); return e && e[0] == '1'; }();
-  if (off || om->G != 1 || om->NR > 76 || !om->d_msv) return BATH_ENORESULT;
+  if (off || om->G != 1 || om->NR > 76 || !om->d_msv) return false;
+  return true;
+}
+
+int launch_msv_lane(bath_hip_ctx *ctx, const bath_hip_oprofile *om, SeqView v, const int32_t *d_todo, int64_t ntodo, float *d_sc, int32_t *d_status, const int *ntodo_dev) {
+  if (!msv_stage_supported(om)) return BATH_ENORESULT;
   if (ntodo == 0) return BATH_OK;
   const size_t shmem = (size_t)kSsvRows * om->ssv_row_bytes;
   const int64_t waves = (ntodo + 63) / 64;

@@ -172,55 +172,107 @@ __device__ __forceinline__ double d_gumbel_surv(double x, double mu, double lamb
 }
 __device__ __forceinline__ double d_exp_surv(double x, double mu, double lambda) { return (x < mu) ? 1.0 : exp(-lambda * (x - mu)); }
 
-// classify the SSV maxima (ssvfilter.c:876-925); undecided targets go to the full-MSV list
+// a candidate's first visit: the SSV maximum classified (ssvfilter.c:876-925), every later stage's field at its start value
+__device__ __forceinline__ int cand_classify(const Cand &cand, int c, int tjb, const MsvConsts &mc) {
+  float sc = 0.f;
+  const int st = ssv_classify(cand.v[c], tjb, mc, &sc);
+  cand.usc[c] = sc; cand.msv_status[c] = st; cand.stage[c] = 0; cand.flags[c] = 0;
+  cand.vfsc[c] = -INFINITY; cand.fwdsc[c] = -INFINITY; cand.vit_status[c] = 0; cand.filtersc[c] = 0.f; cand.P[c] = 1.0;
+  cand.kminmax[2 * c] = 1 << 30; cand.kminmax[2 * c + 1] = 0;
+  return st;
+}
+
+// classify the SSV maxima; undecided targets go to the full-MSV list
 __global__ void classify_kernel(Cand cand, int cand_cap, Counters *__restrict__ ctr, const uint8_t *__restrict__ tjb_tab, MsvConsts mc,
                                 int32_t *__restrict__ todo_msv) {
   const int ncand = min(ctr->cand_count, cand_cap);
   for (int c = blockIdx.x * blockDim.x + threadIdx.x; c < ncand; c += gridDim.x * blockDim.x) {
-    float sc = 0.f;
-    const int st = ssv_classify(cand.v[c], tjb_tab[cand.len[c]], mc, &sc);
-    cand.usc[c] = sc; cand.msv_status[c] = st; cand.stage[c] = 0; cand.flags[c] = 0;
-    cand.vfsc[c] = -INFINITY; cand.fwdsc[c] = -INFINITY; cand.vit_status[c] = 0; cand.filtersc[c] = 0.f; cand.P[c] = 1.0;
-    cand.kminmax[2 * c] = 1 << 30; cand.kminmax[2 * c + 1] = 0;
-    if (st == BATH_ENORESULT) todo_msv[atomicAdd(&ctr->todo_msv, 1)] = c;
+    if (cand_classify(cand, c, tjb_tab[cand.len[c]], mc) == BATH_ENORESULT) todo_msv[atomicAdd(&ctr->todo_msv, 1)] = c;
   }
 }
 
 // MSV P-value (F1), bias filter (F1), then route to Viterbi (P > F2) or SSV windows (P <= F2): p7_pipeline.c:1649-1677
-__global__ void f1_bias_kernel(Cand cand, int cand_cap, Counters *__restrict__ ctr, Params p, const uint8_t *__restrict__ pool, int M,
-                               const float *__restrict__ eo, const float *__restrict__ nullsc_tab, const float *__restrict__ p1_tab,
-                               const float *__restrict__ lt1_tab, const float *__restrict__ lt2_tab,
+struct F1Tables { const float *eo, *nullsc, *p1, *lt1, *lt2; };      // the bias filter's emission odds [Kp][2]; by target length: null score, p1, the length corrections
+__device__ __forceinline__ void cand_f1_bias(const Cand &cand, int c, Counters *__restrict__ ctr, const Params &p, const uint8_t *__restrict__ pool, int M,
+                                             const float *s_eo /* the emission odds in LDS */, const F1Tables &t,
+                                             int32_t *__restrict__ todo_vit, int32_t *__restrict__ todo_ssvb) {
+  const int L = cand.len[c];
+  const float usc = cand.usc[c];
+  const float nullsc = t.nullsc[L];
+  cand.nullsc[c] = nullsc;
+  float seqsc = (float)((double)(usc - nullsc) / kLog2);
+  double P = d_gumbel_surv(seqsc, p.evparam[0], p.evparam[1]);
+  cand.P[c] = P;
+  if (P > p.F1) return;
+  atomicAdd(&ctr->n_past_msv, 1ull); atomicAdd(&ctr->pos_past_msv, (unsigned long long)L * 3ull);
+  cand.stage[c] = 1;
+  float filtersc = nullsc;
+  if (p.do_bias) {
+    filtersc = bias_forward(pool + cand.off[c], L, M, s_eo, t.p1[L]);
+    filtersc = (filtersc + t.lt1[L]) + t.lt2[L];
+    seqsc = (float)((double)(usc - filtersc) / kLog2);
+    P = d_gumbel_surv(seqsc, p.evparam[0], p.evparam[1]);
+    cand.P[c] = P; cand.filtersc[c] = filtersc;
+    if (P > p.F1) return;
+  }
+  cand.filtersc[c] = filtersc;
+  atomicAdd(&ctr->n_past_bias, 1ull); atomicAdd(&ctr->pos_past_bias, (unsigned long long)L * 3ull);
+  cand.stage[c] = 2;
+  if (P > p.F2) { cand.flags[c] |= FLAG_VIT_RUN; todo_vit[atomicAdd(&ctr->todo_vit, 1)] = c; atomicAdd(&ctr->res_vit, (unsigned long long)L); }
+  else todo_ssvb[atomicAdd(&ctr->todo_ssvb, 1)] = c;
+}
+
+__global__ void f1_bias_kernel(Cand cand, int cand_cap, Counters *__restrict__ ctr, Params p, const uint8_t *__restrict__ pool, int M, F1Tables t,
                                int32_t *__restrict__ todo_vit, int32_t *__restrict__ todo_ssvb) {
   __shared__ float s_eo[kKp * 2];                          // the filter HMM's emission odds: read once per residue, from LDS
-  for (int i = threadIdx.x; i < kKp * 2; i += blockDim.x) s_eo[i] = eo[i];
+  for (int i = threadIdx.x; i < kKp * 2; i += blockDim.x) s_eo[i] = t.eo[i];
   __syncthreads();
   const int ncand = min(ctr->cand_count, cand_cap);
-  for (int c = blockIdx.x * blockDim.x + threadIdx.x; c < ncand; c += gridDim.x * blockDim.x) {
-    const int L = cand.len[c];
-    const float usc = cand.usc[c];
-    const float nullsc = nullsc_tab[L];
-    cand.nullsc[c] = nullsc;
-    float seqsc = (float)((double)(usc - nullsc) / kLog2);
-    double P = d_gumbel_surv(seqsc, p.evparam[0], p.evparam[1]);
-    cand.P[c] = P;
-    if (P > p.F1) continue;
-    atomicAdd(&ctr->n_past_msv, 1ull); atomicAdd(&ctr->pos_past_msv, (unsigned long long)L * 3ull);
-    cand.stage[c] = 1;
-    float filtersc = nullsc;
-    if (p.do_bias) {
-      filtersc = bias_forward(pool + cand.off[c], L, M, s_eo, p1_tab[L]);
-      filtersc = (filtersc + lt1_tab[L]) + lt2_tab[L];
-      seqsc = (float)((double)(usc - filtersc) / kLog2);
-      P = d_gumbel_surv(seqsc, p.evparam[0], p.evparam[1]);
-      cand.P[c] = P; cand.filtersc[c] = filtersc;
-      if (P > p.F1) continue;
-    }
-    cand.filtersc[c] = filtersc;
-    atomicAdd(&ctr->n_past_bias, 1ull); atomicAdd(&ctr->pos_past_bias, (unsigned long long)L * 3ull);
-    cand.stage[c] = 2;
-    if (P > p.F2) { cand.flags[c] |= FLAG_VIT_RUN; todo_vit[atomicAdd(&ctr->todo_vit, 1)] = c; atomicAdd(&ctr->res_vit, (unsigned long long)L); }
-    else todo_ssvb[atomicAdd(&ctr->todo_ssvb, 1)] = c;
+  for (int c = blockIdx.x * blockDim.x + threadIdx.x; c < ncand; c += gridDim.x * blockDim.x) cand_f1_bias(cand, c, ctr, p, pool, M, s_eo, t, todo_vit, todo_ssvb);
+}
+
+// The MSV stage of a large block in one kernel, a lane per candidate: what classify_kernel, msv_lane_kernel and f1_bias_kernel do
+// one after the other, in that order and with their arithmetic (cand_classify, msv_lane_rows, cand_f1_bias: the same functions).
+// The candidates are taken in the order ssv_orf_kernel appended them.  That kernel strides a length-sorted ORF list, so the 64
+// lanes of a wave here hold ORFs of nearly one length already: both the MSV rows, which run to the wave's longest ORF, and the
+// bias filter's recurrence, a dependent chain of two divisions and an fp64 logarithm per residue, end together (a counting sort
+// in front of the kernel was measured: it saves the kernel 0.01 ms and costs 0.04).  A candidate's residues are read
+// for the rows and again, from cache, for the bias filter.
+template <int NR>
+__global__ __launch_bounds__(256, 4) void msv_stage_kernel(Cand cand, int cand_cap, Counters *__restrict__ ctr,
+                                                           const int16_t *__restrict__ cost_tab /* the MSV increment table */, int row_bytes,
+                                                           const uint8_t *__restrict__ tjb_tab, MsvConsts mc, Params p, const uint8_t *__restrict__ pool, int M,
+                                                           F1Tables t, int32_t *__restrict__ todo_vit, int32_t *__restrict__ todo_ssvb) {
+  extern __shared__ __attribute__((aligned(16))) char lds[];
+  __shared__ float s_eo[kKp * 2];
+  // Not persistent: the grid covers the candidate buffer, a wave takes the 64 candidates at its place in the list and a block beyond
+  // the list leaves at once.  (With a loop over several waves of candidates per wave, the fp64 logarithm's constants and the other
+  // invariants of the bias loop are hoisted above the row loop, where the tile leaves no register for them: scratch spills.)
+  const int ncand = min(ctr->cand_count, cand_cap);
+  if ((int64_t)blockIdx.x * blockDim.x >= ncand) return;
+  {
+    const int n32 = kSsvRows * row_bytes / 4;
+    const uint32_t *src = reinterpret_cast<const uint32_t *>(cost_tab);
+    uint32_t *dst = reinterpret_cast<uint32_t *>(lds);
+    for (int i = threadIdx.x; i < n32; i += blockDim.x) dst[i] = src[i];
+    for (int i = threadIdx.x; i < kKp * 2; i += blockDim.x) s_eo[i] = t.eo[i];
   }
+  __syncthreads();
+  const int64_t job = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const bool live = job < ncand;
+  const int c = live ? (int)job : 0;
+  const int L = live ? cand.len[c] : 0;
+  const int tjb = tjb_tab[L];
+  const bool rescore = live && cand_classify(cand, c, tjb, mc) == BATH_ENORESULT;   // every candidate of the cascade, in practice (bath_msv_lane.hip)
+  const int Lr = rescore ? L : 0;
+  const uint8_t *s = pool + (rescore ? cand.off[c] : 0);
+  bool overflow = false;
+  const int xJ = msv_lane_rows<NR>(lds, row_bytes, s, Lr, wave_max_i32(Lr), (uint8_t)((int8_t)tjb + (int8_t)mc.tbm), mc, &overflow);
+  if (rescore) {
+    if (overflow) { cand.usc[c] = INFINITY; cand.msv_status[c] = BATH_ERANGE; }
+    else { cand.usc[c] = msv_lane_score(xJ, tjb, mc); cand.msv_status[c] = BATH_OK; }
+  }
+  if (live) cand_f1_bias(cand, c, ctr, p, pool, M, s_eo, t, todo_vit, todo_ssvb);
 }
 
 // p7_SSVFilter_BATH (msvfilter.c:250-427): diagonal windows for strong MSV hits, wave per candidate.
@@ -779,17 +831,37 @@ static int run_filters(bath_hip_ctx *ctx, const bath_hip_oprofile *om, const bat
     // host's proxy.  tools/lane_crossover.py, M = 145, windows of 1 kb: Viterbi 0.72 (lane) / 0.19 (wave) ms at 12.5 k windows,
     // 0.71 / 0.63 at 100 k, 0.75 / 1.11 at 200 k; MSV 0.19 / 0.08, 0.22 / 0.10, 0.23 / 0.13, and 1.08 / 1.41 at 400 k.
     const bool few_cands = dna->total < lane_min_nt(), few_msv = dna->total < 2 * lane_min_nt();
-    // 3. SSV status; full MSV for the undecided
-    hipLaunchKernelGGL(classify_kernel, dim3(dec_blocks), dim3(256), 0, ctx->stream, W.cand, W.cand_cap, W.ctr, om->lt.d_tjb, mc, W.todo_msv);
-    BATH_HIP_TRY(ctx, hipGetLastError());
+    const F1Tables f1t{om->d_bias_eo, om->lt.d_nullsc, om->lt.d_p1, om->lt.d_lt1, om->lt.d_lt2};
     // (the lane-per-ORF kernels pay off when the candidates fill the chip's lanes: see few_cands at the Viterbi stage below)
-    if ((st = launch_msv_wave(ctx, om, cv, W.todo_msv, cap, W.cand.usc, W.cand.msv_status, &W.ctr->todo_msv, !few_msv)) != BATH_OK) return st;
-    BATH_HIP_TRY(ctx, hipEventRecord(ev[e++], ctx->stream));
-    // 3. F1 on the MSV score, bias filter
-    hipLaunchKernelGGL(f1_bias_kernel, dim3(dec_blocks), dim3(256), 0, ctx->stream, W.cand, W.cand_cap, W.ctr, P, W.pool, M, om->d_bias_eo,
-                       om->lt.d_nullsc, om->lt.d_p1, om->lt.d_lt1, om->lt.d_lt2, W.todo_vit, W.todo_ssvb);
-    BATH_HIP_TRY(ctx, hipGetLastError());
-    BATH_HIP_TRY(ctx, hipEventRecord(ev[e++], ctx->stream));
+    const bool msv_stage = !few_msv && msv_stage_supported(om);
+    if (msv_stage) {
+      // 3. a large block: SSV status, full MSV, F1 and the bias filter in one kernel, a lane per candidate
+      bool launched = false;
+#define BATH_MSV_STAGE_CASE(N)                                                                                                              \
+  if (!launched && NRk == N) {                                                                                                              \
+    hipLaunchKernelGGL((msv_stage_kernel<N>), dim3((unsigned)((W.cand_cap + 255) / 256)), dim3(256), ssv_shmem, ctx->stream, W.cand, W.cand_cap, W.ctr, om->d_msv, \
+                       om->ssv_row_bytes, om->lt.d_tjb, mc, P, W.pool, M, f1t, W.todo_vit, W.todo_ssvb);                                      \
+    launched = true;                                                                                                                        \
+  }
+      BATH_MSV_STAGE_CASE(16) BATH_MSV_STAGE_CASE(20) BATH_MSV_STAGE_CASE(24) BATH_MSV_STAGE_CASE(28) BATH_MSV_STAGE_CASE(32) BATH_MSV_STAGE_CASE(36)
+      BATH_MSV_STAGE_CASE(40) BATH_MSV_STAGE_CASE(44) BATH_MSV_STAGE_CASE(48) BATH_MSV_STAGE_CASE(52) BATH_MSV_STAGE_CASE(56) BATH_MSV_STAGE_CASE(60)
+      BATH_MSV_STAGE_CASE(64) BATH_MSV_STAGE_CASE(68) BATH_MSV_STAGE_CASE(72) BATH_MSV_STAGE_CASE(76)
+#undef BATH_MSV_STAGE_CASE
+      if (!launched) { ctx->set_error("MSV stage kernel: no tile shape for this model length"); return BATH_EINVAL; }
+      BATH_HIP_TRY(ctx, hipGetLastError());
+      BATH_HIP_TRY(ctx, hipEventRecord(ev[e++], ctx->stream));
+      BATH_HIP_TRY(ctx, hipEventRecord(ev[e++], ctx->stream));         // the stage "f1_bias" keeps its entry in the timings: empty on this path
+    } else {
+      // 3. SSV status; full MSV for the undecided
+      hipLaunchKernelGGL(classify_kernel, dim3(dec_blocks), dim3(256), 0, ctx->stream, W.cand, W.cand_cap, W.ctr, om->lt.d_tjb, mc, W.todo_msv);
+      BATH_HIP_TRY(ctx, hipGetLastError());
+      if ((st = launch_msv_wave(ctx, om, cv, W.todo_msv, cap, W.cand.usc, W.cand.msv_status, &W.ctr->todo_msv, !few_msv)) != BATH_OK) return st;
+      BATH_HIP_TRY(ctx, hipEventRecord(ev[e++], ctx->stream));
+      // 3. F1 on the MSV score, bias filter
+      hipLaunchKernelGGL(f1_bias_kernel, dim3(dec_blocks), dim3(256), 0, ctx->stream, W.cand, W.cand_cap, W.ctr, P, W.pool, M, f1t, W.todo_vit, W.todo_ssvb);
+      BATH_HIP_TRY(ctx, hipGetLastError());
+      BATH_HIP_TRY(ctx, hipEventRecord(ev[e++], ctx->stream));
+    }
     // 4. Viterbi filter with windows (P > F2) / SSV windows (P <= F2)
     wa.d_filtersc = W.cand.filtersc; wa.d_ssv_scores = d_ssvsc; wa.d_wins = W.wins; wa.d_win_count = &W.ctr->win_count; wa.win_cap = W.win_cap;
     wa.d_kminmax = W.cand.kminmax;
@@ -865,7 +937,7 @@ static int run_filters(bath_hip_ctx *ctx, const bath_hip_oprofile *om, const bat
       continue;
     }
     static const char *names[] = {"translate_orfs", "ssv_f1", "classify_msv", "f1_bias", "viterbi_windows", "ssv_windows", "post_vit", "forward_final"};
-    static const int64_t launches[] = {4, 1, 2, 1, 4, 1, 3, 2};
+    const int64_t launches[] = {4, 1, msv_stage ? 1 : 2, msv_stage ? 0 : 1, 4, 1, 3, 2};
     ctx->timings.clear();
     for (int i = 0; i + 1 < e; i++) {
       float ms = 0.f;
