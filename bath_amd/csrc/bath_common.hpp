@@ -17,6 +17,7 @@
 #include <vector>
 
 #include "bath_hip.h"
+#include "bath_tilings.hpp"
 
 namespace bath {
 
@@ -47,8 +48,8 @@ constexpr int kXaa = 26;                 // 'X'
 constexpr int kOrfBins = 2048;           // ORF length histogram of the work-list sort (longer ORFs share the last bin)
 constexpr int kOrfCursorStride = 32;     // the sort's per-bin cursors, one 128-byte line each: every block adds to every busy bin
 constexpr int kOrfMiscInts = (1 + kOrfCursorStride) * kOrfBins + 64;   // histogram, cursors, total, spare: the misc buffer past 5*nent
-constexpr int kFsMaxNodes = 64 * 20;     // frameshift kernels: at most 20 nodes per lane (fs_columns, odds_columns, BATH_CHAIN_SWITCH)
-constexpr int kCascadeMaxNodes = 64 * 32;   // filter cascade: the MSV / Viterbi / Forward wave kernels take at most 32 nodes per lane (columns_per_lane)
+constexpr int kFsMaxNodes = 64 * BATH_TILING_MAX(BATH_FS_COLUMNS);        // frameshift kernels: at most 20 nodes per lane
+constexpr int kCascadeMaxNodes = 64 * BATH_TILING_MAX(BATH_WAVE_COLUMNS);   // filter cascade: the MSV / Viterbi / Forward wave kernels take at most 32 nodes per lane
 
 #define BATH_HIP_TRY(ctx, call)                                                            \
   do {                                                                                     \

@@ -768,26 +768,9 @@ int launch_ssv_lane(bath_hip_ctx *ctx, const bath_hip_oprofile *om, SeqView v, c
 
 constexpr size_t kWaveTableLdsMax = 150 * 1024;      // Forward / Backward tables above this stay in global memory (160 KB of LDS per CU)
 
-static int columns_per_lane(int M) {
-  int c = (M + 63) / 64;
-  for (int opt : {1, 2, 3, 4, 6, 8, 12, 16, 24, 32}) if (c <= opt) return opt;
-  return -1;
-}
-
-#define BATH_C_SWITCH(C, BODY)                                   \
-  switch (C) {                                                   \
-    case 1: { constexpr int CC = 1; BODY } break;                \
-    case 2: { constexpr int CC = 2; BODY } break;                \
-    case 3: { constexpr int CC = 3; BODY } break;                \
-    case 4: { constexpr int CC = 4; BODY } break;                \
-    case 6: { constexpr int CC = 6; BODY } break;                \
-    case 8: { constexpr int CC = 8; BODY } break;                \
-    case 12: { constexpr int CC = 12; BODY } break;              \
-    case 16: { constexpr int CC = 16; BODY } break;              \
-    case 24: { constexpr int CC = 24; BODY } break;              \
-    case 32: { constexpr int CC = 32; BODY } break;              \
-    default: ctx->set_error("model too long (> 2048 nodes)"); return BATH_EINVAL; \
-  }
+// nodes per lane of the wave-per-target kernels; the body sees them as the constant CC
+#define BATH_C_SWITCH(C, ...) BATH_TILING_SWITCH(BATH_WAVE_COLUMNS, C, { ctx->set_error("model too long (> 2048 nodes)"); return BATH_EINVAL; }, __VA_ARGS__)
+static_assert(kCascadeMaxNodes == 2048, "BATH_C_SWITCH's refusal names the limit");
 
 static int wave_grid(bath_hip_ctx *ctx, int64_t njobs) {
   int64_t blocks = (njobs + 3) / 4;
@@ -801,7 +784,7 @@ int launch_msv_wave(bath_hip_ctx *ctx, const bath_hip_oprofile *om, SeqView v, c
     const int st = launch_msv_lane(ctx, om, v, d_todo, ntodo, d_sc, d_status, ntodo_dev);
     if (st != BATH_ENORESULT) return st;
   }
-  const int C = columns_per_lane(om->M);
+  const int C = BATH_TILING_PICK(BATH_WAVE_COLUMNS, om->M);
   const int grid = wave_grid(ctx, ntodo);
   BATH_C_SWITCH(C, hipLaunchKernelGGL(msv_wave_kernel<CC>, dim3(grid), dim3(256), 0, ctx->stream, v, om->M, om->d_rb, om->rb_stride,
                                       om->lt.d_tjb, msv_consts(om), d_todo, ntodo, ntodo_dev, d_sc, d_status);)
@@ -812,7 +795,7 @@ int launch_msv_wave(bath_hip_ctx *ctx, const bath_hip_oprofile *om, SeqView v, c
 int launch_vit_wave(bath_hip_ctx *ctx, const bath_hip_oprofile *om, SeqView v, const int32_t *d_todo, int64_t ntodo, float *d_sc, int32_t *d_status,
                     const VitWindowArgs *wa, const int *ntodo_dev) {
   if (ntodo == 0) return BATH_OK;
-  const int C = columns_per_lane(om->M);
+  const int C = BATH_TILING_PICK(BATH_WAVE_COLUMNS, om->M);
   const int grid = wave_grid(ctx, ntodo);
   const size_t shmem = ((size_t)kKp * vit_em_stride(om->M) + 64 * (size_t)C) * sizeof(int16_t);
   VitConsts c = vit_consts(om);
@@ -830,7 +813,7 @@ int launch_vit_wave(bath_hip_ctx *ctx, const bath_hip_oprofile *om, SeqView v, c
 int launch_fwd_wave(bath_hip_ctx *ctx, const bath_hip_oprofile *om, SeqView v, const int32_t *d_todo, int64_t ntodo, float *d_sc, int32_t *d_status, const int *ntodo_dev,
                     float *d_xmx, const int64_t *d_xmx_off, float *d_dp, const int64_t *d_dp_off, int unihit, const int32_t *d_cfg_len) {
   if (ntodo == 0) return BATH_OK;
-  const int C = columns_per_lane(om->M);
+  const int C = BATH_TILING_PICK(BATH_WAVE_COLUMNS, om->M);
   const int grid = wave_grid(ctx, ntodo);
   const size_t shmem = ((size_t)kKp * wave_em_stride(om->M) + 64 * (size_t)C) * sizeof(float);
   FwdConsts c{om->xf_E[0], om->xf_E[1]};
@@ -852,7 +835,7 @@ int launch_fwd_wave(bath_hip_ctx *ctx, const bath_hip_oprofile *om, SeqView v, c
 int launch_bwd_wave(bath_hip_ctx *ctx, const bath_hip_oprofile *om, SeqView v, int64_t n, const float *d_fwd_xmx, const int64_t *d_xmx_off,
                     float *d_sc, int32_t *d_status, float *d_bck_xmx, float *d_dp, const int64_t *d_dp_off, int unihit) {
   if (n == 0) return BATH_OK;
-  const int C = columns_per_lane(om->M);
+  const int C = BATH_TILING_PICK(BATH_WAVE_COLUMNS, om->M);
   const int grid = wave_grid(ctx, n);
   const size_t shmem = ((size_t)kKp * wave_em_stride(om->M) + 64 * (size_t)C) * sizeof(float);
   FwdConsts c{om->xf_E[0], om->xf_E[1]};

@@ -1382,26 +1382,6 @@ extern "C" int bath_hip_fsprofile_convert(bath_hip_ctx *ctx, const bath_fs_profi
 
 namespace bath {
 
-static int fs_columns(int M) {
-  const int c = (M + 63) / 64;
-  for (int opt : {1, 2, 3, 4, 6, 8, 12, 16, 20}) if (c <= opt) return opt;
-  return -1;
-}
-
-#define BATH_FS_SWITCH(Cv, BODY)                          \
-  switch (Cv) {                                           \
-    case 1: { constexpr int CC = 1; BODY } break;         \
-    case 2: { constexpr int CC = 2; BODY } break;         \
-    case 3: { constexpr int CC = 3; BODY } break;         \
-    case 4: { constexpr int CC = 4; BODY } break;         \
-    case 6: { constexpr int CC = 6; BODY } break;         \
-    case 8: { constexpr int CC = 8; BODY } break;         \
-    case 12: { constexpr int CC = 12; BODY } break;       \
-    case 16: { constexpr int CC = 16; BODY } break;       \
-    case 20: { constexpr int CC = 20; BODY } break;       \
-    default: ctx->set_error("frameshift kernels support models up to 1280 nodes"); return BATH_EINVAL; \
-  }
-
 // logsum_mode -> kernel MODE: 0 table + wavefront scans, 1 exact log-sums (BATH_LOGSUM_TABLE_SERIAL, "strict", runs the chain
 // kernels of bath_fs_chain.hip instead)
 #define BATH_FS_MODE(modev, BODY)                         \
@@ -1471,7 +1451,7 @@ static int fs3_parser(bath_hip_ctx *ctx, const bath_hip_fsprofile *om, const bat
     if ((st = upload_offsets(ctx, b_off, xmx_off, n)) != BATH_OK) return st;
     d_x = bx.as<float>();
   }
-  const int Cv = fs_columns(om->M);
+  const int Cv = BATH_TILING_PICK(BATH_FS_COLUMNS, om->M);
   const size_t shmem = (size_t)(kLogsumTbl + (om->M + 2) * 8) * sizeof(float);
   const float tE = (float)-0.69314718055994529;
   const int grid_dp = fs_grid_dp(ctx, n);
@@ -1637,7 +1617,7 @@ int fs3_regions(bath_hip_ctx *ctx, const bath_hip_fsprofile *om, const bath_hip_
     BATH_HIP_TRY(ctx, hipMemcpyAsync(b_foff.p, fsel.data(), (size_t)n * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
     d_fx = ctx->scratch[45].as<float>(); d_fxoff = b_foff.as<int64_t>();
   }
-  const int Cv = fs_columns(om->M);
+  const int Cv = BATH_TILING_PICK(BATH_FS_COLUMNS, om->M);
   const size_t shmem = (size_t)(kLogsumTbl + (om->M + 2) * 8) * sizeof(float);
   const float tE = (float)-0.69314718055994529;
   const int grid_dp = fs_grid_dp(ctx, n);
@@ -1791,7 +1771,7 @@ int bath::fs5_envelopes_ex(bath_hip_ctx *ctx, const bath_hip_fsprofile *om, cons
   BATH_HIP_TRY(ctx, hipMemcpyAsync(d_boff, boff.data(), (n + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
   BATH_HIP_TRY(ctx, hipMemcpyAsync(d_xoff, xoff.data(), (n + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
   float *d_fsc = b_sc.as<float>(), *d_bsc = d_fsc + n, *d_osc = d_bsc + n;
-  const int Cv = fs_columns(M);
+  const int Cv = BATH_TILING_PICK(BATH_FS_COLUMNS, M);
   const size_t oa_shmem = (size_t)(M + 2) * 8 * sizeof(float);
   // BATH_LOGSUM_CONTEXT: the odds-ratio kernels while bath_hip_set_fs5_odds is on (before fs_strict), else strict / fast
   const bool odds5 = logsum_mode == BATH_LOGSUM_CONTEXT && ctx->fs5_odds;
@@ -1968,7 +1948,7 @@ int bath::fs5_region_forward(bath_hip_ctx *ctx, const bath_hip_fsprofile *om, co
   int64_t *d_foff = b_off.as<int64_t>(), *d_xoff = d_foff + (n + 1);
   BATH_HIP_TRY(ctx, hipMemcpyAsync(d_foff, foff.data(), (size_t)(n + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
   BATH_HIP_TRY(ctx, hipMemcpyAsync(d_xoff, xoff.data(), (size_t)(n + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
-  const int Cv = fs_columns(M);
+  const int Cv = BATH_TILING_PICK(BATH_FS_COLUMNS, M);
   const size_t shmem = (size_t)(kLogsumTbl + (M + 2) * 8) * sizeof(float);
   const int grid_dp = fs_grid_dp(ctx, n);
   const float tE = (float)-0.69314718055994529;                               // multihit: E->C and E->J both log 1/2 (modelconfig.c:825-831)

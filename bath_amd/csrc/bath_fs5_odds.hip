@@ -40,7 +40,6 @@ using namespace bath;
 
 namespace bath {
 
-constexpr int kOdds5Block = 256;         // 4 waves, one envelope each; nothing is shared inside a block
 constexpr int kDegen5 = 1367;            // p7P_MAXCODONS5: marks a degenerate nucleotide (rows 1364..1366 are the degenerate codons)
 
 // (wave-uniform: the emission rows' addresses stay in scalar registers)
@@ -49,14 +48,6 @@ __device__ __forceinline__ int nuc5(uint8_t c) { return __builtin_amdgcn_readfir
 // natural log of an odds ratio plus the scale, for the matrices (8 C values per lane and row): v_log_f32 (log2) times ln 2;
 // 0 -> -inf.  Within ~1e-7 relative of logf, far inside the mode's bars.
 __device__ __forceinline__ float ln_odds(float v, float s) { return __builtin_amdgcn_logf(v) * 0.6931471805599453f + s; }
-
-// The tables cover every node a lane owns, 1 .. 64 C, with zeros beyond M (ensure_odds): node k's emission at column k-1, so a
-// lane's C values start at lane*C -- whole 16-byte loads when 4 divides C; nodes beyond M come out 0 without a branch or a clamp.
-struct Fs5OddsDev {
-  int M, pitch;
-  const float *rsc;          // [1367][pitch = 64 C + 4] expf(rsc)
-  const float *tf, *tb;      // [64 C + 2][8] expf of the log-space kernels' tf / tb (node 0 and nodes beyond M: zeros)
-};
 
 // emissions fetched one row ahead, off the row's dependency chain, while the registers allow it
 template <int C> constexpr bool odds5_ahead() { return C <= 6; }
@@ -86,7 +77,7 @@ __device__ __forceinline__ void mark_done(int *done, int64_t job, int lane) {
 // tf[node] = {tMM(k-1), tIM(k-1), tDM(k-1), tBM(k-1), tMD(k), tDD(k), tMI(k), tII(k)}
 // ---------------------------------------------------------------------------------------------
 template <int C, bool MULTIHIT>
-__global__ __launch_bounds__(kOdds5Block) void fs5_fwd_odds_kernel(SeqView dna, Fs5OddsDev p, const float *__restrict__ loop_tab, const float *__restrict__ move_tab,
+__global__ __launch_bounds__(kOddsBlock) void fs5_fwd_odds_kernel(SeqView dna, FsOddsDev p, const float *__restrict__ loop_tab, const float *__restrict__ move_tab,
                                                                     float *__restrict__ sc, float *__restrict__ fwd, const int64_t *__restrict__ fwd_off,
                                                                     float *__restrict__ xmx, const int64_t *__restrict__ xmx_off,
                                                                     int cfg_len /* >= 0: the amino length the model is configured for, instead of L/3 */, FsJobs jobs,
@@ -97,8 +88,8 @@ __global__ __launch_bounds__(kOdds5Block) void fs5_fwd_odds_kernel(SeqView dna, 
   // C = 20: the IVX ring in LDS (4 rows x 20 floats per thread, 80 KB per block, each thread its own column, no barrier) -- in
   // registers it is the 80 values that pushed the kernel past 512 registers into scratch
   constexpr bool IVL = C >= 20;
-  __shared__ float s_iv[IVL ? 4 * C * kOdds5Block : 1];
-  auto ivs = [&](int row, int c) -> float & { return s_iv[(((row & 3) * C) + c) * kOdds5Block + threadIdx.x]; };
+  __shared__ float s_iv[IVL ? 4 * C * kOddsBlock : 1];
+  auto ivs = [&](int row, int c) -> float & { return s_iv[(((row & 3) * C) + c) * kOddsBlock + threadIdx.x]; };
   for (int64_t job = fs_next_job(jobs, dna.n, lane); job >= 0; job = fs_next_job(jobs, dna.n, lane)) {
     const int L = dna.len[job];
     const uint8_t *d = dna.data + dna.off[job];
@@ -227,7 +218,7 @@ __global__ __launch_bounds__(kOdds5Block) void fs5_fwd_odds_kernel(SeqView dna, 
 // tb[node] = {tMD(k), tMI(k), tMM(k), tDD(k), tDM(k), tII(k), tIM(k), tBM(k-1)}
 // ---------------------------------------------------------------------------------------------
 template <int C>
-__global__ __launch_bounds__(kOdds5Block) void fs5_bwd_odds_kernel(SeqView dna, Fs5OddsDev p, const float *__restrict__ loop_tab, const float *__restrict__ move_tab,
+__global__ __launch_bounds__(kOddsBlock) void fs5_bwd_odds_kernel(SeqView dna, FsOddsDev p, const float *__restrict__ loop_tab, const float *__restrict__ move_tab,
                                                                     float *__restrict__ sc, float *__restrict__ bck, const int64_t *__restrict__ bck_off,
                                                                     float *__restrict__ xmx, const int64_t *__restrict__ xmx_off, FsJobs jobs) {
   const int M = p.M;
@@ -352,21 +343,6 @@ __global__ __launch_bounds__(kOdds5Block) void fs5_bwd_odds_kernel(SeqView dna, 
   }
 }
 
-// the per-lane tilings of fs_columns (bath_frameshift.hip), the same list (tests/test_fs5_odds_cpu.py holds the two equal)
-#define BATH_FS_SWITCH(Cv, BODY)                          \
-  switch (Cv) {                                           \
-    case 1: { constexpr int CC = 1; BODY } break;         \
-    case 2: { constexpr int CC = 2; BODY } break;         \
-    case 3: { constexpr int CC = 3; BODY } break;         \
-    case 4: { constexpr int CC = 4; BODY } break;         \
-    case 6: { constexpr int CC = 6; BODY } break;         \
-    case 8: { constexpr int CC = 8; BODY } break;         \
-    case 12: { constexpr int CC = 12; BODY } break;       \
-    case 16: { constexpr int CC = 16; BODY } break;       \
-    case 20: { constexpr int CC = 20; BODY } break;       \
-    default: ctx->set_error("frameshift kernels support models up to 1280 nodes"); return BATH_EINVAL; \
-  }
-
 int launch_fs5_odds(bath_hip_ctx *ctx, hipStream_t stream, const bath_hip_fsprofile *om, const bath_hip_seqs *dna, Fs5OddsKind kind,
                     float *d_sc, float *d_mx, const int64_t *d_moff, float *d_xmx, const int64_t *d_xoff, int cfg_len, FsJobs jobs, int *d_done) {
   const int64_t n = dna->n;
@@ -374,20 +350,19 @@ int launch_fs5_odds(bath_hip_ctx *ctx, hipStream_t stream, const bath_hip_fsprof
   if (om->codon_lengths != 5) { ctx->set_error("the 5-codon odds-ratio kernels need a 5-codon profile"); return BATH_EINVAL; }
   int st = om->ensure_odds();
   if (st != BATH_OK) return st;
-  const int Cv = (om->odds_pitch - 4) / 64;                  // the tiling ensure_odds padded the tables for (odds_columns)
-  const Fs5OddsDev p{om->M, om->odds_pitch, om->d_odds_rsc, om->d_odds_tf, om->d_odds_tb};
-  const int wpb = kOdds5Block / 64;
-  const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((n + wpb - 1) / wpb, (int64_t)ctx->prop.multiProcessorCount * 8));
+  const int Cv = (om->odds_pitch - 4) / 64;                  // the tiling ensure_odds padded the tables for
+  const FsOddsDev p = fs_odds_dev(om);
+  const int grid = fs_odds_grid(ctx, n);
   // envelopes: the unihit length model of L/3 (d_loop[1]); regions: the multihit one of <cfg_len> (d_loop[0])
   BATH_FS_SWITCH(Cv, {
     if (kind == kFs5OddsEnvFwd)
-      hipLaunchKernelGGL((fs5_fwd_odds_kernel<CC, false>), dim3(grid), dim3(kOdds5Block), 0, stream, dna->view(), p, om->d_loop[1], om->d_move[1], d_sc, d_mx, d_moff,
+      hipLaunchKernelGGL((fs5_fwd_odds_kernel<CC, false>), dim3(grid), dim3(kOddsBlock), 0, stream, dna->view(), p, om->d_loop[1], om->d_move[1], d_sc, d_mx, d_moff,
                          d_xmx, d_xoff, -1, jobs, (int *)nullptr);
     else if (kind == kFs5OddsRegionFwd)
-      hipLaunchKernelGGL((fs5_fwd_odds_kernel<CC, true>), dim3(grid), dim3(kOdds5Block), 0, stream, dna->view(), p, om->d_loop[0], om->d_move[0], d_sc, d_mx, d_moff,
+      hipLaunchKernelGGL((fs5_fwd_odds_kernel<CC, true>), dim3(grid), dim3(kOddsBlock), 0, stream, dna->view(), p, om->d_loop[0], om->d_move[0], d_sc, d_mx, d_moff,
                          d_xmx, d_xoff, cfg_len, jobs, d_done);
     else
-      hipLaunchKernelGGL((fs5_bwd_odds_kernel<CC>), dim3(grid), dim3(kOdds5Block), 0, stream, dna->view(), p, om->d_loop[1], om->d_move[1], d_sc, d_mx, d_moff,
+      hipLaunchKernelGGL((fs5_bwd_odds_kernel<CC>), dim3(grid), dim3(kOddsBlock), 0, stream, dna->view(), p, om->d_loop[1], om->d_move[1], d_sc, d_mx, d_moff,
                          d_xmx, d_xoff, jobs);
   })
   BATH_HIP_TRY(ctx, hipGetLastError());

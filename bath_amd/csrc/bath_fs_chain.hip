@@ -1411,20 +1411,6 @@ static int chain_waves(bath_hip_ctx *ctx, int64_t n, int M, int C, size_t *shmem
   return W;
 }
 
-#define BATH_CHAIN_SWITCH(Cv, BODY)                       \
-  switch (Cv) {                                           \
-    case 1: { constexpr int CC = 1; BODY } break;         \
-    case 2: { constexpr int CC = 2; BODY } break;         \
-    case 3: { constexpr int CC = 3; BODY } break;         \
-    case 4: { constexpr int CC = 4; BODY } break;         \
-    case 6: { constexpr int CC = 6; BODY } break;         \
-    case 8: { constexpr int CC = 8; BODY } break;         \
-    case 12: { constexpr int CC = 12; BODY } break;       \
-    case 16: { constexpr int CC = 16; BODY } break;       \
-    case 20: { constexpr int CC = 20; BODY } break;       \
-    default: ctx->set_error("frameshift kernels support models up to 1280 nodes"); return BATH_EINVAL; \
-  }
-
 int launch_fs3_fwd_chain(bath_hip_ctx *ctx, hipStream_t stream, const bath_hip_fsprofile *om, const bath_hip_seqs *dna, int Cv, float tEL, float tEM,
                          float *d_sc, float *d_xmx, const int64_t *d_xoff, FsJobs jobs, int cu_share) {
   const int M = om->M;
@@ -1486,7 +1472,7 @@ int launch_fs3_fwd_chain(bath_hip_ctx *ctx, hipStream_t stream, const bath_hip_f
     }
   }
   const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((n + W - 1) / W, (int64_t)ctx->prop.multiProcessorCount));
-  BATH_CHAIN_SWITCH(Cv, {
+  BATH_FS_SWITCH(Cv, {
     BATH_HIP_TRY(ctx, bath::allow_max_lds((const void *)fs3_fwd_chain_kernel<CC>));
     hipLaunchKernelGGL((fs3_fwd_chain_kernel<CC>), dim3(grid), dim3(64 * std::max(W, kChainAwakeWaves)), shmem, stream, dna->view(), dev, om->d_loop[0], om->d_move[0], tEL, tEM, d_sc, d_xmx, d_xoff, jobs, W);
   })
@@ -1544,7 +1530,7 @@ int launch_fs3_bwd_chain(bath_hip_ctx *ctx, hipStream_t stream, const bath_hip_f
     BATH_HIP_TRY(ctx, hipGetLastError());
     return BATH_OK;
   }
-  BATH_CHAIN_SWITCH(Cv, {
+  BATH_FS_SWITCH(Cv, {
     BATH_HIP_TRY(ctx, bath::allow_max_lds((const void *)fs3_bwd_chain_kernel<CC>));
     hipLaunchKernelGGL((fs3_bwd_chain_kernel<CC>), dim3(grid), dim3(64 * std::max(W, kChainAwakeWaves)), shmem, stream, dna->view(), dev, om->d_loop[0], om->d_move[0], tEL, tEM, d_sc, d_xmx, d_xoff, jobs,
                        b_bst.as<int32_t>(), nbat, W);
@@ -1568,7 +1554,7 @@ int launch_fs5_fwd_chain(bath_hip_ctx *ctx, hipStream_t stream, const bath_hip_f
   FsDev dev{om->M, om->pitch, om->maxcodons, om->d_rsc, om->d_tf, om->d_tb, om->d_logsum};
   // a couple of hundred regions are one or two per block: then the kernel built for 256 threads, whose lanes have registers for
   // the row's cells and the next row's emission scores without spilling (a 1024-thread block leaves a lane 128)
-  BATH_CHAIN_SWITCH(Cv, {
+  BATH_FS_SWITCH(Cv, {
     if (64 * W <= 256) {
       BATH_HIP_TRY(ctx, bath::allow_max_lds((const void *)fs5_fwd_chain_kernel<CC, 256>));
       hipLaunchKernelGGL((fs5_fwd_chain_kernel<CC, 256>), dim3(grid), dim3(64 * std::max(W, kChainAwakeWaves)), shmem, stream, dna->view(), dev, om->d_loop[0], om->d_move[0], tEL, tEM, c5_compat, d_sc, d_fwd, d_foff,

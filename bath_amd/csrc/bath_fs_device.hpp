@@ -134,6 +134,7 @@ __device__ __forceinline__ int imin(int a, int b) { return a < b ? a : b; }
 
 // ---- shared by the odds-ratio kernels (bath_fs_odds.hip, bath_fs5_odds.hip)
 constexpr float kOddsRescale = 1.0e4f;   // fwdback_fs.c:472: every value a later row reads is rescaled when E(i) (Backward: B(i)) passes it
+constexpr int kOddsBlock = 256;          // 4 waves, one window or envelope each; nothing is shared inside a block
 
 // x -> m x + a composed over the lanes below (DPP row_shr 1/2/4/8, row_bcast 15/31: the scan of d_chain_fwd); returns the
 // composition's offset EXCLUSIVE of this lane: the value entering the lane's first node when the chain starts at 0.
@@ -203,6 +204,25 @@ inline void fs_order_by_length_desc(const int32_t *len, int64_t n, std::vector<i
 }
 
 struct FsJobs { const int32_t *order; unsigned *counter; };
+
+// The odds-ratio tables (ensure_odds) cover every node a lane of the C-column kernel owns, 1 .. 64 C, with zeros beyond M: a lane's
+// loads are one vector offset plus immediates, and nodes beyond M come out 0 without a branch or a clamp.  The 5-codon kernels read
+// node k's emission at column k-1, so a lane's C values start at lane*C -- whole 16-byte loads when 4 divides C.
+struct FsOddsDev {
+  int M, pitch;
+  const float *rsc;          // [338 or 1367][pitch = 64 C + 4] expf(rsc): every codon, quasi-codon and degenerate row the kernels index
+  const float *tf, *tb;      // [64 C + 2][8] expf of the log-space kernels' tf / tb (node 0 and nodes beyond M: zeros)
+};
+inline FsOddsDev fs_odds_dev(const bath_hip_fsprofile *om) { return FsOddsDev{om->M, om->odds_pitch, om->d_odds_rsc, om->d_odds_tf, om->d_odds_tb}; }
+inline int fs_odds_grid(const bath_hip_ctx *ctx, int64_t n) {    // blocks of kOddsBlock threads, a wave per job, at most 8 per CU
+  const int wpb = kOddsBlock / 64;
+  return (int)std::max<int64_t>(1, std::min<int64_t>((n + wpb - 1) / wpb, (int64_t)ctx->prop.multiProcessorCount * 8));
+}
+
+// every frameshift launcher's dispatch: the body sees C as the constant CC (M beyond kFsMaxNodes: fs_model_ok refuses it earlier)
+#define BATH_FS_SWITCH(Cv, ...) \
+  BATH_TILING_SWITCH(BATH_FS_COLUMNS, Cv, { ctx->set_error("frameshift kernels support models up to 1280 nodes"); return BATH_EINVAL; }, __VA_ARGS__)
+static_assert(kFsMaxNodes == 1280, "BATH_FS_SWITCH's refusal names the limit");
 __device__ __forceinline__ int64_t fs_next_job(const FsJobs &q, int64_t n, int lane) {
   unsigned j = 0;
   if (lane == 0) j = atomicAdd(q.counter, 1u);

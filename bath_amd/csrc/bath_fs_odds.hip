@@ -34,19 +34,10 @@ using namespace bath;
 
 namespace bath {
 
-constexpr int kOddsBlock = 256;          // 4 waves, one window each; nothing is shared inside a block
 constexpr int kDegen3 = 338;             // p7P_MAXCODONS3: marks a degenerate nucleotide (rows 336 / 337 are the degenerate codons)
 
 // (wave-uniform: the emission rows' addresses stay in scalar registers)
 __device__ __forceinline__ int nuc3(uint8_t c) { return __builtin_amdgcn_readfirstlane(c < 4 ? (int)c : kDegen3); }
-
-// The tables cover every node a lane of the C-column kernel owns, 1 .. 64 C, with zeros beyond M: a lane's loads are one vector
-// offset plus immediates, and nodes beyond M come out 0 without a branch or a clamp.
-struct FsOddsDev {
-  int M, pitch;
-  const float *rsc;          // [338][pitch = 64 C + 4] expf(rsc): every codon, quasi-codon and degenerate row the kernels index
-  const float *tf, *tb;      // [64 C + 2][8] expf of the log-space kernels' tf / tb (node 0 and nodes beyond M: zeros)
-};
 
 // emissions fetched one row ahead, off the row's dependency chain, while the registers allow it
 template <int C> constexpr bool odds_ahead() { return C <= 8; }
@@ -289,21 +280,12 @@ __global__ __launch_bounds__(kOddsBlock) void fs3_bwd_odds_kernel(SeqView dna, F
 
 }  // namespace bath
 
-namespace bath {
-// nodes per lane of the frameshift kernels (fs_columns in bath_frameshift.hip): -1 beyond 1280 nodes
-static int odds_columns(int M) {
-  const int c = (M + 63) / 64;
-  for (int opt : {1, 2, 3, 4, 6, 8, 12, 16, 20}) if (c <= opt) return opt;
-  return -1;
-}
-}  // namespace bath
-
 // odds-ratio tables, built on the first odds-mode call for the profile (a strict-only user pays nothing): expf of the log-space
 // tables the other kernels read (-inf -> 0), padded with zeros to the 64 C nodes the kernel's lanes own
 int bath_hip_fsprofile::ensure_odds() const {
   std::lock_guard<std::mutex> lock(odds_mu);
   if (d_odds_rsc) return BATH_OK;
-  const int Cv = bath::odds_columns(M);
+  const int Cv = BATH_TILING_PICK(BATH_FS_COLUMNS, M);
   if (codon_lengths != 3 && codon_lengths != 5) { ctx->set_error("odds-ratio mode needs a 3- or 5-codon profile"); return BATH_EINVAL; }
   if (Cv < 0) return bath::fs_model_ok(ctx, this);
   const int nodes = 64 * Cv + 2, opitch = 64 * Cv + 4;
@@ -340,21 +322,13 @@ int launch_fs3_odds(bath_hip_ctx *ctx, hipStream_t stream, const bath_hip_fsprof
   if (n == 0) return BATH_OK;
   int st = om->ensure_odds();
   if (st != BATH_OK) return st;
-  const int Cv = odds_columns(om->M);
-  const FsOddsDev p{om->M, om->odds_pitch, om->d_odds_rsc, om->d_odds_tf, om->d_odds_tb};
-  const int wpb = kOddsBlock / 64;
-  const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((n + wpb - 1) / wpb, (int64_t)ctx->prop.multiProcessorCount * 8));
+  const FsOddsDev p = fs_odds_dev(om);
+  const int grid = fs_odds_grid(ctx, n);
   const float tE = (float)-0.69314718055994529;
-#define BATH_ODDS_LAUNCH(CC)                                                                                                                       \
-  case CC:                                                                                                                                         \
-    if (backward) hipLaunchKernelGGL((fs3_bwd_odds_kernel<CC>), dim3(grid), dim3(kOddsBlock), 0, stream, dna->view(), p, om->d_loop[0], om->d_move[0], tE, d_sc, d_xmx, d_xoff, jobs); \
-    else hipLaunchKernelGGL((fs3_fwd_odds_kernel<CC>), dim3(grid), dim3(kOddsBlock), 0, stream, dna->view(), p, om->d_loop[0], om->d_move[0], tE, d_sc, d_xmx, d_xoff, jobs);       \
-    break;
-  switch (Cv) {
-    BATH_ODDS_LAUNCH(1) BATH_ODDS_LAUNCH(2) BATH_ODDS_LAUNCH(3) BATH_ODDS_LAUNCH(4) BATH_ODDS_LAUNCH(6) BATH_ODDS_LAUNCH(8)
-    BATH_ODDS_LAUNCH(12) BATH_ODDS_LAUNCH(16) BATH_ODDS_LAUNCH(20)
-  }
-#undef BATH_ODDS_LAUNCH
+  BATH_FS_SWITCH(BATH_TILING_PICK(BATH_FS_COLUMNS, om->M), {
+    if (backward) hipLaunchKernelGGL((fs3_bwd_odds_kernel<CC>), dim3(grid), dim3(kOddsBlock), 0, stream, dna->view(), p, om->d_loop[0], om->d_move[0], tE, d_sc, d_xmx, d_xoff, jobs);
+    else hipLaunchKernelGGL((fs3_fwd_odds_kernel<CC>), dim3(grid), dim3(kOddsBlock), 0, stream, dna->view(), p, om->d_loop[0], om->d_move[0], tE, d_sc, d_xmx, d_xoff, jobs);
+  })
   BATH_HIP_TRY(ctx, hipGetLastError());
   return BATH_OK;
 }

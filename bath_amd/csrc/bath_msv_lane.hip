@@ -65,7 +65,7 @@ __global__ __launch_bounds__(256, NR <= 76 ? 4 : 1) void msv_lane_kernel(SeqView
 // launch_msv_lane returns BATH_ENORESULT when the kernel does not apply.
 bool msv_stage_supported(const bath_hip_oprofile *om) {
   static const bool off = [] { const char *e = std::getenv("BATH_HIP_MSV_WAVE"); return e && e[0] == '1'; }();
-  if (off || om->G != 1 || om->NR > 76 || !om->d_msv) return false;
+  if (off || om->G != 1 || om->NR > BATH_TILING_MAX(BATH_MSV_LANE_NR) || !om->d_msv) return false;
   return true;
 }
 
@@ -76,14 +76,13 @@ int launch_msv_lane(bath_hip_ctx *ctx, const bath_hip_oprofile *om, SeqView v, c
   const int64_t waves = (ntodo + 63) / 64;
   const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((waves + 3) / 4, (int64_t)ctx->prop.multiProcessorCount * 4));
   bool launched = false;
-#define BATH_MSV_CASE(N)                                                                                                               \
+#define BATH_MSV_CASE(N, ...)                                                                                                          \
   if (!launched && om->NR == N) {                                                                                                      \
     hipLaunchKernelGGL((msv_lane_kernel<N>), dim3(grid), dim3(256), shmem, ctx->stream, v, om->d_msv, om->ssv_row_bytes, om->lt.d_tjb,   \
                        MsvConsts{om->tbm_b, om->tec_b, om->base_b, om->bias_b, om->scale_b}, d_todo, ntodo, ntodo_dev, d_sc, d_status); \
     launched = true;                                                                                                                   \
   }
-  BATH_MSV_CASE(16) BATH_MSV_CASE(20) BATH_MSV_CASE(24) BATH_MSV_CASE(28) BATH_MSV_CASE(32) BATH_MSV_CASE(36) BATH_MSV_CASE(40) BATH_MSV_CASE(44)
-  BATH_MSV_CASE(48) BATH_MSV_CASE(52) BATH_MSV_CASE(56) BATH_MSV_CASE(60) BATH_MSV_CASE(64) BATH_MSV_CASE(68) BATH_MSV_CASE(72) BATH_MSV_CASE(76)
+  BATH_MSV_LANE_NR(BATH_MSV_CASE)
 #undef BATH_MSV_CASE
   if (!launched) return BATH_ENORESULT;
   BATH_HIP_TRY(ctx, hipGetLastError());

@@ -687,13 +687,18 @@ __global__ __launch_bounds__(64) void fwd_keep_offsets_kernel(const int32_t *__r
   }
 }
 
-// The cascade's wave kernels (columns_per_lane) stop at kCascadeMaxNodes, below what an OProfile holds (the SSV tiles go to 3328
+// The cascade's wave kernels (BATH_WAVE_COLUMNS) stop at kCascadeMaxNodes, below what an OProfile holds (the SSV tiles go to 3328
 // nodes): a longer model is refused here, before any kernel of the call runs, and not by the Viterbi stage halfway through a block.
 static int cascade_model_ok(bath_hip_ctx *ctx, const bath_hip_oprofile *om) {
   if (om->M <= kCascadeMaxNodes) return BATH_OK;
   ctx->set_error("the filter cascade supports models up to " + std::to_string(kCascadeMaxNodes) + " nodes (this one has " + std::to_string(om->M) + ")");
   return BATH_EINVAL;
 }
+
+// p7_SSVFilter_BATH's windows for the <todo> candidates (their number: ctr->todo_ssvb), a wave per candidate, on <stream> (defined beside its
+// other caller, bath_hip_ssvfilter_bath)
+static int launch_ssv_bath(bath_hip_ctx *ctx, hipStream_t stream, const bath_hip_oprofile *om, const Cand &cand, Counters *ctr, const int32_t *todo, const uint8_t *pool,
+                           const uint8_t *ssv_scores, const MsvConsts &mc, double invP, WindowRec *wins, int win_cap);
 
 static int run_filters(bath_hip_ctx *ctx, const bath_hip_oprofile *om, const bath_hip_seqs *dna,
                        const bath_pipeline_params *prm, bath_pipeline_stats *stats,
@@ -837,15 +842,13 @@ static int run_filters(bath_hip_ctx *ctx, const bath_hip_oprofile *om, const bat
     if (msv_stage) {
       // 3. a large block: SSV status, full MSV, F1 and the bias filter in one kernel, a lane per candidate
       bool launched = false;
-#define BATH_MSV_STAGE_CASE(N)                                                                                                              \
+#define BATH_MSV_STAGE_CASE(N, ...)                                                                                                         \
   if (!launched && NRk == N) {                                                                                                              \
     hipLaunchKernelGGL((msv_stage_kernel<N>), dim3((unsigned)((W.cand_cap + 255) / 256)), dim3(256), ssv_shmem, ctx->stream, W.cand, W.cand_cap, W.ctr, om->d_msv, \
                        om->ssv_row_bytes, om->lt.d_tjb, mc, P, W.pool, M, f1t, W.todo_vit, W.todo_ssvb);                                      \
     launched = true;                                                                                                                        \
   }
-      BATH_MSV_STAGE_CASE(16) BATH_MSV_STAGE_CASE(20) BATH_MSV_STAGE_CASE(24) BATH_MSV_STAGE_CASE(28) BATH_MSV_STAGE_CASE(32) BATH_MSV_STAGE_CASE(36)
-      BATH_MSV_STAGE_CASE(40) BATH_MSV_STAGE_CASE(44) BATH_MSV_STAGE_CASE(48) BATH_MSV_STAGE_CASE(52) BATH_MSV_STAGE_CASE(56) BATH_MSV_STAGE_CASE(60)
-      BATH_MSV_STAGE_CASE(64) BATH_MSV_STAGE_CASE(68) BATH_MSV_STAGE_CASE(72) BATH_MSV_STAGE_CASE(76)
+      BATH_MSV_LANE_NR(BATH_MSV_STAGE_CASE)
 #undef BATH_MSV_STAGE_CASE
       if (!launched) { ctx->set_error("MSV stage kernel: no tile shape for this model length"); return BATH_EINVAL; }
       BATH_HIP_TRY(ctx, hipGetLastError());
@@ -867,21 +870,7 @@ static int run_filters(bath_hip_ctx *ctx, const bath_hip_oprofile *om, const bat
     wa.d_kminmax = W.cand.kminmax;
     // p7_SSVFilter_BATH's windows for the candidates with P <= F2: other candidates than the Viterbi kernels', so it runs beside them
     auto launch_ssvb = [&](hipStream_t stream) -> int {
-      const int Cc = (M + 63) / 64;
-      int Cs = -1;
-      for (int opt : {1, 2, 3, 4, 6, 8, 12, 16, 24, 32, 52}) if (Cc <= opt) { Cs = opt; break; }
-#define BATH_SSVB_CASE(N)                                                                                                          \
-  case N:                                                                                                                          \
-    hipLaunchKernelGGL(ssv_bath_kernel<N>, dim3(wave_grid_blocks(ctx) / 4), dim3(256), 0, stream, W.cand, W.ctr, W.todo_ssvb, W.pool, M,      \
-                       om->d_rb, om->rb_stride, d_ssvsc, om->lt.d_tjb, om->lt.d_nullsc, mc, invP_f1, W.wins, W.win_cap, W.ctr);    \
-    break;
-      switch (Cs) {
-        BATH_SSVB_CASE(1) BATH_SSVB_CASE(2) BATH_SSVB_CASE(3) BATH_SSVB_CASE(4) BATH_SSVB_CASE(6) BATH_SSVB_CASE(8)
-        BATH_SSVB_CASE(12) BATH_SSVB_CASE(16) BATH_SSVB_CASE(24) BATH_SSVB_CASE(32) BATH_SSVB_CASE(52)
-        default: ctx->set_error("model too long for the SSV window kernel"); return BATH_EINVAL;
-      }
-#undef BATH_SSVB_CASE
-      return BATH_OK;
+      return launch_ssv_bath(ctx, stream, om, W.cand, W.ctr, W.todo_ssvb, W.pool, d_ssvsc, mc, invP_f1, W.wins, W.win_cap);
     };
     bool ssvb_done = false;
     if (vit_lane_supported(om) && !few_cands) {       // lane per ORF, ORFs bucketed by length, the long ones to the wave kernel (bath_viterbi.hip)
@@ -1617,6 +1606,15 @@ extern "C" int bath_hip_vitfilter_bath(bath_hip_ctx *ctx, const bath_hip_oprofil
   return windows_out(ctx, reinterpret_cast<const WindowRec *>(p + o_w), wa.d_win_count, cap, wins, nwins);
 }
 
+static int launch_ssv_bath(bath_hip_ctx *ctx, hipStream_t stream, const bath_hip_oprofile *om, const Cand &cand, Counters *ctr, const int32_t *todo, const uint8_t *pool,
+                           const uint8_t *ssv_scores, const MsvConsts &mc, double invP, WindowRec *wins, int win_cap) {
+  BATH_TILING_SWITCH(BATH_SSVB_COLUMNS, BATH_TILING_PICK(BATH_SSVB_COLUMNS, om->M), { ctx->set_error("model too long for the SSV window kernel"); return BATH_EINVAL; },
+    hipLaunchKernelGGL(ssv_bath_kernel<CC>, dim3(wave_grid_blocks(ctx) / 4), dim3(256), 0, stream, cand, ctr, todo, pool, om->M, om->d_rb, om->rb_stride, ssv_scores,
+                       om->lt.d_tjb, om->lt.d_nullsc, mc, invP, wins, win_cap, ctr);)
+  BATH_HIP_TRY(ctx, hipGetLastError());
+  return BATH_OK;
+}
+
 extern "C" int bath_hip_ssvfilter_bath(bath_hip_ctx *ctx, const bath_hip_oprofile *om, const bath_hip_seqs *sq, double P,
                                        const bath_hmm_window **wins, int64_t *nwins) {
   if (!ctx || !om || !sq || !wins || !nwins) return BATH_EINVAL;
@@ -1648,21 +1646,7 @@ extern "C" int bath_hip_ssvfilter_bath(bath_hip_ctx *ctx, const bath_hip_oprofil
   Counters *d_ctr = reinterpret_cast<Counters *>(p + o_ctr);
   const MsvConsts mc = msv_consts(om);
   const double invP = gumbel_invsurv(P, om->evparam[0], om->evparam[1]);                   // msvfilter.c:302
-  const int Cc = (M + 63) / 64;
-  int Cs = -1;
-  for (int opt : {1, 2, 3, 4, 6, 8, 12, 16, 24, 32, 52}) if (Cc <= opt) { Cs = opt; break; }
-#define BATH_SSVB_CASE(N)                                                                                                          \
-  case N:                                                                                                                          \
-    hipLaunchKernelGGL(ssv_bath_kernel<N>, dim3(wave_grid_blocks(ctx) / 4), dim3(256), 0, ctx->stream, cand, d_ctr, reinterpret_cast<const int32_t *>(p + o_todo), \
-                       sq->d_data, M, om->d_rb, om->rb_stride, reinterpret_cast<const uint8_t *>(p + o_ssv), om->lt.d_tjb, om->lt.d_nullsc, mc, invP,       \
-                       reinterpret_cast<WindowRec *>(p + o_w), cap, d_ctr);                                                        \
-    break;
-  switch (Cs) {
-    BATH_SSVB_CASE(1) BATH_SSVB_CASE(2) BATH_SSVB_CASE(3) BATH_SSVB_CASE(4) BATH_SSVB_CASE(6) BATH_SSVB_CASE(8)
-    BATH_SSVB_CASE(12) BATH_SSVB_CASE(16) BATH_SSVB_CASE(24) BATH_SSVB_CASE(32) BATH_SSVB_CASE(52)
-    default: ctx->set_error("model too long for the SSV window kernel"); return BATH_EINVAL;
-  }
-#undef BATH_SSVB_CASE
-  BATH_HIP_TRY(ctx, hipGetLastError());
+  if ((st = launch_ssv_bath(ctx, ctx->stream, om, cand, d_ctr, reinterpret_cast<const int32_t *>(p + o_todo), sq->d_data, reinterpret_cast<const uint8_t *>(p + o_ssv), mc, invP,
+                            reinterpret_cast<WindowRec *>(p + o_w), cap)) != BATH_OK) return st;
   return windows_out(ctx, reinterpret_cast<const WindowRec *>(p + o_w), &d_ctr->win_count, cap, wins, nwins);
 }

@@ -414,7 +414,7 @@ extern "C" int bath_hip_oprofile_convert(bath_hip_ctx *ctx, const bath_profile *
     // a full pair's instructions: M = 145 needs 73, 76 instead of 80 saves 5 % of the kernel)
     int NRv = ((M + 1) / 2 + 15) / 16 * 16;
     if (NRv == 80) NRv = std::max(68, ((M + 1) / 2 + 3) / 4 * 4);
-    if (NRv <= 112) {
+    if (NRv <= BATH_TILING_MAX(BATH_VIT_LANE_NR)) {
       om->vit_NR = NRv;
       om->vit_rw_pitch = 4 * NRv + 16;
       const size_t rowsz = (size_t)om->vit_rw_pitch / 2;

@@ -293,14 +293,13 @@ int launch_vit_lane(bath_hip_ctx *ctx, const bath_hip_oprofile *om, SeqView v, c
   const size_t shmem = (size_t)30 * om->vit_rw_pitch + (size_t)2 * NRv * 2 + 16;
   const int blocks = (int)((ntodo + 255) / 256);
   bool launched = false;
-#define BATH_VITL_CASE(N)                                                                                                              \
+#define BATH_VITL_CASE(N, ...)                                                                                                         \
   if (!launched && NRv == N) {                                                                                                         \
     hipLaunchKernelGGL(vit_lane_kernel<N>, dim3(blocks), dim3(256), shmem, ctx->stream, v, tb, tb.tw2, c, om->lt.d_xwmove, om->lt.d_tjb, d_todo, ntodo, \
                        ntodo_dev, skip_dev, d_sc, d_status, fsc, ssv, wins, wc, cap, kmm);                                                       \
     launched = true;                                                                                                                   \
   }
-  BATH_VITL_CASE(16) BATH_VITL_CASE(32) BATH_VITL_CASE(48) BATH_VITL_CASE(64) BATH_VITL_CASE(68) BATH_VITL_CASE(72) BATH_VITL_CASE(76) BATH_VITL_CASE(80)
-  BATH_VITL_CASE(96) BATH_VITL_CASE(112)
+  BATH_VIT_LANE_NR(BATH_VITL_CASE)
 #undef BATH_VITL_CASE
   if (!launched) { ctx->set_error("lane-per-target Viterbi kernel: unsupported model length"); return BATH_EINVAL; }
   BATH_HIP_TRY(ctx, hipGetLastError());
@@ -315,9 +314,8 @@ int64_t lane_min_nt() {
 }
 
 const char *vit_lane_kernel_name(const bath_hip_oprofile *om) {
-#define BATH_VITL_NAME(N) if (om->vit_NR == N) return "vit_lane_kernel<" #N ">";
-  BATH_VITL_NAME(16) BATH_VITL_NAME(32) BATH_VITL_NAME(48) BATH_VITL_NAME(64) BATH_VITL_NAME(68) BATH_VITL_NAME(72) BATH_VITL_NAME(76) BATH_VITL_NAME(80)
-  BATH_VITL_NAME(96) BATH_VITL_NAME(112)
+#define BATH_VITL_NAME(N, ...) if (om->vit_NR == N) return "vit_lane_kernel<" #N ">";
+  BATH_VIT_LANE_NR(BATH_VITL_NAME)
 #undef BATH_VITL_NAME
   return "vit_lane_kernel<?>";
 }

@@ -1,7 +1,7 @@
 """The frameshift kernels at every per-lane model tiling, against the oracle.
 
-Every frameshift kernel is a template on C, the model nodes a lane owns, picked from the model length M (fs_columns in
-bath_frameshift.hip, odds_columns in bath_fs_odds.hip, BATH_CHAIN_SWITCH in bath_fs_chain.hip): C = 1 2 3 4 6 8 12 16 20, M from
+Every frameshift kernel is a template on C, the model nodes a lane owns, picked from the model length M out of one list
+(BATH_FS_COLUMNS in bath_tilings.hpp, which every frameshift launcher dispatches over): C = 1 2 3 4 6 8 12 16 20, M from
 64 C_prev + 1 to 64 C.  Each C has its own register layout and its own handling of the last, partly filled lane.  FS_M holds the
 smallest and the largest length of each instantiation (the smallest leaves the last used lane partly filled, 257 = 42 * 6 + 5;
 the largest fills all 64 lanes), each checked at the bars of test_frameshift_gpu.py and test_fs_odds_gpu.py:

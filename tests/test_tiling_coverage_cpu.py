@@ -1,8 +1,11 @@
 """CPU tier: the GPU tests reach every per-lane model tiling the kernels are instantiated for.
 
-The option lists are read from the sources (fs_columns / odds_columns / BATH_CHAIN_SWITCH, columns_per_lane / BATH_C_SWITCH, the
-ssv_bath_kernel dispatch, fs_wf_waves) and held against the M lists the GPU modules import: a new instantiation without a test
-fails here, on any machine."""
+Every family's list of instantiations is read from its one definition in bath_tilings.hpp (BATH_FS_COLUMNS, BATH_WAVE_COLUMNS,
+BATH_SSVB_COLUMNS, BATH_VIT_LANE_NR, BATH_MSV_LANE_NR; the wavefront's wave counts from fs_wf_waves) and held against the M lists
+the GPU modules import: a new instantiation without a test fails here, on any machine.  The launchers take their pick, dispatch
+and limits from the same definitions, and no copy of a list is left beside them."""
+import glob
+import os
 import re
 
 import pytest
@@ -23,20 +26,25 @@ def body(text, start):
     return text[i:j if j >= 0 else len(text)]
 
 
-def opt_list(text, start):
-    m = re.search(r"for \(int opt : \{([0-9, ]+)\}\)", body(text, start))
-    assert m, start
-    return [int(x) for x in m.group(1).split(",")]
+def csrc_files():
+    return {os.path.basename(p): open(p).read() for p in sorted(glob.glob(CSRC + "*.hip") + glob.glob(CSRC + "*.hpp") + glob.glob(CSRC + "*.cpp"))}
 
 
-def cases(text, start):
-    return [int(x) for x in re.findall(r"case (\d+):", body(text, start))]
-
-
-def const_nodes(name):
-    m = re.search(r"constexpr int %s = 64 \* (\d+);" % name, src("bath_common.hpp"))
+def tiling(name):
+    """The entries of the list <name>, from its definition: there is one in bath_amd/csrc, in bath_tilings.hpp."""
+    defs = [f for f, text in csrc_files().items() for _ in re.finditer(r"#\s*define\s+%s\b" % name, text)]
+    assert defs == ["bath_tilings.hpp"], (name, defs)
+    m = re.search(r"#define %s\(X, \.\.\.\)((?:[^\n]*\\\n)*[^\n]*)\n" % name, src("bath_tilings.hpp"))
     assert m, name
-    return 64 * int(m.group(1))
+    out = [int(x) for x in re.findall(r"X\((\d+), __VA_ARGS__\)", m.group(1))]
+    assert out and out == sorted(set(out)) and len(out) == m.group(1).count("X("), name      # ascending: the pick takes the first that fits
+    return out
+
+
+def const_nodes(name, lst):
+    """The limit <name> of bath_common.hpp: 64 nodes per lane times the last entry of <lst>, computed from the list."""
+    assert "constexpr int %s = 64 * BATH_TILING_MAX(%s);" % (name, lst) in src("bath_common.hpp"), name
+    return 64 * tiling(lst)[-1]
 
 
 def columns(M, opts):
@@ -53,18 +61,44 @@ def lengths_per_column(opts):
 
 
 def fs_options():
-    fs = opt_list(src("bath_frameshift.hip"), "static int fs_columns(int M)")
-    assert opt_list(src("bath_fs_odds.hip"), "static int odds_columns(int M)") == fs
-    assert cases(src("bath_frameshift.hip"), "#define BATH_FS_SWITCH") == fs
-    assert cases(src("bath_fs_chain.hip"), "#define BATH_CHAIN_SWITCH") == fs
+    """BATH_FS_COLUMNS, and that every frameshift launcher picks from it and dispatches over it."""
+    fs = tiling("BATH_FS_COLUMNS")
+    files = csrc_files()
+    assert [f for f, text in files.items() if "#define BATH_FS_SWITCH" in text] == ["bath_fs_device.hpp"]
+    assert "BATH_TILING_SWITCH(BATH_FS_COLUMNS, Cv," in body(files["bath_fs_device.hpp"], "#define BATH_FS_SWITCH")
+    assert "#define BATH_TILING_CASE(N, ...) case N: { constexpr int CC = N; __VA_ARGS__ } break;" in files["bath_tilings.hpp"]
+    for f in ("bath_frameshift.hip", "bath_fs_chain.hip", "bath_fs_odds.hip", "bath_fs5_odds.hip"):
+        assert "BATH_FS_SWITCH(" in files[f], f
+    for f in ("bath_frameshift.hip", "bath_fs_odds.hip"):
+        assert "BATH_TILING_PICK(BATH_FS_COLUMNS, " in files[f], f
     return fs
+
+
+def sequence(entries):
+    return r"(?<![\w.])" + r"\D{1,24}".join(str(x) for x in entries) + r"(?!\d)"
+
+
+def test_every_tiling_list_is_stated_once():
+    """What held the hand-written copies equal before: there are none.  Outside bath_tilings.hpp no source has a literal option loop,
+    a case ladder on CC or the leading entries of a list in sequence; inside it each list stands once."""
+    lists = {n: tiling(n) for n in ("BATH_FS_COLUMNS", "BATH_WAVE_COLUMNS", "BATH_SSVB_COLUMNS", "BATH_VIT_LANE_NR", "BATH_MSV_LANE_NR")}
+    files = csrc_files()
+    til = files.pop("bath_tilings.hpp")
+    for f, text in files.items():
+        assert "for (int opt : {" not in text, f
+        assert not re.search(r"case \d+:\s*\{\s*constexpr int CC", text), f
+        for n, l in lists.items():
+            assert not re.search(sequence(l[:6]), text), "%s: a copy of %s" % (f, n)
+    assert "for (int opt : {" not in til
+    for n, l in lists.items():
+        assert len(re.findall(sequence(l[:6]), til)) == sum(o[:6] == l[:6] for o in lists.values()), n
 
 
 def test_frameshift_tests_reach_every_tiling_at_both_ends():
     import test_fs_tiling_gpu as t
     fs = fs_options()
     assert t.FS_COLUMNS == fs
-    assert const_nodes("kFsMaxNodes") == t.FS_MAX_NODES == 64 * fs[-1]
+    assert const_nodes("kFsMaxNodes", "BATH_FS_COLUMNS") == t.FS_MAX_NODES == 64 * fs[-1]
     missing = [(c, m) for c, lo, hi in lengths_per_column(fs) for m in (lo, hi) if m not in t.FS_M]
     assert not missing, "frameshift tilings without a test at this model length: %s" % missing
     assert all(columns(m, fs) is not None for m in t.FS_M)
@@ -78,9 +112,10 @@ def test_frameshift_tests_reach_every_tiling_at_both_ends():
 def test_standard_filter_tests_reach_every_tiling():
     import test_filters_gpu as t
     import oracle_lib as ol
-    opts = opt_list(src("bath_filters.hip"), "static int columns_per_lane(int M)")
-    assert cases(src("bath_filters.hip"), "#define BATH_C_SWITCH") == opts
-    assert const_nodes("kCascadeMaxNodes") == 64 * opts[-1]
+    opts = tiling("BATH_WAVE_COLUMNS")
+    filt = src("bath_filters.hip")
+    assert "BATH_TILING_SWITCH(BATH_WAVE_COLUMNS, C," in body(filt, "#define BATH_C_SWITCH") and "BATH_TILING_PICK(BATH_WAVE_COLUMNS, om->M)" in filt
+    assert const_nodes("kCascadeMaxNodes", "BATH_WAVE_COLUMNS") == 64 * opts[-1]
     ms = set()
     for name, idx in t.MODELS:
         ms.add(int(name.split(":")[1]) if name.startswith("synthetic:") else ba.HMM(ol.GOLDEN + "/" + name, idx).M)
@@ -90,19 +125,20 @@ def test_standard_filter_tests_reach_every_tiling():
 
 
 def test_vit_lane_tests_reach_every_instantiation():
-    """vit_lane_kernel<NR> (BATH_VITL_CASE) and msv_lane_kernel<NR> (BATH_MSV_CASE): every instantiation has a test model, the Viterbi
+    """vit_lane_kernel<NR> (BATH_VIT_LANE_NR) and msv_lane_kernel<NR> (BATH_MSV_LANE_NR): every instantiation has a test model, the Viterbi
     ones at the smallest and the largest model that selects them, and the first model beyond the kernel's range is there too."""
     import test_filters_gpu as t
     vit = src("bath_viterbi.hip")
-    nrs = [int(x) for x in re.findall(r"BATH_VITL_CASE\((\d+)\)", vit)]
-    assert nrs and nrs == sorted(set(nrs)) and t.VIT_LANE_NR == nrs
-    assert [int(x) for x in re.findall(r"BATH_VITL_NAME\((\d+)\)", vit)] == nrs            # the names the window sweep reads back
+    nrs = tiling("BATH_VIT_LANE_NR")
+    assert t.VIT_LANE_NR == nrs
+    assert "BATH_VIT_LANE_NR(BATH_VITL_CASE)" in body(vit, "int launch_vit_lane(")
+    assert "BATH_VIT_LANE_NR(BATH_VITL_NAME)" in body(vit, "const char *vit_lane_kernel_name(")       # the names the window sweep reads back
     # the rule that picks NR for a model (bath_profile.hip), restated by t.vit_lane_nr: tied to the source's text here, and on the GPU
     # by the window sweep, which holds the name of the kernel that ran against it
     prof = src("bath_profile.hip")
     assert "int NRv = ((M + 1) / 2 + 15) / 16 * 16;" in prof
     assert "if (NRv == 80) NRv = std::max(68, ((M + 1) / 2 + 3) / 4 * 4);" in prof
-    assert "if (NRv <= 112) {" in prof and max(nrs) == 112
+    assert "if (NRv <= BATH_TILING_MAX(BATH_VIT_LANE_NR)) {" in prof and max(nrs) == 112
     limit = 2 * max(nrs)
     by_nr = {}
     for m in range(1, limit + 1):
@@ -117,10 +153,12 @@ def test_vit_lane_tests_reach_every_instantiation():
     assert any(m % 2 and m < 2 * t.vit_lane_nr(m) for m in t.VIT_LANE_WINDOWS_M)
     # msv_lane_kernel: NR is the SSV tile's -- ceil(M / 2) pairs in steps of 4, one lane per target, at most 76 pairs (152 nodes)
     import oracle_lib as ol
-    msv = [int(x) for x in re.findall(r"BATH_MSV_CASE\((\d+)\)", src("bath_msv_lane.hip"))]
-    assert msv and msv == sorted(set(msv)) and msv[-1] == 76
+    msv = tiling("BATH_MSV_LANE_NR")
+    assert msv[-1] == 76
+    assert "BATH_MSV_LANE_NR(BATH_MSV_CASE)" in body(src("bath_msv_lane.hip"), "int launch_msv_lane(")
+    assert "BATH_MSV_LANE_NR(BATH_MSV_STAGE_CASE)" in src("bath_pipeline.hip")          # the cascade's msv_stage_kernel<NR>
     assert "int NR = ((M + G - 1) / G + 1) / 2;" in prof and "if (G == 1 && NR <= 112) NR = (NR + 3) / 4 * 4;" in prof and "NR = std::max(NR, 16);" in prof
-    assert "om->G != 1 || om->NR > 76" in src("bath_msv_lane.hip")
+    assert "om->G != 1 || om->NR > BATH_TILING_MAX(BATH_MSV_LANE_NR)" in src("bath_msv_lane.hip")
     ms = set(int(x) for x in re.search(r'parametrize\("M", \[([0-9, ]+)\]\)\ndef test_msv_lane_every_register_tiling', open(t.__file__).read()).group(1).split(","))
     ms |= {int(n.split(":")[1]) if n.startswith("synthetic:") else ba.HMM(ol.GOLDEN + "/" + n, i).M for n, i in t.MODELS}     # test_msv_bit_exact
     reached = {max(16, ((m + 1) // 2 + 3) // 4 * 4) for m in ms if m <= 152}
@@ -131,11 +169,11 @@ def test_cascade_and_ssv_window_tests_reach_every_tiling():
     import test_filters_gpu as tf
     import test_pipeline_gpu as tp
     pipe = src("bath_pipeline.hip")
-    lists = re.findall(r"for \(int opt : \{([0-9, ]+)\}\) if \(Cc <= opt\)", pipe)
-    assert len(lists) == 2 and lists[0] == lists[1]                      # the cascade's and bath_hip_ssvfilter_bath's dispatch
-    ssvb = [int(x) for x in lists[0].split(",")]
-    insts = sorted({int(x) for x in re.findall(r"BATH_SSVB_CASE\((\d+)\)\s", pipe)})
-    assert insts == sorted(ssvb)
+    ssvb = tiling("BATH_SSVB_COLUMNS")
+    # one launcher, which picks from the list and dispatches over it, for the cascade and for bath_hip_ssvfilter_bath
+    launch = body(pipe[pipe.rindex("static int launch_ssv_bath("):], "static int launch_ssv_bath(")
+    assert "BATH_TILING_SWITCH(BATH_SSVB_COLUMNS, BATH_TILING_PICK(BATH_SSVB_COLUMNS, om->M)," in launch and "ssv_bath_kernel<CC>" in launch
+    assert len(re.findall(r"ssv_bath_kernel<", pipe)) == 1 and len(re.findall(r"[ (]launch_ssv_bath\(ctx, ", pipe)) == 2
     assert tf.SSV_BATH_COLUMNS == ssvb
     reached = {columns(m, ssvb) for m in tf.SSV_BATH_M}
     assert reached == set(ssvb), "ssv_bath_kernel tilings without a test: %s" % sorted(set(ssvb) - reached)
@@ -143,6 +181,6 @@ def test_cascade_and_ssv_window_tests_reach_every_tiling():
     assert re.search(r"model longer than (\d+) nodes", src("bath_profile.hip")).group(1) == str(64 * ssvb[-1]) == str(max(tf.SSV_BATH_M))
     # the cascade end to end: 6, 12 and every tiling beyond 16 nodes per lane here (the golden-model and 1024-node cascade tests
     # run the others), and the refusal just past its limit
-    wave = opt_list(src("bath_filters.hip"), "static int columns_per_lane(int M)")
-    assert tp.CASCADE_MAX_NODES == const_nodes("kCascadeMaxNodes") == max(tp.CASCADE_M)
+    wave = tiling("BATH_WAVE_COLUMNS")
+    assert tp.CASCADE_MAX_NODES == const_nodes("kCascadeMaxNodes", "BATH_WAVE_COLUMNS") == max(tp.CASCADE_M)
     assert {columns(m, wave) for m in tp.CASCADE_M} >= {c for c in wave if c > 16 or c in (6, 12)}
