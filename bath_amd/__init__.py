@@ -28,6 +28,12 @@ OK, ERANGE, ENORESULT = 0, 16, 19
 KP, K, NEVPARAM = 29, 20, 8
 LOGSUM_TABLE, LOGSUM_EXACT, LOGSUM_TABLE_SERIAL, LOGSUM_CONTEXT = 0, 1, 2, 3
 LOGSUM_ODDS = 4                                     # 3-codon parsers in odds-ratio space (what the reference's --fs runs)
+# Context.set_fs_ensemble: how the frameshift branch samples a multi-domain region's 200 stochastic tracebacks
+ENSEMBLE_SERIAL, ENSEMBLE_STREAMS_HOST, ENSEMBLE_STREAMS_DEVICE = 0, 1, 2
+ENSEMBLE_MODES = {"serial": ENSEMBLE_SERIAL, "streams": ENSEMBLE_STREAMS_HOST, "device": ENSEMBLE_STREAMS_DEVICE}
+ENS_SAMPLES = 200
+ENS_OK, ENS_IMPOSSIBLE, ENS_STEP_CAP, ENS_SEG_OVERFLOW = 0, 1, 2, 3      # per-trace status of the stream modes
+ENS_REGION_OK, ENS_REGION_NO_TRACES = 0, 1
 
 DNA_SYMS = "ACGT-RYMKSWHBVDN*~"
 AMINO_SYMS = "ACDEFGHIKLMNPQRSTVWY-BJZOUX*~"
@@ -202,6 +208,14 @@ ABI = {
     "bath_hip_set_fs_serial": (C.c_int, [_vp, C.c_int]),
     "bath_hip_set_fs_odds": (C.c_int, [_vp, C.c_int]),
     "bath_hip_set_fs5_odds": (C.c_int, [_vp, C.c_int]),
+    "bath_hip_set_fs_ensemble": (C.c_int, [_vp, C.c_int]),
+    "bath_hip_fs_ensemble_counters": (C.c_int, [_vp, _i64p, _i64p, _i64p]),
+    "bath_hip_fs5_region_ensembles": (C.c_int, [_vp, _vp, _vp, C.c_uint32, _i32p, _i32p, _i32p, C.c_int64, _i64p, _i32p, C.c_int64, _i64p]),
+    "bath_selftest_fs_ensemble_seeded": (C.c_int, [C.c_int, _f32p, C.c_float, C.c_float, C.c_float, C.c_int, C.c_int, _f32p, _f32p, C.c_uint32, _i32p, C.c_int, _i32p]),
+    "bath_selftest_fs_ensemble_streams": (C.c_int, [C.c_int, _f32p, C.c_float, C.c_float, C.c_float, C.c_int, C.c_int, _f32p, _f32p, C.c_uint32,
+                                                    _i32p, _i32p, _i32p, C.c_int, _i32p, _i32p, C.c_int, _i32p]),
+    "bath_selftest_rng_jump": (C.c_int, [C.c_uint32, C.c_uint64, C.POINTER(C.c_uint32)]),
+    "bath_selftest_ens_explog": (C.c_int, [C.c_int, _f32p, _f32p, _f32p]),
     "bath_hip_trim": (C.c_int, [_vp]),
     "bath_hip_kernel_times": (C.c_int, [_vp, C.c_int, C.POINTER(KernelTime)]),
     "bath_hip_oprofile_convert": (C.c_int, [_vp, C.POINTER(_Profile), C.POINTER(_vp)]),
@@ -476,6 +490,21 @@ class Context:
         must be 0).  Decoding and optimal accuracy read their matrices unchanged.  False (the default): no change.  With
         set_fs_odds(True) as well, a --fs pass runs the reference's arithmetic everywhere but decoding and optimal accuracy."""
         self._check(lib().bath_hip_set_fs5_odds(self._h, 1 if on else 0), "set_fs5_odds")
+
+    def set_fs_ensemble(self, mode):
+        """How the frameshift branch samples the trace ensemble of a multi-domain region: ENSEMBLE_SERIAL (the default: one
+        random-number stream per region, host threads), ENSEMBLE_STREAMS_HOST (a stream per trace, host threads) or
+        ENSEMBLE_STREAMS_DEVICE (the same walks as 200 lanes of fs_ensemble_kernel; the matrices stay on the device).  Also by name:
+        "serial", "streams", "device".  The two stream modes give identical results; against the serial mode envelopes agree as
+        two seeds of the serial mode do."""
+        self._check(lib().bath_hip_set_fs_ensemble(self._h, ENSEMBLE_MODES.get(mode, mode)), "set_fs_ensemble")
+
+    def fs_ensemble_counters(self):
+        """Since the context was created: regions of the stream modes outside the stream rule (serial walk instead), regions with
+        more segments in a trace than the kernel keeps (host walk instead), bytes of Forward matrices the device mode kept off the host."""
+        a, b, c = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        self._check(lib().bath_hip_fs_ensemble_counters(self._h, C.byref(a), C.byref(b), C.byref(c)), "fs_ensemble_counters")
+        return {"bound_fallbacks": a.value, "overflow_fallbacks": b.value, "matrix_bytes_kept": c.value}
 
     def set_fs_serial(self, on):
         """Measurement aid: the envelopes' Backward wavefront after the Forward one instead of beside it (bath_hip_set_fs_serial)."""
@@ -1302,3 +1331,80 @@ def FS5Envelopes(ctx, om5, dna, logsum=LOGSUM_TABLE, c5_compat=False, want_pp=Fa
     if want_oa:
         out["oa"] = [oa[oao[i]:oao[i + 1]].reshape(-1, M + 1, 3) for i in range(dna.n)]
     return out
+
+
+def FS5ForwardFull(ctx, om5, dna, cfg_len_amino=100):
+    """p7_Forward_Frameshift in the multihit configuration (what the stochastic tracebacks walk): scores, and per sequence the
+    matrix (L+1, M+1, 8) {D, I, M_C0, M_C1..M_C5} and the special-state rows (L+1, 5) {E, N, J, B, C}."""
+    M = om5.M
+    rows = dna.lengths + 1
+    fo = np.zeros(dna.n + 1, dtype=np.int64); np.cumsum(rows * (M + 1) * 8, out=fo[1:])
+    xo = np.zeros(dna.n + 1, dtype=np.int64); np.cumsum(rows * 5, out=xo[1:])
+    sc = np.zeros(dna.n, dtype=np.float32)
+    fwd = np.zeros(int(fo[-1]), dtype=np.float32)
+    xmx = np.zeros(int(xo[-1]), dtype=np.float32)
+    ctx._check(lib().bath_hip_fs5_forward_full(ctx._h, om5._h, dna._h, cfg_len_amino, _f32(sc), _f32(fwd), _f32(xmx)), "fs5_forward_full")
+    return sc, [fwd[fo[i]:fo[i + 1]] for i in range(dna.n)], [xmx[xo[i]:xo[i + 1]] for i in range(dna.n)]
+
+
+def fs_ensemble_loop_scores(L=100):
+    """(xNL, xNM, xE): log loop / move of N, C, J and log 1/2 of the multihit length-L configuration the region stage runs in."""
+    pm = np.float32(3.0) / np.float32(L + 3.0)
+    return (float(np.float32(np.log(np.float64(np.float32(1.0) - pm)))), float(np.float32(np.log(np.float64(pm)))),
+            float(np.float32(-0.69314718055994529)))
+
+
+def _ens_unpack(n, rs, ts, seg, so, env, eo):
+    return [{"status": int(rs[r]), "trace_status": ts[r].copy(), "segments": seg[so[r]:so[r + 1]].copy(),
+             "envelopes": [tuple(int(v) for v in e) for e in env[eo[r]:eo[r + 1]]]} for r in range(n)]
+
+
+def FS5RegionEnsembles(ctx, om5, regions, seed=42):
+    """The multi-domain region stage on its own, in the context's set_fs_ensemble mode: per region a dict with status (ENS_REGION_*),
+    trace_status [200], segments [(trace, i, j, k, m)] in region coordinates (stream modes only) and envelopes [(i, j)]."""
+    n = regions.n
+    rs = np.zeros(max(n, 1), np.int32); ts = np.zeros((max(n, 1), ENS_SAMPLES), np.int32)
+    so = np.zeros(n + 1, np.int64); eo = np.zeros(n + 1, np.int64)
+    max_seg, max_env = 64 * ENS_SAMPLES * max(n, 1), 256 * max(n, 1)
+    while True:
+        seg = np.zeros((max_seg, 5), np.int32); env = np.zeros((max_env, 2), np.int32)
+        p = lambda a: a.ctypes.data_as(_i32p)
+        st = lib().bath_hip_fs5_region_ensembles(ctx._h, om5._h, regions._h, seed, p(rs), p(ts), p(seg), max_seg, _i64(so), p(env), max_env, _i64(eo))
+        if st != ERANGE:
+            break
+        max_seg, max_env = max(max_seg, int(so[-1])), max(max_env, int(eo[-1]))
+    ctx._check(st, "fs5_region_ensembles")
+    return _ens_unpack(n, rs, ts, seg, so, env, eo)
+
+
+def fs_ensemble_streams(M, tsc, xNL, xNM, xE, ireg, Lr, fwd, fx, seed=42):
+    """The host twin of ENSEMBLE_STREAMS_DEVICE on caller-supplied matrices (no GPU): the dict of FS5RegionEnsembles for one region,
+    envelopes in window coordinates (shifted by ireg - 1).  Raises BathError(ERANGE) outside the stream rule."""
+    tsc, fwd, fx = (np.ascontiguousarray(a, np.float32) for a in (tsc, fwd, fx))
+    assert tsc.size >= M * 8 and fwd.size >= (Lr + 1) * (M + 1) * 8 and fx.size >= (Lr + 1) * 5
+    rs, nseg, nenv = C.c_int32(0), C.c_int32(0), C.c_int32(0)
+    ts = np.zeros(ENS_SAMPLES, np.int32); seg = np.zeros((64 * ENS_SAMPLES, 5), np.int32); env = np.zeros((256, 2), np.int32)
+    p = lambda a: a.ctypes.data_as(_i32p)
+    st = lib().bath_selftest_fs_ensemble_streams(M, _f32(tsc), xNL, xNM, xE, ireg, Lr, _f32(fwd), _f32(fx), seed, C.byref(rs), p(ts), p(seg), len(seg), C.byref(nseg),
+                                                 p(env), len(env), C.byref(nenv))
+    if st != OK:
+        raise BathError("fs_ensemble_streams failed (%d)" % st)
+    return {"status": rs.value, "trace_status": ts, "segments": seg[:nseg.value].copy(), "envelopes": [tuple(int(v) for v in e) for e in env[:nenv.value]]}
+
+
+def fs_ensemble_serial(M, tsc, xNL, xNM, xE, ireg, Lr, fwd, fx, seed=42):
+    """The serial ensemble (ENSEMBLE_SERIAL) on caller-supplied matrices (no GPU): its envelopes, window coordinates."""
+    tsc, fwd, fx = (np.ascontiguousarray(a, np.float32) for a in (tsc, fwd, fx))
+    env = np.zeros((256, 2), np.int32); n = C.c_int32(0)
+    st = lib().bath_selftest_fs_ensemble_seeded(M, _f32(tsc), xNL, xNM, xE, ireg, Lr, _f32(fwd), _f32(fx), seed, env.ctypes.data_as(_i32p), len(env), C.byref(n))
+    if st != OK:
+        raise BathError("fs_ensemble_serial failed (%d)" % st)
+    return [tuple(int(v) for v in e) for e in env[:n.value]]
+
+
+def rng_jump(seed, n):
+    """State of the fast generator n steps after seeding, by jump-ahead."""
+    x = C.c_uint32(0)
+    if lib().bath_selftest_rng_jump(seed, n, C.byref(x)) != OK:
+        raise BathError("rng_jump failed")
+    return x.value

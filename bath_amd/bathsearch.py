@@ -40,7 +40,8 @@ OPTIONS = {"-o": str, "--tblout": str, "--fs": "flag", "--cigar": "flag", "--fra
            "--ct": int, "-l": int, "-m": "flag", "-M": "flag", "--strand": str,
            "-E": float, "-T": float, "--incT": float, "-Z": float, "--seed": int,
            "--F1": float, "--F2": float, "--F3": float, "--F4": float, "--max": "flag", "--nobias": "flag", "--nonull2": "flag", "--fsonly": "flag",
-           "--block_length": int, "--gpus": int}
+           "--block_length": int, "--gpus": int,
+           "--ensemble": str}      # an extension, not a reference option (no header line): how --fs samples a multi-domain region's traces
 MAX_GPUS = 16
 # bathsearch options this driver does not implement: refused, never ignored
 REFUSED = ["-h", "--splice", "--exontblout", "--fstblout", "--hmmout", "--acc", "--noali", "--notrans", "--min_intron", "--max_intron",
@@ -99,6 +100,8 @@ def parse_args(argv):
             raise UsageError("option %s requires %s" % (a, b))
     if "--strand" in opts and opts["--strand"] not in ("plus", "minus", "both"):
         raise UsageError("option --strand: expected plus, minus or both")
+    if "--ensemble" in opts and opts["--ensemble"] not in ba.ENSEMBLE_MODES:
+        raise UsageError("option --ensemble: expected serial, streams or device")
     if opts.get("--textw", 150) < 120:
         raise UsageError("option --textw: n >= 120")
     if opts.get("--block_length", 50000) < 50000:
@@ -701,6 +704,7 @@ def _rank_search(argv, opts, hmmfile, seqfile, rank, world, device, dev, chunk_b
         t = time.perf_counter()
         ctx = ba.Context(device)
         ctx.set_fs_strict(True)
+        ctx.set_fs_ensemble(opts.get("--ensemble", "serial"))
         laps["context_s"] = time.perf_counter() - t
         targets = Targets(ctx, seqfile, chunk_bytes, resident_bytes)
         src = _CodesSource(targets)
@@ -862,6 +866,7 @@ def run(argv, stdout=None, chunk_bytes=64 << 20, block_nt=256_000_000, resident_
         ofp.write(output_header(opts, hmmfile, seqfile))
         ctx = ba.Context(device)
         ctx.set_fs_strict(True)
+        ctx.set_fs_ensemble(opts.get("--ensemble", "serial"))
         targets = Targets(ctx, seqfile, chunk_bytes, resident_bytes)
         src = _CodesSource(targets)
         for q in range(nq):

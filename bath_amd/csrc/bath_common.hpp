@@ -170,6 +170,10 @@ struct bath_hip_ctx {
   int fs_strict = 1;                    // frameshift log-sums along the model in the reference's serial order (bit-identical); bath_hip_set_fs_strict(ctx, 0): wavefront scans
   int fs_odds = 0;                      // bath_hip_set_fs_odds(ctx, 1): the 3-codon parsers of the pipeline in odds-ratio space (BATH_LOGSUM_ODDS)
   int fs5_odds = 0;                     // bath_hip_set_fs5_odds(ctx, 1): the 5-codon Forward / Backward (envelopes, regions) in odds-ratio space
+  int fs_ensemble = 0;                  // bath_hip_set_fs_ensemble: how the frameshift branch samples a multi-domain region's traces (BATH_ENSEMBLE_*)
+  // regions of the stream modes that went another way: outside the stream rule (serial ensemble), a trace with more segments than the
+  // kernel keeps (host twin); and the bytes of Forward matrices the device mode did not send to the host (bath_hip_fs_ensemble_counters)
+  std::atomic<int64_t> fs_ens_bound_fallbacks{0}, fs_ens_overflow_fallbacks{0}, fs_ens_bytes_kept{0};
   int fs_serial = -1;                   // envelopes' Backward after Forward on one stream instead of beside it (timing probes); -1: BATH_HIP_FS_SERIAL decides
   uint64_t tabs_uid = 0;                // whose SSV score table sits in scratch[8] (bath_pipeline.hip: uploaded once per profile, not per call)
   const void *tabs_ptr = nullptr;

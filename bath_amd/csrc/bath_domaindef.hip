@@ -372,6 +372,13 @@ static int fs_branch_domains(bath_hip_ctx *ctx, const bath_hip_oprofile *om, con
   // ---- multi-domain regions (p7_domaindef.c:396-455): Forward of the region in the multihit configuration (GPU), ensemble of
   // stochastic tracebacks and clustering (host, bath_ensemble.hip); every cluster is an envelope
   std::vector<std::vector<Env>> found;                                       // written by the ensemble threads: declared BEFORE the joiner, so it outlives the join on every return
+  // bath_hip_set_fs_ensemble.  BATH_ENSEMBLE_STREAMS_DEVICE: the regions' matrices stay in device memory, fs_ensemble_kernel walks the
+  // traces behind the Forward kernel on the same stream, and the ensembles' thread gets statuses and segments in one small copy
+  // (ens_run, read by that thread: declared before the joiner as well); the other modes walk on host threads as before.
+  const int ens_mode = ctx->fs_ensemble;
+  const bool ens_dev = ens_mode == BATH_ENSEMBLE_STREAMS_DEVICE;
+  FsEnsRun ens_run;
+  std::atomic<int> ens_rc{BATH_OK};                                          // a failed copy or synchronize on the ensembles' threads: reported after the join
   // Strict mode, when this is the only context the host holds (host_contexts() == 1; BATH_HIP_FS_CLUSTERS_BESIDE=1|0 forces): the
   // clusters' envelopes go through the kernels on a context of their own as soon as the last ensemble is done, from the ensembles'
   // own thread -- beside the tail of the single-domain batch (its decoding and tracebacks) instead of after it: 62.2-62.5 ms per
@@ -398,6 +405,8 @@ static int fs_branch_domains(bath_hip_ctx *ctx, const bath_hip_oprofile *om, con
     const float *h_sc_live = nullptr;
     std::vector<float> h_sc;
     std::vector<int64_t> foff, xoff;
+    const float pm = (2.0f + 1.0f) / (100.0f + 2.0f + 1.0f);                 // p7_fs_ReconfigLength(L = 100), multihit (nj = 1)
+    const float xNL = (float)std::log((double)(1.0f - pm)), xNM = (float)std::log((double)pm), xE = (float)-kLn2;
     {
       // Strict mode: the regions' Forward is a chain of L x 2M dependent log-sums per region on a few CUs (bath_fs_chain.hip) and
       // the envelope kernels are bound by throughput (bath_fs_wavefront.hip), so the envelopes of the single-domain regions go
@@ -417,29 +426,39 @@ static int fs_branch_domains(bath_hip_ctx *ctx, const bath_hip_oprofile *om, con
         }
       }
       rctx = ctx->fs_strict ? ctx->aux2 : ctx;
-      if (rctx != ctx) { rctx->fs_strict = ctx->fs_strict; rctx->fs_odds = ctx->fs_odds; rctx->fs5_odds = ctx->fs5_odds; rctx->spans_reset(); }
+      if (rctx != ctx) { rctx->fs_strict = ctx->fs_strict; rctx->fs_odds = ctx->fs_odds; rctx->fs5_odds = ctx->fs5_odds; rctx->fs_ensemble = ctx->fs_ensemble; rctx->spans_reset(); }
       bath_hip_seqs view;
       if ((st = fs_gather_view(rctx, dna, rregs, tt.comp, &view, nullptr)) != BATH_OK) { if (rctx != ctx) ctx->set_error(rctx->err); return st; }
       // returns after the launch: a region's ensemble starts as soon as ITS matrix has landed in host memory (h_done[e]), so the
       // tracebacks run while the kernel is still streaming the other regions over PCIe (longest regions first, on both sides)
+      if (ens_dev) st = fs5_region_ensembles_device(rctx, om_fs5, &view, 100, (uint32_t)prm->seed, xNL, xNM, xE, &ens_run);
+      else
       st = fs5_region_forward(rctx, om_fs5, &view, 100, &h_f, &foff, &h_x, &xoff, &h_sc, &h_done, &h_sc_live);      // saveL: the configuration bathsearch starts with
       view.d_data = nullptr; view.d_off = nullptr; view.d_len = nullptr;
       if (st != BATH_OK) { if (rctx != ctx) ctx->set_error(rctx->err); return st; }
     }
-    const float pm = (2.0f + 1.0f) / (100.0f + 2.0f + 1.0f);                 // p7_fs_ReconfigLength(L = 100), multihit (nj = 1)
-    const float xNL = (float)std::log((double)(1.0f - pm)), xNM = (float)std::log((double)pm), xE = (float)-kLn2;
     found.assign(mregs.size(), {});
     // The ensembles are host work (200 dependent tracebacks per region from one random-number stream); the envelopes of the
     // single-domain regions do not depend on them, so their kernels run on the GPU meanwhile.
     { const char *lv = std::getenv("BATH_HIP_FS_LIVE"); if (lv && lv[0] == '0') (void)hipStreamSynchronize(rctx->stream); }
     ensembles = std::thread([&, h_f, h_x, xNL, xNM, xE, foff, xoff, h_done, h_sc_live, rregs] {
+      bool dev_ok = true;                                                      // device mode: the kernel's small copy has landed
+      if (ens_dev) dev_ok = hipSetDevice(ctx->device) == hipSuccess && hipStreamSynchronize(rctx->stream) == hipSuccess;
+      if (!dev_ok) ens_rc = BATH_EFAIL;
       auto work = [&](int64_t first, int64_t step) {
         std::vector<std::pair<int, int>> cl;
         for (size_t e = (size_t)first; e < mregs.size(); e += (size_t)step) {
+          const int Lr = rregs[e].len;
+          if (ens_dev) {                                                       // shift, cluster; a host walk only for a region the kernel could not serve
+            if (!dev_ok) continue;
+            if (fs_ensemble_region_from_device(rctx, ctx, ens_run, (int64_t)e, h5.M, h5.tsc, xNL, xNM, xE, mregs[e].i, Lr, (uint32_t)prm->seed, &cl) != BATH_OK) { ens_rc = BATH_EFAIL; continue; }
+          } else {
           wait_for_flag(h_done + e);                                           // this region's matrix is still on its way
           if (!(h_sc_live[e] > -INFINITY)) continue;                          // Forward underflow: no valid traces for this region (:413)
-          const int Lr = rregs[e].len;
+          if (ens_mode == BATH_ENSEMBLE_SERIAL) {
           if (fs_region_trace_ensemble(h5.M, h5.tsc, xNL, xNM, xE, mregs[e].i, Lr, h_f + foff[e], h_x + xoff[e], &cl, (uint32_t)prm->seed) != BATH_OK) continue;
+          } else if (fs_region_ensemble_host(ctx, ens_mode, h5.M, h5.tsc, xNL, xNM, xE, mregs[e].i, Lr, h_f + foff[e], h_x + xoff[e], &cl, (uint32_t)prm->seed) != BATH_OK) continue;
+          }
           for (const auto &c : cl) {
             const int i2 = std::max(1, c.first), j2 = c.second;               // :449
             if (j2 - i2 + 1 >= 15) found[e].push_back(Env{mregs[e].sel, i2, j2});
@@ -459,7 +478,7 @@ static int fs_branch_domains(bath_hip_ctx *ctx, const bath_hip_oprofile *om, con
         if (!ctx->aux3 && bath_hip_init(ctx->device, &ctx->aux3) != BATH_OK) { cl_rc = BATH_EFAIL; cl_err = "cannot create the context of the clusters' envelopes"; return; }
         mark_internal(ctx->aux3);
         bath_hip_ctx *cctx = ctx->aux3;                                         // the clusters' envelopes on a context of their own
-        cctx->fs_strict = ctx->fs_strict; cctx->fs_odds = ctx->fs_odds; cctx->fs5_odds = ctx->fs5_odds; cctx->spans_reset();
+        cctx->fs_strict = ctx->fs_strict; cctx->fs_odds = ctx->fs_odds; cctx->fs5_odds = ctx->fs5_odds; cctx->fs_ensemble = ctx->fs_ensemble; cctx->spans_reset();
         for (size_t e = 0; e < mregs.size(); e++) cl_envs.insert(cl_envs.end(), found[e].begin(), found[e].end());
         if (!cl_envs.empty() && (cl_rc = run_env_batch(cctx, cl_envs.data(), (int)cl_envs.size(), cl_batch)) != BATH_OK) cl_err = cctx->err;
         eclk.lap("fs:   (clusters' envelope kernels + traces, same thread)");
@@ -469,14 +488,14 @@ static int fs_branch_domains(bath_hip_ctx *ctx, const bath_hip_oprofile *om, con
     if (rctx != ctx && n_single_early > 0) {
       if ((st = run_envelopes(0, n_single_early)) != BATH_OK) {
         (void)hipStreamSynchronize(rctx->stream);
-        for (size_t e = 0; e < mregs.size(); e++) { const_cast<float *>(h_sc_live)[e] = -INFINITY; __atomic_store_n(const_cast<int *>(h_done) + e, 1, __ATOMIC_RELEASE); }
+        if (h_done) for (size_t e = 0; e < mregs.size(); e++) { const_cast<float *>(h_sc_live)[e] = -INFINITY; __atomic_store_n(const_cast<int *>(h_done) + e, 1, __ATOMIC_RELEASE); }
         return st;
       }
       done = n_single_early;
       clk.lap("fs: envelope kernels + traces (single-domain regions, beside the regions' Forward)");
     }
     if (hipStreamSynchronize(rctx->stream) != hipSuccess) {                   // the region Forward itself (the ensembles are already at work)
-      for (size_t e = 0; e < mregs.size(); e++) {                             // release the threads waiting for matrices that will not come
+      for (size_t e = 0; h_done && e < mregs.size(); e++) {                   // release the threads waiting for matrices that will not come
         const_cast<float *>(h_sc_live)[e] = -INFINITY;
         __atomic_store_n(const_cast<int *>(h_done) + e, 1, __ATOMIC_RELEASE);
       }
@@ -499,6 +518,7 @@ static int fs_branch_domains(bath_hip_ctx *ctx, const bath_hip_oprofile *om, con
   }
   if (ensembles.joinable()) {
     ensembles.join();
+    if (ens_rc.load() != BATH_OK) { ctx->set_error("the device ensemble of the multi-domain regions failed (stream synchronize or a region's copy to the host)"); return ens_rc.load(); }
     for (size_t e = 0; e < mregs.size(); e++) envs.insert(envs.end(), found[e].begin(), found[e].end());
     clk.lap("fs: ensembles (host threads)");
   }

@@ -24,6 +24,7 @@
 
 #include "bath_common.hpp"
 #include "bath_launch.hpp"
+#include "bath_fs_ens_walk.hpp"
 
 namespace {
 
@@ -451,6 +452,85 @@ int bath::fs_region_trace_ensemble(int M, const float *tsc, float xNL, float xNM
   return BATH_OK;
 }
 
+// ---- the per-trace-stream modes (bath_hip_set_fs_ensemble: BATH_ENSEMBLE_STREAMS_HOST / _DEVICE): trace t of a region draws from
+// the state the region's generator has after t * 2^20 steps, and walks with bath_fs_ens_walk.hpp's ens_walk, the source the
+// device kernel compiles too.
+
+// The generator's state n steps after <x>: x -> a x + c composed n times, by repeated squaring of the affine map (mod 2^32)
+uint32_t bath::ens_rng_jump(uint32_t x, uint64_t n) {
+  uint32_t a = 69069u, c = 1u, A = 1u, Cc = 0u;           // (A, Cc): the map built so far; (a, c): the current power of two
+  for (; n; n >>= 1) {
+    if (n & 1) { A = a * A; Cc = a * Cc + c; }
+    c = (a + 1u) * c; a = a * a;
+  }
+  return A * x + Cc;
+}
+
+void bath::fs_ensemble_start_states(uint32_t seed, uint32_t *states) {
+  const FastRng r0(region_seed(seed));
+  for (int t = 0; t < kEnsSamples; t++) states[t] = ens_rng_jump(r0.x, (uint64_t)t << kEnsStreamLog2);
+}
+
+// What the walks of one region left (host twin or kernel) -> its envelopes.  status[200]; nseg[200]; seg[200][max_seg][4] in region
+// coordinates, a trace's last domain first.  A region with any trace that is not ok has no valid traces (the serial code's
+// `return BATH_OK` with an empty list).  segs_out (optional): (trace, i, j, k, m) in p7_trace_fs_Index's order, region coordinates.
+int bath::fs_ensemble_consume(const int32_t *status, const int32_t *nseg, const int32_t *seg, int max_seg, int ireg, std::vector<std::pair<int, int>> *env,
+                              std::vector<int32_t> *segs_out) {
+  env->clear();
+  if (segs_out) segs_out->clear();
+  for (int t = 0; t < kEnsSamples; t++) if (status[t] != kEnsOk) return kEnsRegionNoTraces;
+  std::vector<Seg> sp;
+  for (int t = 0; t < kEnsSamples; t++)
+    for (int d = nseg[t] - 1; d >= 0; d--) {
+      const int32_t *g = seg + ((size_t)t * (size_t)max_seg + (size_t)d) * 4;
+      sp.push_back(Seg{t, g[0] + ireg - 1, g[1] + ireg - 1, g[2], g[3], 0.f});
+      if (segs_out) { const int32_t r[5] = {t, g[0], g[1], g[2], g[3]}; segs_out->insert(segs_out->end(), r, r + 5); }
+    }
+  cluster_segments(sp, kEnsSamples, true, env);
+  return kEnsRegionOk;
+}
+
+// the host twin: the 200 walks of one region on the calling thread (seg: [200][kEnsHostMaxSeg][4])
+void bath::fs_ensemble_walk_host(int M, const float *tsc, float xNL, float xNM, float xE, int Lr, const float *fwd, const float *fx, uint32_t seed,
+                                 int32_t *status, int32_t *nseg, int32_t *seg) {
+  uint32_t states[kEnsSamples];
+  fs_ensemble_start_states(seed, states);
+  for (int t = 0; t < kEnsSamples; t++)
+    status[t] = ens_walk(M, tsc, xNL, xNM, xE, Lr, fwd, fx, states[t], seg + (size_t)t * kEnsHostMaxSeg * 4, kEnsHostMaxSeg, nseg + t);
+}
+
+int bath::fs_region_trace_ensemble_streams(int M, const float *tsc, float xNL, float xNM, float xE, int ireg, int Lr, const float *fwd, const float *fx,
+                                           std::vector<std::pair<int, int>> *env, uint32_t seed, int *region_status, std::vector<int32_t> *segs_out,
+                                           int32_t *trace_status) {
+  env->clear();
+  if (!ens_streams_fit(Lr, M)) return BATH_ERANGE;          // the caller falls back to the serial ensemble
+  std::vector<int32_t> buf((size_t)kEnsSamples * (2 + kEnsHostMaxSeg * 4));
+  int32_t *status = buf.data(), *nseg = status + kEnsSamples, *seg = nseg + kEnsSamples;
+  fs_ensemble_walk_host(M, tsc, xNL, xNM, xE, Lr, fwd, fx, seed, status, nseg, seg);
+  if (trace_status) std::copy(status, status + kEnsSamples, trace_status);
+  for (int t = 0; t < kEnsSamples; t++) if (status[t] == kEnsSegOverflow) return BATH_ERANGE;
+  const int rs = fs_ensemble_consume(status, nseg, seg, kEnsHostMaxSeg, ireg, env, segs_out);
+  if (region_status) *region_status = rs;
+  return BATH_OK;
+}
+
+// One region on a host thread in mode BATH_ENSEMBLE_SERIAL or BATH_ENSEMBLE_STREAMS_HOST, with the stream mode's way out: a region
+// outside the stream rule, or with more segments in a trace than the twin keeps, gets the serial ensemble (counted in <counters>).
+// The serial walk keeps no segments and cannot tell "no valid traces" from "no clusters": *region_status is 0 then.
+int bath::fs_region_ensemble_host(bath_hip_ctx *counters, int mode, int M, const float *tsc, float xNL, float xNM, float xE, int ireg, int Lr,
+                                  const float *fwd, const float *fx, std::vector<std::pair<int, int>> *env, uint32_t seed, int *region_status,
+                                  std::vector<int32_t> *segs_out, int32_t *trace_status) {
+  if (mode != BATH_ENSEMBLE_SERIAL) {
+    const int st = fs_region_trace_ensemble_streams(M, tsc, xNL, xNM, xE, ireg, Lr, fwd, fx, env, seed, region_status, segs_out, trace_status);
+    if (st != BATH_ERANGE) return st;
+    if (counters) { if (ens_streams_fit(Lr, M)) counters->fs_ens_overflow_fallbacks++; else counters->fs_ens_bound_fallbacks++; }
+  }
+  if (segs_out) segs_out->clear();
+  if (trace_status) std::fill(trace_status, trace_status + kEnsSamples, 0);
+  if (region_status) *region_status = kEnsRegionOk;
+  return fs_region_trace_ensemble(M, tsc, xNL, xNM, xE, ireg, Lr, fwd, fx, env, seed);
+}
+
 
 // ---- self-test hooks (include/bath_hip.h): the restated easel pieces and the frameshift ensemble, callable without a GPU
 extern "C" int bath_selftest_fs_ensemble(int M, const float *tsc, float xNL, float xNM, float xE, int ireg, int Lr, const float *fwd, const float *fx,
@@ -458,6 +538,17 @@ extern "C" int bath_selftest_fs_ensemble(int M, const float *tsc, float xNL, flo
   if (!tsc || !fwd || !fx || !env || !n_env || M < 1 || Lr < 1 || max_env < 0) return BATH_EINVAL;
   std::vector<std::pair<int, int>> cl;
   const int st = bath::fs_region_trace_ensemble(M, tsc, xNL, xNM, xE, ireg, Lr, fwd, fx, &cl);
+  if (st != BATH_OK) return st;
+  *n_env = (int32_t)cl.size();
+  for (size_t e = 0; e < cl.size() && (int)e < max_env; e++) { env[2 * e] = cl[e].first; env[2 * e + 1] = cl[e].second; }
+  return BATH_OK;
+}
+
+extern "C" int bath_selftest_fs_ensemble_seeded(int M, const float *tsc, float xNL, float xNM, float xE, int ireg, int Lr, const float *fwd, const float *fx,
+                                                uint32_t seed, int32_t *env, int max_env, int32_t *n_env) {
+  if (!tsc || !fwd || !fx || !env || !n_env || M < 1 || Lr < 1 || max_env < 0) return BATH_EINVAL;
+  std::vector<std::pair<int, int>> cl;
+  const int st = bath::fs_region_trace_ensemble(M, tsc, xNL, xNM, xE, ireg, Lr, fwd, fx, &cl, seed);
   if (st != BATH_OK) return st;
   *n_env = (int32_t)cl.size();
   for (size_t e = 0; e < cl.size() && (int)e < max_env; e++) { env[2 * e] = cl[e].first; env[2 * e + 1] = cl[e].second; }
@@ -495,5 +586,41 @@ extern "C" int bath_selftest_fchoose(uint32_t seed, const float *p, int n, int d
     }
     out[d] = r;
   }
+  return BATH_OK;
+}
+
+// state of FastRng(seed) after n steps, by jump-ahead (bath_selftest_rng_stream's value n - 1 is state / 2^32)
+extern "C" int bath_selftest_rng_jump(uint32_t seed, uint64_t n, uint32_t *state) {
+  if (!state) return BATH_EINVAL;
+  *state = bath::ens_rng_jump(FastRng(seed).x, n);
+  return BATH_OK;
+}
+
+// the stream modes' expf / logf on the host (the device compiles the same source): for accuracy measurements
+extern "C" int bath_selftest_ens_explog(int n, const float *x, float *e, float *l) {
+  if (n < 0 || !x) return BATH_EINVAL;
+  for (int q = 0; q < n; q++) { if (e) e[q] = bath::ens_expf(x[q]); if (l) l[q] = bath::ens_logf(x[q]); }
+  return BATH_OK;
+}
+
+// The host twin of BATH_ENSEMBLE_STREAMS_DEVICE on caller-supplied matrices.  trace_status[200] (or NULL); seg: up to max_seg records
+// (trace, i, j, k, m), region coordinates, p7_trace_fs_Index's order, *n_seg their number (all of them, also beyond max_seg);
+// env: up to max_env (i, j) pairs in window coordinates (shifted by ireg - 1); *region_status: 0 ok, 1 no valid traces.
+// BATH_ERANGE: the region is outside the stream rule (4 step_cap >= 2^20) or a trace has more than 64 segments -- the
+// pipeline runs the serial ensemble on such a region.
+extern "C" int bath_selftest_fs_ensemble_streams(int M, const float *tsc, float xNL, float xNM, float xE, int ireg, int Lr, const float *fwd, const float *fx,
+                                                 uint32_t seed, int32_t *region_status, int32_t *trace_status, int32_t *seg, int max_seg, int32_t *n_seg,
+                                                 int32_t *env, int max_env, int32_t *n_env) {
+  if (!tsc || !fwd || !fx || !n_env || !n_seg || !region_status || M < 1 || Lr < 1 || max_env < 0 || max_seg < 0 || (max_seg > 0 && !seg) || (max_env > 0 && !env)) return BATH_EINVAL;
+  std::vector<std::pair<int, int>> cl;
+  std::vector<int32_t> segs;
+  int rs = 0;
+  const int st = bath::fs_region_trace_ensemble_streams(M, tsc, xNL, xNM, xE, ireg, Lr, fwd, fx, &cl, seed, &rs, &segs, trace_status);
+  if (st != BATH_OK) return st;
+  *region_status = rs;
+  *n_seg = (int32_t)(segs.size() / 5);
+  std::copy(segs.begin(), segs.begin() + (size_t)std::min<int>(*n_seg, max_seg) * 5, seg);
+  *n_env = (int32_t)cl.size();
+  for (size_t e = 0; e < cl.size() && (int)e < max_env; e++) { env[2 * e] = cl[e].first; env[2 * e + 1] = cl[e].second; }
   return BATH_OK;
 }

@@ -1323,7 +1323,7 @@ int bath_hip_fsprofile::ensure_len(int maxL_amino) const {
 
 extern "C" void bath_hip_fsprofile_destroy(bath_hip_fsprofile *om) {
   if (!om) return;
-  for (void *p : {(void *)om->d_codons, (void *)om->d_indel, (void *)om->d_rsc, (void *)om->d_tf, (void *)om->d_tb, (void *)om->d_logsum, (void *)om->d_loop[0], (void *)om->d_loop[1],
+  for (void *p : {(void *)om->d_codons, (void *)om->d_indel, (void *)om->d_rsc, (void *)om->d_tf, (void *)om->d_tb, (void *)om->d_logsum, (void *)om->d_tsc, (void *)om->d_loop[0], (void *)om->d_loop[1],
                   (void *)om->d_move[0], (void *)om->d_move[1], (void *)om->d_odds_rsc, (void *)om->d_odds_tf, (void *)om->d_odds_tb})
     if (p) (void)hipFree(p);
   for (void *p : om->retired) (void)hipFree(p);
@@ -1374,6 +1374,7 @@ extern "C" int bath_hip_fsprofile_convert(bath_hip_ctx *ctx, const bath_fs_profi
   BATH_HIP_TRY(ctx, up(&om->d_tf, tf));
   BATH_HIP_TRY(ctx, up(&om->d_tb, tb));
   BATH_HIP_TRY(ctx, up(&om->d_logsum, tbl));
+  BATH_HIP_TRY(ctx, up(&om->d_tsc, om->h_tsc));
   int st = om->ensure_len(4096);
   if (st != BATH_OK) { bath_hip_fsprofile_destroy(om); return st; }
   *ret = om;
@@ -1904,7 +1905,9 @@ int bath::fs5_envelopes_ex(bath_hip_ctx *ctx, const bath_hip_fsprofile *om, cons
 // fwd: (L+1) x (M+1) x {D, I, M_C0, M_C1..M_C5}; xmx: (L+1) x {E,N,J,B,C}.  sc[e] = -inf: no path (the region is dropped).
 int bath::fs5_region_forward(bath_hip_ctx *ctx, const bath_hip_fsprofile *om, const bath_hip_seqs *dna, int cfg_len_amino,
                              const float **fwd, std::vector<int64_t> *fwd_off, const float **xmx, std::vector<int64_t> *xmx_off, std::vector<float> *sc,
-                             const int **done_flags, const float **sc_live) {
+                             const int **done_flags, const float **sc_live, FsRegionDev *dev) {
+  // dev != nullptr (BATH_ENSEMBLE_STREAMS_DEVICE): the matrices, rows and scores stay in device memory for fs_ensemble_kernel, which
+  // follows on ctx->stream -- no page-locked destination, no flags; returns right after the launch with *dev filled in.
   // done_flags != nullptr: return right after the launch.  *done_flags (page-locked, one int per region) turns 1 when that region's
   // matrix, rows and score (*sc_live) have landed in host memory; the caller synchronises the stream before it reuses the buffers.
   const int64_t n = dna->n;
@@ -1922,9 +1925,9 @@ int bath::fs5_region_forward(bath_hip_ctx *ctx, const bath_hip_fsprofile *om, co
   // go, so it writes them straight into page-locked host memory: the transfer rides along with the computation (32 B/cell,
   // ~27 GB/s on the bench block) instead of following it as a copy of its own.  BATH_HIP_FS_REGION_COPY=1: HBM first, then copy.
   const size_t x_bytes = ((size_t)xoff[(size_t)n] * 4 + 255) / 256 * 256;     // then: done flags [n], scores [n]
-  BATH_HIP_TRY(ctx, ctx->pinned[2].reserve((size_t)foff[(size_t)n] * 4 + 64, true)); BATH_HIP_TRY(ctx, ctx->pinned[3].reserve(x_bytes + (size_t)n * 8 + 64, true));
+  if (!dev) { BATH_HIP_TRY(ctx, ctx->pinned[2].reserve((size_t)foff[(size_t)n] * 4 + 64, true)); BATH_HIP_TRY(ctx, ctx->pinned[3].reserve(x_bytes + (size_t)n * 8 + 64, true)); }
   float *d_f = nullptr, *d_fx = nullptr;
-  {
+  if (!dev) {
     const char *e = std::getenv("BATH_HIP_FS_REGION_COPY");
     void *pf = nullptr, *px = nullptr;
     if (!(e && e[0] == '1') && hipHostGetDevicePointer(&pf, ctx->pinned[2].p, 0) == hipSuccess && hipHostGetDevicePointer(&px, ctx->pinned[3].p, 0) == hipSuccess) {
@@ -1932,17 +1935,18 @@ int bath::fs5_region_forward(bath_hip_ctx *ctx, const bath_hip_fsprofile *om, co
     } else (void)hipGetLastError();
   }
   const bool direct = d_f != nullptr;
-  int *h_done = reinterpret_cast<int *>(static_cast<char *>(ctx->pinned[3].p) + x_bytes);
-  float *h_sc = reinterpret_cast<float *>(h_done + n);
+  int *h_done = dev ? nullptr : reinterpret_cast<int *>(static_cast<char *>(ctx->pinned[3].p) + x_bytes);
+  float *h_sc = h_done ? reinterpret_cast<float *>(h_done + n) : nullptr;
   const bool live = direct && done_flags != nullptr;
   if (done_flags) { *done_flags = h_done; *sc_live = h_sc; }
-  for (int64_t i = 0; i < n; i++) h_done[i] = 0;
+  for (int64_t i = 0; h_done && i < n; i++) h_done[i] = 0;
   BATH_HIP_TRY(ctx, b_sc.reserve((size_t)n * 3 * sizeof(float)));            // BEFORE its pointer is taken: on a fresh context it is null, and a growing buffer moves
   int *d_done = live ? reinterpret_cast<int *>(reinterpret_cast<char *>(d_fx) + x_bytes) : nullptr;
   float *d_sc_out = live ? reinterpret_cast<float *>(d_done + n) : b_sc.as<float>();
-  if (!direct) {
-    BATH_HIP_TRY(ctx, b_f.reserve((size_t)foff[(size_t)n] * 4 + 64)); BATH_HIP_TRY(ctx, b_fx.reserve((size_t)xoff[(size_t)n] * 4 + 64));
-    d_f = b_f.as<float>(); d_fx = b_fx.as<float>();
+  if (!direct) {                             // (device destination: buffers of its own -- the envelope batches of the same context use [15] / [18])
+    DevBuf &bf = dev ? ctx->scratch[53] : b_f, &bx = dev ? ctx->scratch[54] : b_fx;
+    BATH_HIP_TRY(ctx, bf.reserve((size_t)foff[(size_t)n] * 4 + 64)); BATH_HIP_TRY(ctx, bx.reserve((size_t)xoff[(size_t)n] * 4 + 64));
+    d_f = bf.as<float>(); d_fx = bx.as<float>();
   }
   BATH_HIP_TRY(ctx, b_off.reserve((size_t)(n + 1) * 3 * sizeof(int64_t)));
   int64_t *d_foff = b_off.as<int64_t>(), *d_xoff = d_foff + (n + 1);
@@ -1953,8 +1957,8 @@ int bath::fs5_region_forward(bath_hip_ctx *ctx, const bath_hip_fsprofile *om, co
   const int grid_dp = fs_grid_dp(ctx, n);
   const float tE = (float)-0.69314718055994529;                               // multihit: E->C and E->J both log 1/2 (modelconfig.c:825-831)
   const int mode = ctx->fs_strict ? BATH_LOGSUM_TABLE_SERIAL : BATH_LOGSUM_TABLE;
-  FsJobs jq[1];
-  if ((st = fs_schedule(ctx, dna, 1, jq)) != BATH_OK) return st;
+  FsJobs jq[2];                                                                // [1]: the ensemble kernel's (device destination)
+  if ((st = fs_schedule(ctx, dna, dev ? 2 : 1, jq)) != BATH_OK) return st;
   if (ctx->fs5_odds) {                                                         // bath_hip_set_fs5_odds: before fs_strict
     const int s1 = ctx->span_begin("fs5_fwd_odds_kernel(regions)", ctx->stream, (double)(foff[(size_t)n] / 8), (double)(foff[(size_t)n] / 8) * 32.0);
     if ((st = launch_fs5_odds(ctx, ctx->stream, om, dna, kFs5OddsRegionFwd, d_sc_out, d_f, d_foff, d_fx, d_xoff, cfg_len_amino, jq[0], d_done)) != BATH_OK) return st;
@@ -1972,6 +1976,7 @@ int bath::fs5_region_forward(bath_hip_ctx *ctx, const bath_hip_fsprofile *om, co
     ctx->span_end(s1, ctx->stream);
   }))
   BATH_HIP_TRY(ctx, hipGetLastError());
+  if (dev) { *dev = FsRegionDev{d_f, d_fx, d_foff, d_xoff, d_sc_out, jq[1].order, jq[1].counter}; return BATH_OK; }
   sc->resize((size_t)n);
   *fwd = ctx->pinned[2].as<float>(); *xmx = ctx->pinned[3].as<float>();      // page-locked: the matrices are a few MB per region
   if (live) return BATH_OK;                                                  // the flags tell the rest

@@ -22,6 +22,7 @@ struct bath_hip_fsprofile {
   float *d_tb = nullptr;         // [(M+2)][8] backward-ordered transitions per node
   float *d_logsum = nullptr;     // [16000]
   std::vector<float> h_tsc;      // [M*8] generic log transitions (OA traceback deltas on the host)
+  float *d_tsc = nullptr;        // ... and on the device (fs_ensemble_kernel's stochastic tracebacks)
   std::vector<uint8_t> h_codons; // [(M+1)*maxcodons] best amino acid per (node, quasi-codon) (null2 along a trace)
   uint8_t *d_codons = nullptr;   // the same on the device (5-codon profiles)
   uint8_t *d_indel = nullptr;    // [(M+1)*maxcodons] indel-type label of that choice (hmmer.h:259-276), for the alignment display

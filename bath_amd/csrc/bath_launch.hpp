@@ -144,9 +144,37 @@ int region_trace_ensemble(const bath_hip_oprofile *om, int cfg_L, const uint8_t 
 
 int fs_region_trace_ensemble(int M, const float *tsc, float xNL, float xNM, float xE, int ireg, int Lr, const float *fwd, const float *fx,
                              std::vector<std::pair<int, int>> *env, uint32_t seed = 42);
+// ---- the per-trace-stream ensemble modes (bath_hip_set_fs_ensemble; bath_fs_ens_walk.hpp is the walk, bath_fs_ensemble.hip the kernel)
+uint32_t ens_rng_jump(uint32_t x, uint64_t n);                           // the fast generator's state n steps after x
+void fs_ensemble_start_states(uint32_t seed, uint32_t *states /* [200] */);   // trace t starts t * 2^20 steps into the region's generator
+void fs_ensemble_walk_host(int M, const float *tsc, float xNL, float xNM, float xE, int Lr, const float *fwd, const float *fx, uint32_t seed,
+                           int32_t *status, int32_t *nseg, int32_t *seg);
+int fs_ensemble_consume(const int32_t *status, const int32_t *nseg, const int32_t *seg, int max_seg, int ireg, std::vector<std::pair<int, int>> *env,
+                        std::vector<int32_t> *segs_out = nullptr);
+// BATH_ERANGE: outside the stream rule or more than kEnsHostMaxSeg segments in a trace (the caller runs the serial ensemble)
+int fs_region_trace_ensemble_streams(int M, const float *tsc, float xNL, float xNM, float xE, int ireg, int Lr, const float *fwd, const float *fx,
+                                     std::vector<std::pair<int, int>> *env, uint32_t seed = 42, int *region_status = nullptr,
+                                     std::vector<int32_t> *segs_out = nullptr, int32_t *trace_status = nullptr);
+// where fs5_region_forward left the regions in DEVICE memory, and the job list of the kernel that reads them next (longest first)
+struct FsRegionDev { const float *d_fwd, *d_fx; const int64_t *d_foff, *d_xoff; const float *d_sc; const int32_t *job_order; unsigned *job_counter; };
 int fs5_region_forward(bath_hip_ctx *ctx, const bath_hip_fsprofile *om5, const bath_hip_seqs *dna, int cfg_len_amino,
                        const float **fwd, std::vector<int64_t> *fwd_off, const float **xmx, std::vector<int64_t> *xmx_off, std::vector<float> *sc,
-                       const int **done_flags, const float **sc_live);
+                       const int **done_flags, const float **sc_live, FsRegionDev *dev = nullptr);
+// BATH_ENSEMBLE_STREAMS_DEVICE: the regions' multihit Forward into device memory and fs_ensemble_kernel behind it on ctx->stream;
+// returns after queueing.  Once the stream is synchronized: out = per region status[200], nseg[200], seg[200][kEnsMaxSeg][4]
+// (kFsEnsOutInts ints), sc = the regions' Forward scores, both page-locked.  The matrices stay where *dev says until the
+// context's next region stage (fs_ensemble_fetch_region copies one region's to the host: the fallbacks).
+constexpr int kFsEnsOutInts = 200 * (2 + 8 * 4);
+struct FsEnsRun { const int32_t *out = nullptr; const float *sc = nullptr; FsRegionDev dev{}; std::vector<int64_t> foff, xoff; };
+int fs5_region_ensembles_device(bath_hip_ctx *ctx, const bath_hip_fsprofile *om5, const bath_hip_seqs *dna, int cfg_len_amino, uint32_t seed,
+                                float xNL, float xNM, float xE, FsEnsRun *run);
+int fs_region_ensemble_host(bath_hip_ctx *counters, int mode, int M, const float *tsc, float xNL, float xNM, float xE, int ireg, int Lr,
+                            const float *fwd, const float *fx, std::vector<std::pair<int, int>> *env, uint32_t seed, int *region_status = nullptr,
+                            std::vector<int32_t> *segs_out = nullptr, int32_t *trace_status = nullptr);
+int fs_ensemble_region_from_device(bath_hip_ctx *ctx, bath_hip_ctx *counters, const FsEnsRun &run, int64_t e, int M, const float *tsc, float xNL, float xNM, float xE,
+                                   int ireg, int Lr, uint32_t seed, std::vector<std::pair<int, int>> *env, int *region_status = nullptr,
+                                   std::vector<int32_t> *segs_out = nullptr, int32_t *trace_status = nullptr);
+int fs_ensemble_fetch_region(bath_hip_ctx *ctx, const FsEnsRun &run, int64_t e, std::vector<float> *fwd, std::vector<float> *fx);
 
 // ---- six-frame translation + ORF work list (bath_orfs.hip)
 struct OrfRec {                   // one ORF of the length-sorted work list

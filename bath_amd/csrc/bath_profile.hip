@@ -245,6 +245,27 @@ extern "C" int bath_hip_set_fs5_odds(bath_hip_ctx *ctx, int on) {
   return BATH_OK;
 }
 
+extern "C" int bath_hip_set_fs_ensemble(bath_hip_ctx *ctx, int mode) {
+  if (!ctx) return BATH_EINVAL;
+  if (mode != BATH_ENSEMBLE_SERIAL && mode != BATH_ENSEMBLE_STREAMS_HOST && mode != BATH_ENSEMBLE_STREAMS_DEVICE) { ctx->set_error("bath_hip_set_fs_ensemble: unknown mode " + std::to_string(mode)); return BATH_EINVAL; }
+  ctx->fs_ensemble = mode;
+  for (bath_hip_ctx *l : ctx->lanes) l->fs_ensemble = mode;
+  return BATH_OK;
+}
+
+extern "C" int bath_hip_fs_ensemble_counters(bath_hip_ctx *ctx, int64_t *bound_fallbacks, int64_t *overflow_fallbacks, int64_t *matrix_bytes_kept) {
+  if (!ctx) return BATH_EINVAL;
+  int64_t b = 0, o = 0, k = 0;
+  for (const bath_hip_ctx *c : {(const bath_hip_ctx *)ctx, (const bath_hip_ctx *)ctx->aux2}) {      // (the regions' stage runs on aux2 in strict mode)
+    if (!c) continue;
+    b += c->fs_ens_bound_fallbacks.load(); o += c->fs_ens_overflow_fallbacks.load(); k += c->fs_ens_bytes_kept.load();
+  }
+  if (bound_fallbacks) *bound_fallbacks = b;
+  if (overflow_fallbacks) *overflow_fallbacks = o;
+  if (matrix_bytes_kept) *matrix_bytes_kept = k;
+  return BATH_OK;
+}
+
 // ------------------------------------------------------------------------------------------ oprofile
 
 extern "C" void bath_hip_oprofile_destroy(bath_hip_oprofile *om) {

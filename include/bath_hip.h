@@ -141,6 +141,25 @@ int         bath_hip_set_fs_odds(bath_hip_ctx *ctx, int on);
  * 0 (the default): no change.  An explicit BATH_LOGSUM_ODDS on the fs5 entry points stays refused.  The reference's whole --fs
  * arithmetic is bath_hip_set_fs_odds(ctx, 1) plus bath_hip_set_fs5_odds(ctx, 1).  A null ctx returns BATH_EINVAL. */
 int         bath_hip_set_fs5_odds(bath_hip_ctx *ctx, int on);
+/* How the frameshift branch samples the 200 stochastic tracebacks of a multi-domain region (region_trace_ensemble_frameshift,
+ * p7_domaindef.c:891-958).
+ *   BATH_ENSEMBLE_SERIAL (0, the default): one random-number stream per region, trace t starts where trace t-1 stopped drawing; on
+ *     host threads, from Forward matrices the kernel streams into page-locked host memory.  The reference's order of draws.
+ *   BATH_ENSEMBLE_STREAMS_HOST (1): trace t starts from the state the region's generator has after t * 2^20 steps (trace 0 where
+ *     the serial stream starts), and the walk uses its own expf / logf (IEEE double arithmetic, the same float on host and device);
+ *     on host threads.  The twin of mode 2: same traces, same segments, same envelopes.
+ *   BATH_ENSEMBLE_STREAMS_DEVICE (2): the same walks as 200 lanes of fs_ensemble_kernel, one block per region, on matrices that stay
+ *     in device memory; only statuses and segments come back.
+ * Modes 1 and 2 sample the same posterior with other random numbers than mode 0: envelopes agree with mode 0's as two seeds of
+ * mode 0 agree with each other, not bit for bit.  A region outside the stream rule (4 (4 (Lr + M) + 64) >= 2^20) takes the serial
+ * path; in mode 2 a region with a trace of more than 8 segments takes mode 1's.  bath_hip_fs_ensemble_counters counts both (since
+ * the context was created), and the bytes of Forward matrices mode 2 did not send to the host.  The standard branch's ensemble
+ * (region_trace_ensemble) is host code in every mode.  Unknown mode or null ctx: BATH_EINVAL. */
+#define BATH_ENSEMBLE_SERIAL 0
+#define BATH_ENSEMBLE_STREAMS_HOST 1
+#define BATH_ENSEMBLE_STREAMS_DEVICE 2
+int         bath_hip_set_fs_ensemble(bath_hip_ctx *ctx, int mode);
+int         bath_hip_fs_ensemble_counters(bath_hip_ctx *ctx, int64_t *bound_fallbacks, int64_t *overflow_fallbacks, int64_t *matrix_bytes_kept);
 /* Measurement aid: 1 = the envelope stage (bath_hip_fs5_envelopes and the domain stage's batches) runs its Backward wavefront AFTER the
  * Forward wavefront on the same stream instead of beside it, so that a kernel's HIP-event span is its time alone on the chip
  * (bench.py: fs.roofline.alone); 0 = side by side (the default); -1 = whatever BATH_HIP_FS_SERIAL says.  Results do not change. */
@@ -664,6 +683,18 @@ int bath_hip_fs5_envelopes_x(bath_hip_ctx *ctx, const bath_hip_fsprofile *om5, c
 int bath_hip_fs5_forward_full(bath_hip_ctx *ctx, const bath_hip_fsprofile *om5, const bath_hip_seqs *dna, int cfg_len_amino,
                               float *sc, float *fwd, float *xmx);
 
+/* The multi-domain region stage on its own: the multihit Forward of every sequence of <regions> (each one region, configuration
+ * length 100 as the pipeline's) and its trace ensemble in the context's bath_hip_set_fs_ensemble mode.  Per region r:
+ *   region_status[r]  0 = ok, 1 = no valid traces (Forward underflow, an impossible state, the step cap): no envelopes;
+ *   trace_status      [n][200] or NULL: 0 ok, 1 impossible state, 2 step cap, 3 segment overflow (modes 1, 2; zeros in mode 0);
+ *   seg, seg_off      records (trace, i, j, k, m) in region coordinates, trace by trace in p7_trace_fs_Index's order; region r's
+ *                     are seg_off[r] .. seg_off[r+1] (modes 1, 2; none in mode 0, whose walk keeps no segments);
+ *   env, env_off      envelopes (i, j) in region coordinates, ordered by start, before the pipeline's length >= 15 rule.
+ * At most max_seg / max_env records are written; the offsets count all of them (BATH_ERANGE when either did not fit). */
+int bath_hip_fs5_region_ensembles(bath_hip_ctx *ctx, const bath_hip_fsprofile *om5, const bath_hip_seqs *regions, uint32_t seed,
+                                  int32_t *region_status, int32_t *trace_status, int32_t *seg, int64_t max_seg, int64_t *seg_off,
+                                  int32_t *env, int64_t max_env, int64_t *env_off);
+
 /* ------------------------------------------------------------------------------------------
  * Self-test hooks (host only, no GPU): the pieces of easel the multi-domain branch restates -- esl_randomness_CreateFast /
  * esl_random (p7_pipeline.c:140: the "fast" generator, x <- 69069 x + 1 on a Jenkins-mixed seed) and esl_vec_FNorm +
@@ -680,6 +711,18 @@ int bath_selftest_cluster_segments(int n, const int32_t *idx, const int32_t *i, 
                                    int nsamples, int fs, int32_t *env, int max_env, int32_t *n_env);
 int bath_selftest_fs_ensemble(int M, const float *tsc, float xNL, float xNM, float xE, int ireg, int Lr, const float *fwd, const float *fx,
                               int32_t *env, int max_env, int32_t *n_env);
+/* ... with the region's seed (bath_selftest_fs_ensemble uses 42) */
+int bath_selftest_fs_ensemble_seeded(int M, const float *tsc, float xNL, float xNM, float xE, int ireg, int Lr, const float *fwd, const float *fx,
+                                     uint32_t seed, int32_t *env, int max_env, int32_t *n_env);
+/* The host twin of BATH_ENSEMBLE_STREAMS_DEVICE (= what BATH_ENSEMBLE_STREAMS_HOST runs) on caller-supplied matrices, no GPU needed.
+ * region_status: 0 ok, 1 no valid traces; trace_status[200] or NULL; seg: up to max_seg records (trace, i, j, k, m) in region
+ * coordinates, *n_seg all of them; env: up to max_env (i, j) pairs in window coordinates (shifted by ireg - 1), *n_env all of them.
+ * BATH_ERANGE: the region is outside the stream rule, or a trace has more than 64 segments (the pipeline then runs the serial ensemble). */
+int bath_selftest_fs_ensemble_streams(int M, const float *tsc, float xNL, float xNM, float xE, int ireg, int Lr, const float *fwd, const float *fx,
+                                      uint32_t seed, int32_t *region_status, int32_t *trace_status, int32_t *seg, int max_seg, int32_t *n_seg,
+                                      int32_t *env, int max_env, int32_t *n_env);
+int bath_selftest_rng_jump(uint32_t seed, uint64_t n, uint32_t *state);   /* the generator's state n steps after seeding, by jump-ahead: value n - 1 of bath_selftest_rng_stream is state / 2^32 */
+int bath_selftest_ens_explog(int n, const float *x, float *e, float *l);  /* the stream modes' own expf / logf (host build of the source the kernel compiles); either output may be NULL */
 
 #ifdef __cplusplus
 }
