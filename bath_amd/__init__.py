@@ -28,7 +28,7 @@ OK, ERANGE, ENORESULT = 0, 16, 19
 KP, K, NEVPARAM = 29, 20, 8
 LOGSUM_TABLE, LOGSUM_EXACT, LOGSUM_TABLE_SERIAL, LOGSUM_CONTEXT = 0, 1, 2, 3
 LOGSUM_ODDS = 4                                     # 3-codon parsers in odds-ratio space (what the reference's --fs runs)
-# Context.set_fs_ensemble: how the frameshift branch samples a multi-domain region's 200 stochastic tracebacks
+# Context.set_fs_ensemble / set_std_ensemble: how a branch samples a multi-domain region's 200 stochastic tracebacks
 ENSEMBLE_SERIAL, ENSEMBLE_STREAMS_HOST, ENSEMBLE_STREAMS_DEVICE = 0, 1, 2
 ENSEMBLE_MODES = {"serial": ENSEMBLE_SERIAL, "streams": ENSEMBLE_STREAMS_HOST, "device": ENSEMBLE_STREAMS_DEVICE}
 ENS_SAMPLES = 200
@@ -210,6 +210,12 @@ ABI = {
     "bath_hip_set_fs5_odds": (C.c_int, [_vp, C.c_int]),
     "bath_hip_set_fs_ensemble": (C.c_int, [_vp, C.c_int]),
     "bath_hip_fs_ensemble_counters": (C.c_int, [_vp, _i64p, _i64p, _i64p]),
+    "bath_hip_set_std_ensemble": (C.c_int, [_vp, C.c_int]),
+    "bath_hip_std_ensemble_counters": (C.c_int, [_vp, _i64p, _i64p, _i64p]),
+    "bath_hip_std_region_ensembles": (C.c_int, [_vp, _vp, _vp, _i32p, C.c_uint32, _i32p, _i32p, _i32p, C.c_int64, _i64p, _i32p, _f32p, C.c_int64, _i64p]),
+    "bath_selftest_std_ensemble": (C.c_int, [C.c_int, C.c_int, _f32p, _f32p, C.c_float, C.c_float, C.c_float, _u8p, C.c_int, _f32p, _f32p, C.c_uint32, _i32p, _i32p,
+                                             _i32p, C.c_int, _i32p, _f32p, _i32p, C.c_int, _i32p]),
+    "bath_selftest_std_ens_walk": (C.c_int, [C.c_int, _f32p, C.c_float, C.c_float, C.c_float, C.c_int, _f32p, _f32p, C.c_uint32, _i32p, _i32p, C.c_int, _i32p]),
     "bath_hip_fs5_region_ensembles": (C.c_int, [_vp, _vp, _vp, C.c_uint32, _i32p, _i32p, _i32p, C.c_int64, _i64p, _i32p, C.c_int64, _i64p]),
     "bath_selftest_fs_ensemble_seeded": (C.c_int, [C.c_int, _f32p, C.c_float, C.c_float, C.c_float, C.c_int, C.c_int, _f32p, _f32p, C.c_uint32, _i32p, C.c_int, _i32p]),
     "bath_selftest_fs_ensemble_streams": (C.c_int, [C.c_int, _f32p, C.c_float, C.c_float, C.c_float, C.c_int, C.c_int, _f32p, _f32p, C.c_uint32,
@@ -505,6 +511,20 @@ class Context:
         a, b, c = C.c_int64(0), C.c_int64(0), C.c_int64(0)
         self._check(lib().bath_hip_fs_ensemble_counters(self._h, C.byref(a), C.byref(b), C.byref(c)), "fs_ensemble_counters")
         return {"bound_fallbacks": a.value, "overflow_fallbacks": b.value, "matrix_bytes_kept": c.value}
+
+    def set_std_ensemble(self, mode):
+        """The same choice as set_fs_ensemble for the STANDARD branch's multi-domain regions (a plain search; the windows of an --fs
+        search that take the standard branch): ENSEMBLE_SERIAL (the default), ENSEMBLE_STREAMS_HOST or ENSEMBLE_STREAMS_DEVICE (200
+        lanes of std_ensemble_kernel per region; the matrices stay on the device), also by name.  The two stream modes give identical
+        domains; against the serial mode envelopes agree as two seeds of the serial mode do."""
+        self._check(lib().bath_hip_set_std_ensemble(self._h, ENSEMBLE_MODES.get(mode, mode)), "set_std_ensemble")
+
+    def std_ensemble_counters(self):
+        """Since the context was created: regions a stream mode of set_std_ensemble sent to the serial ensemble (outside the stream
+        rule, or more than 64 segments in a trace), regions the kernel sent to the host twin (more than 8), regions the kernel walked."""
+        a, b, c = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        self._check(lib().bath_hip_std_ensemble_counters(self._h, C.byref(a), C.byref(b), C.byref(c)), "std_ensemble_counters")
+        return {"serial_fallbacks": a.value, "twin_fallbacks": b.value, "kernel_regions": c.value}
 
     def set_fs_serial(self, on):
         """Measurement aid: the envelopes' Backward wavefront after the Forward one instead of beside it (bath_hip_set_fs_serial)."""
@@ -1375,6 +1395,62 @@ def FS5RegionEnsembles(ctx, om5, regions, seed=42):
         max_seg, max_env = max(max_seg, int(so[-1])), max(max_env, int(eo[-1]))
     ctx._check(st, "fs5_region_ensembles")
     return _ens_unpack(n, rs, ts, seg, so, env, eo)
+
+
+def StdRegionEnsembles(ctx, om, regions, cfg_len=None, seed=42):
+    """The standard branch's multi-domain region stage on its own, in the context's set_std_ensemble mode.  regions: a SeqBlock of
+    amino-acid sequences, each one region; cfg_len: the length the model is configured for per region (None: the region's own).  Per
+    region a dict as FS5RegionEnsembles gives, plus n2corr: the null2 correction of every envelope."""
+    n = regions.n
+    rs = np.zeros(max(n, 1), np.int32); ts = np.zeros((max(n, 1), ENS_SAMPLES), np.int32)
+    so = np.zeros(n + 1, np.int64); eo = np.zeros(n + 1, np.int64)
+    cfg = None if cfg_len is None else np.ascontiguousarray(cfg_len, np.int32)
+    assert cfg is None or cfg.shape == (n,)
+    max_seg, max_env = 64 * ENS_SAMPLES * max(n, 1), 64 * max(n, 1)          # (the twin keeps 64 segments a trace: no second run, which would count fallbacks twice)
+    p = lambda a: a.ctypes.data_as(_i32p)
+    while True:
+        seg = np.zeros((max_seg, 5), np.int32); env = np.zeros((max_env, 2), np.int32); corr = np.zeros(max_env, np.float32)
+        st = lib().bath_hip_std_region_ensembles(ctx._h, om._h, regions._h, None if cfg is None else p(cfg), seed, p(rs), p(ts), p(seg), max_seg, _i64(so),
+                                                 p(env), _f32(corr), max_env, _i64(eo))
+        if st != ERANGE or (int(so[-1]) <= max_seg and int(eo[-1]) <= max_env):
+            break
+        max_seg, max_env = max(max_seg, int(so[-1])), max(max_env, int(eo[-1]))
+    ctx._check(st, "std_region_ensembles")
+    out = _ens_unpack(n, rs, ts, seg, so, env, eo)
+    for r in range(n):
+        out[r]["n2corr"] = corr[eo[r]:eo[r + 1]].copy()
+    return out
+
+
+def std_ensemble_host(mode, M, tf, rf, pmove, tEL, tEM, res, fwd, fx, seed=42):
+    """The standard branch's ensemble of one region on caller-supplied tables and matrices (no GPU), mode ENSEMBLE_SERIAL or
+    ENSEMBLE_STREAMS_HOST: the dict of StdRegionEnsembles for the region, with n2sc, the per-residue null2 log odds, instead of n2corr.
+    Raises BathError where the stream mode does not take the region."""
+    tf, rf, fwd, fx = (np.ascontiguousarray(a, np.float32) for a in (tf, rf, fwd, fx))
+    res = np.ascontiguousarray(res, np.uint8)
+    Lr = len(res)
+    assert tf.size >= (M + 1) * 8 and rf.size >= 20 * (M + 1) and fwd.size >= (Lr + 1) * (M + 1) * 3 and fx.size >= (Lr + 1) * 6
+    rs, nseg, nenv = C.c_int32(0), C.c_int32(0), C.c_int32(0)
+    ts = np.zeros(ENS_SAMPLES, np.int32); seg = np.zeros((64 * ENS_SAMPLES, 5), np.int32); env = np.zeros((256, 2), np.int32)
+    n2sc = np.zeros(Lr, np.float32)
+    p = lambda a: a.ctypes.data_as(_i32p)
+    st = lib().bath_selftest_std_ensemble(ENSEMBLE_MODES.get(mode, mode), M, _f32(tf), _f32(rf), pmove, tEL, tEM, _u8(res), Lr, _f32(fwd), _f32(fx), seed,
+                                          C.byref(rs), p(ts), p(seg), len(seg), C.byref(nseg), _f32(n2sc), p(env), len(env), C.byref(nenv))
+    if st != OK:
+        raise BathError("std_ensemble_host failed (%d)" % st)
+    return {"status": rs.value, "trace_status": ts, "segments": seg[:nseg.value].copy(), "envelopes": [tuple(int(v) for v in e) for e in env[:nenv.value]],
+            "n2sc": n2sc}
+
+
+def std_ens_walk(M, tf, pmove, tEL, tEM, Lr, fwd, fx, rng_state, max_seg=64):
+    """One walk of the standard branch's stream modes from generator state <rng_state>: (status, [(i, j, k, m)] first domain first)."""
+    tf, fwd, fx = (np.ascontiguousarray(a, np.float32) for a in (tf, fwd, fx))
+    st_, n = C.c_int32(0), C.c_int32(0)
+    seg = np.zeros((max_seg, 4), np.int32)
+    st = lib().bath_selftest_std_ens_walk(M, _f32(tf), pmove, tEL, tEM, Lr, _f32(fwd), _f32(fx), rng_state, C.byref(st_), seg.ctypes.data_as(_i32p), max_seg, C.byref(n))
+    if st != OK:
+        raise BathError("std_ens_walk failed (%d)" % st)
+    return st_.value, [tuple(int(v) for v in g) for g in seg[:n.value]]
 
 
 def fs_ensemble_streams(M, tsc, xNL, xNM, xE, ireg, Lr, fwd, fx, seed=42):

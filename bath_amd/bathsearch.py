@@ -41,7 +41,8 @@ OPTIONS = {"-o": str, "--tblout": str, "--fs": "flag", "--cigar": "flag", "--fra
            "-E": float, "-T": float, "--incT": float, "-Z": float, "--seed": int,
            "--F1": float, "--F2": float, "--F3": float, "--F4": float, "--max": "flag", "--nobias": "flag", "--nonull2": "flag", "--fsonly": "flag",
            "--block_length": int, "--gpus": int,
-           "--ensemble": str}      # an extension, not a reference option (no header line): how --fs samples a multi-domain region's traces
+           "--ensemble": str,      # an extension, not a reference option (no header line): how --fs samples a multi-domain region's traces
+           "--ensemble-std": str}  # ... and how the standard branch does (a search without --fs; the --fs windows that take that branch)
 MAX_GPUS = 16
 # bathsearch options this driver does not implement: refused, never ignored
 REFUSED = ["-h", "--splice", "--exontblout", "--fstblout", "--hmmout", "--acc", "--noali", "--notrans", "--min_intron", "--max_intron",
@@ -100,8 +101,9 @@ def parse_args(argv):
             raise UsageError("option %s requires %s" % (a, b))
     if "--strand" in opts and opts["--strand"] not in ("plus", "minus", "both"):
         raise UsageError("option --strand: expected plus, minus or both")
-    if "--ensemble" in opts and opts["--ensemble"] not in ba.ENSEMBLE_MODES:
-        raise UsageError("option --ensemble: expected serial, streams or device")
+    for o in ("--ensemble", "--ensemble-std"):
+        if o in opts and opts[o] not in ba.ENSEMBLE_MODES:
+            raise UsageError("option %s: expected serial, streams or device" % o)
     if opts.get("--textw", 150) < 120:
         raise UsageError("option --textw: n >= 120")
     if opts.get("--block_length", 50000) < 50000:
@@ -705,6 +707,7 @@ def _rank_search(argv, opts, hmmfile, seqfile, rank, world, device, dev, chunk_b
         ctx = ba.Context(device)
         ctx.set_fs_strict(True)
         ctx.set_fs_ensemble(opts.get("--ensemble", "serial"))
+        ctx.set_std_ensemble(opts.get("--ensemble-std", "serial"))
         laps["context_s"] = time.perf_counter() - t
         targets = Targets(ctx, seqfile, chunk_bytes, resident_bytes)
         src = _CodesSource(targets)
@@ -867,6 +870,7 @@ def run(argv, stdout=None, chunk_bytes=64 << 20, block_nt=256_000_000, resident_
         ctx = ba.Context(device)
         ctx.set_fs_strict(True)
         ctx.set_fs_ensemble(opts.get("--ensemble", "serial"))
+        ctx.set_std_ensemble(opts.get("--ensemble-std", "serial"))
         targets = Targets(ctx, seqfile, chunk_bytes, resident_bytes)
         src = _CodesSource(targets)
         for q in range(nq):

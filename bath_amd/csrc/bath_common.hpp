@@ -174,6 +174,11 @@ struct bath_hip_ctx {
   // regions of the stream modes that went another way: outside the stream rule (serial ensemble), a trace with more segments than the
   // kernel keeps (host twin); and the bytes of Forward matrices the device mode did not send to the host (bath_hip_fs_ensemble_counters)
   std::atomic<int64_t> fs_ens_bound_fallbacks{0}, fs_ens_overflow_fallbacks{0}, fs_ens_bytes_kept{0};
+  int std_ensemble = 0;                 // bath_hip_set_std_ensemble: the same choice for the standard branch's multi-domain regions
+  // its regions that went another way: to the serial ensemble (outside the stream rule, more segments in a trace than the twin keeps),
+  // from the kernel to the host twin (a trace with more segments than the kernel keeps) (bath_hip_std_ensemble_counters)
+  // ... and the regions std_ensemble_kernel walked (the fallbacks to the twin included)
+  std::atomic<int64_t> std_ens_serial_fallbacks{0}, std_ens_twin_fallbacks{0}, std_ens_kernel_regions{0};
   int fs_serial = -1;                   // envelopes' Backward after Forward on one stream instead of beside it (timing probes); -1: BATH_HIP_FS_SERIAL decides
   uint64_t tabs_uid = 0;                // whose SSV score table sits in scratch[8] (bath_pipeline.hip: uploaded once per profile, not per call)
   const void *tabs_ptr = nullptr;
@@ -182,11 +187,13 @@ struct bath_hip_ctx {
   std::string err;
   void set_error(const std::string &m) { err = m; }
   // scratch owned by the context (reused across calls)
-  bath::DevBuf scratch[60];             // [50]-[52]: the device-side DNA-window builder (bath_fs_windows.hip)
+  bath::DevBuf scratch[62];             // [50]-[52]: the device-side DNA-window builder (bath_fs_windows.hip); [59]-[61]: the standard branch's device ensemble
+                                        // (its regions' Forward matrices; job list + start states up; statuses, segments, path codes down)
   // page-locked staging for small tables a launch uploads (job order, batch starts, offsets): an asynchronous copy from here needs
   // no synchronize before the local it was built in goes away.  One slot per call site; a site is reused by its context only
   // after the stage that used it has synchronized its stream.  [0] fs_schedule, [1]/[2] chain_batches (Forward / Backward), [3] wavefront Backward
-  bath::HostBuf stage[12];                // ... [4] / [5]: the standard branch's domain stage, its small uploads / downloads (bath_domaindef.hip: std_domains)
+  bath::HostBuf stage[12];                // ... [4] / [5]: the standard branch's domain stage, its small uploads / downloads (bath_domaindef.hip: std_domains);
+                                          // [10] / [11]: std_ensemble_kernel's upload and its results (bath_std_ensemble.hip)
   template <class T> int stage_upload(int slot, void *dst, const T *src, size_t n, hipStream_t s) {
     if (stage[slot].reserve(n * sizeof(T) + 64) != hipSuccess) { set_error("cannot allocate page-locked staging memory"); return BATH_EFAIL; }
     std::memcpy(stage[slot].p, src, n * sizeof(T));

@@ -34,6 +34,7 @@
 #include "bath_common.hpp"
 #include "bath_kernels.hpp"
 #include "bath_launch.hpp"
+#include "bath_std_ens_walk.hpp"
 
 using namespace bath;
 
@@ -234,6 +235,7 @@ static int fs_branch_domains(bath_hip_ctx *ctx, const bath_hip_oprofile *om, con
     if ((st = om->ensure_len_tables(dna->maxlen / 3 + 1)) != BATH_OK) return st;      // the profile's mutable state: fill it before the thread starts
     bath_hip_ctx *aux = ctx->aux;
     aux->fs_domains.clear(); aux->cigars.clear(); aux->traces_clear();
+    aux->std_ensemble = ctx->std_ensemble; aux->spans_reset();
     const DomOpts std_opt(*prm, E_report);
     std_thread = std::thread([&, aux, std_opt] {
       if (hipSetDevice(ctx->device) != hipSuccess) { std_rc = BATH_EFAIL; return; }
@@ -1631,6 +1633,75 @@ __global__ __launch_bounds__(256) void std_envelope_fill_mw_kernel(SeqView sq, i
 
 }  // namespace
 
+// The multi-domain regions of a batch: p7_Forward of every region in the multihit configuration of length cfg[e] (full matrix),
+// then its stochastic-trace ensemble in the context's bath_hip_set_std_ensemble mode; per region the clusters' envelopes
+// (region coordinates) with their null2 corrections (null2_is_done: p7_domaindef.c:1270-1272).  <v> and the d_ arrays are on the
+// device already.  Modes 0 and 1: the kernel writes matrices, special-state rows and residues straight into page-locked host memory,
+// the transfer rides along with the computation, and host threads walk.  Mode 2: the matrices and rows stay in device memory,
+// std_ensemble_kernel walks behind the Forward kernel on the same stream, and the host gets statuses, segments and path codes.
+struct StdRegionOut { int status = 0; std::vector<std::pair<int, int>> env; std::vector<float> corr; std::vector<int32_t> segs, trace_status; };
+static int std_region_stage(bath_hip_ctx *ctx, const bath_hip_oprofile *om, SeqView v, int64_t nm, const int32_t *h_len, const std::vector<int32_t> &cfg,
+                            const std::vector<int64_t> &mxoff, const std::vector<int64_t> &mdpoff, const int64_t *d_xoff, const int64_t *d_dpoff,
+                            const int32_t *d_cfg, uint32_t seed, bool detail, std::vector<StdRegionOut> *out, StageClock &clk) {
+  int st;
+  const int mode = ctx->std_ensemble;
+  const bool dev = mode == BATH_ENSEMBLE_STREAMS_DEVICE;
+  out->assign((size_t)nm, StdRegionOut{});
+  DevBuf &b_fx = ctx->scratch[6], &b_sc = ctx->scratch[2], &b_st = ctx->scratch[3], &b_dp = ctx->scratch[59];
+  BATH_HIP_TRY(ctx, b_fx.reserve((size_t)mxoff[(size_t)nm] * 4 + 64)); BATH_HIP_TRY(ctx, b_sc.reserve((size_t)nm * 8)); BATH_HIP_TRY(ctx, b_st.reserve((size_t)nm * 8));
+  // Residues of region e: h_res + roff[e], one row's worth of bytes per residue row (roff = the x-row offsets / 6).
+  const size_t x_bytes = ((size_t)mxoff[(size_t)nm] * 4 + 255) / 256 * 256;
+  if (dev) BATH_HIP_TRY(ctx, b_dp.reserve((size_t)mdpoff[(size_t)nm] * 4 + 64)); else BATH_HIP_TRY(ctx, ctx->pinned[0].reserve((size_t)mdpoff[(size_t)nm] * 4 + 64));
+  BATH_HIP_TRY(ctx, ctx->pinned[1].reserve(x_bytes + (size_t)mxoff[(size_t)nm] / 6 + 64));
+  float *h_dp = ctx->pinned[0].as<float>(), *h_x = ctx->pinned[1].as<float>();      // page-locked
+  const uint8_t *h_res = reinterpret_cast<const uint8_t *>(ctx->pinned[1].p) + x_bytes;
+  std::vector<int64_t> roff((size_t)nm + 1, 0);
+  for (int64_t e = 0; e <= nm; e++) roff[(size_t)e] = mxoff[(size_t)e] / 6;
+  void *dv_dp = nullptr, *dv_x = nullptr;
+  if ((!dev && hipHostGetDevicePointer(&dv_dp, ctx->pinned[0].p, 0) != hipSuccess) || hipHostGetDevicePointer(&dv_x, ctx->pinned[1].p, 0) != hipSuccess) {
+    ctx->set_error("page-locked host memory is not mapped into the device's address space"); return BATH_EFAIL;
+  }
+  float *dst_x = dev ? b_fx.as<float>() : static_cast<float *>(dv_x), *dst_dp = dev ? b_dp.as<float>() : static_cast<float *>(dv_dp);
+  if ((st = launch_fwd_wave(ctx, om, v, nullptr, nm, b_sc.as<float>(), b_st.as<int32_t>(), nullptr, dst_x, d_xoff, dst_dp, d_dpoff, 0, d_cfg)) != BATH_OK) return st;
+  hipLaunchKernelGGL(gather_residues_kernel, dim3((unsigned)std::min<int64_t>(nm, 4096)), dim3(64), 0, ctx->stream, v, d_xoff, static_cast<uint8_t *>(dv_x) + x_bytes);
+  BATH_HIP_TRY(ctx, hipGetLastError());
+  StdEnsRun run;
+  if (dev && (st = std_region_ensembles_device(ctx, om, nm, h_len, v.len, d_cfg, dst_dp, d_dpoff, dst_x, d_xoff, seed, &run)) != BATH_OK) return st;
+  BATH_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  clk.lap(dev ? "std:   region Forward + ensemble kernel" : "std:   region Forward + copy to host");
+  // the regions are independent (each ensemble starts from the seed): host threads take them round-robin, results are
+  // kept in region order
+  if (om->ensure_len_tables(*std::max_element(cfg.begin(), cfg.end())) != BATH_OK) return BATH_EFAIL;
+  std::atomic<int> rc{BATH_OK};
+  auto work = [&](int64_t first, int64_t step) {
+    std::vector<float> n2sc;
+    std::vector<std::pair<int, int>> cl;
+    for (int64_t e = first; e < nm; e += step) {
+      StdRegionOut &o = (*out)[(size_t)e];
+      const int Lr = h_len[e];
+      const StdEnsModel m = std_ens_model(om, cfg[(size_t)e]);
+      if (detail) o.trace_status.assign(kEnsSamples, 0);
+      int rs = 0, r;
+      if (dev) r = std_ensemble_region_from_device(ctx, run, e, m, h_res + roff[(size_t)e], Lr, mdpoff[(size_t)e], mxoff[(size_t)e], seed, &n2sc, &cl, &rs,
+                                                   detail ? &o.segs : nullptr, detail ? o.trace_status.data() : nullptr);
+      else r = std_region_ensemble_host(ctx, mode, m, h_res + roff[(size_t)e], Lr, h_dp + mdpoff[(size_t)e], h_x + mxoff[(size_t)e], &n2sc, &cl, seed, &rs,
+                                        detail ? &o.segs : nullptr, detail ? o.trace_status.data() : nullptr);
+      if (r != BATH_OK) { rc = r; continue; }
+      o.status = rs;
+      if (rs != kEnsRegionOk) continue;                     // a failed ensemble: the region has no envelopes
+      for (const auto &c : cl) {
+        float corr = 0.f;
+        for (int pos = c.first; pos <= c.second; pos++) corr += n2sc[(size_t)pos];     // null2_is_done: p7_domaindef.c:1270-1272
+        o.env.push_back(c); o.corr.push_back(corr);
+      }
+    }
+  };
+  run_striped(nm, work, [&](int64_t e) { return h_len[e]; });
+  if (rc.load() != BATH_OK) { ctx->set_error("a multi-domain region's ensemble failed (a copy from the device, or records that do not add up)"); return rc.load(); }
+  clk.lap(dev ? "std:   ensembles (null2 + clustering, host threads)" : "std:   ensembles (host threads)");
+  return BATH_OK;
+}
+
 // Domain definition and hit scores for ORFs that passed the Forward filter; appends to ctx->fs_domains.
 static int std_domains(bath_hip_ctx *ctx, const bath_hip_oprofile *om, const bath_hip_seqs *dna, const std::vector<PipelineSurvivor> &surv,
                        const uint8_t *d_pool, const DomOpts &opt, int64_t *n_clustered_regions) {
@@ -1735,7 +1806,7 @@ static int std_domains(bath_hip_ctx *ctx, const bath_hip_oprofile *om, const bat
   if (n_clustered_regions) *n_clustered_regions += (int64_t)mregs.size();      // regions resolved by clustering (ddef->nclustered)
 
   // ---- multi-domain regions (p7_domaindef.c:539-583): p7_Forward of the region with the ORF's multihit configuration on the
-  // GPU, then the stochastic-trace ensemble and its clustering on the host (bath_ensemble.hip); every cluster is an envelope
+  // GPU, then the stochastic-trace ensemble and its clustering (std_region_stage); every cluster is an envelope
   if (!mregs.empty()) {
     const int64_t nm = (int64_t)mregs.size();
     bath_hip_seqs mv;
@@ -1755,51 +1826,17 @@ static int std_domains(bath_hip_ctx *ctx, const bath_hip_oprofile *om, const bat
     if ((st = upload_view(mv, mxoff, nm)) != BATH_OK) return st;
     DevBuf &b_mdpo = ctx->scratch[20], &b_cfg = ctx->scratch[5];
     BATH_HIP_TRY(ctx, b_mdpo.reserve((size_t)(nm + 1) * 8)); BATH_HIP_TRY(ctx, b_cfg.reserve((size_t)nm * 4 + 64));
-    BATH_HIP_TRY(ctx, b_fx.reserve((size_t)mxoff[(size_t)nm] * 4 + 64)); BATH_HIP_TRY(ctx, b_sc.reserve((size_t)nm * 8)); BATH_HIP_TRY(ctx, b_st.reserve((size_t)nm * 8));
     if ((st = up(b_mdpo.p, {{mdpoff.data(), (size_t)(nm + 1) * 8}})) != BATH_OK) return st;
     if ((st = up(b_cfg.p, {{cfg.data(), (size_t)nm * 4}})) != BATH_OK) return st;
-    // The matrices, the special-state rows and the regions' residues are for the host (the ensembles' tracebacks): the kernels
-    // write them straight into page-locked host memory, the transfer rides along with the computation.  Residues of region e:
-    // h_res + roff[e], one row's worth of bytes per residue row (roff = the x-row offsets / 6).
-    const size_t x_bytes = ((size_t)mxoff[(size_t)nm] * 4 + 255) / 256 * 256;
-    BATH_HIP_TRY(ctx, ctx->pinned[0].reserve((size_t)mdpoff[(size_t)nm] * 4 + 64)); BATH_HIP_TRY(ctx, ctx->pinned[1].reserve(x_bytes + (size_t)mxoff[(size_t)nm] / 6 + 64));
-    float *h_dp = ctx->pinned[0].as<float>(), *h_x = ctx->pinned[1].as<float>();      // page-locked
-    const uint8_t *h_res = reinterpret_cast<const uint8_t *>(ctx->pinned[1].p) + x_bytes;
-    std::vector<int64_t> roff((size_t)nm + 1, 0);
-    for (int64_t e = 0; e <= nm; e++) roff[(size_t)e] = mxoff[(size_t)e] / 6;
-    void *dv_dp = nullptr, *dv_x = nullptr;
-    if (hipHostGetDevicePointer(&dv_dp, ctx->pinned[0].p, 0) != hipSuccess || hipHostGetDevicePointer(&dv_x, ctx->pinned[1].p, 0) != hipSuccess) {
-      ctx->set_error("page-locked host memory is not mapped into the device's address space"); return BATH_EFAIL;
-    }
-    if ((st = launch_fwd_wave(ctx, om, mv.view(), nullptr, nm, b_sc.as<float>(), b_st.as<int32_t>(), nullptr, static_cast<float *>(dv_x), b_idx.as<int64_t>() + nm,
-                              static_cast<float *>(dv_dp), b_mdpo.as<int64_t>(), 0, b_cfg.as<int32_t>())) != BATH_OK) return st;
-    hipLaunchKernelGGL(gather_residues_kernel, dim3((unsigned)std::min<int64_t>(nm, 4096)), dim3(64), 0, ctx->stream, mv.view(), b_idx.as<int64_t>() + nm,
-                       static_cast<uint8_t *>(dv_x) + x_bytes);
-    BATH_HIP_TRY(ctx, hipGetLastError());
-    BATH_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    std::vector<StdRegionOut> ro;
+    st = std_region_stage(ctx, om, mv.view(), nm, mv.h_len.data(), cfg, mxoff, mdpoff, b_idx.as<int64_t>() + nm, b_mdpo.as<int64_t>(), b_cfg.as<int32_t>(), opt.seed, false, &ro, clk);
     mv.d_data = nullptr; mv.d_off = nullptr; mv.d_len = nullptr;
-    clk.lap("std:   region Forward + copy to host");
-    // the regions are independent (each ensemble starts from the seed): host threads take them round-robin, results are
-    // appended in region order
-    if (om->ensure_len_tables(*std::max_element(cfg.begin(), cfg.end())) != BATH_OK) return BATH_EFAIL;
-    std::vector<std::vector<Env>> found((size_t)nm);
-    auto work = [&](int64_t first, int64_t step) {
-      std::vector<float> n2sc;
-      std::vector<std::pair<int, int>> cl;
-      for (int64_t e = first; e < nm; e += step) {
-        const Env &en = mregs[(size_t)e];
-        const int Lr = en.j - en.i + 1;
-        if (region_trace_ensemble(om, cfg[(size_t)e], h_res + roff[(size_t)e], Lr, h_dp + mdpoff[(size_t)e], h_x + mxoff[(size_t)e], &n2sc, &cl, opt.seed) != BATH_OK) continue;
-        for (const auto &c : cl) {
-          float corr = 0.f;
-          for (int pos = c.first; pos <= c.second; pos++) corr += n2sc[(size_t)pos];     // null2_is_done: p7_domaindef.c:1270-1272
-          found[(size_t)e].push_back(Env{en.s, en.i + c.first - 1, en.i + c.second - 1, true, corr});
-        }
-      }
-    };
-    run_striped(nm, work, [&](int64_t e) { return mv.h_len[(size_t)e]; });
-    for (int64_t e = 0; e < nm; e++) envs.insert(envs.end(), found[(size_t)e].begin(), found[(size_t)e].end());
-    clk.lap("std:   ensembles (host threads)");
+    if (st != BATH_OK) return st;
+    for (int64_t e = 0; e < nm; e++) {                      // in region order
+      const Env &en = mregs[(size_t)e];
+      for (size_t c = 0; c < ro[(size_t)e].env.size(); c++)
+        envs.push_back(Env{en.s, en.i + ro[(size_t)e].env[c].first - 1, en.i + ro[(size_t)e].env[c].second - 1, true, ro[(size_t)e].corr[c]});
+    }
   }
   const int64_t ne = (int64_t)envs.size();
   if (ne == 0) return BATH_OK;
@@ -1988,6 +2025,7 @@ extern "C" int bath_hip_pipeline_hits(bath_hip_ctx *ctx, const bath_hip_oprofile
   ctx->fs_domains.clear();
   ctx->cigars.clear();
   ctx->traces_clear();
+  ctx->spans_reset();
   bath_pipeline_params prm = *prm_in;
   prm.fs_pipe = 0;
   bath_pipeline_stats st_local{};
@@ -2148,5 +2186,48 @@ extern "C" int bath_hip_domain_traces(bath_hip_ctx *ctx, const bath_domain_trace
   if (i) *i = ctx->tr_i.data();
   if (c) *c = ctx->tr_c.data();
   if (pp) *pp = ctx->tr_pp.data();
+  return BATH_OK;
+}
+
+// The multi-domain region stage of the standard branch on its own (include/bath_hip.h)
+extern "C" int bath_hip_std_region_ensembles(bath_hip_ctx *ctx, const bath_hip_oprofile *om, const bath_hip_seqs *regions, const int32_t *cfg_len, uint32_t seed,
+                                             int32_t *region_status, int32_t *trace_status, int32_t *seg, int64_t max_seg, int64_t *seg_off,
+                                             int32_t *env, float *env_n2corr, int64_t max_env, int64_t *env_off) {
+  if (!ctx || !om || !regions || !region_status || !seg_off || !env_off || max_seg < 0 || max_env < 0 || (max_seg > 0 && !seg) || (max_env > 0 && (!env || !env_n2corr))) {
+    if (ctx) ctx->set_error("bath_hip_std_region_ensembles: needs a profile, the regions and its output arrays");
+    return BATH_EINVAL;
+  }
+  BATH_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  const int64_t n = regions->n;
+  seg_off[0] = 0; env_off[0] = 0;
+  ctx->spans_reset();
+  if (n == 0) return BATH_OK;
+  std::vector<int32_t> cfg((size_t)n);
+  for (int64_t e = 0; e < n; e++) {
+    cfg[(size_t)e] = cfg_len ? cfg_len[e] : regions->h_len[(size_t)e];
+    if (cfg[(size_t)e] < 0) { ctx->set_error("bath_hip_std_region_ensembles: negative configuration length"); return BATH_EINVAL; }
+  }
+  int st = om->ensure_len_tables(std::max(regions->maxlen, *std::max_element(cfg.begin(), cfg.end())) + 1);
+  if (st != BATH_OK) return st;
+  const BlockOffsets o = block_offsets(regions, om->M);
+  DevBuf &b_off = ctx->scratch[20], &b_cfg = ctx->scratch[5];
+  BATH_HIP_TRY(ctx, b_off.reserve((size_t)(n + 1) * 16)); BATH_HIP_TRY(ctx, b_cfg.reserve((size_t)n * 4 + 64));
+  int64_t *d_xo = b_off.as<int64_t>(), *d_dpo = d_xo + (n + 1);
+  BATH_HIP_TRY(ctx, hipMemcpyAsync(d_xo, o.x.data(), (size_t)(n + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
+  BATH_HIP_TRY(ctx, hipMemcpyAsync(d_dpo, o.dp.data(), (size_t)(n + 1) * 8, hipMemcpyHostToDevice, ctx->stream));
+  BATH_HIP_TRY(ctx, hipMemcpyAsync(b_cfg.p, cfg.data(), (size_t)n * 4, hipMemcpyHostToDevice, ctx->stream));
+  std::vector<StdRegionOut> ro;
+  StageClock clk;
+  if ((st = std_region_stage(ctx, om, regions->view(), n, regions->h_len.data(), cfg, o.x, o.dp, d_xo, d_dpo, b_cfg.as<int32_t>(), seed, true, &ro, clk)) != BATH_OK) return st;
+  int64_t nseg = 0, nenv = 0;
+  for (int64_t e = 0; e < n; e++) {
+    const StdRegionOut &r = ro[(size_t)e];
+    region_status[e] = r.status;
+    if (trace_status) std::copy(r.trace_status.begin(), r.trace_status.end(), trace_status + (size_t)e * kEnsSamples);
+    for (size_t q = 0; q + 5 <= r.segs.size(); q += 5, nseg++) if (nseg < max_seg) std::memcpy(seg + nseg * 5, r.segs.data() + q, 5 * sizeof(int32_t));
+    for (size_t c = 0; c < r.env.size(); c++, nenv++) if (nenv < max_env) { env[nenv * 2] = r.env[c].first; env[nenv * 2 + 1] = r.env[c].second; env_n2corr[nenv] = r.corr[c]; }
+    seg_off[e + 1] = nseg; env_off[e + 1] = nenv;
+  }
+  if (nseg > max_seg || nenv > max_env) { ctx->set_error("bath_hip_std_region_ensembles: output arrays too small"); return BATH_ERANGE; }
   return BATH_OK;
 }

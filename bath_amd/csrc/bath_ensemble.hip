@@ -25,6 +25,7 @@
 #include "bath_common.hpp"
 #include "bath_launch.hpp"
 #include "bath_fs_ens_walk.hpp"
+#include "bath_std_ens_walk.hpp"
 
 namespace {
 
@@ -172,6 +173,41 @@ void cluster_segments(const std::vector<Seg> &sp, int nsamples, bool fs, std::ve
   for (size_t d = 0; d < sig.size(); d++) if (!dominated[d]) env->push_back({sig[d].i, sig[d].j});
 }
 
+// match odds ratios node-major, [k][20]: the expectation sum_k cnt[k] * rf[x][k] of all 20 residues is then one pass over the
+// nodes of the domain with 20 independent accumulators (each residue's sum still runs over k in ascending order)
+const float *node_major_rf(const bath::StdEnsModel &om) {
+  static thread_local std::vector<float> rft;
+  const int M = om.M;
+  rft.resize((size_t)(M + 1) * 20);
+  for (int x = 0; x < 20; x++) { const float *e = om.rf + (size_t)x * (M + 1); for (int q = 0; q <= M; q++) rft[(size_t)q * 20 + x] = e[q]; }
+  return rft.data();
+}
+
+// One domain of a trace: p7_Null2_ByTrace (impl_sse/null2.c:131-215) from its per-node counts -- cnt[k]: match and insert steps at node
+// k, zero outside hmmfrom..hmmto, Ld of them in all; scaled in place -- and the per-residue bookkeeping of p7_domaindef.c:790-803
+void add_domain_null2(float *cnt, int hmmfrom, int hmmto, int Ld, const float *rft, int sqfrom, int sqto, const uint8_t *res, int *pos_io, float *n2sc) {
+  const float norm = (float)(1.0 / (float)Ld);
+  for (int q = std::max(hmmfrom, 1); q <= hmmto; q++) cnt[(size_t)q] *= norm;
+  float null2[bath::kKp];
+  for (int x = 0; x < 20; x++) null2[x] = 0.f;
+  for (int q = std::max(hmmfrom, 1); q <= hmmto; q++) {                 // cnt is zero outside the domain's nodes
+    const float c = cnt[(size_t)q], *e = rft + (size_t)q * 20;
+    for (int x = 0; x < 20; x++) null2[x] += c * e[x];
+  }
+  static const int mem[6][2] = {{2, 11}, {7, 9}, {3, 13}, {8, 8}, {1, 1}, {-1, -1}};     // B=DN J=IL Z=EQ O=K U=C X=any
+  for (int dx = 0; dx < 6; dx++) {
+    float s = 0.f; int c = 0;
+    if (dx == 5) { for (int y = 0; y < 20; y++) { s += null2[y]; c++; } }
+    else { s += null2[mem[dx][0]]; c++; if (mem[dx][1] != mem[dx][0]) { s += null2[mem[dx][1]]; c++; } }
+    null2[21 + dx] = s / (float)c;
+  }
+  null2[20] = 1.0f; null2[27] = 1.0f; null2[28] = 1.0f;
+  int pos = *pos_io;
+  for (; pos <= sqfrom; pos++) n2sc[(size_t)pos] += 1.0f;
+  for (; pos <= sqto; pos++) n2sc[(size_t)pos] += null2[std::min<int>(res[pos - 1], bath::kKp - 1)];
+  *pos_io = pos;
+}
+
 }  // namespace
 
 // One region of an ORF.  fwd: (Lr+1) x (M+1) x {M,D,I}, fx: (Lr+1) x {E,N,J,B,C,SCALE} of p7_Forward on the region with the
@@ -179,12 +215,22 @@ void cluster_segments(const std::vector<Seg> &sp, int nsamples, bool fs, std::ve
 // Out: n2sc[0..Lr) per-residue null2 log odds; env: envelopes (1-based, region-relative), ordered by start.
 int bath::region_trace_ensemble(const bath_hip_oprofile *om, int cfg_L, const uint8_t *res, int Lr, const float *fwd, const float *fx,
                                 std::vector<float> *n2sc_out, std::vector<std::pair<int, int>> *env, uint32_t seed) {
-  const int M = om->M, Q = std::max(2, (M - 1) / 4 + 1);
-  const size_t W = (size_t)(M + 1) * 3;
-  const float *tf = om->tf.data();
   if (om->ensure_len_tables(cfg_L) != BATH_OK) return BATH_EFAIL;
-  const float pmove = om->lt.h_pmove[(size_t)cfg_L], ploop = 1.0f - pmove;
-  const float tEL = om->xf_E[0], tEM = om->xf_E[1];
+  return region_trace_ensemble(std_ens_model(om, cfg_L), res, Lr, fwd, fx, n2sc_out, env, seed);
+}
+
+// the model as the ensembles read it; ensure_len_tables(cfg_L) has run
+bath::StdEnsModel bath::std_ens_model(const bath_hip_oprofile *om, int cfg_L) {
+  return StdEnsModel{om->M, om->tf.data(), om->rf.data(), om->lt.h_pmove[(size_t)cfg_L], om->xf_E[0], om->xf_E[1]};
+}
+
+int bath::region_trace_ensemble(const StdEnsModel &om, const uint8_t *res, int Lr, const float *fwd, const float *fx,
+                                std::vector<float> *n2sc_out, std::vector<std::pair<int, int>> *env, uint32_t seed) {
+  const int M = om.M, Q = std::max(2, (M - 1) / 4 + 1);
+  const size_t W = (size_t)(M + 1) * 3;
+  const float *tf = om.tf;
+  const float pmove = om.pmove, ploop = 1.0f - pmove;
+  const float tEL = om.tEL, tEM = om.tEM;
   const int nsamples = 200;
   std::vector<float> &n2sc = *n2sc_out;
   n2sc.assign((size_t)Lr + 1, 0.f);                       // 1-based positions of the region
@@ -194,11 +240,7 @@ int bath::region_trace_ensemble(const bath_hip_oprofile *om, int cfg_L, const ui
   std::vector<Step> tr;
   std::vector<Seg> sp;
   std::vector<float> cnt((size_t)M + 1);
-  // match odds ratios node-major, [k][20]: the expectation sum_k cnt[k] * rf[x][k] of all 20 residues is then one pass over the
-  // nodes of the domain with 20 independent accumulators (each residue's sum still runs over k in ascending order)
-  static thread_local std::vector<float> rft;
-  rft.resize((size_t)(M + 1) * 20);
-  for (int x = 0; x < 20; x++) { const float *e = om->rf.data() + (size_t)x * (M + 1); for (int q = 0; q <= M; q++) rft[(size_t)q * 20 + x] = e[q]; }
+  const float *rft = node_major_rf(om);
   const int step_cap = 4 * (Lr + M) + 64;
   for (int t = 0; t < nsamples; t++) {
     tr.clear();
@@ -262,24 +304,7 @@ int bath::region_trace_ensemble(const bath_hip_oprofile *om, int cfg_L, const ui
         if (tr[z].st == sM || tr[z].st == sI) { Ld++; cnt[(size_t)tr[z].k] += 1.0f; }      // inserts land in the match slot (null2.c:160-166)
       }
       sp.push_back(Seg{t, sqfrom, sqto, hmmfrom, hmmto, 0.f});
-      const float norm = (float)(1.0 / (float)Ld);
-      for (int q = std::max(hmmfrom, 1); q <= hmmto; q++) cnt[(size_t)q] *= norm;
-      float null2[kKp];
-      for (int x = 0; x < 20; x++) null2[x] = 0.f;
-      for (int q = std::max(hmmfrom, 1); q <= hmmto; q++) {                 // cnt is zero outside the domain's nodes
-        const float c = cnt[(size_t)q], *e = rft.data() + (size_t)q * 20;
-        for (int x = 0; x < 20; x++) null2[x] += c * e[x];
-      }
-      static const int mem[6][2] = {{2, 11}, {7, 9}, {3, 13}, {8, 8}, {1, 1}, {-1, -1}};     // B=DN J=IL Z=EQ O=K U=C X=any
-      for (int dx = 0; dx < 6; dx++) {
-        float s = 0.f; int c = 0;
-        if (dx == 5) { for (int y = 0; y < 20; y++) { s += null2[y]; c++; } }
-        else { s += null2[mem[dx][0]]; c++; if (mem[dx][1] != mem[dx][0]) { s += null2[mem[dx][1]]; c++; } }
-        null2[21 + dx] = s / (float)c;
-      }
-      null2[20] = 1.0f; null2[27] = 1.0f; null2[28] = 1.0f;
-      for (; pos <= sqfrom; pos++) n2sc[(size_t)pos] += 1.0f;
-      for (; pos <= sqto; pos++) n2sc[(size_t)pos] += null2[std::min<int>(res[pos - 1], kKp - 1)];
+      add_domain_null2(cnt.data(), hmmfrom, hmmto, Ld, rft, sqfrom, sqto, res, &pos, n2sc.data());
       z++;
     }
     for (; pos <= Lr; pos++) n2sc[(size_t)pos] += 1.0f;
@@ -532,6 +557,115 @@ int bath::fs_region_ensemble_host(bath_hip_ctx *counters, int mode, int M, const
 }
 
 
+// ---- the standard branch in the per-trace-stream modes (bath_hip_set_std_ensemble): the same stream rule, bath_std_ens_walk.hpp's
+// std_ens_walk.  The null2 contributions of the traces are computed HERE, on the host, for the twin and for the kernel alike: a walk
+// leaves its segments and the M / I / D code of every step inside them, and std_ensemble_consume replays those in trace order through
+// the serial code's own add_domain_null2 -- one piece of host code, so modes 1 and 2 cannot differ in a bit of it.
+
+// the host twin: the 200 walks of one region on the calling thread (seg: [200][max_seg][kStdSegInts], path: [200][words])
+void bath::std_ensemble_walk_host(const StdEnsModel &om, int Lr, const float *fwd, const float *fx, uint32_t seed, int max_seg,
+                                  int32_t *status, int32_t *nseg, int32_t *seg, uint32_t *path) {
+  uint32_t states[kEnsSamples];
+  fs_ensemble_start_states(seed, states);
+  const size_t words = (size_t)std_ens_path_words(Lr, om.M, max_seg);
+  for (int t = 0; t < kEnsSamples; t++)
+    status[t] = std_ens_walk(om.M, om.tf, om.pmove, om.tEL, om.tEM, Lr, fwd, fx, states[t], seg + (size_t)t * max_seg * kStdSegInts, max_seg, nseg + t, path + (size_t)t * words);
+}
+
+// What the walks of one region left (host twin or kernel) -> its per-residue null2 scores and its envelopes, as region_trace_ensemble
+// gives them.  A region with any trace that is not ok is a failed ensemble (the serial code's BATH_EFAIL): kEnsRegionNoTraces, nothing
+// else is set.  segs_out (optional): (trace, i, j, k, m) in p7_trace_Index's order.
+int bath::std_ensemble_consume(const StdEnsModel &om, const uint8_t *res, int Lr, const int32_t *status, const int32_t *nseg, const int32_t *seg, int max_seg,
+                               const uint32_t *path, std::vector<float> *n2sc_out, std::vector<std::pair<int, int>> *env, std::vector<int32_t> *segs_out) {
+  env->clear();
+  if (segs_out) segs_out->clear();
+  for (int t = 0; t < kEnsSamples; t++) if (status[t] != kEnsOk) return kEnsRegionNoTraces;
+  const int M = om.M;
+  const size_t words = (size_t)std_ens_path_words(Lr, M, max_seg);
+  std::vector<float> &n2sc = *n2sc_out;
+  n2sc.assign((size_t)Lr + 1, 0.f);
+  const float *rft = node_major_rf(om);
+  std::vector<float> cnt((size_t)M + 1);
+  std::vector<int> code0((size_t)max_seg + 1);
+  std::vector<Seg> sp;
+  for (int t = 0; t < kEnsSamples; t++) {
+    const int32_t *sg = seg + (size_t)t * max_seg * kStdSegInts;
+    const uint32_t *pw = path + (size_t)t * words;
+    const int ns = nseg[t];
+    code0[0] = 0;
+    for (int d = 0; d < ns; d++) code0[(size_t)d + 1] = code0[(size_t)d] + sg[d * kStdSegInts + 4];
+    if (ns < 0 || ns > max_seg || (size_t)code0[(size_t)ns] > words * 16) return BATH_EFAIL;
+    int pos = 1;
+    for (int d = ns - 1; d >= 0; d--) {                     // the walk's last domain is the trace's first
+      const int32_t *g = sg + d * kStdSegInts;
+      const int sqfrom = g[0], sqto = g[1], hmmfrom = g[2], hmmto = g[3];
+      if (hmmfrom < 1 || hmmto > M || hmmfrom > hmmto || sqfrom < 1 || sqto > Lr || sqfrom > sqto) return BATH_EFAIL;
+      sp.push_back(Seg{t, sqfrom, sqto, hmmfrom, hmmto, 0.f});
+      if (segs_out) { const int32_t r[5] = {t, sqfrom, sqto, hmmfrom, hmmto}; segs_out->insert(segs_out->end(), r, r + 5); }
+      std::fill(cnt.begin(), cnt.end(), 0.f);
+      int k = hmmto, Ld = 0;
+      for (int c = code0[(size_t)d]; c < code0[(size_t)d + 1]; c++) {       // from the domain's last match state back to its first
+        const int code = (int)(pw[c >> 4] >> (2 * (c & 15))) & 3;
+        if (k < 1) return BATH_EFAIL;
+        if (code == kStdCodeD) k--;
+        else { cnt[(size_t)k] += 1.0f; Ld++; if (code == kStdCodeM) k--; }    // inserts land in the match slot (null2.c:160-166)
+      }
+      if (k != hmmfrom - 1) return BATH_EFAIL;
+      add_domain_null2(cnt.data(), hmmfrom, hmmto, Ld, rft, sqfrom, sqto, res, &pos, n2sc.data());
+    }
+    for (; pos <= Lr; pos++) n2sc[(size_t)pos] += 1.0f;
+  }
+  for (int pos = 1; pos <= Lr; pos++) n2sc[(size_t)pos] = logf(n2sc[(size_t)pos] / (float)kEnsSamples);
+  cluster_segments(sp, kEnsSamples, false, env);
+  return kEnsRegionOk;
+}
+
+// BATH_ERANGE: outside the stream rule or more than kEnsHostMaxSeg segments in a trace (the caller runs the serial ensemble)
+int bath::std_region_trace_ensemble_streams(const StdEnsModel &om, const uint8_t *res, int Lr, const float *fwd, const float *fx, std::vector<float> *n2sc,
+                                            std::vector<std::pair<int, int>> *env, uint32_t seed, int *region_status, std::vector<int32_t> *segs_out,
+                                            int32_t *trace_status) {
+  env->clear();
+  if (!ens_streams_fit(Lr, om.M)) return BATH_ERANGE;
+  const size_t words = (size_t)std_ens_path_words(Lr, om.M, kEnsHostMaxSeg);
+  std::vector<int32_t> buf((size_t)kEnsSamples * (2 + kEnsHostMaxSeg * kStdSegInts));
+  std::vector<uint32_t> path((size_t)kEnsSamples * words);
+  int32_t *status = buf.data(), *nseg = status + kEnsSamples, *seg = nseg + kEnsSamples;
+  std_ensemble_walk_host(om, Lr, fwd, fx, seed, kEnsHostMaxSeg, status, nseg, seg, path.data());
+  if (trace_status) std::copy(status, status + kEnsSamples, trace_status);
+  for (int t = 0; t < kEnsSamples; t++) if (status[t] == kEnsSegOverflow) return BATH_ERANGE;
+  const int rs = std_ensemble_consume(om, res, Lr, status, nseg, seg, kEnsHostMaxSeg, path.data(), n2sc, env, segs_out);
+  if (rs < 0) return rs;
+  if (region_status) *region_status = rs;
+  return BATH_OK;
+}
+
+// One region on a host thread in mode BATH_ENSEMBLE_SERIAL or BATH_ENSEMBLE_STREAMS_HOST.  A region the stream mode does not take
+// gets the serial ensemble and is counted in <counters> (if any).  *region_status: kEnsRegionNoTraces for a failed ensemble (the
+// serial code's BATH_EFAIL, which its callers answer by giving the region no envelopes): the return value is BATH_OK then.
+int bath::std_region_ensemble_host(bath_hip_ctx *counters, int mode, const StdEnsModel &om, const uint8_t *res, int Lr, const float *fwd, const float *fx,
+                                   std::vector<float> *n2sc, std::vector<std::pair<int, int>> *env, uint32_t seed, int *region_status,
+                                   std::vector<int32_t> *segs_out, int32_t *trace_status) {
+  if (Lr < 1) {                                             // an empty region holds no path (its Forward score is -inf): nothing is walked
+    env->clear();
+    if (segs_out) segs_out->clear();
+    if (trace_status) std::fill(trace_status, trace_status + kEnsSamples, mode == BATH_ENSEMBLE_SERIAL ? 0 : (int32_t)kEnsImpossible);
+    if (region_status) *region_status = kEnsRegionNoTraces;
+    return BATH_OK;
+  }
+  if (mode != BATH_ENSEMBLE_SERIAL) {
+    const int st = std_region_trace_ensemble_streams(om, res, Lr, fwd, fx, n2sc, env, seed, region_status, segs_out, trace_status);
+    if (st != BATH_ERANGE) return st;
+    if (counters) counters->std_ens_serial_fallbacks++;
+  }
+  if (segs_out) segs_out->clear();
+  if (trace_status) std::fill(trace_status, trace_status + kEnsSamples, 0);
+  const int st = region_trace_ensemble(om, res, Lr, fwd, fx, n2sc, env, seed);
+  if (st != BATH_OK) env->clear();
+  if (region_status) *region_status = st == BATH_OK ? kEnsRegionOk : kEnsRegionNoTraces;
+  return BATH_OK;
+}
+
+
 // ---- self-test hooks (include/bath_hip.h): the restated easel pieces and the frameshift ensemble, callable without a GPU
 extern "C" int bath_selftest_fs_ensemble(int M, const float *tsc, float xNL, float xNM, float xE, int ireg, int Lr, const float *fwd, const float *fx,
                                          int32_t *env, int max_env, int32_t *n_env) {
@@ -622,5 +756,45 @@ extern "C" int bath_selftest_fs_ensemble_streams(int M, const float *tsc, float 
   std::copy(segs.begin(), segs.begin() + (size_t)std::min<int>(*n_seg, max_seg) * 5, seg);
   *n_env = (int32_t)cl.size();
   for (size_t e = 0; e < cl.size() && (int)e < max_env; e++) { env[2 * e] = cl[e].first; env[2 * e + 1] = cl[e].second; }
+  return BATH_OK;
+}
+
+// The standard branch's ensemble on caller-supplied tables and matrices, no GPU needed.  tf [M+1][8], rf [>= 20][M+1] (the optimized
+// profile's odds ratios), pmove / tEL / tEM of the multihit configuration; res[Lr]; fwd (Lr+1) x (M+1) x {M, D, I}; fx (Lr+1) x
+// {E, N, J, B, C, SCALE}.  mode: BATH_ENSEMBLE_SERIAL or BATH_ENSEMBLE_STREAMS_HOST (BATH_ERANGE where the stream rule or the twin's 64
+// segments per trace do not hold: the pipeline runs the serial ensemble there).  n2sc[Lr] (or NULL): per-residue null2 log odds;
+// the other outputs as bath_selftest_fs_ensemble_streams's, envelopes in region coordinates.
+extern "C" int bath_selftest_std_ensemble(int mode, int M, const float *tf, const float *rf, float pmove, float tEL, float tEM, const uint8_t *res, int Lr,
+                                          const float *fwd, const float *fx, uint32_t seed, int32_t *region_status, int32_t *trace_status,
+                                          int32_t *seg, int max_seg, int32_t *n_seg, float *n2sc, int32_t *env, int max_env, int32_t *n_env) {
+  if (!tf || !rf || !res || !fwd || !fx || !n_env || !n_seg || !region_status || M < 1 || Lr < 1 || max_env < 0 || max_seg < 0 || (max_seg > 0 && !seg) ||
+      (max_env > 0 && !env) || (mode != BATH_ENSEMBLE_SERIAL && mode != BATH_ENSEMBLE_STREAMS_HOST)) return BATH_EINVAL;
+  const bath::StdEnsModel om{M, tf, rf, pmove, tEL, tEM};
+  std::vector<std::pair<int, int>> cl;
+  std::vector<int32_t> segs;
+  std::vector<float> n2;
+  int rs = 0;
+  if (trace_status) std::fill(trace_status, trace_status + bath::kEnsSamples, 0);
+  const int st = mode == BATH_ENSEMBLE_SERIAL ? bath::std_region_ensemble_host(nullptr, mode, om, res, Lr, fwd, fx, &n2, &cl, seed, &rs, &segs, trace_status)
+                                              : bath::std_region_trace_ensemble_streams(om, res, Lr, fwd, fx, &n2, &cl, seed, &rs, &segs, trace_status);
+  if (st != BATH_OK) return st;
+  *region_status = rs;
+  *n_seg = (int32_t)(segs.size() / 5);
+  std::copy(segs.begin(), segs.begin() + (size_t)std::min<int>(*n_seg, max_seg) * 5, seg);
+  if (n2sc && rs == bath::kEnsRegionOk) std::copy(n2.begin() + 1, n2.begin() + 1 + Lr, n2sc);
+  *n_env = (int32_t)cl.size();
+  for (size_t e = 0; e < cl.size() && (int)e < max_env; e++) { env[2 * e] = cl[e].first; env[2 * e + 1] = cl[e].second; }
+  return BATH_OK;
+}
+
+// one walk of the stream modes from a given generator state (tests: trace t against the generator stepped t * 2^20 times)
+extern "C" int bath_selftest_std_ens_walk(int M, const float *tf, float pmove, float tEL, float tEM, int Lr, const float *fwd, const float *fx, uint32_t rng_state,
+                                          int32_t *status, int32_t *seg, int max_seg, int32_t *n_seg) {
+  if (!tf || !fwd || !fx || !status || !seg || !n_seg || M < 1 || Lr < 1 || max_seg < 1 || max_seg > bath::kEnsHostMaxSeg) return BATH_EINVAL;
+  if (!bath::ens_streams_fit(Lr, M)) return BATH_ERANGE;
+  std::vector<uint32_t> path((size_t)bath::std_ens_path_words(Lr, M, max_seg));
+  std::vector<int32_t> sg((size_t)max_seg * bath::kStdSegInts);
+  *status = bath::std_ens_walk(M, tf, pmove, tEL, tEM, Lr, fwd, fx, rng_state, sg.data(), max_seg, n_seg, path.data());
+  for (int d = 0; d < *n_seg; d++) for (int q = 0; q < 4; q++) seg[d * 4 + q] = sg[(size_t)(*n_seg - 1 - d) * bath::kStdSegInts + q];   // first domain first
   return BATH_OK;
 }

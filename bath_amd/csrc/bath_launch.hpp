@@ -141,6 +141,33 @@ int fs5_envelopes_ex(bath_hip_ctx *ctx, const bath_hip_fsprofile *om5, const bat
 // ---- multi-domain regions (bath_ensemble.hip, host): envelopes and per-residue null2 scores from 200 stochastic tracebacks
 int region_trace_ensemble(const bath_hip_oprofile *om, int cfg_L, const uint8_t *res, int Lr, const float *fwd, const float *fx,
                           std::vector<float> *n2sc, std::vector<std::pair<int, int>> *env, uint32_t seed = 42);
+// ... on the model as plain arrays (what the ensembles read of it): rf [Kp][M+1], tf [M+1][8], pmove of the configured length, xf_E
+struct StdEnsModel { int M; const float *tf, *rf; float pmove, tEL, tEM; };
+StdEnsModel std_ens_model(const bath_hip_oprofile *om, int cfg_L);          // after om->ensure_len_tables(cfg_L)
+int region_trace_ensemble(const StdEnsModel &om, const uint8_t *res, int Lr, const float *fwd, const float *fx,
+                          std::vector<float> *n2sc, std::vector<std::pair<int, int>> *env, uint32_t seed = 42);
+// ---- its per-trace-stream modes (bath_hip_set_std_ensemble; bath_std_ens_walk.hpp is the walk, bath_std_ensemble.hip the kernel)
+void std_ensemble_walk_host(const StdEnsModel &om, int Lr, const float *fwd, const float *fx, uint32_t seed, int max_seg,
+                            int32_t *status, int32_t *nseg, int32_t *seg, uint32_t *path);
+int std_ensemble_consume(const StdEnsModel &om, const uint8_t *res, int Lr, const int32_t *status, const int32_t *nseg, const int32_t *seg, int max_seg,
+                         const uint32_t *path, std::vector<float> *n2sc, std::vector<std::pair<int, int>> *env, std::vector<int32_t> *segs_out = nullptr);
+int std_region_trace_ensemble_streams(const StdEnsModel &om, const uint8_t *res, int Lr, const float *fwd, const float *fx, std::vector<float> *n2sc,
+                                      std::vector<std::pair<int, int>> *env, uint32_t seed = 42, int *region_status = nullptr,
+                                      std::vector<int32_t> *segs_out = nullptr, int32_t *trace_status = nullptr);
+// BATH_ENSEMBLE_STREAMS_DEVICE: std_ensemble_kernel queued on ctx->stream behind the regions' Forward, and what it wrote on its way
+// to page-locked memory in one copy.  Once the stream is synchronized: out = per region status[200], nseg[200],
+// seg[200][kEnsMaxSeg][kStdSegInts]; path + poff[e] = region e's path codes, [200][std_ens_path_words].  The matrices stay in device
+// memory (d_fwd, d_fx) for the regions that fall back to a host walk.
+constexpr int kStdEnsOutInts = 200 * (2 + 8 * 5);
+struct StdEnsRun { const int32_t *out = nullptr; const uint32_t *path = nullptr; std::vector<int64_t> poff; const float *d_fwd = nullptr, *d_fx = nullptr; };
+int std_region_ensembles_device(bath_hip_ctx *ctx, const bath_hip_oprofile *om, int64_t n, const int32_t *h_len, const int32_t *d_len, const int32_t *d_cfg,
+                                const float *d_fwd, const int64_t *d_foff, const float *d_fx, const int64_t *d_xoff, uint32_t seed, StdEnsRun *run);
+int std_ensemble_region_from_device(bath_hip_ctx *ctx, const StdEnsRun &run, int64_t e, const StdEnsModel &om, const uint8_t *res, int Lr,
+                                    int64_t foff, int64_t xoff, uint32_t seed, std::vector<float> *n2sc, std::vector<std::pair<int, int>> *env,
+                                    int *region_status = nullptr, std::vector<int32_t> *segs_out = nullptr, int32_t *trace_status = nullptr);
+int std_region_ensemble_host(bath_hip_ctx *counters, int mode, const StdEnsModel &om, const uint8_t *res, int Lr, const float *fwd, const float *fx,
+                             std::vector<float> *n2sc, std::vector<std::pair<int, int>> *env, uint32_t seed, int *region_status = nullptr,
+                             std::vector<int32_t> *segs_out = nullptr, int32_t *trace_status = nullptr);
 
 int fs_region_trace_ensemble(int M, const float *tsc, float xNL, float xNM, float xE, int ireg, int Lr, const float *fwd, const float *fx,
                              std::vector<std::pair<int, int>> *env, uint32_t seed = 42);

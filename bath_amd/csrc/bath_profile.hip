@@ -204,7 +204,7 @@ extern "C" void *bath_hip_stream(bath_hip_ctx *ctx) { return (void *)ctx->stream
 extern "C" int bath_hip_kernel_times(bath_hip_ctx *ctx, int max, bath_kernel_time *out) {
   if (!ctx || !out) return 0;
   int n = 0;
-  for (const bath_hip_ctx *c : {(const bath_hip_ctx *)ctx, (const bath_hip_ctx *)ctx->aux2, (const bath_hip_ctx *)ctx->aux3}) {     // the regions' Forward runs on a context of its own
+  for (const bath_hip_ctx *c : {(const bath_hip_ctx *)ctx, (const bath_hip_ctx *)ctx->aux, (const bath_hip_ctx *)ctx->aux2, (const bath_hip_ctx *)ctx->aux3}) {     // the standard branch of an --fs pass and the regions' Forward run on contexts of their own
     if (!c) continue;
     for (const bath::KernelSpan &k : c->spans) {
       float ms = 0.f;
@@ -250,6 +250,28 @@ extern "C" int bath_hip_set_fs_ensemble(bath_hip_ctx *ctx, int mode) {
   if (mode != BATH_ENSEMBLE_SERIAL && mode != BATH_ENSEMBLE_STREAMS_HOST && mode != BATH_ENSEMBLE_STREAMS_DEVICE) { ctx->set_error("bath_hip_set_fs_ensemble: unknown mode " + std::to_string(mode)); return BATH_EINVAL; }
   ctx->fs_ensemble = mode;
   for (bath_hip_ctx *l : ctx->lanes) l->fs_ensemble = mode;
+  return BATH_OK;
+}
+
+extern "C" int bath_hip_set_std_ensemble(bath_hip_ctx *ctx, int mode) {
+  if (!ctx) return BATH_EINVAL;
+  if (mode != BATH_ENSEMBLE_SERIAL && mode != BATH_ENSEMBLE_STREAMS_HOST && mode != BATH_ENSEMBLE_STREAMS_DEVICE) { ctx->set_error("bath_hip_set_std_ensemble: unknown mode " + std::to_string(mode)); return BATH_EINVAL; }
+  ctx->std_ensemble = mode;
+  for (bath_hip_ctx *l : ctx->lanes) l->std_ensemble = mode;
+  if (ctx->aux) ctx->aux->std_ensemble = mode;             // (the standard branch beside the frameshift branch; set again before every such run)
+  return BATH_OK;
+}
+
+extern "C" int bath_hip_std_ensemble_counters(bath_hip_ctx *ctx, int64_t *serial_fallbacks, int64_t *twin_fallbacks, int64_t *kernel_regions) {
+  if (!ctx) return BATH_EINVAL;
+  int64_t s = 0, t = 0, k = 0;
+  for (const bath_hip_ctx *c : {(const bath_hip_ctx *)ctx, (const bath_hip_ctx *)ctx->aux}) {       // (the standard branch of an --fs search runs on aux)
+    if (!c) continue;
+    s += c->std_ens_serial_fallbacks.load(); t += c->std_ens_twin_fallbacks.load(); k += c->std_ens_kernel_regions.load();
+  }
+  if (serial_fallbacks) *serial_fallbacks = s;
+  if (twin_fallbacks) *twin_fallbacks = t;
+  if (kernel_regions) *kernel_regions = k;
   return BATH_OK;
 }
 

@@ -154,12 +154,28 @@ int         bath_hip_set_fs5_odds(bath_hip_ctx *ctx, int on);
  * mode 0 agree with each other, not bit for bit.  A region outside the stream rule (4 (4 (Lr + M) + 64) >= 2^20) takes the serial
  * path; in mode 2 a region with a trace of more than 8 segments takes mode 1's.  bath_hip_fs_ensemble_counters counts both (since
  * the context was created), and the bytes of Forward matrices mode 2 did not send to the host.  The standard branch's ensemble
- * (region_trace_ensemble) is host code in every mode.  Unknown mode or null ctx: BATH_EINVAL. */
+ * (region_trace_ensemble) has a switch of its own, bath_hip_set_std_ensemble.  Unknown mode or null ctx: BATH_EINVAL. */
 #define BATH_ENSEMBLE_SERIAL 0
 #define BATH_ENSEMBLE_STREAMS_HOST 1
 #define BATH_ENSEMBLE_STREAMS_DEVICE 2
 int         bath_hip_set_fs_ensemble(bath_hip_ctx *ctx, int mode);
 int         bath_hip_fs_ensemble_counters(bath_hip_ctx *ctx, int64_t *bound_fallbacks, int64_t *overflow_fallbacks, int64_t *matrix_bytes_kept);
+/* The same choice for the STANDARD branch's multi-domain regions (region_trace_ensemble, p7_domaindef.c:766-850, with
+ * p7_StochasticTrace): a plain search, and the windows of an --fs search that take the standard branch.  Same modes, same stream rule
+ * (trace t starts t * 2^20 steps into the region's generator; a region with 4 (4 (Lr + M) + 64) >= 2^20 takes the serial path):
+ *   BATH_ENSEMBLE_SERIAL (0, the default): today's path -- host threads, Forward matrices streamed into page-locked host memory.
+ *   BATH_ENSEMBLE_STREAMS_HOST (1): a stream per trace, the E state's sum in ascending node order; host threads.  The twin of mode 2.
+ *   BATH_ENSEMBLE_STREAMS_DEVICE (2): the same walks as 200 lanes of std_ensemble_kernel, one block per region, on matrices that stay
+ *     in device memory; statuses, segments and the 2-bit M / I / D path codes inside them come back in one copy.
+ * The walk has no transcendental (the matrix holds scaled probabilities), so modes 1 and 2 give the same traces bit for bit; the null2
+ * contributions of the traces (p7_Null2_ByTrace) are computed on the host from segments and path codes by one piece of code for both,
+ * and clustering is unchanged.  Against mode 0 the envelopes agree as two seeds of mode 0 agree.  In mode 2 a region with a trace of
+ * more than 8 segments takes mode 1's walk on a copy of its matrix (more than 64: the serial one).  A region with a trace that is not
+ * ok has no envelopes, as a failed serial ensemble has none.  bath_hip_std_ensemble_counters: regions (since the context was
+ * created) that took the serial path from a stream mode, and that went from the kernel to the host twin; each region counts once;
+ * kernel_regions: the regions std_ensemble_kernel walked. */
+int         bath_hip_set_std_ensemble(bath_hip_ctx *ctx, int mode);
+int         bath_hip_std_ensemble_counters(bath_hip_ctx *ctx, int64_t *serial_fallbacks, int64_t *twin_fallbacks, int64_t *kernel_regions);
 /* Measurement aid: 1 = the envelope stage (bath_hip_fs5_envelopes and the domain stage's batches) runs its Backward wavefront AFTER the
  * Forward wavefront on the same stream instead of beside it, so that a kernel's HIP-event span is its time alone on the chip
  * (bench.py: fs.roofline.alone); 0 = side by side (the default); -1 = whatever BATH_HIP_FS_SERIAL says.  Results do not change. */
@@ -695,6 +711,15 @@ int bath_hip_fs5_region_ensembles(bath_hip_ctx *ctx, const bath_hip_fsprofile *o
                                   int32_t *region_status, int32_t *trace_status, int32_t *seg, int64_t max_seg, int64_t *seg_off,
                                   int32_t *env, int64_t max_env, int64_t *env_off);
 
+/* The standard branch's multi-domain region stage on its own: the multihit Forward of every sequence of <regions> (amino acids, each
+ * one region; model configured for length cfg_len[r], or the region's own length when cfg_len is NULL) and its trace ensemble in
+ * the context's bath_hip_set_std_ensemble mode.  Outputs as bath_hip_fs5_region_ensembles's, in region coordinates, with segments in
+ * p7_trace_Index's order, plus env_n2corr: per envelope the sum of the ensemble's per-residue null2 log odds over it (the domain's
+ * null2 correction, p7_domaindef.c:1270-1272).  An empty region (Forward score -inf) has status 1 and nothing is walked. */
+int bath_hip_std_region_ensembles(bath_hip_ctx *ctx, const bath_hip_oprofile *om, const bath_hip_seqs *regions, const int32_t *cfg_len, uint32_t seed,
+                                  int32_t *region_status, int32_t *trace_status, int32_t *seg, int64_t max_seg, int64_t *seg_off,
+                                  int32_t *env, float *env_n2corr, int64_t max_env, int64_t *env_off);
+
 /* ------------------------------------------------------------------------------------------
  * Self-test hooks (host only, no GPU): the pieces of easel the multi-domain branch restates -- esl_randomness_CreateFast /
  * esl_random (p7_pipeline.c:140: the "fast" generator, x <- 69069 x + 1 on a Jenkins-mixed seed) and esl_vec_FNorm +
@@ -721,6 +746,16 @@ int bath_selftest_fs_ensemble_seeded(int M, const float *tsc, float xNL, float x
 int bath_selftest_fs_ensemble_streams(int M, const float *tsc, float xNL, float xNM, float xE, int ireg, int Lr, const float *fwd, const float *fx,
                                       uint32_t seed, int32_t *region_status, int32_t *trace_status, int32_t *seg, int max_seg, int32_t *n_seg,
                                       int32_t *env, int max_env, int32_t *n_env);
+/* The standard branch's ensemble on caller-supplied tables and matrices, no GPU needed: tf [M+1][8], rf [>= 20][M+1] (odds ratios of
+ * the optimized profile), pmove / tEL / tEM of its multihit configuration, res[Lr], fwd (Lr+1) x (M+1) x {M, D, I}, fx (Lr+1) x
+ * {E, N, J, B, C, SCALE}.  mode 0 or 1 (BATH_ERANGE in mode 1: outside the stream rule or more than 64 segments in a trace).
+ * n2sc[Lr] or NULL: per-residue null2 log odds; the other outputs as bath_selftest_fs_ensemble_streams's, region coordinates. */
+int bath_selftest_std_ensemble(int mode, int M, const float *tf, const float *rf, float pmove, float tEL, float tEM, const uint8_t *res, int Lr,
+                               const float *fwd, const float *fx, uint32_t seed, int32_t *region_status, int32_t *trace_status,
+                               int32_t *seg, int max_seg, int32_t *n_seg, float *n2sc, int32_t *env, int max_env, int32_t *n_env);
+/* one walk of the standard branch's stream modes from generator state <rng_state>: *status, seg[max_seg][4] = (i, j, k, m) first domain first */
+int bath_selftest_std_ens_walk(int M, const float *tf, float pmove, float tEL, float tEM, int Lr, const float *fwd, const float *fx, uint32_t rng_state,
+                               int32_t *status, int32_t *seg, int max_seg, int32_t *n_seg);
 int bath_selftest_rng_jump(uint32_t seed, uint64_t n, uint32_t *state);   /* the generator's state n steps after seeding, by jump-ahead: value n - 1 of bath_selftest_rng_stream is state / 2^32 */
 int bath_selftest_ens_explog(int n, const float *x, float *e, float *l);  /* the stream modes' own expf / logf (host build of the source the kernel compiles); either output may be NULL */
 
