@@ -234,6 +234,7 @@ ABI = {
     "bath_hip_seqs_create": (C.c_int, [_vp, _u8p, _i64p, C.c_int64, C.POINTER(_vp)]),
     "bath_hip_seqs_destroy": (None, [_vp]),
     "bath_hip_seqs_count": (C.c_int64, [_vp]),
+    "bath_hip_seqs_read": (C.c_int64, [_vp, _u8p, C.c_int64, _i64p, _i32p, _i32p]),
     "bath_hip_seqs_set_context": (C.c_int, [_vp, C.POINTER(C.c_int32)]),
     "bath_hip_host_alloc": (C.c_void_p, [C.c_size_t]),
     "bath_hip_host_free": (None, [C.c_void_p]),
@@ -250,6 +251,7 @@ ABI = {
     "bath_hip_fasta_error": (C.c_int, [_vp, _i64p, _i64p, _i64p, _i32p]),
     "bath_hip_fasta_windows": (C.c_int64, [_vp, C.c_int64, C.c_int64, C.c_int32, C.c_int32, C.c_void_p, C.c_int64]),
     "bath_hip_fasta_seqs": (C.c_int, [_vp, C.c_void_p, C.c_int64, C.POINTER(_vp)]),
+    "bath_hip_fasta_seqs_for": (C.c_int, [_vp, _vp, C.c_void_p, C.c_int64, C.POINTER(_vp)]),
     "bath_hip_fasta_codes": (C.c_int, [_vp, C.c_int64, C.c_int64, C.c_int64, _u8p]),
     "bath_hip_fasta_release": (C.c_int, [_vp, C.c_int64]),
     "bath_hip_ssvfilter": (C.c_int, [_vp, _vp, _vp, _f32p, _i32p]),
@@ -472,6 +474,8 @@ class Context:
             raise BathError("%s failed (%d): %s" % (what, st, lib().bath_hip_last_error(self._h).decode()))
 
     def synchronize(self):
+        """Waits for the context's stream; also makes the context's device the calling host thread's current one (HIP keeps a
+        current device per thread, 0 in a new thread): what a worker thread calls first."""
         self._check(lib().bath_hip_synchronize(self._h), "synchronize")
 
     def trim(self):
@@ -624,6 +628,18 @@ class SeqBlock:
         c = np.ascontiguousarray(context, dtype=np.int32)
         assert c.shape == (self.n,)
         self.ctx._check(lib().bath_hip_seqs_set_context(self._h, c.ctypes.data_as(C.POINTER(C.c_int32))), "seqs_set_context")
+
+    def read(self):
+        """The block as it lies on the device: (data bytes with their padding, offsets, lengths, contexts) copied to the host."""
+        L = lib()
+        nbytes = L.bath_hip_seqs_read(self._h, None, 0, None, None, None)
+        if nbytes < 0:
+            self.ctx._check(-1, "seqs_read")
+        data = np.zeros(nbytes, np.uint8)
+        off, ln, cx = np.zeros(max(self.n, 1), np.int64), np.zeros(max(self.n, 1), np.int32), np.zeros(max(self.n, 1), np.int32)
+        if L.bath_hip_seqs_read(self._h, _u8(data), nbytes, _i64(off), ln.ctypes.data_as(_i32p), cx.ctypes.data_as(_i32p)) != nbytes:
+            self.ctx._check(-1, "seqs_read")
+        return data, off[:self.n], ln[:self.n], cx[:self.n]
 
     def __del__(self):
         if getattr(self, "_h", None) and getattr(self.ctx, "_h", None):
@@ -779,13 +795,20 @@ class FastaTargets:
             lib().bath_hip_fasta_windows(self._h, lo, hi, int(max_length), int(block_length), out.ctypes.data, n)
         return out
 
-    def seqs(self, windows):
-        """A SeqBlock of the given windows (laid out by the device, contexts set)."""
+    def seqs(self, windows, ctx=None):
+        """A SeqBlock of the given windows (laid out by the device, contexts set).  ctx: another Context of the same device that
+        the block is gathered for and belongs to (bath_hip_fasta_seqs_for: several contexts, one host thread each, may do so at once
+        once the targets are finished or between two feeds); None: this handle's own context."""
         w = np.ascontiguousarray(windows, dtype=FASTA_WINDOW_DTYPE)
         h = _vp()
-        self.ctx._check(lib().bath_hip_fasta_seqs(self._h, w.ctypes.data if len(w) else None, len(w), C.byref(h)), "fasta_seqs")
+        wp = w.ctypes.data if len(w) else None
+        if ctx is None:
+            ctx = self.ctx
+            ctx._check(lib().bath_hip_fasta_seqs(self._h, wp, len(w), C.byref(h)), "fasta_seqs")
+        else:
+            ctx._check(lib().bath_hip_fasta_seqs_for(ctx._h, self._h, wp, len(w), C.byref(h)), "fasta_seqs_for")
         blk = SeqBlock.__new__(SeqBlock)
-        blk.ctx, blk._h, blk.n = self.ctx, h, len(w)
+        blk.ctx, blk._h, blk.n = ctx, h, len(w)
         blk.lengths = w["n"].astype(np.int64)
         return blk
 

@@ -1,6 +1,6 @@
 """bathsearch on one GPU or several: search the profile HMMs of a model file against the DNA targets of a FASTA file.
 
-    python -m bath_amd.bathsearch [--gpus N] [options] <hmmfile> <seqfile>
+    python -m bath_amd.bathsearch [--gpus N] [--workers N] [options] <hmmfile> <seqfile>
 
 The FASTA file's bytes go to the device as they are (bath_amd.FastaTargets: records, digitising and the windows of
 esl_sqio_ReadWindow are found there); per query the windows run through the pipeline in blocks of at most <block_nt>
@@ -15,6 +15,14 @@ items of every query are cut and dealt the same way on every rank (search_plan),
 owner rank, which merges them in item order and renders the query, and rank 0 writes the queries in order; the output does not
 depend on N.  BATH_SEARCH_SHARE_DEVICE=1 puts every rank on device 0 and BATH_SEARCH_BACKEND=gloo runs the collectives on CPU
 tensors (default nccl); each rank gets an equal share of the parent's CPUs as BATH_HIP_HOST_THREADS unless that is set.
+
+--workers N (1..8, default 1; an extension like --ensemble: no header line) searches the queries of the model file side by side on
+one GPU: N contexts on the device, one host thread each, all reading the one device copy of the targets (FastaTargets.seqs(ctx=)).
+Within a piece of the targets the queries of a batch are drawn from a shared counter, longest first (dist.item_cost); every query
+is finished and rendered by the worker that searched its last piece, and an ordered writer (OrderedWriter) holds its text until
+every earlier query's text is written, so the output is the N = 1 output byte for byte but for the timing lines.  At most 2N
+queries' hits are alive at once, and the models and plans of at most two batches of 2N (feed_batches).  A failure at query k writes the queries before k, nothing from k on, one message, status 1.
+With --gpus G every rank runs its items on N contexts of its device; BATH_HIP_HOST_THREADS is then the CPU share / (G x N).
 """
 import codecs
 import os
@@ -41,9 +49,11 @@ OPTIONS = {"-o": str, "--tblout": str, "--fs": "flag", "--cigar": "flag", "--fra
            "-E": float, "-T": float, "--incT": float, "-Z": float, "--seed": int,
            "--F1": float, "--F2": float, "--F3": float, "--F4": float, "--max": "flag", "--nobias": "flag", "--nonull2": "flag", "--fsonly": "flag",
            "--block_length": int, "--gpus": int,
+           "--workers": int,       # an extension (no header line): queries searched side by side on N contexts of one GPU
            "--ensemble": str,      # an extension, not a reference option (no header line): how --fs samples a multi-domain region's traces
            "--ensemble-std": str}  # ... and how the standard branch does (a search without --fs; the --fs windows that take that branch)
 MAX_GPUS = 16
+MAX_WORKERS = 8
 # bathsearch options this driver does not implement: refused, never ignored
 REFUSED = ["-h", "--splice", "--exontblout", "--fstblout", "--hmmout", "--acc", "--noali", "--notrans", "--min_intron", "--max_intron",
            "--incE", "--qformat", "--tformat", "--singlemx", "--popen", "--pextend", "--mx", "--mxfile", "--w_beta", "--w_length", "--cpu",
@@ -110,6 +120,8 @@ def parse_args(argv):
         raise UsageError("option --block_length: n >= 50000")
     if not 1 <= opts.get("--gpus", 1) <= MAX_GPUS:
         raise UsageError("option --gpus: 1 <= n <= %d" % MAX_GPUS)
+    if not 1 <= opts.get("--workers", 1) <= MAX_WORKERS:
+        raise UsageError("option --workers: 1 <= n <= %d" % MAX_WORKERS)
     if opts.get("-E", 1.0) <= 0:
         raise UsageError("option -E: x > 0")
     if opts.get("-Z", 0.0) < 0 or opts.get("--seed", 0) < 0:
@@ -419,10 +431,16 @@ class _CodesSource:
     def __init__(self, targets):
         self.t = targets
         self._ft = None
+        self._lock = threading.Lock()            # worker threads render side by side (--workers)
 
     def codes_of(self, target, start0, n):
         if self.t.resident:
             return self.t.ft.codes(target, start0, n)
+        with self._lock:
+            self._parse_again()
+        return self._ft.codes(target, start0, n)
+
+    def _parse_again(self):
         if self._ft is None:                     # a streamed file: the hits' records, parsed once more
             ft = ba.FastaTargets(self.t.ctx)
             with open(self.t.path, "rb", buffering=0) as fh:
@@ -433,7 +451,6 @@ class _CodesSource:
                     ft.feed(self.t.pinned, k)
             ft.finish()
             self._ft = ft
-        return self._ft.codes(target, start0, n)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
@@ -494,6 +511,12 @@ def host_threads_per_rank(n, environ=None, affinity=None):
     return max(1, budget // int(n))
 
 
+def host_threads_per_worker(workers, ranks=1, environ=None, affinity=None):
+    """BATH_HIP_HOST_THREADS for each of <workers> contexts in each of <ranks> processes: host_threads_per_rank's budget split
+    over all of them, at least one each; None when the user has set it."""
+    return host_threads_per_rank(int(ranks) * int(workers), environ=environ, affinity=affinity)
+
+
 def rank_env(n, rank, port, environ=None, threads=None):
     """The environment of rank <rank> of <n>: torch.distributed's rendezvous variables and the host-thread share."""
     env = {k: v for k, v in (os.environ if environ is None else environ).items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "LOCAL_WORLD_SIZE")}
@@ -548,7 +571,7 @@ def launch_ranks(n, argv, stdout, run_kw):
     others are stopped, its error message is printed once and the status is 1.  No child outlives this call."""
     code = "import sys; from bath_amd import bathsearch as b; sys.exit(b.rank_main(sys.argv[1:], **%r))" % (run_kw,)
     cmd = [sys.executable] + (["-s"] if sys.flags.no_user_site else []) + ["-c", code] + list(argv)
-    port, threads = _free_port(), host_threads_per_rank(n)
+    port, threads = _free_port(), host_threads_per_worker(parse_args(list(argv))[0].get("--workers", 1), n)
     procs, errs, readers = [], [], []
     t0 = "%.6f" % time.time()
     try:
@@ -623,8 +646,11 @@ def _recv_text(src, dev):
     return bytes(buf.cpu().numpy().tobytes()).decode()
 
 
-def _search_items(ctx, hmm, ft, wins, items, opts, block_nt):
-    """This rank's items of one query in one piece of the targets: [(item, stats, hit window geometry, hit stream)]."""
+def _search_items(ctx, hmm, ft, wins, items, opts, block_nt, cancelled=None):
+    """This rank's items of one query in one piece of the targets: [(item, stats, hit window geometry, hit stream)].  <ctx> is the
+    targets' own context or a worker context beside it (the blocks are then gathered for it); cancelled(): asked before every
+    pipeline call, True ends the search with Cancelled."""
+    gather_for = None if ctx is ft.ctx else ctx
     fs = "--fs" in opts
     ct = opts.get("--ct", 1)
     om = ba.OProfile(ctx, ba.Profile(hmm))
@@ -641,7 +667,9 @@ def _search_items(ctx, hmm, ft, wins, items, opts, block_nt):
         cut = block_cuts(iw["n"], block_nt)
         for a, b in zip(cut[:-1], cut[1:]):
             w = iw[a:b]
-            blk = ft.seqs(w)
+            if cancelled is not None and cancelled():
+                raise Cancelled()
+            blk = ft.seqs(w, ctx=gather_for)
             if fs:
                 stats, _, dm, _ = pipe.run_frameshift_domains(om3, om5, blk, E_report=E, nres_before=nres)
             else:
@@ -690,12 +718,306 @@ def _render_query(q, hmm, desc, parts, opts, names, descs, lengths, src, t0, c0)
     return block, tbl
 
 
+# ---------------------------------------------------------------------------------------------------------------------------
+# --workers N: queries side by side on N contexts of one GPU, one host thread per context (WorkerPool), all of them reading the
+# one device copy of the targets; the finished queries' texts are written in query order (OrderedWriter).
+# ---------------------------------------------------------------------------------------------------------------------------
+
+class Cancelled(Exception):
+    """A worker's search ended early: a query before its own has failed."""
+
+
+class CtMismatch(Exception):
+    """A model whose codon table is not the --ct one (the message is CT_MISMATCH, filled in)."""
+
+
+class OrderedWriter:
+    """write(q, text) for q = 0, 1, 2, ... in that order, whatever order the queries finish in.  A query is alive from its
+    admission (WorkerPool admits a query when a worker picks its first job up; admit() does so for a caller without a pool) until
+    its text is written; at most <bound> are alive at once, so a worker waits instead of running ahead and what is held does not
+    grow with the number of queries.  put() hands a finished query's text over: it is held until every earlier one is written.
+    fail_at(k): nothing from query k on is written any more; the queries before k still are (a query from k on that was admitted
+    and hands no text over keeps its place: no query from k on is started any more, and the queries before k fit beside them)."""
+
+    def __init__(self, write, bound):
+        self.write, self.bound = write, int(bound)
+        self.cv = threading.Condition()
+        self.next, self.alive, self.limit, self.held = 0, 0, None, {}
+        self.max_alive = self.max_held = 0
+
+    def try_admit(self):
+        with self.cv:
+            if self.alive >= self.bound:
+                return False
+            self.alive += 1
+            self.max_alive = max(self.max_alive, self.alive)
+            return True
+
+    def admit(self):
+        with self.cv:
+            while not self.try_admit():
+                self.cv.wait()
+
+    def put(self, q, text):
+        with self.cv:
+            if self.limit is not None and q >= self.limit:
+                self.alive -= 1
+            else:
+                self.held[q] = text
+                self.max_held = max(self.max_held, len(self.held))
+                while self.next in self.held:
+                    self.write(self.next, self.held.pop(self.next))
+                    self.next += 1
+                    self.alive -= 1
+            self.cv.notify_all()
+
+    def fail_at(self, k):
+        with self.cv:
+            self.limit = k if self.limit is None else min(self.limit, k)
+            for q in [q for q in self.held if q >= self.limit]:
+                del self.held[q]
+                self.alive -= 1
+            self.cv.notify_all()
+
+
+class Round:
+    """Jobs the workers draw from a shared counter: <queries> in the order they are handed out, <payload> what work() needs for
+    them; admit: a job of this round is its query's first, and takes one of the writer's places."""
+
+    def __init__(self, queries, payload=None, admit=False):
+        self.queries, self.payload, self.admit, self.taken = list(queries), payload, admit, 0
+
+
+class WorkerPool:
+    """<n> host threads, thread w serving worker context w: work(w, round, query) for every job of every round submitted, rounds in
+    the order of submit(), a round's jobs from a shared counter.  When work raises, or fail() is called, at query k: jobs of
+    queries after k are not started, cancelled(q) turns True for them (a running search asks it before every pipeline call and
+    ends), the writer writes nothing from k on, and the queries before k are still finished and written, as a search query after
+    query leaves them.  wait() returns when every submitted job is done and raises the failure of the lowest query; close() joins
+    the threads; close(exc), after the coordinating thread itself raised <exc>, first fails the pool at the lowest query not yet
+    handed out, so that the workers do not search what is still queued.  start(w), when given, runs first on thread w (the driver
+    binds the thread to its context's device there)."""
+
+    def __init__(self, n, work, writer=None, start=None):
+        self.work, self.writer, self.start = work, writer, start
+        self.cv = writer.cv if writer is not None else threading.Condition()
+        self.rounds, self.pending, self.closing, self.failure = [], 0, False, None
+        self.threads = [threading.Thread(target=self._serve, args=(w,), name="bathsearch-worker-%d" % w) for w in range(n)]
+        for t in self.threads:
+            t.start()
+
+    def submit(self, rnd):
+        with self.cv:
+            self.rounds.append(rnd)
+            self.pending += len(rnd.queries)
+            self.cv.notify_all()
+
+    def cancelled(self, q):
+        f = self.failure
+        return f is not None and q > f[0]
+
+    def fail(self, q, exc):
+        with self.cv:
+            if self.failure is None or q < self.failure[0]:
+                self.failure = (q, exc)
+            if self.writer is not None:
+                self.writer.fail_at(self.failure[0])
+            self.cv.notify_all()
+
+    def _next(self):
+        with self.cv:
+            while True:
+                while self.rounds and self.rounds[0].taken == len(self.rounds[0].queries):
+                    self.rounds.pop(0)
+                if self.rounds:
+                    r = self.rounds[0]
+                    q = r.queries[r.taken]
+                    skip = self.failure is not None and q >= self.failure[0]
+                    if skip or not (r.admit and self.writer is not None) or self.writer.try_admit():
+                        r.taken += 1
+                        return r, q, skip
+                elif self.closing:
+                    return None
+                self.cv.wait()
+
+    def _serve(self, w):
+        if self.start is not None:
+            try:
+                self.start(w)
+            except BaseException as e:
+                self.fail(-1, e)
+        for r, q, skip in iter(self._next, None):
+            try:
+                if not skip:
+                    self.work(w, r, q)
+            except Cancelled:
+                pass
+            except BaseException as e:
+                self.fail(q, e)
+            with self.cv:
+                self.pending -= 1
+                self.cv.notify_all()
+
+    def barrier(self):
+        """Returns when every submitted job is done or skipped."""
+        with self.cv:
+            while self.pending:
+                self.cv.wait()
+
+    def wait(self):
+        self.barrier()
+        if self.failure is not None:
+            raise self.failure[1]
+
+    def wait_written(self, k):
+        """Returns True when the writer has written every query before <k>, False when a query has failed before that."""
+        with self.cv:
+            while self.writer.next < k and self.failure is None:
+                self.cv.wait()
+            return self.failure is None
+
+    def close(self, exc=None):
+        with self.cv:
+            untaken = [r.queries[i] for r in self.rounds for i in range(r.taken, len(r.queries))]
+            if exc is not None and untaken:
+                self.fail(min(untaken), exc)
+            self.closing = True
+            self.cv.notify_all()
+        for t in self.threads:
+            t.join()
+
+
+def new_context(device, opts):
+    ctx = ba.Context(device)
+    ctx.set_fs_strict(True)
+    ctx.set_fs_ensemble(opts.get("--ensemble", "serial"))
+    ctx.set_std_ensemble(opts.get("--ensemble-std", "serial"))
+    return ctx
+
+
+def longest_first(items_by_query, M_by_query, wins_by_query):
+    """The queries (keys of <items_by_query>) by the estimated cost of their items (dist.item_cost), longest first."""
+    cost = {k: sum(dist.item_cost(M_by_query[k], int(wins_by_query[k]["n"][it.lo:it.hi].sum())) for it in items) for k, items in items_by_query.items()}
+    return sorted(cost, key=lambda k: (-cost[k], k))
+
+
+class _Batch:
+    """The queries [b0, b0 + len(hmms)) of a --workers search while they are alive."""
+
+    def __init__(self, b0, hmms):
+        self.b0, self.hmms = b0, hmms
+        self.names, self.descs, self.lengths = [], [], []
+        self.parts = [[] for _ in hmms]
+        self.t0 = [None] * len(hmms)
+        self.c0 = [None] * len(hmms)
+
+
+def _workers_search(opts, hmmfile, seqfile, nq, write, device, chunk_bytes, block_nt, resident_bytes):
+    """The single-process search with --workers N > 1: _rank_search's loop for one rank (pieces of the targets outermost, a
+    query's items of a piece searched by _search_items, the query merged and rendered by _render_query), the queries of a batch of
+    2N spread over N contexts.  Resident targets are one piece: a query is rendered by the worker that searched it, and the next
+    batch is prepared and handed out while the last one's queries are still running (feed_batches: never more than that one).
+    Streamed targets: a piece is released when the generator
+    resumes, so every worker is done with it first; the batch is rendered after its last piece.  Raises what the search of the
+    lowest failing query raised (CtMismatch, ba.FastaFormatError, ...), the queries before it written."""
+    n = opts["--workers"]
+    ct = opts.get("--ct", 1)
+    strand = opts.get("--strand", "both")
+    block_length = opts.get("--block_length", dist.BLOCK_LENGTH)
+    qdescs = model_descriptions(hmmfile)
+    ctxs = [new_context(device, opts) for _ in range(n)]
+    targets = Targets(ctxs[0], seqfile, chunk_bytes, resident_bytes)
+    src = _CodesSource(targets)
+    writer = OrderedWriter(write, 2 * n)
+
+    def render(b, k):
+        q = b.b0 + k
+        parts, b.parts[k] = b.parts[k], None
+        writer.put(q, _render_query(q, b.hmms[k], qdescs[q] if q < len(qdescs) else None, parts, opts, b.names, b.descs, b.lengths, src,
+                                    b.t0[k], b.c0[k]))
+
+    def work(w, rnd, q):
+        b, piece, ft, wins, items, last = rnd.payload
+        k = q - b.b0
+        if ft is not None:
+            if b.t0[k] is None:
+                b.t0[k], b.c0[k] = time.time(), os.times()
+            for it, stats, geometry, stream in _search_items(ctxs[w], b.hmms[k], ft, wins[k], items[k], opts, block_nt, lambda: pool.cancelled(q)):
+                b.parts[k].append(((piece, it.lo), {f: int(getattr(stats, f)) for f in STAT_FIELDS}, geometry, stream))
+        if last:
+            render(b, k)
+
+    pool = WorkerPool(n, work, writer, start=lambda w: ctxs[w].synchronize())    # binds thread w to its context's device
+    shared = None                                        # names, descriptions, lengths of resident targets: one list for every batch
+
+    def prepare(b0, b1):
+        """Loads the models [b0, b1) and hands their jobs to the pool, piece after piece."""
+        nonlocal shared
+        hmms = []
+        for q in range(b0, b1):
+            hmm = ba.HMM(hmmfile, q)
+            if hmm.ct != ct:
+                pool.fail(q, CtMismatch(CT_MISMATCH % (ct, hmmfile, hmm.ct, ct)))
+                break
+            hmms.append(hmm)
+        if not hmms:
+            return
+        b = _Batch(b0, hmms)
+        if shared is not None:
+            b.names, b.descs, b.lengths = shared
+        base = [0] * len(hmms)                           # residues of the earlier pieces, per query
+        try:
+            for piece, (ft, lo, hi) in enumerate(targets.pieces()):
+                recs = ft.records()[lo:hi]
+                if shared is None:
+                    for name, desc in ba.fasta_headers(targets.path, recs):
+                        b.names.append(name); b.descs.append(desc)
+                    b.lengths.extend(int(x) for x in recs["length"])
+                    if targets.resident:
+                        shared = (b.names, b.descs, b.lengths)
+                wins = [ft.windows(h.max_length, block_length, lo, hi) for h in hmms]
+                items = {k: [] for k in range(len(hmms))}
+                for it in search_plan(wins, [h.M for h in hmms], 1, strand):
+                    it.nres_before += base[it.query]
+                    items[it.query].append(it)
+                for k in range(len(hmms)):
+                    base[k] += int(window_nres(wins[k], strand).sum())
+                order = longest_first(items, [h.M for h in hmms], wins)
+                pool.submit(Round([b0 + k for k in order], (b, piece, ft, wins, items, targets.resident), admit=(piece == 0)))
+                if not targets.resident:
+                    pool.barrier()                       # the piece is released next.  After a failure at query k the queries before k
+        except ba.FastaFormatError as e:                 # still get their later pieces and are rendered; the jobs from k on are skipped
+            pool.fail(b0, e)
+        if not targets.resident:
+            pool.submit(Round(range(b0, b0 + len(hmms)), (b, None, None, None, None, True)))
+            pool.barrier()
+
+    try:
+        feed_batches(pool, nq, 2 * n, prepare)
+    finally:
+        pool.close(sys.exc_info()[1] if pool.failure is None else None)     # the coordinator itself raised: nothing queued is searched
+
+
+def feed_batches(pool, nq, size, prepare):
+    """prepare(b0, b1) for the batches of <size> queries one after the other, each only once every query before the previous batch
+    is written: beside the batch the workers are on, one more is prepared and queued, never more, so what the coordinator holds
+    (models, window tables, items) does not grow with the number of queries.  Ends at the first failure; raises it after the
+    queries before it are written."""
+    for b0 in range(0, nq, size):
+        if not pool.wait_written(b0 - size):
+            break
+        prepare(b0, min(nq, b0 + size))
+        if pool.failure is not None:
+            break
+    pool.wait()
+
+
 def _rank_search(argv, opts, hmmfile, seqfile, rank, world, device, dev, chunk_bytes, block_nt, resident_bytes, laps):
     nq = ba.HMM.count(hmmfile)
     qdescs = model_descriptions(hmmfile)
     strand = opts.get("--strand", "both")
     block_length = opts.get("--block_length", dist.BLOCK_LENGTH)
-    ofp = tblfp = None
+    ofp = tblfp = pool = None
     if rank == 0:
         ofp = open(opts["-o"], "w") if "-o" in opts else sys.stdout
         tblfp = open(opts["--tblout"], "w") if "--tblout" in opts else None
@@ -704,11 +1026,15 @@ def _rank_search(argv, opts, hmmfile, seqfile, rank, world, device, dev, chunk_b
             ofp.write(output_header(opts, hmmfile, seqfile))
             ofp.flush()
         t = time.perf_counter()
-        ctx = ba.Context(device)
-        ctx.set_fs_strict(True)
-        ctx.set_fs_ensemble(opts.get("--ensemble", "serial"))
-        ctx.set_std_ensemble(opts.get("--ensemble-std", "serial"))
+        ctxs = [new_context(device, opts) for _ in range(opts.get("--workers", 1))]
+        ctx = ctxs[0]
         laps["context_s"] = time.perf_counter() - t
+        found = {}                                       # --workers: what the workers found in the piece at hand, per query of the batch
+        if len(ctxs) > 1:
+            def work(w, rnd, q):
+                k, h, ft, wk, mine = rnd.payload[q]
+                found[k] = _search_items(ctxs[w], h, ft, wk, mine, opts, block_nt, lambda: pool.cancelled(q))
+            pool = WorkerPool(len(ctxs), work, start=lambda w: ctxs[w].synchronize())     # binds thread w to this rank's device
         targets = Targets(ctx, seqfile, chunk_bytes, resident_bytes)
         src = _CodesSource(targets)
         for b0 in range(0, nq, BATCH_QUERIES):
@@ -729,15 +1055,24 @@ def _rank_search(argv, opts, hmmfile, seqfile, rank, world, device, dev, chunk_b
                 wins = [ft.windows(h.max_length, block_length, lo, hi) for h in hmms]
                 plan = search_plan(wins, [h.M for h in hmms], world, strand)
                 ts = time.perf_counter()
+                mine_by = {}
                 for k, h in enumerate(hmms):
                     n_items[k] += sum(1 for it in plan if it.query == k)
-                    mine = [it for it in plan if it.query == k and it.owner == rank]
-                    for it in mine:
+                    mine_by[k] = [it for it in plan if it.query == k and it.owner == rank]
+                    for it in mine_by[k]:
                         it.nres_before += base[k]
-                    for it, stats, geometry, stream in (_search_items(ctx, h, ft, wins[k], mine, opts, block_nt) if mine else []):
+                    base[k] += int(window_nres(wins[k], strand).sum())
+                if len(ctxs) > 1:                        # this rank's items of the piece side by side, a query per worker, longest first
+                    found.clear()
+                    order = longest_first({k: m for k, m in mine_by.items() if m}, [h.M for h in hmms], wins)
+                    pool.submit(Round([qs[k] for k in order], {qs[k]: (k, hmms[k], ft, wins[k], mine_by[k]) for k in order}))
+                    pool.wait()                          # every worker is done with the piece before it is released
+                for k, h in enumerate(hmms):
+                    mine = mine_by[k]
+                    for it, stats, geometry, stream in ((found[k] if len(ctxs) > 1 else _search_items(ctx, h, ft, wins[k], mine, opts, block_nt))
+                                                        if mine else []):
                         by_dest.setdefault(dist.query_owner(qs[k], world), bytearray()).extend(
                             _pack_item(k, piece, it.lo, stats, geometry, stream))
-                    base[k] += int(window_nres(wins[k], strand).sum())
                 laps["items"] += sum(1 for it in plan if it.owner == rank)
                 laps["search_s"] += time.perf_counter() - ts
                 tb = time.perf_counter()
@@ -772,6 +1107,8 @@ def _rank_search(argv, opts, hmmfile, seqfile, rank, world, device, dev, chunk_b
                 tblfp.write(tabular_tail(hmmfile, seqfile, argv))
             ofp.write("[ok]\n")
     finally:
+        if pool is not None:
+            pool.close(sys.exc_info()[1])
         if ofp is not None and ofp is not sys.stdout:
             ofp.close()
         elif ofp is not None:
@@ -836,7 +1173,9 @@ def rank_main(argv, chunk_bytes=64 << 20, block_nt=256_000_000, resident_bytes=8
 
 def run(argv, stdout=None, chunk_bytes=64 << 20, block_nt=256_000_000, resident_bytes=8 << 30, device=0):
     """The whole search; returns the exit status.  chunk_bytes: FASTA bytes per upload; block_nt: nucleotides per pipeline call;
-    resident_bytes: the device-memory budget for the digitised targets kept across queries."""
+    resident_bytes: the device-memory budget for the digitised targets kept across queries.  With --workers N > 1 and no
+    BATH_HIP_HOST_THREADS in the environment, the variable is set in os.environ (process-wide: the library reads it at every
+    ensemble) for the time of the search and removed afterwards; a caller with threads of its own that read or set it sees that."""
     stdout = stdout or sys.stdout
     try:
         opts, hmmfile, seqfile = parse_args(argv)
@@ -865,34 +1204,48 @@ def run(argv, stdout=None, chunk_bytes=64 << 20, block_nt=256_000_000, resident_
     descs = model_descriptions(hmmfile)
     ofp = open(opts["-o"], "w") if "-o" in opts else stdout
     tblfp = open(opts["--tblout"], "w") if "--tblout" in opts else None
+    workers = opts.get("--workers", 1)
+    threads = host_threads_per_worker(workers) if workers > 1 else None
     try:
         ofp.write(output_header(opts, hmmfile, seqfile))
-        ctx = ba.Context(device)
-        ctx.set_fs_strict(True)
-        ctx.set_fs_ensemble(opts.get("--ensemble", "serial"))
-        ctx.set_std_ensemble(opts.get("--ensemble-std", "serial"))
-        targets = Targets(ctx, seqfile, chunk_bytes, resident_bytes)
-        src = _CodesSource(targets)
-        for q in range(nq):
-            hmm = ba.HMM(hmmfile, q)
-            if hmm.ct != ct:
-                sys.stderr.write(CT_MISMATCH % (ct, hmmfile, hmm.ct, ct))
-                return 1
-            t0, c0 = time.time(), os.times()
-            r = search_query(ctx, hmm, targets, opts, block_nt, None)
-            c1 = os.times()
-            ofp.write(main_output_query(hmm, descs[q] if q < len(descs) else None, r, opts, src, time.time() - t0,
-                                        (c1.user - c0.user, c1.system - c0.system)))
-            if tblfp:
-                tblfp.write(r["th"].tblout(hmm.name, hmm.acc, hmm.M, fs_pipe="--fs" in opts, show_cigar="--cigar" in opts, show_header=(q == 0)))
-            ofp.flush()
+        if workers > 1:
+            def write(q, text):
+                ofp.write(text[0])
+                if tblfp:
+                    tblfp.write(text[1])
+                ofp.flush()
+            if threads is not None:                  # the library reads it at every ensemble: each worker context's share
+                os.environ["BATH_HIP_HOST_THREADS"] = str(threads)
+            _workers_search(opts, hmmfile, seqfile, nq, write, device, chunk_bytes, block_nt, resident_bytes)
+        else:
+            ctx = new_context(device, opts)
+            targets = Targets(ctx, seqfile, chunk_bytes, resident_bytes)
+            src = _CodesSource(targets)
+            for q in range(nq):
+                hmm = ba.HMM(hmmfile, q)
+                if hmm.ct != ct:
+                    sys.stderr.write(CT_MISMATCH % (ct, hmmfile, hmm.ct, ct))
+                    return 1
+                t0, c0 = time.time(), os.times()
+                r = search_query(ctx, hmm, targets, opts, block_nt, None)
+                c1 = os.times()
+                ofp.write(main_output_query(hmm, descs[q] if q < len(descs) else None, r, opts, src, time.time() - t0,
+                                            (c1.user - c0.user, c1.system - c0.system)))
+                if tblfp:
+                    tblfp.write(r["th"].tblout(hmm.name, hmm.acc, hmm.M, fs_pipe="--fs" in opts, show_cigar="--cigar" in opts, show_header=(q == 0)))
+                ofp.flush()
         if tblfp:
             tblfp.write(tabular_tail(hmmfile, seqfile, argv))
         ofp.write("[ok]\n")
     except ba.FastaFormatError as e:
         sys.stderr.write("Error: %s: %s\n" % (seqfile, e))
         return 1
+    except CtMismatch as e:
+        sys.stderr.write(str(e))
+        return 1
     finally:
+        if threads is not None:
+            os.environ.pop("BATH_HIP_HOST_THREADS", None)
         if ofp is not stdout:
             ofp.close()
         if tblfp:

@@ -357,6 +357,11 @@ struct bath_hip_fasta {
   bath_hip_ctx *ctx = nullptr;
   bath::DevBuf raw[2];                 // chunk bytes, two slots: the upload of chunk k+1 may run while chunk k is written out
   hipEvent_t ev_up = nullptr, ev_free[2] = {nullptr, nullptr};
+  hipEvent_t ev_ready = nullptr;       // on the ingest stream after the last feed / finish: what another context's gather waits on
+                                       // (release records nothing: its copy and hipFree are synchronous, done before d_codes is republished)
+  std::mutex mu;                       // the host state below, for gathers of several contexts' threads (bath_hip_fasta_seqs_for)
+  std::condition_variable cv_idle;     // gathers == 0
+  int gathers = 0;                     // gathers between reading d_codes and the end of their kernel: release waits for none
   int slot = 0;
   bath::DevBuf agg, entry;
   uint8_t *d_codes = nullptr;          // symbols [sym_base, syms) of the file
@@ -376,6 +381,7 @@ int fasta_sync_records(bath_hip_fasta *f) {
   bath_hip_ctx *ctx = f->ctx;
   const int64_t R = f->h_state->recs;
   if (f->recs_valid == R) return BATH_OK;
+  BATH_HIP_TRY(ctx, hipSetDevice(ctx->device));
   std::vector<int64_t> h((size_t)std::max<int64_t>(R, 1) * 3);
   if (R > 0) {
     BATH_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
@@ -427,6 +433,7 @@ extern "C" int bath_hip_fasta_create(bath_hip_ctx *ctx, bath_hip_fasta **ret) {
     BATH_HIP_TRY(ctx, hipMemcpy(f->d_state, f->h_state, sizeof(FastaState), hipMemcpyHostToDevice));
     BATH_HIP_TRY(ctx, hipEventCreateWithFlags(&f->ev_up, hipEventDisableTiming));
     for (auto &e : f->ev_free) BATH_HIP_TRY(ctx, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    BATH_HIP_TRY(ctx, hipEventCreateWithFlags(&f->ev_ready, hipEventDisableTiming));
     return BATH_OK;
   };
   if (int st = init(); st != BATH_OK) { bath_hip_fasta_destroy(f); return st; }
@@ -447,6 +454,7 @@ extern "C" void bath_hip_fasta_destroy(bath_hip_fasta *f) {
   if (f->h_state) (void)hipHostFree(f->h_state);
   if (f->ev_up) (void)hipEventDestroy(f->ev_up);
   for (auto e : f->ev_free) if (e) (void)hipEventDestroy(e);
+  if (f->ev_ready) (void)hipEventDestroy(f->ev_ready);
   delete f;
 }
 
@@ -502,6 +510,7 @@ extern "C" int bath_hip_fasta_feed(bath_hip_fasta *f, const void *bytes, int64_t
                      f->d_codes, f->sym_base, f->d_rec, f->d_rec + f->rec_cap, f->d_rec + 2 * f->rec_cap);
   BATH_HIP_TRY(ctx, hipGetLastError());
   BATH_HIP_TRY(ctx, hipEventRecord(f->ev_free[s], ctx->stream));
+  BATH_HIP_TRY(ctx, hipEventRecord(f->ev_ready, ctx->stream));
   f->fed += n;
   return BATH_OK;
 }
@@ -509,8 +518,11 @@ extern "C" int bath_hip_fasta_feed(bath_hip_fasta *f, const void *bytes, int64_t
 extern "C" int bath_hip_fasta_finish(bath_hip_fasta *f) {
   if (!f) return BATH_EINVAL;
   if (f->failed) return BATH_EINVAL;
+  std::lock_guard<std::mutex> g(f->mu);
   f->finished = true;
+  BATH_HIP_TRY(f->ctx, hipSetDevice(f->ctx->device));
   BATH_HIP_TRY(f->ctx, hipStreamSynchronize(f->ctx->stream));
+  BATH_HIP_TRY(f->ctx, hipEventRecord(f->ev_ready, f->ctx->stream));
   f->recs_valid = -1;
   return fasta_sync_records(f);
 }
@@ -520,6 +532,7 @@ extern "C" int64_t bath_hip_fasta_symbols(bath_hip_fasta *f) { return f ? f->h_s
 
 extern "C" int bath_hip_fasta_records(bath_hip_fasta *f, int64_t lo, int64_t n, bath_fasta_record *out) {
   if (!f || lo < 0 || n < 0 || lo + n > f->h_state->recs) return BATH_EINVAL;
+  std::lock_guard<std::mutex> g(f->mu);
   if (int st = fasta_sync_records(f); st != BATH_OK) return st;
   if (n > 0) std::memcpy(out, f->recs.data() + lo, (size_t)n * sizeof(bath_fasta_record));
   return BATH_OK;
@@ -535,6 +548,7 @@ extern "C" int bath_hip_fasta_error(const bath_hip_fasta *f, int64_t *offset, in
 extern "C" int64_t bath_hip_fasta_windows(bath_hip_fasta *f, int64_t lo, int64_t hi, int32_t max_length, int32_t block_length,
                                           bath_fasta_window *out, int64_t cap) {
   if (!f || lo < 0 || hi < lo || hi > f->h_state->recs || max_length < 1 || block_length < 1) return -1;
+  std::lock_guard<std::mutex> g(f->mu);
   if (fasta_sync_records(f) != BATH_OK) return -1;
   const int64_t C = 3 * (int64_t)max_length;
   int64_t k = 0;
@@ -553,17 +567,24 @@ extern "C" int64_t bath_hip_fasta_windows(bath_hip_fasta *f, int64_t lo, int64_t
   return k;
 }
 
-extern "C" int bath_hip_fasta_seqs(bath_hip_fasta *f, const bath_fasta_window *w, int64_t n, bath_hip_seqs **ret) {
-  *ret = nullptr;
-  if (!f || n < 0 || (n > 0 && !w)) return BATH_EINVAL;
-  bath_hip_ctx *ctx = f->ctx;
-  if (int st = fasta_sync_records(f); st != BATH_OK) return st;
+namespace {
+// The windows <w> of <f> as a block of <ctx>: the owner's own context (bath_hip_fasta_seqs) or another one of the same device
+// (bath_hip_fasta_seqs_for: <shared>).  The handle's host tables are read under its mutex; the gather runs on <ctx>'s stream and is
+// complete when the call returns; f->gathers counts the calls between those two points, which bath_hip_fasta_release waits for.
+int fasta_gather(bath_hip_ctx *ctx, bath_hip_fasta *f, const bath_fasta_window *w, int64_t n, bath_hip_seqs **ret, bool shared) {
   std::vector<WinCopy> cp((size_t)std::max<int64_t>(n, 1));
   bath_hip_seqs *sq = new bath_hip_seqs();
   sq->ctx = ctx; sq->n = n;
   sq->h_off.resize((size_t)n); sq->h_len.resize((size_t)n); sq->h_context.resize((size_t)n);
   int64_t pos = 0;
   bool any_context = false;
+  const uint8_t *d_codes = nullptr;
+  std::unique_lock<std::mutex> lock(f->mu);
+  if (int st = fasta_sync_records(f); st != BATH_OK) {
+    if (shared) ctx->set_error("FASTA targets: the record table could not be read: " + f->ctx->err);
+    delete sq;
+    return st;
+  }
   for (int64_t i = 0; i < n; i++) {
     const bath_fasta_window &x = w[i];
     const bool ok = x.target >= 0 && x.target < (int64_t)f->recs.size() && x.n >= 0 && x.context >= 0 && x.context <= x.n && x.start0 >= 0 &&
@@ -578,8 +599,13 @@ extern "C" int bath_hip_fasta_seqs(bath_hip_fasta *f, const bath_fasta_window *w
     pos += padded;
   }
   sq->total_aligned = pos;
+  d_codes = f->d_codes;
+  f->gathers++;
+  lock.unlock();
   auto build = [&]() -> int {
     const size_t bytes = (size_t)pos + 64;
+    BATH_HIP_TRY(ctx, hipSetDevice(ctx->device));
+    if (shared) BATH_HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, f->ev_ready, 0));   // the codes are written: ingest stream -> this one
     BATH_HIP_TRY(ctx, hipMalloc((void **)&sq->d_data, bytes));
     BATH_HIP_TRY(ctx, hipMalloc((void **)&sq->d_off, (size_t)std::max<int64_t>(n, 1) * sizeof(int64_t)));
     BATH_HIP_TRY(ctx, hipMalloc((void **)&sq->d_len, (size_t)std::max<int64_t>(n, 1) * sizeof(int32_t)));
@@ -591,7 +617,7 @@ extern "C" int bath_hip_fasta_seqs(bath_hip_fasta *f, const bath_fasta_window *w
       BATH_HIP_TRY(ctx, hipMemcpyAsync(sq->d_off, sq->h_off.data(), (size_t)n * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
       BATH_HIP_TRY(ctx, hipMemcpyAsync(sq->d_len, sq->h_len.data(), (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
       if (n > INT32_MAX) { ctx->set_error("too many windows in one block"); return BATH_EINVAL; }
-      hipLaunchKernelGGL(window_gather_kernel, dim3((unsigned)n), dim3(TPB), 0, ctx->stream, f->d_codes, d_cp, sq->d_data);
+      hipLaunchKernelGGL(window_gather_kernel, dim3((unsigned)n), dim3(TPB), 0, ctx->stream, d_codes, d_cp, sq->d_data);
       BATH_HIP_TRY(ctx, hipGetLastError());
       BATH_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
       (void)hipFree(d_cp);
@@ -605,18 +631,39 @@ extern "C" int bath_hip_fasta_seqs(bath_hip_fasta *f, const bath_fasta_window *w
     BATH_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     return BATH_OK;
   };
-  if (int st = build(); st != BATH_OK) { bath_hip_seqs_destroy(sq); return st; }
+  const int st = build();
+  if (st != BATH_OK) (void)hipStreamSynchronize(ctx->stream);      // nothing of this call reads the codes any more
+  lock.lock();
+  if (--f->gathers == 0) f->cv_idle.notify_all();
+  lock.unlock();
+  if (st != BATH_OK) { bath_hip_seqs_destroy(sq); return st; }
   *ret = sq;
   return BATH_OK;
+}
+}  // namespace
+
+extern "C" int bath_hip_fasta_seqs(bath_hip_fasta *f, const bath_fasta_window *w, int64_t n, bath_hip_seqs **ret) {
+  *ret = nullptr;
+  if (!f || n < 0 || (n > 0 && !w)) return BATH_EINVAL;
+  return fasta_gather(f->ctx, f, w, n, ret, false);
+}
+
+extern "C" int bath_hip_fasta_seqs_for(bath_hip_ctx *consumer, bath_hip_fasta *f, const bath_fasta_window *w, int64_t n, bath_hip_seqs **ret) {
+  if (ret) *ret = nullptr;
+  if (!consumer || !f || !ret || n < 0 || (n > 0 && !w)) return BATH_EINVAL;
+  if (consumer->device != f->ctx->device) { consumer->set_error("FASTA targets of another device"); return BATH_EINVAL; }
+  return fasta_gather(consumer, f, w, n, ret, consumer != f->ctx);
 }
 
 extern "C" int bath_hip_fasta_codes(bath_hip_fasta *f, int64_t target, int64_t start, int64_t n, uint8_t *out) {
   if (!f || n < 0) return BATH_EINVAL;
   bath_hip_ctx *ctx = f->ctx;
+  std::lock_guard<std::mutex> g(f->mu);
   if (int st = fasta_sync_records(f); st != BATH_OK) return st;
   if (target < 0 || target >= (int64_t)f->recs.size() || start < 0 || start + n > f->recs[(size_t)target].length ||
       f->recs[(size_t)target].sym_start + start < f->sym_base) { ctx->set_error("codes outside the target"); return BATH_EINVAL; }
   if (n == 0) return BATH_OK;
+  BATH_HIP_TRY(ctx, hipSetDevice(ctx->device));      // a worker thread renders: the copy below is from this context's device
   BATH_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   BATH_HIP_TRY(ctx, hipMemcpy(out, f->d_codes + (f->recs[(size_t)target].sym_start + start - f->sym_base), (size_t)n, hipMemcpyDeviceToHost));
   return BATH_OK;
@@ -625,12 +672,15 @@ extern "C" int bath_hip_fasta_codes(bath_hip_fasta *f, int64_t target, int64_t s
 extern "C" int bath_hip_fasta_release(bath_hip_fasta *f, int64_t lo) {
   if (!f || lo < 0 || lo > f->h_state->recs) return BATH_EINVAL;
   bath_hip_ctx *ctx = f->ctx;
+  std::unique_lock<std::mutex> lock(f->mu);
+  f->cv_idle.wait(lock, [&] { return f->gathers == 0; });          // no gather in flight reads the codes freed below
   if (int st = fasta_sync_records(f); st != BATH_OK) return st;
   const int64_t base = lo < (int64_t)f->recs.size() ? f->recs[(size_t)lo].sym_start : f->h_state->syms;
   if (base <= f->sym_base) return BATH_OK;
   const int64_t keep = f->h_state->syms - base;
   uint8_t *q = nullptr;
   const int64_t cap = std::max<int64_t>(keep + keep / 2, 1 << 16);
+  BATH_HIP_TRY(ctx, hipSetDevice(ctx->device));
   BATH_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   BATH_HIP_TRY(ctx, hipMalloc((void **)&q, (size_t)cap));
   if (keep > 0) BATH_HIP_TRY(ctx, hipMemcpy(q, f->d_codes + (base - f->sym_base), (size_t)keep, hipMemcpyDeviceToDevice));

@@ -196,6 +196,7 @@ extern "C" int bath_hip_trim(bath_hip_ctx *ctx) {
 extern "C" const char *bath_hip_last_error(const bath_hip_ctx *ctx) { return ctx ? ctx->err.c_str() : "no context"; }
 
 extern "C" int bath_hip_synchronize(bath_hip_ctx *ctx) {
+  BATH_HIP_TRY(ctx, hipSetDevice(ctx->device));      // HIP's current device is per host thread: a new thread starts on device 0
   BATH_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   return BATH_OK;
 }
@@ -324,6 +325,7 @@ extern "C" int bath_hip_oprofile_convert(bath_hip_ctx *ctx, const bath_profile *
   *ret = nullptr;
   const int M = gm->M;
   if (M < 1) { ctx->set_error("profile has no nodes"); return BATH_EINVAL; }
+  BATH_HIP_TRY(ctx, hipSetDevice(ctx->device));      // the calling thread may be a new one (a worker beside the context's creator)
   const size_t W = (size_t)M + 1;
   auto msc = [&](int k, int x) { return gm->rsc[(size_t)x * W * 2 + 2 * k]; };
   auto tsc = [&](int k, int s) { return gm->tsc[(size_t)k * 8 + s]; };   // valid for 0 <= k < M
@@ -561,12 +563,26 @@ extern "C" void bath_hip_seqs_destroy(bath_hip_seqs *sq) {
 
 extern "C" int64_t bath_hip_seqs_count(const bath_hip_seqs *sq) { return sq->n; }
 
+extern "C" int64_t bath_hip_seqs_read(const bath_hip_seqs *sq, uint8_t *data, int64_t cap, int64_t *offsets, int32_t *lengths, int32_t *context) {
+  if (!sq || cap < 0 || (cap > 0 && !data)) return -1;
+  bath_hip_ctx *ctx = sq->ctx;
+  const int64_t bytes = sq->total_aligned + 64;
+  if (hipSetDevice(ctx->device) != hipSuccess || hipStreamSynchronize(ctx->stream) != hipSuccess) { ctx->set_error("seqs_read: the block's stream failed"); return -1; }
+  auto get = [&](void *dst, const void *src, size_t n) { return n == 0 || !dst || hipMemcpy(dst, src, n, hipMemcpyDeviceToHost) == hipSuccess; };
+  const bool ok = get(data, sq->d_data, (size_t)std::min(cap, bytes)) && get(offsets, sq->d_off, (size_t)sq->n * sizeof(int64_t)) &&
+                  get(lengths, sq->d_len, (size_t)sq->n * sizeof(int32_t)) &&
+                  (!context || (sq->d_context ? get(context, sq->d_context, (size_t)sq->n * sizeof(int32_t)) : (std::memset(context, 0, (size_t)sq->n * sizeof(int32_t)), true)));
+  if (!ok) { ctx->set_error("seqs_read: copy to the host failed"); return -1; }
+  return bytes;
+}
+
 // ESL_SQ.C of the windows of a long target read with esl_sqio_ReadWindow(dbfp, 3 * max_length, block_length, .)
 // (bathsearch.c:1099): the pipeline skips ORFs that lie inside the context (p7_pipeline.c:1635-1637) and counts only the
 // new residues (pli->nres += dnaSeq->W, bathsearch.c:1258,1268).
 extern "C" int bath_hip_seqs_set_context(bath_hip_seqs *sq, const int32_t *context) {
   if (!sq || sq->is_part) return BATH_EINVAL;
   bath_hip_ctx *ctx = sq->ctx;
+  BATH_HIP_TRY(ctx, hipSetDevice(ctx->device));
   for (bath_hip_seqs *part : sq->parts) bath_hip_seqs_destroy(part);    // parts carry a pointer into d_context: rebuild on next use
   sq->parts.clear();
   sq->cache_minlen = -1;
@@ -581,6 +597,7 @@ extern "C" int bath_hip_seqs_set_context(bath_hip_seqs *sq, const int32_t *conte
 extern "C" int bath_hip_seqs_create(bath_hip_ctx *ctx, const uint8_t *dsq, const int64_t *offsets, int64_t n, bath_hip_seqs **ret) {
   *ret = nullptr;
   if (n < 0) return BATH_EINVAL;
+  BATH_HIP_TRY(ctx, hipSetDevice(ctx->device));
   bath_hip_seqs *sq = new bath_hip_seqs();
   sq->ctx = ctx; sq->n = n;
   sq->h_off.resize(n); sq->h_len.resize(n);

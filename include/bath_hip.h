@@ -214,6 +214,10 @@ int  bath_hip_oprofile_get_fwd(const bath_hip_oprofile *om, float *rf, float *tf
 int     bath_hip_seqs_create(bath_hip_ctx *ctx, const uint8_t *dsq, const int64_t *offsets, int64_t n, bath_hip_seqs **ret);
 void    bath_hip_seqs_destroy(bath_hip_seqs *sq);
 int64_t bath_hip_seqs_count(const bath_hip_seqs *sq);
+/* The block as it lies on the device, copied to the host (for checks and tools): up to <cap> bytes of its data -- every sequence
+ * at its offset, padded to 16 with 0x1d, 64 more padding bytes behind the last -- and, where the pointer is not NULL, the <n>
+ * offsets, lengths and contexts (zeros when none are set).  Returns the number of data bytes the block holds, -1 on an error. */
+int64_t bath_hip_seqs_read(const bath_hip_seqs *sq, uint8_t *data, int64_t cap, int64_t *offsets, int32_t *lengths, int32_t *context);
 /* Windows of a long target (esl_sqio_ReadWindow with context, bathsearch.c:1099): context[i] = ESL_SQ.C of window i, the
  * leading nucleotides that also ended the previous window.  ORFs inside the context are skipped (p7_pipeline.c:1635-1637)
  * and only the new residues are counted in stats->nres (bathsearch.c:1258).  NULL clears it. */
@@ -270,9 +274,21 @@ int     bath_hip_fasta_error(const bath_hip_fasta *f, int64_t *offset, int64_t *
 int64_t bath_hip_fasta_windows(bath_hip_fasta *f, int64_t lo, int64_t hi, int32_t max_length, int32_t block_length, bath_fasta_window *out, int64_t cap);
 /* a block of the given windows, laid out as bath_hip_seqs_create lays out sequences, with their contexts set */
 int     bath_hip_fasta_seqs(bath_hip_fasta *f, const bath_fasta_window *w, int64_t n, bath_hip_seqs **ret);
+/* The same block for another context of the handle's device: a search that runs several queries side by side, one context and one
+ * host thread each, over one resident copy of the targets.  The block belongs to <consumer> (allocated for it, laid out as
+ * bath_hip_fasta_seqs lays it out, contexts set; destroyed like any other); the gather runs on <consumer>'s stream, after that
+ * stream has waited on an event recorded on the ingest stream behind the last feed / finish, and is complete when the call returns.
+ * Ownership and ordering: the handle, its codes and its tables stay the creating context's.  Once the handle is finished, or
+ * between two feeds, any number of host threads may call this at once, each with its own <consumer>, beside records / windows /
+ * codes / seqs calls: the handle's host tables are read under a mutex inside it.  feed and finish must not run beside them.
+ * bath_hip_fasta_release waits for every gather in flight before it frees codes, so the caller need not synchronise the
+ * consumers first; blocks returned earlier are copies and stay valid.  Destroy the handle only after the last such call returned.
+ * Errors are <consumer>'s (bath_hip_last_error(consumer)); the handle stays usable.  <consumer> may be the handle's own context. */
+int     bath_hip_fasta_seqs_for(bath_hip_ctx *consumer, bath_hip_fasta *f, const bath_fasta_window *w, int64_t n, bath_hip_seqs **ret);
 /* codes [start, start + n) of record <target> to the host (the windows of reported hits, for their alignments) */
 int     bath_hip_fasta_codes(bath_hip_fasta *f, int64_t target, int64_t start, int64_t n, uint8_t *out);
-/* drop the codes of the records before <lo> from device memory (a file streamed through a budget); their windows are gone */
+/* drop the codes of the records before <lo> from device memory (a file streamed through a budget); their windows are gone.
+ * Waits for the gathers of other contexts that are in flight (bath_hip_fasta_seqs_for). */
 int     bath_hip_fasta_release(bath_hip_fasta *f, int64_t lo);
 
 /* ------------------------------------------------------------------------------------------
