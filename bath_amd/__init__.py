@@ -326,6 +326,15 @@ ABI = {
     "bath_hip_fs5_envelopes_x": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, C.POINTER(Fs5Result), _f32p, _f32p, _f32p, _f32p]),
     "bath_hip_fs5_forward_full": (C.c_int, [_vp, _vp, _vp, C.c_int, _f32p, _f32p, _f32p]),
     "bath_hip_fs5_envelopes": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, C.POINTER(Fs5Result), _f32p, _i64p, _f32p, _i64p]),
+    "bath_hip_fs5_forward_parser": (C.c_int, [_vp, _vp, _vp, C.c_int, _f32p]),
+    "bath_calib_sample": (C.c_int, [C.POINTER(C.c_uint32), _f32p, C.c_int, C.c_int, C.c_int, _u8p]),
+    "bath_gumbel_fit_complete": (C.c_int, [C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "bath_gumbel_invcdf": (C.c_double, [C.c_double, C.c_double, C.c_double]),
+    "bath_calib_tau": (C.c_int, [C.POINTER(C.c_double), C.c_int, C.c_double, C.c_double, C.POINTER(C.c_double)]),
+    "bath_bg_fs_nullone": (C.c_float, [C.c_int]),
+    "bath_hmm_max_length": (C.c_int, [C.POINTER(_Hmm), C.c_double]),
+    "bath_hip_calibrate_fs": (C.c_int, [_vp, C.POINTER(_Hmm), C.c_int, C.POINTER(C.c_uint32), C.c_int, C.c_int, C.c_double,
+                                        C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
 }
 
 _lib = None
@@ -1507,3 +1516,89 @@ def rng_jump(seed, n):
     if lib().bath_selftest_rng_jump(seed, n, C.byref(x)) != OK:
         raise BathError("rng_jump failed")
     return x.value
+
+
+def FS5ForwardParser(ctx, om5, dna, cfg_len_amino=100):
+    """The score of p7_Forward_Frameshift in the multihit configuration of <cfg_len_amino> per window, and nothing else: no matrix
+    leaves the kernel (what calibration needs of p7_ForwardParser_Frameshift_5Codons).  Always strict log-sums."""
+    sc = np.zeros(dna.n, dtype=np.float32)
+    ctx._check(lib().bath_hip_fs5_forward_parser(ctx._h, om5._h, dna._h, cfg_len_amino, _f32(sc)), "fs5_forward_parser")
+    return sc
+
+
+CALIB_SEED, CALIB_L, CALIB_N, CALIB_TAILP = 42, 100, 200, 0.04       # bathconvert.c:128, :157-160
+FS_UNSET = -99999.0                                                   # p7_EVPARAM_UNSET: a tau the model file does not carry
+
+
+def rng_state(seed=CALIB_SEED):
+    """The fast generator's state right after seeding: what calib_sample and calibrate_fs carry from model to model."""
+    return rng_jump(seed, 0)
+
+
+def _f64p(a):
+    return a.ctypes.data_as(C.POINTER(C.c_double))
+
+
+def calib_sample(state, L=CALIB_L, N=CALIB_N, ncbi_table=1, f=None):
+    """N background sequences of L amino acids, reverse-translated with a random synonymous codon each (the stream of
+    p7_fs_Tau_3codons / _5codons): (codes [N, 3L], the generator's state afterwards).  f: 20 frequencies (None: the background)."""
+    st = C.c_uint32(state)
+    dna = np.zeros((N, 3 * L), dtype=np.uint8)
+    fa = None if f is None else np.ascontiguousarray(f, dtype=np.float32)
+    assert fa is None or fa.shape == (20,)
+    if lib().bath_calib_sample(C.byref(st), _f32(fa), ncbi_table, L, N, _u8(dna) if dna.size else None) != OK:
+        raise BathError("calib_sample failed: unknown translation table %d, or a residue without a codon in it" % ncbi_table)
+    return dna, st.value
+
+
+def gumbel_fit_complete(x):
+    """Maximum-likelihood Gumbel (mu, lambda) of complete data (esl_gumbel_FitComplete)."""
+    x = np.ascontiguousarray(x, dtype=np.float64)
+    mu, lam = C.c_double(0), C.c_double(0)
+    st = lib().bath_gumbel_fit_complete(_f64p(x), len(x), C.byref(mu), C.byref(lam))
+    if st != OK:
+        raise BathError("gumbel_fit_complete failed (%d)" % st)
+    return mu.value, lam.value
+
+
+def gumbel_invcdf(p, mu, lam):
+    return lib().bath_gumbel_invcdf(p, mu, lam)
+
+
+def calib_tau(xv, lambda_model, tailp=CALIB_TAILP):
+    """tau of an exponential tail of slope lambda_model from N bit scores (evalues.c:651-658)."""
+    x = np.ascontiguousarray(xv, dtype=np.float64)
+    tau = C.c_double(0)
+    st = lib().bath_calib_tau(_f64p(x), len(x), lambda_model, tailp, C.byref(tau))
+    if st != OK:
+        raise BathError("calib_tau failed (%d)" % st)
+    return tau.value
+
+
+def bg_fs_nullone(L_amino):
+    return lib().bath_bg_fs_nullone(L_amino)
+
+
+def hmm_max_length(hmm, emit_thresh=1e-7):
+    """p7_Builder_MaxLength: MAXL of a model file that has none."""
+    return lib().bath_hmm_max_length(hmm._p, emit_thresh)
+
+
+def kernel_times(ctx):
+    """Per-kernel device times recorded on the context since its spans were last reset (calibrate_fs resets them on entry):
+    {name: (ms, launches, cells, bytes)}."""
+    arr = (KernelTime * 32)()
+    n = lib().bath_hip_kernel_times(ctx._h, 32, arr)
+    return {arr[i].name.decode(): (float(arr[i].ms), int(arr[i].launches), float(arr[i].cells), float(arr[i].bytes)) for i in range(n)}
+
+
+def calibrate_fs(ctx, hmm, ncbi_table, state, L=CALIB_L, N=CALIB_N, tailp=CALIB_TAILP, want_xv=False):
+    """p7_fs_Tau_3codons then p7_fs_Tau_5codons of one model on the GPU: (tau3, tau5, the generator's state afterwards), with
+    want_xv also the two arrays of N bit scores the taus were fitted to."""
+    st = C.c_uint32(state)
+    t3, t5 = C.c_double(0), C.c_double(0)
+    x3 = np.zeros(N, np.float64) if want_xv else None
+    x5 = np.zeros(N, np.float64) if want_xv else None
+    ctx._check(lib().bath_hip_calibrate_fs(ctx._h, hmm._p, ncbi_table, C.byref(st), L, N, tailp, C.byref(t3), C.byref(t5),
+                                           None if x3 is None else _f64p(x3), None if x5 is None else _f64p(x5)), "calibrate_fs")
+    return (t3.value, t5.value, st.value, x3, x5) if want_xv else (t3.value, t5.value, st.value)

@@ -64,6 +64,9 @@ EXCLUSIVE = [("-m", "-M"), ("--textw", "--notextw"), ("-E", "-T"), ("--max", "--
 REQUIRES = {"--frameline": "--fs", "--cigar": "--tblout", "--F4": "--fs"}
 
 
+# bathsearch.c:748-750 (the reference's spelling): a model without the frameshift taus, such as a plain HMMER3 file's
+NOT_FORMATED = "HMM file %s not formated for this version bathsearch. Please run 'bathconvert new_file.bhmm old_file.bhmm'."
+
 CT_MISMATCH = ("Error: Requested codon translation tabel ID %d does not match the codon translation tabel ID of the HMM file %s. "
                "Please either run bathsearch with option '--ct %d' or run bathconvert with option '--ct %d'.\n")
 
@@ -1185,6 +1188,9 @@ def run(argv, stdout=None, chunk_bytes=64 << 20, block_nt=256_000_000, resident_
         if not os.path.exists(seqfile):
             raise UsageError("target file %s not found" % seqfile)
         check_target_file(seqfile)
+        for q in range(nq):                          # before any GPU work: P-values from an unset tau mean nothing
+            if (ba.HMM(hmmfile, q).evparam[6:8] == np.float32(ba.FS_UNSET)).any():
+                raise UsageError(NOT_FORMATED % hmmfile)
     except UsageError as e:
         sys.stderr.write("Error: %s\n" % e)
         return 1

@@ -1,0 +1,221 @@
+// bath_calibrate.hip -- the frameshift Forward taus of a model, by simulation: what bathconvert adds to a HMMER3 file.
+//
+// Reference: p7_fs_Tau_3codons / p7_fs_Tau_5codons (src/evalues.c:608-770) as bathconvert calls them (src/bathconvert.c:128-162):
+// N = 200 sequences of L = 100 amino acids drawn from the background, reverse-translated with a random synonymous codon each
+// (p7_codontable_Create / _GetCodon, src/hmmer.c:197-273), scored by the 3-codon and the 5-codon Forward parsers in the multihit
+// configuration of length L; a Gumbel fitted to the N bit scores; tau where the Gumbel's tail of mass <tailp> starts, moved back to
+// the origin of the exponential tail.  Also p7_Builder_MaxLength (src/p7_builder.c:678), which bathconvert runs for a file without MAXL.
+//
+// Where it runs.  The two parsers are the device's work (bath_hip_fs3_forward_parser; bath_hip_fs5_forward_parser, the score-only
+// instantiation of the regions' chain kernel).  The sampler is a strictly serial consumer of one random-number stream carried from
+// model to model (2 x 200 x 200 steps per model) and its output is 60 KB per parser: host code.  So are the fit (200 numbers) and MAXL.
+//
+// easel is not part of the reference tree, so esl_rsq_xfIID, esl_rnd_FChoose, esl_rnd_Roll, esl_stats_DMean, esl_gumbel_FitComplete
+// and esl_gumbel_invcdf are restated from their published behaviour, as bath_ensemble.hip restates the generator.  The reference
+// redraws a sequence whose odds-ratio parser overflows (eslERANGE, evalues.c:645, :740); the strict log-space kernels cannot
+// overflow, so nothing is redrawn.
+#include <cmath>
+#include <cstdint>
+#include <cstring>
+#include <vector>
+
+#include "bath_common.hpp"
+#include "bath_launch.hpp"
+#include "host_model.hpp"
+
+using namespace bath;
+
+// p7_codontable_Create: for each amino acid its codons in x, y, z order over ACGT; num[a] of them (at most 6)
+static void codon_table(const uint8_t basic[64], uint8_t table[20][6], int num[20]) {
+  for (int a = 0; a < 20; a++) num[a] = 0;
+  for (int c = 0; c < 64; c++) {
+    const int a = basic[c];
+    if (a < 20 && num[a] < 6) table[a][num[a]++] = (uint8_t)c;
+  }
+}
+
+extern "C" int bath_calib_sample(uint32_t *rng_state, const float *f, int ncbi_table, int L, int N, uint8_t *dna) {
+  if (!rng_state || !dna || L < 0 || N < 0) return BATH_EINVAL;
+  if (!f) f = kAminoBg;
+  uint8_t basic[64], table[20][6];
+  int num[20];
+  if (bath_gencode_basic(ncbi_table, basic) != BATH_OK) return BATH_EINVAL;
+  codon_table(basic, table, num);
+  FastRng rng = FastRng::from_state(*rng_state);
+  std::vector<uint8_t> aa((size_t)L);
+  for (int s = 0; s < N; s++) {
+    for (int i = 0; i < L; i++) {                          // esl_rsq_xfIID: L draws of esl_rnd_FChoose (f is used as it stands: no esl_vec_FNorm)
+      int a = -1;
+      while (a < 0) {
+        const float roll = (float)rng.next();
+        float acc = 0.f;
+        for (int q = 0; q < 20; q++) { acc += f[q]; if (roll < acc) { a = q; break; } }
+      }
+      aa[(size_t)i] = (uint8_t)a;
+    }
+    uint8_t *d = dna + (size_t)s * 3 * L;
+    for (int i = 0; i < L; i++) {                          // p7_codontable_GetCodon: esl_rnd_Roll(r, num_codons[a])
+      const int a = aa[(size_t)i];
+      if (num[a] == 0) return BATH_EINVAL;                 // (eslEINVAL: the table has no codon for a residue the background emits)
+      const int x = (int)(rng.next() * num[a]);
+      const int c = table[a][x];
+      d[3 * i] = (uint8_t)(c >> 4); d[3 * i + 1] = (uint8_t)((c >> 2) & 3); d[3 * i + 2] = (uint8_t)(c & 3);
+    }
+  }
+  *rng_state = rng.x;
+  return BATH_OK;
+}
+
+// Lawless's equation 4.1.6 for the ML lambda of a Gumbel on complete data, and its derivative (esl_gumbel.c: lawless416)
+static void lawless416(const double *x, int n, double lambda, double *ret_f, double *ret_df) {
+  double esum = 0., xesum = 0., xxesum = 0., xsum = 0.;
+  for (int i = 0; i < n; i++) {
+    const double e = std::exp(-1. * lambda * x[i]);
+    xsum += x[i]; xesum += x[i] * e; xxesum += x[i] * x[i] * e; esum += e;
+  }
+  *ret_f = (1. / lambda) - (xsum / n) + (xesum / esum);
+  *ret_df = ((xesum / esum) * (xesum / esum)) - (xxesum / esum) - (1. / (lambda * lambda));
+}
+
+// esl_gumbel_FitComplete: method-of-moments start, Newton-Raphson on lawless416 until |f| < 1e-5 (a bisection if a hundred steps
+// do not get there), mu from Lawless 4.1.5.  One Newton step is taken past the stopping rule: the step that meets it has usually
+// landed at 1e-10 already, and when it has only just met it (|f| ~ 1e-5 leaves lambda 2e-6 off) the extra step does -- the value
+// then is the root to double precision either way, where easel's may be 2e-6 off it (1e-5 in tau, a tenth of its last printed digit).
+extern "C" int bath_gumbel_fit_complete(const double *x, int n, double *ret_mu, double *ret_lambda) {
+  if (!x || n < 2 || !ret_mu || !ret_lambda) return BATH_EINVAL;
+  double sum = 0., sqsum = 0.;
+  for (int i = 0; i < n; i++) { sum += x[i]; sqsum += x[i] * x[i]; }
+  const double variance = (sqsum - sum * sum / (double)n) / ((double)n - 1.);     // esl_stats_DMean
+  if (!(variance > 0.)) return BATH_EINVAL;
+  double lambda = 3.14159265358979323846264338328 / std::sqrt(6. * variance);
+  double fx = 0., dfx = 0.;
+  const double tol = 1e-5;
+  int i;
+  for (i = 0; i < 100; i++) {
+    lawless416(x, n, lambda, &fx, &dfx);
+    const bool met = std::fabs(fx) < tol;
+    if (met && dfx == 0.) break;
+    lambda = lambda - fx / dfx;
+    if (lambda <= 0.) lambda = 0.001;
+    if (met) break;
+  }
+  if (i == 100) {                                          // Newton-Raphson failed: bracket the root, then bisect
+    double left = 0., right = 3.14159265358979323846264338328 / std::sqrt(6. * variance);
+    lawless416(x, n, right, &fx, &dfx);
+    while (fx > 0.) { right *= 2.; if (right > 100.) return BATH_ENORESULT; lawless416(x, n, right, &fx, &dfx); }
+    for (i = 0; i < 100; i++) {
+      const double mid = (left + right) / 2.;
+      lawless416(x, n, mid, &fx, &dfx);
+      if (std::fabs(fx) < tol) { left = right = mid; break; }
+      if (fx > 0.) left = mid; else right = mid;
+    }
+    if (i == 100) return BATH_ENORESULT;
+    lambda = (left + right) / 2.;
+  }
+  double esum = 0.;
+  for (i = 0; i < n; i++) esum += std::exp(-lambda * x[i]);
+  *ret_mu = -std::log(esum / n) / lambda;
+  *ret_lambda = lambda;
+  return BATH_OK;
+}
+
+extern "C" double bath_gumbel_invcdf(double p, double mu, double lambda) { return mu - (std::log(-1. * std::log(p)) / lambda); }
+
+// evalues.c:658, :753
+extern "C" int bath_calib_tau(const double *xv, int n, double lambda_model, double tailp, double *ret_tau) {
+  double gmu = 0., glam = 0.;
+  const int st = bath_gumbel_fit_complete(xv, n, &gmu, &glam);
+  if (st != BATH_OK) return st;
+  *ret_tau = bath_gumbel_invcdf(1.0 - tailp, gmu, glam) + (std::log(tailp) / lambda_model);
+  return BATH_OK;
+}
+
+// p7_bg_SetLength(bg, L) then p7_bg_fs_NullOne (p7_bg.c:189, :377): the null score of L amino acids in any of three frames
+extern "C" float bath_bg_fs_nullone(int L_amino) {
+  const float p1 = (float)L_amino / (float)(L_amino + 1);
+  const float per_frame = (float)((float)L_amino * std::log((double)p1) + std::log(1. - p1));
+  return (float)(per_frame + std::log(3.0));
+}
+
+// p7_Builder_MaxLength (p7_builder.c:678): the length beyond which a sequence emitted by the core model has probability < emit_thresh
+extern "C" int bath_hmm_max_length(const bath_hmm *hmm, double emit_thresh) {
+  if (!hmm || hmm->M < 1) return -1;
+  const int m = hmm->M;
+  if (m == 1) return 1;
+  enum { MM = 0, MI, MD, IM, II, DM, DD };
+  auto t = [&](int k, int s) -> double { return (double)hmm->t[(size_t)k * 7 + s]; };
+  const int length_bound = std::max(m, std::min(20 * m, 100000));
+  std::vector<double> I((size_t)(m + 1) * 2, 0.), Mx((size_t)(m + 1) * 2, 0.), D((size_t)(m + 1) * 2, 0.);
+  auto at = [](std::vector<double> &v, int k, int c) -> double & { return v[(size_t)k * 2 + c]; };
+  at(Mx, 1, 0) = 1.0;
+  at(D, 2, 0) = t(1, MD);
+  for (int k = 3; k <= m; k++) at(D, k, 0) = t(k - 1, DD) * at(D, k - 1, 0);
+  at(I, 1, 1) = t(1, MI) * at(Mx, 1, 0);
+  at(Mx, 2, 1) = t(1, MM) * at(Mx, 1, 0);
+  for (int k = 3; k <= m; k++) {
+    at(Mx, k, 1) = t(k - 1, DM) * at(D, k - 1, 0);
+    at(D, k, 1) = t(k - 1, MD) * at(Mx, k - 1, 1) + t(k - 1, DD) * at(D, k - 1, 1);
+  }
+  double p_sum = at(Mx, m, 0) + at(Mx, m, 1) + at(D, m, 0) + at(D, m, 1);
+  int cp = 0;
+  for (int col = 3; col <= length_bound; col++) {
+    const int pp = 1 - cp;
+    double surv = 0.0;
+    at(Mx, 1, cp) = at(D, 1, cp) = 0;
+    at(I, 1, cp) = t(1, II) * at(I, 1, pp);
+    surv += at(I, 1, cp);
+    for (int k = 2; k <= m; k++) {
+      at(Mx, k, cp) = t(k - 1, MM) * at(Mx, k - 1, pp) + t(k - 1, DM) * at(D, k - 1, pp) + t(k - 1, IM) * at(I, k - 1, pp);
+      at(I, k, cp) = t(k, MI) * at(Mx, k, pp) + t(k, II) * at(I, k, pp);
+      at(D, k, cp) = t(k - 1, MD) * at(Mx, k - 1, cp) + t(k - 1, DD) * at(D, k - 1, cp);
+      surv += at(I, k, cp) + at(Mx, k, cp) * (1 - t(k, MD)) + at(D, k, cp) * (1 - t(k, DD));
+    }
+    surv += at(Mx, m, cp) * t(m, MD) + at(D, m, cp) * t(m, DD) - at(I, m, cp);
+    p_sum += at(Mx, m, cp) + at(D, m, cp);
+    surv /= surv + p_sum;
+    if (surv < emit_thresh) return col;
+    cp = 1 - cp;
+  }
+  return length_bound;
+}
+
+extern "C" int bath_hip_calibrate_fs(bath_hip_ctx *ctx, const bath_hmm *hmm, int ncbi_table, uint32_t *rng_state, int L, int N, double tailp,
+                                     double *tau3, double *tau5, double *xv3, double *xv5) {
+  if (!ctx) return BATH_EINVAL;
+  if (!hmm || !rng_state || !tau3 || !tau5 || L < 2 || N < 2 || !(tailp > 0. && tailp < 1.)) { ctx->set_error("calibrate_fs: needs a model, a generator state, L >= 2, N >= 2 and 0 < tailp < 1"); return BATH_EINVAL; }
+  uint8_t basic[64];
+  if (bath_gencode_basic(ncbi_table, basic) != BATH_OK) { ctx->set_error("calibrate_fs: unknown NCBI translation table " + std::to_string(ncbi_table)); return BATH_EINVAL; }
+  ctx->spans_reset();                                      // bath_hip_kernel_times afterwards: this model's two parser launches
+  const float nullsc = bath_bg_fs_nullone(L);
+  const double lambda = (double)hmm->evparam[5];           // p7_FLAMBDA
+  std::vector<uint8_t> dna((size_t)N * 3 * L);
+  std::vector<int64_t> off((size_t)N + 1);
+  for (int i = 0; i <= N; i++) off[(size_t)i] = (int64_t)i * 3 * L;
+  std::vector<float> sc((size_t)N);
+  std::vector<double> own((size_t)N);
+  uint32_t state = *rng_state;
+  for (int pass = 0; pass < 2; pass++) {                   // bathconvert.c:157-161: the 3-codon fit, then the 5-codon fit, one generator
+    const int cl = pass == 0 ? 3 : 5;
+    bath_fs_profile *gm = nullptr;
+    bath_hip_fsprofile *om = nullptr;
+    bath_hip_seqs *sq = nullptr;
+    int st = bath_fs_profile_config(hmm, basic, cl, L, &gm);
+    if (st == BATH_OK) st = bath_hip_fsprofile_convert(ctx, gm, &om);
+    if (st == BATH_OK && (st = bath_calib_sample(&state, kAminoBg, ncbi_table, L, N, dna.data())) != BATH_OK) ctx->set_error("calibrate_fs: translation table " + std::to_string(ncbi_table) + " has no codon for a background residue");
+    if (st == BATH_OK) st = bath_hip_seqs_create(ctx, dna.data(), off.data(), N, &sq);
+    if (st == BATH_OK) st = pass == 0 ? bath_hip_fs3_forward_parser(ctx, om, sq, BATH_LOGSUM_TABLE_SERIAL, sc.data(), nullptr, nullptr)
+                                      : bath_hip_fs5_forward_parser(ctx, om, sq, L, sc.data());
+    if (sq) bath_hip_seqs_destroy(sq);
+    if (om) bath_hip_fsprofile_destroy(om);
+    if (gm) bath_fs_profile_destroy(gm);
+    if (st != BATH_OK) return st;
+    double *xv = pass == 0 ? (xv3 ? xv3 : own.data()) : (xv5 ? xv5 : own.data());
+    for (int i = 0; i < N; i++) {
+      if (!std::isfinite(sc[(size_t)i])) { ctx->set_error("calibrate_fs: a sampled sequence has no path through the " + std::to_string(cl) + "-codon model (L too short)"); return BATH_ERANGE; }
+      xv[i] = (sc[(size_t)i] - nullsc) / 0.69314718055994529;    // evalues.c:649: float difference, double quotient
+    }
+    if ((st = bath_calib_tau(xv, N, lambda, tailp, pass == 0 ? tau3 : tau5)) != BATH_OK) { ctx->set_error("calibrate_fs: the Gumbel fit did not converge"); return st; }
+  }
+  *rng_state = state;
+  return BATH_OK;
+}

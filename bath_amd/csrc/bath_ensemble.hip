@@ -26,6 +26,7 @@
 #include "bath_launch.hpp"
 #include "bath_fs_ens_walk.hpp"
 #include "bath_std_ens_walk.hpp"
+#include "host_model.hpp"
 
 namespace {
 
@@ -34,17 +35,7 @@ enum { cM = 0, cD = 1, cI = 2 };
 enum { MM = 0, IM, DM, BM, MD, DD, MI, II };
 enum { sS = 0, sN, sB, sM, sD, sI, sE, sJ, sC, sT };
 
-struct FastRng {
-  uint32_t x;
-  explicit FastRng(uint32_t seed) {
-    uint32_t a = seed, b = 87654321u, c = 12345678u;
-    a -= b; a -= c; a ^= (c >> 13);  b -= c; b -= a; b ^= (a << 8);   c -= a; c -= b; c ^= (b >> 13);
-    a -= b; a -= c; a ^= (c >> 12);  b -= c; b -= a; b ^= (a << 16);  c -= a; c -= b; c ^= (b >> 5);
-    a -= b; a -= c; a ^= (c >> 3);   b -= c; b -= a; b ^= (a << 10);  c -= a; c -= b; c ^= (b >> 15);
-    x = c ? c : 42u;
-  }
-  double next() { x = x * 69069u + 1u; return (double)x / 4294967296.0; }
-};
+using bath::FastRng;                                      // host_model.hpp
 
 // pli->r and ddef->do_reseeding (p7_pipeline.c:135-143; p7_domaindef.c:781, :904).  With a seed (--seed, 42 by default) every region's
 // ensemble starts from it.  Seed 0 means "an arbitrary one-time seed, no reseeding": the reference takes the time of day and lets the

@@ -1180,8 +1180,11 @@ __global__ __launch_bounds__(1024) void fs3_bwd_chain_half_kernel(SeqView dna, F
 // 5-codon Forward, full matrix, MULTIHIT (the regions of p7_domaindef.c:396-455), strict.  IVX(i,k) collects the paths leaving
 // row i-1 and B(i-1), so rows cannot be paired: one row per step, W windows per block, the D chain and the E sum of all W rows
 // in one wave.  fwd[(i*(M+1)+k)*8 + {D,I,C0..C5}], xmx[i*5 + {E,N,J,B,C}]; done[job] = 1 (system scope) once the matrix has landed.
+// STORE = false is the score-only parser (p7_fs_Tau_5codons' caller, bath_calibrate.hip): the same recurrence, value for value, with
+// no store of a cell or a special-state row -- fwd, xmx, their offsets and done are not read.  What the recurrence reaches back to
+// (M and I of rows i-1..i-3, D of row i-1, IVX of rows i-1..i-4, N/J/C of rows i-1..i-3) is in registers, the row in flight in LDS.
 // ---------------------------------------------------------------------------------------------------------------------------
-template <int C, int THREADS>
+template <int C, int THREADS, bool STORE = true>
 __global__ __launch_bounds__(THREADS) void fs5_fwd_chain_kernel(SeqView dna, FsDev p, const float *__restrict__ loop_tab, const float *__restrict__ move_tab,
                                                              float tEL, float tEM, int c5_compat, float *__restrict__ sc, float *__restrict__ fwd, const int64_t *__restrict__ fwd_off,
                                                              float *__restrict__ xmx, const int64_t *__restrict__ xmx_off, int cfg_len, FsJobs jobs, int *__restrict__ done,
@@ -1211,14 +1214,14 @@ __global__ __launch_bounds__(THREADS) void fs5_fwd_chain_kernel(SeqView dna, FsD
     const int L = job >= 0 ? dna.len[job] : 0;
     const bool live = job >= 0 && L >= 5;
     const uint8_t *d = job >= 0 ? dna.data + dna.off[job] : dna.data;
-    float *fo = job >= 0 ? fwd + fwd_off[job] : fwd;
-    float *xo = job >= 0 ? xmx + xmx_off[job] : xmx;
+    float *fo = (STORE && job >= 0) ? fwd + fwd_off[job] : fwd;
+    float *xo = (STORE && job >= 0) ? xmx + xmx_off[job] : xmx;
     const int Lc = cfg_len >= 0 ? cfg_len : L / 3;
     const float tNL = loop_tab[Lc], tNM = move_tab[Lc], tJL = tNL, tJM = tNM, tCL = tNL, tCM = tNM;
     float Mr0[C], Mr1[C], Mr2[C], Ir0[C], Ir1[C], Ir2[C], Dr1[C], iv0[C], iv1[C], iv2[C], iv3[C];   // M, I of rows i-1..i-3; D of row i-1; IVX(i-1..i-4)
 #pragma unroll
     for (int c = 0; c < C; c++) Mr0[c] = Mr1[c] = Mr2[c] = Ir0[c] = Ir1[c] = Ir2[c] = Dr1[c] = iv0[c] = iv1[c] = iv2[c] = iv3[c] = -INFINITY;
-    if (live) {
+    if (STORE && live) {
       for (int k = lane; k <= M; k += 64)
 #pragma unroll
         for (int q = 0; q < 8; q++) fo[(size_t)k * 8 + q] = -INFINITY;
@@ -1249,8 +1252,8 @@ __global__ __launch_bounds__(THREADS) void fs5_fwd_chain_kernel(SeqView dna, FsD
       const bool act = live && i <= L;
       const float mIn = wave_shr1(Mr0[C - 1], -INFINITY), iIn = wave_shr1(Ir0[C - 1], -INFINITY), dIn = wave_shr1(Dr1[C - 1], -INFINITY);
       float Mc[C], Ic[C], ivc[C];
-      float *row = fo + (size_t)(act ? i : 0) * (M + 1) * 8;
-      if (act && lane == 0) {
+      float *row = STORE ? fo + (size_t)(act ? i : 0) * (M + 1) * 8 : nullptr;
+      if (STORE && act && lane == 0) {
 #pragma unroll
         for (int q = 0; q < 8; q++) row[q] = -INFINITY;
       }
@@ -1287,7 +1290,7 @@ __global__ __launch_bounds__(THREADS) void fs5_fwd_chain_kernel(SeqView dna, FsD
         }
       };
       if (i >= 5) cells(std::false_type{}); else cells(std::true_type{});
-      if (act) {
+      if (STORE && act) {
 #pragma unroll
         for (int c = 0; c < C; c++) {
           const int node = lane * C + c + 1;
@@ -1319,7 +1322,7 @@ __global__ __launch_bounds__(THREADS) void fs5_fwd_chain_kernel(SeqView dna, FsD
         const int node = lane * C + c + 1, ne = imin(node, M);
         const float dv = s_stage[((size_t)wv * 2) * stride + ne];
         Dc[c] = (node <= M) ? dv : -INFINITY;
-        if (act && node <= M) row[(size_t)node * 8] = Dc[c];
+        if (STORE && act && node <= M) row[(size_t)node * 8] = Dc[c];
       }
       const float xE = s_e[wv];
       float nN, nJ, nC, nB;
@@ -1329,7 +1332,7 @@ __global__ __launch_bounds__(THREADS) void fs5_fwd_chain_kernel(SeqView dna, FsD
         nB = LS(nN + tNM, nJ + tJM);
       }
       if (act) {
-        if (lane == 0) { xo[i * 5 + 0] = xE; xo[i * 5 + 1] = nN; xo[i * 5 + 2] = nJ; xo[i * 5 + 3] = nB; xo[i * 5 + 4] = nC; }
+        if (STORE && lane == 0) { xo[i * 5 + 0] = xE; xo[i * 5 + 1] = nN; xo[i * 5 + 2] = nJ; xo[i * 5 + 3] = nB; xo[i * 5 + 4] = nC; }
         xN2 = xN1; xN1 = xN0; xN0 = nN; xJ2 = xJ1; xJ1 = xJ0; xJ0 = nJ; xC2 = xC1; xC1 = xC0; xC0 = nC;
         xBprev = nB;
 #pragma unroll
@@ -1341,13 +1344,13 @@ __global__ __launch_bounds__(THREADS) void fs5_fwd_chain_kernel(SeqView dna, FsD
         }
         if (i == L) {                                             // this window is complete: score, then the flag the host waits for
           if (lane == 0) sc[job] = LS(xC0, LS(xC1 + tCL, xC2 + tCL)) + tCM;
-          if (done) { __threadfence_system(); if (lane == 0) __hip_atomic_store(done + job, 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM); }
+          if (STORE && done) { __threadfence_system(); if (lane == 0) __hip_atomic_store(done + job, 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM); }
         }
       }
     }
     if (job >= 0 && !live) {
       if (lane == 0) sc[job] = -INFINITY;
-      if (done) { __threadfence_system(); if (lane == 0) __hip_atomic_store(done + job, 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM); }
+      if (STORE && done) { __threadfence_system(); if (lane == 0) __hip_atomic_store(done + job, 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM); }
     }
     __syncthreads();
   }
@@ -1564,6 +1567,25 @@ int launch_fs5_fwd_chain(bath_hip_ctx *ctx, hipStream_t stream, const bath_hip_f
       hipLaunchKernelGGL((fs5_fwd_chain_kernel<CC, chain_threads(CC)>), dim3(grid), dim3(64 * std::max(W, kChainAwakeWaves)), shmem, stream, dna->view(), dev, om->d_loop[0], om->d_move[0], tEL, tEM, c5_compat, d_sc, d_fwd, d_foff,
                          d_xmx, d_xoff, cfg_len, jobs, d_done, W);
     }
+  })
+  BATH_HIP_TRY(ctx, hipGetLastError());
+  return BATH_OK;
+}
+
+// The score-only instantiation of fs5_fwd_chain_kernel (p7_Forward_Frameshift's score in the multihit configuration of <cfg_len> amino
+// acids; strict log-sums), one to four windows per block of 256 threads: calibration's 200 windows are a block each on as many CUs.
+int launch_fs5_fwd_parser(bath_hip_ctx *ctx, hipStream_t stream, const bath_hip_fsprofile *om, const bath_hip_seqs *dna, int Cv, float tEL, float tEM,
+                          float *d_sc, int cfg_len, FsJobs jobs) {
+  const int M = om->M;
+  size_t shmem = 0;
+  const int W = chain_waves(ctx, dna->n, M, Cv, &shmem, 1, 256);
+  const int64_t n = dna->n;
+  const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((n + W - 1) / W, (int64_t)ctx->prop.multiProcessorCount));
+  FsDev dev{om->M, om->pitch, om->maxcodons, om->d_rsc, om->d_tf, om->d_tb, om->d_logsum};
+  BATH_FS_SWITCH(Cv, {
+    BATH_HIP_TRY(ctx, bath::allow_max_lds((const void *)fs5_fwd_chain_kernel<CC, 256, false>));
+    hipLaunchKernelGGL((fs5_fwd_chain_kernel<CC, 256, false>), dim3(grid), dim3(64 * std::max(W, kChainAwakeWaves)), shmem, stream, dna->view(), dev, om->d_loop[0], om->d_move[0], tEL, tEM, 0, d_sc,
+                       (float *)nullptr, (const int64_t *)nullptr, (float *)nullptr, (const int64_t *)nullptr, cfg_len, jobs, (int *)nullptr, W);
   })
   BATH_HIP_TRY(ctx, hipGetLastError());
   return BATH_OK;

@@ -15,7 +15,8 @@
 
 // The other families are templates on one number, listed in ascending order: LIST(X, ...) applies X(N, ...) to every entry, handing
 // on what follows X (a switch's body).
-// C model nodes per lane of the frameshift kernels (bath_frameshift.hip, bath_fs_chain.hip, bath_fs_odds.hip, bath_fs5_odds.hip)
+// C model nodes per lane of the frameshift kernels (bath_frameshift.hip, bath_fs_chain.hip, bath_fs_odds.hip, bath_fs5_odds.hip);
+// the score-only 5-codon Forward parser of calibration (fs5_fwd_chain_kernel<C, 256, false>, launch_fs5_fwd_parser) goes over the same list
 #define BATH_FS_COLUMNS(X, ...)                                                                                                          \
   X(1, __VA_ARGS__) X(2, __VA_ARGS__) X(3, __VA_ARGS__) X(4, __VA_ARGS__) X(6, __VA_ARGS__) X(8, __VA_ARGS__) X(12, __VA_ARGS__)         \
   X(16, __VA_ARGS__) X(20, __VA_ARGS__)

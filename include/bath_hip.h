@@ -715,6 +715,37 @@ int bath_hip_fs5_envelopes_x(bath_hip_ctx *ctx, const bath_hip_fsprofile *om5, c
 int bath_hip_fs5_forward_full(bath_hip_ctx *ctx, const bath_hip_fsprofile *om5, const bath_hip_seqs *dna, int cfg_len_amino,
                               float *sc, float *fwd, float *xmx);
 
+/* The score of bath_hip_fs5_forward_full and nothing else (p7_Forward_Frameshift in the multihit local configuration of
+ * <cfg_len_amino>; what p7_fs_Tau_5codons needs of p7_ForwardParser_Frameshift_5Codons): no DP matrix and no special-state row goes
+ * to global memory.  sc[n]; a window shorter than 5 nt scores -inf.  Always the strict arithmetic (serial table log-sums, bit-identical
+ * to the generic reference): bath_hip_set_fs_strict and bath_hip_set_fs5_odds do not reach this entry point. */
+int bath_hip_fs5_forward_parser(bath_hip_ctx *ctx, const bath_hip_fsprofile *om5, const bath_hip_seqs *dna, int cfg_len_amino, float *sc);
+
+/* ------------------------------------------------------------------------------------------
+ * Frameshift calibration (bathconvert.c:128-169): the FS3 / FS5 Forward taus by simulation, and MAXL.
+ * ------------------------------------------------------------------------------------------ */
+/* The sample stream of p7_fs_Tau_3codons / _5codons (evalues.c:633-643): N sequences; for each, L draws of esl_rnd_FChoose over the
+ * 20 frequencies <f> (NULL: the Swiss-Prot background; used as they stand, a roll beyond their sum is drawn again), then L draws of
+ * esl_rnd_Roll over the codons of each residue in p7_codontable_Create's order.  dna: N x 3L codes 0..3.  *rng_state: the "fast"
+ * generator's state (bath_selftest_rng_jump(seed, 0, &state) right after seeding), in and out: the reference carries one generator,
+ * seeded with 42, through all the models of a file.  BATH_EINVAL: unknown table, or a drawn residue without a codon in it.  Host only. */
+int bath_calib_sample(uint32_t *rng_state, const float *f, int ncbi_table, int L, int N, uint8_t *dna);
+/* esl_gumbel_FitComplete: maximum-likelihood Gumbel on complete data (Newton-Raphson on Lawless 4.1.6 from a method-of-moments start,
+ * one step past easel's |f| < 1e-5; mu from 4.1.5).  BATH_ENORESULT: no convergence.  Host only, double. */
+int    bath_gumbel_fit_complete(const double *x, int n, double *mu, double *lambda);
+double bath_gumbel_invcdf(double p, double mu, double lambda);
+/* tau = invcdf(1 - tailp; fit of xv) + log(tailp) / lambda_model (evalues.c:658) */
+int    bath_calib_tau(const double *xv, int n, double lambda_model, double tailp, double *tau);
+float  bath_bg_fs_nullone(int L_amino);                    /* p7_bg_SetLength(bg, L) + p7_bg_fs_NullOne (p7_bg.c:189, :377) */
+int    bath_hmm_max_length(const bath_hmm *hmm, double emit_thresh);   /* p7_Builder_MaxLength (p7_builder.c:678); -1 without a model */
+/* p7_fs_Tau_3codons then p7_fs_Tau_5codons of one model (bathconvert.c:147-161): the two frameshift profiles at length L, N sampled
+ * sequences each (the 3-codon fit's first, from the same generator), bath_hip_fs3_forward_parser (strict) and
+ * bath_hip_fs5_forward_parser, xv[i] = (sc - nullsc) / ln 2, the fits.  xv3 / xv5 (NULL or [N]): the bit scores.  Nothing is redrawn:
+ * the reference's redraw is for its odds-ratio parser's overflow, which log space does not have.  BATH_ERANGE: a sequence without
+ * a path (L below two codons). */
+int bath_hip_calibrate_fs(bath_hip_ctx *ctx, const bath_hmm *hmm, int ncbi_table, uint32_t *rng_state, int L, int N, double tailp,
+                          double *tau3, double *tau5, double *xv3, double *xv5);
+
 /* The multi-domain region stage on its own: the multihit Forward of every sequence of <regions> (each one region, configuration
  * length 100 as the pipeline's) and its trace ensemble in the context's bath_hip_set_fs_ensemble mode.  Per region r:
  *   region_status[r]  0 = ok, 1 = no valid traces (Forward underflow, an impossible state, the step cap): no envelopes;
