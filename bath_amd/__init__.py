@@ -24,7 +24,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 _ROOT = os.path.dirname(_HERE)
 LIB_PATH = os.environ.get("BATH_HIP_LIBRARY") or os.path.join(_HERE, "libbathhip.so")   # the override is for A/B timing of two builds
 
-OK, ERANGE, ENORESULT = 0, 16, 19
+OK, EINVAL, ERANGE, ENORESULT = 0, 11, 16, 19
 KP, K, NEVPARAM = 29, 20, 8
 LOGSUM_TABLE, LOGSUM_EXACT, LOGSUM_TABLE_SERIAL, LOGSUM_CONTEXT = 0, 1, 2, 3
 LOGSUM_ODDS = 4                                     # 3-codon parsers in odds-ratio space (what the reference's --fs runs)
@@ -32,6 +32,8 @@ LOGSUM_ODDS = 4                                     # 3-codon parsers in odds-ra
 ENSEMBLE_SERIAL, ENSEMBLE_STREAMS_HOST, ENSEMBLE_STREAMS_DEVICE = 0, 1, 2
 ENSEMBLE_MODES = {"serial": ENSEMBLE_SERIAL, "streams": ENSEMBLE_STREAMS_HOST, "device": ENSEMBLE_STREAMS_DEVICE}
 ENS_SAMPLES = 200
+ARITH_STRICT, ARITH_ODDS3, ARITH_ODDS = 0, 1, 2     # bath_hip_calibrate_fs_arith; bathsearch / bathconvert --arith
+ARITH_MODES = {"strict": ARITH_STRICT, "odds3": ARITH_ODDS3, "odds": ARITH_ODDS}
 ENS_OK, ENS_IMPOSSIBLE, ENS_STEP_CAP, ENS_SEG_OVERFLOW = 0, 1, 2, 3      # per-trace status of the stream modes
 ENS_REGION_OK, ENS_REGION_NO_TRACES = 0, 1
 
@@ -188,6 +190,8 @@ class Fs5Result(C.Structure):
     _fields_ = [("fwdsc", C.c_float), ("bcksc", C.c_float), ("oasc", C.c_float), ("null2", C.c_float * KP)]
 
 
+_CALIB_SCORE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_uint8), C.c_int, C.c_int, C.POINTER(C.c_float))   # bath_calib_score_fn
+
 # name -> (restype, argtypes); every symbol include/bath_hip.h declares
 _vp, _u8p, _f32p, _i32p, _i64p = C.c_void_p, C.POINTER(C.c_uint8), C.POINTER(C.c_float), C.POINTER(C.c_int32), C.POINTER(C.c_int64)
 ABI = {
@@ -327,6 +331,12 @@ ABI = {
     "bath_hip_fs5_forward_full": (C.c_int, [_vp, _vp, _vp, C.c_int, _f32p, _f32p, _f32p]),
     "bath_hip_fs5_envelopes": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, C.POINTER(Fs5Result), _f32p, _i64p, _f32p, _i64p]),
     "bath_hip_fs5_forward_parser": (C.c_int, [_vp, _vp, _vp, C.c_int, _f32p]),
+    "bath_hip_fs5_forward_parser_odds": (C.c_int, [_vp, _vp, _vp, C.c_int, _f32p]),
+    "bath_calib_fit_scores": (C.c_int, [C.POINTER(C.c_uint32), _f32p, C.c_int, C.c_int, C.c_int, _CALIB_SCORE_FN, C.c_void_p, C.c_float,
+                                        C.POINTER(C.c_double), C.POINTER(C.c_int)]),
+    "bath_hip_calibrate_fs_arith": (C.c_int, [_vp, C.POINTER(_Hmm), C.c_int, C.POINTER(C.c_uint32), C.c_int, C.c_int, C.c_double,
+                                              C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                              C.c_int, C.POINTER(C.c_int)]),
     "bath_calib_sample": (C.c_int, [C.POINTER(C.c_uint32), _f32p, C.c_int, C.c_int, C.c_int, _u8p]),
     "bath_gumbel_fit_complete": (C.c_int, [C.POINTER(C.c_double), C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "bath_gumbel_invcdf": (C.c_double, [C.c_double, C.c_double, C.c_double]),
@@ -1526,6 +1536,15 @@ def FS5ForwardParser(ctx, om5, dna, cfg_len_amino=100):
     return sc
 
 
+def FS5ForwardParserOdds(ctx, om5, dna, cfg_len_amino=100):
+    """FS5ForwardParser in the reference's arithmetic: the multihit score of the 5-codon odds-ratio Forward (FS5ForwardFull under
+    set_fs5_odds, bit for bit) and nothing else.  -inf for a window shorter than 5 nt and for an overflow.  Always odds ratios,
+    whatever the context's switches say; a 3-codon profile is refused."""
+    sc = np.zeros(dna.n, dtype=np.float32)
+    ctx._check(lib().bath_hip_fs5_forward_parser_odds(ctx._h, om5._h, dna._h, cfg_len_amino, _f32(sc)), "fs5_forward_parser_odds")
+    return sc
+
+
 CALIB_SEED, CALIB_L, CALIB_N, CALIB_TAILP = 42, 100, 200, 0.04       # bathconvert.c:128, :157-160
 FS_UNSET = -99999.0                                                   # p7_EVPARAM_UNSET: a tau the model file does not carry
 
@@ -1592,13 +1611,54 @@ def kernel_times(ctx):
     return {arr[i].name.decode(): (float(arr[i].ms), int(arr[i].launches), float(arr[i].cells), float(arr[i].bytes)) for i in range(n)}
 
 
-def calibrate_fs(ctx, hmm, ncbi_table, state, L=CALIB_L, N=CALIB_N, tailp=CALIB_TAILP, want_xv=False):
+def calib_fit_scores(state, score, nullsc, L=CALIB_L, N=CALIB_N, ncbi_table=1, f=None):
+    """The reference's redraw loop (evalues.c:633-649) over a Python scorer: score(dna [n, 3L] uint8) -> n float scores, one call per
+    batch of sequences still missing; a sequence whose score is not finite is discarded and the next one is drawn from where the
+    generator stands after it.  Returns (xv [N] bit scores, the generator's state afterwards, sequences redrawn); BathError
+    (.status = ERANGE) when more than N were discarded."""
+    def cb(_user, dna, n, L3, sc):
+        try:
+            got = np.asarray(score(np.ctypeslib.as_array(dna, shape=(n, L3))), dtype=np.float32)
+            assert got.shape == (n,)
+            np.ctypeslib.as_array(sc, shape=(n,))[:] = got
+            return OK
+        except Exception as e:                             # (an exception must not cross the C frames)
+            err.append(e)
+            return EINVAL
+    err = []
+    st = C.c_uint32(state)
+    xv = np.zeros(N, np.float64)
+    nre = C.c_int(0)
+    fa = None if f is None else np.ascontiguousarray(f, dtype=np.float32)
+    assert fa is None or fa.shape == (20,)
+    rc = lib().bath_calib_fit_scores(C.byref(st), _f32(fa), ncbi_table, L, N, _CALIB_SCORE_FN(cb), None, nullsc, _f64p(xv), C.byref(nre))
+    if err:
+        raise err[0]
+    if rc != OK:
+        e = BathError("calib_fit_scores failed (%d)%s" % (rc, ": more than N sequences had no finite score" if rc == ERANGE else ""))
+        e.status, e.redrawn = rc, nre.value
+        raise e
+    return xv, st.value, nre.value
+
+
+def calibrate_fs(ctx, hmm, ncbi_table, state, L=CALIB_L, N=CALIB_N, tailp=CALIB_TAILP, want_xv=False, arith="strict"):
     """p7_fs_Tau_3codons then p7_fs_Tau_5codons of one model on the GPU: (tau3, tau5, the generator's state afterwards), with
-    want_xv also the two arrays of N bit scores the taus were fitted to."""
+    want_xv also the two arrays of N bit scores the taus were fitted to and, in the odds modes, [sequences redrawn in the 3-codon
+    fit, in the 5-codon fit] (strict has no redraw and keeps its five values).  arith (ARITH_MODES): "strict", the log-space parsers (nothing is ever redrawn); "odds3", the 3-codon parser in fp32 odds
+    ratios; "odds", both parsers -- the reference's arithmetic, with its redraw of a sequence whose parser overflows."""
+    if arith not in ARITH_MODES:
+        raise ValueError("arith: expected one of %s" % ", ".join(ARITH_MODES))
     st = C.c_uint32(state)
     t3, t5 = C.c_double(0), C.c_double(0)
     x3 = np.zeros(N, np.float64) if want_xv else None
     x5 = np.zeros(N, np.float64) if want_xv else None
-    ctx._check(lib().bath_hip_calibrate_fs(ctx._h, hmm._p, ncbi_table, C.byref(st), L, N, tailp, C.byref(t3), C.byref(t5),
-                                           None if x3 is None else _f64p(x3), None if x5 is None else _f64p(x5)), "calibrate_fs")
+    px3, px5 = None if x3 is None else _f64p(x3), None if x5 is None else _f64p(x5)
+    re2 = (C.c_int * 2)(0, 0)
+    if arith == "strict":
+        ctx._check(lib().bath_hip_calibrate_fs(ctx._h, hmm._p, ncbi_table, C.byref(st), L, N, tailp, C.byref(t3), C.byref(t5), px3, px5), "calibrate_fs")
+    else:
+        ctx._check(lib().bath_hip_calibrate_fs_arith(ctx._h, hmm._p, ncbi_table, C.byref(st), L, N, tailp, C.byref(t3), C.byref(t5), px3, px5,
+                                                     ARITH_MODES[arith], re2), "calibrate_fs")
+    if want_xv and arith != "strict":
+        return t3.value, t5.value, st.value, x3, x5, [re2[0], re2[1]]
     return (t3.value, t5.value, st.value, x3, x5) if want_xv else (t3.value, t5.value, st.value)

@@ -1,6 +1,6 @@
 """bathconvert: HMMER3 or BATH model files to the BATH format bathsearch takes, the frameshift taus fitted on the GPU.
 
-    python -m bath_amd.bathconvert [--ct N] <hmmfile_out> <hmmfile_in>
+    python -m bath_amd.bathconvert [--ct N] [--arith strict|odds3|odds] <hmmfile_out> <hmmfile_in>
 
 What bathconvert.c does: per model of a HMMER3/f or BATH3/f file, the codon table is --ct if given, else the file's, else 1; the
 FS3 and FS5 Forward taus are fitted by simulation (bath_amd.calibrate_fs: p7_fs_Tau_3codons then p7_fs_Tau_5codons, one generator
@@ -9,6 +9,10 @@ MAXL is computed (p7_Builder_MaxLength) only when the file has none; FRAMESHIFT 
 the header line, MAXL, the STATS lines and the four frameshift lines rewritten (rewrite_model), every other byte kept: the model's
 parameters never pass through a number.  Anything else -- older format letters, binary files, a non-amino alphabet, an output path
 that is the input -- is refused by name, status 1.  One context on one device, created only if a model needs a fit.
+
+--arith (an extension) chooses the arithmetic of the two Forward parsers a fit runs (bath_amd.ARITH_MODES): strict, the default,
+today's output byte for byte; odds3, the 3-codon parser in fp32 odds ratios; odds, both parsers, which is what the reference's own
+bathconvert runs (with its redraw of a sequence whose parser overflows).  A file whose taus are kept is not touched by it.
 """
 import os
 import re
@@ -38,20 +42,31 @@ class UsageError(Exception):
 
 def parse_args(argv):
     """(--ct or None, hmmfile_out, hmmfile_in); raises UsageError naming what is wrong."""
-    ct, pos, i = None, [], 0
+    return parse_options(argv)[:3]
+
+
+def parse_options(argv):
+    """(--ct or None, hmmfile_out, hmmfile_in, {"arith": "strict" | "odds3" | "odds"}): what run() reads."""
+    ct, pos, i, opts = None, [], 0, {"arith": "strict"}
     while i < len(argv):
         a = argv[i]
         if a.startswith("-") and len(a) > 1:
             name, val = (a.split("=", 1) + [None])[:2] if a.startswith("--") and "=" in a else (a, None)
             if name == "-h":
                 raise UsageError("option -h is not supported by this bathconvert: %s" % USAGE)
-            if name != "--ct":
+            if name not in ("--ct", "--arith"):
                 raise UsageError("unknown option %s" % name)
             if val is None:
                 i += 1
                 if i >= len(argv):
-                    raise UsageError("option --ct needs an argument")
+                    raise UsageError("option %s needs an argument" % name)
                 val = argv[i]
+            if name == "--arith":
+                if val not in ba.ARITH_MODES:
+                    raise UsageError("option --arith: %r is not one of %s" % (val, ", ".join(ba.ARITH_MODES)))
+                opts["arith"] = val
+                i += 1
+                continue
             try:
                 ct = int(val)
             except ValueError:
@@ -63,7 +78,7 @@ def parse_args(argv):
         i += 1
     if len(pos) != 2:
         raise UsageError("Incorrect number of command line arguments: %s" % USAGE)
-    return ct, pos[0], pos[1]
+    return ct, pos[0], pos[1], opts
 
 
 def split_models(text):
@@ -217,7 +232,7 @@ def run(argv, stdout=None, device=0):
     stdout = stdout or sys.stdout
     t0, c0 = time.time(), os.times()
     try:
-        ct_opt, path_out, path_in = parse_args(argv)
+        ct_opt, path_out, path_in, opts = parse_options(argv)
         if not os.path.isfile(path_in):
             raise UsageError("File existence/permissions problem in trying to open HMM file %s." % path_in)
         if os.path.exists(path_out) and os.path.samefile(path_out, path_in):
@@ -250,7 +265,7 @@ def run(argv, stdout=None, device=0):
             if p["fit"]:
                 if ctx is None:
                     ctx = ba.Context(device)
-                tau3, tau5, state = ba.calibrate_fs(ctx, hmm, p["ct"], state)
+                tau3, tau5, state = ba.calibrate_fs(ctx, hmm, p["ct"], state, arith=opts["arith"])
             maxl = ba.hmm_max_length(hmm, W_BETA) if p["need_maxl"] else None
             out.append(rewrite_model(model, p["ct"], tau3, tau5, maxl))
             stdout.write(result_line(i + 1, p, mean_match_relative_entropy(hmm)))

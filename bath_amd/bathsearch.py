@@ -1,6 +1,6 @@
 """bathsearch on one GPU or several: search the profile HMMs of a model file against the DNA targets of a FASTA file.
 
-    python -m bath_amd.bathsearch [--gpus N] [--workers N] [options] <hmmfile> <seqfile>
+    python -m bath_amd.bathsearch [--gpus N] [--workers N] [--arith strict|odds3|odds] [options] <hmmfile> <seqfile>
 
 The FASTA file's bytes go to the device as they are (bath_amd.FastaTargets: records, digitising and the windows of
 esl_sqio_ReadWindow are found there); per query the windows run through the pipeline in blocks of at most <block_nt>
@@ -23,6 +23,12 @@ is finished and rendered by the worker that searched its last piece, and an orde
 every earlier query's text is written, so the output is the N = 1 output byte for byte but for the timing lines.  At most 2N
 queries' hits are alive at once, and the models and plans of at most two batches of 2N (feed_batches).  A failure at query k writes the queries before k, nothing from k on, one message, status 1.
 With --gpus G every rank runs its items on N contexts of its device; BATH_HIP_HOST_THREADS is then the CPU share / (G x N).
+
+--arith strict|odds3|odds (default strict; an extension like --ensemble: no header line; needs --fs) chooses the arithmetic of the
+frameshift Forward / Backward recursions: strict, the log-space kernels bit-identical to the generic reference; odds3, the 3-codon
+parsers in fp32 odds ratios (Context.set_fs_odds); odds, the 5-codon Forward / Backward of envelopes and regions too
+(Context.set_fs5_odds) -- what the reference binary's --fs runs.  new_context applies it, so every context of --workers and every
+rank of --gpus runs the same arithmetic.  Search a file converted with the same bathconvert --arith.
 """
 import codecs
 import os
@@ -50,6 +56,7 @@ OPTIONS = {"-o": str, "--tblout": str, "--fs": "flag", "--cigar": "flag", "--fra
            "--F1": float, "--F2": float, "--F3": float, "--F4": float, "--max": "flag", "--nobias": "flag", "--nonull2": "flag", "--fsonly": "flag",
            "--block_length": int, "--gpus": int,
            "--workers": int,       # an extension (no header line): queries searched side by side on N contexts of one GPU
+           "--arith": str,         # an extension (no header line): the arithmetic of the --fs Forward / Backward recursions (ba.ARITH_MODES)
            "--ensemble": str,      # an extension, not a reference option (no header line): how --fs samples a multi-domain region's traces
            "--ensemble-std": str}  # ... and how the standard branch does (a search without --fs; the --fs windows that take that branch)
 MAX_GPUS = 16
@@ -61,7 +68,7 @@ REFUSED = ["-h", "--splice", "--exontblout", "--fstblout", "--hmmout", "--acc", 
            "--nodeinfo"]
 EXCLUSIVE = [("-m", "-M"), ("--textw", "--notextw"), ("-E", "-T"), ("--max", "--F1"), ("--max", "--F2"), ("--max", "--F3"), ("--max", "--F4"),
              ("--max", "--nobias")]
-REQUIRES = {"--frameline": "--fs", "--cigar": "--tblout", "--F4": "--fs"}
+REQUIRES = {"--frameline": "--fs", "--cigar": "--tblout", "--F4": "--fs", "--arith": "--fs"}
 
 
 # bathsearch.c:748-750 (the reference's spelling): a model without the frameshift taus, such as a plain HMMER3 file's
@@ -117,6 +124,8 @@ def parse_args(argv):
     for o in ("--ensemble", "--ensemble-std"):
         if o in opts and opts[o] not in ba.ENSEMBLE_MODES:
             raise UsageError("option %s: expected serial, streams or device" % o)
+    if "--arith" in opts and opts["--arith"] not in ba.ARITH_MODES:
+        raise UsageError("option --arith: expected %s" % ", ".join(ba.ARITH_MODES))
     if opts.get("--textw", 150) < 120:
         raise UsageError("option --textw: n >= 120")
     if opts.get("--block_length", 50000) < 50000:
@@ -892,7 +901,10 @@ class WorkerPool:
 
 def new_context(device, opts):
     ctx = ba.Context(device)
-    ctx.set_fs_strict(True)
+    ctx.set_fs_strict(True)                              # in every --arith mode: the stages the odds switches do not cover
+    arith = ba.ARITH_MODES[opts.get("--arith", "strict")]
+    ctx.set_fs_odds(arith >= ba.ARITH_ODDS3)
+    ctx.set_fs5_odds(arith >= ba.ARITH_ODDS)
     ctx.set_fs_ensemble(opts.get("--ensemble", "serial"))
     ctx.set_std_ensemble(opts.get("--ensemble-std", "serial"))
     return ctx

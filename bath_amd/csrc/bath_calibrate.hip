@@ -13,7 +13,9 @@
 // easel is not part of the reference tree, so esl_rsq_xfIID, esl_rnd_FChoose, esl_rnd_Roll, esl_stats_DMean, esl_gumbel_FitComplete
 // and esl_gumbel_invcdf are restated from their published behaviour, as bath_ensemble.hip restates the generator.  The reference
 // redraws a sequence whose odds-ratio parser overflows (eslERANGE, evalues.c:645, :740); the strict log-space kernels cannot
-// overflow, so nothing is redrawn.
+// overflow, so bath_hip_calibrate_fs redraws nothing.  bath_hip_calibrate_fs_arith runs the parsers in the reference's odds-ratio
+// arithmetic (bath_hip_fs3_forward_parser in BATH_LOGSUM_ODDS, bath_hip_fs5_forward_parser_odds) and there the redraw applies:
+// bath_calib_fit_scores is that loop, host code around a batch scoring callback.
 #include <cmath>
 #include <cstdint>
 #include <cstring>
@@ -63,6 +65,37 @@ extern "C" int bath_calib_sample(uint32_t *rng_state, const float *f, int ncbi_t
     }
   }
   *rng_state = rng.x;
+  return BATH_OK;
+}
+
+// evalues.c:633-649 (and :728-744): for (i = 0; i < N; i++) { sample; score; if (eslERANGE) { i--; continue; } xv[i] = ... }.  The
+// sequence after a discarded one is drawn from where the generator stands after the discarded one, so the sequences the serial
+// loop sees are ONE stream of draws, whatever their scores: the batch form draws what is still missing from that stream, scores
+// it in one call, keeps the finite scores in order and counts the others; the next batch continues the stream.  It ends when N
+// are kept, which is where the serial loop's generator ends (the last sequence drawn is a kept one in both).
+extern "C" int bath_calib_fit_scores(uint32_t *rng_state, const float *f, int ncbi_table, int L, int N, bath_calib_score_fn score, void *user,
+                                     float nullsc, double *xv, int *n_redrawn) {
+  if (!rng_state || !score || !xv || L < 1 || N < 1) return BATH_EINVAL;
+  std::vector<uint8_t> dna((size_t)N * 3 * L);
+  std::vector<float> sc((size_t)N);
+  uint32_t state = *rng_state;
+  int kept = 0, redrawn = 0;
+  if (n_redrawn) *n_redrawn = 0;
+  while (kept < N) {
+    const int need = N - kept;
+    int st = bath_calib_sample(&state, f, ncbi_table, L, need, dna.data());
+    if (st != BATH_OK) return st;
+    if ((st = score(user, dna.data(), need, 3 * L, sc.data())) != BATH_OK) return st;
+    for (int j = 0; j < need; j++) {
+      if (!std::isfinite(sc[(size_t)j])) {
+        if (n_redrawn) *n_redrawn = redrawn + 1;
+        if (++redrawn > N) return BATH_ERANGE;             // (the reference would loop on)
+        continue;
+      }
+      xv[kept++] = (sc[(size_t)j] - nullsc) / 0.69314718055994529;           // evalues.c:649: float difference, double quotient
+    }
+  }
+  *rng_state = state;
   return BATH_OK;
 }
 
@@ -179,8 +212,78 @@ extern "C" int bath_hmm_max_length(const bath_hmm *hmm, double emit_thresh) {
   return length_bound;
 }
 
+namespace {
+// what bath_calib_fit_scores calls back: one batch of sampled sequences through one parser of the odds-ratio calibration
+struct CalibScore {
+  bath_hip_ctx *ctx;
+  const bath_hip_fsprofile *om;
+  int cfg_len, kind;                                        // kind 0: fs3 odds, 1: fs5 strict, 2: fs5 odds
+  std::vector<int64_t> off;
+  bool failed;                                              // the parser refused (its message stands)
+};
+int calib_score(void *user, const uint8_t *dna, int n, int L3, float *sc) {
+  CalibScore *c = static_cast<CalibScore *>(user);
+  c->off.resize((size_t)n + 1);
+  for (int i = 0; i <= n; i++) c->off[(size_t)i] = (int64_t)i * L3;
+  bath_hip_seqs *sq = nullptr;
+  int st = bath_hip_seqs_create(c->ctx, dna, c->off.data(), n, &sq);
+  if (st == BATH_OK) st = c->kind == 0 ? bath_hip_fs3_forward_parser(c->ctx, c->om, sq, BATH_LOGSUM_ODDS, sc, nullptr, nullptr)
+                        : c->kind == 1 ? bath_hip_fs5_forward_parser(c->ctx, c->om, sq, c->cfg_len, sc)
+                                       : bath_hip_fs5_forward_parser_odds(c->ctx, c->om, sq, c->cfg_len, sc);
+  if (sq) bath_hip_seqs_destroy(sq);
+  if (st != BATH_OK) c->failed = true;
+  return st;
+}
+}  // namespace
+
+static int calibrate_fs_strict(bath_hip_ctx *ctx, const bath_hmm *hmm, int ncbi_table, uint32_t *rng_state, int L, int N, double tailp,
+                               double *tau3, double *tau5, double *xv3, double *xv5);
+
 extern "C" int bath_hip_calibrate_fs(bath_hip_ctx *ctx, const bath_hmm *hmm, int ncbi_table, uint32_t *rng_state, int L, int N, double tailp,
                                      double *tau3, double *tau5, double *xv3, double *xv5) {
+  return calibrate_fs_strict(ctx, hmm, ncbi_table, rng_state, L, N, tailp, tau3, tau5, xv3, xv5);
+}
+
+extern "C" int bath_hip_calibrate_fs_arith(bath_hip_ctx *ctx, const bath_hmm *hmm, int ncbi_table, uint32_t *rng_state, int L, int N, double tailp,
+                                           double *tau3, double *tau5, double *xv3, double *xv5, int arith, int *redrawn) {
+  if (!ctx) return BATH_EINVAL;
+  if (arith < BATH_ARITH_STRICT || arith > BATH_ARITH_ODDS) { ctx->set_error("calibrate_fs: arith is 0 (strict), 1 (3-codon parser in odds ratios) or 2 (both parsers)"); return BATH_EINVAL; }
+  if (redrawn) redrawn[0] = redrawn[1] = 0;
+  if (arith == BATH_ARITH_STRICT) return calibrate_fs_strict(ctx, hmm, ncbi_table, rng_state, L, N, tailp, tau3, tau5, xv3, xv5);
+  if (!hmm || !rng_state || !tau3 || !tau5 || L < 2 || N < 2 || !(tailp > 0. && tailp < 1.)) { ctx->set_error("calibrate_fs: needs a model, a generator state, L >= 2, N >= 2 and 0 < tailp < 1"); return BATH_EINVAL; }
+  uint8_t basic[64];
+  if (bath_gencode_basic(ncbi_table, basic) != BATH_OK) { ctx->set_error("calibrate_fs: unknown NCBI translation table " + std::to_string(ncbi_table)); return BATH_EINVAL; }
+  ctx->spans_reset();
+  const float nullsc = bath_bg_fs_nullone(L);
+  const double lambda = (double)hmm->evparam[5];           // p7_FLAMBDA
+  std::vector<double> own((size_t)N);
+  uint32_t state = *rng_state;
+  for (int pass = 0; pass < 2; pass++) {
+    const int cl = pass == 0 ? 3 : 5;
+    bath_fs_profile *gm = nullptr;
+    bath_hip_fsprofile *om = nullptr;
+    int st = bath_fs_profile_config(hmm, basic, cl, L, &gm);
+    if (st == BATH_OK) st = bath_hip_fsprofile_convert(ctx, gm, &om);
+    double *xv = pass == 0 ? (xv3 ? xv3 : own.data()) : (xv5 ? xv5 : own.data());
+    int nre = 0;
+    if (st == BATH_OK) {
+      CalibScore cs{ctx, om, L, pass == 0 ? 0 : (arith == BATH_ARITH_ODDS ? 2 : 1), {}, false};
+      st = bath_calib_fit_scores(&state, kAminoBg, ncbi_table, L, N, calib_score, &cs, nullsc, xv, &nre);
+      if (st == BATH_ERANGE) ctx->set_error("calibrate_fs: more than N sampled sequences had no finite score in the " + std::to_string(cl) + "-codon model");
+      else if (st == BATH_EINVAL && !cs.failed) ctx->set_error("calibrate_fs: translation table " + std::to_string(ncbi_table) + " has no codon for a background residue");
+    }
+    if (redrawn) redrawn[pass] = nre;
+    if (om) bath_hip_fsprofile_destroy(om);
+    if (gm) bath_fs_profile_destroy(gm);
+    if (st != BATH_OK) return st;
+    if ((st = bath_calib_tau(xv, N, lambda, tailp, pass == 0 ? tau3 : tau5)) != BATH_OK) { ctx->set_error("calibrate_fs: the Gumbel fit did not converge"); return st; }
+  }
+  *rng_state = state;
+  return BATH_OK;
+}
+
+static int calibrate_fs_strict(bath_hip_ctx *ctx, const bath_hmm *hmm, int ncbi_table, uint32_t *rng_state, int L, int N, double tailp,
+                               double *tau3, double *tau5, double *xv3, double *xv5) {
   if (!ctx) return BATH_EINVAL;
   if (!hmm || !rng_state || !tau3 || !tau5 || L < 2 || N < 2 || !(tailp > 0. && tailp < 1.)) { ctx->set_error("calibrate_fs: needs a model, a generator state, L >= 2, N >= 2 and 0 < tailp < 1"); return BATH_EINVAL; }
   uint8_t basic[64];

@@ -1761,6 +1761,30 @@ extern "C" int bath_hip_fs5_forward_parser(bath_hip_ctx *ctx, const bath_hip_fsp
   return BATH_OK;
 }
 
+// bath_hip_fs5_forward_parser in the reference's arithmetic: the multihit score of fs5_fwd_odds_kernel and nothing else
+// (fs5_fwd_odds_kernel<C, true, false>).  Odds ratios whatever the context's switches say; -inf for a window shorter than 5 nt and
+// for an overflow (the reference's eslERANGE, which its calibration answers with a redraw: bath_calib_fit_scores).
+extern "C" int bath_hip_fs5_forward_parser_odds(bath_hip_ctx *ctx, const bath_hip_fsprofile *om, const bath_hip_seqs *dna, int cfg_len_amino, float *sc) {
+  if (!ctx || !om || !dna || !sc || om->codon_lengths != 5) { if (ctx) ctx->set_error("needs a 5-codon profile"); return BATH_EINVAL; }
+  if (cfg_len_amino < 0) { ctx->set_error("fs5_forward_parser_odds: the configuration length is negative"); return BATH_EINVAL; }
+  if (bath::fs_model_ok(ctx, om) != BATH_OK) return BATH_EINVAL;
+  BATH_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  const int64_t n = dna->n;
+  if (n == 0) return BATH_OK;
+  int st = om->ensure_len(std::max(dna->maxlen / 3 + 1, cfg_len_amino));
+  if (st != BATH_OK) return st;
+  DevBuf &b_sc = ctx->scratch[21];
+  BATH_HIP_TRY(ctx, b_sc.reserve((size_t)n * 3 * sizeof(float)));
+  bath::FsJobs jq[1];
+  if ((st = bath::fs_schedule(ctx, dna, 1, jq)) != BATH_OK) return st;
+  const int sp = ctx->span_begin("fs5_fwd_odds_parser_kernel", ctx->stream, (double)dna->total * om->M, (double)dna->total);
+  if ((st = bath::launch_fs5_odds_parser(ctx, ctx->stream, om, dna, b_sc.as<float>(), cfg_len_amino, jq[0])) != BATH_OK) return st;
+  ctx->span_end(sp, ctx->stream);
+  BATH_HIP_TRY(ctx, hipMemcpyAsync(sc, b_sc.p, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+  BATH_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  return BATH_OK;
+}
+
 // Envelope rescoring; layouts per envelope i, rows = L_i+1: pp rows*(M+1)*8, oa rows*(M+1)*3, ppx / oax rows*5
 // {E,N,J,B,C} (posterior and OA special-state rows), each packed back to back in envelope order.
 int bath::fs5_envelopes_ex(bath_hip_ctx *ctx, const bath_hip_fsprofile *om, const bath_hip_seqs *dna, int logsum_mode, int c5_compat,

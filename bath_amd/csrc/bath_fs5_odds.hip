@@ -3,13 +3,16 @@
 // p7_Backward_Frameshift :2634-2970; the stochastic-traceback Forward of p7_domaindef.c:411-414), not the log-space generic
 // recursion (generic_fwdback_frameshift.c:64, :1035) the other modes restate.  Switched on by bath_hip_set_fs5_odds.
 //
-//   fs5_fwd_odds_kernel<C, MULTIHIT>
+//   fs5_fwd_odds_kernel<C, MULTIHIT, STORE>
 //       IVX(i,k)  = B(i-1) tBM(k-1) + M(i-1,k-1) tMM(k-1) + I(i-1,k-1) tIM(k-1) + D(i-1,k-1) tDM(k-1)   (rows 1, 2: B only)
 //       M_c(i,k)  = IVX(i-c+1,k) e_c(k), c = 1..5 (c5_compat = 0, fwdback_fs.c:1464);  M(i,k) = sum_c M_c(i,k)
 //       I(i,k)    = M(i-3,k) tMI(k) + I(i-3,k) tII(k);  D(i,k) = M(i,k-1) tMD(k-1) + D(i,k-1) tDD(k-1)
 //       E(i)      = sum_k M(i,k) + D(i,k);  N, J, C from row i-3, B(i) = N(i) tNM + J(i) tJM; rows 1, 2: N = 1, B = tNM
 //       MULTIHIT = false: the envelopes' unihit configuration (p7_fs_ReconfigUnihit: E->J impossible, E->C = 1);
 //       MULTIHIT = true:  the regions' configuration of a fixed amino length (E->C = E->J = 1/2)
+//       STORE = false:    the score alone (calibration's parser, bath_hip_fs5_forward_parser_odds): every store of a cell, of a
+//                         special-state row and of <done> is compiled out with the logarithms that only fed them; the matrix and
+//                         offset pointers are never read; the recurrence, the rescale and sc[job] are the same source
 //   fs5_bwd_odds_kernel<C>  unihit, the mirror image, rows L down to 0: with the rows beyond L held at zero one formula covers
 //       every row case of the generic code (:1054-1392; row L, the tail rows L-1 / L-2, the main recursion)
 //
@@ -76,7 +79,7 @@ __device__ __forceinline__ void mark_done(int *done, int64_t job, int lane) {
 // Forward.  fwd[(i*(M+1)+k)*8 + {D,I,C0..C5}], xmx[i*5 + {E,N,J,B,C}].  Index 0 of a ring = the most recent row.
 // tf[node] = {tMM(k-1), tIM(k-1), tDM(k-1), tBM(k-1), tMD(k), tDD(k), tMI(k), tII(k)}
 // ---------------------------------------------------------------------------------------------
-template <int C, bool MULTIHIT>
+template <int C, bool MULTIHIT, bool STORE = true>
 __global__ __launch_bounds__(kOddsBlock) void fs5_fwd_odds_kernel(SeqView dna, FsOddsDev p, const float *__restrict__ loop_tab, const float *__restrict__ move_tab,
                                                                     float *__restrict__ sc, float *__restrict__ fwd, const int64_t *__restrict__ fwd_off,
                                                                     float *__restrict__ xmx, const int64_t *__restrict__ xmx_off,
@@ -93,16 +96,21 @@ __global__ __launch_bounds__(kOddsBlock) void fs5_fwd_odds_kernel(SeqView dna, F
   for (int64_t job = fs_next_job(jobs, dna.n, lane); job >= 0; job = fs_next_job(jobs, dna.n, lane)) {
     const int L = dna.len[job];
     const uint8_t *d = dna.data + dna.off[job];
-    float *fo = static_cast<float *>(__builtin_assume_aligned(fwd + fwd_off[job], 32));       // rows of (M+1) x 8 floats: every cell is 32-byte aligned
-    float *xo = xmx + xmx_off[job];
-    if (L < 5) { if (lane == 0) sc[job] = -INFINITY; mark_done(done, job, lane); continue; }
+    float *fo = nullptr, *xo = nullptr;
+    if constexpr (STORE) {
+      fo = static_cast<float *>(__builtin_assume_aligned(fwd + fwd_off[job], 32));            // rows of (M+1) x 8 floats: every cell is 32-byte aligned
+      xo = xmx + xmx_off[job];
+    }
+    if (L < 5) { if (lane == 0) sc[job] = -INFINITY; if constexpr (STORE) mark_done(done, job, lane); continue; }
     const int Lc = cfg_len >= 0 ? cfg_len : L / 3;
     const float tNL = expf(loop_tab[Lc]), tNM = expf(move_tab[Lc]), tJL = tNL, tJM = tNM, tCL = tNL, tCM = tNM;
     // row 0, and node 0 of every row
-    const float4 ninf4 = make_float4(-INFINITY, -INFINITY, -INFINITY, -INFINITY);
-    for (int k = lane; k <= M; k += 64) { float4 *c4 = reinterpret_cast<float4 *>(fo + (size_t)k * 8); c4[0] = ninf4; c4[1] = ninf4; }
-    for (int i = 1 + lane; i <= L; i += 64) { float4 *c4 = reinterpret_cast<float4 *>(fo + (size_t)i * (M + 1) * 8); c4[0] = ninf4; c4[1] = ninf4; }
-    if (lane == 0) put_row(xo, 0, 0.f, 1.f, 0.f, tNM, 0.f, 0.0);
+    if constexpr (STORE) {
+      const float4 ninf4 = make_float4(-INFINITY, -INFINITY, -INFINITY, -INFINITY);
+      for (int k = lane; k <= M; k += 64) { float4 *c4 = reinterpret_cast<float4 *>(fo + (size_t)k * 8); c4[0] = ninf4; c4[1] = ninf4; }
+      for (int i = 1 + lane; i <= L; i += 64) { float4 *c4 = reinterpret_cast<float4 *>(fo + (size_t)i * (M + 1) * 8); c4[0] = ninf4; c4[1] = ninf4; }
+      if (lane == 0) put_row(xo, 0, 0.f, 1.f, 0.f, tNM, 0.f, 0.0);
+    }
     float Mr[3][C], Ir[3][C], Dr[C], iv[IVL ? 1 : 4][C];     // M, I of rows i-1..i-3; D of row i-1; IVX(i-1..i-4)
 #pragma unroll
     for (int c = 0; c < C; c++) {
@@ -132,13 +140,14 @@ __global__ __launch_bounds__(kOddsBlock) void fs5_fwd_odds_kernel(SeqView dna, F
 #pragma unroll
       for (int c = 0; c < C; c++) { e1[c] = e1n[c]; e2[c] = e2n[c]; e3[c] = e3n[c]; e4[c] = e4n[c]; e5[c] = e5n[c]; }
       if (i < L) { t = u; u = v; v = w; w = x; x = nuc5(d[i]); if (odds5_ahead<C>()) fetch(x, w, v, u, t); }
-      const float s = (float)totscale;
-      float *row = fo + (size_t)i * (M + 1) * 8;
+      [[maybe_unused]] const float s = (float)totscale;
+      [[maybe_unused]] float *row = STORE ? fo + (size_t)i * (M + 1) * 8 : nullptr;
       // row i-1 at node k-1 for the lane's first node; rows 1, 2 take B(i-1) only (generic :109, :150)
       const float g = (i <= 2) ? 0.f : 1.f;
       const float mIn = wave_shr1(Mr[0][C - 1], 0.f), iIn = wave_shr1(Ir[0][C - 1], 0.f), dIn = wave_shr1(Dr[C - 1], 0.f);
       const float *tf = per_row(p.tf);
-      float Mc[C], Ic[C], ivc[C], c1[C];
+      float Mc[C], Ic[C], ivc[C];
+      [[maybe_unused]] float c1[STORE ? C : 1];
       float mloc = 1.f, aloc = 0.f;                          // the lane's D map: D(first node of the next lane) = mloc D(first node) + aloc
 #pragma unroll
       for (int c = 0; c < C; c++) {
@@ -150,11 +159,12 @@ __global__ __launch_bounds__(kOddsBlock) void fs5_fwd_odds_kernel(SeqView dna, F
         ivc[c] = ivn;
         const float k1 = ivn * e1[c], k2 = ivr(0, c, i) * e2[c], k3 = ivr(1, c, i) * e3[c], k4 = ivr(2, c, i) * e4[c], k5 = ivr(3, c, i) * e5[c];
         const float mv = (k1 + (k2 + k3)) + (k4 + k5);
-        Mc[c] = mv; c1[c] = k1;
+        Mc[c] = mv;
+        if constexpr (STORE) c1[c] = k1;
         Ic[c] = Mr[2][c] * tb.z + Ir[2][c] * tb.w;           // node M: tMI(M) = tII(M) = 0
         aloc = aloc * tb.y + mv * tb.x;
         mloc = mloc * tb.y;
-        if (nd <= M) reinterpret_cast<float4 *>(row + (size_t)nd * 8)[1] = make_float4(ln_odds(k2, s), ln_odds(k3, s), ln_odds(k4, s), ln_odds(k5, s));
+        if constexpr (STORE) if (nd <= M) reinterpret_cast<float4 *>(row + (size_t)nd * 8)[1] = make_float4(ln_odds(k2, s), ln_odds(k3, s), ln_odds(k4, s), ln_odds(k5, s));
       }
       float dcur = affine_scan_excl(mloc, aloc);
       float esum = 0.f, Dc[C];
@@ -164,7 +174,7 @@ __global__ __launch_bounds__(kOddsBlock) void fs5_fwd_odds_kernel(SeqView dna, F
         const float2 tb = *reinterpret_cast<const float2 *>(tf + nd * 8 + 4);      // tMD(k), tDD(k)
         Dc[c] = dcur;
         esum += Mc[c] + dcur;
-        if (nd <= M) reinterpret_cast<float4 *>(row + (size_t)nd * 8)[0] = make_float4(ln_odds(dcur, s), ln_odds(Ic[c], s), ln_odds(Mc[c], s), ln_odds(c1[c], s));
+        if constexpr (STORE) if (nd <= M) reinterpret_cast<float4 *>(row + (size_t)nd * 8)[0] = make_float4(ln_odds(dcur, s), ln_odds(Ic[c], s), ln_odds(Mc[c], s), ln_odds(c1[c], s));
         dcur = dcur * tb.y + Mc[c] * tb.x;
       }
       float xE = wave_sum(esum);
@@ -189,7 +199,7 @@ __global__ __launch_bounds__(kOddsBlock) void fs5_fwd_odds_kernel(SeqView dna, F
         totscale += (double)logf(xE);
         xE = 1.0f;
       }
-      if (lane == 0) put_row(xo, i, xE, nN, nJ, nB, nC, totscale);
+      if constexpr (STORE) if (lane == 0) put_row(xo, i, xE, nN, nJ, nB, nC, totscale);
       xN[2] = xN[1]; xN[1] = xN[0]; xN[0] = nN;
       xJ[2] = xJ[1]; xJ[1] = xJ[0]; xJ[0] = nJ;
       xC[2] = xC[1]; xC[1] = xC[0]; xC[0] = nC;
@@ -207,7 +217,7 @@ __global__ __launch_bounds__(kOddsBlock) void fs5_fwd_odds_kernel(SeqView dna, F
       const float tot = xC[0] + xC[1] * tCL + xC[2] * tCL;    // C(L) + C(L-1) tCL + C(L-2) tCL
       sc[job] = (tot > 0.f && tot < INFINITY) ? (float)(totscale + (double)(logf(tot) + logf(tCM))) : -INFINITY;   // eslERANGE -> -inf, never NaN
     }
-    mark_done(done, job, lane);
+    if constexpr (STORE) mark_done(done, job, lane);
   }
 }
 
@@ -364,6 +374,24 @@ int launch_fs5_odds(bath_hip_ctx *ctx, hipStream_t stream, const bath_hip_fsprof
     else
       hipLaunchKernelGGL((fs5_bwd_odds_kernel<CC>), dim3(grid), dim3(kOddsBlock), 0, stream, dna->view(), p, om->d_loop[1], om->d_move[1], d_sc, d_mx, d_moff,
                          d_xmx, d_xoff, jobs);
+  })
+  BATH_HIP_TRY(ctx, hipGetLastError());
+  return BATH_OK;
+}
+
+// the multihit score of launch_fs5_odds(kFs5OddsRegionFwd) alone: the same kernel instantiated without its stores
+int launch_fs5_odds_parser(bath_hip_ctx *ctx, hipStream_t stream, const bath_hip_fsprofile *om, const bath_hip_seqs *dna, float *d_sc, int cfg_len, FsJobs jobs) {
+  const int64_t n = dna->n;
+  if (n == 0) return BATH_OK;
+  if (om->codon_lengths != 5) { ctx->set_error("the 5-codon odds-ratio kernels need a 5-codon profile"); return BATH_EINVAL; }
+  int st = om->ensure_odds();
+  if (st != BATH_OK) return st;
+  const int Cv = (om->odds_pitch - 4) / 64;                  // the tiling ensure_odds padded the tables for
+  const FsOddsDev p = fs_odds_dev(om);
+  const int grid = fs_odds_grid(ctx, n);
+  BATH_FS_SWITCH(Cv, {
+    hipLaunchKernelGGL((fs5_fwd_odds_kernel<CC, true, false>), dim3(grid), dim3(kOddsBlock), 0, stream, dna->view(), p, om->d_loop[0], om->d_move[0], d_sc,
+                       (float *)nullptr, (const int64_t *)nullptr, (float *)nullptr, (const int64_t *)nullptr, cfg_len, jobs, (int *)nullptr);
   })
   BATH_HIP_TRY(ctx, hipGetLastError());
   return BATH_OK;

@@ -262,5 +262,7 @@ int launch_fs3_odds(bath_hip_ctx *ctx, hipStream_t stream, const bath_hip_fsprof
 enum Fs5OddsKind { kFs5OddsEnvFwd = 0, kFs5OddsEnvBwd = 1, kFs5OddsRegionFwd = 2 };
 int launch_fs5_odds(bath_hip_ctx *ctx, hipStream_t stream, const bath_hip_fsprofile *om, const bath_hip_seqs *dna, Fs5OddsKind kind,
                     float *d_sc, float *d_mx, const int64_t *d_moff, float *d_xmx, const int64_t *d_xoff, int cfg_len, FsJobs jobs, int *d_done);
+// the multihit score of launch_fs5_odds(kFs5OddsRegionFwd) alone: the same kernel instantiated without its stores (calibration in odds arithmetic)
+int launch_fs5_odds_parser(bath_hip_ctx *ctx, hipStream_t stream, const bath_hip_fsprofile *om, const bath_hip_seqs *dna, float *d_sc, int cfg_len, FsJobs jobs);
 
 }  // namespace bath

@@ -720,6 +720,11 @@ int bath_hip_fs5_forward_full(bath_hip_ctx *ctx, const bath_hip_fsprofile *om5, 
  * to global memory.  sc[n]; a window shorter than 5 nt scores -inf.  Always the strict arithmetic (serial table log-sums, bit-identical
  * to the generic reference): bath_hip_set_fs_strict and bath_hip_set_fs5_odds do not reach this entry point. */
 int bath_hip_fs5_forward_parser(bath_hip_ctx *ctx, const bath_hip_fsprofile *om5, const bath_hip_seqs *dna, int cfg_len_amino, float *sc);
+/* The same score in the reference's arithmetic: the multihit score of bath_hip_fs5_forward_full under bath_hip_set_fs5_odds, bit for
+ * bit, and nothing else (the 5-codon odds-ratio Forward instantiated without its stores; what p7_fs_Tau_5codons gets from
+ * p7_ForwardParser_Frameshift_5Codons, impl_sse/fwdback_fs.c).  sc[n]; -inf for a window shorter than 5 nt and for an overflow (the
+ * reference's eslERANGE), never NaN.  Always odds ratios, whatever the context's switches say.  BATH_EINVAL for a 3-codon profile. */
+int bath_hip_fs5_forward_parser_odds(bath_hip_ctx *ctx, const bath_hip_fsprofile *om5, const bath_hip_seqs *dna, int cfg_len_amino, float *sc);
 
 /* ------------------------------------------------------------------------------------------
  * Frameshift calibration (bathconvert.c:128-169): the FS3 / FS5 Forward taus by simulation, and MAXL.
@@ -741,10 +746,29 @@ int    bath_hmm_max_length(const bath_hmm *hmm, double emit_thresh);   /* p7_Bui
 /* p7_fs_Tau_3codons then p7_fs_Tau_5codons of one model (bathconvert.c:147-161): the two frameshift profiles at length L, N sampled
  * sequences each (the 3-codon fit's first, from the same generator), bath_hip_fs3_forward_parser (strict) and
  * bath_hip_fs5_forward_parser, xv[i] = (sc - nullsc) / ln 2, the fits.  xv3 / xv5 (NULL or [N]): the bit scores.  Nothing is redrawn:
- * the reference's redraw is for its odds-ratio parser's overflow, which log space does not have.  BATH_ERANGE: a sequence without
- * a path (L below two codons). */
+ * the reference's redraw is for its odds-ratio parser's overflow, which log space does not have (bath_hip_calibrate_fs_arith below runs
+ * that arithmetic, with the redraw).  BATH_ERANGE: a sequence without a path (L below two codons). */
 int bath_hip_calibrate_fs(bath_hip_ctx *ctx, const bath_hmm *hmm, int ncbi_table, uint32_t *rng_state, int L, int N, double tailp,
                           double *tau3, double *tau5, double *xv3, double *xv5);
+/* The reference's redraw loop (evalues.c:633-649, :728-744, with their `i--; continue`) around a batch scoring callback: sequences
+ * are drawn one after another from the carried generator (bath_calib_sample's stream), a sequence whose score is not finite is
+ * discarded and the next one is drawn from where the generator stands after it, until N scores are kept:
+ * xv[i] = (sc - nullsc) / ln 2 (float difference, double quotient).  score(user, dna, n, L3, sc): n sequences of L3 = 3L codes back to
+ * back, sc[n] out, BATH_OK or an error that ends the fit.  Each call scores what is still missing.  *n_redrawn (or NULL): sequences
+ * discarded; more than N of them in one fit returns BATH_ERANGE (the reference would loop for ever).  *rng_state ends where the
+ * serial loop's generator ends and is left alone on error.  Host only. */
+typedef int (*bath_calib_score_fn)(void *user, const uint8_t *dna, int n, int L3, float *sc);
+int bath_calib_fit_scores(uint32_t *rng_state, const float *f, int ncbi_table, int L, int N, bath_calib_score_fn score, void *user,
+                          float nullsc, double *xv, int *n_redrawn);
+/* bath_hip_calibrate_fs in a chosen arithmetic.  BATH_ARITH_STRICT: that call's result, bit for bit.  BATH_ARITH_ODDS3: the 3-codon
+ * scores from bath_hip_fs3_forward_parser in BATH_LOGSUM_ODDS.  BATH_ARITH_ODDS: also the 5-codon scores from
+ * bath_hip_fs5_forward_parser_odds -- what the reference's bathconvert runs.  The odds modes go through bath_calib_fit_scores;
+ * redrawn[2] (or NULL): sequences discarded in the 3-codon and the 5-codon fit.  The context's switches are neither read nor changed. */
+#define BATH_ARITH_STRICT 0
+#define BATH_ARITH_ODDS3  1
+#define BATH_ARITH_ODDS   2
+int bath_hip_calibrate_fs_arith(bath_hip_ctx *ctx, const bath_hmm *hmm, int ncbi_table, uint32_t *rng_state, int L, int N, double tailp,
+                                double *tau3, double *tau5, double *xv3, double *xv5, int arith, int *redrawn);
 
 /* The multi-domain region stage on its own: the multihit Forward of every sequence of <regions> (each one region, configuration
  * length 100 as the pipeline's) and its trace ensemble in the context's bath_hip_set_fs_ensemble mode.  Per region r:
