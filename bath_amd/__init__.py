@@ -327,6 +327,7 @@ ABI = {
     "bath_hip_ssvfilter_bath": (C.c_int, [_vp, _vp, _vp, C.c_double, C.POINTER(C.POINTER(HmmWindow)), _i64p]),
     "bath_hip_forward_full": (C.c_int, [_vp, _vp, _vp, _i32p, C.c_int, _f32p, _i32p, _f32p, _f32p]),
     "bath_hip_std_envelopes": (C.c_int, [_vp, _vp, _vp, C.POINTER(StdResult), _f32p, _f32p, _f32p, _f32p]),
+    "bath_hip_std_envelopes_fill": (C.c_int, [_vp, _vp, _vp, C.POINTER(StdResult), _f32p, _f32p, _f32p, _f32p, C.c_int]),
     "bath_hip_fs5_envelopes_x": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, C.POINTER(Fs5Result), _f32p, _f32p, _f32p, _f32p]),
     "bath_hip_fs5_forward_full": (C.c_int, [_vp, _vp, _vp, C.c_int, _f32p, _f32p, _f32p]),
     "bath_hip_fs5_envelopes": (C.c_int, [_vp, _vp, _vp, C.c_int, C.c_int, C.POINTER(Fs5Result), _f32p, _i64p, _f32p, _i64p]),
@@ -1407,6 +1408,28 @@ def FS5ForwardFull(ctx, om5, dna, cfg_len_amino=100):
     xmx = np.zeros(int(xo[-1]), dtype=np.float32)
     ctx._check(lib().bath_hip_fs5_forward_full(ctx._h, om5._h, dna._h, cfg_len_amino, _f32(sc), _f32(fwd), _f32(xmx)), "fs5_forward_full")
     return sc, [fwd[fo[i]:fo[i + 1]] for i in range(dna.n)], [xmx[xo[i]:xo[i + 1]] for i in range(dna.n)]
+
+
+STD_FILL_SERIAL, STD_FILL_WAVE, STD_FILL_BLOCK = 0, 1, 2
+
+
+def StdEnvelopes(ctx, om, seqs, fill=STD_FILL_SERIAL):
+    """rescore_isolated_domain_bath's passes over a SeqBlock of amino-acid envelopes (unihit, L = each envelope's length) with the
+    domain stage's kernels chosen by <fill>: STD_FILL_SERIAL a lane per envelope, STD_FILL_WAVE std_envelope_fill_kernel<C>,
+    STD_FILL_BLOCK std_envelope_fill_mw_kernel<C> (the last two for models of up to 1024 nodes).  Returns the StdResult array and,
+    per envelope, the posteriors and the optimal-accuracy matrix (L+1, M+1, 3) {M, D, I} and their special-state rows (L+1, 5)
+    {E, N, J, B, C}: what the stage's traceback reads (row 0 of the posteriors is not part of that)."""
+    M = om.M
+    rows = seqs.lengths.astype(np.int64) + 1
+    do = np.zeros(seqs.n + 1, dtype=np.int64); np.cumsum(rows * (M + 1) * 3, out=do[1:])
+    xo = np.zeros(seqs.n + 1, dtype=np.int64); np.cumsum(rows * 5, out=xo[1:])
+    res = (StdResult * max(seqs.n, 1))()
+    pp, oa = np.zeros(int(do[-1]), np.float32), np.zeros(int(do[-1]), np.float32)
+    ppx, oax = np.zeros(int(xo[-1]), np.float32), np.zeros(int(xo[-1]), np.float32)
+    ctx._check(lib().bath_hip_std_envelopes_fill(ctx._h, om._h, seqs._h, res, _f32(pp), _f32(oa), _f32(ppx), _f32(oax), int(fill)), "std_envelopes_fill")
+    mats = lambda a: [a[do[i]:do[i + 1]].reshape(int(rows[i]), M + 1, 3) for i in range(seqs.n)]
+    xrows = lambda a: [a[xo[i]:xo[i + 1]].reshape(int(rows[i]), 5) for i in range(seqs.n)]
+    return res, mats(pp), mats(oa), xrows(ppx), xrows(oax)
 
 
 def fs_ensemble_loop_scores(L=100):

@@ -1190,7 +1190,8 @@ template <int C>
 __global__ __launch_bounds__(256) void std_envelope_fill_kernel(SeqView sq, int M, const float *__restrict__ tf, const float *__restrict__ rf, float *__restrict__ fwd,
                                                                 float *__restrict__ bck, const int64_t *__restrict__ dp_off, const float *__restrict__ fx,
                                                                 const float *__restrict__ bx, const int64_t *__restrict__ x_off, float *__restrict__ ppx_all,
-                                                                float *__restrict__ oax_all, StdEnvOut *__restrict__ out) {
+                                                                float *__restrict__ oax_all, StdEnvOut *__restrict__ out,
+                                                                float *__restrict__ null2_out /* optional [n][Kp]: the null2 vector itself */) {
   enum { XE = 0, XN, XJ, XB, XC, XS };
   enum { cM = 0, cD = 1, cI = 2 };
   enum { MM = 0, IM, DM, BM, MD, DD, MI, II };
@@ -1376,6 +1377,9 @@ __global__ __launch_bounds__(256) void std_envelope_fill_kernel(SeqView sq, int 
         null2[21 + dx] = sum / (float)cnt;
       }
       null2[20] = 1.0f; null2[27] = 1.0f; null2[28] = 1.0f;
+      if (null2_out && lane == 0)
+#pragma unroll
+        for (int x = 0; x < kKp; x++) null2_out[(size_t)t * kKp + x] = null2[x];
       float corr = 0.f;
       for (int pos = 1 + lane; pos <= L; pos += 64) {
         const int x = min((int)dsq[pos], kKp - 1);
@@ -1405,7 +1409,8 @@ template <int C>
 __global__ __launch_bounds__(256) void std_envelope_fill_mw_kernel(SeqView sq, int M, const float *__restrict__ tf, const float *__restrict__ rf, float *__restrict__ fwd,
                                                                    float *__restrict__ bck, const int64_t *__restrict__ dp_off, const float *__restrict__ fx,
                                                                    const float *__restrict__ bx, const int64_t *__restrict__ x_off, float *__restrict__ ppx_all,
-                                                                   float *__restrict__ oax_all, StdEnvOut *__restrict__ out) {
+                                                                   float *__restrict__ oax_all, StdEnvOut *__restrict__ out,
+                                                                   float *__restrict__ null2_out /* optional [n][Kp]: the null2 vector itself */) {
   enum { XE = 0, XN, XJ, XB, XC, XS };
   enum { cM = 0, cD = 1, cI = 2 };
   enum { MM = 0, IM, DM, BM, MD, DD, MI, II };
@@ -1611,6 +1616,9 @@ __global__ __launch_bounds__(256) void std_envelope_fill_mw_kernel(SeqView sq, i
         null2[21 + dx] = sum / (float)cnt;
       }
       null2[20] = 1.0f; null2[27] = 1.0f; null2[28] = 1.0f;
+      if (null2_out && threadIdx.x == 0)
+#pragma unroll
+        for (int x = 0; x < kKp; x++) null2_out[(size_t)t * kKp + x] = null2[x];
       float corr = 0.f;
       for (int pos = 1 + (int)threadIdx.x; pos <= L; pos += (int)blockDim.x) {
         const int x = min((int)dsq[pos], kKp - 1);
@@ -1699,6 +1707,40 @@ static int std_region_stage(bath_hip_ctx *ctx, const bath_hip_oprofile *om, SeqV
   run_striped(nm, work, [&](int64_t e) { return h_len[e]; });
   if (rc.load() != BATH_OK) { ctx->set_error("a multi-domain region's ensemble failed (a copy from the device, or records that do not add up)"); return rc.load(); }
   clk.lap(dev ? "std:   ensembles (null2 + clustering, host threads)" : "std:   ensembles (host threads)");
+  return BATH_OK;
+}
+
+// The fill kernel std_domains runs before the traceback: 0 none (std_envelope_kernel does everything, a lane per envelope:
+// BATH_HIP_STD_SERIAL=1, or a model beyond the fill kernels' 1024 nodes), 1 a wave per envelope, 2 a block of four waves per
+// envelope -- from 4 nodes per lane on (BATH_HIP_STD_FILL_MW=0: never, =1: for every model).
+static int std_fill_choice(int M) {
+  const char *e = std::getenv("BATH_HIP_STD_SERIAL");
+  if ((e && e[0] == '1') || !(M <= 1024)) return 0;
+  const int c = (M + 63) / 64;
+  const char *mwe = std::getenv("BATH_HIP_STD_FILL_MW");
+  return (mwe ? mwe[0] == '1' : c >= 4) ? 2 : 1;
+}
+
+// Launches std_envelope_fill_kernel<C> (fill == 1) or std_envelope_fill_mw_kernel<C> (fill == 2) for a model of M nodes over <ne>
+// envelopes: the one place where a model length picks an instantiation of either (tests/test_tiling_coverage_cpu.py reads it).
+static int std_launch_fill(bath_hip_ctx *ctx, int M, int fill, SeqView v, int64_t ne, const float *tf, const float *rf, float *f, float *b, const int64_t *dpo,
+                           const float *fx, const float *bx, const int64_t *xoff, float *px, float *ox, StdEnvOut *out, float *null2_out) {
+  if (M > 1024 || (fill != 1 && fill != 2)) { ctx->set_error("the standard branch's fill kernels take models of up to 1024 nodes"); return BATH_ERANGE; }
+  if (fill == 2) {
+    const unsigned mgrid = (unsigned)std::min<int64_t>(ne, (int64_t)ctx->prop.multiProcessorCount * 8);
+#define BATH_FILL_MW(CC) hipLaunchKernelGGL(std_envelope_fill_mw_kernel<CC>, dim3(mgrid), dim3(256), 0, ctx->stream, v, M, tf, rf, f, b, dpo, fx, bx, xoff, px, ox, out, null2_out)
+    const int c4 = (M + 255) / 256;
+    if (c4 <= 1) { BATH_FILL_MW(1); } else if (c4 <= 2) { BATH_FILL_MW(2); } else { BATH_FILL_MW(4); }
+#undef BATH_FILL_MW
+  } else {
+    const unsigned grid = (unsigned)std::min<int64_t>((ne + 3) / 4, (int64_t)ctx->prop.multiProcessorCount * 8);
+#define BATH_FILL(CC) hipLaunchKernelGGL(std_envelope_fill_kernel<CC>, dim3(grid), dim3(256), 0, ctx->stream, v, M, tf, rf, f, b, dpo, fx, bx, xoff, px, ox, out, null2_out)
+    const int c = (M + 63) / 64;
+    if (c <= 1) { BATH_FILL(1); } else if (c <= 2) { BATH_FILL(2); } else if (c <= 3) { BATH_FILL(3); } else if (c <= 4) { BATH_FILL(4); }
+    else if (c <= 6) { BATH_FILL(6); } else if (c <= 8) { BATH_FILL(8); } else if (c <= 12) { BATH_FILL(12); } else { BATH_FILL(16); }
+#undef BATH_FILL
+  }
+  BATH_HIP_TRY(ctx, hipGetLastError());
   return BATH_OK;
 }
 
@@ -1888,31 +1930,10 @@ static int std_domains(bath_hip_ctx *ctx, const bath_hip_oprofile *om, const bat
   if ((st = launch_bwd_wave(ctx, om, ev.view(), ne, b_fx.as<float>(), d_exoff, b_sc.as<float>() + ne, b_st.as<int32_t>() + ne, b_bx.as<float>(), b_b.as<float>(), b_dpo.as<int64_t>(), 1)) != BATH_OK) return st;
   // decoding + OA fill + null2: a wave per envelope; then the traceback, a lane per envelope.  BATH_HIP_STD_SERIAL=1 (tests) or a
   // model longer than 1024 nodes: everything in the lane-per-envelope kernel.
-  int filled = 0;
-  {
-    const char *e = std::getenv("BATH_HIP_STD_SERIAL");
-    const int c = (M + 63) / 64;
-    const unsigned grid = (unsigned)std::min<int64_t>((ne + 3) / 4, (int64_t)ctx->prop.multiProcessorCount * 8);
-#define BATH_FILL(CC) hipLaunchKernelGGL(std_envelope_fill_kernel<CC>, dim3(grid), dim3(256), 0, ctx->stream, ev.view(), M, om->d_tf, om->d_rf, b_f.as<float>(), b_b.as<float>(), \
-                                         b_dpo.as<int64_t>(), b_fx.as<float>(), b_bx.as<float>(), d_exoff, b_px.as<float>(), b_ox.as<float>(), b_out.as<StdEnvOut>()); filled = 1
-    // a block of four waves per envelope from 4 nodes per lane on (BATH_HIP_STD_FILL_MW=0: never, =1: for every model)
-    const char *mwe = std::getenv("BATH_HIP_STD_FILL_MW");
-    const bool mw = M <= 1024 && (mwe ? mwe[0] == '1' : c >= 4);
-    if (!(e && e[0] == '1') && mw) {
-      const unsigned mgrid = (unsigned)std::min<int64_t>(ne, (int64_t)ctx->prop.multiProcessorCount * 8);
-#define BATH_FILL_MW(CC) hipLaunchKernelGGL(std_envelope_fill_mw_kernel<CC>, dim3(mgrid), dim3(256), 0, ctx->stream, ev.view(), M, om->d_tf, om->d_rf, b_f.as<float>(), b_b.as<float>(), \
-                                            b_dpo.as<int64_t>(), b_fx.as<float>(), b_bx.as<float>(), d_exoff, b_px.as<float>(), b_ox.as<float>(), b_out.as<StdEnvOut>()); filled = 1
-      const int c4 = (M + 255) / 256;
-      if (c4 <= 1) { BATH_FILL_MW(1); } else if (c4 <= 2) { BATH_FILL_MW(2); } else { BATH_FILL_MW(4); }
-#undef BATH_FILL_MW
-    } else
-    if (!(e && e[0] == '1')) {
-      if (c <= 1) { BATH_FILL(1); } else if (c <= 2) { BATH_FILL(2); } else if (c <= 3) { BATH_FILL(3); } else if (c <= 4) { BATH_FILL(4); }
-      else if (c <= 6) { BATH_FILL(6); } else if (c <= 8) { BATH_FILL(8); } else if (c <= 12) { BATH_FILL(12); } else if (c <= 16) { BATH_FILL(16); }
-    }
-#undef BATH_FILL
-    BATH_HIP_TRY(ctx, hipGetLastError());
-  }
+  const int fill = std_fill_choice(M);
+  if (fill && (st = std_launch_fill(ctx, M, fill, ev.view(), ne, om->d_tf, om->d_rf, b_f.as<float>(), b_b.as<float>(), b_dpo.as<int64_t>(), b_fx.as<float>(), b_bx.as<float>(), d_exoff,
+                                    b_px.as<float>(), b_ox.as<float>(), b_out.as<StdEnvOut>(), nullptr)) != BATH_OK) return st;
+  const int filled = fill ? 1 : 0;
   const bool lane_trace = [] { const char *e = std::getenv("BATH_HIP_STD_TRACE_LANE"); return e && e[0] == '1'; }();             // A/B and tests: the walk by one lane
   if (filled && !lane_trace)
     hipLaunchKernelGGL(std_trace_wave_kernel, dim3((unsigned)ne), dim3(64), 0, ctx->stream, ev.view(), M, om->d_tf, b_f.as<float>(), b_b.as<float>(), b_dpo.as<int64_t>(), d_exoff,
@@ -2098,13 +2119,14 @@ extern "C" int bath_hip_forward_full(bath_hip_ctx *ctx, const bath_hip_oprofile 
   return BATH_OK;
 }
 
-extern "C" int bath_hip_std_envelopes(bath_hip_ctx *ctx, const bath_hip_oprofile *om, const bath_hip_seqs *sq, bath_std_result *res,
-                                      float *pp, float *oa, float *ppx, float *oax) {
-  if (!ctx || !om || !sq || !res) return BATH_EINVAL;
+extern "C" int bath_hip_std_envelopes_fill(bath_hip_ctx *ctx, const bath_hip_oprofile *om, const bath_hip_seqs *sq, bath_std_result *res,
+                                           float *pp, float *oa, float *ppx, float *oax, int fill) {
+  if (!ctx || !om || !sq || !res || fill < 0 || fill > 2) return BATH_EINVAL;
   BATH_HIP_TRY(ctx, hipSetDevice(ctx->device));
   const int64_t n = sq->n;
   if (n == 0) return BATH_OK;
   const int M = om->M;
+  if (fill && M > 1024) { ctx->set_error("the standard branch's fill kernels take models of up to 1024 nodes"); return BATH_ERANGE; }
   int st = om->ensure_len_tables(sq->maxlen + 1);
   if (st != BATH_OK) return st;
   const BlockOffsets o = block_offsets(sq, M);
@@ -2128,10 +2150,17 @@ extern "C" int bath_hip_std_envelopes(bath_hip_ctx *ctx, const bath_hip_oprofile
   if ((st = launch_fwd_wave(ctx, om, sq->view(), nullptr, n, d_sc, d_st, nullptr, b_fx.as<float>(), d_xo, b_f.as<float>(), d_dpo, 1)) != BATH_OK) return st;
   if ((st = launch_bwd_wave(ctx, om, sq->view(), n, b_fx.as<float>(), d_xo, d_sc + n, d_st + n, b_bx.as<float>(), b_b.as<float>(), d_dpo, 1)) != BATH_OK) return st;
   // p7_Decoding, p7_OptimalAccuracy, p7_Null2_ByExpectation (and the traceback, unused here), a lane per envelope: posteriors
-  // overwrite Backward, the OA matrix overwrites Forward, as in the reference
+  // overwrite Backward, the OA matrix overwrites Forward, as in the reference.  fill 1 / 2: the domain stage's fill kernel for this
+  // model first, then the lane-per-envelope kernel for the traceback alone, as std_domains runs them: what comes back is what the
+  // traceback read
+  if (fill) {
+    BATH_HIP_TRY(ctx, hipMemsetAsync(b_n2.p, 0, (size_t)n * kKp * 4, ctx->stream));       // (an envelope whose decoding overflows gets no null2)
+    if ((st = std_launch_fill(ctx, M, fill, sq->view(), n, om->d_tf, om->d_rf, b_f.as<float>(), b_b.as<float>(), d_dpo, b_fx.as<float>(), b_bx.as<float>(), d_xo,
+                              b_px.as<float>(), b_ox.as<float>(), b_out.as<StdEnvOut>(), b_n2.as<float>())) != BATH_OK) return st;
+  }
   hipLaunchKernelGGL(std_envelope_kernel, dim3((unsigned)((n * kStdTraceSpread + 63) / 64)), dim3(64), 0, ctx->stream, sq->view(), M, om->d_tf, om->d_rf, b_f.as<float>(), b_b.as<float>(), d_dpo,
                      b_fx.as<float>(), b_bx.as<float>(), d_xo, b_px.as<float>(), b_ox.as<float>(), b_em.as<float>(), b_out.as<StdEnvOut>(),
-                     (const uint8_t *)nullptr, b_tb.as<uint8_t>(), d_to, 0, (const float *)nullptr, (const float *)nullptr, (const uint8_t *)nullptr,
+                     (const uint8_t *)nullptr, b_tb.as<uint8_t>(), d_to, fill ? 1 : 0, (const float *)nullptr, (const float *)nullptr, (const uint8_t *)nullptr,
                      (const int64_t *)nullptr, (const int64_t *)nullptr, b_n2.as<float>());
   BATH_HIP_TRY(ctx, hipGetLastError());
   std::vector<StdEnvOut> eo((size_t)n);
@@ -2153,6 +2182,11 @@ extern "C" int bath_hip_std_envelopes(bath_hip_ctx *ctx, const bath_hip_oprofile
     std::memcpy(r.null2, &h_n2[(size_t)e * kKp], sizeof(float) * kKp);
   }
   return BATH_OK;
+}
+
+extern "C" int bath_hip_std_envelopes(bath_hip_ctx *ctx, const bath_hip_oprofile *om, const bath_hip_seqs *sq, bath_std_result *res,
+                                      float *pp, float *oa, float *ppx, float *oax) {
+  return bath_hip_std_envelopes_fill(ctx, om, sq, res, pp, oa, ppx, oax, 0);
 }
 
 extern "C" const char *bath_hip_domain_cigars(const bath_hip_ctx *ctx) { return ctx ? ctx->cigars.c_str() : nullptr; }

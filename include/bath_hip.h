@@ -557,7 +557,11 @@ int  bath_hip_pipeline_hits(bath_hip_ctx *ctx, const bath_hip_oprofile *om, cons
  *   bath_hip_std_envelopes <- p7_Forward + p7_Backward + p7_Decoding + p7_OptimalAccuracy + p7_Null2_ByExpectation on envelopes
  *       (rescore_isolated_domain_bath, p7_domaindef.c:1194-1262; unihit, L = L_i): scores, null2[Kp], posterior matrices <pp>
  *       and optimal-accuracy matrices <oa> in the Forward matrix layout, posterior / OA special-state rows (L_i+1) x {E,N,J,B,C}
- *       in <ppx> / <oax> (any of the four may be NULL). */
+ *       in <ppx> / <oax> (any of the four may be NULL).
+ *   bath_hip_std_envelopes_fill: the same with the domain stage's choice of kernels made by the caller -- fill 0: one lane per
+ *       envelope does everything (bath_hip_std_envelopes); 1: std_envelope_fill_kernel<C>, a wave per envelope, for the model's C,
+ *       then the traceback; 2: std_envelope_fill_mw_kernel<C>, a block of four waves per envelope.  1 and 2 take models of up to
+ *       1024 nodes (BATH_ERANGE beyond).  The matrices are those the stage's traceback reads; row 0 of <pp> is not part of them. */
 typedef struct {
   float   fwdsc, bcksc, oasc;
   int32_t fwd_status, bck_status, ok;       /* ok == 0: numeric range error in decoding (eslERANGE), the domain is dropped */
@@ -567,6 +571,8 @@ int bath_hip_forward_full(bath_hip_ctx *ctx, const bath_hip_oprofile *om, const 
                           float *sc, int32_t *status, float *dp, float *xmx);
 int bath_hip_std_envelopes(bath_hip_ctx *ctx, const bath_hip_oprofile *om, const bath_hip_seqs *sq, bath_std_result *res,
                            float *pp, float *oa, float *ppx, float *oax);
+int bath_hip_std_envelopes_fill(bath_hip_ctx *ctx, const bath_hip_oprofile *om, const bath_hip_seqs *sq, bath_std_result *res,
+                                float *pp, float *oa, float *ppx, float *oax, int fill);
 
 /* ------------------------------------------------------------------------------------------
  * Hit list of a search and its tabular output (P7_TOPHITS; host code).

@@ -369,6 +369,8 @@ int  bo_backward_full(const uint8_t *dsq, int L, const bo_oprofile *om, const fl
 void bo_oprofile_reconfig_unihit(bo_oprofile *om, int L);       /* p7_oprofile.c:1418 */
 void bo_oprofile_reconfig_multihit(bo_oprofile *om, int L);     /* p7_oprofile.c:1395 */
 int  bo_std_envelope_trace(bo_oprofile *om, const uint8_t *dsq, int L, int *path_st, int *path_k, int *path_i, float *oasc_out);   /* test hook: optacc.c:225 on one envelope */
+int  bo_std_envelope_matrices(bo_oprofile *om, const uint8_t *dsq, int L, float *sc, float *pp, float *ppx, float *oa, float *ox, float *null2,
+                              float *fwd, float *bck, float *fx, float *bx);                                     /* test hook: the matrices of that envelope */
 int  bo_domain_decoding(const bo_oprofile *om, const float *fx, const float *bx, int L, int own_scales, float *btot, float *etot, float *mocc); /* decoding.c:155 */
 int  bo_domaindef_std(bo_pipeline *pli, bo_oprofile *om, bo_bg *bg, const uint8_t *dsq, int n, int orf_start, int win_start,
                       int complementarity, int seq_n, bo_fsdomain **doms, int *ndom, int *dalloc, int *nskipped, const uint8_t *strand_dsq);

@@ -351,6 +351,37 @@ int bo_std_envelope_trace(bo_oprofile *om, const uint8_t *dsq, int L, int *path_
   return pn;
 }
 
+/* Test hook: the matrices of one envelope, after the same calls: p7_Forward, p7_Backward, p7_Decoding, p7_OptimalAccuracy and
+ * p7_Null2_ByExpectation on dsq[1..L] in the unihit configuration of length L.  sc: {Forward score, Backward score, oasc};
+ * pp, oa: (L+1) x (M+1) x {M, D, I}; ppx, ox: (L+1) x {E, N, J, B, C}; null2[BO_KP_AMINO]; fwd, bck, fx, bx (any may be NULL):
+ * the parsers' own scaled matrices and (L+1) x 6 rows, before decoding overwrites them.  Returns BO_OK, or BO_ERANGE when decoding
+ * overflows (pp and ppx are then filled, the rest is not). */
+int bo_std_envelope_matrices(bo_oprofile *om, const uint8_t *dsq, int L, float *sc, float *pp, float *ppx, float *oa, float *ox, float *null2,
+                             float *fwd, float *bck, float *fx, float *bx)
+{
+  const int M = om->M;
+  const size_t W = (size_t)(M + 1) * 3, nc = (size_t)(L + 1) * W;
+  bo_oprofile_reconfig_unihit(om, L);
+  float *efx = calloc((size_t)(L + 1) * 6, sizeof(float)), *ebx = calloc((size_t)(L + 1) * 6, sizeof(float));
+  int eown = 0, status = BO_ERANGE;
+  memset(oa, 0, sizeof(float) * nc); memset(pp, 0, sizeof(float) * nc);
+  bo_forward_full(dsq, L, om, oa, efx, &sc[0]);                    /* as in the reference: OA will overwrite Forward, posteriors Backward */
+  bo_backward_full(dsq, L, om, efx, pp, ebx, &sc[1], &eown);
+  if (fwd) memcpy(fwd, oa, sizeof(float) * nc);
+  if (bck) memcpy(bck, pp, sizeof(float) * nc);
+  if (fx) memcpy(fx, efx, sizeof(float) * (size_t)(L + 1) * 6);
+  if (bx) memcpy(bx, ebx, sizeof(float) * (size_t)(L + 1) * 6);
+  sc[2] = 0.0f;
+  if (decoding(om, L, oa, efx, pp, ebx, eown, ppx) != BO_ERANGE) {
+    sc[2] = optimal_accuracy(om, L, pp, ppx, oa, ox);
+    null2_by_expectation(om, L, pp, ppx, null2);
+    status = BO_OK;
+  }
+  free(efx); free(ebx);
+  bo_oprofile_reconfig_multihit(om, L);
+  return status;
+}
+
 /* p7_domaindef_ByPosteriorHeuristics_BATH + p7_pli_postDomainDef_BATH for one ORF that passed the Forward filter.
  * dsq[1..n]: the ORF; orf_start: first nucleotide of the ORF on the strand being read; win_start: windowsq->start on
  * that strand (= orf_start in the plain pipeline, the DNA window's start in the frameshift pipeline's standard branch);

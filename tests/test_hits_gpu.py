@@ -56,14 +56,17 @@ def test_hits_match_recorded_runs(ctx, hmmfile):
 LEDGER = []
 
 
-def _write_ledger():
+def _write_ledger(name="std_branch_ledger.json", record=None):
     """How the standard branch's domains compared in this run: gpurun_out/std_branch_ledger.json (every compare_hits call)."""
+    # (other modules of the standard branch leave their <record> under a <name> of their own in the same place)
     import json, os
     out = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "gpurun_out")
     try:
         os.makedirs(out, exist_ok=True)
-        tot = {k: sum(e[k] for e in LEDGER) for k in ("domains", "clustered_regions", "exact", "unmatched_gpu", "unmatched_oracle", "same_envelope_other_ensemble")}
-        json.dump({"total": tot, "calls": LEDGER}, open(os.path.join(out, "std_branch_ledger.json"), "w"), indent=1)
+        if record is None:
+            tot = {k: sum(e[k] for e in LEDGER) for k in ("domains", "clustered_regions", "exact", "unmatched_gpu", "unmatched_oracle", "same_envelope_other_ensemble")}
+            record = {"total": tot, "calls": LEDGER}
+        json.dump(record, open(os.path.join(out, name), "w"), indent=1)
     except OSError:
         pass
 

@@ -184,3 +184,47 @@ def test_cascade_and_ssv_window_tests_reach_every_tiling():
     wave = tiling("BATH_WAVE_COLUMNS")
     assert tp.CASCADE_MAX_NODES == const_nodes("kCascadeMaxNodes", "BATH_WAVE_COLUMNS") == max(tp.CASCADE_M)
     assert {columns(m, wave) for m in tp.CASCADE_M} >= {c for c in wave if c > 16 or c in (6, 12)}
+
+
+def test_std_envelope_tests_reach_every_instantiation():
+    """std_envelope_fill_kernel<C> and std_envelope_fill_mw_kernel<C> (bath_domaindef.hip): the instantiations are those of the two
+    ladders in std_launch_fill, which the domain stage and bath_hip_std_envelopes_fill both call; test_std_tiling_gpu holds the
+    smallest and the largest model of each, and its pipeline test the first model past them and the cascade's last."""
+    import test_std_tiling_gpu as t
+    dom = src("bath_domaindef.hip")
+    helper = body(dom, "static int std_launch_fill(")
+    fill = [int(x) for x in re.findall(r"\{ BATH_FILL\((\d+)\); \}", helper)]
+    mw = [int(x) for x in re.findall(r"\{ BATH_FILL_MW\((\d+)\); \}", helper)]
+    assert fill == t.STD_FILL_COLUMNS and mw == t.STD_FILL_MW_COLUMNS
+    # one ladder each, in the helper and nowhere else; every launch of a fill kernel is the helper's macro
+    assert len(re.findall(r"BATH_FILL\(\d+\)", dom)) == len(fill) and len(re.findall(r"BATH_FILL_MW\(\d+\)", dom)) == len(mw)
+    assert dom.count("#define BATH_FILL(CC)") == 1 and dom.count("#define BATH_FILL_MW(CC)") == 1 and dom.count("static int std_launch_fill(") == 1
+    assert len(re.findall(r"std_envelope_fill_kernel<[^C]", dom)) == 0 and len(re.findall(r"std_envelope_fill_mw_kernel<[^C]", dom)) == 0
+    assert dom.count("(std_envelope_fill_kernel<CC>,") == 1 and dom.count("(std_envelope_fill_mw_kernel<CC>,") == 1
+    assert len(re.findall(r"[ (]std_launch_fill\(ctx, M, fill, ", dom)) == 2                   # std_domains and the stage-level entry
+    for f, text in csrc_files().items():
+        assert f == "bath_domaindef.hip" or ("BATH_FILL" not in text and "std_envelope_fill" not in text), f
+    # the pick: ceil(M / 64) nodes per lane takes the first entry that fits; the block kernel ceil(M / 256); its last entry has no test
+    assert "const int c = (M + 63) / 64;" in helper and "const int c4 = (M + 255) / 256;" in helper
+    for c in fill[:-1]:
+        assert "(c <= %d) { BATH_FILL(%d); }" % (c, c) in helper
+    for c in mw[:-1]:
+        assert "(c4 <= %d) { BATH_FILL_MW(%d); }" % (c, c) in helper
+    assert "else { BATH_FILL(%d); }" % fill[-1] in helper and "else { BATH_FILL_MW(%d); }" % mw[-1] in helper
+    assert "if (M > 1024 ||" in helper and 64 * fill[-1] == 256 * mw[-1] == 1024 == t.STD_FILL_MAX_NODES
+    # std_domains' default: a fill kernel up to 1024 nodes, the block kernel from 4 nodes per lane on
+    choice = body(dom, "static int std_fill_choice(")
+    assert "!(M <= 1024)) return 0;" in choice and "const int c = (M + 63) / 64;" in choice and "c >= 4) ? 2 : 1;" in choice
+    assert 'std::getenv("BATH_HIP_STD_SERIAL")' in choice and 'std::getenv("BATH_HIP_STD_FILL_MW")' in choice
+    assert "const int fill = std_fill_choice(M);" in dom
+    missing = [(c, m) for c, lo, hi in lengths_per_column(fill) for m in (lo, hi) if m not in t.STD_M]
+    assert not missing, "std_envelope_fill_kernel instantiations without a test at this model length: %s" % missing
+    prev = 0
+    for c in mw:
+        assert 256 * prev + 1 in t.STD_M and 256 * c in t.STD_M, "std_envelope_fill_mw_kernel<%d> without a test at both ends" % c
+        prev = c
+    assert all(columns(m, fill) is not None for m in t.STD_M) and max(t.STD_M) == 1024
+    # the default takes the block kernel from 193 nodes on: both sides of that are there
+    assert 192 in t.STD_M and 193 in t.STD_M
+    assert 1025 in t.PIPELINE_M and const_nodes("kCascadeMaxNodes", "BATH_WAVE_COLUMNS") in t.PIPELINE_M
+    assert all(m <= 1024 and v == ["0"] for m, v in t.PIPELINE_M.items() if v) and {columns(m, fill) for m, v in t.PIPELINE_M.items() if v} == {4, 12}
