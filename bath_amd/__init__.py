@@ -154,6 +154,11 @@ class AliDisplayOpts(C.Structure):
                 ("initiator", C.c_int32)]
 
 
+class FsRow(C.Structure):
+    """bath_fs_row: one row of --fstblout."""
+    _fields_ = [("type", C.c_char), ("length", C.c_int32), ("ali_start", C.c_int32), ("seq_start", C.c_int64)]
+
+
 class DistItem(C.Structure):
     """bath_dist_item: windows [lo, hi) of query <query>."""
     _fields_ = [("query", C.c_int32), ("lo", C.c_int64), ("hi", C.c_int64)]
@@ -314,6 +319,9 @@ ABI = {
     "bath_tophits_pipeline_statistics": (C.c_int64, [_vp, C.POINTER(PipelineStats), C.POINTER(PipelineParams), C.c_int64, C.c_int64, C.c_int64, C.c_char_p, C.c_int64]),
     "bath_tophits_set_inclusion": (None, [_vp, C.c_double]),
     "bath_tophits_tabular_targets": (C.c_int64, [_vp, C.c_char_p, C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_int64]),
+    "bath_trace_frameshift_rows": (C.c_int64, [C.POINTER(DomainTrace), C.POINTER(C.c_int8), _i32p, _i32p, C.POINTER(C.c_int8), _u8p, C.c_int32,
+                                               C.POINTER(_FsProfile), C.c_int64, C.c_int64, C.POINTER(FsRow), C.c_int64]),
+    "bath_tophits_tabular_frameshifts": (C.c_int64, [_vp, C.c_char_p, C.c_char_p, C.POINTER(FsRow), _i64p, C.c_int64, C.c_int, C.c_char_p, C.c_int64]),
     "bath_hip_pipeline_hits": (C.c_int, [_vp, _vp, _vp, C.POINTER(PipelineParams), C.c_double, C.POINTER(PipelineStats),
                                          C.POINTER(C.POINTER(FsDomain)), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     "bath_hip_pipeline_frameshift_domains": (C.c_int, [_vp, _vp, _vp, _vp, _vp, C.POINTER(PipelineParams), C.c_double, C.POINTER(PipelineStats),
@@ -1117,6 +1125,26 @@ def alidisplay_print(trace, window_codes, hmm, sqfrom, sqto, seq_name, gm_fs5=No
     return buf.raw[:n].decode()
 
 
+def frameshift_rows(trace, window_codes, gm_fs5, iali, jali):
+    """The --fstblout rows of one hit (bath_trace_frameshift_rows: the loop of p7_tophits_TabularFrameshifts over its trace):
+    [(type, length, seq_start, ali_start)], type 'D' / 'I' for a quasi-codon that lacks / has extra nucleotides, 'S' for a stop
+    codon in a match state.  trace, window_codes, gm_fs5 as alidisplay_print takes them; a standard-branch trace has no rows."""
+    t, st, k, i, c = trace[:5]
+    st = np.ascontiguousarray(st, np.int8); k = np.ascontiguousarray(k, np.int32); i = np.ascontiguousarray(i, np.int32)
+    c = np.ascontiguousarray(c, np.int8)
+    win = np.ascontiguousarray(window_codes, np.uint8)
+    tr = DomainTrace(0, int(t.N), int(t.win_start), int(t.orf_start), int(t.frameshift))
+    p8 = lambda a: a.ctypes.data_as(C.POINTER(C.c_int8))
+    args = [C.byref(tr), p8(st), k.ctypes.data_as(_i32p), i.ctypes.data_as(_i32p), p8(c), _u8(win), len(win),
+            gm_fs5._p if gm_fs5 is not None else None, int(iali), int(jali)]
+    n = lib().bath_trace_frameshift_rows(*args, None, 0)
+    if n < 0:
+        raise BathError("frameshift_rows failed")
+    rows = (FsRow * max(n, 1))()
+    lib().bath_trace_frameshift_rows(*args, rows, n)
+    return [(rows[x].type.decode(), int(rows[x].length), int(rows[x].seq_start), int(rows[x].ali_start)) for x in range(n)]
+
+
 class HitArray:
     """The hits of a pipeline call as one numpy record array (dtype of FsDomain) plus the pool their cigar_off fields point into."""
 
@@ -1232,7 +1260,7 @@ class HitArray:
 
 class TopHits:
     """P7_TOPHITS for this path: collect the hits of pipeline calls, finish the search (E-values, duplicates, sorting,
-    thresholds; bathsearch.c:868-921) and print --tblout (p7_tophits_TabularTargets)."""
+    thresholds; bathsearch.c:868-921) and print --tblout (p7_tophits_TabularTargets) and --fstblout (p7_tophits_TabularFrameshifts)."""
 
     def __init__(self):
         self._h = lib().bath_tophits_create()
@@ -1313,6 +1341,25 @@ class TopHits:
         n = lib().bath_tophits_tabular_targets(*args, None, 0)
         buf = C.create_string_buffer(n + 1)
         lib().bath_tophits_tabular_targets(*args, buf, n)
+        return buf.raw[:n].decode()
+
+    def fstblout(self, qname, qacc, rows_by_reported_hit, show_header=True):
+        """--fstblout (p7_tophits_TabularFrameshifts): rows_by_reported_hit[r] is frameshift_rows() of the r-th reported hit in
+        the list's current order -- of hits(), those with flag 1.  The header is written only when the list holds a hit."""
+        nrep = len(rows_by_reported_hit)
+        off = (C.c_int64 * (nrep + 1))()
+        flat = [x for rows in rows_by_reported_hit for x in rows]
+        arr = (FsRow * max(len(flat), 1))()
+        for r, rows in enumerate(rows_by_reported_hit):
+            off[r + 1] = off[r] + len(rows)
+        for x, (typ, length, seq_start, ali_start) in enumerate(flat):
+            arr[x] = FsRow(typ.encode(), int(length), int(ali_start), int(seq_start))
+        args = (self._h, qname.encode(), (qacc or "").encode(), arr, off, nrep, int(show_header))
+        n = lib().bath_tophits_tabular_frameshifts(*args, None, 0)
+        if n < 0:
+            raise BathError("tophits_tabular_frameshifts failed: %d row lists for %d reported hits" % (nrep, self.reported()))
+        buf = C.create_string_buffer(n + 1)
+        lib().bath_tophits_tabular_frameshifts(*args, buf, n)
         return buf.raw[:n].decode()
 
     def annotations(self, M, fs_pipe=False):

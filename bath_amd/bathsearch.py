@@ -4,7 +4,14 @@
 
 The FASTA file's bytes go to the device as they are (bath_amd.FastaTargets: records, digitising and the windows of
 esl_sqio_ReadWindow are found there); per query the windows run through the pipeline in blocks of at most <block_nt>
-nucleotides, and the hits are finished, sorted and printed as bathsearch.c does (main output and --tblout).
+nucleotides, and the hits are finished, sorted and printed as bathsearch.c does (main output, --tblout and --fstblout).
+
+--fstblout <f> (needs --fs) writes the table of frameshift and stop-codon locations (p7_tophits_TabularFrameshifts): a row per
+quasi-codon and per stop codon in a match state of every reported hit of the frameshift branch, from the same trace and the same
+window codes its alignment block is rendered from (main_output_query); the file is opened, filled per query and closed with the
+same tail as the --tblout file, in every run mode.  Its header lines come with the first query only, and only when that query's hit
+list is not empty (the reference's rule).  --notrans adds its header line and changes nothing else: the reference sets
+pli->show_translated_sequence and never reads it, so the translation line of the alignment blocks is printed regardless.
 
 Every option the library implements is mapped; every other bathsearch option, a sequence or alignment query and a target file that
 is not plain FASTA are refused (exit status 1, a message naming it).
@@ -50,7 +57,8 @@ BANNER = ("# bathsearch :: search protein profile(s) against DNA sequence databa
 RULE = "# - - - - - - - - - - - - - - - - - - - - - - - - - - - - - - - - - - - -\n\n"
 
 # option -> kind ('flag', int, float, str)
-OPTIONS = {"-o": str, "--tblout": str, "--fs": "flag", "--cigar": "flag", "--frameline": "flag", "--textw": int, "--notextw": "flag",
+OPTIONS = {"-o": str, "--tblout": str, "--fstblout": str, "--fs": "flag", "--cigar": "flag", "--frameline": "flag", "--textw": int, "--notextw": "flag",
+           "--notrans": "flag",    # accepted as the reference accepts it: a header line, nothing else
            "--ct": int, "-l": int, "-m": "flag", "-M": "flag", "--strand": str,
            "-E": float, "-T": float, "--incT": float, "-Z": float, "--seed": int,
            "--F1": float, "--F2": float, "--F3": float, "--F4": float, "--max": "flag", "--nobias": "flag", "--nonull2": "flag", "--fsonly": "flag",
@@ -61,14 +69,15 @@ OPTIONS = {"-o": str, "--tblout": str, "--fs": "flag", "--cigar": "flag", "--fra
            "--ensemble-std": str}  # ... and how the standard branch does (a search without --fs; the --fs windows that take that branch)
 MAX_GPUS = 16
 MAX_WORKERS = 8
-# bathsearch options this driver does not implement: refused, never ignored
-REFUSED = ["-h", "--splice", "--exontblout", "--fstblout", "--hmmout", "--acc", "--noali", "--notrans", "--min_intron", "--max_intron",
+# bathsearch options this driver does not implement: refused, never ignored (--crick and --watson too: the reference declares them
+# and never reads them)
+REFUSED = ["-h", "--splice", "--exontblout", "--hmmout", "--acc", "--noali", "--min_intron", "--max_intron",
            "--incE", "--qformat", "--tformat", "--singlemx", "--popen", "--pextend", "--mx", "--mxfile", "--w_beta", "--w_length", "--cpu",
            "--restrictdb_stkey", "--restrictdb_n", "--ssifile", "--domZ", "--domE", "--domT", "--incdomE", "--incdomT", "--crick", "--watson",
            "--nodeinfo"]
 EXCLUSIVE = [("-m", "-M"), ("--textw", "--notextw"), ("-E", "-T"), ("--max", "--F1"), ("--max", "--F2"), ("--max", "--F3"), ("--max", "--F4"),
              ("--max", "--nobias")]
-REQUIRES = {"--frameline": "--fs", "--cigar": "--tblout", "--F4": "--fs", "--arith": "--fs"}
+REQUIRES = {"--frameline": "--fs", "--cigar": "--tblout", "--F4": "--fs", "--arith": "--fs", "--fstblout": "--fs"}
 
 
 # bathsearch.c:748-750 (the reference's spelling): a model without the frameshift taus, such as a plain HMMER3 file's
@@ -148,7 +157,8 @@ def output_header(opts, hmmfile, seqfile):
     s += "# query HMM file:                                %s\n" % hmmfile
     s += "# target sequence database:                      %s\n" % seqfile
     s += "# codon translation table:                       %d\n" % o.get("--ct", 1)
-    lines = [("-o", "# output directed to file:                       %s\n"), ("--tblout", "# per-seq hits tabular output:                   %s\n")]
+    lines = [("-o", "# output directed to file:                       %s\n"), ("--tblout", "# per-seq hits tabular output:                   %s\n"),
+             ("--fstblout", "# frameshift tabular output:                     %s\n")]
     for k, f in lines:
         if k in o:
             s += f % o[k]
@@ -156,6 +166,8 @@ def output_header(opts, hmmfile, seqfile):
         s += "# max ASCII text line length:                    unlimited\n"
     if "--textw" in o:
         s += "# max ASCII text line length:                    %d\n" % o["--textw"]
+    if "--notrans" in o:
+        s += "# show translated DNA sequence:                  no\n"
     for k, f in [("-E", "# sequence reporting threshold:       E-value <= %g\n"), ("-T", "# sequence reporting threshold:         score >= %g\n"),
                  ("--incT", "# sequence inclusion threshold:         score >= %g\n")]:
         if k in o:
@@ -405,7 +417,9 @@ def _key(d):
     return (int(d.window), int(d.iali), int(d.jali), int(d.ihmm), int(d.jhmm), float(d.bitscore))
 
 
-def main_output_query(hmm, desc, r, opts, targets, elapsed, cpu):
+def main_output_query(hmm, desc, r, opts, targets, elapsed, cpu, fs_rows=None):
+    """The query's block of the main output.  fs_rows: a list that receives, per reported hit in the order of the block, the hit's
+    --fstblout rows (ba.frameshift_rows), made from the window codes its alignment block is rendered from."""
     fs = "--fs" in opts
     textw = 0 if "--notextw" in opts else opts.get("--textw", 150)
     th = r["th"]
@@ -424,6 +438,8 @@ def main_output_query(hmm, desc, r, opts, targets, elapsed, cpu):
         bottom = d.iali > d.jali
         strand = revcomp(codes) if bottom else codes
         win = strand[h.trace[0].win_start - 1:]
+        if fs_rows is not None:
+            fs_rows.append(ba.frameshift_rows(h.trace, win, r["gm5"], d.iali, d.jali))
         ali = ba.alidisplay_print(h.trace, win, hmm, d.iali, d.jali, r["names"][idx], gm_fs5=r["gm5"], gm=r["gm"], ncbi_table=opts.get("--ct", 1),
                                   textw=textw, frameline="--frameline" in opts,
                                   initiator=ba.INIT_AUG if "-m" in opts else (ba.INIT_TABLE if "-M" in opts else ba.INIT_ANY))
@@ -435,6 +451,13 @@ def main_output_query(hmm, desc, r, opts, targets, elapsed, cpu):
     s += timing_lines(cpu[0], cpu[1], elapsed, r["nres"], hmm.M)
     s += "//\n"
     return s
+
+
+def tabular_query(hmm, th, opts, q, fs_rows):
+    """(--tblout rows, --fstblout rows) of query <q>, '' for a file not asked for; the header lines go with the first query."""
+    tbl = th.tblout(hmm.name, hmm.acc, hmm.M, fs_pipe="--fs" in opts, show_cigar="--cigar" in opts, show_header=(q == 0)) if "--tblout" in opts else ""
+    fstbl = th.fstblout(hmm.name, hmm.acc, fs_rows, show_header=(q == 0)) if "--fstblout" in opts else ""
+    return tbl, fstbl
 
 
 class _CodesSource:
@@ -470,8 +493,8 @@ class _CodesSource:
 # starts N fresh children (rank_main).  Every rank ingests the whole target file, cuts every query's windows into (query, window
 # group) items the same way (search_plan), searches the items dealt to it, and ships each item's hits -- with their CIGARs and
 # traces, in the library's hit stream -- and counters to the query's owner (dist.query_owner), which merges them in item order,
-# finishes the query over the whole search's residues and renders its main-output block and --tblout rows.  Rank 0 writes the
-# blocks in query order and the [ok] line last.
+# finishes the query over the whole search's residues and renders its main-output block and its --tblout and --fstblout rows.
+# Rank 0 writes the blocks in query order and the [ok] line last.
 # ---------------------------------------------------------------------------------------------------------------------------
 
 BATCH_QUERIES = 256         # queries planned and merged together: what a rank holds of the hits at once
@@ -705,7 +728,7 @@ def _search_items(ctx, hmm, ft, wins, items, opts, block_nt, cancelled=None):
 
 def _render_query(q, hmm, desc, parts, opts, names, descs, lengths, src, t0, c0):
     """The owner's end of query <q>: its items' hits added in item order, counters summed, the query finished as search_query
-    finishes it, and its main-output block and --tblout rows rendered."""
+    finishes it, and its main-output block, --tblout rows and --fstblout rows rendered."""
     fs = "--fs" in opts
     ct = opts.get("--ct", 1)
     th = ba.TopHits()
@@ -725,9 +748,9 @@ def _render_query(q, hmm, desc, parts, opts, names, descs, lengths, src, t0, c0)
     r = dict(th=th, stats=total, pipe=ba.Pipeline(None, None, fs_pipe=fs, ncbi_table=ct, **pipeline_overrides(opts)), traces=traces,
              nseqs=len(names), gm=ba.Profile(hmm), gm5=ba.FSProfile(hmm, 5, ncbi_table=ct), names=names, nres=total.nres)
     c1 = os.times()
-    block = main_output_query(hmm, desc, r, opts, src, time.time() - t0, (c1.user - c0.user, c1.system - c0.system))
-    tbl = th.tblout(hmm.name, hmm.acc, hmm.M, fs_pipe=fs, show_cigar="--cigar" in opts, show_header=(q == 0)) if "--tblout" in opts else ""
-    return block, tbl
+    fs_rows = [] if "--fstblout" in opts else None
+    block = main_output_query(hmm, desc, r, opts, src, time.time() - t0, (c1.user - c0.user, c1.system - c0.system), fs_rows)
+    return (block,) + tabular_query(hmm, th, opts, q, fs_rows)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
@@ -1032,10 +1055,11 @@ def _rank_search(argv, opts, hmmfile, seqfile, rank, world, device, dev, chunk_b
     qdescs = model_descriptions(hmmfile)
     strand = opts.get("--strand", "both")
     block_length = opts.get("--block_length", dist.BLOCK_LENGTH)
-    ofp = tblfp = pool = None
+    ofp = tblfp = fstblfp = pool = None
     if rank == 0:
         ofp = open(opts["-o"], "w") if "-o" in opts else sys.stdout
         tblfp = open(opts["--tblout"], "w") if "--tblout" in opts else None
+        fstblfp = open(opts["--fstblout"], "w") if "--fstblout" in opts else None
     try:
         if ofp:
             ofp.write(output_header(opts, hmmfile, seqfile))
@@ -1106,20 +1130,24 @@ def _rank_search(argv, opts, hmmfile, seqfile, rank, world, device, dev, chunk_b
                     text = _render_query(q, hmms[k], qdescs[q] if q < len(qdescs) else None, parts.pop(k, []), opts, names, descs, lengths,
                                          src, t0, c0)
                     if rank != 0:
-                        _send_text("%d\n%s%s" % (len(text[0]), text[0], text[1]), 0, dev)
+                        _send_text("%d %d\n%s%s%s" % ((len(text[0]), len(text[1])) + text), 0, dev)
                 elif rank == 0:
                     msg = _recv_text(owner, dev)
                     head, rest = msg.split("\n", 1)
-                    text = (rest[:int(head)], rest[int(head):])
+                    n0, n1 = (int(x) for x in head.split())
+                    text = (rest[:n0], rest[n0:n0 + n1], rest[n0 + n1:])
                 if rank == 0:
                     ofp.write(text[0])
                     if tblfp:
                         tblfp.write(text[1])
+                    if fstblfp:
+                        fstblfp.write(text[2])
                     ofp.flush()
             laps["merge_write_s"] += time.perf_counter() - tm
         if rank == 0:
-            if tblfp:
-                tblfp.write(tabular_tail(hmmfile, seqfile, argv))
+            for fp in (tblfp, fstblfp):
+                if fp:
+                    fp.write(tabular_tail(hmmfile, seqfile, argv))
             ofp.write("[ok]\n")
     finally:
         if pool is not None:
@@ -1128,8 +1156,9 @@ def _rank_search(argv, opts, hmmfile, seqfile, rank, world, device, dev, chunk_b
             ofp.close()
         elif ofp is not None:
             ofp.flush()
-        if tblfp:
-            tblfp.close()
+        for fp in (tblfp, fstblfp):
+            if fp:
+                fp.close()
     return 0
 
 
@@ -1222,15 +1251,18 @@ def run(argv, stdout=None, chunk_bytes=64 << 20, block_nt=256_000_000, resident_
     descs = model_descriptions(hmmfile)
     ofp = open(opts["-o"], "w") if "-o" in opts else stdout
     tblfp = open(opts["--tblout"], "w") if "--tblout" in opts else None
+    fstblfp = open(opts["--fstblout"], "w") if "--fstblout" in opts else None
     workers = opts.get("--workers", 1)
     threads = host_threads_per_worker(workers) if workers > 1 else None
     try:
         ofp.write(output_header(opts, hmmfile, seqfile))
         if workers > 1:
-            def write(q, text):
+            def write(q, text):                      # (main output, --tblout rows[, --fstblout rows]) of query q
                 ofp.write(text[0])
                 if tblfp:
                     tblfp.write(text[1])
+                if fstblfp and len(text) > 2:
+                    fstblfp.write(text[2])
                 ofp.flush()
             if threads is not None:                  # the library reads it at every ensemble: each worker context's share
                 os.environ["BATH_HIP_HOST_THREADS"] = str(threads)
@@ -1247,13 +1279,18 @@ def run(argv, stdout=None, chunk_bytes=64 << 20, block_nt=256_000_000, resident_
                 t0, c0 = time.time(), os.times()
                 r = search_query(ctx, hmm, targets, opts, block_nt, None)
                 c1 = os.times()
+                fs_rows = [] if fstblfp else None
                 ofp.write(main_output_query(hmm, descs[q] if q < len(descs) else None, r, opts, src, time.time() - t0,
-                                            (c1.user - c0.user, c1.system - c0.system)))
+                                            (c1.user - c0.user, c1.system - c0.system), fs_rows))
+                tbl, fstbl = tabular_query(hmm, r["th"], opts, q, fs_rows)
                 if tblfp:
-                    tblfp.write(r["th"].tblout(hmm.name, hmm.acc, hmm.M, fs_pipe="--fs" in opts, show_cigar="--cigar" in opts, show_header=(q == 0)))
+                    tblfp.write(tbl)
+                if fstblfp:
+                    fstblfp.write(fstbl)
                 ofp.flush()
-        if tblfp:
-            tblfp.write(tabular_tail(hmmfile, seqfile, argv))
+        for fp in (tblfp, fstblfp):
+            if fp:
+                fp.write(tabular_tail(hmmfile, seqfile, argv))
         ofp.write("[ok]\n")
     except ba.FastaFormatError as e:
         sys.stderr.write("Error: %s: %s\n" % (seqfile, e))
@@ -1266,8 +1303,9 @@ def run(argv, stdout=None, chunk_bytes=64 << 20, block_nt=256_000_000, resident_
             os.environ.pop("BATH_HIP_HOST_THREADS", None)
         if ofp is not stdout:
             ofp.close()
-        if tblfp:
-            tblfp.close()
+        for fp in (tblfp, fstblfp):
+            if fp:
+                fp.close()
     return 0
 
 

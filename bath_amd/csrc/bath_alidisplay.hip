@@ -17,13 +17,15 @@
 #include <string>
 #include <vector>
 
+#include "bath_codons.hpp"
 #include "bath_hip.h"
 
 namespace {
 
+using namespace bath;   // the I_* codes, codon_index, codon_row, codon3_is_stop
+
 const char kAmino[] = "ACDEFGHIKLMNPQRSTVWY-BJZOUX*~";
 const char kDna[] = "ACGT-RYMKSWHBVDN*~";
-enum { I___X = 0, I_X__, I_XX_, I_X_X, I__XX, I_XXX, I_XXx, I_XxX, I_xXX, I_xxx, I_XXxX, I_XxXX, I_xXXX, I_XXxxX, I_XxxXX, I_xxXXX };   // hmmer.h:252-270
 
 void appendf(std::string &out, const char *fmt, ...) {
   char tmp[512];
@@ -36,19 +38,6 @@ void appendf(std::string &out, const char *fmt, ...) {
 
 int integer_textwidth(long n) { int w = (n < 0) ? 1 : 0; while (n != 0) { n /= 10; w++; } return w; }
 char encode_pp(float p) { return (p + 0.05 >= 1.0) ? '*' : (char)((char)((p + 0.05) * 10.0) + '0'); }
-
-// get_codon_index, p7_alidisplay.c:32-88
-int codon_index(int len, const int *n) {
-  bool canon = true;
-  for (int q = 0; q < len; q++) canon = canon && n[q] >= 0 && n[q] < 4;
-  switch (len) {
-    case 1: return canon ? n[0] * 341 : 1366;
-    case 2: return canon ? n[1] * 341 + n[0] * 85 + 1 : 1365;
-    case 3: return canon ? n[2] * 341 + n[1] * 85 + n[0] * 21 + 2 : 1364;
-    case 4: return canon ? n[3] * 341 + n[2] * 85 + n[1] * 21 + n[0] * 5 + 3 : 1365;
-    default: return canon ? n[4] * 341 + n[3] * 85 + n[2] * 21 + n[1] * 5 + n[0] + 4 : 1366;
-  }
-}
 
 char low(char ch) { return (char)std::tolower((unsigned char)ch); }
 char sym(int x) { return (x >= 0 && x < 18) ? kDna[x] : '?'; }
@@ -146,8 +135,7 @@ extern "C" int64_t bath_alidisplay_print(const bath_domain_trace *tr, const int8
       if (cl < 1 || cl > 5) return -1;
       int n[5] = {-1, -1, -1, -1, -1};
       for (int q = 0; q < cl; q++) n[q] = nt(ii - cl + 1 + q);
-      const int idx = codon_index(cl, n);
-      const size_t row = (size_t)kk * (size_t)gm_fs5->maxcodons + (size_t)idx;
+      const size_t row = codon_row(gm_fs5, kk, cl, n);
       const int aa = gm_fs5->codons[row], indel = gm_fs5->indel_pos[row];
       ad.model[(size_t)z] = o->consensus[kk];
       ad.codon[(size_t)z] = cl;
@@ -159,7 +147,7 @@ extern "C" int64_t bath_alidisplay_print(const bath_domain_trace *tr, const int8
       if (aa == cons_code) ad.mline[(size_t)z] = ad.model[(size_t)z];
       else if (expf(msc) > 1.0f) ad.mline[(size_t)z] = '+';
       ad.aseq[(size_t)z] = (char)std::toupper((unsigned char)kAmino[aa]);
-      if (cl == 3 && (indel == I_XXx || indel == I_XxX || indel == I_xXX)) ad.codon[(size_t)z] = 6;   // a stop codon
+      if (cl == 3 && codon3_is_stop(indel)) ad.codon[(size_t)z] = 6;
     } else if (s == BATH_T_M) {                                         // p7_alidisplay_nonfs_Create, :1100-1130
       const int a = nt(ii - 2), b = nt(ii - 1), cc = nt(ii);
       int aa = translate(basic, a, b, cc);
@@ -179,10 +167,10 @@ extern "C" int64_t bath_alidisplay_print(const bath_domain_trace *tr, const int8
       ad.codon[(size_t)z] = 3;
       if (tr->frameshift) {                                             // :865-885: lower case; a stop codon reads '*'
         const int n[3] = {a, b, cc};
-        const size_t row = (size_t)kk * (size_t)gm_fs5->maxcodons + (size_t)codon_index(3, n);
+        const size_t row = codon_row(gm_fs5, kk, 3, n);
         const int indel = gm_fs5->indel_pos[row];
         int aa = gm_fs5->codons[row];
-        if (indel == I_XXx || indel == I_XxX || indel == I_xXX) { ad.codon[(size_t)z] = 6; aa = 27; }
+        if (codon3_is_stop(indel)) { ad.codon[(size_t)z] = 6; aa = 27; }
         ad.aseq[(size_t)z] = low(kAmino[aa]);
         n5[1] = sym(a); n5[2] = sym(b); n5[3] = sym(cc);
       } else {                                                          // :1145-1160: upper case

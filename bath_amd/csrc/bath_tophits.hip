@@ -7,6 +7,7 @@
 //   p7_tophits_SortBySortkey              :345 with hit_sorter_by_sortkey :261-283
 //   p7_tophits_Threshold                  :914-966 (pli->Z = 1, by E-value)
 //   p7_tophits_TabularTargets             :1603-1729 (--tblout, with or without --cigar, with or without --fs)
+//   p7_tophits_TabularFrameshifts         :1428-1582 (--fstblout: a row per frameshift and per stop codon of every reported --fs hit)
 // A hit is one bath_fs_domain that passed the in-pipeline E-value test (p7_pipeline.c:1080, 1246), with the names of its
 // target sequence.  qsort is not stable and neither need this be: ties are broken by the comparators' own secondary keys.
 #include <algorithm>
@@ -18,6 +19,7 @@
 #include <string>
 #include <vector>
 
+#include "bath_codons.hpp"
 #include "bath_hip.h"
 
 namespace {
@@ -181,14 +183,11 @@ void appendf(std::string &out, const char *fmt, ...) {
   va_end(ap);
   out.append(big.data(), (size_t)n);
 }
-}  // namespace
 
-// p7_tophits_TabularTargets, p7_tophits.c:1603-1729 (pli->spliced = FALSE).  Returns the table's size in bytes; copies at
-// most <cap> of them into <buf>.
-extern "C" int64_t bath_tophits_tabular_targets(const bath_tophits *th, const char *qname, const char *qacc, int M, int fs_pipe, int show_cigar,
-                                                int show_header, char *buf, int64_t cap) {
-  if (!th || !qname) return -1;
-  const std::vector<Hit> &H = th->unsrt;
+// Column widths of the tabular outputs: the maxima run over every hit of the list, reported or not (p7_tophits_GetMaxNameLength,
+// _GetMaxAccessionLength, _GetMaxPositionLength over th->unsrt; p7_tophits.c:504-567).
+struct TabWidths { int qnamew, tnamew, qaccw, taccw, posw; };
+TabWidths tab_widths(const std::vector<Hit> &H, const char *qname, const char *qacc) {
   size_t maxname = 0, maxacc = 0;
   int maxpos = 0;
   for (const Hit &h : H) {
@@ -200,11 +199,24 @@ extern "C" int64_t bath_tophits_tabular_targets(const bath_tophits *th, const ch
       maxpos = std::max(maxpos, snprintf(b, sizeof b, "%" PRId64, (int64_t)h.d.jali));
     }
   }
-  const int qnamew = (int)std::max<size_t>(20, std::strlen(qname));
-  const int tnamew = (int)std::max<size_t>(20, maxname);
-  const int qaccw = qacc ? (int)std::max<size_t>(10, std::strlen(qacc)) : 10;
-  const int taccw = (int)std::max<size_t>(10, maxacc);
-  const int posw = std::max(9, maxpos);
+  TabWidths w;
+  w.qnamew = (int)std::max<size_t>(20, std::strlen(qname));
+  w.tnamew = (int)std::max<size_t>(20, maxname);
+  w.qaccw = qacc ? (int)std::max<size_t>(10, std::strlen(qacc)) : 10;
+  w.taccw = (int)std::max<size_t>(10, maxacc);
+  w.posw = std::max(9, maxpos);
+  return w;
+}
+}  // namespace
+
+// p7_tophits_TabularTargets, p7_tophits.c:1603-1729 (pli->spliced = FALSE).  Returns the table's size in bytes; copies at
+// most <cap> of them into <buf>.
+extern "C" int64_t bath_tophits_tabular_targets(const bath_tophits *th, const char *qname, const char *qacc, int M, int fs_pipe, int show_cigar,
+                                                int show_header, char *buf, int64_t cap) {
+  if (!th || !qname) return -1;
+  const std::vector<Hit> &H = th->unsrt;
+  const TabWidths tw = tab_widths(H, qname, qacc);
+  const int qnamew = tw.qnamew, tnamew = tw.tnamew, qaccw = tw.qaccw, taccw = tw.taccw, posw = tw.posw;
   std::string out;
   if (show_header) {
     appendf(out, "#%7s %-*s %-*s %-*s %-*s %9s %9s %9s %9s %9s %9s", " hit ID", tnamew - 1, " target name", taccw, " accession", qnamew, " query name", qaccw,
@@ -230,6 +242,83 @@ extern "C" int64_t bath_tophits_tabular_targets(const bath_tophits *th, const ch
     if (fs_pipe) appendf(out, " %7d %6d", h.d.n_shifted_codons, h.d.n_stops);
     if (show_cigar) appendf(out, " %s\n", h.cigar.c_str());
     else appendf(out, " %s\n", h.desc.empty() ? "-" : h.desc.c_str());
+  }
+  if (buf && cap > 0) std::memcpy(buf, out.data(), (size_t)std::min<int64_t>(cap, (int64_t)out.size()));
+  return (int64_t)out.size();
+}
+
+// The loop of p7_tophits_TabularFrameshifts over one hit's trace (p7_tophits.c:1485-1558): the states from the first to the last
+// match state -- exactly those a bath_domain_trace holds -- with ali_pos starting at 1.  A match state on a quasi-codon of length
+// 1 / 2 gives a 'D' row of length 2 / 1, of length 4 / 5 an 'I' row of length 1 / 2, on a stop codon (bath::codon3_is_stop, the
+// renderer's ad->codon == 6) an 'S' row of length 0; ali_pos then moves on by the codon's length.  An insert state gives no row,
+// not even on a stop codon, and moves ali_pos on by 3; a delete state does neither.  A trace of the standard branch
+// (frameshift == 0) has no rows: the reference tests hit->frameshift.
+extern "C" int64_t bath_trace_frameshift_rows(const bath_domain_trace *tr, const int8_t *st, const int32_t *k, const int32_t *i, const int8_t *c,
+                                              const uint8_t *window_dsq, int32_t window_len, const bath_fs_profile *gm_fs5, int64_t iali, int64_t jali,
+                                              bath_fs_row *rows, int64_t cap) {
+  if (!tr || tr->N < 0 || (tr->N > 0 && (!st || !k || !i || !c))) return -1;
+  if (!tr->frameshift) return 0;
+  if (!window_dsq || !gm_fs5 || gm_fs5->codon_lengths != 5 || !gm_fs5->indel_pos) return -1;
+  auto nt = [&](int pos) -> int { return (pos >= 1 && pos <= window_len) ? (int)window_dsq[pos - 1] : 15; };
+  int64_t nrows = 0;
+  int ali_pos = 1;
+  for (int z = 0; z < tr->N; z++) {
+    if (st[z] == BATH_T_M) {
+      const int cl = c[z];
+      if (cl < 1 || cl > 5 || k[z] < 0 || k[z] > gm_fs5->M) return -1;
+      bath_fs_row row;
+      row.ali_start = ali_pos;
+      row.seq_start = iali < jali ? iali + ali_pos - 1 : iali - ali_pos + 1;
+      bool emit = true;
+      if (cl == 3) {
+        const int n[3] = {nt(i[z] - 2), nt(i[z] - 1), nt(i[z])};
+        emit = bath::codon3_is_stop(gm_fs5->indel_pos[bath::codon_row(gm_fs5, k[z], 3, n)]);
+        row.type = 'S'; row.length = 0;
+      } else {
+        row.type = cl < 3 ? 'D' : 'I';
+        row.length = cl < 3 ? 3 - cl : cl - 3;
+      }
+      if (emit) {
+        if (rows && nrows < cap) rows[nrows] = row;
+        nrows++;
+      }
+      ali_pos += cl;
+    } else if (st[z] == BATH_T_I) ali_pos += 3;
+    else if (st[z] != BATH_T_D) return -1;
+  }
+  return nrows;
+}
+
+// p7_tophits_TabularFrameshifts, p7_tophits.c:1428-1582.  rows[row_off[r] .. row_off[r + 1]) are the rows of the r-th REPORTED hit
+// in the list's current order (bath_trace_frameshift_rows of its trace); n_reported must be the number of reported hits.  The two
+// header lines are written when show_header is set and the list holds a hit of any kind (th->N > 0, :1465): a first query without
+// hits leaves the file without a header.  Returns the table's size in bytes; copies at most <cap> of them into <buf>.
+extern "C" int64_t bath_tophits_tabular_frameshifts(const bath_tophits *th, const char *qname, const char *qacc, const bath_fs_row *rows,
+                                                    const int64_t *row_off, int64_t n_reported, int show_header, char *buf, int64_t cap) {
+  if (!th || !qname || n_reported < 0 || (n_reported > 0 && !row_off)) return -1;
+  const std::vector<Hit> &H = th->unsrt;
+  int64_t have = 0;
+  for (const Hit &h : H) if (h.flags & IS_REPORTED) have++;
+  if (have != n_reported) return -1;
+  for (int64_t r = 0; r < n_reported; r++)
+    if (row_off[r] < 0 || row_off[r + 1] < row_off[r] || (row_off[r + 1] > row_off[r] && !rows)) return -1;
+  const TabWidths w = tab_widths(H, qname, qacc);
+  std::string out;
+  if (show_header && !H.empty()) {
+    appendf(out, "#%-*s %-*s %-*s %-*s %-9s %-*s %-*s  %5s %6s %-*s %9s\n", w.tnamew - 1, " target name", w.taccw, " accession", w.qnamew, " query name", w.qaccw,
+            " accession", " E-value", w.posw, " ali from", w.posw, " ali to", " I D S", " length", w.posw, " seq start", " ali start");
+    appendf(out, "#%*s %*s %*s %*s %9s %-*s %-*s  %5s  %6s  %-*s  %9s\n", w.tnamew - 1, "-------------------", w.taccw, "-----------", w.qnamew, "--------------------",
+            w.qaccw, "----------", "---------", w.posw, "---------", w.posw, "---------", "-----", "------", w.posw, "---------", "---------");
+  }
+  int64_t rep = 0;
+  for (size_t r = 0; r < H.size(); r++) {
+    const Hit &h = H[(size_t)(th->order.empty() ? (int)r : th->order[r])];
+    if (!(h.flags & IS_REPORTED)) continue;
+    for (int64_t x = row_off[rep]; x < row_off[rep + 1]; x++)
+      appendf(out, " %-*s %-*s %-*s %-*s %9.2g %-*" PRId64 " %-*" PRId64 "  %5c  %6d  %-*" PRId64 "  %9d\n", w.tnamew, h.name.c_str(), w.taccw,
+              h.acc.empty() ? "-" : h.acc.c_str(), w.qnamew, qname, w.qaccw, (qacc && qacc[0]) ? qacc : "-", std::exp(h.lnP), w.posw, (int64_t)h.d.iali, w.posw,
+              (int64_t)h.d.jali, rows[x].type, rows[x].length, w.posw, rows[x].seq_start, rows[x].ali_start);
+    rep++;
   }
   if (buf && cap > 0) std::memcpy(buf, out.data(), (size_t)std::min<int64_t>(cap, (int64_t)out.size()));
   return (int64_t)out.size();

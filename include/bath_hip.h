@@ -578,7 +578,7 @@ int bath_hip_std_envelopes_fill(bath_hip_ctx *ctx, const bath_hip_oprofile *om, 
  * Hit list of a search and its tabular output (P7_TOPHITS; host code).
  * What bathsearch does after its workers finish (bathsearch.c:868-921): p7_tophits_ComputeEvalues_BATH
  * (p7_tophits.c:789), SortBySeqidxAndAlipos (:379), RemoveDuplicates (:816), SortBySortkey (:345), Threshold (:914),
- * and p7_tophits_TabularTargets (:1603) for --tblout.
+ * p7_tophits_TabularTargets (:1603) for --tblout and p7_tophits_TabularFrameshifts (:1428) for --fstblout.
  * ------------------------------------------------------------------------------------------ */
 typedef struct bath_tophits bath_tophits;
 bath_tophits *bath_tophits_create(void);
@@ -617,6 +617,33 @@ void bath_tophits_set_inclusion(bath_tophits *th, double incE);   /* --incE, def
 #define BATH_HIT_INCLUDED  2
 int64_t bath_tophits_tabular_targets(const bath_tophits *th, const char *qname, const char *qacc, int M, int fs_pipe,
                                      int show_cigar, int show_header, char *buf, int64_t cap);
+
+/* --fstblout: where a coding region is broken (p7_tophits_TabularFrameshifts, p7_tophits.c:1428-1582).  Host code.
+ * bath_trace_frameshift_rows: the rows of one hit, from its trace as bath_hip_domain_traces / bath_hits_traces give it (st .. c
+ *   already offset to this trace), window_dsq / window_len as bath_alidisplay_print takes them, the 5-codon frameshift profile and
+ *   the hit's iali / jali on the sequence.  Walking the states with ali_pos = 1 at the first match state:
+ *     M on a quasi-codon of 1 / 2 nt   'D', length 2 / 1        M on 4 / 5 nt   'I', length 1 / 2
+ *     M on a stop codon                'S', length 0  (the renderer's rule for ad->codon == 6)
+ *   then ali_pos += the codon's length; I: no row, even on a stop codon, ali_pos += 3; D: no row, no advance.  So a hit can have
+ *   fewer 'S' rows than its n_stops, which counts the stops of insert states too.  ali_start is ali_pos before the advance,
+ *   seq_start = iali + ali_pos - 1 (iali < jali) or iali - ali_pos + 1.  A trace with frameshift == 0 has no rows.
+ *   Returns the number of rows and writes at most <cap> of them to <rows> (which may be NULL); < 0 on error.
+ * bath_tophits_tabular_frameshifts: the table of every hit with BATH_HIT_REPORTED in the list's current order; the rows of the
+ *   r-th of them are rows[row_off[r] .. row_off[r + 1]), n_reported = bath_tophits_reported(th).  Column widths as --tblout's, over
+ *   every hit of the list.  The two header lines are written when show_header is set AND the list holds a hit of any kind, as the
+ *   reference does: a first query without hits leaves the file without a header.  The E-value is --tblout's.
+ *   Returns the table's size in bytes and copies at most <cap> of them to <buf>; < 0 on error. */
+typedef struct {
+  char    type;                      /* 'D' nucleotides missing from the codon, 'I' extra nucleotides in it, 'S' a stop codon */
+  int32_t length;                    /* nucleotides missing / extra; 0 for 'S'                                                 */
+  int32_t ali_start;                 /* 1-based position in the alignment's own nucleotides                                    */
+  int64_t seq_start;                 /* the same position on the target sequence                                               */
+} bath_fs_row;
+int64_t bath_trace_frameshift_rows(const bath_domain_trace *tr, const int8_t *st, const int32_t *k, const int32_t *i, const int8_t *c,
+                                   const uint8_t *window_dsq, int32_t window_len, const bath_fs_profile *gm_fs5, int64_t iali, int64_t jali,
+                                   bath_fs_row *rows, int64_t cap);
+int64_t bath_tophits_tabular_frameshifts(const bath_tophits *th, const char *qname, const char *qacc, const bath_fs_row *rows,
+                                         const int64_t *row_off, int64_t n_reported, int show_header, char *buf, int64_t cap);
 
 /* ------------------------------------------------------------------------------------------
  * One search on several GPUs from a C host: the hit list as a byte stream and the division of the work.
