@@ -25,10 +25,14 @@ tensors (default nccl); each rank gets an equal share of the parent's CPUs as BA
 
 --workers N (1..8, default 1; an extension like --ensemble: no header line) searches the queries of the model file side by side on
 one GPU: N contexts on the device, one host thread each, all reading the one device copy of the targets (FastaTargets.seqs(ctx=)).
+There is one search loop: without the option, or with N = 1, it runs on one context and one worker thread (_workers_search), and
+a rank of --gpus runs its share of the items through the same pool (_rank_search); plan_pieces walks the targets for both,
+_search_items is the only loop over the blocks of windows, _render_query finishes and renders every query, Output writes the files.
 Within a piece of the targets the queries of a batch are drawn from a shared counter, longest first (dist.item_cost); every query
 is finished and rendered by the worker that searched its last piece, and an ordered writer (OrderedWriter) holds its text until
 every earlier query's text is written, so the output is the N = 1 output byte for byte but for the timing lines.  At most 2N
-queries' hits are alive at once, and the models and plans of at most two batches of 2N (feed_batches).  A failure at query k writes the queries before k, nothing from k on, one message, status 1.
+queries' hits are alive at once, and the models and plans of at most two batches of 2N (feed_batches).  A failure at query k
+writes the queries before k, nothing from k on, one message, status 1.
 With --gpus G every rank runs its items on N contexts of its device; BATH_HIP_HOST_THREADS is then the CPU share / (G x N).
 
 --arith strict|odds3|odds (default strict; an extension like --ensemble: no header line; needs --fs) chooses the arithmetic of the
@@ -38,6 +42,7 @@ parsers in fp32 odds ratios (Context.set_fs_odds); odds, the 5-codon Forward / B
 rank of --gpus runs the same arithmetic.  Search a file converted with the same bathconvert --arith.
 """
 import codecs
+import contextlib
 import os
 import socket
 import subprocess
@@ -347,61 +352,6 @@ def pipeline_overrides(opts):
     return over
 
 
-def search_query(ctx, hmm, targets, opts, block_nt, names_out):
-    """One query: (TopHits, summed PipelineStats, Pipeline, trace map, number of targets, target names, ...)."""
-    fs = "--fs" in opts
-    ct = opts.get("--ct", 1)
-    gm = ba.Profile(hmm)
-    om = ba.OProfile(ctx, gm)
-    over = pipeline_overrides(opts)
-    pipe = ba.Pipeline(ctx, om, fs_pipe=fs, ncbi_table=ct, **over)
-    if fs:
-        om3 = ba.FSOProfile(ctx, ba.FSProfile(hmm, 3, ncbi_table=ct))
-        gm5 = ba.FSProfile(hmm, 5, ncbi_table=ct)
-        om5 = ba.FSOProfile(ctx, gm5)
-    else:
-        gm5 = ba.FSProfile(hmm, 5, ncbi_table=ct)          # the renderer's translation of the codons
-    E = opts.get("-E", 10.0)
-    th = ba.TopHits()
-    total = ba.PipelineStats()
-    traces = {}
-    names, descs, lengths = [], [], []
-    nres = 0
-    block_length = opts.get("--block_length", dist.BLOCK_LENGTH)
-    for ft, lo, hi in targets.pieces():
-        recs = ft.records()[lo:hi]
-        for name, desc in ba.fasta_headers(targets.path, recs):
-            names.append(name); descs.append(desc)
-        lengths.extend(int(x) for x in recs["length"])
-        wins = ft.windows(hmm.max_length, block_length, lo, hi)
-        cut = block_cuts(wins["n"], block_nt)
-        for a, b in zip(cut[:-1], cut[1:]):
-            if a == b:
-                continue
-            w = wins[a:b]
-            blk = ft.seqs(w)
-            if fs:
-                stats, _, dm, _ = pipe.run_frameshift_domains(om3, om5, blk, E_report=E, nres_before=nres)
-            else:
-                stats, dm, _ = pipe.run_hits(blk, E_report=E, nres_before=nres)
-            trs = pipe.traces()
-            for f, _t in ba.PipelineStats._fields_:
-                setattr(total, f, getattr(total, f) + getattr(stats, f))
-            nres += stats.nres
-            for d, tr in zip(dm, trs):
-                win = w[d.window]
-                off = int(win["start0"])
-                d.ienv += off; d.jenv += off; d.iali += off; d.jali += off
-                d.window = int(win["target"])
-                h = Hit()
-                h.trace, h.target, h.start0, h.n = tr, int(win["target"]), off, int(win["n"])
-                traces.setdefault(_key(d), h)
-            th.add(dm, names, lengths, descs=descs) if dm else None
-            del blk
-    finish_tophits(th, opts, nres, hmm.max_length, E)
-    return dict(th=th, stats=total, pipe=pipe, traces=traces, nseqs=len(names), gm=gm, gm5=gm5, names=names, nres=nres)
-
-
 def finish_tophits(th, opts, nres, max_length, E):
     """The end of a query's search: -T / --incT thresholds, E-values over the whole search's residues (or -Z), duplicates, sorting."""
     if "--incT" in opts or "-T" in opts:
@@ -458,6 +408,47 @@ def tabular_query(hmm, th, opts, q, fs_rows):
     tbl = th.tblout(hmm.name, hmm.acc, hmm.M, fs_pipe="--fs" in opts, show_cigar="--cigar" in opts, show_header=(q == 0)) if "--tblout" in opts else ""
     fstbl = th.fstblout(hmm.name, hmm.acc, fs_rows, show_header=(q == 0)) if "--fstblout" in opts else ""
     return tbl, fstbl
+
+
+class Output:
+    """The files a search writes: the main output (-o, or the stream given), --tblout and --fstblout.  A context manager: the
+    banner is written on entry, and on every exit the files it opened are closed and a stream it was given is flushed."""
+
+    def __init__(self, argv, opts, hmmfile, seqfile, stdout):
+        self.header, self.tail_args, self.stdout = output_header(opts, hmmfile, seqfile), (hmmfile, seqfile, argv), stdout
+        self.ofp = open(opts["-o"], "w") if "-o" in opts else stdout
+        self.tblfp = open(opts["--tblout"], "w") if "--tblout" in opts else None
+        self.fstblfp = open(opts["--fstblout"], "w") if "--fstblout" in opts else None
+
+    def __enter__(self):
+        self.ofp.write(self.header)
+        self.ofp.flush()
+        return self
+
+    def write_query(self, q, text):
+        """Query <q>'s (main-output block, --tblout rows, --fstblout rows), as _render_query returns them."""
+        self.ofp.write(text[0])
+        if self.tblfp:
+            self.tblfp.write(text[1])
+        if self.fstblfp:
+            self.fstblfp.write(text[2])
+        self.ofp.flush()
+
+    def finish(self):
+        """The end of a search that succeeded: the tails of the tabular files and the [ok] line."""
+        for fp in (self.tblfp, self.fstblfp):
+            if fp:
+                fp.write(tabular_tail(*self.tail_args))
+        self.ofp.write("[ok]\n")
+
+    def __exit__(self, *exc):
+        if self.ofp is self.stdout:
+            self.ofp.flush()
+        else:
+            self.ofp.close()
+        for fp in (self.tblfp, self.fstblfp):
+            if fp:
+                fp.close()
 
 
 class _CodesSource:
@@ -521,13 +512,38 @@ def window_nres(windows, strand="both"):
 def search_plan(windows_by_query, M_by_query, world, strand="both"):
     """[Item] of one batch of queries, the same on every rank without communication: query q's windows cut into consecutive groups
     in proportion to its share of the work (dist.query_items_weighted, cost windows' nucleotides x (M + 150)), dealt to the ranks
-    longest first (dist.deal, dist.item_cost).  nres_before: the residues the single-GPU loop has counted before the item's first
-    window (the summed stats.nres of the query's earlier windows)."""
+    longest first (dist.deal, dist.item_cost).  nres_before: the residues counted before the item's first window when the query's
+    windows are searched in order (the summed stats.nres of its earlier windows)."""
     ns = [np.asarray(w)["n"].astype(np.int64) for w in windows_by_query]
     items = dist.query_items_weighted([len(n) for n in ns], [float(n.sum()) * (M + 150.0) for n, M in zip(ns, M_by_query)], world)
     owner = dist.deal([dist.item_cost(M_by_query[q], int(ns[q][lo:hi].sum())) for q, lo, hi in items], world)
     before = [np.concatenate([[0], np.cumsum(window_nres(w, strand))]) for w in windows_by_query]
     return [Item(q, lo, hi, o, int(before[q][lo])) for (q, lo, hi), o in zip(items, owner)]
+
+
+def plan_pieces(targets, hmms, opts, world, heads):
+    """The loop over the targets for one batch of models, the same for every coordinator: yields (piece, FastaTargets, the window
+    table of every model, search_plan's items for <world>) for every piece of targets.pieces(), an item's nres_before counted over
+    the whole search (the residues of the query's earlier pieces added).  heads: the (names, descriptions, lengths) lists that
+    receive the piece's targets before it is yielded; None for a caller that has them already.  A streamed piece is released when
+    the generator resumes."""
+    strand = opts.get("--strand", "both")
+    block_length = opts.get("--block_length", dist.BLOCK_LENGTH)
+    base = [0] * len(hmms)                               # residues of the earlier pieces, per query
+    for piece, (ft, lo, hi) in enumerate(targets.pieces()):
+        if heads is not None:
+            names, descs, lengths = heads
+            recs = ft.records()[lo:hi]
+            for name, desc in ba.fasta_headers(targets.path, recs):
+                names.append(name); descs.append(desc)
+            lengths.extend(int(x) for x in recs["length"])
+        wins = [ft.windows(h.max_length, block_length, lo, hi) for h in hmms]
+        plan = search_plan(wins, [h.M for h in hmms], world, strand)
+        for it in plan:
+            it.nres_before += base[it.query]
+        for k in range(len(hmms)):
+            base[k] += int(window_nres(wins[k], strand).sum())
+        yield piece, ft, wins, plan
 
 
 def host_threads_per_rank(n, environ=None, affinity=None):
@@ -712,7 +728,7 @@ def _search_items(ctx, hmm, ft, wins, items, opts, block_nt, cancelled=None):
             for f in STAT_FIELDS:
                 setattr(total, f, getattr(total, f) + getattr(stats, f))
             nres += stats.nres
-            for d in dm:                                 # window -> target coordinates, as search_query does
+            for d in dm:                                 # window -> target coordinates
                 win = w[d.window]
                 off = int(win["start0"])
                 d.ienv += off; d.jenv += off; d.iali += off; d.jali += off
@@ -727,8 +743,8 @@ def _search_items(ctx, hmm, ft, wins, items, opts, block_nt, cancelled=None):
 
 
 def _render_query(q, hmm, desc, parts, opts, names, descs, lengths, src, t0, c0):
-    """The owner's end of query <q>: its items' hits added in item order, counters summed, the query finished as search_query
-    finishes it, and its main-output block, --tblout rows and --fstblout rows rendered."""
+    """The owner's end of query <q>: its items' hits added in item order, counters summed, the query finished (finish_tophits), and
+    its (main-output block, --tblout rows, --fstblout rows) rendered, '' for a file not asked for."""
     fs = "--fs" in opts
     ct = opts.get("--ct", 1)
     th = ba.TopHits()
@@ -754,8 +770,9 @@ def _render_query(q, hmm, desc, parts, opts, names, descs, lengths, src, t0, c0)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------
-# --workers N: queries side by side on N contexts of one GPU, one host thread per context (WorkerPool), all of them reading the
-# one device copy of the targets; the finished queries' texts are written in query order (OrderedWriter).
+# The search in one process, --workers N or none (N = 1): queries side by side on N contexts of one GPU, one host thread per
+# context (WorkerPool), all of them reading the one device copy of the targets; the finished queries' texts are written in query
+# order (OrderedWriter).
 # ---------------------------------------------------------------------------------------------------------------------------
 
 class Cancelled(Exception):
@@ -951,17 +968,15 @@ class _Batch:
 
 
 def _workers_search(opts, hmmfile, seqfile, nq, write, device, chunk_bytes, block_nt, resident_bytes):
-    """The single-process search with --workers N > 1: _rank_search's loop for one rank (pieces of the targets outermost, a
-    query's items of a piece searched by _search_items, the query merged and rendered by _render_query), the queries of a batch of
-    2N spread over N contexts.  Resident targets are one piece: a query is rendered by the worker that searched it, and the next
-    batch is prepared and handed out while the last one's queries are still running (feed_batches: never more than that one).
-    Streamed targets: a piece is released when the generator
-    resumes, so every worker is done with it first; the batch is rendered after its last piece.  Raises what the search of the
-    lowest failing query raised (CtMismatch, ba.FastaFormatError, ...), the queries before it written."""
-    n = opts["--workers"]
+    """The single-process search, with --workers N or without (N = 1): the pieces of the targets outermost (plan_pieces with one
+    rank), a query's items of a piece searched by _search_items, the query merged and rendered by _render_query, the queries of a
+    batch of 2N spread over N contexts.  Resident targets are one piece: a query is rendered by the worker that searched it, and the
+    next batch is prepared and handed out while the last one's queries are still running (feed_batches: never more than that one).
+    Streamed targets: a piece is released when the generator resumes, so every worker is done with it first; the batch is rendered
+    after its last piece.  write(q, text) gets every query's text in query order.  Raises what the search of the lowest failing
+    query raised (CtMismatch, ba.FastaFormatError, ...), the queries before it written."""
+    n = opts.get("--workers", 1)
     ct = opts.get("--ct", 1)
-    strand = opts.get("--strand", "both")
-    block_length = opts.get("--block_length", dist.BLOCK_LENGTH)
     qdescs = model_descriptions(hmmfile)
     ctxs = [new_context(device, opts) for _ in range(n)]
     targets = Targets(ctxs[0], seqfile, chunk_bytes, resident_bytes)
@@ -1003,23 +1018,12 @@ def _workers_search(opts, hmmfile, seqfile, nq, write, device, chunk_bytes, bloc
         b = _Batch(b0, hmms)
         if shared is not None:
             b.names, b.descs, b.lengths = shared
-        base = [0] * len(hmms)                           # residues of the earlier pieces, per query
+        heads = (b.names, b.descs, b.lengths)
         try:
-            for piece, (ft, lo, hi) in enumerate(targets.pieces()):
-                recs = ft.records()[lo:hi]
-                if shared is None:
-                    for name, desc in ba.fasta_headers(targets.path, recs):
-                        b.names.append(name); b.descs.append(desc)
-                    b.lengths.extend(int(x) for x in recs["length"])
-                    if targets.resident:
-                        shared = (b.names, b.descs, b.lengths)
-                wins = [ft.windows(h.max_length, block_length, lo, hi) for h in hmms]
-                items = {k: [] for k in range(len(hmms))}
-                for it in search_plan(wins, [h.M for h in hmms], 1, strand):
-                    it.nres_before += base[it.query]
-                    items[it.query].append(it)
-                for k in range(len(hmms)):
-                    base[k] += int(window_nres(wins[k], strand).sum())
+            for piece, ft, wins, plan in plan_pieces(targets, hmms, opts, 1, heads if shared is None else None):
+                if targets.resident:
+                    shared = heads
+                items = {k: [it for it in plan if it.query == k] for k in range(len(hmms))}
                 order = longest_first(items, [h.M for h in hmms], wins)
                 pool.submit(Round([b0 + k for k in order], (b, piece, ft, wins, items, targets.resident), admit=(piece == 0)))
                 if not targets.resident:
@@ -1051,68 +1055,50 @@ def feed_batches(pool, nq, size, prepare):
 
 
 def _rank_search(argv, opts, hmmfile, seqfile, rank, world, device, dev, chunk_bytes, block_nt, resident_bytes, laps):
+    """One rank's share of the search: per batch of queries and piece of the targets (plan_pieces, the same on every rank) its own
+    items go through its pool of --workers contexts (one by default), a query per worker, longest first; the batch's results
+    travel to the queries' owners, which render them, and rank 0 writes the texts in query order."""
     nq = ba.HMM.count(hmmfile)
     qdescs = model_descriptions(hmmfile)
-    strand = opts.get("--strand", "both")
-    block_length = opts.get("--block_length", dist.BLOCK_LENGTH)
-    ofp = tblfp = fstblfp = pool = None
-    if rank == 0:
-        ofp = open(opts["-o"], "w") if "-o" in opts else sys.stdout
-        tblfp = open(opts["--tblout"], "w") if "--tblout" in opts else None
-        fstblfp = open(opts["--fstblout"], "w") if "--fstblout" in opts else None
-    try:
-        if ofp:
-            ofp.write(output_header(opts, hmmfile, seqfile))
-            ofp.flush()
+    with contextlib.ExitStack() as stack:                # leaves in reverse order: the pool's threads joined, then the files closed
+        out = stack.enter_context(Output(argv, opts, hmmfile, seqfile, sys.stdout)) if rank == 0 else None
         t = time.perf_counter()
         ctxs = [new_context(device, opts) for _ in range(opts.get("--workers", 1))]
-        ctx = ctxs[0]
         laps["context_s"] = time.perf_counter() - t
-        found = {}                                       # --workers: what the workers found in the piece at hand, per query of the batch
-        if len(ctxs) > 1:
-            def work(w, rnd, q):
-                k, h, ft, wk, mine = rnd.payload[q]
-                found[k] = _search_items(ctxs[w], h, ft, wk, mine, opts, block_nt, lambda: pool.cancelled(q))
-            pool = WorkerPool(len(ctxs), work, start=lambda w: ctxs[w].synchronize())     # binds thread w to this rank's device
-        targets = Targets(ctx, seqfile, chunk_bytes, resident_bytes)
+        found = {}                                       # what the workers found in the piece at hand, per query of the batch
+
+        def work(w, rnd, q):
+            k, h, ft, wk, mine = rnd.payload[q]
+            found[k] = _search_items(ctxs[w], h, ft, wk, mine, opts, block_nt, lambda: pool.cancelled(q))
+        pool = WorkerPool(len(ctxs), work, start=lambda w: ctxs[w].synchronize())     # binds thread w to this rank's device
+        stack.push(lambda et, exc, tb: pool.close(exc))
+        targets = Targets(ctxs[0], seqfile, chunk_bytes, resident_bytes)
         src = _CodesSource(targets)
         for b0 in range(0, nq, BATCH_QUERIES):
             qs = list(range(b0, min(nq, b0 + BATCH_QUERIES)))
             t0, c0 = time.time(), os.times()
             hmms = [ba.HMM(hmmfile, q) for q in qs]
             names, descs, lengths = [], [], []
-            base = [0] * len(qs)                         # residues of the earlier pieces, per query
             n_items = [0] * len(qs)
             by_dest = {}
             tb = time.perf_counter()
-            for piece, (ft, lo, hi) in enumerate(targets.pieces()):
-                laps["ingest_s"] += time.perf_counter() - tb
-                recs = ft.records()[lo:hi]
-                for name, desc in ba.fasta_headers(targets.path, recs):
-                    names.append(name); descs.append(desc)
-                lengths.extend(int(x) for x in recs["length"])
-                wins = [ft.windows(h.max_length, block_length, lo, hi) for h in hmms]
-                plan = search_plan(wins, [h.M for h in hmms], world, strand)
+            for piece, ft, wins, plan in plan_pieces(targets, hmms, opts, world, (names, descs, lengths)):
                 ts = time.perf_counter()
+                laps["ingest_s"] += ts - tb              # the piece parsed, its windows cut and planned
                 mine_by = {}
-                for k, h in enumerate(hmms):
-                    n_items[k] += sum(1 for it in plan if it.query == k)
-                    mine_by[k] = [it for it in plan if it.query == k and it.owner == rank]
-                    for it in mine_by[k]:
-                        it.nres_before += base[k]
-                    base[k] += int(window_nres(wins[k], strand).sum())
-                if len(ctxs) > 1:                        # this rank's items of the piece side by side, a query per worker, longest first
-                    found.clear()
-                    order = longest_first({k: m for k, m in mine_by.items() if m}, [h.M for h in hmms], wins)
-                    pool.submit(Round([qs[k] for k in order], {qs[k]: (k, hmms[k], ft, wins[k], mine_by[k]) for k in order}))
-                    pool.wait()                          # every worker is done with the piece before it is released
-                for k, h in enumerate(hmms):
-                    mine = mine_by[k]
-                    for it, stats, geometry, stream in ((found[k] if len(ctxs) > 1 else _search_items(ctx, h, ft, wins[k], mine, opts, block_nt))
-                                                        if mine else []):
+                for it in plan:
+                    n_items[it.query] += 1
+                    if it.owner == rank:
+                        mine_by.setdefault(it.query, []).append(it)
+                found.clear()                            # this rank's items of the piece, a query per worker, longest first
+                order = longest_first(mine_by, [h.M for h in hmms], wins)
+                pool.submit(Round([qs[k] for k in order], {qs[k]: (k, hmms[k], ft, wins[k], mine_by[k]) for k in order}))
+                pool.wait()                              # every worker is done with the piece before it is released
+                for k in sorted(found):
+                    for it, stats, geometry, stream in found[k]:
                         by_dest.setdefault(dist.query_owner(qs[k], world), bytearray()).extend(
                             _pack_item(k, piece, it.lo, stats, geometry, stream))
-                laps["items"] += sum(1 for it in plan if it.owner == rank)
+                laps["items"] += sum(len(m) for m in mine_by.values())
                 laps["search_s"] += time.perf_counter() - ts
                 tb = time.perf_counter()
             tm = time.perf_counter()
@@ -1123,7 +1109,6 @@ def _rank_search(argv, opts, hmmfile, seqfile, rank, world, device, dev, chunk_b
                     parts.setdefault(k, []).append(((piece, lo), stats, geometry, stream))
             for k, q in enumerate(qs):
                 owner = dist.query_owner(q, world)
-                text = None
                 if owner == rank:
                     if len(parts.get(k, ())) != n_items[k]:
                         raise RuntimeError("query %d: %d of its %d items arrived" % (q, len(parts.get(k, ())), n_items[k]))
@@ -1137,28 +1122,10 @@ def _rank_search(argv, opts, hmmfile, seqfile, rank, world, device, dev, chunk_b
                     n0, n1 = (int(x) for x in head.split())
                     text = (rest[:n0], rest[n0:n0 + n1], rest[n0 + n1:])
                 if rank == 0:
-                    ofp.write(text[0])
-                    if tblfp:
-                        tblfp.write(text[1])
-                    if fstblfp:
-                        fstblfp.write(text[2])
-                    ofp.flush()
+                    out.write_query(q, text)
             laps["merge_write_s"] += time.perf_counter() - tm
         if rank == 0:
-            for fp in (tblfp, fstblfp):
-                if fp:
-                    fp.write(tabular_tail(hmmfile, seqfile, argv))
-            ofp.write("[ok]\n")
-    finally:
-        if pool is not None:
-            pool.close(sys.exc_info()[1])
-        if ofp is not None and ofp is not sys.stdout:
-            ofp.close()
-        elif ofp is not None:
-            ofp.flush()
-        for fp in (tblfp, fstblfp):
-            if fp:
-                fp.close()
+            out.finish()
     return 0
 
 
@@ -1248,50 +1215,14 @@ def run(argv, stdout=None, chunk_bytes=64 << 20, block_nt=256_000_000, resident_
                 sys.stderr.write(CT_MISMATCH % (ct, hmmfile, hmm.ct, ct))
                 return 1
         return launch_ranks(opts["--gpus"], argv, stdout, dict(chunk_bytes=chunk_bytes, block_nt=block_nt, resident_bytes=resident_bytes))
-    descs = model_descriptions(hmmfile)
-    ofp = open(opts["-o"], "w") if "-o" in opts else stdout
-    tblfp = open(opts["--tblout"], "w") if "--tblout" in opts else None
-    fstblfp = open(opts["--fstblout"], "w") if "--fstblout" in opts else None
     workers = opts.get("--workers", 1)
     threads = host_threads_per_worker(workers) if workers > 1 else None
     try:
-        ofp.write(output_header(opts, hmmfile, seqfile))
-        if workers > 1:
-            def write(q, text):                      # (main output, --tblout rows[, --fstblout rows]) of query q
-                ofp.write(text[0])
-                if tblfp:
-                    tblfp.write(text[1])
-                if fstblfp and len(text) > 2:
-                    fstblfp.write(text[2])
-                ofp.flush()
+        with Output(argv, opts, hmmfile, seqfile, stdout) as out:
             if threads is not None:                  # the library reads it at every ensemble: each worker context's share
                 os.environ["BATH_HIP_HOST_THREADS"] = str(threads)
-            _workers_search(opts, hmmfile, seqfile, nq, write, device, chunk_bytes, block_nt, resident_bytes)
-        else:
-            ctx = new_context(device, opts)
-            targets = Targets(ctx, seqfile, chunk_bytes, resident_bytes)
-            src = _CodesSource(targets)
-            for q in range(nq):
-                hmm = ba.HMM(hmmfile, q)
-                if hmm.ct != ct:
-                    sys.stderr.write(CT_MISMATCH % (ct, hmmfile, hmm.ct, ct))
-                    return 1
-                t0, c0 = time.time(), os.times()
-                r = search_query(ctx, hmm, targets, opts, block_nt, None)
-                c1 = os.times()
-                fs_rows = [] if fstblfp else None
-                ofp.write(main_output_query(hmm, descs[q] if q < len(descs) else None, r, opts, src, time.time() - t0,
-                                            (c1.user - c0.user, c1.system - c0.system), fs_rows))
-                tbl, fstbl = tabular_query(hmm, r["th"], opts, q, fs_rows)
-                if tblfp:
-                    tblfp.write(tbl)
-                if fstblfp:
-                    fstblfp.write(fstbl)
-                ofp.flush()
-        for fp in (tblfp, fstblfp):
-            if fp:
-                fp.write(tabular_tail(hmmfile, seqfile, argv))
-        ofp.write("[ok]\n")
+            _workers_search(opts, hmmfile, seqfile, nq, out.write_query, device, chunk_bytes, block_nt, resident_bytes)
+            out.finish()
     except ba.FastaFormatError as e:
         sys.stderr.write("Error: %s: %s\n" % (seqfile, e))
         return 1
@@ -1301,11 +1232,6 @@ def run(argv, stdout=None, chunk_bytes=64 << 20, block_nt=256_000_000, resident_
     finally:
         if threads is not None:
             os.environ.pop("BATH_HIP_HOST_THREADS", None)
-        if ofp is not stdout:
-            ofp.close()
-        for fp in (tblfp, fstblfp):
-            if fp:
-                fp.close()
     return 0
 
 

@@ -114,7 +114,7 @@ def synthetic_windows(rng, n_records, max_length, block_length):
 
 
 def single_gpu_nres_before(wins, block_nt, strand_factor=2):
-    """The loop of search_query: nres before every window, accumulated block by block (stats.nres of each block)."""
+    """The block loop of _search_items: nres before every window, accumulated block by block (stats.nres of each block)."""
     before, acc = {}, 0
     cut = bs.block_cuts(wins["n"], block_nt)
     for a, b in zip(cut[:-1], cut[1:]):

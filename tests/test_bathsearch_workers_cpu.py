@@ -183,21 +183,27 @@ def test_a_failure_of_the_coordinator_stops_the_jobs_not_yet_started():
     assert ran == [0, 1] and pool.cancelled(3) and not pool.cancelled(2) and not pool.cancelled(1)
 
 
+@pytest.mark.parametrize("option", [["--workers", "2"], ["--workers", "1"], []])
 @pytest.mark.parametrize("exc,text", [(bs.CtMismatch(bs.CT_MISMATCH % (1, "q.bhmm", 4, 1)), "codon translation tabel ID 1 does not match")])
-def test_run_reports_a_workers_failure_once_with_status_1(exc, text, tmp_path, capsys, monkeypatch):
+def test_run_reports_a_workers_failure_once_with_status_1(exc, text, option, tmp_path, capsys, monkeypatch):
+    """With --workers 2, --workers 1 and without the option: one search, whose failure after the first query is reported once."""
+    during = []
+
     def search(opts, hmmfile, seqfile, nq, write, *a):
+        during.append(os.environ.get("BATH_HIP_HOST_THREADS"))
         write(0, ("Query:       first\n//\n", ""))
         raise exc
 
     monkeypatch.setattr(bs, "_workers_search", search)
     monkeypatch.delenv("BATH_HIP_HOST_THREADS", raising=False)
     out = tmp_path / "o.txt"
-    assert bs.run(["--workers", "2", "-o", str(out), HMM, FA]) == 1
+    assert bs.run(option + ["-o", str(out), HMM, FA]) == 1
     err = capsys.readouterr().err
     assert err.count("Error:") == 1 and text in err
     got = out.read_text()
     assert "Query:       first" in got and "[ok]" not in got
     assert "BATH_HIP_HOST_THREADS" not in os.environ           # the workers' share does not outlive the search
+    assert len(during) == 1 and (during[0] is None) == (option != ["--workers", "2"])      # ... and one worker is given none
 
 
 def test_host_threads_split_among_worker_contexts(monkeypatch):

@@ -1,6 +1,6 @@
 """GPU tier of `bathsearch --workers N`: the queries of a model file searched side by side on N contexts of one GPU write the
 N = 1 search's main output and --tblout byte for byte (but for the timing lines and the tail's option, directory and date lines),
-resident or streamed targets, one rank or two; a failing query ends the search as the search query after query ends; and the
+resident or streamed targets, one rank or two; a failing query ends the search the same way with one worker and with two; and the
 library rule underneath: one FastaTargets, its windows gathered for other contexts from several threads at once.  Every search is
 a fresh child process under a time limit; only recorded fixtures are searched."""
 import os
@@ -165,17 +165,17 @@ def test_a_model_of_another_codon_table_ends_the_search_there(tmp_path):
         p = cli(d, extra + argv, expect=1)
         ends.append((p.stderr, normalise((d / "out.txt").read_text()), normalise((d / "hits.tbl").read_text())))
     names = [ba.HMM(str(d / "q.bhmm"), q).name for q in range(3)]
-    err, out, tbl = ends[0]
-    assert err.count("Error:") == 1 and "codon translation tabel ID 1 does not match" in err, err
-    assert "--ct 4" in err and "Traceback" not in err
-    assert [ln.split()[1] for ln in out if ln.startswith("Query:")] == names[:1] and out.count("//") == 1 and "[ok]" not in out
-    assert "[ok]" not in tbl
-    assert ends[0] == ends[1]                       # the search query after query ends the same way
+    for err, out, tbl in ends:
+        assert err.count("Error:") == 1 and "codon translation tabel ID 1 does not match" in err, err
+        assert "--ct 4" in err and "Traceback" not in err
+        assert [ln.split()[1] for ln in out if ln.startswith("Query:")] == names[:1] and out.count("//") == 1 and "[ok]" not in out
+        assert "[ok]" not in tbl
+    assert ends[0] == ends[1]                       # one worker ends the same way
 
 
 def test_streamed_targets_a_failing_query_in_the_middle_of_a_batch(tmp_path):
     """Streamed targets in several pieces, three models in one batch, the second with another codon table: the first query still
-    gets every piece and is written, as the search query after query writes it; nothing of the second and third."""
+    gets every piece and is written, with two workers and with one; nothing of the second and third."""
     models = [open(os.path.join(ol.GOLDEN, f)).read() for f in ("PTH2.bhmm", "2OG-FeII_Oxy_3.bhmm", "AMP_N.bhmm")]
     assert "CODON TABLE  1\n" in models[1]
     models[1] = models[1].replace("CODON TABLE  1\n", "CODON TABLE  4\n")
@@ -187,9 +187,9 @@ def test_streamed_targets_a_failing_query_in_the_middle_of_a_batch(tmp_path):
         (d / "q.bhmm").write_text("".join(models))
         p = cli(d, extra + argv, expect=1, run_kw=kw)
         ends.append((p.stderr, normalise((d / "out.txt").read_text()), normalise((d / "hits.tbl").read_text())))
-    err, out, tbl = ends[0]
-    assert err.count("Error:") == 1 and "codon translation tabel ID 1 does not match" in err and "Traceback" not in err, err
-    assert [ln.split()[1] for ln in out if ln.startswith("Query:")] == ["PTH2"] and any(ln.startswith(">> ") for ln in out)
+    for err, out, tbl in ends:
+        assert err.count("Error:") == 1 and "codon translation tabel ID 1 does not match" in err and "Traceback" not in err, err
+        assert [ln.split()[1] for ln in out if ln.startswith("Query:")] == ["PTH2"] and any(ln.startswith(">> ") for ln in out)
     assert ends[0] == ends[1]
 
 
