@@ -43,6 +43,8 @@ inline hipError_t allow_max_lds(const void *fn) {
 constexpr int kKp = BATH_KP_AMINO;       // 29 amino symbols
 constexpr int kRowReset = 29;            // extra "row" of the SSV cost table: every cost +127 (resets every diagonal)
 constexpr int kSsvRows = 30;
+constexpr size_t kSsvLdsMax = 160 * 1024;   // the LDS a workgroup can have: the SSV kernels keep the model's whole cost table there
+constexpr int kSsvMaxNodes = 2560;         // ... which holds 8 lanes x 160 registers x 2 nodes (BATH_SSV_SHAPES ends there)
 constexpr int kStop = 27;                // '*'
 constexpr int kXaa = 26;                 // 'X'
 constexpr int kOrfBins = 2048;           // ORF length histogram of the work-list sort (longer ORFs share the last bin)

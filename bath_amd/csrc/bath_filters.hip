@@ -745,7 +745,17 @@ static int length_order(bath_hip_ctx *ctx, const bath_hip_seqs *sq, DevBuf &buf)
   return BATH_OK;
 }
 
+// the one statement of the SSV kernels' model limit, for the standalone filters and the cascade: checked before any launch
+int ssv_table_fits(bath_hip_ctx *ctx, const bath_hip_oprofile *om) {
+  static_assert((size_t)kSsvRows * 16 * ((160 * 8 / 4 + 1) | 1) <= kSsvLdsMax && (size_t)kSsvRows * 16 * ((176 * 8 / 4 + 1) | 1) > kSsvLdsMax && kSsvMaxNodes == 2 * 160 * 8,
+                "kSsvMaxNodes is the largest model whose table fits");
+  if ((size_t)kSsvRows * om->ssv_row_bytes <= kSsvLdsMax) return BATH_OK;
+  ctx->set_error("model too long for the LDS-resident SSV cost table: the SSV filters take up to " + std::to_string(kSsvMaxNodes) + " nodes");
+  return BATH_EINVAL;
+}
+
 int launch_ssv_lane(bath_hip_ctx *ctx, const bath_hip_oprofile *om, SeqView v, const int32_t *d_order, int16_t *d_v) {
+  if (const int fit = ssv_table_fits(ctx, om)) return fit;
   if (v.n == 0) return BATH_OK;
   const int G = om->G;
   const size_t shmem = (size_t)kSsvRows * om->ssv_row_bytes;

@@ -31,6 +31,8 @@ struct VitWindowArgs {            // p7_ViterbiFilter_BATH's extra inputs/output
   int32_t *d_kminmax;             // [2n] min start node / max end node over the target's windows
 };
 
+// BATH_OK, or BATH_EINVAL with the context's error set: the model's SSV cost table exceeds a workgroup's LDS (beyond kSsvMaxNodes nodes)
+int ssv_table_fits(bath_hip_ctx *ctx, const bath_hip_oprofile *om);
 int launch_ssv_lane(bath_hip_ctx *ctx, const bath_hip_oprofile *om, SeqView v, const int32_t *d_order, int16_t *d_v);
 int launch_ssv_classify(bath_hip_ctx *ctx, const bath_hip_oprofile *om, int64_t n, const int32_t *d_len, const int16_t *d_v, float *d_sc, int32_t *d_status);
 int launch_msv_wave(bath_hip_ctx *ctx, const bath_hip_oprofile *om, SeqView v, const int32_t *d_todo, int64_t ntodo, float *d_sc, int32_t *d_status, const int *ntodo_dev, bool lane_ok = true);

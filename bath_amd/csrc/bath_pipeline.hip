@@ -765,6 +765,10 @@ static int run_filters(bath_hip_ctx *ctx, const bath_hip_oprofile *om, const bat
   if (max_orfs >= (int64_t)INT32_MAX) { ctx->set_error("DNA block too large for one pipeline call (ORF list indices are 32-bit): split it"); return BATH_EINVAL; }
   int64_t cap = std::max<int64_t>(4096, (int64_t)((double)max_orfs * std::min(1.0, prm->F1 * 4.0 + 0.01)));
   cap = std::min<int64_t>(cap, std::max<int64_t>(max_orfs, 4096));
+  {                                                         // tests: start with a candidate list that is too small (BATH_HIP_TEST_CANDCAP)
+    static const int forced = [] { const char *e = std::getenv("BATH_HIP_TEST_CANDCAP"); return e ? std::atoi(e) : 0; }();
+    if (forced > 0) cap = forced;                           // the first attempt only: a pass that overflows doubles it
+  }
 
   // ---- translation / ORF work-list buffers (bath_orfs.hip)
   if ((st = orf_tiles_ensure(ctx, dna)) != BATH_OK) return st;
@@ -779,7 +783,7 @@ static int run_filters(bath_hip_ctx *ctx, const bath_hip_oprofile *om, const bat
 
   const int NRk = om->NR;
   const size_t ssv_shmem = (size_t)kSsvRows * om->ssv_row_bytes;
-  if (ssv_shmem > 160 * 1024) { ctx->set_error("model too long for the LDS-resident SSV cost table"); return BATH_EINVAL; }
+  if ((st = ssv_table_fits(ctx, om)) != BATH_OK) return st;
   const int dec_blocks = ctx->prop.multiProcessorCount * 4;
 
   std::vector<hipEvent_t> &ev = ctx->ev_pool;

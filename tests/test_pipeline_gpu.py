@@ -247,6 +247,46 @@ print(json.dumps({"fw": sorted((w.window, w.strand, w.n, w.length, w.orf_cnt, w.
     assert outs[0] == outs[1] and len(outs[0]["fw"]) >= 30
 
 
+def test_candidate_buffer_overflow_is_retried():
+    """The candidate list has the same contract as the window buffer: ssv_orf_kernel counts every ORF it would hand on, drops those
+    beyond the list and raises the overflow flag; the cascade then repeats the whole pass, translation and sort included, with a
+    list that holds them all.  BATH_HIP_TEST_CANDCAP (read once per process, applied to a call's first attempt) starts with a list
+    of 3 and of 300 candidates: stats and records must be those of an ordinary run, at the default F1 and at F1 = 1.0, where
+    every ORF is a candidate."""
+    import subprocess, sys, os, json
+    code = r'''
+import sys, json, numpy as np
+sys.path.insert(0, %r); sys.path.insert(0, %r)
+import bath_amd as ba, common, oracle_lib as ol
+path = ol.GOLDEN + "/Caudal_act.bhmm"
+model = ol.Model(path)
+rng = np.random.default_rng(5)
+wins = [common.revtranslate(rng, aa, model.basic) for aa in common.emit_from_model(rng, model, 60, flank=10, sharpen=2.0)]
+ctx = ba.Context(0)
+hmm = ba.HMM(path)
+om = ba.OProfile(ctx, ba.Profile(hmm))
+out = {}
+for name, over in (("default", {}), ("every_orf", {"F1": 1.0, "min_orf_len": 5})):
+    stats, res = ba.Pipeline(ctx, om, fs_pipe=False, **over).run(ba.SeqBlock(ctx, wins))
+    bits = lambda f: [int(x) for x in np.asarray(res[f], np.float32).view(np.uint32)]
+    out[name] = {"stats": [int(getattr(stats, f)) for f, _ in ba.PipelineStats._fields_],
+                 "records": sorted(zip(*([[int(x) for x in res[f]] for f in ("window", "strand", "frame", "start", "end", "n", "stage", "msv_status", "vit_status")]
+                                         + [bits(f) for f in ("usc", "nullsc", "filtersc", "vfsc", "fwdsc")])))}
+print(json.dumps(out))
+''' % (os.path.dirname(os.path.dirname(os.path.abspath(__file__))), os.path.dirname(os.path.abspath(__file__)))
+    outs = []
+    for cap in (None, "3", "300"):
+        env = dict(os.environ)
+        env.pop("BATH_HIP_TEST_CANDCAP", None)
+        if cap:
+            env["BATH_HIP_TEST_CANDCAP"] = cap
+        p = subprocess.run([sys.executable, "-c", code], env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=600)
+        assert p.returncode == 0, p.stderr[-2000:]
+        outs.append(json.loads(p.stdout.strip().splitlines()[-1]))
+    assert outs[0] == outs[1] == outs[2]
+    assert len(outs[0]["default"]["records"]) >= 30 and len(outs[0]["every_orf"]["records"]) > 300
+
+
 def test_streamed_packed_blocks_equal_resident_blocks(gpu_ctx):
     """A block uploaded in 2 bits per nucleotide (+ exception list for degenerate codes), expanded on the device, must give the
     cascade exactly what the byte-per-nucleotide block gives: ragged lengths (not multiples of 4 or 16), degenerate nucleotides,

@@ -228,3 +228,86 @@ def test_std_envelope_tests_reach_every_instantiation():
     assert 192 in t.STD_M and 193 in t.STD_M
     assert 1025 in t.PIPELINE_M and const_nodes("kCascadeMaxNodes", "BATH_WAVE_COLUMNS") in t.PIPELINE_M
     assert all(m <= 1024 and v == ["0"] for m, v in t.PIPELINE_M.items() if v) and {columns(m, fill) for m, v in t.PIPELINE_M.items() if v} == {4, 12}
+
+
+def ssv_shapes():
+    """The (NR, G) entries of BATH_SSV_SHAPES, from its one definition: X(NR, G), a list of pairs with a parser of its own."""
+    defs = [f for f, text in csrc_files().items() for _ in re.finditer(r"#\s*define\s+BATH_SSV_SHAPES\b", text)]
+    assert defs == ["bath_tilings.hpp"], defs
+    m = re.search(r"#define BATH_SSV_SHAPES\(X\)((?:[^\n]*\\\n)*[^\n]*)\n", src("bath_tilings.hpp"))
+    assert m
+    out = [(int(a), int(b)) for a, b in re.findall(r"X\((\d+), (\d+)\)", m.group(1))]
+    assert out and len(out) == len(set(out)) == m.group(1).count("X(")
+    return out
+
+
+def test_ssv_tests_reach_every_shape():
+    """ssv_lane_kernel<NR, G> (bath_filters.hip) and ssv_orf_kernel<NR, G> (bath_pipeline.hip): both launchers expand BATH_SSV_SHAPES and
+    nothing else instantiates the kernels; the rule of bath_profile.hip, default or under BATH_HIP_SSV_WIDE=1, selects listed shapes
+    only and every listed shape for some model; every shape's cost table fits a workgroup's LDS; test_ssv_shapes_gpu runs every
+    shape at the smallest and the largest model that selects it.  The cascade stops at 2048 nodes, so (144, 8) and (160, 8), 2049 to
+    2560 nodes, are reached by the standalone filters alone: test_ssv_standalone_every_shape runs them."""
+    import test_ssv_shapes_gpu as t
+    shapes = ssv_shapes()
+    table_bytes = lambda nr, g: 30 * 16 * ((nr * g // 4 + 1) | 1)
+    too_big = [s for s in shapes if table_bytes(*s) > 160 * 1024]
+    assert not too_big, "SSV shapes whose cost table exceeds a workgroup's 160 KB of LDS (they can never launch): %s" % too_big
+    assert t.SSV_SHAPES == shapes
+    files = csrc_files()
+    filt, pipe, prof = files["bath_filters.hip"], files["bath_pipeline.hip"], files["bath_profile.hip"]
+    assert "BATH_SSV_SHAPES(BATH_SSV_CASE)" in body(filt, "int launch_ssv_lane(") and "BATH_SSV_SHAPES(BATH_ORF_CASE)" in pipe
+    for f, text in files.items():
+        assert len(re.findall(r"\bBATH_SSV_SHAPES\(", text)) == {"bath_tilings.hpp": 1, "bath_filters.hip": 1, "bath_pipeline.hip": 1}.get(f, 0), f
+        for kernel, home in (("ssv_lane_kernel", "bath_filters.hip"), ("ssv_orf_kernel", "bath_pipeline.hip")):
+            inst = re.findall(kernel + r"<([^>]*)>", text)
+            assert inst == (["N, GG"] * 2 if f == home else []), (f, kernel, inst)
+    # the rule, tied to the source's text
+    for line in ('static const bool wide = [] { const char *e = std::getenv("BATH_HIP_SSV_WIDE"); return e && e[0] == \'1\'; }();',
+                 'static const int g2max = [] { const char *e = std::getenv("BATH_HIP_SSV_G2_MAX"); return e ? std::atoi(e) : 304; }();',
+                 "int G = (!wide && M > 152 && M <= g2max) ? 2 : 1;",
+                 "while (G < 8 && M > 416 * G) G *= 2;",
+                 'if (M > 416 * G) { ctx->set_error("model longer than 3328 nodes"); delete om; return BATH_EINVAL; }',
+                 "int NR = ((M + G - 1) / G + 1) / 2;",
+                 "if (G == 1 && NR <= 112) NR = (NR + 3) / 4 * 4;",
+                 "else if (G == 2 && NR <= 76) NR = NR <= 40 ? 40 : (NR <= 72 ? (NR + 7) / 8 * 8 : 76);",
+                 "else NR = std::max((NR + 15) / 16 * 16, G > 1 ? 112 : 16);",
+                 "NR = std::max(NR, 16);",
+                 "om->ssv_row_bytes = 16 * ((NR * G / 4 + 1) | 1);"):
+        assert line in prof, line
+    assert t.OPROFILE_MAX_NODES == 3328 == 416 * 8
+    # the table's limit, stated once and used by both entry points before they launch
+    common_hpp = files["bath_common.hpp"]
+    assert "constexpr int kSsvRows = 30;" in common_hpp and "constexpr size_t kSsvLdsMax = 160 * 1024;" in common_hpp
+    assert "constexpr int kSsvMaxNodes = %d;" % t.SSV_MAX_NODES in common_hpp
+    fits = body(filt, "int ssv_table_fits(")
+    assert "if ((size_t)kSsvRows * om->ssv_row_bytes <= kSsvLdsMax) return BATH_OK;" in fits and '"%s' % t.LDS_MESSAGE in fits
+    assert "ssv_table_fits(ctx, om)" in body(filt, "int launch_ssv_lane(").split("hipLaunchKernelGGL")[0]
+    assert pipe.index("ssv_table_fits(ctx, om)") < pipe.index("BATH_SSV_SHAPES(BATH_ORF_CASE)") and sum(text.count(t.LDS_MESSAGE) for text in files.values()) == 1
+    # what the rule selects
+    by_shape = {}
+    for wide in (False, True):
+        for m in range(1, t.OPROFILE_MAX_NODES + 1):
+            s = t.ssv_shape(m, wide)
+            if table_bytes(*s) <= 160 * 1024:
+                by_shape.setdefault((s, "wide" if wide else None), []).append(m)
+            else:
+                assert m > t.SSV_MAX_NODES and s not in shapes       # refused by ssv_table_fits; ssv_bath_kernel<52> alone takes them
+    assert t.ssv_shape(t.SSV_MAX_NODES) in shapes and max(m for (s, w), ms in by_shape.items() for m in ms) == t.SSV_MAX_NODES
+    selected = {s for s, _ in by_shape}
+    assert not selected - set(shapes), "the rule selects shapes that are not instantiated: %s" % sorted(selected - set(shapes))
+    assert not set(shapes) - selected, "instantiated shapes that no model selects: %s" % sorted(set(shapes) - selected)
+    for s in shapes:
+        assert s in t.SSV_M, "SSV shape %s has no entry in test_ssv_shapes_gpu.SSV_M: no test runs it" % (s,)
+        lo, hi, switch = t.SSV_M[s]
+        assert switch == (None if (s, None) in by_shape else "wide"), s      # the default rule where it reaches the shape
+        ms = by_shape[(s, switch)]
+        assert (lo, hi) == (ms[0], ms[-1]), "SSV shape %s: the tests' models %d, %d are not its smallest and largest, %d, %d" % (s, lo, hi, ms[0], ms[-1])
+    assert set(t.SSV_M) == set(shapes)
+    # every entry is a test case, and the cascade leg leaves out only what lies beyond its limit
+    assert {(m, nr, g) for (nr, g), (lo, hi, sw) in t.SSV_M.items() for m in (lo, hi)} == set(t.DEFAULT_CASES) | set(t.WIDE_CASES)
+    assert {c[1:] for c in t.DEFAULT_CASES} - {c[1:] for c in t.CASCADE_CASES} == {(144, 8), (160, 8)} and t.CASCADE_MAX_NODES == const_nodes("kCascadeMaxNodes", "BATH_WAVE_COLUMNS")
+    assert len(t.WIDE_CASES) == 22 and all(t.ssv_shape(m, True) == (nr, g) and t.ssv_shape(m) != (nr, g) for m, nr, g in t.WIDE_CASES)
+    assert sorted(t.ssv_shape(m)[1] for m in t.CHUNK_M) == [1, 2, 4, 8] and max(t.CHUNK_M) <= t.CASCADE_MAX_NODES
+    # seams: node 1, node M, every multiple of NR below M, odd multiples between the halves, even ones between lanes
+    assert t.ssv_seams(1024, 128, 4) == [(1, "first")] + [(128 * i, "half" if i % 2 else "lane") for i in range(1, 8)] + [(1024, "last")]
+    assert t.ssv_seams(1, 16, 1) == [(1, "first")] and t.ssv_seams(16, 16, 1) == [(1, "first"), (16, "last")] and t.ssv_seams(17, 16, 1)[1] == (16, "half")
