@@ -354,6 +354,22 @@ ABI = {
     "bath_hmm_max_length": (C.c_int, [C.POINTER(_Hmm), C.c_double]),
     "bath_hip_calibrate_fs": (C.c_int, [_vp, C.POINTER(_Hmm), C.c_int, C.POINTER(C.c_uint32), C.c_int, C.c_int, C.c_double,
                                         C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    # single-sequence models and their calibration (bathbuild)
+    "bath_scorematrix_builtin": (C.c_char_p, [C.c_char_p]),
+    "bath_scoresystem_create": (C.c_int, [C.c_char_p, C.c_char_p, C.c_double, C.c_double, C.POINTER(_vp), C.c_char_p, C.c_int]),
+    "bath_scoresystem_destroy": (None, [_vp]),
+    "bath_scoresystem_lambda": (C.c_double, [_vp]),
+    "bath_scoresystem_conditionals": (C.c_int, [_vp, C.POINTER(C.c_double)]),
+    "bath_hmm_from_sequence": (C.c_int, [_vp, _u8p, C.c_int, C.c_char_p, C.c_int, C.POINTER(C.POINTER(_Hmm))]),
+    "bath_hmm_mean_match_relent": (C.c_double, [C.POINTER(_Hmm)]),
+    "bath_hmm_lambda": (C.c_double, [C.POINTER(_Hmm)]),
+    "bath_hmm_write_ascii": (C.c_int64, [C.POINTER(_Hmm), C.c_int, C.c_double, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_int64]),
+    "bath_calib_sample_amino": (C.c_int, [C.POINTER(C.c_uint32), _f32p, C.c_int, C.c_int, _u8p]),
+    "bath_gumbel_fit_complete_loc": (C.c_int, [C.POINTER(C.c_double), C.c_int, C.c_double, C.POINTER(C.c_double)]),
+    "bath_hip_calib_samples_create": (C.c_int, [_vp, C.POINTER(C.c_uint32), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(_vp)]),
+    "bath_hip_calib_samples_destroy": (None, [_vp]),
+    "bath_hip_calibrate": (C.c_int, [_vp, C.POINTER(_Hmm), C.c_int, C.POINTER(C.c_uint32), _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                     C.c_double, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int)]),
 }
 
 _lib = None
@@ -408,6 +424,16 @@ class HMM:
         st = lib().bath_hmmfile_read(os.fsencode(path), index, C.byref(p))
         if st != OK:
             raise BathError("cannot read model %d of %s (status %d)" % (index, path, st))
+        self._adopt(p)
+
+    @classmethod
+    def _from_pointer(cls, p):
+        """A model the library made in memory (seq_model); owned by the object like one read from a file."""
+        self = cls.__new__(cls)
+        self._adopt(p)
+        return self
+
+    def _adopt(self, p):
         self._p = p
         self.M = p.contents.M
         self.ct = p.contents.ct
@@ -1732,3 +1758,165 @@ def calibrate_fs(ctx, hmm, ncbi_table, state, L=CALIB_L, N=CALIB_N, tailp=CALIB_
     if want_xv and arith != "strict":
         return t3.value, t5.value, st.value, x3, x5, [re2[0], re2[1]]
     return (t3.value, t5.value, st.value, x3, x5) if want_xv else (t3.value, t5.value, st.value)
+
+
+# ---- single-sequence models and their calibration: what bath_amd.bathbuild calls
+CALIB_DEFAULTS = {"EmL": 200, "EmN": 200, "EvL": 200, "EvN": 200, "EfL": 100, "EfN": 200, "Eft": 0.04}   # p7_builder.c:116-122
+SEQ_COMLOG = "[HMM created from a query sequence]"                     # seqmodel.c:54
+DEGENERATE_AMINO = "BJZOUX"
+
+
+def scorematrix_builtin(name="BLOSUM62"):
+    """The NCBI-format text of a built-in score matrix (BLOSUM62 is the only one); BathError for any other name."""
+    t = lib().bath_scorematrix_builtin(name.encode())
+    if t is None:
+        raise BathError("no matrix named %s is available as a built-in" % name)
+    return t.decode()
+
+
+class ScoreSystem:
+    """p7_builder_LoadScoreSystem / _SetScoreSystem: a substitution matrix (built-in name, or an NCBI-format file) as conditional
+    probabilities against the background, with the gap-open and gap-extend probabilities.  BathError carries the reference's message."""
+
+    def __init__(self, mx="BLOSUM62", mxfile=None, popen=0.02, pextend=0.4):
+        h, err = C.c_void_p(), C.create_string_buffer(1024)
+        st = lib().bath_scoresystem_create(None if mx is None else mx.encode(), None if mxfile is None else os.fsencode(mxfile),
+                                           popen, pextend, C.byref(h), err, len(err))
+        if st != OK:
+            e = BathError(err.value.decode() or "cannot set the score system (status %d)" % st)
+            e.status = st
+            raise e
+        self._h, self.popen, self.pextend = h, popen, pextend
+        self.lambda_ = lib().bath_scoresystem_lambda(h)
+
+    def conditionals(self):
+        """P(b | a) [20, 20] float64: row a is the match emission vector of a query residue a before it is narrowed to float."""
+        q = np.zeros((K, K), np.float64)
+        lib().bath_scoresystem_conditionals(self._h, _f64p(q))
+        return q
+
+    def __del__(self):
+        if getattr(self, "_h", None):
+            lib().bath_scoresystem_destroy(self._h)
+            self._h = None
+
+
+def strip_query(seq):
+    """p7_SingleBuilder:513-524: the residues of a query with every non-residue symbol (gap, *, ~) dropped, as codes 0..19.  A
+    degenerate code (BJZOUX) is refused by name: the reference indexes outside its K x K matrix there.  A symbol outside the
+    amino alphabet is refused too."""
+    codes = digitize(seq, AMINO_SYMS)
+    bad = sorted({AMINO_SYMS[c] for c in codes if 21 <= c <= 26})
+    if bad:
+        raise BathError("the query holds the degenerate residue code%s %s: a single-sequence model has no emission row for it" %
+                        ("s" if len(bad) > 1 else "", ", ".join(bad)))
+    return np.ascontiguousarray(codes[codes < K])
+
+
+def seq_model(score, seq, name, ct=1):
+    """p7_SingleBuilder up to calibration: the HMM of one protein sequence (a string, or residue codes 0..19) under a ScoreSystem --
+    p7_Seqmodel, p7_hmm_SetComposition, p7_hmm_SetConsensus -- in memory, uncalibrated, MAXL unset."""
+    codes = strip_query(seq) if isinstance(seq, str) else np.ascontiguousarray(seq, dtype=np.uint8)
+    if len(codes) < 1:
+        raise BathError("the query %s holds no residue" % name)
+    p = C.POINTER(_Hmm)()
+    st = lib().bath_hmm_from_sequence(score._h, _u8(codes), len(codes), name.encode(), ct, C.byref(p))
+    if st == ERANGE:
+        raise BathError("the query's name %s... is longer than the 127 bytes a model's NAME holds" % name[:24])
+    if st != OK:
+        raise BathError("cannot build a model from the query %s (status %d)" % (name, st))
+    return HMM._from_pointer(p)
+
+
+def hmm_relent(hmm):
+    """p7_MeanMatchRelativeEntropy: bits per match state (the summary's re/pos)."""
+    return lib().bath_hmm_mean_match_relent(hmm._p)
+
+
+def hmm_lambda(hmm):
+    """p7_Lambda: ln 2 + 1.44 / (M * re/pos)."""
+    return lib().bath_hmm_lambda(hmm._p)
+
+
+def hmm_set_max_length(hmm, maxl):
+    hmm._p.contents.max_length = hmm.max_length = int(maxl)
+
+
+def hmm_set_evparam(hmm, evparam):
+    """Stores eight E-value parameters (MSV mu, lambda, Viterbi mu, lambda, Forward tau, lambda, FS3 tau, FS5 tau) as floats."""
+    ev = np.asarray(evparam, dtype=np.float32)
+    assert ev.shape == (NEVPARAM,)
+    for i in range(NEVPARAM):
+        hmm._p.contents.evparam[i] = float(ev[i])
+    hmm.evparam = ev.copy()
+
+
+def hmm_text(hmm, nseq=1, eff_nseq=1.0, desc=None, date=None, comlog=SEQ_COMLOG):
+    """p7_hmmfile_WriteASCII in the BATH3/f format: the whole model's text (bytes)."""
+    enc = lambda v: None if v is None else v.encode("latin-1")
+    args = (hmm._p, nseq, eff_nseq, enc(desc), enc(date), enc(comlog))
+    n = lib().bath_hmm_write_ascii(*args, None, 0)
+    if n < 0:
+        raise BathError("the model cannot be written")
+    buf = C.create_string_buffer(n)
+    lib().bath_hmm_write_ascii(*args, buf, n)
+    return buf.raw
+
+
+def calib_sample_amino(state, L, N, f=None):
+    """N background sequences of L residues (esl_rsq_xfIID, the stream of p7_MSVMu / p7_ViterbiMu / p7_Tau): (codes [N, L], the
+    generator's state afterwards)."""
+    st = C.c_uint32(state)
+    aa = np.zeros((N, L), dtype=np.uint8)
+    fa = None if f is None else np.ascontiguousarray(f, dtype=np.float32)
+    if lib().bath_calib_sample_amino(C.byref(st), _f32(fa), L, N, _u8(aa) if aa.size else None) != OK:
+        raise BathError("calib_sample_amino failed")
+    return aa, st.value
+
+
+def gumbel_fit_complete_loc(x, lam):
+    """esl_gumbel_FitCompleteLoc: the ML mu of a Gumbel of known lambda."""
+    x = np.ascontiguousarray(x, dtype=np.float64)
+    mu = C.c_double(0)
+    st = lib().bath_gumbel_fit_complete_loc(_f64p(x), len(x), lam, C.byref(mu))
+    if st != OK:
+        raise BathError("gumbel_fit_complete_loc failed (%d)" % st)
+    return mu.value
+
+
+class CalibSamples:
+    """The three standard sample sets of a calibration, resident on the device: drawn once from <state> (.state_after: the generator
+    behind them), handed to every calibrate() call of a run that reseeds its generator per model."""
+
+    def __init__(self, ctx, state, EmL=200, EmN=200, EvL=200, EvN=200, EfL=100, EfN=200):
+        st, h = C.c_uint32(state), C.c_void_p()
+        ctx._check(lib().bath_hip_calib_samples_create(ctx._h, C.byref(st), EmL, EmN, EvL, EvN, EfL, EfN, C.byref(h)), "calib_samples_create")
+        self._h, self._ctx, self.state_before, self.state_after = h, ctx, state, st.value
+
+    def close(self):
+        if getattr(self, "_h", None):
+            lib().bath_hip_calib_samples_destroy(self._h)
+            self._h = None
+
+    __del__ = close
+
+
+def calibrate(ctx, hmm, ncbi_table, state, samples=None, EmL=200, EmN=200, EvL=200, EvN=200, EfL=100, EfN=200, Eft=0.04, arith="strict",
+              want_xv=False):
+    """p7_Calibrate of a model in memory, on the GPU: lambda, the MSV and Viterbi mus, the Forward tau and the two frameshift taus
+    are stored in the model (hmm.evparam).  Returns the generator's state afterwards; with want_xv also the bit scores the five
+    fits saw, {"msv", "vit", "fwd", "fs3", "fs5"}.  samples: a CalibSamples drawn from <state> with these lengths and counts, or
+    None to draw the three standard sets for this call."""
+    if arith not in ARITH_MODES:
+        raise ValueError("arith: expected one of %s" % ", ".join(ARITH_MODES))
+    st = C.c_uint32(state)
+    n = [EmN, EvN, EfN, EfN, EfN]
+    xv = np.zeros(sum(n), np.float64) if want_xv else None
+    re2 = (C.c_int * 2)(0, 0)
+    ctx._check(lib().bath_hip_calibrate(ctx._h, hmm._p, ncbi_table, C.byref(st), None if samples is None else samples._h,
+                                        EmL, EmN, EvL, EvN, EfL, EfN, Eft, ARITH_MODES[arith], None if xv is None else _f64p(xv), re2), "calibrate")
+    hmm.evparam = np.array(hmm._p.contents.evparam[:], dtype=np.float32)
+    if not want_xv:
+        return st.value
+    cut = np.cumsum([0] + n)
+    return st.value, {k: xv[cut[i]:cut[i + 1]].copy() for i, k in enumerate(("msv", "vit", "fwd", "fs3", "fs5"))}

@@ -6,6 +6,10 @@
 // configuration of length L; a Gumbel fitted to the N bit scores; tau where the Gumbel's tail of mass <tailp> starts, moved back to
 // the origin of the exponential tail.  Also p7_Builder_MaxLength (src/p7_builder.c:678), which bathconvert runs for a file without MAXL.
 //
+// And p7_Calibrate (src/evalues.c:64-199) for a model built in memory (bathbuild on a protein sequence): the MSV and Viterbi mus and the
+// Forward tau from three sets of background sequences through the filter kernels, then the two taus above (bath_hip_calibrate, at
+// the end of this file).
+//
 // Where it runs.  The two parsers are the device's work (bath_hip_fs3_forward_parser; bath_hip_fs5_forward_parser, the score-only
 // instantiation of the regions' chain kernel).  The sampler is a strictly serial consumer of one random-number stream carried from
 // model to model (2 x 200 x 200 steps per model) and its output is 60 KB per parser: host code.  So are the fit (200 numbers) and MAXL.
@@ -36,6 +40,28 @@ static void codon_table(const uint8_t basic[64], uint8_t table[20][6], int num[2
   }
 }
 
+// esl_rsq_xfIID: L draws of esl_rnd_FChoose (f is used as it stands: no esl_vec_FNorm; a roll beyond its sum is drawn again)
+static void draw_amino(FastRng &rng, const float *f, int L, uint8_t *aa) {
+  for (int i = 0; i < L; i++) {
+    int a = -1;
+    while (a < 0) {
+      const float roll = (float)rng.next();
+      float acc = 0.f;
+      for (int q = 0; q < 20; q++) { acc += f[q]; if (roll < acc) { a = q; break; } }
+    }
+    aa[(size_t)i] = (uint8_t)a;
+  }
+}
+
+extern "C" int bath_calib_sample_amino(uint32_t *rng_state, const float *f, int L, int N, uint8_t *aa) {
+  if (!rng_state || (!aa && (int64_t)L * N > 0) || L < 0 || N < 0) return BATH_EINVAL;
+  if (!f) f = kAminoBg;
+  FastRng rng = FastRng::from_state(*rng_state);
+  for (int s = 0; s < N; s++) draw_amino(rng, f, L, aa + (size_t)s * L);
+  *rng_state = rng.x;
+  return BATH_OK;
+}
+
 extern "C" int bath_calib_sample(uint32_t *rng_state, const float *f, int ncbi_table, int L, int N, uint8_t *dna) {
   if (!rng_state || !dna || L < 0 || N < 0) return BATH_EINVAL;
   if (!f) f = kAminoBg;
@@ -46,15 +72,7 @@ extern "C" int bath_calib_sample(uint32_t *rng_state, const float *f, int ncbi_t
   FastRng rng = FastRng::from_state(*rng_state);
   std::vector<uint8_t> aa((size_t)L);
   for (int s = 0; s < N; s++) {
-    for (int i = 0; i < L; i++) {                          // esl_rsq_xfIID: L draws of esl_rnd_FChoose (f is used as it stands: no esl_vec_FNorm)
-      int a = -1;
-      while (a < 0) {
-        const float roll = (float)rng.next();
-        float acc = 0.f;
-        for (int q = 0; q < 20; q++) { acc += f[q]; if (roll < acc) { a = q; break; } }
-      }
-      aa[(size_t)i] = (uint8_t)a;
-    }
+    draw_amino(rng, f, L, aa.data());
     uint8_t *d = dna + (size_t)s * 3 * L;
     for (int i = 0; i < L; i++) {                          // p7_codontable_GetCodon: esl_rnd_Roll(r, num_codons[a])
       const int a = aa[(size_t)i];
@@ -152,6 +170,15 @@ extern "C" int bath_gumbel_fit_complete(const double *x, int n, double *ret_mu, 
   return BATH_OK;
 }
 
+// esl_gumbel_FitCompleteLoc: the ML location of a Gumbel of known lambda on complete data
+extern "C" int bath_gumbel_fit_complete_loc(const double *x, int n, double lambda, double *ret_mu) {
+  if (!x || n < 2 || !ret_mu || !(lambda > 0.)) return BATH_EINVAL;
+  double esum = 0.;
+  for (int i = 0; i < n; i++) esum += std::exp(-lambda * x[i]);
+  *ret_mu = -1. * std::log(esum / n) / lambda;
+  return BATH_OK;
+}
+
 extern "C" double bath_gumbel_invcdf(double p, double mu, double lambda) { return mu - (std::log(-1. * std::log(p)) / lambda); }
 
 // evalues.c:658, :753
@@ -236,8 +263,13 @@ int calib_score(void *user, const uint8_t *dna, int n, int L3, float *sc) {
 }
 }  // namespace
 
+// keep_spans: the caller (bath_hip_calibrate) has recorded this model's standard filters on the context and wants them kept
+// lambda_known: the slope the taus are anchored with; <= 0: the model's own float (bathconvert reads it from the file, bathconvert.c:128-162;
+// p7_Calibrate hands its double on, evalues.c:142-143)
 static int calibrate_fs_strict(bath_hip_ctx *ctx, const bath_hmm *hmm, int ncbi_table, uint32_t *rng_state, int L, int N, double tailp,
-                               double *tau3, double *tau5, double *xv3, double *xv5);
+                               double *tau3, double *tau5, double *xv3, double *xv5, bool keep_spans = false, double lambda_known = 0.);
+static int calibrate_fs_any(bath_hip_ctx *ctx, const bath_hmm *hmm, int ncbi_table, uint32_t *rng_state, int L, int N, double tailp,
+                            double *tau3, double *tau5, double *xv3, double *xv5, int arith, int *redrawn, bool keep_spans, double lambda_known = 0.);
 
 extern "C" int bath_hip_calibrate_fs(bath_hip_ctx *ctx, const bath_hmm *hmm, int ncbi_table, uint32_t *rng_state, int L, int N, double tailp,
                                      double *tau3, double *tau5, double *xv3, double *xv5) {
@@ -246,16 +278,21 @@ extern "C" int bath_hip_calibrate_fs(bath_hip_ctx *ctx, const bath_hmm *hmm, int
 
 extern "C" int bath_hip_calibrate_fs_arith(bath_hip_ctx *ctx, const bath_hmm *hmm, int ncbi_table, uint32_t *rng_state, int L, int N, double tailp,
                                            double *tau3, double *tau5, double *xv3, double *xv5, int arith, int *redrawn) {
+  return calibrate_fs_any(ctx, hmm, ncbi_table, rng_state, L, N, tailp, tau3, tau5, xv3, xv5, arith, redrawn, false);
+}
+
+static int calibrate_fs_any(bath_hip_ctx *ctx, const bath_hmm *hmm, int ncbi_table, uint32_t *rng_state, int L, int N, double tailp,
+                            double *tau3, double *tau5, double *xv3, double *xv5, int arith, int *redrawn, bool keep_spans, double lambda_known) {
   if (!ctx) return BATH_EINVAL;
   if (arith < BATH_ARITH_STRICT || arith > BATH_ARITH_ODDS) { ctx->set_error("calibrate_fs: arith is 0 (strict), 1 (3-codon parser in odds ratios) or 2 (both parsers)"); return BATH_EINVAL; }
   if (redrawn) redrawn[0] = redrawn[1] = 0;
-  if (arith == BATH_ARITH_STRICT) return calibrate_fs_strict(ctx, hmm, ncbi_table, rng_state, L, N, tailp, tau3, tau5, xv3, xv5);
+  if (arith == BATH_ARITH_STRICT) return calibrate_fs_strict(ctx, hmm, ncbi_table, rng_state, L, N, tailp, tau3, tau5, xv3, xv5, keep_spans, lambda_known);
   if (!hmm || !rng_state || !tau3 || !tau5 || L < 2 || N < 2 || !(tailp > 0. && tailp < 1.)) { ctx->set_error("calibrate_fs: needs a model, a generator state, L >= 2, N >= 2 and 0 < tailp < 1"); return BATH_EINVAL; }
   uint8_t basic[64];
   if (bath_gencode_basic(ncbi_table, basic) != BATH_OK) { ctx->set_error("calibrate_fs: unknown NCBI translation table " + std::to_string(ncbi_table)); return BATH_EINVAL; }
-  ctx->spans_reset();
+  if (!keep_spans) ctx->spans_reset();
   const float nullsc = bath_bg_fs_nullone(L);
-  const double lambda = (double)hmm->evparam[5];           // p7_FLAMBDA
+  const double lambda = lambda_known > 0. ? lambda_known : (double)hmm->evparam[5];   // p7_FLAMBDA
   std::vector<double> own((size_t)N);
   uint32_t state = *rng_state;
   for (int pass = 0; pass < 2; pass++) {
@@ -283,14 +320,14 @@ extern "C" int bath_hip_calibrate_fs_arith(bath_hip_ctx *ctx, const bath_hmm *hm
 }
 
 static int calibrate_fs_strict(bath_hip_ctx *ctx, const bath_hmm *hmm, int ncbi_table, uint32_t *rng_state, int L, int N, double tailp,
-                               double *tau3, double *tau5, double *xv3, double *xv5) {
+                               double *tau3, double *tau5, double *xv3, double *xv5, bool keep_spans, double lambda_known) {
   if (!ctx) return BATH_EINVAL;
   if (!hmm || !rng_state || !tau3 || !tau5 || L < 2 || N < 2 || !(tailp > 0. && tailp < 1.)) { ctx->set_error("calibrate_fs: needs a model, a generator state, L >= 2, N >= 2 and 0 < tailp < 1"); return BATH_EINVAL; }
   uint8_t basic[64];
   if (bath_gencode_basic(ncbi_table, basic) != BATH_OK) { ctx->set_error("calibrate_fs: unknown NCBI translation table " + std::to_string(ncbi_table)); return BATH_EINVAL; }
-  ctx->spans_reset();                                      // bath_hip_kernel_times afterwards: this model's two parser launches
+  if (!keep_spans) ctx->spans_reset();                     // bath_hip_kernel_times afterwards: this model's two parser launches
   const float nullsc = bath_bg_fs_nullone(L);
-  const double lambda = (double)hmm->evparam[5];           // p7_FLAMBDA
+  const double lambda = lambda_known > 0. ? lambda_known : (double)hmm->evparam[5];   // p7_FLAMBDA
   std::vector<uint8_t> dna((size_t)N * 3 * L);
   std::vector<int64_t> off((size_t)N + 1);
   for (int i = 0; i <= N; i++) off[(size_t)i] = (int64_t)i * 3 * L;
@@ -319,6 +356,187 @@ static int calibrate_fs_strict(bath_hip_ctx *ctx, const bath_hmm *hmm, int ncbi_
     }
     if ((st = bath_calib_tau(xv, N, lambda, tailp, pass == 0 ? tau3 : tau5)) != BATH_OK) { ctx->set_error("calibrate_fs: the Gumbel fit did not converge"); return st; }
   }
+  *rng_state = state;
+  return BATH_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// p7_Calibrate (evalues.c:64-199) for a model built in memory: lambda, the MSV and Viterbi mus, the Forward tau, then the two
+// frameshift taus from the same generator.
+//
+// The three standard sample sets (EmN x EmL, EvN x EvL, EfN x EfL residues, drawn in that order: evalues.c:119-121) depend on
+// nothing a kernel computes, and a builder that reseeds its generator for every model (p7_builder.c:130-131, evalues.c:94-95)
+// draws the same three for every model: bath_hip_calib_samples holds them on the device with the buffers the fits need, made
+// once per run.  A model's three filters are queued on the context's stream one after another and their scores and statuses
+// come back in one batch of copies behind them: one synchronize per model.  p7_MSVFilter is the SSV filter first and the full MSV
+// filter for the sequences SSV cannot decide (eslENORESULT, msvfilter.c:90): those few, if any, take a second launch.
+// ---------------------------------------------------------------------------------------------------------------------------
+struct bath_hip_calib_samples {
+  bath_hip_ctx *ctx = nullptr;
+  int L[3] = {0, 0, 0}, N[3] = {0, 0, 0};                  // MSV, Viterbi, Forward
+  uint32_t state_before = 0, state_after = 0;              // the generator before the first draw and after the last
+  bath_hip_seqs *sq[3] = {nullptr, nullptr, nullptr};
+  DevBuf order[2], v, sc[3], st[3], todo;                  // identity orders (every sequence of a set has the set's length), SSV maxima, results
+};
+
+extern "C" void bath_hip_calib_samples_destroy(bath_hip_calib_samples *S) {
+  if (!S) return;
+  if (S->ctx) (void)hipSetDevice(S->ctx->device);
+  for (bath_hip_seqs *q : S->sq) if (q) bath_hip_seqs_destroy(q);
+  for (DevBuf &b : S->order) b.release();
+  for (DevBuf &b : S->sc) b.release();
+  for (DevBuf &b : S->st) b.release();
+  S->v.release(); S->todo.release();
+  delete S;
+}
+
+static int calib_samples_create(bath_hip_ctx *ctx, uint32_t *rng_state, const int L[3], const int N[3], bath_hip_calib_samples **ret) {
+  *ret = nullptr;
+  for (int s = 0; s < 3; s++)
+    if (L[s] < 1 || N[s] < 2 || (int64_t)L[s] * N[s] > (int64_t)1 << 28) { ctx->set_error("calibrate: every sample set needs a length >= 1 and at least 2 sequences (and at most 2^28 residues)"); return BATH_EINVAL; }
+  BATH_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  bath_hip_calib_samples *S = new bath_hip_calib_samples();
+  S->ctx = ctx;
+  S->state_before = *rng_state;
+  uint32_t state = *rng_state;
+  int st = BATH_OK;
+  for (int s = 0; s < 3 && st == BATH_OK; s++) {
+    S->L[s] = L[s]; S->N[s] = N[s];
+    std::vector<uint8_t> aa((size_t)L[s] * N[s]);
+    std::vector<int64_t> off((size_t)N[s] + 1);
+    for (int i = 0; i <= N[s]; i++) off[(size_t)i] = (int64_t)i * L[s];
+    st = bath_calib_sample_amino(&state, kAminoBg, L[s], N[s], aa.data());
+    if (st == BATH_OK) st = bath_hip_seqs_create(ctx, aa.data(), off.data(), N[s], &S->sq[s]);
+    if (st == BATH_OK && (S->sc[s].reserve((size_t)N[s] * sizeof(float)) != hipSuccess || S->st[s].reserve((size_t)N[s] * sizeof(int32_t)) != hipSuccess)) st = BATH_EMEM;
+  }
+  for (int s = 0; s < 2 && st == BATH_OK; s++) {
+    std::vector<int32_t> order((size_t)N[s]);
+    for (int i = 0; i < N[s]; i++) order[(size_t)i] = i;
+    if (S->order[s].reserve(order.size() * sizeof(int32_t) + 16) != hipSuccess) { st = BATH_EMEM; break; }
+    if (hipMemcpy(S->order[s].p, order.data(), order.size() * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess) st = BATH_EFAIL;
+  }
+  if (st == BATH_OK && (S->v.reserve((size_t)N[0] * sizeof(int16_t)) != hipSuccess || S->todo.reserve((size_t)N[0] * sizeof(int32_t)) != hipSuccess)) st = BATH_EMEM;
+  if (st != BATH_OK) {
+    if (st == BATH_EMEM || st == BATH_EFAIL) ctx->set_error("calibrate: cannot place the sample sets on the device");
+    bath_hip_calib_samples_destroy(S);
+    return st;
+  }
+  S->state_after = state;
+  *rng_state = state;
+  *ret = S;
+  return BATH_OK;
+}
+
+extern "C" int bath_hip_calib_samples_create(bath_hip_ctx *ctx, uint32_t *rng_state, int EmL, int EmN, int EvL, int EvN, int EfL, int EfN,
+                                             bath_hip_calib_samples **ret) {
+  if (!ctx) return BATH_EINVAL;
+  if (!rng_state || !ret) { ctx->set_error("calib_samples_create: needs a generator state and a place for the handle"); return BATH_EINVAL; }
+  const int L[3] = {EmL, EvL, EfL}, N[3] = {EmN, EvN, EfN};
+  return calib_samples_create(ctx, rng_state, L, N, ret);
+}
+
+// the three standard fits of one model on the resident sets: mu[0] MSV, mu[1] Viterbi, mu[2] the Forward tau; xv: NULL or
+// N[0] + N[1] + N[2] bit scores, set after set
+static int calibrate_std(bath_hip_ctx *ctx, const bath_hip_oprofile *om, bath_hip_calib_samples *S, double lambda, double tailp, double mu[3], double *xv) {
+  BATH_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  int st = om->ensure_len_tables(std::max(S->L[0], std::max(S->L[1], S->L[2])));
+  if (st != BATH_OK) return st;
+  const double M = (double)om->M;
+  const bath_hip_seqs *qm = S->sq[0], *qv = S->sq[1], *qf = S->sq[2];
+  int sp = ctx->span_begin("calib_msv", ctx->stream, M * S->L[0] * S->N[0], 0.);
+  if ((st = launch_ssv_lane(ctx, om, qm->view(), S->order[0].as<int32_t>(), S->v.as<int16_t>())) != BATH_OK) return st;
+  if ((st = launch_ssv_classify(ctx, om, qm->n, qm->d_len, S->v.as<int16_t>(), S->sc[0].as<float>(), S->st[0].as<int32_t>())) != BATH_OK) return st;
+  ctx->span_end(sp, ctx->stream);
+  sp = ctx->span_begin("calib_vit", ctx->stream, M * S->L[1] * S->N[1], 0.);
+  st = vit_lane_supported(om) ? launch_vit_lane(ctx, om, qv->view(), S->order[1].as<int32_t>(), qv->n, nullptr, S->sc[1].as<float>(), S->st[1].as<int32_t>(), nullptr)
+                              : launch_vit_wave(ctx, om, qv->view(), nullptr, qv->n, S->sc[1].as<float>(), S->st[1].as<int32_t>(), nullptr, nullptr);
+  if (st != BATH_OK) return st;
+  ctx->span_end(sp, ctx->stream);
+  sp = ctx->span_begin("calib_fwd", ctx->stream, M * S->L[2] * S->N[2], 0.);
+  if ((st = launch_fwd_wave(ctx, om, qf->view(), nullptr, qf->n, S->sc[2].as<float>(), S->st[2].as<int32_t>(), nullptr)) != BATH_OK) return st;
+  ctx->span_end(sp, ctx->stream);
+
+  std::vector<float> sc[3];
+  std::vector<int32_t> status[3];
+  for (int s = 0; s < 3; s++) {
+    sc[s].resize((size_t)S->N[s]); status[s].resize((size_t)S->N[s]);
+    BATH_HIP_TRY(ctx, hipMemcpyAsync(sc[s].data(), S->sc[s].p, (size_t)S->N[s] * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    BATH_HIP_TRY(ctx, hipMemcpyAsync(status[s].data(), S->st[s].p, (size_t)S->N[s] * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+  }
+  BATH_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  std::vector<int32_t> todo;
+  for (int i = 0; i < S->N[0]; i++) if (status[0][(size_t)i] == BATH_ENORESULT) todo.push_back(i);
+  if (!todo.empty()) {                                     // msvfilter.c:90: SSV could not decide, the full MSV filter does
+    BATH_HIP_TRY(ctx, hipMemcpyAsync(S->todo.p, todo.data(), todo.size() * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+    sp = ctx->span_begin("calib_msv", ctx->stream, 0., 0.);
+    if ((st = launch_msv_wave(ctx, om, qm->view(), S->todo.as<int32_t>(), (int64_t)todo.size(), S->sc[0].as<float>(), S->st[0].as<int32_t>(), nullptr)) != BATH_OK) return st;
+    ctx->span_end(sp, ctx->stream);
+    BATH_HIP_TRY(ctx, hipMemcpyAsync(sc[0].data(), S->sc[0].p, (size_t)S->N[0] * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    BATH_HIP_TRY(ctx, hipMemcpyAsync(status[0].data(), S->st[0].p, (size_t)S->N[0] * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    BATH_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  }
+
+  const float maxsc[2] = {(float)((255 - om->base_b) / om->scale_b),            // evalues.c:305
+                          (float)((32767.0 - om->base_w) / om->scale_w)};        // evalues.c:374
+  static const char *const kWhat[3] = {"msv mu", "vit mu", "fwd tau"};
+  std::vector<double> x;
+  for (int s = 0; s < 3; s++) {
+    const float nullsc = om->lt.h_nullsc[(size_t)S->L[s]];                       // p7_bg_SetLength(bg, L) + p7_bg_NullOne
+    x.assign((size_t)S->N[s], 0.);
+    for (int i = 0; i < S->N[s]; i++) {
+      float v = sc[s][(size_t)i];
+      const int32_t code = status[s][(size_t)i];
+      if (code == BATH_ERANGE && s < 2) v = maxsc[s];
+      else if (code != BATH_OK) { ctx->set_error(std::string("failed to determine ") + kWhat[s] + ": a sampled sequence's filter returned status " + std::to_string(code)); return code == BATH_ERANGE ? BATH_ERANGE : BATH_EFAIL; }
+      x[(size_t)i] = (v - nullsc) / 0.69314718055994529;                          // float difference, double quotient
+    }
+    st = s < 2 ? bath_gumbel_fit_complete_loc(x.data(), S->N[s], lambda, &mu[s]) : bath_calib_tau(x.data(), S->N[s], lambda, tailp, &mu[s]);
+    if (st != BATH_OK) { ctx->set_error(std::string("failed to determine ") + kWhat[s] + ": the fit did not converge"); return st; }
+    if (xv) { std::copy(x.begin(), x.end(), xv); xv += S->N[s]; }
+  }
+  return BATH_OK;
+}
+
+extern "C" int bath_hip_calibrate(bath_hip_ctx *ctx, bath_hmm *hmm, int ncbi_table, uint32_t *rng_state, bath_hip_calib_samples *samples,
+                                  int EmL, int EmN, int EvL, int EvN, int EfL, int EfN, double Eft, int arith, double *xv, int *redrawn) {
+  if (!ctx) return BATH_EINVAL;
+  if (!hmm || hmm->M < 1 || !rng_state || !(Eft > 0. && Eft < 1.)) { ctx->set_error("calibrate: needs a model, a generator state and 0 < Eft < 1"); return BATH_EINVAL; }
+  if (arith < BATH_ARITH_STRICT || arith > BATH_ARITH_ODDS) { ctx->set_error("calibrate: arith is 0 (strict), 1 (3-codon parser in odds ratios) or 2 (both parsers)"); return BATH_EINVAL; }
+  const int L[3] = {EmL, EvL, EfL}, N[3] = {EmN, EvN, EfN};
+  uint32_t state = *rng_state;
+  bath_hip_calib_samples *S = samples, *own = nullptr;
+  if (S) {
+    if (S->ctx != ctx || std::memcmp(S->L, L, sizeof L) || std::memcmp(S->N, N, sizeof N) || S->state_before != state) {
+      ctx->set_error("calibrate: the resident sample sets were drawn for another context, other lengths or counts, or from another generator state");
+      return BATH_EINVAL;
+    }
+    state = S->state_after;
+  } else {
+    const int st = calib_samples_create(ctx, &state, L, N, &own);
+    if (st != BATH_OK) return st;
+    S = own;
+  }
+  ctx->spans_reset();                                      // bath_hip_kernel_times afterwards: this model's filters and parsers
+  bath_profile *gm = nullptr;
+  bath_hip_oprofile *om = nullptr;
+  int st = bath_profile_config(hmm, EvL, &gm);             // evalues.c:109 (the length does not matter: every fit sets its own)
+  if (st == BATH_OK) st = bath_hip_oprofile_convert(ctx, gm, &om);
+  const double lambda = bath_hmm_lambda(hmm);              // p7_Lambda
+  double mu[3] = {0., 0., 0.};
+  if (st == BATH_OK) st = calibrate_std(ctx, om, S, lambda, Eft, mu, xv);
+  if (om) bath_hip_oprofile_destroy(om);
+  if (gm) bath_profile_destroy(gm);
+  if (own) bath_hip_calib_samples_destroy(own);
+  if (st != BATH_OK) return st;
+  float ev[BATH_NEVPARAM];
+  std::memcpy(ev, hmm->evparam, sizeof ev);
+  hmm->evparam[1] = hmm->evparam[3] = hmm->evparam[5] = (float)lambda;           // evalues.c:148-153
+  hmm->evparam[0] = (float)mu[0]; hmm->evparam[2] = (float)mu[1]; hmm->evparam[4] = (float)mu[2];
+  double tau3 = 0., tau5 = 0.;
+  double *xv3 = xv ? xv + EmN + EvN + EfN : nullptr, *xv5 = xv3 ? xv3 + EfN : nullptr;
+  st = calibrate_fs_any(ctx, hmm, ncbi_table, &state, EfL, EfN, Eft, &tau3, &tau5, xv3, xv5, arith, redrawn, true, lambda);
+  if (st != BATH_OK) { std::memcpy(hmm->evparam, ev, sizeof ev); return st; }
+  hmm->evparam[6] = (float)tau3; hmm->evparam[7] = (float)tau5;
   *rng_state = state;
   return BATH_OK;
 }

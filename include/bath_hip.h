@@ -803,6 +803,62 @@ int bath_calib_fit_scores(uint32_t *rng_state, const float *f, int ncbi_table, i
 int bath_hip_calibrate_fs_arith(bath_hip_ctx *ctx, const bath_hmm *hmm, int ncbi_table, uint32_t *rng_state, int L, int N, double tailp,
                                 double *tau3, double *tau5, double *xv3, double *xv5, int arith, int *redrawn);
 
+/* ------------------------------------------------------------------------------------------
+ * Single-sequence models (bathbuild on an unaligned protein file; p7_SingleBuilder, p7_builder.c:501-569) and their calibration
+ * (p7_Calibrate, evalues.c:64-199).  The model is host code; calibration runs the filters and parsers above on sampled sequences.
+ * ------------------------------------------------------------------------------------------ */
+/* The score system of p7_builder_LoadScoreSystem / _SetScoreSystem: a substitution matrix -- the built-in named <mx_name> (NULL:
+ * BLOSUM62, the only one; bath_scorematrix_builtin gives its NCBI-format text or NULL) or, when <mxfile> is not NULL, an NCBI-format
+ * file -- turned into conditional probabilities P(b | a) against the Swiss-Prot background widened to double
+ * (esl_scorematrix_ProbifyGivenBG: lambda solves sum_ab f_a f_b exp(lambda s_ab) = 1; esl_scorematrix_JointToConditionalOnQuery),
+ * with the gap-open and gap-extend probabilities.  On failure <errbuf> holds the reference's message: BATH_EFAIL an unknown
+ * built-in or an unreadable file, BATH_EFORMAT a file that is not a matrix, BATH_EINVAL a matrix without a positive root for lambda. */
+typedef struct bath_scoresystem bath_scoresystem;
+const char *bath_scorematrix_builtin(const char *name);
+int    bath_scoresystem_create(const char *mx_name, const char *mxfile, double popen, double pextend, bath_scoresystem **ret,
+                               char *errbuf, int errlen);
+void   bath_scoresystem_destroy(bath_scoresystem *s);
+double bath_scoresystem_lambda(const bath_scoresystem *s);
+int    bath_scoresystem_conditionals(const bath_scoresystem *s, double *Q /* [20][20], row = the query's residue */);
+/* p7_Seqmodel + p7_hmm_SetComposition + p7_hmm_SetConsensus(hmm, sq) for the residues dsq[0 .. n) (codes 0..19 only: the caller has
+ * stripped non-residues and refused degenerate codes): match emissions of node k are row dsq[k-1] narrowed to float, inserts the
+ * background, transitions from popen / pextend with node M's special cases (seqmodel.c:59-82), the consensus the sequence itself.
+ * evparam unset, max_length -1, fsprob 0.01, ct as given.  BATH_ERANGE: a name of more than 127 bytes (bath_hmm.name would cut it).  The model is in memory as the reference's is when it calibrates it. */
+int    bath_hmm_from_sequence(const bath_scoresystem *s, const uint8_t *dsq, int n, const char *name, int ct, bath_hmm **ret);
+double bath_hmm_mean_match_relent(const bath_hmm *hmm);   /* p7_MeanMatchRelativeEntropy (modelstats.c:80), bits per match state */
+double bath_hmm_lambda(const bath_hmm *hmm);              /* p7_Lambda (evalues.c:244): ln 2 + 1.44 / (M * relent); 0 without a model */
+/* p7_hmmfile_WriteASCII(fp, p7_BATH_3f, hmm) (p7_hmmfile.c:565-689): the whole model's text, fields in the reference's order and
+ * widths.  What bath_hmm does not hold comes as arguments: NSEQ (> 0), EFFN (>= 0), DESC, DATE and the command log, one line per
+ * command (NULL or "": the line is left out).  The STATS block is written when the model is calibrated (evparam set).  Returns the
+ * text's size in bytes and copies at most <cap> of them to <buf>; < 0 on error. */
+int64_t bath_hmm_write_ascii(const bath_hmm *hmm, int nseq, double eff_nseq, const char *desc, const char *date, const char *comlog,
+                             char *buf, int64_t cap);
+/* esl_rsq_xfIID as p7_MSVMu / p7_ViterbiMu / p7_Tau call it (evalues.c:317, :386, :556): N sequences of L residues, aa[N * L] codes
+ * 0..19, from the generator state carried in *rng_state (bath_calib_sample's stream without the codons).  Host only. */
+int bath_calib_sample_amino(uint32_t *rng_state, const float *f, int L, int N, uint8_t *aa);
+int bath_gumbel_fit_complete_loc(const double *x, int n, double lambda, double *mu);   /* esl_gumbel_FitCompleteLoc; host only */
+/* The three standard sample sets of a calibration, resident on the device: EmN x EmL, EvN x EvL and EfN x EfL residues drawn in
+ * that order from *rng_state (advanced past them), with the device buffers a model's three fits need.  They depend on nothing a
+ * kernel computes, and a builder that reseeds its generator for every model (--seed other than 0) draws the same three for every
+ * model: make them once per run and hand them to every bath_hip_calibrate call.  Owned by the caller; destroy before the context. */
+typedef struct bath_hip_calib_samples bath_hip_calib_samples;
+int  bath_hip_calib_samples_create(bath_hip_ctx *ctx, uint32_t *rng_state, int EmL, int EmN, int EvL, int EvN, int EfL, int EfN,
+                                   bath_hip_calib_samples **ret);
+void bath_hip_calib_samples_destroy(bath_hip_calib_samples *s);
+/* p7_Calibrate: lambda (p7_Lambda), then the MSV mu (p7_MSVMu: the MSV filter, SSV first, on EmN sequences of length EmL; an
+ * overflow scores maxsc, evalues.c:305; esl_gumbel_FitCompleteLoc at lambda), the Viterbi mu (p7_ViterbiMu, :374), the Forward tau
+ * (p7_Tau: bath_calib_tau at tail mass Eft), each sequence scored at its own length, xv = (sc - null1) / ln 2; then the FS3 and FS5
+ * taus as bath_hip_calibrate_fs_arith fits them in <arith>, at L = EfL, N = EfN, from the same generator.  The sets are drawn in that
+ * order.  <samples> NULL: the three standard sets are drawn from *rng_state for this call (a generator carried from model to model,
+ * --seed 0); else they are <samples> -- which must have been drawn from the state *rng_state holds, for this context, with these
+ * lengths and counts (BATH_EINVAL otherwise) -- and the frameshift fits go on from where those draws ended.  The model's three
+ * filters are queued before the first synchronize and their scores come back together.  On success hmm->evparam holds all eight
+ * values and *rng_state the generator after the last draw; on failure both are as they were.  xv: NULL or EmN + EvN + 3 EfN bit
+ * scores (MSV, Viterbi, Forward, FS3, FS5); redrawn: as bath_hip_calibrate_fs_arith's.  bath_hip_kernel_times afterwards: this
+ * model's launches ("calib_msv", "calib_vit", "calib_fwd" and the frameshift parsers). */
+int  bath_hip_calibrate(bath_hip_ctx *ctx, bath_hmm *hmm, int ncbi_table, uint32_t *rng_state, bath_hip_calib_samples *samples,
+                        int EmL, int EmN, int EvL, int EvN, int EfL, int EfN, double Eft, int arith, double *xv, int *redrawn);
+
 /* The multi-domain region stage on its own: the multihit Forward of every sequence of <regions> (each one region, configuration
  * length 100 as the pipeline's) and its trace ensemble in the context's bath_hip_set_fs_ensemble mode.  Per region r:
  *   region_status[r]  0 = ok, 1 = no valid traces (Forward underflow, an impossible state, the step cap): no envelopes;
