@@ -6,15 +6,15 @@
 // maximal run of non-stop codons of at least <minlen> residues in each of the six frames of a window is one
 // ORF; windows shorter than 15 nt are skipped (bathsearch.c:1066).
 //
-// GPU formulation.  A window is cut into tiles of 384 nt; a half wave (32 lanes x 12 nt) owns a tile, so the work
+// GPU formulation.  A window is cut into tiles of 384 nt; a quarter wave (16 lanes x 24 nt) owns a tile, so the work
 // is parallel over the total sequence length whatever the shape of the block (10^6 windows of 1 kb, or a few
 // windows of 256 kb), loads are contiguous across lanes and every stream's residues leave as contiguous dwords.
 //   orf_tile_kernel   The three bytes at position p are codon p/3 of forward frame p%3 and, on the other strand, a codon
 //                     of reverse frame (n-p)%3 (runs of non-stop codons are the same whichever way a frame is walked,
 //                     so reverse frames are scanned in memory order too).  Canonical ACGT codons are decoded by one
-//                     24-bit multiply + bit-field extract + a 64-entry LDS table per strand, degenerate codes by the
-//                     general 18^3 table.  Per stream, the length of the stop-free run entering each lane's four codons
-//                     comes from a DPP running maximum over the half wave (the last stop before the lane); runs closed by two stops inside the tile are recorded as ORFs
+//                     24-bit multiply + bit-field extract + one 64-entry LDS table for both strands, degenerate codes by the
+//                     general 18^3 table.  Per stream, the length of the stop-free run entering each lane's eight codons
+//                     comes from a DPP running maximum over the tile's 16-lane row (the last stop before the lane); runs closed by two stops inside the tile are recorded as ORFs
 //                     at once, the run touching the tile's left edge ("prefix") and the one open at its right edge
 //                     ("suffix") are left in the tile summary.  Positions past the end of a stream count as stops.
 //   orf_stitch_kernel one lane per (window, frame) walks the tile summaries and records the ORFs that cross tiles.
@@ -32,9 +32,11 @@
 
 namespace bath {
 
-constexpr int kTileLanes = 32;
-constexpr int kTileCodons = 4 * kTileLanes;    // scan positions per stream and tile
-constexpr int kTileNt = 12 * kTileLanes;
+constexpr int kTileLanes = 16;                 // a quarter wave owns a tile: exactly one 16-lane DPP row
+constexpr int kLaneCodons = 8;                 // codons per stream and lane
+constexpr int kLaneNt = 3 * kLaneCodons;       // nucleotides per lane (it reads two more: its last codons run into the next lane's bytes)
+constexpr int kTileCodons = kLaneCodons * kTileLanes;    // scan positions per stream and tile
+constexpr int kTileNt = kLaneNt * kTileLanes;
 
 struct OrfScanTables {
   const uint8_t *aa_full;   // [5832] (a*18+b)*18+c -> amino code, degenerate codons resolved (esl_gencode_GetTranslation)
@@ -72,31 +74,30 @@ struct OrfFilter {
 
 __device__ __forceinline__ int orf_bin(int len) { return min(len, kOrfBins - 1); }
 
-__device__ __forceinline__ int half_shfl_up(int v, int d) { return __shfl_up(v, d, kTileLanes); }
-
-// Exclusive running maximum over the lanes of a 32-lane half wave (lane 0 of a half gets <ident>), by DPP: one lane shift, then
-// row_shr 1/2/4/8 inside the 16-lane rows and row_bcast:15 into the upper row of each half.  ~11 VALU instructions; the ballot
-// form this replaces cost 7 per codon of the chunk.
+// Exclusive running maximum over the 16 lanes of a DPP row (lane 0 of a row gets <ident>): row_shr:1, then row_shr 1/2/4/8 of the
+// shifted value.  5 VALU instructions once the identity is INT_MIN (the compiler folds each step into one v_max_i32_dpp; with
+// another identity it emits mov + dpp-mov + max).  A tile is one row, so nothing crosses rows.
 template <int CTRL, int ROW_MASK = 0xf>
 __device__ __forceinline__ int dpp_or_ident(int v, int ident) { return __builtin_amdgcn_update_dpp(ident, v, CTRL, ROW_MASK, 0xf, false); }
-__device__ __forceinline__ int half_excl_max_scan(int v, int ident, bool first_lane_of_half) {
-  int x = dpp_or_ident<0x138>(v, ident);                           // wave_shr:1
-  x = first_lane_of_half ? ident : x;
+__device__ __forceinline__ int row_excl_max_scan(int v, int ident) {
+  int x = dpp_or_ident<0x111>(v, ident);                           // row_shr:1
   x = max(x, dpp_or_ident<0x111>(x, ident));                       // row_shr:1
   x = max(x, dpp_or_ident<0x112>(x, ident));                       // row_shr:2
   x = max(x, dpp_or_ident<0x114>(x, ident));                       // row_shr:4
   x = max(x, dpp_or_ident<0x118>(x, ident));                       // row_shr:8
-  x = max(x, dpp_or_ident<0x142, 0xa>(x, ident));                  // row_bcast:15 into rows 1 and 3
   return x;
 }
 
-__global__ __launch_bounds__(256) void orf_tile_kernel(SeqView dna, OrfTiles tiles, OrfScanTables tabs, OrfScanOut out, int minlen) {
+__global__ __launch_bounds__(256, 5) void orf_tile_kernel(SeqView dna, OrfTiles tiles, OrfScanTables tabs, OrfScanOut out, int minlen) {
   __shared__ int s_hist[kOrfBins];
   __shared__ __attribute__((aligned(16))) uint8_t s_full[5832 + 8];
   __shared__ uint16_t s_fr[64];                                // canonical codon -> forward amino acid | reverse-strand amino acid << 8, bit 7 of each = stop
   __shared__ uint8_t s_comp[32];
   __shared__ unsigned s_red[2];
-  __shared__ int s_cnt[8];                                     // per half wave: ORFs recorded in the current tile
+  // per quarter wave, for the current tile: [0..5] prefix and [6..11] suffix of the six frames, [12] ORFs recorded.  The tile's
+  // summary leaves as ONE store instruction of 13 lanes: the kernel is bound by the number of memory instructions it issues
+  // (DESIGN 4.0), and twelve single-lane stores per tile cost as much there as twelve full ones.
+  __shared__ int s_sum[256 / kTileLanes][16];
   for (int i = threadIdx.x; i < kOrfBins; i += blockDim.x) s_hist[i] = 0;
   for (int i = threadIdx.x; i < 5832; i += blockDim.x) s_full[i] = tabs.aa_full[i];
   if (threadIdx.x < 64) {
@@ -106,88 +107,106 @@ __global__ __launch_bounds__(256) void orf_tile_kernel(SeqView dna, OrfTiles til
   if (threadIdx.x < 18) s_comp[threadIdx.x] = tabs.comp[threadIdx.x];
   if (threadIdx.x < 2) s_red[threadIdx.x] = 0;
   __syncthreads();
-  const int hw = threadIdx.x / kTileLanes;                     // half wave within the block
+  const int qw = threadIdx.x / kTileLanes;                     // quarter wave within the block
   const int i = threadIdx.x % kTileLanes;                      // lane within the tile
   const int64_t wave0 = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
   const int64_t nwaves = ((int64_t)gridDim.x * blockDim.x) >> 6;
   unsigned my_orfs = 0, my_res = 0;
-  // Software pipeline over this wave's tiles: descriptors are fetched two tiles ahead and the lane's 16 bytes of DNA one
-  // tile ahead, so the dependent loads (descriptor -> sequence data) of a tile are in flight while the previous one computes.
-  const int half = (threadIdx.x & 63) / kTileLanes;
+  // Software pipeline over this wave's tiles (four per iteration, one per quarter wave): descriptors are fetched two tiles ahead
+  // and the lane's 26 bytes of DNA one tile ahead, so the dependent loads (descriptor -> sequence data) of a tile are in flight
+  // while the previous one computes.
+  const int quarter = (threadIdx.x & 63) / kTileLanes;
   const int4 none = {0, 0, 0, 0};
-  auto fetch_desc = [&](int64_t tb) { const int64_t t = tb + half; return t < tiles.ntiles ? tiles.desc[t] : none; };
-  auto fetch_data = [&](const int4 &dsc, uint32_t (&D)[4]) {
-    const int p0 = kTileNt * dsc.w + 12 * i;
-    D[0] = D[1] = D[2] = D[3] = 0u;
-    if (p0 < dsc.y) {
-      const uint8_t *d = dna.data + ((int64_t)(uint32_t)dsc.x << 4) + p0;
+  auto fetch_desc = [&](int64_t tb) { const int64_t t = tb + quarter; return t < tiles.ntiles ? tiles.desc[t] : none; };
+  auto fetch_data = [&](const int4 &dsc, uint32_t (&D)[7]) {
+    const int p0 = kTileNt * dsc.w + kLaneNt * i;
 #pragma unroll
-      for (int k = 0; k < 4; k++) D[k] = *reinterpret_cast<const uint32_t *>(d + 4 * k);
-    }
+    for (int k = 0; k < 7; k++) D[k] = 0u;
+    const uint8_t *d = dna.data + ((int64_t)(uint32_t)dsc.x << 4) + p0;   // 8-byte aligned: windows start on 16, p0 is a multiple of 8
+    // no load starts at or past the window end, so none reaches further than 7 bytes beyond it
+#pragma unroll
+    for (int k = 0; k < 3; k++)
+      if (p0 + 8 * k < dsc.y) { const uint2 v = *reinterpret_cast<const uint2 *>(d + 8 * k); D[2 * k] = v.x; D[2 * k + 1] = v.y; }
+    if (p0 + 24 < dsc.y) D[6] = *reinterpret_cast<const uint32_t *>(d + 24);
   };
-  const int64_t tstep = nwaves * 2;
-  int4 d_next = fetch_desc(wave0 * 2), d_next2 = fetch_desc(wave0 * 2 + tstep);
-  uint32_t D_next[4];
+  const int64_t tstep = nwaves * 4;
+  int4 d_next = fetch_desc(wave0 * 4), d_next2 = fetch_desc(wave0 * 4 + tstep);
+  uint32_t D_next[7];
   fetch_data(d_next, D_next);
-  for (int64_t tb = wave0 * 2; tb < tiles.ntiles; tb += tstep) {
-    const int64_t tile = tb + half;
+  for (int64_t tb = wave0 * 4; tb < tiles.ntiles; tb += tstep) {
+    const int64_t tile = tb + quarter;
     const int4 dsc = d_next;
-    uint32_t D[4] = {D_next[0], D_next[1], D_next[2], D_next[3]};
+    uint32_t D[7];
+#pragma unroll
+    for (int k = 0; k < 7; k++) D[k] = D_next[k];
     d_next = d_next2;
     d_next2 = fetch_desc(tb + 2 * tstep);
     fetch_data(d_next, D_next);
-    const int n = dsc.y;                                       // n >= 15 for every window that has tiles; 0: no tile for this half wave
+    const int n = dsc.y;                                       // n >= 15 for every window that has tiles; 0: no tile for this quarter wave
     const bool live = n > 0;
     const int w = dsc.z, T = dsc.w;
     const int64_t off = (int64_t)(uint32_t)dsc.x << 4;
-    const int p0 = kTileNt * T + 12 * i;
-    if (i == 0) s_cnt[hw] = 0;
-    // ---- bytes past the window end read as 0 (they only feed positions that count as stops)
+    const int p0 = kTileNt * T + kLaneNt * i;
+    if (i == 0) s_sum[qw][12] = 0;
+    // ---- bytes past the window end read as 0 (they only feed positions that count as stops, but the padding between windows is
+    // not a nucleotide code and would send the wave down the degenerate path): dword k keeps its low clamp(n - p0 - 4k, 0, 4) bytes
+    const int rem8 = 8 * min(n - p0, 32);
 #pragma unroll
-    for (int k = 0; k < 4; k++) {
-      const int rem = n - (p0 + 4 * k);
-      if (rem < 4) D[k] = (rem <= 0) ? 0u : (D[k] & ((1u << (8 * rem)) - 1u));
+    for (int k = 0; k < 7; k++) {
+      const int t8 = min(max(rem8 - 32 * k, 0), 32);
+      D[k] &= (uint32_t)((0xffffffffull << t8) >> 32);
     }
-    const bool canonical = ((D[0] | D[1] | D[2] | (D[3] & 0xffffu)) & 0xfcfcfcfcu) == 0u;
-    int af[12], ar[12];
+    const bool canonical = ((D[0] | D[1] | D[2] | D[3] | D[4] | D[5] | (D[6] & 0xffffu)) & 0xfcfcfcfcu) == 0u;
+    // The 16-bit table entries of codon k (bytes k .. k+2 of the lane) stay whole, forward amino acid in the low byte and the
+    // reverse strand's in the high byte, a stop flag in bit 7 of each.  Codon k belongs to phase k % 3 and is codon c = k / 3 of
+    // that phase's streams; W[4 ph + c / 2] holds the entries of codons c, c + 1 (c even) in its low and high half.
+    unsigned W[12];
     if (__all(canonical)) {
+      unsigned e[24];
 #pragma unroll
-      for (int k = 0; k < 12; k++) {
+      for (int k = 0; k < 24; k++) {
         const unsigned t = (k % 4 == 0) ? D[k / 4] : __builtin_amdgcn_alignbyte(D[k / 4 + 1], D[k / 4], k % 4);
-        // bytes x0,x1,x2 < 4 at bits 0,8,16: t * (2^20 + 2^10 + 1) has x0<<4|x1<<2|x2 at bits 16..21 and nothing else there
-        const unsigned idx = (__umul24(t, 0x100401u) >> 16) & 63u;
-        const unsigned e = s_fr[idx];
-        af[k] = (int)(e & 0xffu); ar[k] = (int)(e >> 8);
+        // bytes x0,x1,x2 < 4 at bits 0,8,16: t * (2^21 + 2^11 + 2) has (x0<<4|x1<<2|x2) << 1, the byte offset of the codon's
+        // 16-bit entry, at bits 16..22 (bit 16 is always 0) and nothing else there
+        const unsigned boff = (__umul24(t, 0x200802u) >> 16) & 127u;
+        e[k] = *reinterpret_cast<const uint16_t *>(reinterpret_cast<const uint8_t *>(s_fr) + boff);
       }
-    } else {
 #pragma unroll
-      for (int k = 0; k < 12; k++) {
+      for (int q = 0; q < 12; q++) W[q] = e[q / 4 + 6 * (q % 4)] | (e[q / 4 + 6 * (q % 4) + 3] << 16);
+    } else {
+      unsigned e[24];
+#pragma unroll
+      for (int k = 0; k < 24; k++) {
         const unsigned t = (k % 4 == 0) ? D[k / 4] : __builtin_amdgcn_alignbyte(D[k / 4 + 1], D[k / 4], k % 4);
         const int x0 = min((int)(t & 0xffu), 17), x1 = min((int)((t >> 8) & 0xffu), 17), x2 = min((int)((t >> 16) & 0xffu), 17);
-        const int f = s_full[(x0 * 18 + x1) * 18 + x2];
-        const int r = s_full[((int)s_comp[x2] * 18 + (int)s_comp[x1]) * 18 + (int)s_comp[x0]];
-        af[k] = f | (f == kStop ? 0x80 : 0); ar[k] = r | (r == kStop ? 0x80 : 0);
+        const unsigned f = s_full[(x0 * 18 + x1) * 18 + x2];
+        const unsigned r = s_full[((int)s_comp[x2] * 18 + (int)s_comp[x1]) * 18 + (int)s_comp[x0]];
+        e[k] = (f | (f == kStop ? 0x80u : 0u)) | ((r | (r == kStop ? 0x80u : 0u)) << 8);
       }
+#pragma unroll
+      for (int q = 0; q < 12; q++) W[q] = e[q / 4 + 6 * (q % 4)] | (e[q / 4 + 6 * (q % 4) + 3] << 16);
     }
-    const int nvalid = live ? min(max(n - 2 - p0, 0), 12) : 0;            // positions p0 .. p0+nvalid-1 start a codon inside the window
+    const int nvalid = live ? min(max(n - 2 - p0, 0), kLaneNt) : 0;      // positions p0 .. p0+nvalid-1 start a codon inside the window
     const int pitch = orf_stream_pitch(n);
     uint8_t *const abase = out.aa + (2 * off + 96 * (int64_t)w);
-    const int u0 = kTileCodons * T + 4 * i;                              // scan index of the lane's first codon, every stream
-    // af[], ar[] carry a stop flag in bit 7.  A stream's four codons packed into a dword give its stops as the flag bits 7, 15,
-    // 23, 31 with one AND; codons past the end of the stream count as stops: cv = how many of the four exist (x / 3 = x * 11 >> 5
-    // for x < 15), the others' flags are forced.
-    unsigned inv[3];
+    const int u0 = kTileCodons * T + kLaneCodons * i;                    // scan index of the lane's first codon, every stream
+    // A stream's eight residues are picked out of its four W words in the order they are stored: codons 0..7 for a forward stream,
+    // 7..0 for a reverse one (its codon index runs against memory order).  Their flag bits 7, 15, .. 63 are the stream's stops, one
+    // 64-bit mask in the same order.  Codons past the end of the stream count as stops: cv = how many of the eight exist
+    // (x / 3 = x * 43 >> 7 for x < 128), the flags of the others are forced, from the top of the mask (forward) or its bottom (reverse).
+    unsigned long long inv_f[3], inv_r[3];
     int cv[3];
 #pragma unroll
     for (int ph = 0; ph < 3; ph++) {
-      cv[ph] = (max(nvalid - ph + 2, 0) * 11) >> 5;
-      inv[ph] = cv[ph] >= 4 ? 0u : (0x80808080u << (8 * cv[ph]));
+      cv[ph] = ((nvalid - ph + 2) * 43) >> 7;
+      inv_f[ph] = cv[ph] >= kLaneCodons ? 0ull : (0x8080808080808080ull << (8 * cv[ph]));
+      inv_r[ph] = cv[ph] >= kLaneCodons ? 0ull : (0x8080808080808080ull >> (8 * cv[ph]));
     }
     // n = 3 q3 + r3 once per tile: the reverse frame of phase ph is (r3 - ph) mod 3 and that stream has q3 - (r3 < ph) codons,
     // without a division per stream
     const int q3 = n / 3, r3 = n - 3 * q3;
     uint2 *const slots = out.slots + tile * out.cap;                     // per tile, not per stream
-    int *const prefix6 = out.prefix + tile * 6, *const suffix6 = out.suffix + tile * 6;
+    int *const prefix6 = &s_sum[qw][0], *const suffix6 = &s_sum[qw][6];
 #pragma unroll
     for (int st = 0; st < 6; st++) {                                      // st: phase 0..2 forward, 3..5 the same phases on the other strand
       const int ph = st % 3;
@@ -195,46 +214,60 @@ __global__ __launch_bounds__(256) void orf_tile_kernel(SeqView dna, OrfTiles til
       const int fr = r3 - ph + (r3 < ph ? 3 : 0);                         // reverse frame of phase ph in this window: (n - ph) mod 3
       const int sf = rev ? 3 + fr : ph;                                   // strand*3 + frame as reported
       const int C = q3 - 1 - (r3 < ph ? 1 : 0);                           // (n - 3 - fr - ph) / 3; reverse stream: codon index j = C - u
-      const int *a = rev ? ar : af;
-      const unsigned pk = (unsigned)a[ph] | ((unsigned)a[ph + 3] << 8) | ((unsigned)a[ph + 6] << 16) | ((unsigned)a[ph + 9] << 24);
-      const unsigned mf = (pk & 0x80808080u) | inv[ph];                   // stops, counting positions past the end of the stream
-      // ---- residues out: one dword per lane when all four codons exist, bytes otherwise
-      const int so = sf * pitch + (rev ? C - u0 - 3 : u0);                // 32-bit offset of the lane's dword in this tile's window
-      if (cv[ph] == 4) {
-        *reinterpret_cast<uint32_t *>(abase + so) = rev ? __builtin_amdgcn_perm(0u, pk & 0x7f7f7f7fu, 0x00010203u) /* bytes reversed */ : (pk & 0x7f7f7f7fu);
-      } else {
-#pragma unroll
-        for (int c = 0; c < 4; c++) if (c < cv[ph]) abase[so + (rev ? 3 - c : c)] = (uint8_t)(a[ph + 3 * c] & 0x7f);
+      // v_perm_b32 picks the forward (even) or the reverse-strand (odd) bytes of four codons out of two W words
+      const unsigned lo = rev ? __builtin_amdgcn_perm(W[4 * ph + 3], W[4 * ph + 2], 0x01030507u) : __builtin_amdgcn_perm(W[4 * ph + 1], W[4 * ph + 0], 0x06040200u);
+      const unsigned hi = rev ? __builtin_amdgcn_perm(W[4 * ph + 1], W[4 * ph + 0], 0x01030507u) : __builtin_amdgcn_perm(W[4 * ph + 3], W[4 * ph + 2], 0x06040200u);
+      // stops in stored order (byte b is codon b of a forward stream, codon 7 - b of a reverse one), counting positions past the end
+      const unsigned long long mf = (((unsigned long long)(hi & 0x80808080u) << 32) | (unsigned long long)(lo & 0x80808080u)) | (rev ? inv_r[ph] : inv_f[ph]);
+      // ---- residues out: two dwords per lane when all eight codons exist
+      const int so = sf * pitch + (rev ? C - u0 - (kLaneCodons - 1) : u0);     // 32-bit offset of the lane's first stored byte in this tile's window
+      uint8_t *const ap = abase + so;
+      const unsigned lo7 = lo & 0x7f7f7f7fu, hi7 = hi & 0x7f7f7f7fu;
+      if (cv[ph] == kLaneCodons) {
+        *reinterpret_cast<uint32_t *>(ap) = lo7;                            // a reverse stream's address has no alignment to speak of
+        *reinterpret_cast<uint32_t *>(ap + 4) = hi7;
+      } else if (cv[ph] > 0) {
+        // a lane that is only partly inside the window: its cv residues are the low bytes of a forward stream's eight and the top
+        // bytes of a reverse stream's, stored as 4 + 2 + 1 bytes (three store instructions at the most, not seven)
+        unsigned long long v = ((unsigned long long)hi7 << 32) | lo7;
+        uint8_t *q = ap;
+        if (rev) { v >>= 8 * (kLaneCodons - cv[ph]); q += kLaneCodons - cv[ph]; }
+        if (cv[ph] & 4) { *reinterpret_cast<uint32_t *>(q) = (uint32_t)v; v >>= 32; q += 4; }
+        if (cv[ph] & 2) { *reinterpret_cast<uint16_t *>(q) = (uint16_t)v; v >>= 16; q += 2; }
+        if (cv[ph] & 1) *q = (uint8_t)v;
       }
-      // ---- length of the stop-free run entering this lane's four codons: scan position of the last stop before them in the tile
-      // (identity INT_MIN: the compiler then folds each step into one v_max_i32_dpp; with another identity it emits mov + dpp-mov + max)
-      const int mine = mf ? 4 * i + ((31 - (int)__clz(mf)) >> 3) : INT_MIN;    // scan position of this lane's last stop
-      const int last = half_excl_max_scan(mine, INT_MIN, i == 0);
+      // ---- length of the stop-free run entering this lane's eight codons: scan position of the last stop before them in the tile
+      const bool any = mf != 0ull;
+      const int b_top = (63 - (int)__clzll((long long)mf)) >> 3, b_bot = (__ffsll((long long)mf) - 1) >> 3;   // highest / lowest flagged byte (any only)
+      const int c_last = rev ? kLaneCodons - 1 - b_bot : b_top;           // the lane's last and first stop, as codons 0..7
+      const int c_first = rev ? kLaneCodons - 1 - b_top : b_bot;
+      const int mine = any ? kLaneCodons * i + c_last : INT_MIN;          // scan position of this lane's last stop
+      const int last = row_excl_max_scan(mine, INT_MIN);
       bool open = last < 0;                                               // no stop in the tile before this lane
-      const int run_in = open ? 4 * i : 4 * i - 1 - last;
+      const int run_in = open ? kLaneCodons * i : kLaneCodons * i - 1 - last;
       auto record = [&](int u_stop, int len) {
-        const int k = atomicAdd(&s_cnt[hw], 1);
+        const int k = atomicAdd(&s_sum[qw][12], 1);
         slots[k] = make_uint2((unsigned)(rev ? C - u_stop + 1 : u_stop - len), (unsigned)len | ((unsigned)sf << 28));
         atomicAdd(&s_hist[orf_bin(len)], 1);
         my_orfs++; my_res += (unsigned)len;
       };
-      if (minlen > 2) {
-        // a run that starts after a stop inside these four codons is at most 2 long: only the chunk's first stop can close an ORF
-        if (mf != 0u) {
-          const int first = (__ffs((int)mf) - 1) >> 3;
-          const int len = run_in + first;
+      if (minlen > kLaneCodons - 2) {
+        // a run that starts after a stop inside these eight codons and ends at another is at most 6 long: only the lane's first
+        // stop can close an ORF
+        if (any) {
+          const int len = run_in + c_first;
           if (open) { if (live) prefix6[sf] = len; }
-          else if (live && len >= minlen) record(u0 + first, len);
+          else if (live && len >= minlen) record(u0 + c_first, len);
         }
         if (live && i == kTileLanes - 1) {
-          suffix6[sf] = mf ? (int)__clz(mf) >> 3 : run_in + 4;             // the run open at the tile's right edge
-          if (open && mf == 0u) prefix6[sf] = kTileCodons;                 // no stop anywhere in the tile
+          suffix6[sf] = any ? kLaneCodons - 1 - c_last : run_in + kLaneCodons;   // the run open at the tile's right edge
+          if (open && !any) prefix6[sf] = kTileCodons;                     // no stop anywhere in the tile
         }
       } else {
         int len = run_in;
 #pragma unroll
-        for (int c = 0; c < 4; c++) {
-          if ((mf >> (8 * c + 7)) & 1u) {
+        for (int c = 0; c < kLaneCodons; c++) {
+          if ((mf >> (8 * (rev ? kLaneCodons - 1 - c : c) + 7)) & 1ull) {
             if (open) { if (live) prefix6[sf] = len; open = false; }
             else if (live && len >= minlen) record(u0 + c, len);
             len = 0;
@@ -246,7 +279,12 @@ __global__ __launch_bounds__(256) void orf_tile_kernel(SeqView dna, OrfTiles til
         }
       }
     }
-    if (live && i == 0) out.cnt[tile] = s_cnt[hw];
+    // every (tile, frame) got its prefix from exactly one lane and its suffix from lane 15; LDS operations of one wave complete in order
+    __builtin_amdgcn_fence(__ATOMIC_ACQ_REL, "wavefront");
+    if (live && i < 13) {
+      int *const dst = i < 6 ? out.prefix + tile * 6 + i : i < 12 ? out.suffix + tile * 6 + (i - 6) : out.cnt + tile;
+      *dst = s_sum[qw][i];
+    }
   }
   if (my_orfs) { atomicAdd(&s_red[0], my_orfs); atomicAdd(&s_red[1], my_res); }
   __syncthreads();
@@ -666,7 +704,7 @@ int launch_orf_scan(bath_hip_ctx *ctx, const bath_hip_seqs *dna, const OrfTables
   // persistent blocks: exactly as many as are resident at once, so that every block gets the same share of the tiles
   int per_cu = 0;
   if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, orf_tile_kernel, 256, 0) != hipSuccess || per_cu < 1) per_cu = 4;
-  const int blocks = (int)std::max<int64_t>(1, std::min<int64_t>((ntiles + 7) / 8, (int64_t)cus * per_cu));
+  const int blocks = (int)std::max<int64_t>(1, std::min<int64_t>((ntiles + 15) / 16, (int64_t)cus * per_cu));
   hipLaunchKernelGGL(orf_tile_kernel, dim3(blocks), dim3(256), 0, ctx->stream, dna->view(), tiles, tabs, out, minlen);
   static const int stitch_env = [] { const char *e = std::getenv("BATH_HIP_STITCH_WAVE"); return e ? std::atoi(e) : -1; }();   // 1 / 0: always / never the wave kernel (tests, A/B)
   const bool long_windows = stitch_env >= 0 ? stitch_env == 1 : ntiles > 32 * dna->n;                   // more than 32 tiles (12 kb) per window on average
