@@ -231,6 +231,9 @@ ABI = {
                                                     _i32p, _i32p, _i32p, C.c_int, _i32p, _i32p, C.c_int, _i32p]),
     "bath_selftest_rng_jump": (C.c_int, [C.c_uint32, C.c_uint64, C.POINTER(C.c_uint32)]),
     "bath_selftest_ens_explog": (C.c_int, [C.c_int, _f32p, _f32p, _f32p]),
+    "bath_selftest_compute_units": (C.c_int, [_vp]),
+    "bath_selftest_compo_terms": (C.c_int, [C.c_int, C.c_float, _f32p]),
+    "bath_selftest_len_sort": (C.c_int, [_vp, C.c_int, _i32p, C.c_int, _i32p, _i32p]),
     "bath_hip_trim": (C.c_int, [_vp]),
     "bath_hip_kernel_times": (C.c_int, [_vp, C.c_int, C.POINTER(KernelTime)]),
     "bath_hip_oprofile_convert": (C.c_int, [_vp, C.POINTER(_Profile), C.POINTER(_vp)]),

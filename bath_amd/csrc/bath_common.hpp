@@ -368,6 +368,7 @@ struct bath_hip_oprofile {
   float *d_rfb = nullptr, *d_tfb = nullptr;   // d_rf / d_tf padded to M+2 nodes (zeros), for the Backward kernel when the tables stay in global memory
   float *d_msc = nullptr, *d_tsc = nullptr;   // log-odds match scores [Kp][M+1] and log transitions [M][8] (p7_pli_computeAliScores_BATH)
   float *d_bias_eo = nullptr;   // [Kp][2] emission odds of the 2-state bias filter HMM for om->compo
+  float *d_compo_terms = nullptr;   // [20][256] bg_f[x] * exp((base_b - s) / scale_b): the local-composition filter's terms by byte score (bath_pipeline.hip)
   // lane-per-target Viterbi kernel tables (bath_viterbi.hip); vit_NR == 0 when the model is too long for it
   int vit_NR = 0, vit_rw_pitch = 0;
   int16_t *d_vit_rw = nullptr; uint32_t *d_vit_tw2 = nullptr; int16_t *d_vit_rank = nullptr;
@@ -387,6 +388,7 @@ struct bath_hip_oprofile {
 // implemented in bath_profile.hip
 namespace bath {
 int build_len_tables(const bath_hip_oprofile *om, int maxL);
+int build_compo_terms(bath_hip_ctx *ctx, bath_hip_oprofile *om);   // bath_pipeline.hip
 void bias_filter_eo(const float *compo, float eo[kKp][2]);
 double gumbel_surv(double x, double mu, double lambda);
 double gumbel_invsurv(double p, double mu, double lambda);

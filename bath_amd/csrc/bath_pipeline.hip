@@ -182,20 +182,101 @@ __device__ __forceinline__ int cand_classify(const Cand &cand, int c, int tjb, c
   return st;
 }
 
-// classify the SSV maxima; undecided targets go to the full-MSV list
-__global__ void classify_kernel(Cand cand, int cand_cap, Counters *__restrict__ ctr, const uint8_t *__restrict__ tjb_tab, MsvConsts mc,
-                                int32_t *__restrict__ todo_msv) {
-  const int ncand = min(ctr->cand_count, cand_cap);
-  for (int c = blockIdx.x * blockDim.x + threadIdx.x; c < ncand; c += gridDim.x * blockDim.x) {
-    if (cand_classify(cand, c, tjb_tab[cand.len[c]], mc) == BATH_ENORESULT) todo_msv[atomicAdd(&ctr->todo_msv, 1)] = c;
+// ---- block-level counting and appending
+// The decision kernels add to members of the one Counters struct and append ids to work lists whose lengths live there too: a
+// few hot addresses, where returning global atomics serialise (~3 ns each on MI355X; the compiler already issues one per wave,
+// not per lane).  A block therefore tallies in LDS -- NS 64-bit sums, and NL lists whose ids wait in LDS at a rank taken from an
+// LDS atomic -- and touches each global address once: one atomicAdd per non-zero sum, and per non-empty list one atomicAdd that
+// reserves the block's range, into which the lanes then copy the waiting ids.  A kernel that strides over its candidates
+// tallies over all of its iterations; the lists alone are written out early when the next iteration might not fit (CAP ids per
+// list, CAP >= 2 * blockDim.x for such a kernel, >= blockDim.x for one without a loop).
+// Every counter keeps its value.  The ORDER of the ids inside a list differs from the per-wave appends this replaces -- which
+// was a race between waves already, and nothing reads a list for its order: the Viterbi stage's length sort scatters the ids
+// again, hit windows are appended by atomics of their own, and the records are sorted by key.
+// tally_reset, tally_lists_full, tally_write_lists and tally_finish hold barriers: every lane of the block calls them, together.
+template <int NL, int NS, int CAP>
+struct BlockTally {
+  int n[NL > 0 ? NL : 1], base[NL > 0 ? NL : 1];
+  unsigned long long sum[NS > 0 ? NS : 1];
+  int32_t ids[NL > 0 ? NL : 1][NL > 0 ? CAP : 1];
+};
+template <int NL, int NS>
+struct TallyOut {                      // where a block's tally goes: the lists with their lengths, the 64-bit counters
+  int32_t *list[NL > 0 ? NL : 1]; int *count[NL > 0 ? NL : 1];
+  unsigned long long *sum[NS > 0 ? NS : 1];
+};
+template <int NL, int NS, int CAP>
+__device__ __forceinline__ void tally_reset(BlockTally<NL, NS, CAP> &t) {
+  if ((int)threadIdx.x < NL) t.n[threadIdx.x] = 0;
+  if ((int)threadIdx.x < NS) t.sum[threadIdx.x] = 0ull;
+  __syncthreads();
+}
+template <int NL, int NS, int CAP>
+__device__ __forceinline__ void tally_add(BlockTally<NL, NS, CAP> &t, int k, unsigned long long v) { atomicAdd(&t.sum[k], v); }
+template <int NL, int NS, int CAP>
+__device__ __forceinline__ void tally_push(BlockTally<NL, NS, CAP> &t, int l, int32_t id) { t.ids[l][atomicAdd(&t.n[l], 1)] = id; }
+// can every lane still push one id to every list?  (the same answer in all lanes)
+template <int NL, int NS, int CAP>
+__device__ __forceinline__ bool tally_lists_full(BlockTally<NL, NS, CAP> &t) {
+  bool full = false;
+  __syncthreads();
+#pragma unroll
+  for (int l = 0; l < NL; l++) full |= t.n[l] > CAP - (int)blockDim.x;
+  __syncthreads();
+  return full;
+}
+template <int NL, int NS, int CAP>
+__device__ __forceinline__ void tally_write_lists(BlockTally<NL, NS, CAP> &t, const TallyOut<NL, NS> &o) {
+  if (NL == 0) return;
+  __syncthreads();
+#pragma unroll
+  for (int l = 0; l < NL; l++) if ((int)threadIdx.x == l && t.n[l] > 0) t.base[l] = atomicAdd(o.count[l], t.n[l]);
+  __syncthreads();
+#pragma unroll
+  for (int l = 0; l < NL; l++) {
+    const int n = t.n[l], b = t.base[l];
+    for (int i = threadIdx.x; i < n; i += blockDim.x) o.list[l][b + i] = t.ids[l][i];
   }
+  __syncthreads();
+  if ((int)threadIdx.x < NL) t.n[threadIdx.x] = 0;
+  __syncthreads();
+}
+template <int NL, int NS, int CAP>
+__device__ __forceinline__ void tally_finish(BlockTally<NL, NS, CAP> &t, const TallyOut<NL, NS> &o) {
+  tally_write_lists(t, o);             // (its first barrier also orders the lanes' tally_add before the reads below)
+  if (NL == 0) __syncthreads();
+#pragma unroll
+  for (int k = 0; k < NS; k++) if ((int)threadIdx.x == k && t.sum[k] != 0ull) atomicAdd(o.sum[k], t.sum[k]);
+}
+
+// classify the SSV maxima; undecided targets go to the full-MSV list
+__global__ __launch_bounds__(256) void classify_kernel(Cand cand, int cand_cap, Counters *__restrict__ ctr, const uint8_t *__restrict__ tjb_tab, MsvConsts mc,
+                                                       int32_t *__restrict__ todo_msv) {
+  __shared__ BlockTally<1, 0, 512> tally;
+  tally_reset(tally);
+  const TallyOut<1, 0> out{{todo_msv}, {&ctr->todo_msv}, {nullptr}};
+  const int ncand = min(ctr->cand_count, cand_cap);
+  for (int c0 = blockIdx.x * blockDim.x; c0 < ncand; c0 += gridDim.x * blockDim.x) {
+    if (tally_lists_full(tally)) tally_write_lists(tally, out);
+    const int c = c0 + threadIdx.x;
+    if (c < ncand && cand_classify(cand, c, tjb_tab[cand.len[c]], mc) == BATH_ENORESULT) tally_push(tally, 0, c);
+  }
+  tally_finish(tally, out);
 }
 
 // MSV P-value (F1), bias filter (F1), then route to Viterbi (P > F2) or SSV windows (P <= F2): p7_pipeline.c:1649-1677
 struct F1Tables { const float *eo, *nullsc, *p1, *lt1, *lt2; };      // the bias filter's emission odds [Kp][2]; by target length: null score, p1, the length corrections
-__device__ __forceinline__ void cand_f1_bias(const Cand &cand, int c, Counters *__restrict__ ctr, const Params &p, const uint8_t *__restrict__ pool, int M,
-                                             const float *s_eo /* the emission odds in LDS */, const F1Tables &t,
-                                             int32_t *__restrict__ todo_vit, int32_t *__restrict__ todo_ssvb) {
+// what cand_f1_bias tallies per block: the lists todo_vit and todo_ssvb, five counters
+enum { F1_TODO_VIT = 0, F1_TODO_SSVB = 1, F1_NL = 2 };
+enum { F1_N_MSV = 0, F1_POS_MSV, F1_N_BIAS, F1_POS_BIAS, F1_RES_VIT, F1_NS };
+__device__ __forceinline__ TallyOut<F1_NL, F1_NS> f1_tally_out(Counters *__restrict__ ctr, int32_t *__restrict__ todo_vit, int32_t *__restrict__ todo_ssvb) {
+  return TallyOut<F1_NL, F1_NS>{{todo_vit, todo_ssvb}, {&ctr->todo_vit, &ctr->todo_ssvb},
+                                {&ctr->n_past_msv, &ctr->pos_past_msv, &ctr->n_past_bias, &ctr->pos_past_bias, &ctr->res_vit}};
+}
+// (a lane may leave this function early: it holds no barrier, and its callers reach tally_finish with every lane of the block)
+template <int CAP>
+__device__ __forceinline__ void cand_f1_bias(const Cand &cand, int c, BlockTally<F1_NL, F1_NS, CAP> &tally, const Params &p, const uint8_t *__restrict__ pool, int M,
+                                             const float *s_eo /* the emission odds in LDS */, const F1Tables &t) {
   const int L = cand.len[c];
   const float usc = cand.usc[c];
   const float nullsc = t.nullsc[L];
@@ -204,7 +285,7 @@ __device__ __forceinline__ void cand_f1_bias(const Cand &cand, int c, Counters *
   double P = d_gumbel_surv(seqsc, p.evparam[0], p.evparam[1]);
   cand.P[c] = P;
   if (P > p.F1) return;
-  atomicAdd(&ctr->n_past_msv, 1ull); atomicAdd(&ctr->pos_past_msv, (unsigned long long)L * 3ull);
+  tally_add(tally, F1_N_MSV, 1ull); tally_add(tally, F1_POS_MSV, (unsigned long long)L * 3ull);
   cand.stage[c] = 1;
   float filtersc = nullsc;
   if (p.do_bias) {
@@ -216,19 +297,26 @@ __device__ __forceinline__ void cand_f1_bias(const Cand &cand, int c, Counters *
     if (P > p.F1) return;
   }
   cand.filtersc[c] = filtersc;
-  atomicAdd(&ctr->n_past_bias, 1ull); atomicAdd(&ctr->pos_past_bias, (unsigned long long)L * 3ull);
+  tally_add(tally, F1_N_BIAS, 1ull); tally_add(tally, F1_POS_BIAS, (unsigned long long)L * 3ull);
   cand.stage[c] = 2;
-  if (P > p.F2) { cand.flags[c] |= FLAG_VIT_RUN; todo_vit[atomicAdd(&ctr->todo_vit, 1)] = c; atomicAdd(&ctr->res_vit, (unsigned long long)L); }
-  else todo_ssvb[atomicAdd(&ctr->todo_ssvb, 1)] = c;
+  if (P > p.F2) { cand.flags[c] |= FLAG_VIT_RUN; tally_push(tally, F1_TODO_VIT, c); tally_add(tally, F1_RES_VIT, (unsigned long long)L); }
+  else tally_push(tally, F1_TODO_SSVB, c);
 }
 
-__global__ void f1_bias_kernel(Cand cand, int cand_cap, Counters *__restrict__ ctr, Params p, const uint8_t *__restrict__ pool, int M, F1Tables t,
-                               int32_t *__restrict__ todo_vit, int32_t *__restrict__ todo_ssvb) {
+__global__ __launch_bounds__(256) void f1_bias_kernel(Cand cand, int cand_cap, Counters *__restrict__ ctr, Params p, const uint8_t *__restrict__ pool, int M, F1Tables t,
+                                                      int32_t *__restrict__ todo_vit, int32_t *__restrict__ todo_ssvb) {
   __shared__ float s_eo[kKp * 2];                          // the filter HMM's emission odds: read once per residue, from LDS
+  __shared__ BlockTally<F1_NL, F1_NS, 512> tally;
   for (int i = threadIdx.x; i < kKp * 2; i += blockDim.x) s_eo[i] = t.eo[i];
-  __syncthreads();
+  tally_reset(tally);
+  const TallyOut<F1_NL, F1_NS> out = f1_tally_out(ctr, todo_vit, todo_ssvb);
   const int ncand = min(ctr->cand_count, cand_cap);
-  for (int c = blockIdx.x * blockDim.x + threadIdx.x; c < ncand; c += gridDim.x * blockDim.x) cand_f1_bias(cand, c, ctr, p, pool, M, s_eo, t, todo_vit, todo_ssvb);
+  for (int c0 = blockIdx.x * blockDim.x; c0 < ncand; c0 += gridDim.x * blockDim.x) {
+    if (tally_lists_full(tally)) tally_write_lists(tally, out);
+    const int c = c0 + threadIdx.x;
+    if (c < ncand) cand_f1_bias(cand, c, tally, p, pool, M, s_eo, t);
+  }
+  tally_finish(tally, out);
 }
 
 // The MSV stage of a large block in one kernel, a lane per candidate: what classify_kernel, msv_lane_kernel and f1_bias_kernel do
@@ -245,6 +333,7 @@ __global__ __launch_bounds__(256, 4) void msv_stage_kernel(Cand cand, int cand_c
                                                            F1Tables t, int32_t *__restrict__ todo_vit, int32_t *__restrict__ todo_ssvb) {
   extern __shared__ __attribute__((aligned(16))) char lds[];
   __shared__ float s_eo[kKp * 2];
+  __shared__ BlockTally<F1_NL, F1_NS, 256> tally;          // a lane has one candidate: at most 256 ids per list
   // Not persistent: the grid covers the candidate buffer, a wave takes the 64 candidates at its place in the list and a block beyond
   // the list leaves at once.  (With a loop over several waves of candidates per wave, the fp64 logarithm's constants and the other
   // invariants of the bias loop are hoisted above the row loop, where the tile leaves no register for them: scratch spills.)
@@ -257,7 +346,7 @@ __global__ __launch_bounds__(256, 4) void msv_stage_kernel(Cand cand, int cand_c
     for (int i = threadIdx.x; i < n32; i += blockDim.x) dst[i] = src[i];
     for (int i = threadIdx.x; i < kKp * 2; i += blockDim.x) s_eo[i] = t.eo[i];
   }
-  __syncthreads();
+  tally_reset(tally);
   const int64_t job = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const bool live = job < ncand;
   const int c = live ? (int)job : 0;
@@ -272,7 +361,8 @@ __global__ __launch_bounds__(256, 4) void msv_stage_kernel(Cand cand, int cand_c
     if (overflow) { cand.usc[c] = INFINITY; cand.msv_status[c] = BATH_ERANGE; }
     else { cand.usc[c] = msv_lane_score(xJ, tjb, mc); cand.msv_status[c] = BATH_OK; }
   }
-  if (live) cand_f1_bias(cand, c, ctr, p, pool, M, s_eo, t, todo_vit, todo_ssvb);
+  if (live) cand_f1_bias(cand, c, tally, p, pool, M, s_eo, t);
+  tally_finish(tally, f1_tally_out(ctr, todo_vit, todo_ssvb));
 }
 
 // p7_SSVFilter_BATH (msvfilter.c:250-427): diagonal windows for strong MSV hits, wave per candidate.
@@ -412,40 +502,53 @@ __device__ void local_compo_finish(float *compo, const float *bgf, float *eo) {
 }
 
 // after Viterbi / SSV windows: F2 test, local-composition re-filter (p7_pipeline.c:1672-1718)
-__global__ void post_vit_kernel(Cand cand, int cand_cap, Counters *__restrict__ ctr, Params p, int32_t *__restrict__ todo_lb, int32_t *__restrict__ todo_fwd) {
+enum { PV_TODO_LB = 0, PV_TODO_FWD = 1, PV_NL = 2 };
+enum { PV_N_VIT = 0, PV_POS_VIT, PV_RES_FWD, PV_NS };
+__global__ __launch_bounds__(256) void post_vit_kernel(Cand cand, int cand_cap, Counters *__restrict__ ctr, Params p, int32_t *__restrict__ todo_lb, int32_t *__restrict__ todo_fwd) {
+  __shared__ BlockTally<PV_NL, PV_NS, 512> tally;
+  tally_reset(tally);
+  const TallyOut<PV_NL, PV_NS> out{{todo_lb, todo_fwd}, {&ctr->todo_lb, &ctr->todo_fwd}, {&ctr->n_past_vit, &ctr->pos_past_vit, &ctr->res_fwd}};
   const int ncand = min(ctr->cand_count, cand_cap);
-  for (int c = blockIdx.x * blockDim.x + threadIdx.x; c < ncand; c += gridDim.x * blockDim.x) {
-    if (cand.stage[c] != 2) continue;
-    const int L = cand.len[c];
-    if (cand.flags[c] & FLAG_VIT_RUN) {
+  for (int c0 = blockIdx.x * blockDim.x; c0 < ncand; c0 += gridDim.x * blockDim.x) {
+    if (tally_lists_full(tally)) tally_write_lists(tally, out);
+    const int c = c0 + threadIdx.x;
+    bool past = c < ncand && cand.stage[c] == 2;           // decide, then fall through: every lane comes round to the barriers above and below
+    if (past && (cand.flags[c] & FLAG_VIT_RUN)) {
       const float seqsc = (float)((double)(cand.vfsc[c] - cand.filtersc[c]) / kLog2);
       const double P = d_gumbel_surv(seqsc, p.evparam[2], p.evparam[3]);
       cand.P[c] = P;
-      if (P > p.F2) { cand.kminmax[2 * c] = 1 << 30; cand.kminmax[2 * c + 1] = 0; continue; }
+      if (P > p.F2) { cand.kminmax[2 * c] = 1 << 30; cand.kminmax[2 * c + 1] = 0; past = false; }
     }
-    atomicAdd(&ctr->n_past_vit, 1ull); atomicAdd(&ctr->pos_past_vit, (unsigned long long)L * 3ull);
+    if (!past) continue;
+    const int L = cand.len[c];
+    tally_add(tally, PV_N_VIT, 1ull); tally_add(tally, PV_POS_VIT, (unsigned long long)L * 3ull);
     if (p.do_bias && cand.kminmax[2 * c] <= cand.kminmax[2 * c + 1]) {
       // the local-composition bias filter (p7_pipeline.c:1688-1712) is ~10^3 times the work of everything else here and only the
       // few per cent of candidates that passed Viterbi with a hit window need it: they go to a list and a dense kernel
       // (post_vit_local_kernel); done in place, every wave of this kernel would walk the long path for one or two of its lanes
       cand.flags[c] |= FLAG_HAS_WIN;
-      todo_lb[atomicAdd(&ctr->todo_lb, 1)] = c;
+      tally_push(tally, PV_TODO_LB, c);
       continue;
     }
     cand.stage[c] = 3;
-    todo_fwd[atomicAdd(&ctr->todo_fwd, 1)] = c; atomicAdd(&ctr->res_fwd, (unsigned long long)L);
+    tally_push(tally, PV_TODO_FWD, c); tally_add(tally, PV_RES_FWD, (unsigned long long)L);
   }
+  tally_finish(tally, out);
 }
 
-// The local-composition bias filter in three dense steps.  (1) compo_terms_kernel, once per call: the 20 x 256 possible terms
+// The local-composition bias filter in three dense steps.  (1) compo_terms_kernel, once per profile (build_compo_terms, when the
+// OProfile is made: its inputs are constants of the model): the 20 x 256 possible terms
 // bg_f[x] * exp((base_b - s) / scale_b) of p7_pli_ComputeLocalCompo (s: a byte score).  (2) local_compo_kernel: three candidates per
 // wave, lanes 20g..20g+19 each add the terms of one residue over the window's nodes (the 20 sums are independent; each still adds in
 // ascending k).  (3) post_vit_local_kernel: a lane per candidate does the serial rest -- normalisation, the 2-state filter HMM
 // over the ORF, the decisions -- with its emission odds in LDS.
+__host__ __device__ __forceinline__ float compo_term(float bg, int base_b, int sc, float scale_b) {
+  const float lo = ((float)base_b - (float)sc) / scale_b;
+  return bg * expf(lo);
+}
 __global__ void compo_terms_kernel(const float *__restrict__ bgf, int base_b, float scale_b, float *__restrict__ terms /* [20][256] */) {
   const int x = blockIdx.x, sc = threadIdx.x;
-  const float lo = ((float)base_b - (float)sc) / scale_b;
-  terms[x * 256 + sc] = bgf[x] * expf(lo);
+  terms[x * 256 + sc] = compo_term(bgf[x], base_b, sc, scale_b);
 }
 
 __global__ __launch_bounds__(64) void local_compo_kernel(Cand cand, const Counters *__restrict__ ctr, int M, const uint8_t *__restrict__ ssv_scores,
@@ -472,8 +575,14 @@ __global__ __launch_bounds__(64) void post_vit_local_kernel(Cand cand, Counters 
                                                             const float *__restrict__ p1_tab, const float *__restrict__ lt1_tab, const float *__restrict__ lt2_tab,
                                                             const int32_t *__restrict__ todo_lb, int32_t *__restrict__ todo_vit2, int32_t *__restrict__ todo_fwd) {
   __shared__ float s_eo[64][kKp * 2 + 1];
+  __shared__ BlockTally<2, 2, 128> tally;                  // lists: todo_vit2, todo_fwd; counters: res_vit, res_fwd
+  tally_reset(tally);
+  const TallyOut<2, 2> out{{todo_vit2, todo_fwd}, {&ctr->todo_vit2, &ctr->todo_fwd}, {&ctr->res_vit, &ctr->res_fwd}};
   const int ntodo = ctr->todo_lb;
-  for (int job = blockIdx.x * blockDim.x + threadIdx.x; job < ntodo; job += gridDim.x * blockDim.x) {
+  for (int job0 = blockIdx.x * blockDim.x; job0 < ntodo; job0 += gridDim.x * blockDim.x) {
+    if (tally_lists_full(tally)) tally_write_lists(tally, out);
+    const int job = job0 + threadIdx.x;
+    if (job >= ntodo) continue;
     const int c = todo_lb[job];
     const int L = cand.len[c];
     const float usc = cand.usc[c];
@@ -493,7 +602,7 @@ __global__ __launch_bounds__(64) void post_vit_local_kernel(Cand cand, Counters 
         const float seqsc = (float)((double)(usc - filtersc) / kLog2);
         const double P = d_gumbel_surv(seqsc, p.evparam[0], p.evparam[1]);
         cand.P[c] = P;
-        if (P > p.F2) { cand.stage[c] = 5; todo_vit2[atomicAdd(&ctr->todo_vit2, 1)] = c; atomicAdd(&ctr->res_vit, (unsigned long long)L); to_fwd = false; }
+        if (P > p.F2) { cand.stage[c] = 5; tally_push(tally, 0, c); tally_add(tally, 0, (unsigned long long)L); to_fwd = false; }
       } else {
         const float seqsc = (float)((double)(vfsc - filtersc) / kLog2);
         const double P = d_gumbel_surv(seqsc, p.evparam[2], p.evparam[3]);
@@ -501,26 +610,37 @@ __global__ __launch_bounds__(64) void post_vit_local_kernel(Cand cand, Counters 
         if (P > p.F2) to_fwd = false;                      // rejected; stays at stage 2 (the reference has already counted it past Vit)
       }
     }
-    if (to_fwd) { cand.stage[c] = 3; todo_fwd[atomicAdd(&ctr->todo_fwd, 1)] = c; atomicAdd(&ctr->res_fwd, (unsigned long long)L); }
+    if (to_fwd) { cand.stage[c] = 3; tally_push(tally, 1, c); tally_add(tally, 1, (unsigned long long)L); }
   }
+  tally_finish(tally, out);
 }
 
 // plain p7_ViterbiFilter re-run for candidates whose local filter score demanded it (p7_pipeline.c:1703-1708)
-__global__ void post_vit2_kernel(Cand cand, Counters *__restrict__ ctr, Params p, const int32_t *__restrict__ todo_vit2, int32_t *__restrict__ todo_fwd) {
+__global__ __launch_bounds__(256) void post_vit2_kernel(Cand cand, Counters *__restrict__ ctr, Params p, const int32_t *__restrict__ todo_vit2, int32_t *__restrict__ todo_fwd) {
+  __shared__ BlockTally<1, 1, 512> tally;                  // list: todo_fwd; counter: res_fwd
+  tally_reset(tally);
+  const TallyOut<1, 1> out{{todo_fwd}, {&ctr->todo_fwd}, {&ctr->res_fwd}};
   const int ntodo = ctr->todo_vit2;
-  for (int job = blockIdx.x * blockDim.x + threadIdx.x; job < ntodo; job += gridDim.x * blockDim.x) {
+  for (int job0 = blockIdx.x * blockDim.x; job0 < ntodo; job0 += gridDim.x * blockDim.x) {
+    if (tally_lists_full(tally)) tally_write_lists(tally, out);
+    const int job = job0 + threadIdx.x;
+    if (job >= ntodo) continue;
     const int c = todo_vit2[job];
     const float seqsc = (float)((double)(cand.vfsc[c] - cand.filtersc[c]) / kLog2);
     const double P = d_gumbel_surv(seqsc, p.evparam[2], p.evparam[3]);
     cand.P[c] = P;
     if (P > p.F2) { cand.stage[c] = 2; continue; }
     cand.stage[c] = 3;
-    todo_fwd[atomicAdd(&ctr->todo_fwd, 1)] = c; atomicAdd(&ctr->res_fwd, (unsigned long long)cand.len[c]);
+    tally_push(tally, 0, c); tally_add(tally, 0, (unsigned long long)cand.len[c]);
   }
+  tally_finish(tally, out);
 }
 
 // Forward P-value: F3, or F4 in the frameshift pipeline (p7_pipeline.c:1735-1738, 1779-1785)
-__global__ void final_kernel(Cand cand, Counters *__restrict__ ctr, Params p, const int32_t *__restrict__ todo_fwd) {
+__global__ __launch_bounds__(256) void final_kernel(Cand cand, Counters *__restrict__ ctr, Params p, const int32_t *__restrict__ todo_fwd) {
+  __shared__ BlockTally<0, 2, 1> tally;                    // counters: n_past_fwd, pos_past_fwd; no list, so no barrier inside the loop
+  tally_reset(tally);
+  const TallyOut<0, 2> out{{nullptr}, {nullptr}, {&ctr->n_past_fwd, &ctr->pos_past_fwd}};
   const int ntodo = ctr->todo_fwd;
   for (int job = blockIdx.x * blockDim.x + threadIdx.x; job < ntodo; job += gridDim.x * blockDim.x) {
     const int c = todo_fwd[job];
@@ -529,9 +649,10 @@ __global__ void final_kernel(Cand cand, Counters *__restrict__ ctr, Params p, co
     cand.P[c] = P;
     if (P > (p.fs_pipe ? p.F4 : p.F3)) continue;
     cand.stage[c] = 4;
-    atomicAdd(&ctr->n_past_fwd, 1ull);
-    if (!p.fs_pipe) atomicAdd(&ctr->pos_past_fwd, (unsigned long long)cand.len[c] * 3ull);
+    tally_add(tally, 0, 1ull);
+    if (!p.fs_pipe) tally_add(tally, 1, (unsigned long long)cand.len[c] * 3ull);
   }
+  tally_finish(tally, out);
 }
 
 // wave-per-candidate kernels take their work list length from device memory
@@ -599,6 +720,18 @@ static int ensure_emit_table(bath_hip_ctx *ctx, const bath_hip_oprofile *om, dou
   return BATH_OK;
 }
 
+// The local-composition filter's term table of a new profile (bath_profile.hip calls this once, before anything shares the
+// profile): compo_terms_kernel fills it, so that its floats are the device's own expf, as when the kernel ran in every call.
+int build_compo_terms(bath_hip_ctx *ctx, bath_hip_oprofile *om) {
+  BATH_HIP_TRY(ctx, hipMalloc((void **)&om->d_compo_terms, (size_t)(20 * 256 + 20) * sizeof(float) + 64));
+  float *d_bgf = om->d_compo_terms + 20 * 256;
+  BATH_HIP_TRY(ctx, hipMemcpyAsync(d_bgf, kAminoBg, 20 * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+  hipLaunchKernelGGL(compo_terms_kernel, dim3(20), dim3(256), 0, ctx->stream, d_bgf, (int)om->base_b, om->scale_b, om->d_compo_terms);
+  BATH_HIP_TRY(ctx, hipGetLastError());
+  BATH_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  return BATH_OK;
+}
+
 static int wave_grid_blocks(bath_hip_ctx *ctx) { return ctx->prop.multiProcessorCount * 8; }
 
 struct PipelineWork {
@@ -644,6 +777,14 @@ static size_t layout(PipelineWork &w, char *base, int cap, int win_cap) {
 }
 
 }  // namespace bath
+
+// Self-test hook (host only, no GPU): the 20 x 256 term table by the host build of compo_term, the function compo_terms_kernel compiles.
+extern "C" int bath_selftest_compo_terms(int base_b, float scale_b, float *terms) {
+  if (!terms || !(scale_b > 0.f)) return BATH_EINVAL;
+  for (int x = 0; x < 20; x++)
+    for (int sc = 0; sc < 256; sc++) terms[x * 256 + sc] = bath::compo_term(kAminoBg[x], base_b, sc, scale_b);
+  return BATH_OK;
+}
 
 extern "C" void bath_pipeline_params_default(bath_pipeline_params *p, int fs_pipe) {   // p7_pipeline.c:219-222, bathsearch.c:104
   p->F1 = 0.02; p->F2 = 1e-3; p->F3 = 1e-5; p->F4 = 5e-4;
@@ -889,11 +1030,10 @@ static int run_filters(bath_hip_ctx *ctx, const bath_hip_oprofile *om, const bat
     // 5. F2, local composition re-filter, optional plain Viterbi re-run
     hipLaunchKernelGGL(post_vit_kernel, dim3(dec_blocks), dim3(256), 0, ctx->stream, W.cand, W.cand_cap, W.ctr, P, W.todo_msv /* free by now */, W.todo_fwd);
     if (P.do_bias) {
-      DevBuf &b_compo = ctx->scratch[36];                                       // 20 x 256 terms, then 20 sums per candidate
-      BATH_HIP_TRY(ctx, b_compo.reserve((size_t)20 * 256 * 4 + (size_t)W.cand_cap * 20 * 4 + 256));
-      float *d_terms = b_compo.as<float>(), *d_compo = d_terms + 20 * 256;
-      hipLaunchKernelGGL(compo_terms_kernel, dim3(20), dim3(256), 0, ctx->stream, d_bgf, (int)om->base_b, om->scale_b, d_terms);
-      hipLaunchKernelGGL(local_compo_kernel, dim3(16384), dim3(64), 0, ctx->stream, W.cand, W.ctr, M, d_ssvsc, d_terms, W.todo_msv, d_compo);
+      DevBuf &b_compo = ctx->scratch[36];                                       // 20 sums per candidate (the 20 x 256 terms are the profile's)
+      BATH_HIP_TRY(ctx, b_compo.reserve((size_t)W.cand_cap * 20 * 4 + 256));
+      float *d_compo = b_compo.as<float>();
+      hipLaunchKernelGGL(local_compo_kernel, dim3(16384), dim3(64), 0, ctx->stream, W.cand, W.ctr, M, d_ssvsc, om->d_compo_terms, W.todo_msv, d_compo);
       hipLaunchKernelGGL(post_vit_local_kernel, dim3(std::max(1, dec_blocks)), dim3(64), 0, ctx->stream, W.cand, W.ctr, P, W.pool, M, d_bgf, d_compo,
                          om->lt.d_p1, om->lt.d_lt1, om->lt.d_lt2, W.todo_msv, W.todo_vit2, W.todo_fwd);
     }

@@ -289,12 +289,14 @@ extern "C" int bath_hip_fs_ensemble_counters(bath_hip_ctx *ctx, int64_t *bound_f
   return BATH_OK;
 }
 
+extern "C" int bath_selftest_compute_units(const bath_hip_ctx *ctx) { return ctx ? ctx->prop.multiProcessorCount : 0; }
+
 // ------------------------------------------------------------------------------------------ oprofile
 
 extern "C" void bath_hip_oprofile_destroy(bath_hip_oprofile *om) {
   if (!om) return;
   for (void *p : {(void *)om->d_emit, (void *)om->d_ssv, (void *)om->d_msv, (void *)om->d_rb, (void *)om->d_rw, (void *)om->d_tw, (void *)om->d_rf, (void *)om->d_tf,
-                  (void *)om->d_bias_eo, (void *)om->d_vit_rw, (void *)om->d_vit_tw2, (void *)om->d_vit_rank, (void *)om->lt.d_tjb, (void *)om->lt.d_xwmove, (void *)om->lt.d_pmove,
+                  (void *)om->d_bias_eo, (void *)om->d_compo_terms, (void *)om->d_vit_rw, (void *)om->d_vit_tw2, (void *)om->d_vit_rank, (void *)om->lt.d_tjb, (void *)om->lt.d_xwmove, (void *)om->lt.d_pmove,
                   (void *)om->lt.d_nullsc, (void *)om->lt.d_lt1, (void *)om->lt.d_lt2, (void *)om->lt.d_p1, (void *)om->d_cons, (void *)om->d_msc, (void *)om->d_tsc, (void *)om->d_rfb, (void *)om->d_tfb})
     if (p) (void)hipFree(p);
   for (void *p : om->retired) (void)hipFree(p);
@@ -510,7 +512,8 @@ extern "C" int bath_hip_oprofile_convert(bath_hip_ctx *ctx, const bath_profile *
     BATH_HIP_TRY(ctx, upload(&om->d_bias_eo, &eo[0][0], (size_t)kKp * 2, ctx->stream));
   }
   BATH_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  int st = om->ensure_len_tables(4096);
+  int st = bath::build_compo_terms(ctx, om);
+  if (st == BATH_OK) st = om->ensure_len_tables(4096);
   if (st != BATH_OK) { bath_hip_oprofile_destroy(om); return st; }
   *ret = om;
   return BATH_OK;

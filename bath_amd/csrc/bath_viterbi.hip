@@ -238,16 +238,25 @@ __global__ __launch_bounds__(256) void len_hist_kernel(const int32_t *__restrict
   __syncthreads();
   for (int i = threadIdx.x; i < kLenBins; i += blockDim.x) if (s_cnt[i]) atomicAdd(&hist[i], s_cnt[i]);
 }
-__global__ void len_scan_kernel(int *__restrict__ hist /* in: counts, out: start offsets; longest first */) {
-  __shared__ int tmp[kLenBins];
-  for (int i = threadIdx.x; i < kLenBins; i += blockDim.x) tmp[i] = hist[i];
+// One block of 256 threads, each owning 8 consecutive bins in longest-first order (as orf_scan_bins, bath_orfs.hip): a scan by
+// shuffles within a wave and four wave sums in LDS, not one lane's walk of the 2048 bins in front of the Viterbi kernel.
+__global__ __launch_bounds__(256) void len_scan_kernel(int *__restrict__ hist /* in: counts, out: start offsets; longest first */) {
+  constexpr int kPer = kLenBins / 256;
+  __shared__ int s_wsum[4];
+  const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+  int c[kPer], sum = 0;
+#pragma unroll
+  for (int k = 0; k < kPer; k++) { c[k] = hist[kLenBins - 1 - (kPer * tid + k)]; sum += c[k]; }
+  int x = sum;
+#pragma unroll
+  for (int d = 1; d < 64; d <<= 1) { const int y = __shfl_up(x, d, 64); if (lane >= d) x += y; }
+  if (lane == 63) s_wsum[wv] = x;
   __syncthreads();
-  if (threadIdx.x == 0) {
-    int run = 0;
-    for (int b = kLenBins - 1; b >= 0; b--) { const int cnt = tmp[b]; tmp[b] = run; run += cnt; }
-  }
-  __syncthreads();
-  for (int i = threadIdx.x; i < kLenBins; i += blockDim.x) hist[i] = tmp[i];
+  int run = x - sum;
+#pragma unroll
+  for (int u = 0; u < 4; u++) run += u < wv ? s_wsum[u] : 0;
+#pragma unroll
+  for (int k = 0; k < kPer; k++) { hist[kLenBins - 1 - (kPer * tid + k)] = run; run += c[k]; }   // (a thread reads its 8 bins before it writes them; no other thread touches them)
 }
 __global__ __launch_bounds__(256) void len_scatter_kernel(const int32_t *__restrict__ todo, const int *__restrict__ ntodo_dev, const int32_t *__restrict__ len,
                                                           int *__restrict__ cursor, int32_t *__restrict__ sorted) {
@@ -278,6 +287,30 @@ int launch_len_sort(bath_hip_ctx *ctx, const int32_t *d_todo, const int *d_ntodo
   hipLaunchKernelGGL(len_scatter_kernel, dim3(256), dim3(256), 0, ctx->stream, d_todo, d_ntodo, d_len, d_bins, d_sorted);
   BATH_HIP_TRY(ctx, hipGetLastError());
   return BATH_OK;
+}
+
+// Self-test hook: the length sort alone.  lens[n]: the lengths of targets 0..n-1, all of them on the work list; sorted[n]: the list
+// longest first (targets of one bin in any order); *n_longer: what len_sort_count_longer(T) points at after the sort.
+extern "C" int bath_selftest_len_sort(bath_hip_ctx *ctx, int n, const int32_t *lens, int T, int32_t *sorted, int32_t *n_longer) {
+  if (!ctx || n < 0 || (n > 0 && (!lens || !sorted)) || !n_longer) return BATH_EINVAL;
+  BATH_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  const size_t m = (size_t)std::max(n, 1);
+  int32_t *d = nullptr;                                   // lens[m] | todo[m] | sorted[m] | bins[kLenBins] | count
+  BATH_HIP_TRY(ctx, hipMalloc((void **)&d, (3 * m + kLenBins + 1) * sizeof(int32_t)));
+  int32_t *d_len = d, *d_todo = d + m, *d_sorted = d + 2 * m, *d_bins = d + 3 * m, *d_n = d_bins + kLenBins;
+  std::vector<int32_t> todo(m);
+  for (size_t i = 0; i < m; i++) todo[i] = (int32_t)i;
+  hipError_t e = hipSuccess;
+  if (n > 0) e = hipMemcpy(d_len, lens, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(d_todo, todo.data(), m * sizeof(int32_t), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(d_n, &n, sizeof(int32_t), hipMemcpyHostToDevice);
+  int st = e == hipSuccess ? launch_len_sort(ctx, d_todo, d_n, d_len, d_bins, d_sorted) : BATH_EFAIL;
+  if (st == BATH_OK) e = hipStreamSynchronize(ctx->stream);
+  if (st == BATH_OK && e == hipSuccess && n > 0) e = hipMemcpy(sorted, d_sorted, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost);
+  if (st == BATH_OK && e == hipSuccess) e = hipMemcpy(n_longer, len_sort_count_longer(d_bins, T), sizeof(int32_t), hipMemcpyDeviceToHost);
+  (void)hipFree(d);
+  if (st == BATH_OK && e != hipSuccess) { ctx->set_error(std::string("bath_selftest_len_sort: ") + hipGetErrorString(e)); st = BATH_EFAIL; }
+  return st;
 }
 
 int launch_vit_lane(bath_hip_ctx *ctx, const bath_hip_oprofile *om, SeqView v, const int32_t *d_todo, int64_t ntodo, const int *ntodo_dev,

@@ -917,7 +917,11 @@ int bath_selftest_std_ensemble(int mode, int M, const float *tf, const float *rf
 int bath_selftest_std_ens_walk(int M, const float *tf, float pmove, float tEL, float tEM, int Lr, const float *fwd, const float *fx, uint32_t rng_state,
                                int32_t *status, int32_t *seg, int max_seg, int32_t *n_seg);
 int bath_selftest_rng_jump(uint32_t seed, uint64_t n, uint32_t *state);   /* the generator's state n steps after seeding, by jump-ahead: value n - 1 of bath_selftest_rng_stream is state / 2^32 */
-int bath_selftest_ens_explog(int n, const float *x, float *e, float *l);  /* the stream modes' own expf / logf (host build of the source the kernel compiles); either output may be NULL */
+int bath_selftest_compo_terms(int base_b, float scale_b, float *terms /* [20][256] */);   /* the local-composition filter's term table bg_f[x] * expf((base_b - s) / scale_b), by the host build of the function the profile's kernel compiles */
+/* (needs the GPU) the cascade's counting sort of a work list by length: targets 0..n-1 of lengths lens[], sorted[n] longest first (ties in any order), *n_longer: the number of targets longer than T */
+int bath_selftest_len_sort(bath_hip_ctx *ctx, int n, const int32_t *lens, int T, int32_t *sorted, int32_t *n_longer);
+int bath_selftest_compute_units(const bath_hip_ctx *ctx);   /* the device's compute units: the cascade sizes its decision kernels' grids by them (4 blocks of 256 threads each), and a test its blocks by that */
+int bath_selftest_ens_explog(int n,const float *x, float *e, float *l);  /* the stream modes' own expf / logf (host build of the source the kernel compiles); either output may be NULL */
 
 #ifdef __cplusplus
 }
