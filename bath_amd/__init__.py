@@ -234,6 +234,8 @@ ABI = {
     "bath_selftest_compute_units": (C.c_int, [_vp]),
     "bath_selftest_compo_terms": (C.c_int, [C.c_int, C.c_float, _f32p]),
     "bath_selftest_len_sort": (C.c_int, [_vp, C.c_int, _i32p, C.c_int, _i32p, _i32p]),
+    "bath_selftest_fs_windows": (C.c_int, [_vp, _vp, _vp, _vp, C.c_double, C.c_int, C.c_int, _vp, C.c_int, C.c_int, _vp, _vp, _vp, _i32p, _i64p, _i32p, _vp]),
+    "bath_selftest_fs_decide": (C.c_int, [_vp, _vp, _vp, C.c_int, _f32p, _f32p, C.c_int, C.c_int, C.c_double, C.c_int]),
     "bath_hip_trim": (C.c_int, [_vp]),
     "bath_hip_kernel_times": (C.c_int, [_vp, C.c_int, C.POINTER(KernelTime)]),
     "bath_hip_oprofile_convert": (C.c_int, [_vp, C.POINTER(_Profile), C.POINTER(_vp)]),
@@ -1617,6 +1619,57 @@ def fs_ensemble_serial(M, tsc, xNL, xNM, xE, ireg, Lr, fwd, fx, seed=42):
     if st != OK:
         raise BathError("fs_ensemble_serial failed (%d)" % st)
     return [tuple(int(v) for v in e) for e in env[:n.value]]
+
+
+class FsLane(C.Structure):
+    """bath_fs_lane: one cascade lane's survivor lists for fs_windows_selftest."""
+    _fields_ = [("cands", C.c_void_p), ("wins", C.c_void_p), ("n_c", C.c_int32), ("n_w", C.c_int32), ("cand_base", C.c_int32),
+                ("first_window", C.c_int64), ("dpool", C.c_int64)]
+
+
+FS_CAND_DTYPE = np.dtype([("window", "<i8"), ("aa_off", "<i8"), ("P", "<f8"), ("cand", "<i4"), ("sf", "<i4"), ("startj", "<i4"), ("len", "<i4"),
+                          ("fwdsc", "<f4"), ("nullsc", "<f4"), ("fxoff", "<i8")], align=True)                       # bath_fs_cand
+FS_HITWIN_DTYPE = np.dtype([("cand", "<i4"), ("n", "<i4"), ("k", "<i4"), ("length", "<i4"), ("score", "<f4")], align=True)   # bath_fs_hitwin
+FS_ORF_DTYPE = np.dtype([("w", "<i8"), ("aa_off", "<i8"), ("P", "<f8"), ("cand", "<i4"), ("strand", "<i4"), ("start", "<i4"), ("end", "<i4"), ("n", "<i4"),
+                         ("fwd_null", "<f4"), ("wb", "<i4"), ("we", "<i4"), ("dw_n", "<i4"), ("dw_len", "<i4"), ("dw_k", "<i4"), ("kmin", "<i4"), ("kmax", "<i4"),
+                         ("g0", "<i4"), ("g1", "<i4"), ("pad_", "<i4")], align=True)                                 # bath_fs_orf
+FS_WINDESC_DTYPE = np.dtype([("src_off", "<i8"), ("dst_off", "<i8"), ("seq_n", "<i4"), ("start", "<i4"), ("len", "<i4"), ("strand", "<i4"),
+                             ("kmin", "<i4"), ("kmax", "<i4")], align=True)                                          # bath_fs_windesc
+
+
+def fs_windows_selftest(ctx, om, om_fs3, dna, lanes, nc_total, F3=1e-5, std_pipe=1, driver=0):
+    """bath_selftest_fs_windows.  lanes: list of (cands FS_CAND_DTYPE[], wins FS_HITWIN_DTYPE[], cand_base, first_window, dpool).
+    Returns (status, None) when the build hands the block back or fails, else (OK, dict): n_orfs, nw, maxlen, pool_bytes, total, orfs
+    (FS_ORF_DTYPE), windows (bath_fs_window records), grp [nw][2], voff, vlen, desc (FS_WINDESC_DTYPE)."""
+    keep, arr = [], (FsLane * max(len(lanes), 1))()
+    n = 0
+    for k, (cands, wins, cand_base, first_window, dpool) in enumerate(lanes):
+        cands, wins = np.ascontiguousarray(cands, FS_CAND_DTYPE), np.ascontiguousarray(wins, FS_HITWIN_DTYPE)
+        keep += [cands, wins]
+        arr[k] = FsLane(cands.ctypes.data if len(cands) else None, wins.ctypes.data if len(wins) else None, len(cands), len(wins), cand_base, first_window, dpool)
+        n += len(cands)
+    m = max(n, 1)
+    hdr = np.zeros(6, np.int64)                        # bath_fs_winbuild: 4 int32, 2 int64
+    orfs, windows = np.zeros(m, FS_ORF_DTYPE), np.zeros(m, _np_dtype(FsWindow))
+    grp, voff, vlen, desc = np.zeros((m, 2), np.int32), np.zeros(m, np.int64), np.zeros(m, np.int32), np.zeros(m, FS_WINDESC_DTYPE)
+    st = lib().bath_selftest_fs_windows(ctx._h, om._h, om_fs3._h, dna._h, F3, std_pipe, driver, C.addressof(arr), len(lanes), nc_total, hdr.ctypes.data,
+                                        orfs.ctypes.data, windows.ctypes.data, grp.ctypes.data_as(_i32p), _i64(voff), vlen.ctypes.data_as(_i32p), desc.ctypes.data)
+    if st == ENORESULT:
+        return st, None
+    ctx._check(st, "selftest_fs_windows")
+    h32 = hdr.view(np.int32)
+    n_orfs, nw = int(h32[0]), int(h32[1])
+    return st, {"n_orfs": n_orfs, "nw": nw, "maxlen": int(h32[2]), "pool_bytes": int(hdr[2]), "total": int(hdr[3]), "orfs": orfs[:n_orfs],
+                "windows": windows[:nw], "grp": grp[:nw], "voff": voff[:nw], "vlen": vlen[:nw], "desc": desc[:nw]}
+
+
+def fs_decide_selftest(ctx, om_fs3, records, bias, fsc, do_biasfilter=1, std_pipe=1, F3=1e-5, driver=0):
+    """bath_selftest_fs_decide: a copy of records (bath_fs_window records as a build leaves them) completed by the branch decision."""
+    rec = np.ascontiguousarray(records, _np_dtype(FsWindow)).copy()
+    bias, fsc = np.ascontiguousarray(bias, np.float32), np.ascontiguousarray(fsc, np.float32)
+    assert bias.shape == (len(rec), 2, 3) and fsc.shape == (len(rec),)
+    ctx._check(lib().bath_selftest_fs_decide(ctx._h, om_fs3._h, rec.ctypes.data, len(rec), _f32(bias), _f32(fsc), do_biasfilter, std_pipe, F3, driver), "selftest_fs_decide")
+    return rec
 
 
 def rng_jump(seed, n):

@@ -189,7 +189,8 @@ struct bath_hip_ctx {
   std::string err;
   void set_error(const std::string &m) { err = m; }
   // scratch owned by the context (reused across calls)
-  bath::DevBuf scratch[62];             // [50]-[52]: the device-side DNA-window builder (bath_fs_windows.hip); [59]-[61]: the standard branch's device ensemble
+  std::vector<float> fsw_len_terms;     // the branch decision's length terms by window length / 3, two floats each, as uploaded to scratch[62] (bath_fs_windows.hip)
+  bath::DevBuf scratch[63];             // [50]-[52], [62]: the device-side DNA-window builder and decision (bath_fs_windows.hip); [59]-[61]: the standard branch's device ensemble
                                         // (its regions' Forward matrices; job list + start states up; statuses, segments, path codes down)
   // page-locked staging for small tables a launch uploads (job order, batch starts, offsets): an asynchronous copy from here needs
   // no synchronize before the local it was built in goes away.  One slot per call site; a site is reused by its context only

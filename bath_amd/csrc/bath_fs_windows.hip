@@ -16,7 +16,8 @@
 //               reference's order, P_min, P_tot (:1376-1415, :1457)
 //     layout    the pool offsets of the windows' copies and the sequence-block view the parsers read
 //   fs_build_windows_host     the fallback for inputs the kernels do not take (more than 32768 surviving ORFs or 65536 hit windows
-//     in a block, more than 16 cascade lanes, more than 1024 surviving ORFs on one strand of one sequence; BATH_HIP_FS_WINDOWS_HOST=1
+//     in a block, more than 16 cascade lanes, more than 1024 surviving ORFs on one strand of one sequence, a hit window beyond what the
+//     kernels' key holds: hit_key_fits; BATH_HIP_FS_WINDOWS_HOST=1
 //     sends every block here): the same steps as loops over the same rules, from the survivor lists fetched to the host, the
 //     (sequence, strand) groups spread over up to four threads
 // Both leave the same product (FsWinBuild): the ordered ORFs, the windows' records, gather descriptors, pool offsets and lengths, on
@@ -25,6 +26,7 @@
 // completed records once, or a host loop with libm's exp / log for a block of the host build.
 #include <algorithm>
 #include <cmath>
+#include <cstddef>
 #include <cstdint>
 #include <cstdlib>
 #include <cstring>
@@ -163,21 +165,26 @@ __host__ __device__ inline void fsw_summarize(const FsOrfDev *orfs, int g0, int 
 
 // p7_pipeline.c:1425-1465 for one window: null score (p7_bg_fs_NullOne), bias filter score (p7_bg_fs_FilterScore: the three frames'
 // Forward scores of the 2-state filter HMM from fs_bias_kernel, <bias>[2][3], summed with the table, plus the length term), Forward
-// score -> P-values -> branch
-template <class LogSum>
-__host__ __device__ inline void fsw_decide(bath_fs_window &r, const float *bias, float fwdsc, LogSum logsum, int do_biasfilter, int std_pipe, double F3, double tau3, double lambda) {
-  const double kLn2 = 0.69314718055994529;
-  const int L3 = r.length / 3;
+// score -> P-values -> branch.  <lt>: the two terms that depend on the window's length alone, from the host's libm on either path
+// (fsw_len_terms; the kernel looks them up, as the cascade's kernels look up theirs: the device's logf is not libm's to the last bit, and
+// L3 * logf(p1) carries that bit into the filter score and the P-value)
+struct FswLen { float null_frame, filt; };
+inline FswLen fsw_len_terms(int L3) {
   const float p1 = (float)L3 / (float)(L3 + 1);
-  const float per_frame = (float)((float)L3 * log((double)p1) + log(1. - p1));                        // p7_bg_fs_NullOne, p7_bg.c:380
-  r.nullsc = (float)(per_frame + log(3.0));
+  return FswLen{(float)((float)L3 * std::log((double)p1) + std::log(1. - p1)),                         // p7_bg_fs_NullOne, p7_bg.c:380
+                (float)L3 * logf(p1) + logf((float)(1. - p1))};                                        // p7_bg.c:561
+}
+template <class LogSum>
+__host__ __device__ inline void fsw_decide(bath_fs_window &r, const float *bias, float fwdsc, const FswLen lt, LogSum logsum, int do_biasfilter, int std_pipe, double F3, double tau3, double lambda) {
+  const double kLn2 = 0.69314718055994529, kLn3 = 1.0986122886681098;
+  r.nullsc = (float)(lt.null_frame + kLn3);
   if (do_biasfilter) {
     float f2[2];
     for (int pass = 0; pass < 2; pass++) {
       const float *b = &bias[pass * 3];
       float sum = -INFINITY;
       for (int f = 0; f < 3; f++) sum = logsum(sum, b[f]);
-      f2[pass] = (float)((double)sum + ((double)((float)L3 * logf(p1) + logf((float)(1. - p1))) + log(3.0)));   // p7_bg.c:561
+      f2[pass] = (float)((double)sum + ((double)lt.filt + kLn3));                                      // p7_bg.c:561
     }
     r.filtersc = f2[0];
     if (r.k_min <= r.k_max && f2[1] > r.filtersc) r.filtersc = f2[1];                                  // :1432-1440
@@ -244,19 +251,26 @@ __global__ void fsw_slot_kernel(const FsOrfDev *__restrict__ orfs, int n, int32_
   if (s < n) slot_of[orfs[s].cand] = s;
 }
 
-// a hit window's rank among its ORF's windows as one integer: highest score first, then the longest, then the leftmost (:486-495)
+// a hit window's rank among its ORF's windows as one integer: highest score first, then the longest, then the leftmost (:486-495).
+// The key holds 12 bits of length and 20 bits of start, and the second pass 15 bits of k: hit_key_fits says whether a window fits
+// (a block with one that does not goes to the host path).
+__host__ __device__ __forceinline__ bool hit_key_fits(const WindowRec &x) { return (uint32_t)x.length <= 0xfffu && (uint32_t)x.n <= 0xfffffu && (uint32_t)x.k <= 0x7fffu; }
 __device__ __forceinline__ unsigned long long hit_key(const WindowRec &x) {
   uint32_t u = __float_as_uint(x.score);
   u = (u & 0x80000000u) ? ~u : (u | 0x80000000u);                     // floats in their order as unsigned integers
   return ((unsigned long long)u << 32) | ((unsigned long long)((uint32_t)x.length & 0xfffu) << 20) | (unsigned long long)(0xfffffu - ((uint32_t)x.n & 0xfffffu));
 }
-// per hit window, pass 1: the best key and k_min / k_max of its ORF; pass 2: among the windows that hold the best key, the first
-__global__ void fsw_hits1_kernel(const WindowRec *__restrict__ wins, int nhw, const int32_t *__restrict__ slot_of, unsigned long long *__restrict__ best_key, FsOrfDev *__restrict__ orfs) {
+// per hit window, pass 1: the best key and k_min / k_max of its ORF; pass 2: among the windows that hold the best key (equal score,
+// length and start) the one with the smallest k, whatever order the select kernels appended them in: orfs[s].wb = k << 16 | index
+// (fsw_orf_kernel takes the index out; records equal in k as well are interchangeable)
+__global__ void fsw_hits1_kernel(const WindowRec *__restrict__ wins, int nhw, const int32_t *__restrict__ slot_of, unsigned long long *__restrict__ best_key, FsOrfDev *__restrict__ orfs,
+                                 int *__restrict__ flags) {
   const int t = blockIdx.x * blockDim.x + threadIdx.x;
   if (t >= nhw) return;
   const WindowRec x = wins[t];
   const int s = slot_of[x.cand];
   if (s < 0) return;
+  if (!hit_key_fits(x)) { atomicOr(flags, 1); return; }                 // the host path takes such a block
   atomicMax(&best_key[s], hit_key(x));
   atomicMin(&orfs[s].kmin, x.k - x.length + 1);
   atomicMax(&orfs[s].kmax, x.k);
@@ -266,8 +280,8 @@ __global__ void fsw_hits2_kernel(const WindowRec *__restrict__ wins, int nhw, co
   if (t >= nhw) return;
   const WindowRec x = wins[t];
   const int s = slot_of[x.cand];
-  if (s < 0 || hit_key(x) != best_key[s]) return;
-  atomicMin(reinterpret_cast<unsigned int *>(&orfs[s].wb), (unsigned int)t);          // wb starts at -1 = 0xffffffff: "no hit window"
+  if (s < 0 || !hit_key_fits(x) || hit_key(x) != best_key[s]) return;
+  atomicMin(reinterpret_cast<unsigned int *>(&orfs[s].wb), ((unsigned int)x.k << 16) | (unsigned int)t);   // wb starts at -1 = 0xffffffff: "no hit window"; t < kMaxHitWins = 2^16
 }
 
 template <class T>
@@ -281,6 +295,7 @@ __global__ void fsw_orf_kernel(FsOrfDev *__restrict__ orfs, int n, const WindowR
   const int s = blockIdx.x * blockDim.x + threadIdx.x;
   if (s >= n) return;
   FsOrfDev o = orfs[s];
+  o.wb = (o.wb >= 0) ? (o.wb & 0xffff) : -1;                           // fsw_hits2_kernel's k << 16 | index
   fsw_orf_window(o, wins, seq_len[o.w], p);
   orfs[s] = o;
 }
@@ -389,11 +404,11 @@ __global__ __launch_bounds__(1024) void fsw_layout_kernel(FsWinDev *__restrict__
 
 // per window, after the parsers: the branch decision
 __global__ void fsw_decide_kernel(bath_fs_window *__restrict__ out, int nw, const float *__restrict__ bias /* [nw][2][3] */, const float *__restrict__ fsc,
-                                  const float *__restrict__ tbl, int do_biasfilter, int std_pipe, double F3, double tau3, double lambda) {
+                                  const float *__restrict__ tbl, const FswLen *__restrict__ len_terms /* by L3 */, int do_biasfilter, int std_pipe, double F3, double tau3, double lambda) {
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= nw) return;
   bath_fs_window r = out[i];
-  fsw_decide(r, &bias[(size_t)i * 6], fsc[i], [tbl](float a, float b) { return flogsum_g(a, b, tbl); }, do_biasfilter, std_pipe, F3, tau3, lambda);
+  fsw_decide(r, &bias[(size_t)i * 6], fsc[i], len_terms[r.length / 3], [tbl](float a, float b) { return flogsum_g(a, b, tbl); }, do_biasfilter, std_pipe, F3, tau3, lambda);
   out[i] = r;
 }
 
@@ -405,6 +420,7 @@ __global__ void fsw_decide_kernel(bath_fs_window *__restrict__ out, int nw, cons
 struct ResLayout { size_t hdr, voff, vlen, a_bytes, orf, grp, b_end, out, desc, bytes; };
 static size_t al256(size_t x) { return (x + 255) & ~(size_t)255; }
 static ResLayout res_layout(int n) {
+  static_assert(kMaxHitWins <= 0x10000, "fsw_hits2_kernel keeps a hit window's index in 16 bits");
   static_assert(sizeof(FsOrfDev) % 8 == 0 && sizeof(bath_fs_window) % 8 == 0 && sizeof(FsWinDev) % 8 == 0, "records are laid out back to back");
   ResLayout r;
   r.hdr = 0; r.voff = 256; r.vlen = r.voff + al256((size_t)n * 8); r.a_bytes = r.vlen + al256((size_t)n * 4);
@@ -483,7 +499,7 @@ int fs_build_windows_device(bath_hip_ctx *ctx, const bath_hip_oprofile *om, cons
   hipLaunchKernelGGL(fsw_scatter_kernel<FsOrfDev>, dim3(gn), dim3(T), 0, s, d_orf0, d_orank, n, d_orf);
   if (nhw > 0) {
     hipLaunchKernelGGL(fsw_slot_kernel, dim3(gn), dim3(T), 0, s, d_orf, n, d_slot);
-    hipLaunchKernelGGL(fsw_hits1_kernel, dim3(gh), dim3(T), 0, s, d_win, nhw, d_slot, d_best, d_orf);
+    hipLaunchKernelGGL(fsw_hits1_kernel, dim3(gh), dim3(T), 0, s, d_win, nhw, d_slot, d_best, d_orf, d_hdr + 1);
     hipLaunchKernelGGL(fsw_hits2_kernel, dim3(gh), dim3(T), 0, s, d_win, nhw, d_slot, d_best, d_orf);
   }
   hipLaunchKernelGGL(fsw_orf_kernel, dim3(gn), dim3(T), 0, s, d_orf, n, d_win, dna->d_len, p);
@@ -507,7 +523,8 @@ int fs_build_windows_device(bath_hip_ctx *ctx, const bath_hip_oprofile *om, cons
   return BATH_OK;
 }
 
-// The same product from the survivor lists on the host: <sel> in ascending candidate id, <wins> by (candidate id, start), ids the block's own.
+// The same product from the survivor lists on the host: <sel> in ascending candidate id, <wins> by (candidate id, start, k), ids the block's own
+// (fs_order_survivors, fs_merge_survivors).
 int fs_build_windows_host(bath_hip_ctx *ctx, const bath_hip_oprofile *om, const bath_hip_seqs *dna, const bath_pipeline_params *prm,
                           const FsCandRec *sel, int n, const WindowRec *wins, int nhw, FsWinBuild *B) {
   *B = FsWinBuild{};
@@ -525,7 +542,7 @@ int fs_build_windows_host(bath_hip_ctx *ctx, const bath_hip_oprofile *om, const 
   const BuildParams p{om->M, om->max_length, om->prefix_lengths.data(), om->suffix_lengths.data(), prm->F3, (double)om->evparam[BATH_FTAU], (double)om->evparam[BATH_FLAMBDA],
                       prm->std_pipe, nullptr};
 
-  // ---- the ORFs with their best hit window (highest score, then longest, then first: :486-495) and k_min / k_max, then in the reference's order
+  // ---- the ORFs with their best hit window (highest score, then longest, then first -- in <wins>' order, the leftmost and of those the one with the smallest k: :486-495) and k_min / k_max, then in the reference's order
   struct Keyed { Key key; FsOrfDev o; };
   std::vector<Keyed> keyed((size_t)n);
   for (int i = 0, wi = 0; i < n; i++) {
@@ -613,12 +630,23 @@ int fs_decide(bath_hip_ctx *ctx, const bath_hip_fsprofile *om_fs3, const bath_pi
     BATH_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     for (int i = 0; i < B.nw; i++) {
       h_out[i] = B.h_out[i];
-      fsw_decide(h_out[i], &h_bias[(size_t)i * 6], h_fsc[i], flogsum_host, prm->do_biasfilter, prm->std_pipe, prm->F3, tau3, lambda);
+      fsw_decide(h_out[i], &h_bias[(size_t)i * 6], h_fsc[i], fsw_len_terms(h_out[i].length / 3), flogsum_host, prm->do_biasfilter, prm->std_pipe, prm->F3, tau3, lambda);
     }
     return BATH_OK;
   }
+  // the length terms by L3, up to the longest window of the block: kept by the context, extended (and uploaded again) when a block needs more
+  DevBuf &b_len = ctx->scratch[62];
+  const size_t need = (size_t)std::max(B.maxlen, 0) / 3 + 1;
+  if (ctx->fsw_len_terms.size() < need * 2 || !b_len.p) {
+    const size_t n = std::max(need, ctx->fsw_len_terms.size());       // (two floats per L3: grows to twice what is asked for)
+    ctx->fsw_len_terms.resize(2 * n);
+    for (size_t L3 = 0; L3 < n; L3++) { const FswLen t = fsw_len_terms((int)L3); ctx->fsw_len_terms[2 * L3] = t.null_frame; ctx->fsw_len_terms[2 * L3 + 1] = t.filt; }
+    BATH_HIP_TRY(ctx, b_len.reserve(2 * n * sizeof(float)));
+    BATH_HIP_TRY(ctx, hipMemcpyAsync(b_len.p, ctx->fsw_len_terms.data(), 2 * n * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+    BATH_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  }
   hipLaunchKernelGGL(fsw_decide_kernel, dim3((unsigned)((B.nw + 255) / 256)), dim3(256), 0, ctx->stream, B.d_out, B.nw, d_bias, d_fsc, om_fs3->d_logsum,
-                     prm->do_biasfilter, prm->std_pipe, prm->F3, tau3, lambda);
+                     b_len.as<FswLen>(), prm->do_biasfilter, prm->std_pipe, prm->F3, tau3, lambda);
   BATH_HIP_TRY(ctx, hipGetLastError());
   if (ctx->stage[7].reserve((size_t)B.nw * sizeof(bath_fs_window) + 64) != hipSuccess) { ctx->set_error("cannot allocate page-locked staging memory"); return BATH_EFAIL; }
   BATH_HIP_TRY(ctx, hipMemcpyAsync(ctx->stage[7].p, B.d_out, (size_t)B.nw * sizeof(bath_fs_window), hipMemcpyDeviceToHost, ctx->stream));
@@ -627,4 +655,129 @@ int fs_decide(bath_hip_ctx *ctx, const bath_hip_fsprofile *om_fs3, const bath_pi
   return BATH_OK;
 }
 
+void fs_order_survivors(std::vector<FsCandRec> *sel, std::vector<WindowRec> *wins) {
+  std::sort(sel->begin(), sel->end(), [](const FsCandRec &a, const FsCandRec &b) { return a.cand < b.cand; });
+  // an ORF's windows in the order the Viterbi filter emits them (by start); windows of one start, which it never emits, by k
+  std::stable_sort(wins->begin(), wins->end(), [](const WindowRec &a, const WindowRec &b) { return a.cand != b.cand ? a.cand < b.cand : (a.n != b.n ? a.n < b.n : a.k < b.k); });
+}
+
+void fs_merge_survivors(const FsLaneSurv *lanes, int nlanes, const std::vector<std::vector<FsCandRec>> &lsel, const std::vector<std::vector<WindowRec>> &lwin,
+                        std::vector<FsCandRec> *sel, std::vector<WindowRec> *wins) {
+  sel->clear(); wins->clear();
+  for (size_t k = 0; k < (size_t)nlanes; k++) {
+    const FsLaneSurv &ls = lanes[k];
+    for (FsCandRec q : lsel[k]) { q.cand += ls.cand_base; q.window += ls.first_window; q.aa_off += ls.dpool; if (nlanes > 1) q.fxoff = -1; sel->push_back(q); }
+    for (WindowRec w : lwin[k]) { w.cand += ls.cand_base; wins->push_back(w); }
+  }
+}
+
 }  // namespace bath
+
+// ---- self-test hooks (include/bath_hip.h): the builder and the decision on lists a test makes up
+static_assert(sizeof(bath_fs_cand) == sizeof(bath::FsCandRec) && offsetof(bath_fs_cand, fxoff) == offsetof(bath::FsCandRec, fxoff) && offsetof(bath_fs_cand, cand) == offsetof(bath::FsCandRec, cand), "bath_fs_cand is FsCandRec");
+static_assert(sizeof(bath_fs_hitwin) == sizeof(bath::WindowRec) && offsetof(bath_fs_hitwin, score) == offsetof(bath::WindowRec, score), "bath_fs_hitwin is WindowRec");
+static_assert(sizeof(bath_fs_orf) == sizeof(bath::FsOrfDev) && offsetof(bath_fs_orf, g1) == offsetof(bath::FsOrfDev, g1) && offsetof(bath_fs_orf, dw_n) == offsetof(bath::FsOrfDev, dw_n), "bath_fs_orf is FsOrfDev");
+static_assert(sizeof(bath_fs_windesc) == sizeof(bath::FsWinDev) && offsetof(bath_fs_windesc, kmax) == offsetof(bath::FsWinDev, kmax), "bath_fs_windesc is FsWinDev");
+
+extern "C" int bath_selftest_fs_windows(bath_hip_ctx *ctx, const bath_hip_oprofile *om, const bath_hip_fsprofile *om_fs3, const bath_hip_seqs *dna, double F3, int std_pipe,
+                                        int driver, const bath_fs_lane *lanes, int nlanes, int nc_total, bath_fs_winbuild *hdr, bath_fs_orf *orfs,
+                                        bath_fs_window *windows, int32_t *grp, int64_t *voff, int32_t *vlen, bath_fs_windesc *desc) {
+  using namespace bath;
+  if (!ctx || !om || !om_fs3 || !dna || !hdr || nlanes < 0 || (nlanes > 0 && !lanes) || (driver != 0 && driver != 1)) return BATH_EINVAL;
+  BATH_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  *hdr = bath_fs_winbuild{};
+  bath_pipeline_params prm;
+  bath_pipeline_params_default(&prm, 1);
+  prm.F3 = F3; prm.std_pipe = std_pipe;
+  size_t n = 0;
+  for (int k = 0; k < nlanes; k++) {
+    if (lanes[k].n_c < 0 || lanes[k].n_w < 0 || (lanes[k].n_c > 0 && !lanes[k].cands) || (lanes[k].n_w > 0 && !lanes[k].wins)) return BATH_EINVAL;
+    n += (size_t)lanes[k].n_c;
+  }
+  if (n > 0 && (!orfs || !windows || !grp || !voff || !vlen || !desc)) return BATH_EINVAL;
+  FsWinBuild B;
+  int st;
+  char *d_lists = nullptr;
+  if (driver == 0) {
+    std::vector<FsLaneSurv> dl((size_t)nlanes);
+    std::vector<size_t> o_c((size_t)nlanes), o_w((size_t)nlanes);
+    size_t bytes = 256;
+    for (int k = 0; k < nlanes; k++) {
+      o_c[(size_t)k] = bytes; bytes += ((size_t)lanes[k].n_c * sizeof(FsCandRec) + 255) / 256 * 256;
+      o_w[(size_t)k] = bytes; bytes += ((size_t)lanes[k].n_w * sizeof(WindowRec) + 255) / 256 * 256;
+    }
+    BATH_HIP_TRY(ctx, hipMalloc((void **)&d_lists, bytes));
+    hipError_t e = hipSuccess;
+    for (int k = 0; k < nlanes && e == hipSuccess; k++) {
+      FsLaneSurv &ls = dl[(size_t)k];
+      ls.d_c = reinterpret_cast<const FsCandRec *>(d_lists + o_c[(size_t)k]); ls.d_w = reinterpret_cast<const WindowRec *>(d_lists + o_w[(size_t)k]);
+      ls.n_c = lanes[k].n_c; ls.n_w = lanes[k].n_w; ls.cand_base = lanes[k].cand_base; ls.first_window = lanes[k].first_window; ls.dpool = lanes[k].dpool;
+      if (ls.n_c) e = hipMemcpy(d_lists + o_c[(size_t)k], lanes[k].cands, (size_t)ls.n_c * sizeof(FsCandRec), hipMemcpyHostToDevice);
+      if (ls.n_w && e == hipSuccess) e = hipMemcpy(d_lists + o_w[(size_t)k], lanes[k].wins, (size_t)ls.n_w * sizeof(WindowRec), hipMemcpyHostToDevice);
+    }
+    if (e != hipSuccess) { (void)hipFree(d_lists); ctx->set_error(std::string("bath_selftest_fs_windows: ") + hipGetErrorString(e)); return BATH_EFAIL; }
+    st = fs_build_windows_device(ctx, om, om_fs3, dna, &prm, dl.data(), nlanes, nc_total, &B);
+  } else {
+    std::vector<FsLaneSurv> hl((size_t)nlanes);
+    std::vector<std::vector<FsCandRec>> lsel((size_t)nlanes);
+    std::vector<std::vector<WindowRec>> lwin((size_t)nlanes);
+    for (int k = 0; k < nlanes; k++) {
+      FsLaneSurv &ls = hl[(size_t)k];
+      ls = FsLaneSurv{};
+      ls.n_c = lanes[k].n_c; ls.n_w = lanes[k].n_w; ls.cand_base = lanes[k].cand_base; ls.first_window = lanes[k].first_window; ls.dpool = lanes[k].dpool;
+      lsel[(size_t)k].resize((size_t)ls.n_c); lwin[(size_t)k].resize((size_t)ls.n_w);
+      if (ls.n_c) std::memcpy(lsel[(size_t)k].data(), lanes[k].cands, (size_t)ls.n_c * sizeof(FsCandRec));
+      if (ls.n_w) std::memcpy(lwin[(size_t)k].data(), lanes[k].wins, (size_t)ls.n_w * sizeof(WindowRec));
+      fs_order_survivors(&lsel[(size_t)k], &lwin[(size_t)k]);
+    }
+    std::vector<FsCandRec> sel;
+    std::vector<WindowRec> wins;
+    fs_merge_survivors(hl.data(), nlanes, lsel, lwin, &sel, &wins);
+    st = fs_build_windows_host(ctx, om, dna, &prm, sel.data(), (int)sel.size(), wins.data(), (int)wins.size(), &B);
+  }
+  hipError_t e = hipStreamSynchronize(ctx->stream);
+  if (st == BATH_OK && e == hipSuccess && B.nw > 0) {
+    hdr->n_orfs = B.n_orfs; hdr->nw = B.nw; hdr->maxlen = B.maxlen; hdr->pool_bytes = B.pool_bytes; hdr->total = B.total;
+    std::memcpy(orfs, B.h_orfs, (size_t)B.n_orfs * sizeof(FsOrfDev));
+    std::memcpy(grp, B.h_grp, (size_t)B.nw * 8);
+    std::memcpy(voff, B.h_voff, (size_t)B.nw * 8);
+    std::memcpy(vlen, B.h_vlen, (size_t)B.nw * 4);
+    if (B.host_built) std::memcpy(windows, B.h_out, (size_t)B.nw * sizeof(bath_fs_window));
+    else e = hipMemcpy(windows, B.d_out, (size_t)B.nw * sizeof(bath_fs_window), hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(desc, B.d_desc, (size_t)B.nw * sizeof(FsWinDev), hipMemcpyDeviceToHost);
+  }
+  if (d_lists) (void)hipFree(d_lists);
+  if ((st == BATH_OK || st == BATH_ENORESULT) && e != hipSuccess) { ctx->set_error(std::string("bath_selftest_fs_windows: ") + hipGetErrorString(e)); st = BATH_EFAIL; }
+  return st;
+}
+
+extern "C" int bath_selftest_fs_decide(bath_hip_ctx *ctx, const bath_hip_fsprofile *om_fs3, bath_fs_window *records, int nw, const float *bias, const float *fsc,
+                                       int do_biasfilter, int std_pipe, double F3, int driver) {
+  using namespace bath;
+  if (!ctx || !om_fs3 || nw < 0 || (nw > 0 && (!records || !bias || !fsc)) || (driver != 0 && driver != 1)) return BATH_EINVAL;
+  if (nw == 0) return BATH_OK;
+  int maxlen = 0;
+  for (int i = 0; i < nw; i++) { if (records[i].length < 0) return BATH_EINVAL; maxlen = std::max(maxlen, records[i].length); }
+  BATH_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  bath_pipeline_params prm;
+  bath_pipeline_params_default(&prm, 1);
+  prm.F3 = F3; prm.std_pipe = std_pipe; prm.do_biasfilter = do_biasfilter;
+  const size_t o_rec = 0, o_bias = al256((size_t)nw * sizeof(bath_fs_window)), o_fsc = o_bias + al256((size_t)nw * 6 * sizeof(float)), bytes = o_fsc + al256((size_t)nw * sizeof(float));
+  char *d = nullptr;
+  BATH_HIP_TRY(ctx, hipMalloc((void **)&d, bytes));
+  hipError_t e = hipMemcpy(d + o_rec, records, (size_t)nw * sizeof(bath_fs_window), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(d + o_bias, bias, (size_t)nw * 6 * sizeof(float), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMemcpy(d + o_fsc, fsc, (size_t)nw * sizeof(float), hipMemcpyHostToDevice);
+  int st = BATH_EFAIL;
+  if (e == hipSuccess) {
+    std::vector<bath_fs_window> in(records, records + nw), out((size_t)nw);
+    FsWinBuild B;
+    B.nw = nw; B.maxlen = maxlen; B.host_built = driver == 1; B.h_out = in.data(); B.d_out = reinterpret_cast<bath_fs_window *>(d + o_rec);
+    st = fs_decide(ctx, om_fs3, &prm, B, reinterpret_cast<const float *>(d + o_bias), reinterpret_cast<const float *>(d + o_fsc), fsc, out.data());
+    if (st == BATH_OK) std::memcpy(records, out.data(), (size_t)nw * sizeof(bath_fs_window));
+    e = hipStreamSynchronize(ctx->stream);
+  }
+  (void)hipFree(d);
+  if (e != hipSuccess) { ctx->set_error(std::string("bath_selftest_fs_decide: ") + hipGetErrorString(e)); return BATH_EFAIL; }
+  return st;
+}

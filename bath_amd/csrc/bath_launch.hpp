@@ -110,6 +110,11 @@ int fs_build_windows_device(bath_hip_ctx *ctx, const bath_hip_oprofile *om, cons
 // the same from the survivor lists on the host: sel[n] by candidate id, wins[nhw] by (candidate id, start), ids the block's own
 int fs_build_windows_host(bath_hip_ctx *ctx, const bath_hip_oprofile *om, const bath_hip_seqs *dna, const bath_pipeline_params *prm,
                           const FsCandRec *sel, int n, const WindowRec *wins, int nhw, FsWinBuild *out);
+// the order fs_build_windows_host reads the lists in: one lane's lists as the select kernels appended them -> by candidate id, its hit
+// windows by (candidate id, start, k); then the lanes' lists as one, ids, sequence indices and pool offsets made the block's own
+void fs_order_survivors(std::vector<FsCandRec> *sel, std::vector<WindowRec> *wins);
+void fs_merge_survivors(const FsLaneSurv *lanes, int nlanes, const std::vector<std::vector<FsCandRec>> &lsel, const std::vector<std::vector<WindowRec>> &lwin,
+                        std::vector<FsCandRec> *sel, std::vector<WindowRec> *wins);
 bool fs_orf_in_window(const FsOrfDev &o, const bath_fs_window &r, int n_seq);   // the ORF lies inside the window of its strand (p7_pipeline.c:1405)
 // after the parsers: scores -> P-values -> branch, where the windows were built; the completed records into h_out[nw]
 int fs_decide(bath_hip_ctx *ctx, const bath_hip_fsprofile *om_fs3, const bath_pipeline_params *prm, const FsWinBuild &B, const float *d_bias,

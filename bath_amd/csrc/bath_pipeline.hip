@@ -1458,9 +1458,7 @@ static int fetch_survivors(bath_hip_ctx *lane, const FsLaneSurv &ls, std::vector
   if (ls.n_c) BATH_HIP_TRY(lane, hipMemcpyAsync(sel->data(), ls.d_c, sel->size() * sizeof(FsCandRec), hipMemcpyDeviceToHost, lane->stream));
   if (ls.n_w) BATH_HIP_TRY(lane, hipMemcpyAsync(wins->data(), ls.d_w, wins->size() * sizeof(WindowRec), hipMemcpyDeviceToHost, lane->stream));
   BATH_HIP_TRY(lane, hipStreamSynchronize(lane->stream));
-  // the kernels append in completion order: candidate order makes what follows deterministic
-  std::sort(sel->begin(), sel->end(), [](const FsCandRec &a, const FsCandRec &b) { return a.cand < b.cand; });
-  std::stable_sort(wins->begin(), wins->end(), [](const WindowRec &a, const WindowRec &b) { return a.cand != b.cand ? a.cand < b.cand : a.n < b.n; });
+  fs_order_survivors(sel, wins);           // the kernels append in completion order: candidate order makes what follows deterministic
   return BATH_OK;
 }
 
@@ -1492,12 +1490,7 @@ static int select_survivors(bath_hip_ctx *lane, const FilterState &S, bool want_
 }
 
 static void merge_lane_lists(SurvivorSet *out, const std::vector<std::vector<FsCandRec>> &lsel, const std::vector<std::vector<WindowRec>> &lwin) {
-  out->sel.clear(); out->wins.clear();
-  for (size_t k = 0; k < (size_t)out->n_states; k++) {
-    const FsLaneSurv &ls = out->lanes[k];
-    for (FsCandRec q : lsel[k]) { q.cand += ls.cand_base; q.window += ls.first_window; q.aa_off += ls.dpool; if (out->n_states > 1) q.fxoff = -1; out->sel.push_back(q); }
-    for (WindowRec w : lwin[k]) { w.cand += ls.cand_base; out->wins.push_back(w); }
-  }
+  fs_merge_survivors(out->lanes.data(), out->n_states, lsel, lwin, &out->sel, &out->wins);
 }
 
 // the host path after a device-only cascade (an input bath_fs_windows.hip does not take): the lanes' lists come over after all

@@ -922,6 +922,32 @@ int bath_selftest_compo_terms(int base_b, float scale_b, float *terms /* [20][25
 int bath_selftest_len_sort(bath_hip_ctx *ctx, int n, const int32_t *lens, int T, int32_t *sorted, int32_t *n_longer);
 int bath_selftest_compute_units(const bath_hip_ctx *ctx);   /* the device's compute units: the cascade sizes its decision kernels' grids by them (4 blocks of 256 threads each), and a test its blocks by that */
 int bath_selftest_ens_explog(int n,const float *x, float *e, float *l);  /* the stream modes' own expf / logf (host build of the source the kernel compiles); either output may be NULL */
+/* (need the GPU) The frameshift stage's DNA-window builder and branch decision on their own (bath_fs_windows.hip), from lists a test
+ * makes up in place of what a cascade leaves.  A lane = one cascade lane's F4 survivors and their hit windows, ids the lane's own. */
+typedef struct { int64_t window, aa_off; double P; int32_t cand, sf, startj, len; float fwdsc, nullsc; int64_t fxoff; } bath_fs_cand;   /* sf = strand * 3 + frame; startj: first codon of the frame's stream */
+typedef struct { int32_t cand, n, k, length; float score; } bath_fs_hitwin;                                                            /* P7_HMM_WINDOW of candidate <cand> */
+typedef struct { const bath_fs_cand *cands; const bath_fs_hitwin *wins; int32_t n_c, n_w, cand_base; int64_t first_window, dpool; } bath_fs_lane;
+typedef struct {                   /* an F4 survivor in the builder's order, with the DNA window it asks for */
+  int64_t w, aa_off; double P;
+  int32_t cand, strand, start, end, n; float fwd_null;
+  int32_t wb, we;                  /* we > wb: a hit window of the ORF was found */
+  int32_t dw_n, dw_len, dw_k, kmin, kmax, g0, g1, pad_;
+} bath_fs_orf;
+typedef struct { int64_t src_off, dst_off; int32_t seq_n, start, len, strand, kmin, kmax; } bath_fs_windesc;   /* a window's gather descriptor */
+typedef struct { int32_t n_orfs, nw, maxlen, pad_; int64_t pool_bytes, total; } bath_fs_winbuild;
+/* driver 0: the lists uploaded as given, then the kernels; driver 1: the lists ordered and merged as the pipeline's host path does, then
+ * the host build.  F3, std_pipe: of the search.  Only the lengths and offsets of <dna> are read.  Returns the build's status
+ * (BATH_ENORESULT: the kernels hand the block back; nothing is written then) and, the stream synchronized, the whole product: hdr, the
+ * ordered ORFs [sum n_c], and per window (at most sum n_c) the record, its group grp[2 i], grp[2 i + 1] (a range of orfs), pool offset,
+ * length and descriptor (read back from the device copy). */
+int bath_selftest_fs_windows(bath_hip_ctx *ctx, const bath_hip_oprofile *om, const bath_hip_fsprofile *om_fs3, const bath_hip_seqs *dna, double F3, int std_pipe,
+                             int driver, const bath_fs_lane *lanes, int nlanes, int nc_total, bath_fs_winbuild *hdr, bath_fs_orf *orfs,
+                             bath_fs_window *windows, int32_t *grp, int64_t *voff, int32_t *vlen, bath_fs_windesc *desc);
+/* the branch decision over records[nw] (in: as a build leaves them; out: completed) from bias[nw][2][3], the three frames' Forward scores of
+ * the bias filter HMM under the model's and the local composition, and fsc[nw], the windows' Forward scores.  driver 0: fsw_decide_kernel;
+ * driver 1: the host loop a host-built block takes. */
+int bath_selftest_fs_decide(bath_hip_ctx *ctx, const bath_hip_fsprofile *om_fs3, bath_fs_window *records, int nw, const float *bias, const float *fsc,
+                            int do_biasfilter, int std_pipe, double F3, int driver);
 
 #ifdef __cplusplus
 }

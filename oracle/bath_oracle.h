@@ -377,6 +377,19 @@ int  bo_domaindef_std(bo_pipeline *pli, bo_oprofile *om, bo_bg *bg, const uint8_
 
 void bo_pipeline_init(bo_pipeline *pli, int fs_pipe);
 void  bo_local_compo(const bo_scoredata *sd, const bo_oprofile *om, const bo_bg *bg, int k_min, int k_max, float *compo); /* p7_pipeline.c:427 */
+/* the frameshift stage's window rules on their own (fs_pipeline.c; bo_pli_frameshift calls both) */
+typedef struct {                 /* a DNA window of one (sequence, strand) and the summary of the ORFs inside it */
+  int64_t n;                     /* start, 1-based on the strand being read */
+  int32_t length, k;
+  int32_t orf_cnt, k_min, k_max;
+  float   tot_orfsc;
+  double  P_min, P_tot;
+} bo_fsw;
+int  bo_fs_build_windows(const bo_orfblock *blk, const double *P_orf, const float *fwdsc, const bo_windowlist *hw, int n, int complementarity,
+                         const bo_oprofile *om, const bo_scoredata *sd, double F4, int std_pipe, bo_fsw **out, int *nout, int32_t *per_orf /* [4 * blk->count] or NULL */);
+void bo_fs_decide_window(bo_bg *bg, int L, int k_min, int k_max, int orf_cnt, double P_tot, double P_min, float bias_compo, float bias_local,
+                         float fsc, int do_biasfilter, int std_pipe, double F3, double tau3, double lambda3,
+                         float *nullsc_out, float *filtersc_out, double *P_fs_out, double *P_null_out, int *branch_out);
 /* frameshift stage for one strand (fs_pipeline.c); dsq[1..n] is the strand being read */
 int  bo_pli_frameshift(bo_pipeline *pli, bo_oprofile *om, bo_fs_profile *gm3, bo_fs_profile *gm5, const bo_scoredata *sd, bo_bg *bg, const uint8_t basic[64],
                        const bo_orfblock *blk, const double *P_orf, const float *fwdsc, const bo_windowlist *hw,
