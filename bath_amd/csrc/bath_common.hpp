@@ -18,6 +18,7 @@
 
 #include "bath_hip.h"
 #include "bath_tilings.hpp"
+#include "bath_slots.hpp"
 
 namespace bath {
 
@@ -182,22 +183,17 @@ struct bath_hip_ctx {
   // ... and the regions std_ensemble_kernel walked (the fallbacks to the twin included)
   std::atomic<int64_t> std_ens_serial_fallbacks{0}, std_ens_twin_fallbacks{0}, std_ens_kernel_regions{0};
   int fs_serial = -1;                   // envelopes' Backward after Forward on one stream instead of beside it (timing probes); -1: BATH_HIP_FS_SERIAL decides
-  uint64_t tabs_uid = 0;                // whose SSV score table sits in scratch[8] (bath_pipeline.hip: uploaded once per profile, not per call)
+  uint64_t tabs_uid = 0;                // whose SSV score table sits in Scratch::kSsvScoreTable (bath_pipeline.hip: uploaded once per profile, not per call)
   const void *tabs_ptr = nullptr;
-  uint64_t fsw_pad_uid = 0;             // whose window padding fractions sit in scratch[52] (bath_fs_windows.hip)
-  int orf_tables_id = -1;               // the NCBI table whose codon tables sit in scratch[28] (bath_orfs.hip: built and uploaded once per context and table)
+  uint64_t fsw_pad_uid = 0;             // whose window padding fractions sit in Scratch::kFsWindowPadding (bath_fs_windows.hip)
+  int orf_tables_id = -1;               // the NCBI table whose codon tables sit in Scratch::kOrfCodonTables (bath_orfs.hip: built and uploaded once per context and table)
   std::string err;
   void set_error(const std::string &m) { err = m; }
-  // scratch owned by the context (reused across calls)
-  std::vector<float> fsw_len_terms;     // the branch decision's length terms by window length / 3, two floats each, as uploaded to scratch[62] (bath_fs_windows.hip)
-  bath::DevBuf scratch[63];             // [50]-[52], [62]: the device-side DNA-window builder and decision (bath_fs_windows.hip); [59]-[61]: the standard branch's device ensemble
-                                        // (its regions' Forward matrices; job list + start states up; statuses, segments, path codes down)
-  // page-locked staging for small tables a launch uploads (job order, batch starts, offsets): an asynchronous copy from here needs
-  // no synchronize before the local it was built in goes away.  One slot per call site; a site is reused by its context only
-  // after the stage that used it has synchronized its stream.  [0] fs_schedule, [1]/[2] chain_batches (Forward / Backward), [3] wavefront Backward
-  bath::HostBuf stage[12];                // ... [4] / [5]: the standard branch's domain stage, its small uploads / downloads (bath_domaindef.hip: std_domains);
-                                          // [10] / [11]: std_ensemble_kernel's upload and its results (bath_std_ensemble.hip)
-  template <class T> int stage_upload(int slot, void *dst, const T *src, size_t n, hipStream_t s) {
+  std::vector<float> fsw_len_terms;     // the branch decision's length terms by window length / 3, two floats each, as uploaded to Scratch::kFsWindowLenTerms (bath_fs_windows.hip)
+  // device scratch and page-locked staging owned by the context (reused across calls): who holds what, and what shares, is bath_slots.hpp
+  bath::SlotArray<bath::Scratch, bath::DevBuf> scratch;
+  bath::SlotArray<bath::Pinned, bath::HostBuf> stage;
+  template <class T> int stage_upload(bath::Pinned slot, void *dst, const T *src, size_t n, hipStream_t s) {
     if (stage[slot].reserve(n * sizeof(T) + 64) != hipSuccess) { set_error("cannot allocate page-locked staging memory"); return BATH_EFAIL; }
     std::memcpy(stage[slot].p, src, n * sizeof(T));
     if (hipMemcpyAsync(dst, stage[slot].p, n * sizeof(T), hipMemcpyHostToDevice, s) != hipSuccess) { set_error("staging upload failed"); return BATH_EFAIL; }
@@ -217,7 +213,7 @@ struct bath_hip_ctx {
   const float *fwd_rows_kept = nullptr;
   const int64_t *fwd_rows_off = nullptr;
   bool fs_want_regions = false;           // set by the domain stage: the decision stage also runs the Backward parser and the region heuristics
-  std::vector<int64_t> fs_keep_xoff;      // the decision stage's Forward parser rows stay on the device (scratch[45]): offsets per DNA window, in floats
+  std::vector<int64_t> fs_keep_xoff;      // the decision stage's Forward parser rows stay on the device (Scratch::kFsKeptFwdRows): offsets per DNA window, in floats
   std::vector<int32_t> fs_regions_all;    // ... for every DNA window: 1 + 3*fs_max_regions() ints each (bath_frameshift.hip: fs3_regions)
   std::vector<bath_fs_domain> fs_domains; // bath_hip_pipeline_frameshift_domains output
   std::string cigars;                     // NUL-terminated CIGAR strings of fs_domains (bath_fs_domain.cigar_off)

@@ -1655,7 +1655,7 @@ static int std_region_stage(bath_hip_ctx *ctx, const bath_hip_oprofile *om, SeqV
   const int mode = ctx->std_ensemble;
   const bool dev = mode == BATH_ENSEMBLE_STREAMS_DEVICE;
   out->assign((size_t)nm, StdRegionOut{});
-  DevBuf &b_fx = ctx->scratch[6], &b_sc = ctx->scratch[2], &b_st = ctx->scratch[3], &b_dp = ctx->scratch[59];
+  DevBuf &b_fx = ctx->scratch[Scratch::kStdFwdRows], &b_sc = ctx->scratch[Scratch::kStdScores], &b_st = ctx->scratch[Scratch::kStdStatus], &b_dp = ctx->scratch[Scratch::kStdRegionFwdMatrix];
   BATH_HIP_TRY(ctx, b_fx.reserve((size_t)mxoff[(size_t)nm] * 4 + 64)); BATH_HIP_TRY(ctx, b_sc.reserve((size_t)nm * 8)); BATH_HIP_TRY(ctx, b_st.reserve((size_t)nm * 8));
   // Residues of region e: h_res + roff[e], one row's worth of bytes per residue row (roff = the x-row offsets / 6).
   const size_t x_bytes = ((size_t)mxoff[(size_t)nm] * 4 + 255) / 256 * 256;
@@ -1762,19 +1762,19 @@ static int std_domains(bath_hip_ctx *ctx, const bath_hip_oprofile *om, const bat
     view.h_off[(size_t)i] = surv[(size_t)i].aa_off; view.h_len[(size_t)i] = surv[(size_t)i].n; view.maxlen = std::max(view.maxlen, surv[(size_t)i].n);
     xoff[(size_t)i + 1] = xoff[(size_t)i] + ((int64_t)surv[(size_t)i].n + 1) * 6;
   }
-  DevBuf &b_idx = ctx->scratch[0], &b_fx = ctx->scratch[6], &b_bx = ctx->scratch[7], &b_sc = ctx->scratch[2], &b_st = ctx->scratch[3], &b_work = ctx->scratch[4], &b_reg = ctx->scratch[5];
-  // The small transfers of a stage go through page-locked memory (ctx->stage[4] up, [5] down): a hipMemcpyAsync from or to
+  DevBuf &b_idx = ctx->scratch[Scratch::kStdViewArrays], &b_fx = ctx->scratch[Scratch::kStdFwdRows], &b_bx = ctx->scratch[Scratch::kStdBwdRows], &b_sc = ctx->scratch[Scratch::kStdScores], &b_st = ctx->scratch[Scratch::kStdStatus], &b_work = ctx->scratch[Scratch::kStdRegionWork], &b_reg = ctx->scratch[Scratch::kStdRegionList];
+  // The small transfers of a stage go through page-locked memory (Pinned::kStdUploads, Pinned::kStdDownloads): a hipMemcpyAsync from or to
   // pageable memory is staged by the runtime and holds the host ~20 us, and one query's domain stage had two dozen of them -- a
   // fifth of its time on a 12.5 Mb block (configs[3]).  up_begin() sizes the staging area for ALL uploads of a stage (it may move
   // while nothing is in flight: every stage ends with a synchronize); a sequence view's three arrays travel as ONE copy.
   size_t up_used = 0;
-  auto up_begin = [&](size_t bytes) -> int { up_used = 0; BATH_HIP_TRY(ctx, ctx->stage[4].reserve(bytes + 1024)); return BATH_OK; };
+  auto up_begin = [&](size_t bytes) -> int { up_used = 0; BATH_HIP_TRY(ctx, ctx->stage[Pinned::kStdUploads].reserve(bytes + 1024)); return BATH_OK; };
   auto up = [&](void *dst, std::initializer_list<std::pair<const void *, size_t>> parts) -> int {
     size_t bytes = 0;
     for (const auto &q : parts) bytes += q.second;
     const size_t end = up_used + ((bytes + 63) & ~(size_t)63);
-    if (end > ctx->stage[4].cap) { ctx->set_error("staging area of the domain stage too small"); return BATH_EFAIL; }      // before anything is written
-    char *h = static_cast<char *>(ctx->stage[4].p) + up_used;
+    if (end > ctx->stage[Pinned::kStdUploads].cap) { ctx->set_error("staging area of the domain stage too small"); return BATH_EFAIL; }      // before anything is written
+    char *h = static_cast<char *>(ctx->stage[Pinned::kStdUploads].p) + up_used;
     bytes = 0;
     for (const auto &q : parts) { std::memcpy(h + bytes, q.first, q.second); bytes += q.second; }
     up_used = end;
@@ -1793,7 +1793,7 @@ static int std_domains(bath_hip_ctx *ctx, const bath_hip_oprofile *om, const bat
     return BATH_OK;
   };
   // downloads: into page-locked memory, then (after the stage's synchronize) a host copy into the vector the code reads
-  auto down_reserve = [&](size_t bytes) -> int { BATH_HIP_TRY(ctx, ctx->stage[5].reserve(bytes + 1024)); return BATH_OK; };
+  auto down_reserve = [&](size_t bytes) -> int { BATH_HIP_TRY(ctx, ctx->stage[Pinned::kStdDownloads].reserve(bytes + 1024)); return BATH_OK; };
   if ((st = om->ensure_len_tables(view.maxlen)) != BATH_OK) return st;
   if ((st = up_begin(view_bytes(ns) + (size_t)ns * 8 + 256)) != BATH_OK) return st;                 // (+ the kept Forward rows' offsets, below)
   if ((st = upload_view(view, xoff, ns)) != BATH_OK) return st;
@@ -1811,7 +1811,7 @@ static int std_domains(bath_hip_ctx *ctx, const bath_hip_oprofile *om, const bat
   if (kept) {
     std::vector<int64_t> src((size_t)ns);
     for (int64_t i = 0; i < ns; i++) src[(size_t)i] = surv[(size_t)i].fx_off;
-    DevBuf &b_src = ctx->scratch[49];
+    DevBuf &b_src = ctx->scratch[Scratch::kStdKeptRowSource];
     BATH_HIP_TRY(ctx, b_src.reserve((size_t)ns * 8 + 64));
     if ((st = up(b_src.p, {{src.data(), (size_t)ns * 8}})) != BATH_OK) return st;
     hipLaunchKernelGGL(copy_rows_kernel, dim3((unsigned)std::min<int64_t>(ns, 65535)), dim3(256), 0, ctx->stream, ns, view.d_len, ctx->fwd_rows_kept, b_src.as<int64_t>(), b_fx.as<float>(), d_xoff);
@@ -1832,9 +1832,9 @@ static int std_domains(bath_hip_ctx *ctx, const bath_hip_oprofile *om, const bat
   BATH_HIP_TRY(ctx, hipGetLastError());
   std::vector<int32_t> regions((size_t)ns * RS);
   if ((st = down_reserve(regions.size() * 4)) != BATH_OK) return st;
-  BATH_HIP_TRY(ctx, hipMemcpyAsync(ctx->stage[5].p, b_reg.p, regions.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
+  BATH_HIP_TRY(ctx, hipMemcpyAsync(ctx->stage[Pinned::kStdDownloads].p, b_reg.p, regions.size() * 4, hipMemcpyDeviceToHost, ctx->stream));
   BATH_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  std::memcpy(regions.data(), ctx->stage[5].p, regions.size() * 4);
+  std::memcpy(regions.data(), ctx->stage[Pinned::kStdDownloads].p, regions.size() * 4);
   view.d_data = nullptr; view.d_off = nullptr; view.d_len = nullptr;
   clk.lap("std:   parsers + regions");
 
@@ -1866,7 +1866,7 @@ static int std_domains(bath_hip_ctx *ctx, const bath_hip_oprofile *om, const bat
     }
     if ((st = up_begin(view_bytes(nm) + (size_t)(nm + 1) * 8 + (size_t)nm * 4 + 256)) != BATH_OK) return st;
     if ((st = upload_view(mv, mxoff, nm)) != BATH_OK) return st;
-    DevBuf &b_mdpo = ctx->scratch[20], &b_cfg = ctx->scratch[5];
+    DevBuf &b_mdpo = ctx->scratch[Scratch::kEnvOffsets], &b_cfg = ctx->scratch[Scratch::kStdRegionCfgLen];
     BATH_HIP_TRY(ctx, b_mdpo.reserve((size_t)(nm + 1) * 8)); BATH_HIP_TRY(ctx, b_cfg.reserve((size_t)nm * 4 + 64));
     if ((st = up(b_mdpo.p, {{mdpoff.data(), (size_t)(nm + 1) * 8}})) != BATH_OK) return st;
     if ((st = up(b_cfg.p, {{cfg.data(), (size_t)nm * 4}})) != BATH_OK) return st;
@@ -1898,7 +1898,7 @@ static int std_domains(bath_hip_ctx *ctx, const bath_hip_oprofile *om, const bat
   if ((st = up_begin(view_bytes(ne) + (size_t)(4 * ne + 2) * 8 + 512)) != BATH_OK) return st;      // the view, the columns' offsets (3 ne + 1), the matrices' (ne + 1)
   if ((st = upload_view(ev, exoff, ne)) != BATH_OK) return st;
   const int64_t *d_exoff = b_idx.as<int64_t>() + ne;
-  DevBuf &b_f = ctx->scratch[15], &b_b = ctx->scratch[16], &b_dpo = ctx->scratch[20], &b_px = ctx->scratch[18], &b_ox = ctx->scratch[19], &b_em = ctx->scratch[22], &b_out = ctx->scratch[21];
+  DevBuf &b_f = ctx->scratch[Scratch::kEnvFwdMatrix], &b_b = ctx->scratch[Scratch::kEnvBwdMatrix], &b_dpo = ctx->scratch[Scratch::kEnvOffsets], &b_px = ctx->scratch[Scratch::kStdPosteriorRows], &b_ox = ctx->scratch[Scratch::kStdOaRows], &b_em = ctx->scratch[Scratch::kEnvNull2Work], &b_out = ctx->scratch[Scratch::kStdEnvOut];
   BATH_HIP_TRY(ctx, b_f.reserve((size_t)dpoff[(size_t)ne] * 4 + 64 + kStdFillSlack)); BATH_HIP_TRY(ctx, b_b.reserve((size_t)dpoff[(size_t)ne] * 4 + 64 + kStdFillSlack));
   BATH_HIP_TRY(ctx, b_dpo.reserve((size_t)(ne + 1) * 8)); BATH_HIP_TRY(ctx, b_fx.reserve((size_t)exoff[(size_t)ne] * 4 + 64)); BATH_HIP_TRY(ctx, b_bx.reserve((size_t)exoff[(size_t)ne] * 4 + 64));
   BATH_HIP_TRY(ctx, b_px.reserve((size_t)exoff[(size_t)ne] / 6 * 5 * 4 + 64)); BATH_HIP_TRY(ctx, b_ox.reserve((size_t)exoff[(size_t)ne] / 6 * 5 * 4 + 64));
@@ -1915,7 +1915,7 @@ static int std_domains(bath_hip_ctx *ctx, const bath_hip_oprofile *om, const bat
     toff[(size_t)ne + 1 + (size_t)e] = o.strand ? woff + wn - p : woff + p - 1;
     toff[(size_t)ne + 1 + (size_t)ne + (size_t)e] = o.strand ? -1 : 1;
   }
-  DevBuf &b_tb = ctx->scratch[10], &b_toff = ctx->scratch[13];
+  DevBuf &b_tb = ctx->scratch[Scratch::kEnvTraceColumns], &b_toff = ctx->scratch[Scratch::kStdTraceOffsets];
   if ((size_t)toff[(size_t)ne] >= (size_t)INT32_MAX) { ctx->set_error("too many envelopes for the trace columns' 32-bit offsets"); return BATH_ERANGE; }
   // [columns: 1 B each, per envelope] [cursor] [the columns' posteriors, densely: 4 B per column that exists]
   const size_t tb_cols = ((size_t)toff[(size_t)ne] + 255) / 256 * 256;
@@ -1954,7 +1954,7 @@ static int std_domains(bath_hip_ctx *ctx, const bath_hip_oprofile *om, const bat
     // what does not depend on the number of columns first (with the count), then the columns' posteriors
     const size_t o_tc = 64, o_eo = o_tc + ((tcols.size() + 63) & ~(size_t)63), o_sc = o_eo + (((size_t)ne * sizeof(StdEnvOut) + 63) & ~(size_t)63), o_end = o_sc + (size_t)ne * 4;
     if ((st = down_reserve(o_end)) != BATH_OK) return st;
-    char *h = static_cast<char *>(ctx->stage[5].p);
+    char *h = static_cast<char *>(ctx->stage[Pinned::kStdDownloads].p);
     BATH_HIP_TRY(ctx, hipMemcpyAsync(h, d_col_cursor, sizeof(int), hipMemcpyDeviceToHost, ctx->stream));
     BATH_HIP_TRY(ctx, hipMemcpyAsync(h + o_tc, b_tb.p, tcols.size(), hipMemcpyDeviceToHost, ctx->stream));
     BATH_HIP_TRY(ctx, hipMemcpyAsync(h + o_eo, b_out.p, (size_t)ne * sizeof(StdEnvOut), hipMemcpyDeviceToHost, ctx->stream));
@@ -1968,9 +1968,9 @@ static int std_domains(bath_hip_ctx *ctx, const bath_hip_oprofile *om, const bat
     col_pp.resize((size_t)total);
     if (total > 0) {
       if ((st = down_reserve((size_t)total * sizeof(float))) != BATH_OK) return st;
-      BATH_HIP_TRY(ctx, hipMemcpyAsync(ctx->stage[5].p, d_col_pp, (size_t)total * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+      BATH_HIP_TRY(ctx, hipMemcpyAsync(ctx->stage[Pinned::kStdDownloads].p, d_col_pp, (size_t)total * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
       BATH_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-      std::memcpy(col_pp.data(), ctx->stage[5].p, (size_t)total * sizeof(float));
+      std::memcpy(col_pp.data(), ctx->stage[Pinned::kStdDownloads].p, (size_t)total * sizeof(float));
     }
   }
   ev.d_data = nullptr; ev.d_off = nullptr; ev.d_len = nullptr;
@@ -2100,7 +2100,7 @@ extern "C" int bath_hip_forward_full(bath_hip_ctx *ctx, const bath_hip_oprofile 
   int st = om->ensure_len_tables(maxcfg + 1);
   if (st != BATH_OK) return st;
   const BlockOffsets o = block_offsets(sq, M);
-  DevBuf &b_f = ctx->scratch[15], &b_off = ctx->scratch[20], &b_fx = ctx->scratch[18], &b_sc = ctx->scratch[21], &b_cfg = ctx->scratch[5];
+  DevBuf &b_f = ctx->scratch[Scratch::kEnvFwdMatrix], &b_off = ctx->scratch[Scratch::kEnvOffsets], &b_fx = ctx->scratch[Scratch::kEnvFwdRows], &b_sc = ctx->scratch[Scratch::kEnvScores], &b_cfg = ctx->scratch[Scratch::kStdRegionCfgLen];
   BATH_HIP_TRY(ctx, b_f.reserve((size_t)o.dp[(size_t)n] * 4 + 64)); BATH_HIP_TRY(ctx, b_fx.reserve((size_t)o.x[(size_t)n] * 4 + 64));
   BATH_HIP_TRY(ctx, b_off.reserve((size_t)(n + 1) * 16)); BATH_HIP_TRY(ctx, b_sc.reserve((size_t)n * 8)); BATH_HIP_TRY(ctx, b_cfg.reserve((size_t)n * 4 + 64));
   int64_t *d_xo = b_off.as<int64_t>(), *d_dpo = d_xo + (n + 1);
@@ -2132,8 +2132,8 @@ extern "C" int bath_hip_std_envelopes_fill(bath_hip_ctx *ctx, const bath_hip_opr
   const BlockOffsets o = block_offsets(sq, M);
   std::vector<int64_t> toff((size_t)n + 1, 0);
   for (int64_t e = 0; e < n; e++) toff[(size_t)e + 1] = toff[(size_t)e] + sq->h_len[(size_t)e] + M + 2;
-  DevBuf &b_f = ctx->scratch[15], &b_b = ctx->scratch[16], &b_off = ctx->scratch[20], &b_fx = ctx->scratch[6], &b_bx = ctx->scratch[7], &b_px = ctx->scratch[18],
-         &b_ox = ctx->scratch[19], &b_em = ctx->scratch[22], &b_out = ctx->scratch[21], &b_tb = ctx->scratch[10], &b_sc = ctx->scratch[2], &b_n2 = ctx->scratch[23];
+  DevBuf &b_f = ctx->scratch[Scratch::kEnvFwdMatrix], &b_b = ctx->scratch[Scratch::kEnvBwdMatrix], &b_off = ctx->scratch[Scratch::kEnvOffsets], &b_fx = ctx->scratch[Scratch::kStdFwdRows], &b_bx = ctx->scratch[Scratch::kStdBwdRows], &b_px = ctx->scratch[Scratch::kStdPosteriorRows],
+         &b_ox = ctx->scratch[Scratch::kStdOaRows], &b_em = ctx->scratch[Scratch::kEnvNull2Work], &b_out = ctx->scratch[Scratch::kStdEnvOut], &b_tb = ctx->scratch[Scratch::kEnvTraceColumns], &b_sc = ctx->scratch[Scratch::kStdScores], &b_n2 = ctx->scratch[Scratch::kEnvNull2];
   const size_t nx = (size_t)o.x[(size_t)n], ndp = (size_t)o.dp[(size_t)n];
   BATH_HIP_TRY(ctx, b_f.reserve(ndp * 4 + 64 + kStdFillSlack)); BATH_HIP_TRY(ctx, b_b.reserve(ndp * 4 + 64 + kStdFillSlack));
   BATH_HIP_TRY(ctx, b_fx.reserve(nx * 4 + 64)); BATH_HIP_TRY(ctx, b_bx.reserve(nx * 4 + 64));
@@ -2244,7 +2244,7 @@ extern "C" int bath_hip_std_region_ensembles(bath_hip_ctx *ctx, const bath_hip_o
   int st = om->ensure_len_tables(std::max(regions->maxlen, *std::max_element(cfg.begin(), cfg.end())) + 1);
   if (st != BATH_OK) return st;
   const BlockOffsets o = block_offsets(regions, om->M);
-  DevBuf &b_off = ctx->scratch[20], &b_cfg = ctx->scratch[5];
+  DevBuf &b_off = ctx->scratch[Scratch::kEnvOffsets], &b_cfg = ctx->scratch[Scratch::kStdRegionCfgLen];
   BATH_HIP_TRY(ctx, b_off.reserve((size_t)(n + 1) * 16)); BATH_HIP_TRY(ctx, b_cfg.reserve((size_t)n * 4 + 64));
   int64_t *d_xo = b_off.as<int64_t>(), *d_dpo = d_xo + (n + 1);
   BATH_HIP_TRY(ctx, hipMemcpyAsync(d_xo, o.x.data(), (size_t)(n + 1) * 8, hipMemcpyHostToDevice, ctx->stream));

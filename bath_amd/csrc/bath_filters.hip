@@ -894,7 +894,7 @@ static int ssv_or_msv(bath_hip_ctx *ctx, const bath_hip_oprofile *om, const bath
   if (st != BATH_OK) return st;
   const int64_t n = sq->n;
   if (n == 0) return BATH_OK;
-  DevBuf &b_order = ctx->scratch[0], &b_v = ctx->scratch[1], &b_sc = ctx->scratch[2], &b_st = ctx->scratch[3], &b_todo = ctx->scratch[4];
+  DevBuf &b_order = ctx->scratch[Scratch::kFilterOrder], &b_v = ctx->scratch[Scratch::kFilterSsvRaw], &b_sc = ctx->scratch[Scratch::kStdScores], &b_st = ctx->scratch[Scratch::kStdStatus], &b_todo = ctx->scratch[Scratch::kMsvTodo];
   if ((st = length_order(ctx, sq, b_order)) != BATH_OK) return st;
   BATH_HIP_TRY(ctx, b_v.reserve((size_t)n * sizeof(int16_t)));
   BATH_HIP_TRY(ctx, b_sc.reserve((size_t)n * sizeof(float)));
@@ -930,7 +930,7 @@ static int score_batch(bath_hip_ctx *ctx, const bath_hip_oprofile *om, const bat
   if (st != BATH_OK) return st;
   const int64_t n = sq->n;
   if (n == 0) return BATH_OK;
-  DevBuf &b_sc = ctx->scratch[2], &b_st = ctx->scratch[3];
+  DevBuf &b_sc = ctx->scratch[Scratch::kStdScores], &b_st = ctx->scratch[Scratch::kStdStatus];
   BATH_HIP_TRY(ctx, b_sc.reserve((size_t)n * sizeof(float)));
   BATH_HIP_TRY(ctx, b_st.reserve((size_t)n * sizeof(int32_t)));
   if ((st = launch(b_sc.as<float>(), b_st.as<int32_t>())) != BATH_OK) return st;
@@ -944,7 +944,7 @@ extern "C" int bath_hip_vitfilter(bath_hip_ctx *ctx, const bath_hip_oprofile *om
   if (vit_lane_supported(om) && sq && sq->n > 0) {       // lane-per-target kernel: targets sorted by length
     int st0 = check_batch(ctx, om, sq);
     if (st0 != BATH_OK) return st0;
-    DevBuf &b_order = ctx->scratch[0];
+    DevBuf &b_order = ctx->scratch[Scratch::kFilterOrder];
     if ((st0 = length_order(ctx, sq, b_order)) != BATH_OK) return st0;
     return score_batch(ctx, om, sq, sc, status, [&](float *d_sc, int32_t *d_st) {
       return launch_vit_lane(ctx, om, sq->view(), b_order.as<int32_t>(), sq->n, nullptr, d_sc, d_st, nullptr); });
@@ -965,7 +965,7 @@ extern "C" int bath_hip_fwdback_parser(bath_hip_ctx *ctx, const bath_hip_oprofil
   const int64_t n = sq->n;
   if (n == 0) return BATH_OK;
   const size_t nx = (size_t)xmx_offsets[n];
-  DevBuf &b_sc = ctx->scratch[2], &b_st = ctx->scratch[3], &b_off = ctx->scratch[4], &b_fx = ctx->scratch[6], &b_bx = ctx->scratch[7];
+  DevBuf &b_sc = ctx->scratch[Scratch::kStdScores], &b_st = ctx->scratch[Scratch::kStdStatus], &b_off = ctx->scratch[Scratch::kFwdbackRowOffsets], &b_fx = ctx->scratch[Scratch::kStdFwdRows], &b_bx = ctx->scratch[Scratch::kStdBwdRows];
   BATH_HIP_TRY(ctx, b_sc.reserve((size_t)n * 2 * sizeof(float)));
   BATH_HIP_TRY(ctx, b_st.reserve((size_t)n * 2 * sizeof(int32_t)));
   BATH_HIP_TRY(ctx, b_off.reserve((size_t)(n + 1) * sizeof(int64_t)));
@@ -990,7 +990,7 @@ extern "C" int bath_hip_bias_filter(bath_hip_ctx *ctx, const bath_hip_oprofile *
   if (st != BATH_OK) return st;
   const int64_t n = sq->n;
   if (n == 0) return BATH_OK;
-  DevBuf &b_a = ctx->scratch[2], &b_b = ctx->scratch[5];
+  DevBuf &b_a = ctx->scratch[Scratch::kStdScores], &b_b = ctx->scratch[Scratch::kBiasFilterScores];
   BATH_HIP_TRY(ctx, b_a.reserve((size_t)n * sizeof(float)));
   BATH_HIP_TRY(ctx, b_b.reserve((size_t)n * sizeof(float)));
   if ((st = launch_bias_lane(ctx, om, sq->view(), nullptr, 0, nullptr, n, b_a.as<float>(), b_b.as<float>())) != BATH_OK) return st;

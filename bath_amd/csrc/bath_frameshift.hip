@@ -1423,10 +1423,10 @@ static int fs_schedule(bath_hip_ctx *ctx, const bath_hip_seqs *dna, int k, FsJob
   std::vector<int32_t> order;
   fs_order_by_length_desc(dna->h_len.data(), n, &order);
   if (k > 64) { ctx->set_error("fs_schedule: more than 64 job counters"); return BATH_EINVAL; }
-  DevBuf &b = ctx->scratch[40];                                    // its own slot: the cascade's local-composition terms live in 36
+  DevBuf &b = ctx->scratch[Scratch::kFsJobList];
   BATH_HIP_TRY(ctx, b.reserve(256 + (size_t)n * sizeof(int32_t) + 64));
   BATH_HIP_TRY(ctx, hipMemsetAsync(b.p, 0, 256, ctx->stream));
-  if (ctx->stage_upload(0, b.as<char>() + 256, order.data(), (size_t)n, ctx->stream) != BATH_OK) return BATH_EFAIL;   // through page-locked staging: no synchronize
+  if (ctx->stage_upload(Pinned::kFsJobOrder, b.as<char>() + 256, order.data(), (size_t)n, ctx->stream) != BATH_OK) return BATH_EFAIL;   // through page-locked staging: no synchronize
   for (int i = 0; i < k; i++) jobs[i] = FsJobs{reinterpret_cast<const int32_t *>(b.as<char>() + 256), b.as<unsigned>() + i};
   return BATH_OK;
 }
@@ -1443,7 +1443,7 @@ static int fs3_parser(bath_hip_ctx *ctx, const bath_hip_fsprofile *om, const bat
   if (n == 0) return BATH_OK;
   int st = om->ensure_len(dna->maxlen / 3 + 1);
   if (st != BATH_OK) return st;
-  DevBuf &b_sc = ctx->scratch[12], &b_x = ctx->scratch[13], &b_off = ctx->scratch[14];
+  DevBuf &b_sc = ctx->scratch[Scratch::kFs3FwdScores], &b_x = ctx->scratch[Scratch::kFs3FwdRows], &b_off = ctx->scratch[Scratch::kFs3RowOffsets];
   BATH_HIP_TRY(ctx, b_sc.reserve((size_t)n * sizeof(float)));
   float *d_x = nullptr;
   if (xmx || keep) {
@@ -1596,7 +1596,7 @@ int fs3_regions(bath_hip_ctx *ctx, const bath_hip_fsprofile *om, const bath_hip_
   if (st != BATH_OK) return st;
   std::vector<int64_t> xoff((size_t)n + 1, 0);
   for (int64_t i = 0; i < n; i++) xoff[(size_t)i + 1] = xoff[(size_t)i] + ((int64_t)dna->h_len[(size_t)i] + 1) * 5;
-  DevBuf &b_sc = ctx->scratch[12], &b_fx = ctx->scratch[13], &b_off = ctx->scratch[14], &b_bx = ctx->scratch[11], &b_work = ctx->scratch[10], &b_reg = ctx->scratch[15];
+  DevBuf &b_sc = ctx->scratch[Scratch::kFs3FwdScores], &b_fx = ctx->scratch[Scratch::kFs3FwdRows], &b_off = ctx->scratch[Scratch::kFs3RowOffsets], &b_bx = ctx->scratch[Scratch::kFs3BwdRows], &b_work = ctx->scratch[Scratch::kFs3RegionWork], &b_reg = ctx->scratch[Scratch::kFs3RegionList];
   BATH_HIP_TRY(ctx, b_sc.reserve((size_t)n * sizeof(float)));
   BATH_HIP_TRY(ctx, b_fx.reserve((size_t)xoff[(size_t)n] * sizeof(float) + 64));
   BATH_HIP_TRY(ctx, b_bx.reserve((size_t)xoff[(size_t)n] * sizeof(float) + 64));
@@ -1607,7 +1607,7 @@ int fs3_regions(bath_hip_ctx *ctx, const bath_hip_fsprofile *om, const bath_hip_
   // <kept>: window q of <dna> is window kept[q] of the block whose Forward rows fs3_forward_scores left on the device -- the
   // reference runs the Forward parser once per window too (p7_pipeline.c:1450, rows kept in pli->oxf)
   const bool reuse = kept && !ctx->fs_keep_xoff.empty() && fwd_sc_out == nullptr;
-  DevBuf &b_foff = ctx->scratch[46];
+  DevBuf &b_foff = ctx->scratch[Scratch::kFsKeptFwdRowOffsets];
   const float *d_fx = b_fx.as<float>();
   const int64_t *d_fxoff = b_off.as<int64_t>();
   std::vector<int64_t> fsel;
@@ -1616,7 +1616,7 @@ int fs3_regions(bath_hip_ctx *ctx, const bath_hip_fsprofile *om, const bath_hip_
     for (int64_t q = 0; q < n; q++) fsel[(size_t)q] = ctx->fs_keep_xoff[(size_t)kept[q]];
     BATH_HIP_TRY(ctx, b_foff.reserve((size_t)n * sizeof(int64_t)));
     BATH_HIP_TRY(ctx, hipMemcpyAsync(b_foff.p, fsel.data(), (size_t)n * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
-    d_fx = ctx->scratch[45].as<float>(); d_fxoff = b_foff.as<int64_t>();
+    d_fx = ctx->scratch[Scratch::kFsKeptFwdRows].as<float>(); d_fxoff = b_foff.as<int64_t>();
   }
   const int Cv = BATH_TILING_PICK(BATH_FS_COLUMNS, om->M);
   const size_t shmem = (size_t)(kLogsumTbl + (om->M + 2) * 8) * sizeof(float);
@@ -1681,7 +1681,7 @@ int fs3_forward_scores(bath_hip_ctx *ctx, const bath_hip_fsprofile *om3, const b
   // windows that take the frameshift branch need the Backward parser only
   std::vector<int64_t> xoff((size_t)dna->n + 1, 0);
   for (int64_t i = 0; i < dna->n; i++) xoff[(size_t)i + 1] = xoff[(size_t)i] + ((int64_t)dna->h_len[(size_t)i] + 1) * 5;
-  const int st = fs3_parser(ctx, om3, dna, mode, sc, nullptr, xoff.data(), false, &ctx->scratch[45]);
+  const int st = fs3_parser(ctx, om3, dna, mode, sc, nullptr, xoff.data(), false, &ctx->scratch[Scratch::kFsKeptFwdRows]);
   if (st == BATH_OK) ctx->fs_keep_xoff = std::move(xoff);
   return st;
 }
@@ -1748,7 +1748,7 @@ extern "C" int bath_hip_fs5_forward_parser(bath_hip_ctx *ctx, const bath_hip_fsp
   if (n == 0) return BATH_OK;
   int st = om->ensure_len(std::max(dna->maxlen / 3 + 1, cfg_len_amino));
   if (st != BATH_OK) return st;
-  DevBuf &b_sc = ctx->scratch[21];
+  DevBuf &b_sc = ctx->scratch[Scratch::kEnvScores];
   BATH_HIP_TRY(ctx, b_sc.reserve((size_t)n * 3 * sizeof(float)));
   bath::FsJobs jq[1];
   if ((st = bath::fs_schedule(ctx, dna, 1, jq)) != BATH_OK) return st;
@@ -1773,7 +1773,7 @@ extern "C" int bath_hip_fs5_forward_parser_odds(bath_hip_ctx *ctx, const bath_hi
   if (n == 0) return BATH_OK;
   int st = om->ensure_len(std::max(dna->maxlen / 3 + 1, cfg_len_amino));
   if (st != BATH_OK) return st;
-  DevBuf &b_sc = ctx->scratch[21];
+  DevBuf &b_sc = ctx->scratch[Scratch::kEnvScores];
   BATH_HIP_TRY(ctx, b_sc.reserve((size_t)n * 3 * sizeof(float)));
   bath::FsJobs jq[1];
   if ((st = bath::fs_schedule(ctx, dna, 1, jq)) != BATH_OK) return st;
@@ -1805,8 +1805,8 @@ int bath::fs5_envelopes_ex(bath_hip_ctx *ctx, const bath_hip_fsprofile *om, cons
     const int64_t rows = (int64_t)dna->h_len[i] + 1;
     foff[i + 1] = foff[i] + rows * (M + 1) * 8; boff[i + 1] = boff[i] + rows * (M + 1) * 3; xoff[i + 1] = xoff[i] + rows * 5;
   }
-  DevBuf &b_f = ctx->scratch[15], &b_b = ctx->scratch[16], &b_o = ctx->scratch[17], &b_fx = ctx->scratch[18], &b_bx = ctx->scratch[19];
-  DevBuf &b_off = ctx->scratch[20], &b_sc = ctx->scratch[21], &b_cs = ctx->scratch[22], &b_n2 = ctx->scratch[23], &b_ox = ctx->scratch[11];
+  DevBuf &b_f = ctx->scratch[Scratch::kEnvFwdMatrix], &b_b = ctx->scratch[Scratch::kEnvBwdMatrix], &b_o = ctx->scratch[Scratch::kFs5OaMatrix], &b_fx = ctx->scratch[Scratch::kEnvFwdRows], &b_bx = ctx->scratch[Scratch::kEnvBwdRows];
+  DevBuf &b_off = ctx->scratch[Scratch::kEnvOffsets], &b_sc = ctx->scratch[Scratch::kEnvScores], &b_cs = ctx->scratch[Scratch::kEnvNull2Work], &b_n2 = ctx->scratch[Scratch::kEnvNull2], &b_ox = ctx->scratch[Scratch::kFs5OaRows];
   if (oax || trace) BATH_HIP_TRY(ctx, b_ox.reserve((size_t)xoff[n] * 4 + 64));
   BATH_HIP_TRY(ctx, b_f.reserve((size_t)foff[n] * 4 + 64)); BATH_HIP_TRY(ctx, b_b.reserve((size_t)boff[n] * 4 + 64)); BATH_HIP_TRY(ctx, b_o.reserve((size_t)boff[n] * 4 + 64));
   BATH_HIP_TRY(ctx, b_fx.reserve((size_t)xoff[n] * 4 + 64)); BATH_HIP_TRY(ctx, b_bx.reserve((size_t)xoff[n] * 4 + 64));
@@ -1832,7 +1832,7 @@ int bath::fs5_envelopes_ex(bath_hip_ctx *ctx, const bath_hip_fsprofile *om, cons
   // from the Forward and Backward matrices -- which then stay as they are -- and the rows' normalising factors (4 B per ROW) with the
   // decoding kernels' own arithmetic, value for value
   const bool store_pp = pp != nullptr;
-  DevBuf &b_rowden = ctx->scratch[37];
+  DevBuf &b_rowden = ctx->scratch[Scratch::kFs5RowDenominators];
   BATH_HIP_TRY(ctx, b_rowden.reserve((size_t)(xoff[(size_t)n] / 5 + 8) * sizeof(float)));
   float *d_rowden = store_pp ? nullptr : b_rowden.as<float>();
   FsJobs jq[4];
@@ -1845,7 +1845,7 @@ int bath::fs5_envelopes_ex(bath_hip_ctx *ctx, const bath_hip_fsprofile *om, cons
   // (odds5: the odds-ratio kernels of bath_fs5_odds.hip, node per lane; Backward with scales of its own, so still beside Forward)
   const int s1 = ctx->span_begin(odds5 ? "fs5_fwd_odds_kernel" : "fs5_fwd_kernel", ctx->stream, cells5, cells5 * 32.0);
   if (odds5) st = launch_fs5_odds(ctx, ctx->stream, om, dna, kFs5OddsEnvFwd, d_fsc, b_f.as<float>(), d_foff, b_fx.as<float>(), d_xoff, -1, jq[0], nullptr);
-  else st = launch_fs5_fwd_wf(ctx, ctx->stream, om, dna, exact, c5_compat, d_fsc, b_f.as<float>(), d_foff, b_fx.as<float>(), d_xoff, ctx->scratch[41], jq[0]);
+  else st = launch_fs5_fwd_wf(ctx, ctx->stream, om, dna, exact, c5_compat, d_fsc, b_f.as<float>(), d_foff, b_fx.as<float>(), d_xoff, ctx->scratch[Scratch::kFs5FwdRing], jq[0]);
   if (st != BATH_OK) return st;
   ctx->span_end(s1, ctx->stream);
   static const bool serial_env = [] { const char *e = std::getenv("BATH_HIP_FS_SERIAL"); return e && e[0] == '1'; }();   // timing probes: Backward after Forward
@@ -1853,7 +1853,7 @@ int bath::fs5_envelopes_ex(bath_hip_ctx *ctx, const bath_hip_fsprofile *om, cons
   hipStream_t bs = serial ? ctx->stream : ctx->side_stream;
   const int s2 = ctx->span_begin(odds5 ? "fs5_bwd_odds_kernel" : "fs_bwd_kernel<5>", bs, cells5, cells5 * 12.0);
   if (odds5) st = launch_fs5_odds(ctx, bs, om, dna, kFs5OddsEnvBwd, d_bsc, b_b.as<float>(), d_boff, b_bx.as<float>(), d_xoff, -1, jq[1], nullptr);
-  else st = launch_fs5_bwd_wf(ctx, bs, om, dna, exact, d_bsc, b_b.as<float>(), d_boff, b_bx.as<float>(), d_xoff, ctx->scratch[42], ctx->scratch[43], ctx->scratch[44], jq[1], jq[3]);
+  else st = launch_fs5_bwd_wf(ctx, bs, om, dna, exact, d_bsc, b_b.as<float>(), d_boff, b_bx.as<float>(), d_xoff, ctx->scratch[Scratch::kFs5BwdRing], ctx->scratch[Scratch::kFs5BwdTerms], ctx->scratch[Scratch::kFs5BwdTermOffsets], jq[1], jq[3]);
   if (st != BATH_OK) return st;
   ctx->span_end(s2, bs);
   if ((st = fs_join(ctx)) != BATH_OK) return st;
@@ -1888,7 +1888,7 @@ int bath::fs5_envelopes_ex(bath_hip_ctx *ctx, const bath_hip_fsprofile *om, cons
     if (!om->d_codons) { ctx->set_error("traceback needs the profile's codon table"); return BATH_EINVAL; }
     std::vector<int64_t> toff((size_t)n + 1, 0);
     for (int64_t i = 0; i < n; i++) toff[(size_t)i + 1] = toff[(size_t)i] + dna->h_len[(size_t)i] + M + 16;
-    DevBuf &b_tb = ctx->scratch[10], &b_to = ctx->scratch[13], &b_steps = ctx->scratch[14];
+    DevBuf &b_tb = ctx->scratch[Scratch::kEnvTraceColumns], &b_to = ctx->scratch[Scratch::kFs5TraceOut], &b_steps = ctx->scratch[Scratch::kFs5TraceSteps];
     BATH_HIP_TRY(ctx, b_tb.reserve((size_t)toff[(size_t)n] * sizeof(uint2) + (size_t)(n + 1) * sizeof(int64_t) + 256));
     // dense columns: [cursor (256 B)] [pp: 4 B per column] [codes: 2 B per column], at most toff[n] columns
     const size_t col_cap = (size_t)toff[(size_t)n];
@@ -1968,7 +1968,7 @@ int bath::fs5_region_forward(bath_hip_ctx *ctx, const bath_hip_fsprofile *om, co
     const int64_t rows = (int64_t)dna->h_len[(size_t)i] + 1;
     foff[(size_t)i + 1] = foff[(size_t)i] + rows * (M + 1) * 8; xoff[(size_t)i + 1] = xoff[(size_t)i] + rows * 5;
   }
-  DevBuf &b_f = ctx->scratch[15], &b_fx = ctx->scratch[18], &b_off = ctx->scratch[20], &b_sc = ctx->scratch[21];
+  DevBuf &b_f = ctx->scratch[Scratch::kEnvFwdMatrix], &b_fx = ctx->scratch[Scratch::kEnvFwdRows], &b_off = ctx->scratch[Scratch::kEnvOffsets], &b_sc = ctx->scratch[Scratch::kEnvScores];
   // The matrices are for the host (the ensembles' tracebacks).  The kernel is bound by its row chain, not by where its stores
   // go, so it writes them straight into page-locked host memory: the transfer rides along with the computation (32 B/cell,
   // ~27 GB/s on the bench block) instead of following it as a copy of its own.  BATH_HIP_FS_REGION_COPY=1: HBM first, then copy.
@@ -1991,8 +1991,8 @@ int bath::fs5_region_forward(bath_hip_ctx *ctx, const bath_hip_fsprofile *om, co
   BATH_HIP_TRY(ctx, b_sc.reserve((size_t)n * 3 * sizeof(float)));            // BEFORE its pointer is taken: on a fresh context it is null, and a growing buffer moves
   int *d_done = live ? reinterpret_cast<int *>(reinterpret_cast<char *>(d_fx) + x_bytes) : nullptr;
   float *d_sc_out = live ? reinterpret_cast<float *>(d_done + n) : b_sc.as<float>();
-  if (!direct) {                             // (device destination: buffers of its own -- the envelope batches of the same context use [15] / [18])
-    DevBuf &bf = dev ? ctx->scratch[53] : b_f, &bx = dev ? ctx->scratch[54] : b_fx;
+  if (!direct) {                             // (device destination: buffers of its own -- the envelope batches of the same context use kEnvFwdMatrix / kEnvFwdRows)
+    DevBuf &bf = dev ? ctx->scratch[Scratch::kFsRegionFwdMatrix] : b_f, &bx = dev ? ctx->scratch[Scratch::kFsRegionFwdRows] : b_fx;
     BATH_HIP_TRY(ctx, bf.reserve((size_t)foff[(size_t)n] * 4 + 64)); BATH_HIP_TRY(ctx, bx.reserve((size_t)xoff[(size_t)n] * 4 + 64));
     d_f = bf.as<float>(); d_fx = bx.as<float>();
   }

@@ -1362,7 +1362,7 @@ __global__ __launch_bounds__(THREADS) void fs5_fwd_chain_kernel(SeqView dna, FsD
 // smallest T such that batches of w(L) = (2T / L - t0) / dt windows (at most <wmax>), longest windows first, need no more blocks than
 // there are CUs -- the batches of the longest windows are smaller, and all blocks end together.  <bst>: batch b = windows
 // bst[b] .. bst[b+1]-1 of the list sorted by decreasing length.  BATH_HIP_FS_BATCH=w: uniform batches of w (A/B runs).
-static int chain_batches(bath_hip_ctx *ctx, hipStream_t stream, const bath_hip_seqs *dna, double t0, double dt, int wmax, DevBuf &buf, int stage_slot, int *nbat_out, int cu_share = 1) {
+static int chain_batches(bath_hip_ctx *ctx, hipStream_t stream, const bath_hip_seqs *dna, double t0, double dt, int wmax, DevBuf &buf, Pinned stage_slot, int *nbat_out, int cu_share = 1) {
   const int64_t n = dna->n;
   std::vector<int32_t> ls;
   fs_order_by_length_desc(dna->h_len.data(), n, nullptr, &ls);
@@ -1430,8 +1430,8 @@ int launch_fs3_fwd_chain(bath_hip_ctx *ctx, hipStream_t stream, const bath_hip_f
     // Bench block (7.6 k windows of 300-1000 nt, the longest 500 within 860-1000): a handful of windows in the first batches,
     // 32 for the bulk: 10.9 -> 9.9 ms
     int nbat = 0;
-    DevBuf &b_bst = ctx->scratch[47];
-    int stb = chain_batches(ctx, stream, dna, 0.085 * M + 3.5 + 0.4 * CH, 0.021 * CH, 32, b_bst, 1, &nbat);
+    DevBuf &b_bst = ctx->scratch[Scratch::kChainBatchesFwd];
+    int stb = chain_batches(ctx, stream, dna, 0.085 * M + 3.5 + 0.4 * CH, 0.021 * CH, 32, b_bst, Pinned::kChainBatchesFwd, &nbat);
     if (stb != BATH_OK) return stb;
     const int cus = ctx->prop.multiProcessorCount;
     const int hgrid = std::max(1, std::min(nbat, cus));
@@ -1462,7 +1462,7 @@ int launch_fs3_fwd_chain(bath_hip_ctx *ctx, hipStream_t stream, const bath_hip_f
       const size_t ms = fixed + (size_t)Wm * 2 * fs_chain_stride(Cv) * sizeof(float);
       static const int grid_env = [] { const char *e = std::getenv("BATH_HIP_FS_FWD_MEM_GRID"); return e ? std::atoi(e) : 0; }();   // tests: few blocks, several batches each
       const int mgrid = (int)std::max<int64_t>(1, std::min<int64_t>((n + Wm - 1) / Wm, grid_env > 0 ? (int64_t)grid_env : (int64_t)ctx->prop.multiProcessorCount));
-      DevBuf &b_hist = ctx->scratch[58];
+      DevBuf &b_hist = ctx->scratch[Scratch::kChainFwdHistory];
       BATH_HIP_TRY(ctx, b_hist.reserve((size_t)mgrid * Wm * 2 * kChainHistRows * fs_chain_hist_pitch(Cv) * sizeof(float)));
 #define BATH_MEM(C_)                                                                                                               \
       case C_: BATH_HIP_TRY(ctx, bath::allow_max_lds((const void *)fs3_fwd_chain_mem_kernel<C_>));                                  \
@@ -1496,8 +1496,8 @@ int launch_fs3_bwd_chain(bath_hip_ctx *ctx, hipStream_t stream, const bath_hip_f
     if (half_env != 0 && CH <= 6 && (half_env == 1 || n > (int64_t)ctx->prop.multiProcessorCount * 8)) {
       const size_t hs = (size_t)(kLogsumTbl + (M + 2) * 8 + 32 * 2 * (CH * 32 + 1) + 64 + 16) * sizeof(float);
       int nbat = 0;
-      DevBuf &b_bst = ctx->scratch[48];
-      const int stb = chain_batches(ctx, stream, dna, 0.128 * M + 6.6 + 0.5 * CH, 0.03 * CH, 32, b_bst, 2, &nbat, cu_share);
+      DevBuf &b_bst = ctx->scratch[Scratch::kChainBatchesBwd];
+      const int stb = chain_batches(ctx, stream, dna, 0.128 * M + 6.6 + 0.5 * CH, 0.03 * CH, 32, b_bst, Pinned::kChainBatchesBwd, &nbat, cu_share);
       if (stb != BATH_OK) return stb;
       const int hgrid = std::max(1, std::min(nbat, (int)ctx->prop.multiProcessorCount));
       FsDev dev{om->M, om->pitch, om->maxcodons, om->d_rsc, om->d_tf, om->d_tb, om->d_logsum};
@@ -1514,8 +1514,8 @@ int launch_fs3_bwd_chain(bath_hip_ctx *ctx, hipStream_t stream, const bath_hip_f
   const int W = chain_waves(ctx, dna->n, M, Cv, &shmem, cu_share, bwd_chain_threads(Cv), chain_compact(Cv) ? (M + 3) * 4 : 0);
   // batches by length (chain_batches); t(w) measured at M = 145 (C = 3): 25.4 us per row pair at one window, 28.5 at 16
   int nbat = 0;
-  DevBuf &b_bst = ctx->scratch[48];                                // (its own buffer: Forward's launch may be running on another stream)
-  const int stb = chain_batches(ctx, stream, dna, 0.128 * M + 6.6, 0.067 * Cv, W, b_bst, 2, &nbat, cu_share);
+  DevBuf &b_bst = ctx->scratch[Scratch::kChainBatchesBwd];     // (its own buffer: Forward's launch may be running on another stream)
+  const int stb = chain_batches(ctx, stream, dna, 0.128 * M + 6.6, 0.067 * Cv, W, b_bst, Pinned::kChainBatchesBwd, &nbat, cu_share);
   if (stb != BATH_OK) return stb;
   const int grid = std::max(1, std::min(nbat, (int)ctx->prop.multiProcessorCount));
   FsDev dev{om->M, om->pitch, om->maxcodons, om->d_rsc, om->d_tf, om->d_tb, om->d_logsum};

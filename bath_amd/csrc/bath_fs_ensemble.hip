@@ -62,12 +62,12 @@ int fs5_region_ensembles_device(bath_hip_ctx *ctx, const bath_hip_fsprofile *om,
   // start states: one jump-ahead per trace, on the host (200 x 32 multiplications per region)
   std::vector<uint32_t> states((size_t)n * kEnsSamples);
   for (int64_t e = 0; e < n; e++) fs_ensemble_start_states(seed, states.data() + (size_t)e * kEnsSamples);
-  DevBuf &b_states = ctx->scratch[57], &b_out = ctx->scratch[55];
+  DevBuf &b_states = ctx->scratch[Scratch::kFsEnsembleStates], &b_out = ctx->scratch[Scratch::kFsEnsembleOut];
   BATH_HIP_TRY(ctx, b_states.reserve(states.size() * sizeof(uint32_t) + 64));
   BATH_HIP_TRY(ctx, b_out.reserve((size_t)n * kFsEnsOutInts * sizeof(int32_t) + 64));
-  if ((st = ctx->stage_upload(8, b_states.p, states.data(), states.size(), ctx->stream)) != BATH_OK) return st;
+  if ((st = ctx->stage_upload(Pinned::kFsEnsembleStates, b_states.p, states.data(), states.size(), ctx->stream)) != BATH_OK) return st;
   const size_t out_bytes = (size_t)n * kFsEnsOutInts * sizeof(int32_t);
-  if (ctx->stage[9].reserve(out_bytes + (size_t)n * sizeof(float) + 64) != hipSuccess) { ctx->set_error("cannot allocate page-locked memory for the ensembles' segments"); return BATH_EFAIL; }
+  if (ctx->stage[Pinned::kFsEnsembleOut].reserve(out_bytes + (size_t)n * sizeof(float) + 64) != hipSuccess) { ctx->set_error("cannot allocate page-locked memory for the ensembles' segments"); return BATH_EFAIL; }
   const int grid = (int)std::max<int64_t>(1, std::min<int64_t>(n, (int64_t)ctx->prop.multiProcessorCount * 4));
   const double cells = (double)(run->foff[(size_t)n] / 8);
   const int s1 = ctx->span_begin("fs_ensemble_kernel", ctx->stream, cells, 0.0);
@@ -75,10 +75,10 @@ int fs5_region_ensembles_device(bath_hip_ctx *ctx, const bath_hip_fsprofile *om,
                      run->dev.d_fx, run->dev.d_xoff, run->dev.d_sc, b_states.as<uint32_t>(), b_out.as<int32_t>(), FsJobs{run->dev.job_order, run->dev.job_counter});
   ctx->span_end(s1, ctx->stream);
   BATH_HIP_TRY(ctx, hipGetLastError());
-  BATH_HIP_TRY(ctx, hipMemcpyAsync(ctx->stage[9].p, b_out.p, out_bytes, hipMemcpyDeviceToHost, ctx->stream));
-  BATH_HIP_TRY(ctx, hipMemcpyAsync(ctx->stage[9].as<char>() + out_bytes, run->dev.d_sc, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
-  run->out = ctx->stage[9].as<int32_t>();
-  run->sc = reinterpret_cast<const float *>(ctx->stage[9].as<char>() + out_bytes);
+  BATH_HIP_TRY(ctx, hipMemcpyAsync(ctx->stage[Pinned::kFsEnsembleOut].p, b_out.p, out_bytes, hipMemcpyDeviceToHost, ctx->stream));
+  BATH_HIP_TRY(ctx, hipMemcpyAsync(ctx->stage[Pinned::kFsEnsembleOut].as<char>() + out_bytes, run->dev.d_sc, (size_t)n * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+  run->out = ctx->stage[Pinned::kFsEnsembleOut].as<int32_t>();
+  run->sc = reinterpret_cast<const float *>(ctx->stage[Pinned::kFsEnsembleOut].as<char>() + out_bytes);
   ctx->fs_ens_bytes_kept += (int64_t)(run->foff[(size_t)n] + run->xoff[(size_t)n]) * 4;
   return BATH_OK;
 }

@@ -414,7 +414,7 @@ __global__ void fsw_decide_kernel(bath_fs_window *__restrict__ out, int nw, cons
 
 }  // namespace
 
-// What a build leaves in scratch[51] and (regions A and B) in the page-locked stage[6], records back to back.  Two regions for the
+// What a build leaves in Scratch::kFsWindowResult and (regions A and B) in the page-locked Pinned::kFsWindowResult, records back to back.  Two regions for the
 // device path's read-back: A = what the host needs BEFORE it can launch the parsers (header, the windows' pool offsets and lengths),
 // B = what it reads after the branch decision (ordered ORFs, group bounds; the records travel then, completed).
 struct ResLayout { size_t hdr, voff, vlen, a_bytes, orf, grp, b_end, out, desc, bytes; };
@@ -454,7 +454,7 @@ int fs_build_windows_device(bath_hip_ctx *ctx, const bath_hip_oprofile *om, cons
   if (n > kMaxOrfs || nhw > kMaxHitWins) return BATH_ENORESULT;
   const int M = om->M;
   // the window padding fractions of P7_SCOREDATA, once per profile and context
-  DevBuf &b_pad = ctx->scratch[52];
+  DevBuf &b_pad = ctx->scratch[Scratch::kFsWindowPadding];
   if (ctx->fsw_pad_uid != om->uid || !b_pad.p) {
     BATH_HIP_TRY(ctx, b_pad.reserve((size_t)(M + 1) * 2 * sizeof(float) + 64));
     BATH_HIP_TRY(ctx, hipMemcpyAsync(b_pad.p, om->prefix_lengths.data(), (size_t)(M + 1) * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
@@ -468,10 +468,10 @@ int fs_build_windows_device(bath_hip_ctx *ctx, const bath_hip_oprofile *om, cons
                o_win = o_orank + al((size_t)n * 4), o_slot = o_win + al((size_t)std::max(nhw, 1) * sizeof(WindowRec)), o_best = o_slot + al((size_t)std::max(nc_total, 1) * 4),
                o_wl = o_best + al((size_t)n * 8), o_cnt = o_wl + al((size_t)n * sizeof(DnaWinDev)), o_base = o_cnt + al((size_t)n * 4), ws_bytes = o_base + al((size_t)n * 4);
   const ResLayout R = res_layout(n);
-  DevBuf &b_ws = ctx->scratch[50], &b_res = ctx->scratch[51];
+  DevBuf &b_ws = ctx->scratch[Scratch::kFsWindowWork], &b_res = ctx->scratch[Scratch::kFsWindowResult];
   BATH_HIP_TRY(ctx, b_ws.reserve(ws_bytes + 256));
   BATH_HIP_TRY(ctx, b_res.reserve(R.bytes + 256));
-  if (ctx->stage[6].reserve(R.b_end + 256) != hipSuccess) { ctx->set_error("cannot allocate page-locked staging memory"); return BATH_EFAIL; }
+  if (ctx->stage[Pinned::kFsWindowResult].reserve(R.b_end + 256) != hipSuccess) { ctx->set_error("cannot allocate page-locked staging memory"); return BATH_EFAIL; }
   char *ws = b_ws.as<char>(), *rs = b_res.as<char>();
   FsOrfDev *d_orf0 = reinterpret_cast<FsOrfDev *>(ws + o_orf0), *d_orf = reinterpret_cast<FsOrfDev *>(rs + R.orf);
   Key *d_okey = reinterpret_cast<Key *>(ws + o_okey);
@@ -511,7 +511,7 @@ int fs_build_windows_device(bath_hip_ctx *ctx, const bath_hip_oprofile *om, cons
   BATH_HIP_TRY(ctx, hipGetLastError());
   // region A now (the one synchronize of this stage), region B behind it on the same stream: it is complete long before the
   // decision's synchronize, which is the next time the host looks
-  char *h = static_cast<char *>(ctx->stage[6].p);
+  char *h = static_cast<char *>(ctx->stage[Pinned::kFsWindowResult].p);
   BATH_HIP_TRY(ctx, hipMemcpyAsync(h, rs, R.a_bytes, hipMemcpyDeviceToHost, s));
   BATH_HIP_TRY(ctx, hipStreamSynchronize(s));
   BATH_HIP_TRY(ctx, hipMemcpyAsync(h + R.a_bytes, rs + R.a_bytes, R.b_end - R.a_bytes, hipMemcpyDeviceToHost, s));
@@ -530,10 +530,10 @@ int fs_build_windows_host(bath_hip_ctx *ctx, const bath_hip_oprofile *om, const 
   *B = FsWinBuild{};
   if (n == 0) return BATH_OK;
   const ResLayout R = res_layout(n);
-  DevBuf &b_res = ctx->scratch[51];
+  DevBuf &b_res = ctx->scratch[Scratch::kFsWindowResult];
   BATH_HIP_TRY(ctx, b_res.reserve(R.bytes + 256));
-  if (ctx->stage[6].reserve(R.bytes + 256) != hipSuccess) { ctx->set_error("cannot allocate page-locked staging memory"); return BATH_EFAIL; }
-  char *h = static_cast<char *>(ctx->stage[6].p);
+  if (ctx->stage[Pinned::kFsWindowResult].reserve(R.bytes + 256) != hipSuccess) { ctx->set_error("cannot allocate page-locked staging memory"); return BATH_EFAIL; }
+  char *h = static_cast<char *>(ctx->stage[Pinned::kFsWindowResult].p);
   FsOrfDev *orfs = reinterpret_cast<FsOrfDev *>(h + R.orf);
   int32_t *grp = reinterpret_cast<int32_t *>(h + R.grp), *vlen = reinterpret_cast<int32_t *>(h + R.vlen);
   int64_t *voff = reinterpret_cast<int64_t *>(h + R.voff);
@@ -624,9 +624,9 @@ int fs_decide(bath_hip_ctx *ctx, const bath_hip_fsprofile *om_fs3, const bath_pi
   const double tau3 = (double)ev3[BATH_FTAUFS3], lambda = (double)ev3[BATH_FLAMBDA];
   if (B.host_built) {
     // the host build decides on the host: libm's exp() and log(), whose last bit the kernel's need not share
-    if (ctx->stage[7].reserve((size_t)B.nw * 6 * sizeof(float) + 64) != hipSuccess) { ctx->set_error("cannot allocate page-locked staging memory"); return BATH_EFAIL; }
-    const float *h_bias = static_cast<const float *>(ctx->stage[7].p);
-    BATH_HIP_TRY(ctx, hipMemcpyAsync(ctx->stage[7].p, d_bias, (size_t)B.nw * 6 * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    if (ctx->stage[Pinned::kFsDecideDown].reserve((size_t)B.nw * 6 * sizeof(float) + 64) != hipSuccess) { ctx->set_error("cannot allocate page-locked staging memory"); return BATH_EFAIL; }
+    const float *h_bias = static_cast<const float *>(ctx->stage[Pinned::kFsDecideDown].p);
+    BATH_HIP_TRY(ctx, hipMemcpyAsync(ctx->stage[Pinned::kFsDecideDown].p, d_bias, (size_t)B.nw * 6 * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
     BATH_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     for (int i = 0; i < B.nw; i++) {
       h_out[i] = B.h_out[i];
@@ -635,7 +635,7 @@ int fs_decide(bath_hip_ctx *ctx, const bath_hip_fsprofile *om_fs3, const bath_pi
     return BATH_OK;
   }
   // the length terms by L3, up to the longest window of the block: kept by the context, extended (and uploaded again) when a block needs more
-  DevBuf &b_len = ctx->scratch[62];
+  DevBuf &b_len = ctx->scratch[Scratch::kFsWindowLenTerms];
   const size_t need = (size_t)std::max(B.maxlen, 0) / 3 + 1;
   if (ctx->fsw_len_terms.size() < need * 2 || !b_len.p) {
     const size_t n = std::max(need, ctx->fsw_len_terms.size());       // (two floats per L3: grows to twice what is asked for)
@@ -648,10 +648,10 @@ int fs_decide(bath_hip_ctx *ctx, const bath_hip_fsprofile *om_fs3, const bath_pi
   hipLaunchKernelGGL(fsw_decide_kernel, dim3((unsigned)((B.nw + 255) / 256)), dim3(256), 0, ctx->stream, B.d_out, B.nw, d_bias, d_fsc, om_fs3->d_logsum,
                      b_len.as<FswLen>(), prm->do_biasfilter, prm->std_pipe, prm->F3, tau3, lambda);
   BATH_HIP_TRY(ctx, hipGetLastError());
-  if (ctx->stage[7].reserve((size_t)B.nw * sizeof(bath_fs_window) + 64) != hipSuccess) { ctx->set_error("cannot allocate page-locked staging memory"); return BATH_EFAIL; }
-  BATH_HIP_TRY(ctx, hipMemcpyAsync(ctx->stage[7].p, B.d_out, (size_t)B.nw * sizeof(bath_fs_window), hipMemcpyDeviceToHost, ctx->stream));
+  if (ctx->stage[Pinned::kFsDecideDown].reserve((size_t)B.nw * sizeof(bath_fs_window) + 64) != hipSuccess) { ctx->set_error("cannot allocate page-locked staging memory"); return BATH_EFAIL; }
+  BATH_HIP_TRY(ctx, hipMemcpyAsync(ctx->stage[Pinned::kFsDecideDown].p, B.d_out, (size_t)B.nw * sizeof(bath_fs_window), hipMemcpyDeviceToHost, ctx->stream));
   BATH_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-  std::memcpy(h_out, ctx->stage[7].p, (size_t)B.nw * sizeof(bath_fs_window));
+  std::memcpy(h_out, ctx->stage[Pinned::kFsDecideDown].p, (size_t)B.nw * sizeof(bath_fs_window));
   return BATH_OK;
 }
 

@@ -664,8 +664,8 @@ static void build_codon_table(const uint8_t basic[64], std::vector<uint8_t> &tab
 int orf_tables_upload(bath_hip_ctx *ctx, int ncbi_table, OrfTablesDev *t, int initiator) {
   const int key = ncbi_table | (initiator << 16);
   t->using_initiators = initiator != BATH_INIT_ANY;
-  if (ctx->orf_tables_id == key && ctx->scratch[28].p) {            // still there from the last call: every query of a database pass asks again
-    t->full = ctx->scratch[28].as<uint8_t>(); t->fwd = t->full + 6144; t->rev = t->fwd + 64; t->comp = t->rev + 64; t->is_init = t->comp + 32;
+  if (ctx->orf_tables_id == key && ctx->scratch[Scratch::kOrfCodonTables].p) {            // still there from the last call: every query of a database pass asks again
+    t->full = ctx->scratch[Scratch::kOrfCodonTables].as<uint8_t>(); t->fwd = t->full + 6144; t->rev = t->fwd + 64; t->comp = t->rev + 64; t->is_init = t->comp + 32;
     return BATH_OK;
   }
   uint8_t basic[64];
@@ -683,7 +683,7 @@ int orf_tables_upload(bath_hip_ctx *ctx, int ncbi_table, OrfTablesDev *t, int in
   static const uint8_t kComp[18] = {3, 2, 1, 0, 4, 6, 5, 8, 7, 9, 10, 14, 13, 12, 11, 15, 16, 17};   // ACGT-RYMKSWHBVDN*~
   std::memcpy(comp, kComp, 18);
   if (bath_gencode_initiators(ncbi_table, initiator, comp + 32) != BATH_OK) { ctx->set_error("no initiation codons for this table / initiator mode"); return BATH_EINVAL; }
-  DevBuf &b = ctx->scratch[28];
+  DevBuf &b = ctx->scratch[Scratch::kOrfCodonTables];
   BATH_HIP_TRY(ctx, b.reserve(host.size()));
   BATH_HIP_TRY(ctx, hipMemcpyAsync(b.p, host.data(), host.size(), hipMemcpyHostToDevice, ctx->stream));
   BATH_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
@@ -752,7 +752,7 @@ extern "C" int bath_hip_translate_orfs_opts(bath_hip_ctx *ctx, const bath_hip_se
   int64_t max_orfs = 0;
   for (int64_t i = 0; i < dna->n; i++) if (dna->h_len[i] >= 15) max_orfs += 6 * (int64_t)((dna->h_len[i] / 3 + 1) / (min_orf_len + 1) + 1);
   const size_t nent = (size_t)dna->ntiles * 6;
-  DevBuf &b_aa = ctx->scratch[24], &b_slots = ctx->scratch[25], &b_orfs = ctx->scratch[26], &b_misc = ctx->scratch[27];
+  DevBuf &b_aa = ctx->scratch[Scratch::kOrfAminoPool], &b_slots = ctx->scratch[Scratch::kOrfSlots], &b_orfs = ctx->scratch[Scratch::kOrfRecords], &b_misc = ctx->scratch[Scratch::kOrfMisc];
   BATH_HIP_TRY(ctx, b_aa.reserve(orf_aa_bytes(dna)));
   BATH_HIP_TRY(ctx, b_slots.reserve(((size_t)dna->ntiles * (size_t)orf_slot_cap(min_orf_len) + 64) * 8));
   BATH_HIP_TRY(ctx, b_orfs.reserve((size_t)(max_orfs + 64) * sizeof(OrfRec)));

@@ -735,10 +735,10 @@ int build_compo_terms(bath_hip_ctx *ctx, bath_hip_oprofile *om) {
 static int wave_grid_blocks(bath_hip_ctx *ctx) { return ctx->prop.multiProcessorCount * 8; }
 
 struct PipelineWork {
-  // device allocations live in ctx->scratch[8..]; this struct only carves them up
+  // the device allocation is Scratch::kCascadeWork; this struct only carves it up
   Cand cand;
   int cand_cap = 0;
-  uint8_t *pool = nullptr;             // the amino-acid streams of bath_orfs.hip (ctx->scratch[24])
+  uint8_t *pool = nullptr;             // the amino-acid streams of bath_orfs.hip (Scratch::kOrfAminoPool)
   int32_t *todo_msv = nullptr, *todo_vit = nullptr, *todo_ssvb = nullptr, *todo_vit2 = nullptr, *todo_fwd = nullptr, *todo_sorted = nullptr;
   int *len_bins = nullptr;
   WindowRec *wins = nullptr;
@@ -862,7 +862,7 @@ static int run_filters(bath_hip_ctx *ctx, const bath_hip_oprofile *om, const bat
   if (prm->strands < 0 || prm->strands > 2 || prm->initiator < 0 || prm->initiator > 2) { ctx->set_error("bath_pipeline_params: strands / initiator out of range"); return BATH_EINVAL; }
   if ((st = orf_tables_upload(ctx, prm->ncbi_table, &tt, prm->initiator)) != BATH_OK) return st;
   if ((st = ensure_emit_table(ctx, om, prm->F1, max_orf)) != BATH_OK) return st;
-  DevBuf &b_tabs = ctx->scratch[8], &b_work = ctx->scratch[9];
+  DevBuf &b_tabs = ctx->scratch[Scratch::kSsvScoreTable], &b_work = ctx->scratch[Scratch::kCascadeWork];
   const size_t ssv_bytes = (size_t)(M + 1) * kKp;
   const size_t tabs_bytes = 8192 + ssv_bytes + 256 + 20 * 4 + 256;
   if (tabs_bytes > b_tabs.cap) ctx->tabs_uid = 0;                 // the buffer is about to be replaced: whatever it held is gone
@@ -914,7 +914,7 @@ static int run_filters(bath_hip_ctx *ctx, const bath_hip_oprofile *om, const bat
   // ---- translation / ORF work-list buffers (bath_orfs.hip)
   if ((st = orf_tiles_ensure(ctx, dna)) != BATH_OK) return st;
   const size_t nent = (size_t)dna->ntiles * 6;
-  DevBuf &b_aa = ctx->scratch[24], &b_slots = ctx->scratch[25], &b_orfs = ctx->scratch[26], &b_misc = ctx->scratch[27];
+  DevBuf &b_aa = ctx->scratch[Scratch::kOrfAminoPool], &b_slots = ctx->scratch[Scratch::kOrfSlots], &b_orfs = ctx->scratch[Scratch::kOrfRecords], &b_misc = ctx->scratch[Scratch::kOrfMisc];
   BATH_HIP_TRY(ctx, b_aa.reserve(orf_aa_bytes(dna)));
   BATH_HIP_TRY(ctx, b_slots.reserve(((size_t)dna->ntiles * (size_t)orf_slot_cap(prm->min_orf_len) + 64) * 8));
   BATH_HIP_TRY(ctx, b_orfs.reserve((size_t)(max_orfs + 64) * sizeof(OrfRec)));
@@ -1030,7 +1030,7 @@ static int run_filters(bath_hip_ctx *ctx, const bath_hip_oprofile *om, const bat
     // 5. F2, local composition re-filter, optional plain Viterbi re-run
     hipLaunchKernelGGL(post_vit_kernel, dim3(dec_blocks), dim3(256), 0, ctx->stream, W.cand, W.cand_cap, W.ctr, P, W.todo_msv /* free by now */, W.todo_fwd);
     if (P.do_bias) {
-      DevBuf &b_compo = ctx->scratch[36];                                       // 20 sums per candidate (the 20 x 256 terms are the profile's)
+      DevBuf &b_compo = ctx->scratch[Scratch::kLocalCompoSums];                                       // 20 sums per candidate (the 20 x 256 terms are the profile's)
       BATH_HIP_TRY(ctx, b_compo.reserve((size_t)W.cand_cap * 20 * 4 + 256));
       float *d_compo = b_compo.as<float>();
       hipLaunchKernelGGL(local_compo_kernel, dim3(16384), dim3(64), 0, ctx->stream, W.cand, W.ctr, M, d_ssvsc, om->d_compo_terms, W.todo_msv, d_compo);
@@ -1047,7 +1047,7 @@ static int run_filters(bath_hip_ctx *ctx, const bath_hip_oprofile *om, const bat
     float *d_keep = nullptr; int64_t *d_keep_off = nullptr;
     if (ctx->keep_fwd_rows) {
       constexpr int64_t kKeepFloats = (int64_t)8 << 20;                        // 32 MB: ~1.4 M residue rows; what does not fit is computed again by the domain stage
-      DevBuf &b_rows = ctx->scratch[38], &b_roff = ctx->scratch[39];
+      DevBuf &b_rows = ctx->scratch[Scratch::kCascadeFwdRows], &b_roff = ctx->scratch[Scratch::kCascadeFwdRowOffsets];
       BATH_HIP_TRY(ctx, b_rows.reserve((size_t)kKeepFloats * sizeof(float) + 64)); BATH_HIP_TRY(ctx, b_roff.reserve((size_t)cap * sizeof(int64_t) + 64));
       d_keep = b_rows.as<float>(); d_keep_off = b_roff.as<int64_t>();
       hipLaunchKernelGGL(fwd_keep_offsets_kernel, dim3(1), dim3(64), 0, ctx->stream, W.todo_fwd, &W.ctr->todo_fwd, W.cand.len, d_keep_off, kKeepFloats);
@@ -1367,7 +1367,7 @@ int fs_gather_view(bath_hip_ctx *ctx, const bath_hip_seqs *dna, std::vector<FsWi
   const int nw = (int)regs.size();
   int64_t pool_bytes = 0;
   for (FsWinDev &d : regs) { d.dst_off = pool_bytes; pool_bytes += ((int64_t)d.len + 15) / 16 * 16 + 16; }
-  DevBuf &b_pool = ctx->scratch[29], &b_desc = ctx->scratch[30];
+  DevBuf &b_pool = ctx->scratch[Scratch::kFsGatherPool], &b_desc = ctx->scratch[Scratch::kFsGatherDesc];
   BATH_HIP_TRY(ctx, b_pool.reserve((size_t)pool_bytes + 256));
   const size_t desc_bytes = ((size_t)nw * sizeof(FsWinDev) + 255) / 256 * 256;
   BATH_HIP_TRY(ctx, b_desc.reserve(desc_bytes + (size_t)nw * 12 + 64));          // descriptors, then the view's off[] and len[]
@@ -1397,7 +1397,7 @@ int fs_gather_view(bath_hip_ctx *ctx, const bath_hip_seqs *dna, std::vector<FsWi
 // len[] are already there; only the pool is reserved and the copy kernel launched
 int fs_gather_view_built(bath_hip_ctx *ctx, const bath_hip_seqs *dna, const FsWinBuild &B, const uint8_t *d_comp, bath_hip_seqs *view, const FsWinDev **d_desc_out) {
   const int nw = B.nw;
-  DevBuf &b_pool = ctx->scratch[56];                                          // its own pool, apart from the one the domain stage gathers into (scratch[29])
+  DevBuf &b_pool = ctx->scratch[Scratch::kFsWindowPool];             // its own pool, apart from the one the domain stage gathers into (kFsGatherPool)
   BATH_HIP_TRY(ctx, b_pool.reserve((size_t)B.pool_bytes + 256));
   BATH_HIP_TRY(ctx, hipMemsetAsync(b_pool.p, 0x1d, (size_t)B.pool_bytes + 256, ctx->stream));
   hipLaunchKernelGGL(fs_window_gather_kernel, dim3((unsigned)std::max(1, std::min(nw, 65535))), dim3(256), 0, ctx->stream, dna->d_data, B.d_desc, nw, d_comp, b_pool.as<uint8_t>());
@@ -1469,7 +1469,7 @@ static int select_survivors(bath_hip_ctx *lane, const FilterState &S, bool want_
   const int nc = S.hc.cand_count;
   if (nc <= 0) return BATH_OK;
   const int nwins = want_wins ? std::min(S.hc.win_count, S.W.win_cap) : 0;
-  DevBuf &b_sel = lane->scratch[32];
+  DevBuf &b_sel = lane->scratch[Scratch::kSurvivorSelect];
   const size_t o_c = 256, o_w = o_c + ((size_t)nc * sizeof(FsCandRec) + 255) / 256 * 256;
   BATH_HIP_TRY(lane, b_sel.reserve(o_w + (size_t)std::max(nwins, 1) * sizeof(WindowRec) + 256));
   int *d_cnt = b_sel.as<int>();
@@ -1607,7 +1607,7 @@ extern "C" int bath_hip_pipeline_frameshift(bath_hip_ctx *ctx, const bath_hip_op
   ctx->fs_std_pool = sv.pool;
   if (nw > 0) {
     // ---- the windows' copies, bias filter and 3-codon frameshift Forward for all of them
-    DevBuf &b_out = ctx->scratch[31];
+    DevBuf &b_out = ctx->scratch[Scratch::kFsWindowBias];
     bath_hip_seqs view;
     const FsWinDev *d_desc = nullptr;
     if ((st = fs_gather_view_built(ctx, dna, B, S.tt.comp, &view, &d_desc)) != BATH_OK) return st;   // descriptors, offsets and lengths are on the device
@@ -1641,7 +1641,7 @@ extern "C" int bath_hip_pipeline_frameshift(bath_hip_ctx *ctx, const bath_hip_op
     // ---- scores -> P-values -> branch (fsw_decide_kernel); the host reads the completed records once and keeps the bookkeeping:
     // pos_past_fwd, and the ORFs of the windows that take the standard branch (:1479-1487), from the ordered ORF list
     if ((st = fs_join(ctx)) != BATH_OK) return st;                            // the bias kernel's side stream
-    if ((st = fs_decide(ctx, om_fs3, &prm, B, b_out.as<float>(), ctx->scratch[12].as<float>(), h_fsc.data(), out.data())) != BATH_OK) return st;
+    if ((st = fs_decide(ctx, om_fs3, &prm, B, b_out.as<float>(), ctx->scratch[Scratch::kFs3FwdScores].as<float>(), h_fsc.data(), out.data())) != BATH_OK) return st;
     clk.lap("fs:   gather + bias + 3-codon Forward + branch decision (device)");
     std::vector<char> aligned((size_t)std::max(nc, 1), 0);                   // oxf_holder[i] == NULL: an overlapping window already took the ORF (:1485)
     for (int i = 0; i < nw; i++) {
@@ -1703,7 +1703,7 @@ extern "C" int bath_hip_vitfilter_bath(bath_hip_ctx *ctx, const bath_hip_oprofil
   std::vector<uint8_t> ssv_scores((size_t)(M + 1) * kKp, 0);
   bath_hip_oprofile_get_ssv_scores(om, ssv_scores.data());
   const int cap = (int)std::min<int64_t>((int64_t)1 << 26, sq->total / 2 + 16 * n + 1024);      // a window ends at least one residue after the last
-  DevBuf &b = ctx->scratch[9];
+  DevBuf &b = ctx->scratch[Scratch::kFilterBathWork];
   // The cascade's switch (run_filters): a batch as large as the ORFs of a block of lane_min_nt() nucleotides takes the lane-per-target
   // kernel through launch_vit_sorted, on an identity work list whose count lives on the device like the cascade's; smaller ones the
   // wave-per-target kernel.  Which one ran is left as the call's one kernel span (bath_hip_kernel_times).
@@ -1766,7 +1766,7 @@ extern "C" int bath_hip_ssvfilter_bath(bath_hip_ctx *ctx, const bath_hip_oprofil
   std::vector<uint8_t> ssv_scores((size_t)(M + 1) * kKp, 0);
   bath_hip_oprofile_get_ssv_scores(om, ssv_scores.data());
   const int cap = (int)std::min<int64_t>((int64_t)1 << 26, sq->total / 2 + 16 * n + 1024);
-  DevBuf &b = ctx->scratch[9];
+  DevBuf &b = ctx->scratch[Scratch::kFilterBathWork];
   const size_t o_todo = 0, o_km = o_todo + (size_t)n * 4, o_ctr = (o_km + (size_t)n * 8 + 255) / 256 * 256, o_ssv = o_ctr + 256 + sizeof(Counters),
                o_w = (o_ssv + ssv_scores.size() + 255) / 256 * 256, total = o_w + (size_t)cap * sizeof(WindowRec);
   BATH_HIP_TRY(ctx, b.reserve(total + 256));

@@ -43,7 +43,7 @@ __global__ void record_build_kernel(Cand cand, const unsigned *__restrict__ idx,
 int build_orf_records(bath_hip_ctx *ctx, const Cand &cand, int nc, int64_t window_offset, bath_orf_result **d_out, int64_t *n_out) {
   *d_out = nullptr; *n_out = 0;
   if (nc <= 0) return BATH_OK;
-  DevBuf &b_keys = ctx->scratch[33], &b_tmp = ctx->scratch[34], &b_rec = ctx->scratch[35];
+  DevBuf &b_keys = ctx->scratch[Scratch::kRecordKeys], &b_tmp = ctx->scratch[Scratch::kRecordSortTemp], &b_rec = ctx->scratch[Scratch::kRecords];
   const size_t n = (size_t)nc;
   const size_t o_k1 = 256, o_k2 = o_k1 + (n * 8 + 255) / 256 * 256, o_i1 = o_k2 + (n * 8 + 255) / 256 * 256, o_i2 = o_i1 + (n * 4 + 255) / 256 * 256;
   BATH_HIP_TRY(ctx, b_keys.reserve(o_i2 + n * 4 + 256));

@@ -75,13 +75,13 @@ int std_region_ensembles_device(bath_hip_ctx *ctx, const bath_hip_oprofile *om, 
   std::memcpy(up.data() + o_order, order.data(), (size_t)n * 4);
   std::memcpy(up.data() + o_poff, run->poff.data(), ((size_t)n + 1) * 8);
   for (int64_t e = 0; e < n; e++) fs_ensemble_start_states(seed, up.data() + o_states + (size_t)e * kEnsSamples);   // one jump-ahead per trace
-  DevBuf &b_up = ctx->scratch[60], &b_out = ctx->scratch[61];
+  DevBuf &b_up = ctx->scratch[Scratch::kStdEnsembleUpload], &b_out = ctx->scratch[Scratch::kStdEnsembleOut];
   const size_t out_words = (size_t)n * kStdEnsOutInts + (size_t)run->poff[(size_t)n];
   BATH_HIP_TRY(ctx, b_up.reserve(up_words * 4 + 64));
   BATH_HIP_TRY(ctx, b_out.reserve(out_words * 4 + 64));
   int st;
-  if ((st = ctx->stage_upload(10, b_up.p, up.data(), up_words, ctx->stream)) != BATH_OK) return st;
-  if (ctx->stage[11].reserve(out_words * 4 + 64) != hipSuccess) { ctx->set_error("cannot allocate page-locked memory for the ensembles' segments"); return BATH_EFAIL; }
+  if ((st = ctx->stage_upload(Pinned::kStdEnsembleUpload, b_up.p, up.data(), up_words, ctx->stream)) != BATH_OK) return st;
+  if (ctx->stage[Pinned::kStdEnsembleOut].reserve(out_words * 4 + 64) != hipSuccess) { ctx->set_error("cannot allocate page-locked memory for the ensembles' segments"); return BATH_EFAIL; }
   uint32_t *d_up = b_up.as<uint32_t>();
   int32_t *d_out = b_out.as<int32_t>();
   uint32_t *d_path = reinterpret_cast<uint32_t *>(d_out + (size_t)n * kStdEnsOutInts);
@@ -92,8 +92,8 @@ int std_region_ensembles_device(bath_hip_ctx *ctx, const bath_hip_oprofile *om, 
                      FsJobs{reinterpret_cast<const int32_t *>(d_up + o_order), d_up});
   ctx->span_end(s1, ctx->stream);
   BATH_HIP_TRY(ctx, hipGetLastError());
-  BATH_HIP_TRY(ctx, hipMemcpyAsync(ctx->stage[11].p, b_out.p, out_words * 4, hipMemcpyDeviceToHost, ctx->stream));
-  run->out = ctx->stage[11].as<int32_t>();
+  BATH_HIP_TRY(ctx, hipMemcpyAsync(ctx->stage[Pinned::kStdEnsembleOut].p, b_out.p, out_words * 4, hipMemcpyDeviceToHost, ctx->stream));
+  run->out = ctx->stage[Pinned::kStdEnsembleOut].as<int32_t>();
   run->path = reinterpret_cast<const uint32_t *>(run->out + (size_t)n * kStdEnsOutInts);
   return BATH_OK;
 }
