@@ -359,6 +359,9 @@ ABI = {
     "bath_hmm_max_length": (C.c_int, [C.POINTER(_Hmm), C.c_double]),
     "bath_hip_calibrate_fs": (C.c_int, [_vp, C.POINTER(_Hmm), C.c_int, C.POINTER(C.c_uint32), C.c_int, C.c_int, C.c_double,
                                         C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "bath_calib_sample_batch": (C.c_int, [C.POINTER(C.c_uint32), _f32p, C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, _u8p]),
+    "bath_hip_calibrate_fs_batch": (C.c_int, [_vp, C.POINTER(C.POINTER(_Hmm)), C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_uint32), C.c_int, C.c_int,
+                                              C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     # single-sequence models and their calibration (bathbuild)
     "bath_scorematrix_builtin": (C.c_char_p, [C.c_char_p]),
     "bath_scoresystem_create": (C.c_int, [C.c_char_p, C.c_char_p, C.c_double, C.c_double, C.POINTER(_vp), C.c_char_p, C.c_int]),
@@ -1814,6 +1817,43 @@ def calibrate_fs(ctx, hmm, ncbi_table, state, L=CALIB_L, N=CALIB_N, tailp=CALIB_
     if want_xv and arith != "strict":
         return t3.value, t5.value, st.value, x3, x5, [re2[0], re2[1]]
     return (t3.value, t5.value, st.value, x3, x5) if want_xv else (t3.value, t5.value, st.value)
+
+
+CALIB_BATCH_MAX = 64                                                  # BATH_CALIB_BATCH_MAX: models per calibrate_fs_batch call
+
+
+def calib_sample_batch(state, ncbi_tables, L=CALIB_L, N=CALIB_N, f=None):
+    """The stream that len(ncbi_tables) successive calibrate_fs calls draw, in their order: per model its 3-codon set, then its
+    5-codon set, each model with its own table.  (codes [n, 2, N, 3L], the generator's state afterwards); on error the state the
+    caller holds is what it was."""
+    tabs = np.ascontiguousarray(ncbi_tables, dtype=np.int32).reshape(-1)
+    st = C.c_uint32(state)
+    dna = np.zeros((len(tabs), 2, N, 3 * L), dtype=np.uint8)
+    fa = None if f is None else np.ascontiguousarray(f, dtype=np.float32)
+    assert fa is None or fa.shape == (20,)
+    if lib().bath_calib_sample_batch(C.byref(st), _f32(fa), tabs.ctypes.data_as(C.POINTER(C.c_int)), len(tabs), L, N, _u8(dna) if dna.size else _u8(np.zeros(1, np.uint8))) != OK:
+        raise BathError("calib_sample_batch failed: an unknown translation table among %s, or a residue without a codon in one" % (list(map(int, tabs)),))
+    return dna, st.value
+
+
+def calibrate_fs_batch(ctx, hmms, ncbi_tables, state, L=CALIB_L, N=CALIB_N, tailp=CALIB_TAILP, want_xv=False):
+    """calibrate_fs of several models (at most CALIB_BATCH_MAX) with the windows of all of them in each parser launch: what
+    len(hmms) successive calibrate_fs calls with the state carried return, bit for bit, strict arithmetic only.
+    (tau3 [n], tau5 [n], the generator's state afterwards), with want_xv also the bit scores xv3 [n, N], xv5 [n, N].  All or
+    nothing: a BathError names the position in the batch of the model it is about, and the caller's state is what it was."""
+    hmms = list(hmms)
+    n = len(hmms)
+    tabs = np.ascontiguousarray(ncbi_tables, dtype=np.int32).reshape(-1)
+    if len(tabs) != n:
+        raise ValueError("calibrate_fs_batch: %d models, %d translation tables" % (n, len(tabs)))
+    st = C.c_uint32(state)
+    ptrs = (C.POINTER(_Hmm) * max(n, 1))(*[h._p for h in hmms])
+    t3, t5 = np.zeros(max(n, 1), np.float64), np.zeros(max(n, 1), np.float64)
+    x3 = np.zeros((max(n, 1), N), np.float64) if want_xv else None
+    x5 = np.zeros((max(n, 1), N), np.float64) if want_xv else None
+    ctx._check(lib().bath_hip_calibrate_fs_batch(ctx._h, ptrs, tabs.ctypes.data_as(C.POINTER(C.c_int)), n, C.byref(st), L, N, tailp, _f64p(t3), _f64p(t5),
+                                                 None if x3 is None else _f64p(x3), None if x5 is None else _f64p(x5)), "calibrate_fs_batch")
+    return (t3[:n], t5[:n], st.value, x3[:n], x5[:n]) if want_xv else (t3[:n], t5[:n], st.value)
 
 
 # ---- single-sequence models and their calibration: what bath_amd.bathbuild calls

@@ -1,6 +1,6 @@
 """bathconvert: HMMER3 or BATH model files to the BATH format bathsearch takes, the frameshift taus fitted on the GPU.
 
-    python -m bath_amd.bathconvert [--ct N] [--arith strict|odds3|odds] <hmmfile_out> <hmmfile_in>
+    python -m bath_amd.bathconvert [--ct N] [--arith strict|odds3|odds] [--batch N] <hmmfile_out> <hmmfile_in>
 
 What bathconvert.c does: per model of a HMMER3/f or BATH3/f file, the codon table is --ct if given, else the file's, else 1; the
 FS3 and FS5 Forward taus are fitted by simulation (bath_amd.calibrate_fs: p7_fs_Tau_3codons then p7_fs_Tau_5codons, one generator
@@ -13,6 +13,12 @@ that is the input -- is refused by name, status 1.  One context on one device, c
 --arith (an extension) chooses the arithmetic of the two Forward parsers a fit runs (bath_amd.ARITH_MODES): strict, the default,
 today's output byte for byte; odds3, the 3-codon parser in fp32 odds ratios; odds, both parsers, which is what the reference's own
 bathconvert runs (with its redraw of a sequence whose parser overflows).  A file whose taus are kept is not touched by it.
+
+--batch N (an extension, 1..64, default 1: today's path call for call) fits up to N models with one bath_amd.calibrate_fs_batch:
+the models that need a fit are collected in file order, the windows of all of them go into each parser launch, and models whose
+taus are kept pass through between them.  The generator is carried in file order as always, so the output file and the summary
+lines are the bytes of --batch 1; one batch of models is alive at a time.  Strict arithmetic only: with --arith odds3 or odds it
+is refused by name.
 """
 import os
 import re
@@ -46,7 +52,8 @@ def parse_args(argv):
 
 
 def parse_options(argv):
-    """(--ct or None, hmmfile_out, hmmfile_in, {"arith": "strict" | "odds3" | "odds"}): what run() reads."""
+    """(--ct or None, hmmfile_out, hmmfile_in, {"arith": "strict" | "odds3" | "odds"}): what run() reads.  The dictionary has
+    "batch": N only when --batch was given (absent: 1)."""
     ct, pos, i, opts = None, [], 0, {"arith": "strict"}
     while i < len(argv):
         a = argv[i]
@@ -54,7 +61,7 @@ def parse_options(argv):
             name, val = (a.split("=", 1) + [None])[:2] if a.startswith("--") and "=" in a else (a, None)
             if name == "-h":
                 raise UsageError("option -h is not supported by this bathconvert: %s" % USAGE)
-            if name not in ("--ct", "--arith"):
+            if name not in ("--ct", "--arith", "--batch"):
                 raise UsageError("unknown option %s" % name)
             if val is None:
                 i += 1
@@ -67,6 +74,16 @@ def parse_options(argv):
                 opts["arith"] = val
                 i += 1
                 continue
+            if name == "--batch":
+                try:
+                    batch = int(val)
+                except ValueError:
+                    raise UsageError("option --batch: bad argument %r" % (val,))
+                if not 1 <= batch <= ba.CALIB_BATCH_MAX:
+                    raise UsageError("option --batch: %d is not in 1..%d" % (batch, ba.CALIB_BATCH_MAX))
+                opts["batch"] = batch
+                i += 1
+                continue
             try:
                 ct = int(val)
             except ValueError:
@@ -76,6 +93,9 @@ def parse_options(argv):
         else:
             pos.append(a)
         i += 1
+    if opts.get("batch", 1) > 1 and opts["arith"] != "strict":
+        raise UsageError("option --batch: several models per launch are fitted in strict arithmetic only, not with --arith %s "
+                         "(its redraw makes a model's samples depend on the scores of the model before it)" % opts["arith"])
     if len(pos) != 2:
         raise UsageError("Incorrect number of command line arguments: %s" % USAGE)
     return ct, pos[0], pos[1], opts
@@ -253,6 +273,26 @@ def run(argv, stdout=None, device=0):
     ctx, state, out = None, ba.rng_state(ba.CALIB_SEED), []          # one generator per file (bathconvert.c:128)
     scratch = tempfile.TemporaryDirectory()
     one = os.path.join(scratch.name, "model.hmm")
+    batch = opts.get("batch", 1)
+    # --batch N > 1: the models read since the last fit, in file order -- [index, text, plan, MAXL, entropy, the model if it awaits
+    # a fit].  A model whose taus are kept waits here only as text, for its place in the output.
+    waiting = []
+
+    def fit_waiting():
+        nonlocal ctx, state
+        fits = [w for w in waiting if w[5] is not None]
+        taus = {}
+        if fits:
+            if ctx is None:
+                ctx = ba.Context(device)
+            t3, t5, state = ba.calibrate_fs_batch(ctx, [w[5] for w in fits], [w[2]["ct"] for w in fits], state)
+            taus = {w[0]: (float(a), float(b)) for w, a, b in zip(fits, t3, t5)}
+        for i, model, p, maxl, entropy, _ in waiting:
+            tau3, tau5 = taus.get(i, (p["tau3"], p["tau5"]))
+            out.append(rewrite_model(model, p["ct"], tau3, tau5, maxl))
+            stdout.write(result_line(i + 1, p, entropy))
+        del waiting[:]
+
     try:
         for i, (model, p) in enumerate(zip(models, plans)):
             with open(one, "wb") as fh:                              # the library reads model <index> of a file from the file's start:
@@ -261,6 +301,12 @@ def run(argv, stdout=None, device=0):
                 hmm = ba.HMM(one, 0)
             except ba.BathError:
                 raise ba.BathError("model %d (%s) of %s cannot be read" % (i + 1, p["name"], path_in))
+            if batch > 1:
+                maxl = ba.hmm_max_length(hmm, W_BETA) if p["need_maxl"] else None
+                waiting.append([i, model, p, maxl, mean_match_relative_entropy(hmm), hmm if p["fit"] else None])
+                if sum(w[5] is not None for w in waiting) in (0, batch):     # nothing to wait for, or a full batch
+                    fit_waiting()
+                continue
             tau3, tau5 = p["tau3"], p["tau5"]
             if p["fit"]:
                 if ctx is None:
@@ -269,6 +315,7 @@ def run(argv, stdout=None, device=0):
             maxl = ba.hmm_max_length(hmm, W_BETA) if p["need_maxl"] else None
             out.append(rewrite_model(model, p["ct"], tau3, tau5, maxl))
             stdout.write(result_line(i + 1, p, mean_match_relative_entropy(hmm)))
+        fit_waiting()
         with open(path_out, "wb") as fh:
             fh.write("".join(out).encode(ENC))
     except (ba.BathError, OSError) as e:

@@ -13,6 +13,8 @@
 // Where it runs.  The two parsers are the device's work (bath_hip_fs3_forward_parser; bath_hip_fs5_forward_parser, the score-only
 // instantiation of the regions' chain kernel).  The sampler is a strictly serial consumer of one random-number stream carried from
 // model to model (2 x 200 x 200 steps per model) and its output is 60 KB per parser: host code.  So are the fit (200 numbers) and MAXL.
+// bath_hip_calibrate_fs_batch fits several models with the windows of all of them in each parser launch (the batch kernels of
+// bath_fs_chain.hip); it is told where it stands, behind the single-model calls.
 //
 // easel is not part of the reference tree, so esl_rsq_xfIID, esl_rnd_FChoose, esl_rnd_Roll, esl_stats_DMean, esl_gumbel_FitComplete
 // and esl_gumbel_invcdf are restated from their published behaviour, as bath_ensemble.hip restates the generator.  The reference
@@ -20,12 +22,18 @@
 // overflow, so bath_hip_calibrate_fs redraws nothing.  bath_hip_calibrate_fs_arith runs the parsers in the reference's odds-ratio
 // arithmetic (bath_hip_fs3_forward_parser in BATH_LOGSUM_ODDS, bath_hip_fs5_forward_parser_odds) and there the redraw applies:
 // bath_calib_fit_scores is that loop, host code around a batch scoring callback.
+#include <algorithm>
+#include <atomic>
 #include <cmath>
 #include <cstdint>
 #include <cstring>
+#include <string>
+#include <thread>
 #include <vector>
 
 #include "bath_common.hpp"
+#include "bath_fs_device.hpp"
+#include "bath_host_threads.hpp"
 #include "bath_launch.hpp"
 #include "host_model.hpp"
 
@@ -355,6 +363,182 @@ static int calibrate_fs_strict(bath_hip_ctx *ctx, const bath_hmm *hmm, int ncbi_
       xv[i] = (sc[(size_t)i] - nullsc) / 0.69314718055994529;    // evalues.c:649: float difference, double quotient
     }
     if ((st = bath_calib_tau(xv, N, lambda, tailp, pass == 0 ? tau3 : tau5)) != BATH_OK) { ctx->set_error("calibrate_fs: the Gumbel fit did not converge"); return st; }
+  }
+  *rng_state = state;
+  return BATH_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// Several models per launch.  One model's 2 x N windows give each of its two parser launches N blocks of one working wave on as many
+// CUs, and a launch lasts L x t_row whatever the other CUs could do meanwhile.  In strict arithmetic nothing a kernel
+// computes feeds the generator, so the samples of a whole batch can be drawn before the first launch (bath_calib_sample_batch: the
+// stream that successive bath_hip_calibrate_fs calls would draw, in their order), every profile built and uploaded, and the windows of
+// all models scored by one launch per parser and per tiling present (fs3_fwd_batch_kernel, fs5_fwd_parser_batch_kernel: a block reads
+// its model's FsBatchModel at blockIdx.y): the 3-codon launches on the context's stream, the 5-codon ones beside them on its side
+// stream, one synchronize, then the fits.  The result is defined by what it equals -- the serial calls, bit for bit -- because every
+// window's arithmetic is the single-model kernel's own source and a window's score depends on nothing but its model and itself.
+// ---------------------------------------------------------------------------------------------------------------------------
+extern "C" int bath_calib_sample_batch(uint32_t *rng_state, const float *f, const int *ncbi_tables, int n_models, int L, int N, uint8_t *dna) {
+  if (!rng_state || !ncbi_tables || !dna || n_models < 0 || L < 0 || N < 0) return BATH_EINVAL;
+  uint32_t state = *rng_state;
+  const size_t set = (size_t)N * 3 * L;
+  for (int k = 0; k < n_models; k++)
+    for (int pass = 0; pass < 2; pass++) {                   // bathconvert.c:157-161: a model's 3-codon set, then its 5-codon set
+      const int st = bath_calib_sample(&state, f, ncbi_tables[k], L, N, dna + ((size_t)k * 2 + pass) * set);
+      if (st != BATH_OK) return st;
+    }
+  *rng_state = state;
+  return BATH_OK;
+}
+
+namespace {
+// the profiles and the windows of a batch, freed however the call ends
+struct CalibBatch {
+  std::vector<bath_fs_profile *> gm;
+  std::vector<bath_hip_fsprofile *> om;
+  bath_hip_seqs *sq = nullptr;
+  ~CalibBatch() {
+    if (sq) bath_hip_seqs_destroy(sq);
+    for (bath_hip_fsprofile *o : om) if (o) bath_hip_fsprofile_destroy(o);
+    for (bath_fs_profile *g : gm) if (g) bath_fs_profile_destroy(g);
+  }
+};
+}  // namespace
+
+extern "C" int bath_hip_calibrate_fs_batch(bath_hip_ctx *ctx, const bath_hmm *const *hmms, const int *ncbi_tables, int n_models,
+                                           uint32_t *rng_state, int L, int N, double tailp,
+                                           double *tau3, double *tau5, double *xv3, double *xv5) {
+  if (!ctx) return BATH_EINVAL;
+  // ---- 1. everything that can be refused, before anything is drawn or written
+  if (n_models < 1 || n_models > BATH_CALIB_BATCH_MAX) { ctx->set_error("calibrate_fs_batch: a batch holds 1 to " + std::to_string(BATH_CALIB_BATCH_MAX) + " models (this one " + std::to_string(n_models) + ")"); return BATH_EINVAL; }
+  if (!hmms || !ncbi_tables || !rng_state || !tau3 || !tau5 || L < 2 || N < 2 || !(tailp > 0. && tailp < 1.)) { ctx->set_error("calibrate_fs_batch: needs models, their tables, a generator state, L >= 2, N >= 2 and 0 < tailp < 1"); return BATH_EINVAL; }
+  std::vector<uint8_t> basic((size_t)n_models * 64);
+  for (int k = 0; k < n_models; k++) {
+    const std::string who = "calibrate_fs_batch: model at position " + std::to_string(k) + " of the batch: ";
+    if (!hmms[k] || hmms[k]->M < 1) { ctx->set_error(who + "no model"); return BATH_EINVAL; }
+    if (hmms[k]->M > kFsMaxNodes) { ctx->set_error(who + "frameshift kernels support models up to " + std::to_string(kFsMaxNodes) + " nodes (this one has " + std::to_string(hmms[k]->M) + ")"); return BATH_EINVAL; }
+    if (bath_gencode_basic(ncbi_tables[k], &basic[(size_t)k * 64]) != BATH_OK) { ctx->set_error(who + "unknown NCBI translation table " + std::to_string(ncbi_tables[k])); return BATH_EINVAL; }
+  }
+  BATH_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  ctx->spans_reset();                                      // bath_hip_kernel_times afterwards: the batch's launches
+  // ---- 2. the samples: [model][3-codon set, 5-codon set][N][3L]
+  const int sets = 2 * n_models;
+  const int64_t nwin = (int64_t)sets * N, L3 = 3 * (int64_t)L;
+  std::vector<uint8_t> dna((size_t)nwin * L3);
+  uint32_t state = *rng_state;
+  for (int k = 0; k < n_models; k++) {                     // (model by model only to name the one whose table fails)
+    if (bath_calib_sample_batch(&state, kAminoBg, ncbi_tables + k, 1, L, N, dna.data() + (size_t)k * 2 * N * L3) != BATH_OK) {
+      ctx->set_error("calibrate_fs_batch: model at position " + std::to_string(k) + " of the batch: translation table " + std::to_string(ncbi_tables[k]) + " has no codon for a background residue");
+      return BATH_EINVAL;
+    }
+  }
+  // ---- 3. the 2 x n_models profiles: built on host threads (independent of each other, host code), uploaded by this one
+  CalibBatch B;
+  B.gm.assign((size_t)sets, nullptr); B.om.assign((size_t)sets, nullptr);
+  {
+    std::vector<int> status((size_t)sets, BATH_OK);
+    std::atomic<int> next{0};
+    auto build = [&] {
+      for (int s = next.fetch_add(1); s < sets; s = next.fetch_add(1))
+        status[(size_t)s] = bath_fs_profile_config(hmms[s / 2], &basic[(size_t)(s / 2) * 64], s % 2 == 0 ? 3 : 5, L, &B.gm[(size_t)s]);
+    };
+    const int T = std::min(sets, host_thread_count());
+    if (T <= 1) build();
+    else {
+      std::vector<std::thread> th;
+      for (int t = 0; t < T; t++) th.emplace_back(build);
+      for (std::thread &t : th) t.join();
+    }
+    for (int s = 0; s < sets; s++)
+      if (status[(size_t)s] != BATH_OK) { ctx->set_error("calibrate_fs_batch: model at position " + std::to_string(s / 2) + " of the batch: the profile cannot be configured"); return status[(size_t)s]; }
+  }
+  for (int s = 0; s < sets; s++) {
+    int st = bath_hip_fsprofile_convert(ctx, B.gm[(size_t)s], &B.om[(size_t)s]);
+    if (st == BATH_OK) st = B.om[(size_t)s]->ensure_len(L + 1);
+    if (st != BATH_OK) return st;
+    bath_fs_profile_destroy(B.gm[(size_t)s]); B.gm[(size_t)s] = nullptr;      // (a 5-codon profile of 1280 nodes is 7 MB on the host)
+  }
+  {
+    std::vector<int64_t> off((size_t)nwin + 1);
+    for (int64_t i = 0; i <= nwin; i++) off[(size_t)i] = i * L3;
+    const int st = bath_hip_seqs_create(ctx, dna.data(), off.data(), nwin, &B.sq);
+    if (st != BATH_OK) return st;
+  }
+  // ---- 4. the grouped launches.  One buffer: a job counter per set, the job order (every window of a set has the set's length:
+  // the identity), the descriptors -- the 3-codon sets' by tiling, then the 5-codon sets' by tiling -- and behind them the scores
+  std::vector<int> by_tiling((size_t)n_models);
+  for (int k = 0; k < n_models; k++) by_tiling[(size_t)k] = k;
+  auto tiling = [&](int k) { return BATH_TILING_PICK(BATH_FS_COLUMNS, hmms[k]->M); };
+  std::stable_sort(by_tiling.begin(), by_tiling.end(), [&](int a, int b) { return tiling(a) < tiling(b); });
+  const size_t o_order = (size_t)sets * sizeof(unsigned), o_desc = (o_order + (size_t)N * sizeof(int32_t) + 15) / 16 * 16;
+  const size_t o_sc = o_desc + (size_t)sets * sizeof(FsBatchModel), total = o_sc + (size_t)nwin * sizeof(float);
+  DevBuf &b_work = ctx->scratch[Scratch::kCalibBatchWork];
+  BATH_HIP_TRY(ctx, b_work.reserve(total));
+  char *d_base = b_work.as<char>();
+  float *d_sc = reinterpret_cast<float *>(d_base + o_sc);
+  std::vector<char> up(o_sc, 0);
+  for (int i = 0; i < N; i++) reinterpret_cast<int32_t *>(up.data() + o_order)[i] = i;
+  const SeqView all = B.sq->view();
+  for (int pass = 0; pass < 2; pass++)
+    for (int j = 0; j < n_models; j++) {
+      const int k = by_tiling[(size_t)j], s = 2 * k + pass;
+      const bath_hip_fsprofile *om = B.om[(size_t)s];
+      FsBatchModel m{};
+      m.dna = SeqView{all.data, all.off + (int64_t)s * N, all.len + (int64_t)s * N, N, nullptr};
+      m.p = FsDev{om->M, om->pitch, om->maxcodons, om->d_rsc, om->d_tf, om->d_tb, om->d_logsum};
+      m.loop_tab = om->d_loop[0]; m.move_tab = om->d_move[0];
+      m.sc = d_sc + (int64_t)s * N;
+      m.jobs = FsJobs{reinterpret_cast<const int32_t *>(d_base + o_order), reinterpret_cast<unsigned *>(d_base) + s};
+      m.cfg_len = L;
+      std::memcpy(up.data() + o_desc + ((size_t)pass * n_models + j) * sizeof(FsBatchModel), &m, sizeof m);
+    }
+  int st = ctx->stage_upload(Pinned::kCalibBatchUpload, d_base, up.data(), up.size(), ctx->stream);
+  if (st != BATH_OK) return st;
+  if ((st = fs_fork(ctx)) != BATH_OK) return st;            // the 5-codon launches on the side stream, beside the 3-codon ones
+  const float tE = (float)-0.69314718055994529;             // multihit (modelconfig.c:825-831)
+  const FsBatchModel *d_desc = reinterpret_cast<const FsBatchModel *>(d_base + o_desc);
+  for (int pass = 0; pass < 2; pass++) {
+    hipStream_t stream = pass == 0 ? ctx->stream : ctx->side_stream;
+    for (int j0 = 0; j0 < n_models;) {
+      const int Cv = tiling(by_tiling[(size_t)j0]);
+      int j1 = j0, Mmax = 0;
+      double nodes = 0.;
+      for (; j1 < n_models && tiling(by_tiling[(size_t)j1]) == Cv; j1++) { const int M = hmms[by_tiling[(size_t)j1]]->M; Mmax = std::max(Mmax, M); nodes += M; }
+      const int sp = ctx->span_begin(pass == 0 ? "fs3_fwd_batch_kernel" : "fs5_fwd_parser_batch_kernel", stream, nodes * N * (double)L3, (double)(j1 - j0) * N * (double)L3);
+      st = pass == 0 ? launch_fs3_fwd_batch(ctx, stream, d_desc + j0, j1 - j0, Mmax, Cv, N, tE, tE)
+                     : launch_fs5_fwd_parser_batch(ctx, stream, d_desc + n_models + j0, j1 - j0, Mmax, Cv, N, tE, tE);
+      ctx->span_end(sp, stream);
+      if (st != BATH_OK) break;
+      j0 = j1;
+    }
+    if (st != BATH_OK) break;
+  }
+  const int stj = fs_join(ctx);                            // (also after a refused launch: the context's streams stay in step)
+  // ---- 5. one synchronize, then the fits
+  std::vector<float> sc((size_t)nwin);
+  if (st == BATH_OK && stj == BATH_OK && hipMemcpyAsync(sc.data(), d_sc, (size_t)nwin * sizeof(float), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) { ctx->set_error("calibrate_fs_batch: cannot copy the scores"); st = BATH_EFAIL; }
+  BATH_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  if (st != BATH_OK) return st;
+  if (stj != BATH_OK) return stj;
+  const float nullsc = bath_bg_fs_nullone(L);
+  std::vector<double> xv((size_t)nwin), taus((size_t)sets);
+  for (int s = 0; s < sets; s++) {
+    const int cl = s % 2 == 0 ? 3 : 5;
+    double *x = &xv[(size_t)s * N];
+    for (int i = 0; i < N; i++) {
+      const float v = sc[(size_t)s * N + i];
+      if (!std::isfinite(v)) { ctx->set_error("calibrate_fs_batch: model at position " + std::to_string(s / 2) + " of the batch: a sampled sequence has no path through the " + std::to_string(cl) + "-codon model (L too short)"); return BATH_ERANGE; }
+      x[i] = (v - nullsc) / 0.69314718055994529;             // evalues.c:649: float difference, double quotient
+    }
+    if ((st = bath_calib_tau(x, N, (double)hmms[s / 2]->evparam[5], tailp, &taus[(size_t)s])) != BATH_OK) {
+      ctx->set_error("calibrate_fs_batch: model at position " + std::to_string(s / 2) + " of the batch: the Gumbel fit did not converge");
+      return st;
+    }
+  }
+  for (int k = 0; k < n_models; k++) {
+    tau3[k] = taus[(size_t)2 * k]; tau5[k] = taus[(size_t)2 * k + 1];
+    if (xv3) std::copy(&xv[(size_t)2 * k * N], &xv[(size_t)(2 * k + 1) * N], xv3 + (size_t)k * N);
+    if (xv5) std::copy(&xv[(size_t)(2 * k + 1) * N], &xv[(size_t)(2 * k + 2) * N], xv5 + (size_t)k * N);
   }
   *rng_state = state;
   return BATH_OK;

@@ -333,143 +333,32 @@ __device__ __forceinline__ unsigned lds_addr(const void *p) { return (unsigned)(
 // ---------------------------------------------------------------------------------------------------------------------------
 // 3-codon Forward parser, multihit, strict.  tf[node] = {tMM(k-1), tIM(k-1), tDM(k-1), tBM(k-1), tMD(k), tDD(k), tMI(k), tII(k)}
 // xmx (optional): (L+1) x {E,N,J,B,C}
+// The recurrence, a block's whole life, is bath_fs3_fwd_chain_rows.hpp: one text, the body of two kernels.  fs3_fwd_chain_kernel's
+// blocks all serve the one model of the launch; fs3_fwd_batch_kernel's find their model at blockIdx.y (calibration of several models
+// per launch).  The text is included, not called: as a __device__ function that both kernels call (always inlined, with or without
+// __restrict__ on its parameters, structures by value or by reference) the same statements left 25 of the file's existing kernels
+// with other register counts or spills than before, a few per cent either way; included, they compile to what they were.
 // ---------------------------------------------------------------------------------------------------------------------------
 template <int C>
 __global__ __launch_bounds__(chain_threads(C)) void fs3_fwd_chain_kernel(SeqView dna, FsDev p, const float *__restrict__ loop_tab, const float *__restrict__ move_tab,
                                                              float tEL, float tEM, float *__restrict__ sc, float *__restrict__ xmx, const int64_t *__restrict__ xmx_off, FsJobs jobs,
                                                              int W /* windows per block: the block has max(W, kChainAwakeWaves) waves */) {
-  extern __shared__ __attribute__((aligned(16))) char lds[];
-  float *s_tbl = reinterpret_cast<float *>(lds);
-  float *s_tf = s_tbl + kLogsumTbl;
-  const int M = p.M;
-  const int stride = fs_chain_stride(C);
-  float *s_stage = s_tf + (M + 2) * 8;                          // [W][2][stride]
-  float *s_e = s_stage + (size_t)W * 2 * stride;                // [W][2] E(i) of the pair's rows
-  int *s_ctl = reinterpret_cast<int *>(s_e + 2 * kChainMaxWaves);   // [0]: first job of the block's batch; [4]: the row pair whose serial part is done
-  if (threadIdx.x == 0) s_ctl[4] = 0;
-  int pair = 0;
-  fs_load_logsum_table(s_tbl, p.logsum);
-  for (int i = threadIdx.x; i < (M + 2) * 8; i += blockDim.x) s_tf[i] = p.tf[i];
-  __syncthreads();
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#define LS(a, b) flogsum<false>((a), (b), s_tbl)
-  for (;;) {
-    if (threadIdx.x == 0) s_ctl[0] = (int)atomicAdd(jobs.counter, (unsigned)W);
-    __syncthreads();
-    const int64_t base = s_ctl[0];
-    if (base >= dna.n) break;
-    const int64_t job = (wv < W && base + wv < dna.n) ? (int64_t)jobs.order[base + wv] : (int64_t)-1;
-    const int Lmax = dna.len[jobs.order[base]];                 // the batch's longest window (the list is sorted by length)
-    const int L = job >= 0 ? dna.len[job] : 0;
-    const uint8_t *d = job >= 0 ? dna.data + dna.off[job] : dna.data;
-    float *xo = (xmx && job >= 0) ? xmx + xmx_off[job] : nullptr;
-    const int Lc = L / 3;
-    const float tNL = loop_tab[Lc], tNM = move_tab[Lc], tJL = tNL, tJM = tNM, tCL = tNL, tCM = tNM;
-    // rows i-1 ("1"), i-2 ("2"), i-3 ("3") of the pair (i, i+1)
-    float M1[C], I1[C], D1[C], M2[C], I2[C], D2[C], M3[C], I3[C], iv_1[C], iv_2[C];
-#pragma unroll
-    for (int c = 0; c < C; c++) M1[c] = I1[c] = D1[c] = M2[c] = I2[c] = D2[c] = M3[c] = I3[c] = iv_1[c] = iv_2[c] = -INFINITY;
-    float N1 = 0.f, N2 = 0.f, N3 = 0.f, J1 = -INFINITY, J2 = -INFINITY, J3 = -INFINITY, C1 = -INFINITY, C2 = -INFINITY, C3 = -INFINITY;
-    float B1 = tNM, B2 = tNM;                                   // B(i-1), B(i-2)
-    if (xo && lane == 0 && L >= 3)
-      for (int i = 0; i < 2; i++) { xo[i * 5 + 0] = -INFINITY; xo[i * 5 + 1] = 0.f; xo[i * 5 + 2] = -INFINITY; xo[i * 5 + 3] = tNM; xo[i * 5 + 4] = -INFINITY; }
-    auto nuc = [&](int i) -> int { return (i >= 1 && i <= L) ? ((d[i - 1] < 4) ? (int)d[i - 1] : 338) : 338; };   // x_i; 338 = p7P_MAXCODONS3 (degenerate / outside)
-    for (int i = 2; i <= Lmax; i += 2) {
-      ++pair;
-      if (wv >= W) { lds_barrier(); chain_keepalive(s_ctl + 4, pair); lds_barrier(); continue; }   // a poller without a window
-      const bool actA = job >= 0 && L >= 3 && i <= L, actB = job >= 0 && L >= 3 && i + 1 <= L;
-      // ---- emission rows of the pair: codon lengths 2, 3, 4 ending at x_i (row A) and x_{i+1} (row B)
-      const int xa = nuc(i), wa = nuc(i - 1), va = nuc(i - 2), ua = nuc(i - 3), xb = nuc(i + 1);
-      const float *qa2 = p.rsc + (size_t)imin(xa * 84 + wa * 21, 337) * p.pitch;
-      const float *qa3 = p.rsc + (size_t)imin(xa * 84 + wa * 21 + va * 5 + 1, 336) * p.pitch;
-      const float *qa4 = p.rsc + (size_t)imin(xa * 84 + wa * 21 + va * 5 + ua + 2, 337) * p.pitch;
-      const float *qb2 = p.rsc + (size_t)imin(xb * 84 + xa * 21, 337) * p.pitch;
-      const float *qb3 = p.rsc + (size_t)imin(xb * 84 + xa * 21 + wa * 5 + 1, 336) * p.pitch;
-      const float *qb4 = p.rsc + (size_t)imin(xb * 84 + xa * 21 + wa * 5 + va + 2, 337) * p.pitch;
-      // ---- 1. everything of both rows that is parallel over the nodes
-      const float mInA = wave_shr1(M2[C - 1], -INFINITY), iInA = wave_shr1(I2[C - 1], -INFINITY), dInA = wave_shr1(D2[C - 1], -INFINITY);
-      const float mInB = wave_shr1(M1[C - 1], -INFINITY), iInB = wave_shr1(I1[C - 1], -INFINITY), dInB = wave_shr1(D1[C - 1], -INFINITY);
-      float MA[C], IA[C], ivA[C], MB[C], IB[C], ivB[C];
-#pragma unroll
-      for (int c = 0; c < C; c++) {
-        const int node = lane * C + c + 1, nd = imin(node, M + 1), ne = imin(node, M);
-        const float4 ta = *reinterpret_cast<const float4 *>(s_tf + nd * 8);
-        const float4 tb = *reinterpret_cast<const float4 *>(s_tf + nd * 8 + 4);
-        const bool in = node <= M;
-        // (no branches in this loop: loads and stores are unconditional -- the slots past node M exist -- so that the log-sums of
-        // a lane's C nodes, independent of each other, can be interleaved)
-        const float la2 = qa2[ne], la3 = qa3[ne], la4 = qa4[ne], lb2 = qb2[ne], lb3 = qb3[ne], lb4 = qb4[ne];
-        const float ea2 = in ? la2 : -INFINITY, ea3 = in ? la3 : -INFINITY, ea4 = in ? la4 : -INFINITY;
-        const float eb2 = in ? lb2 : -INFINITY, eb3 = in ? lb3 : -INFINITY, eb4 = in ? lb4 : -INFINITY;
-        // row A = i: from row i-2 and B(i-2) (:562-569); row 2 takes B(0) only (:503)
-        const float mA = (c == 0) ? mInA : M2[c - 1], iA = (c == 0) ? iInA : I2[c - 1], dA = (c == 0) ? dInA : D2[c - 1];
-        float a = LS(mA + ta.x, LS(iA + ta.y, LS(dA + ta.z, B2 + ta.w)));
-        // (row 2 takes B(0) only (:503): rows 0 and 1 are -inf, and LS(-inf, x) = x exactly)
-        ivA[c] = a;
-        float mv = a + ea2;
-        mv = LS(mv, iv_1[c] + ea3); mv = LS(mv, iv_2[c] + ea4);      // :571-574 (row 2: the IVX of rows 1, 0 are -inf)
-        MA[c] = mv;
-        const float insA = LS(M3[c] + tb.z, I3[c] + tb.w);
-        IA[c] = (i > 2 && node < M) ? insA : -INFINITY;
-        // row B = i+1: from row i-1 and B(i-1); its 3- and 4-nucleotide codons start in rows i and i-1
-        const float mB = (c == 0) ? mInB : M1[c - 1], iB = (c == 0) ? iInB : I1[c - 1], dB = (c == 0) ? dInB : D1[c - 1];
-        const float b = LS(mB + ta.x, LS(iB + ta.y, LS(dB + ta.z, B1 + ta.w)));
-        ivB[c] = b;
-        float mw = b + eb2;
-        mw = LS(mw, a + eb3); mw = LS(mw, iv_1[c] + eb4);
-        MB[c] = mw;
-        const float insB = LS(M2[c] + tb.z, I2[c] + tb.w);
-        IB[c] = (node < M) ? insB : -INFINITY;
-        s_stage[((size_t)wv * 2 + 0) * stride + node] = mv; s_stage[((size_t)wv * 2 + 1) * stride + node] = mw;
-      }
-      lds_barrier();
-      // ---- 2. the serial part, a lane per row: D(i,k) = LS(M(i,k-1) + tMD, D(i,k-1) + tDD), E(i) = LS(M(i,k), LS(D(i,k), E)) (:577-590)
-      if (wv == 0 && lane < 2 * W) {
-        float *st = s_stage + (size_t)lane * stride;
-        float dch = -INFINITY, ech = -INFINITY;
-        // the loop's own loads (M(i,k), the transitions) are a node ahead: what a node waits for is the chain's log-sums only
-        // (slot M+1 of the row and of the transitions exists: the loads run a node ahead)
-        FwdChainRegs r{ech, dch, st[1], s_tf[1 * 8 + 4], s_tf[1 * 8 + 5], lds_addr(st + 1), lds_addr(s_tf + 2 * 8 + 4)};   // tMD(k), tDD(k)
-        fwd_chain_nodes(r, M, lds_addr(s_tbl), 15.999f);
-        ech = r.e; dch = r.d;
-        s_e[lane] = ech;
-      }
-      if (wv == 0) chain_done(s_ctl + 4, pair); else if (chain_poller(wv)) chain_keepalive(s_ctl + 4, pair);
-      lds_barrier();
-      // ---- 3. D and E back to the window's wave; special states of both rows (:592-603)
-      float DA[C], DB[C];
-#pragma unroll
-      for (int c = 0; c < C; c++) {
-        const int node = lane * C + c + 1, ne = imin(node, M);
-        const float da = s_stage[((size_t)wv * 2 + 0) * stride + ne], db = s_stage[((size_t)wv * 2 + 1) * stride + ne];
-        DA[c] = (node <= M) ? da : -INFINITY; DB[c] = (node <= M) ? db : -INFINITY;
-      }
-      const float EA = s_e[wv * 2 + 0], EB = s_e[wv * 2 + 1];
-      float NA, JA, CA;
-      if (i == 2) { NA = 0.f; JA = EA + tEL; CA = EA + tEM; }
-      else { NA = N3 + tNL; JA = LS(J3 + tJL, EA + tEL); CA = LS(C3 + tCL, EA + tEM); }
-      const float BA = LS(NA + tNM, JA + tJM);
-      const float NB = N2 + tNL, JB = LS(J2 + tJL, EB + tEL), CB = LS(C2 + tCL, EB + tEM);
-      const float BB = LS(NB + tNM, JB + tJM);
-      if (xo && lane == 0) {
-        if (actA) { float *r = xo + (size_t)i * 5; r[0] = EA; r[1] = NA; r[2] = JA; r[3] = BA; r[4] = CA; }
-        if (actB) { float *r = xo + (size_t)(i + 1) * 5; r[0] = EB; r[1] = NB; r[2] = JB; r[3] = BB; r[4] = CB; }
-      }
-      if (actB) {                                               // both rows exist: the rings move by two
-        N3 = N1; N2 = NA; N1 = NB; J3 = J1; J2 = JA; J1 = JB; C3 = C1; C2 = CA; C1 = CB; B2 = BA; B1 = BB;
-#pragma unroll
-        for (int c = 0; c < C; c++) {
-          M3[c] = M1[c]; I3[c] = I1[c]; M2[c] = MA[c]; I2[c] = IA[c]; D2[c] = DA[c]; M1[c] = MB[c]; I1[c] = IB[c]; D1[c] = DB[c];
-          iv_2[c] = ivA[c]; iv_1[c] = ivB[c];
-        }
-      } else if (actA) {                                        // the window's last row: only C(L), C(L-1), C(L-2) are still needed
-        C3 = C2; C2 = C1; C1 = CA;
-      }
-    }
-    if (job >= 0 && lane == 0) sc[job] = (L >= 3) ? LS(C1, LS(C2 + tCL, C3 + tCL)) + tCM : -INFINITY;
-    __syncthreads();                                            // s_ctl is rewritten at the top
-  }
-#undef LS
+#include "bath_fs3_fwd_chain_rows.hpp"
+}
+
+// Several models per launch: gridDim.y models of one tiling, the blocks of row blockIdx.y work for models[blockIdx.y] alone -- its
+// transitions staged once, its windows drawn from its own counter -- and no block knows of another.  Scores only.
+template <int C>
+__global__ __launch_bounds__(chain_threads(C)) void fs3_fwd_batch_kernel(const FsBatchModel *__restrict__ models, float tEL, float tEM,
+                                                             int W /* windows per block, as above */) {
+  const FsBatchModel m = models[blockIdx.y];
+  const SeqView dna = m.dna;
+  const FsDev p = m.p;
+  const float *__restrict__ loop_tab = m.loop_tab, *__restrict__ move_tab = m.move_tab;
+  float *__restrict__ sc = m.sc, *const xmx = nullptr;
+  const int64_t *const xmx_off = nullptr;
+  const FsJobs jobs = m.jobs;
+#include "bath_fs3_fwd_chain_rows.hpp"
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
@@ -1183,178 +1072,33 @@ __global__ __launch_bounds__(1024) void fs3_bwd_chain_half_kernel(SeqView dna, F
 // STORE = false is the score-only parser (p7_fs_Tau_5codons' caller, bath_calibrate.hip): the same recurrence, value for value, with
 // no store of a cell or a special-state row -- fwd, xmx, their offsets and done are not read.  What the recurrence reaches back to
 // (M and I of rows i-1..i-3, D of row i-1, IVX of rows i-1..i-4, N/J/C of rows i-1..i-3) is in registers, the row in flight in LDS.
+// The recurrence is bath_fs5_fwd_chain_rows.hpp, the body of two kernels (included, not called, for the reason given at
+// fs3_fwd_chain_kernel): fs5_fwd_chain_kernel for the one model of a launch, fs5_fwd_parser_batch_kernel the score-only entry whose
+// blocks find their model at blockIdx.y.
 // ---------------------------------------------------------------------------------------------------------------------------
 template <int C, int THREADS, bool STORE = true>
 __global__ __launch_bounds__(THREADS) void fs5_fwd_chain_kernel(SeqView dna, FsDev p, const float *__restrict__ loop_tab, const float *__restrict__ move_tab,
                                                              float tEL, float tEM, int c5_compat, float *__restrict__ sc, float *__restrict__ fwd, const int64_t *__restrict__ fwd_off,
                                                              float *__restrict__ xmx, const int64_t *__restrict__ xmx_off, int cfg_len, FsJobs jobs, int *__restrict__ done,
                                                              int W /* windows per block: the block has max(W, kChainAwakeWaves) waves */) {
-  extern __shared__ __attribute__((aligned(16))) char lds[];
-  float *s_tbl = reinterpret_cast<float *>(lds);
-  float *s_tf = s_tbl + kLogsumTbl;
-  const int M = p.M;
-  const int stride = fs_chain_stride(C);
-  float *s_stage = s_tf + (M + 2) * 8;                          // [W][2][stride]; row 0 of each pair of slots is used
-  float *s_e = s_stage + (size_t)W * 2 * stride;
-  int *s_ctl = reinterpret_cast<int *>(s_e + 2 * kChainMaxWaves);   // [0]: first job of the block's batch; [4]: the row whose serial part is done
-  if (threadIdx.x == 0) s_ctl[4] = 0;
-  int pair = 0;
-  fs_load_logsum_table(s_tbl, p.logsum);
-  for (int i = threadIdx.x; i < (M + 2) * 8; i += blockDim.x) s_tf[i] = p.tf[i];
-  __syncthreads();
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-#define LS(a, b) flogsum<false>((a), (b), s_tbl)
-  for (;;) {
-    if (threadIdx.x == 0) s_ctl[0] = (int)atomicAdd(jobs.counter, (unsigned)W);
-    __syncthreads();
-    const int64_t base = s_ctl[0];
-    if (base >= dna.n) break;
-    const int64_t job = (wv < W && base + wv < dna.n) ? (int64_t)jobs.order[base + wv] : (int64_t)-1;
-    const int Lmax = dna.len[jobs.order[base]];
-    const int L = job >= 0 ? dna.len[job] : 0;
-    const bool live = job >= 0 && L >= 5;
-    const uint8_t *d = job >= 0 ? dna.data + dna.off[job] : dna.data;
-    float *fo = (STORE && job >= 0) ? fwd + fwd_off[job] : fwd;
-    float *xo = (STORE && job >= 0) ? xmx + xmx_off[job] : xmx;
-    const int Lc = cfg_len >= 0 ? cfg_len : L / 3;
-    const float tNL = loop_tab[Lc], tNM = move_tab[Lc], tJL = tNL, tJM = tNM, tCL = tNL, tCM = tNM;
-    float Mr0[C], Mr1[C], Mr2[C], Ir0[C], Ir1[C], Ir2[C], Dr1[C], iv0[C], iv1[C], iv2[C], iv3[C];   // M, I of rows i-1..i-3; D of row i-1; IVX(i-1..i-4)
-#pragma unroll
-    for (int c = 0; c < C; c++) Mr0[c] = Mr1[c] = Mr2[c] = Ir0[c] = Ir1[c] = Ir2[c] = Dr1[c] = iv0[c] = iv1[c] = iv2[c] = iv3[c] = -INFINITY;
-    if (STORE && live) {
-      for (int k = lane; k <= M; k += 64)
-#pragma unroll
-        for (int q = 0; q < 8; q++) fo[(size_t)k * 8 + q] = -INFINITY;
-      if (lane == 0) { xo[0] = -INFINITY; xo[1] = 0.f; xo[2] = -INFINITY; xo[3] = tNM; xo[4] = -INFINITY; }
-    }
-    float xN0 = 0.f, xN1 = 0.f, xN2 = 0.f, xJ0 = -INFINITY, xJ1 = -INFINITY, xJ2 = -INFINITY, xC0 = -INFINITY, xC1 = -INFINITY, xC2 = -INFINITY;   // rows i-1, i-2, i-3
-    float xBprev = tNM;
-    auto nuc = [&](int i) -> int { return (i >= 1 && i <= L) ? ((d[i - 1] < 4) ? (int)d[i - 1] : 1367) : 1367; };
-    // the emission scores of a row are loaded during the chain of the row before: nothing in a row waits for global memory
-    float E1[C], E2[C], E3[C], E4[C], E5[C];
-    auto load_emissions = [&](int i) {
-      const int x = nuc(i), w = nuc(i - 1), v = nuc(i - 2), u = nuc(i - 3), t = nuc(i - 4);
-      const float *r1 = p.rsc + (size_t)imin(x * 341, 1366) * p.pitch;
-      const float *r2 = p.rsc + (size_t)imin(x * 341 + w * 85 + 1, 1365) * p.pitch;
-      const float *r3 = p.rsc + (size_t)imin(x * 341 + w * 85 + v * 21 + 2, 1364) * p.pitch;
-      const float *r4 = p.rsc + (size_t)imin(x * 341 + w * 85 + v * 21 + u * 5 + 3, 1365) * p.pitch;
-      const float *r5 = p.rsc + (size_t)imin(x * 341 + w * 85 + v * 21 + u * 5 + t + 4, 1366) * p.pitch;
-#pragma unroll
-      for (int c = 0; c < C; c++) {
-        const int ne = imin(lane * C + c + 1, M);
-        E1[c] = r1[ne]; E2[c] = r2[ne]; E3[c] = r3[ne]; E4[c] = r4[ne]; E5[c] = r5[ne];
-      }
-    };
-    load_emissions(1);
-    for (int i = 1; i <= Lmax; i++) {
-      ++pair;
-      if (wv >= W) { lds_barrier(); chain_keepalive(s_ctl + 4, pair); lds_barrier(); continue; }   // a poller without a window
-      const bool act = live && i <= L;
-      const float mIn = wave_shr1(Mr0[C - 1], -INFINITY), iIn = wave_shr1(Ir0[C - 1], -INFINITY), dIn = wave_shr1(Dr1[C - 1], -INFINITY);
-      float Mc[C], Ic[C], ivc[C];
-      float *row = STORE ? fo + (size_t)(act ? i : 0) * (M + 1) * 8 : nullptr;
-      if (STORE && act && lane == 0) {
-#pragma unroll
-        for (int q = 0; q < 8; q++) row[q] = -INFINITY;
-      }
-      // The cells of the row, then their stores.  Rows >= 5 (all but four of a window) go through a loop without branches, so that
-      // the log-sums of a lane's C nodes -- independent of each other -- are interleaved; the first rows take the general form.
-      float q1[C], q2[C], q3[C], q4[C], q5[C];
-      auto cells = [&](auto early_tag) {
-        constexpr bool EARLY = decltype(early_tag)::value;
-#pragma unroll
-        for (int c = 0; c < C; c++) {
-          const int node = lane * C + c + 1, nd = imin(node, M + 1);
-          const float4 ta = *reinterpret_cast<const float4 *>(s_tf + nd * 8);
-          const float4 tb = *reinterpret_cast<const float4 *>(s_tf + nd * 8 + 4);
-          const float m1 = (c == 0) ? mIn : Mr0[c - 1], i1 = (c == 0) ? iIn : Ir0[c - 1], d1 = (c == 0) ? dIn : Dr1[c - 1];
-          const float e1 = E1[c], e2 = E2[c], e3 = E3[c], e4 = E4[c], e5 = E5[c];
-          float ivn = LS(m1 + ta.x, LS(i1 + ta.y, LS(d1 + ta.z, xBprev + ta.w)));  // :332-335
-          if (EARLY && i <= 2) ivn = xBprev + ta.w;                                  // rows 1, 2: only B(i-1) enters (:109, :150)
-          ivc[c] = ivn;
-          const float c1 = ivn + e1;
-          const float c2 = (!EARLY || i >= 2) ? iv0[c] + e2 : -INFINITY;
-          const float c3 = (!EARLY || i >= 3) ? iv1[c] + e3 : -INFINITY;
-          const float c4 = (!EARLY || i >= 4) ? iv2[c] + e4 : -INFINITY;
-          const float c5 = !EARLY ? (c5_compat ? ivn : iv3[c]) + e5 : -INFINITY;
-          float c0;
-          if (!EARLY) c0 = LS(LS(c1, LS(c2, c3)), LS(c4, c5));
-          else if (i == 1) c0 = c1;
-          else if (i == 2) c0 = LS(c1, c2);
-          else c0 = LS(c1, LS(c2, LS(c3, c4)));
-          Mc[c] = c0;
-          const float ins = LS(Mr2[c] + tb.z, Ir2[c] + tb.w);
-          Ic[c] = ((!EARLY || i >= 3) && node < M) ? ins : -INFINITY;
-          q1[c] = c1; q2[c] = c2; q3[c] = c3; q4[c] = c4; q5[c] = c5;
-          s_stage[((size_t)wv * 2) * stride + node] = c0;           // (the slots past node M exist)
-        }
-      };
-      if (i >= 5) cells(std::false_type{}); else cells(std::true_type{});
-      if (STORE && act) {
-#pragma unroll
-        for (int c = 0; c < C; c++) {
-          const int node = lane * C + c + 1;
-          if (node <= M) {
-            float *cell = row + (size_t)node * 8;
-            cell[1] = Ic[c]; cell[2] = Mc[c]; cell[3] = q1[c]; cell[4] = q2[c]; cell[5] = q3[c]; cell[6] = q4[c]; cell[7] = q5[c];
-          }
-        }
-      }
-      load_emissions(i + 1);
-      lds_barrier();
-      // ---- the serial part, a lane per window: D(i,k), E(i) in the reference's order; rows >= 5 pair M(i,M) and D(i,M) first (:392-394)
-      if (wv == 0 && lane < W) {
-        float *st = s_stage + (size_t)lane * 2 * stride;
-        float dch = -INFINITY, ech = -INFINITY;
-        FwdChainRegs r{ech, dch, st[1], s_tf[1 * 8 + 4], s_tf[1 * 8 + 5], lds_addr(st + 1), lds_addr(s_tf + 2 * 8 + 4)};   // tMD(k), tDD(k)
-        fwd_chain_nodes(r, M - 1, lds_addr(s_tbl), 15.999f);
-        ech = r.e; dch = r.d;
-        const float Mn = r.Mk;                                    // M(i,M)
-        st[M] = dch;
-        ech = (i >= 5) ? LS(LS(Mn, dch), ech) : LS(Mn, LS(dch, ech));
-        s_e[lane] = ech;
-      }
-      if (wv == 0) chain_done(s_ctl + 4, pair); else if (chain_poller(wv)) chain_keepalive(s_ctl + 4, pair);
-      lds_barrier();
-      float Dc[C];
-#pragma unroll
-      for (int c = 0; c < C; c++) {
-        const int node = lane * C + c + 1, ne = imin(node, M);
-        const float dv = s_stage[((size_t)wv * 2) * stride + ne];
-        Dc[c] = (node <= M) ? dv : -INFINITY;
-        if (STORE && act && node <= M) row[(size_t)node * 8] = Dc[c];
-      }
-      const float xE = s_e[wv];
-      float nN, nJ, nC, nB;
-      if (i <= 2) { nN = 0.f; nJ = xE + tEL; nC = xE + tEM; nB = tNM; }           // :126-132, :166-167
-      else {
-        nN = xN2 + tNL; nJ = LS(xJ2 + tJL, xE + tEL); nC = LS(xC2 + tCL, xE + tEM);
-        nB = LS(nN + tNM, nJ + tJM);
-      }
-      if (act) {
-        if (STORE && lane == 0) { xo[i * 5 + 0] = xE; xo[i * 5 + 1] = nN; xo[i * 5 + 2] = nJ; xo[i * 5 + 3] = nB; xo[i * 5 + 4] = nC; }
-        xN2 = xN1; xN1 = xN0; xN0 = nN; xJ2 = xJ1; xJ1 = xJ0; xJ0 = nJ; xC2 = xC1; xC1 = xC0; xC0 = nC;
-        xBprev = nB;
-#pragma unroll
-        for (int c = 0; c < C; c++) {
-          Mr2[c] = Mr1[c]; Mr1[c] = Mr0[c]; Mr0[c] = Mc[c];
-          Ir2[c] = Ir1[c]; Ir1[c] = Ir0[c]; Ir0[c] = Ic[c];
-          Dr1[c] = Dc[c];
-          iv3[c] = iv2[c]; iv2[c] = iv1[c]; iv1[c] = iv0[c]; iv0[c] = ivc[c];
-        }
-        if (i == L) {                                             // this window is complete: score, then the flag the host waits for
-          if (lane == 0) sc[job] = LS(xC0, LS(xC1 + tCL, xC2 + tCL)) + tCM;
-          if (STORE && done) { __threadfence_system(); if (lane == 0) __hip_atomic_store(done + job, 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM); }
-        }
-      }
-    }
-    if (job >= 0 && !live) {
-      if (lane == 0) sc[job] = -INFINITY;
-      if (STORE && done) { __threadfence_system(); if (lane == 0) __hip_atomic_store(done + job, 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM); }
-    }
-    __syncthreads();
-  }
-#undef LS
+#include "bath_fs5_fwd_chain_rows.hpp"
+}
+
+template <int C, int THREADS>
+__global__ __launch_bounds__(THREADS) void fs5_fwd_parser_batch_kernel(const FsBatchModel *__restrict__ models, float tEL, float tEM,
+                                                             int W /* windows per block, as above */) {
+  constexpr bool STORE = false;
+  constexpr int c5_compat = 0;
+  const FsBatchModel m = models[blockIdx.y];
+  const SeqView dna = m.dna;
+  const FsDev p = m.p;
+  const float *__restrict__ loop_tab = m.loop_tab, *__restrict__ move_tab = m.move_tab;
+  float *__restrict__ sc = m.sc, *const fwd = nullptr, *const xmx = nullptr;
+  const int64_t *const fwd_off = nullptr, *const xmx_off = nullptr;
+  int *const done = nullptr;
+  const int cfg_len = m.cfg_len;
+  const FsJobs jobs = m.jobs;
+#include "bath_fs5_fwd_chain_rows.hpp"
 }
 
 // Batches of windows for the blocks of a chain kernel.  A row pair of a block with w windows takes t(w) = t0 + w * dt (the chain
@@ -1586,6 +1330,49 @@ int launch_fs5_fwd_parser(bath_hip_ctx *ctx, hipStream_t stream, const bath_hip_
     BATH_HIP_TRY(ctx, bath::allow_max_lds((const void *)fs5_fwd_chain_kernel<CC, 256, false>));
     hipLaunchKernelGGL((fs5_fwd_chain_kernel<CC, 256, false>), dim3(grid), dim3(64 * std::max(W, kChainAwakeWaves)), shmem, stream, dna->view(), dev, om->d_loop[0], om->d_move[0], tEL, tEM, 0, d_sc,
                        (float *)nullptr, (const int64_t *)nullptr, (float *)nullptr, (const int64_t *)nullptr, cfg_len, jobs, (int *)nullptr, W);
+  })
+  BATH_HIP_TRY(ctx, hipGetLastError());
+  return BATH_OK;
+}
+
+// Windows per block of a launch that holds several models.  chain_waves sizes a block for a couple of hundred windows that are to
+// end as early as possible: it halves the block until every CU has one.  A batch has thousands of windows of one length and is
+// judged by windows per second, so the block takes what its thread bound and LDS allow, sized for the longest model of the launch
+// (<Mmax>; a shorter model's block uses less of it), and the dispatcher packs blocks as LDS and registers let it; what that was
+// measured against is DESIGN 4.6g.  BATH_HIP_CALIB_BATCH_W=w caps the windows per block, BATH_HIP_CALIB_BATCH_SOLO=1 pads a
+// block's LDS beyond half a CU's so that it has its CU to itself (A/B runs: tools/bathconvert_batch_time.py).
+static int batch_waves(int64_t n, int Mmax, int C, int threads, size_t *shmem_out) {
+  const size_t fixed = (size_t)(kLogsumTbl + (Mmax + 2) * 8 + 2 * kChainMaxWaves + 16 + 2 * kChainMaxWaves) * sizeof(float);
+  int W = threads / 64;
+  while (W > 1 && fixed + (size_t)W * 2 * fs_chain_stride(C) * sizeof(float) > 160 * 1024) W >>= 1;
+  static const int w_env = [] { const char *e = std::getenv("BATH_HIP_CALIB_BATCH_W"); return e ? std::atoi(e) : 0; }();
+  static const bool solo = [] { const char *e = std::getenv("BATH_HIP_CALIB_BATCH_SOLO"); return e && e[0] == '1'; }();
+  while (W > 1 && ((w_env >= 1 && W > w_env) || (int64_t)(W / 2) >= n)) W >>= 1;
+  *shmem_out = fixed + (size_t)W * 2 * fs_chain_stride(C) * sizeof(float);
+  if (solo) *shmem_out = std::max(*shmem_out, (size_t)100 * 1024);
+  return W;
+}
+
+// <n_models> models of the tiling <Cv>, <n> windows each: a row of ceil(n / W) blocks per model
+int launch_fs3_fwd_batch(bath_hip_ctx *ctx, hipStream_t stream, const FsBatchModel *d_models, int n_models, int Mmax, int Cv, int64_t n, float tEL, float tEM) {
+  if (n_models < 1 || n < 1) return BATH_OK;
+  BATH_FS_SWITCH(Cv, {
+    size_t shmem = 0;
+    const int W = batch_waves(n, Mmax, CC, chain_threads(CC), &shmem);
+    BATH_HIP_TRY(ctx, bath::allow_max_lds((const void *)fs3_fwd_batch_kernel<CC>));
+    hipLaunchKernelGGL((fs3_fwd_batch_kernel<CC>), dim3((unsigned)((n + W - 1) / W), (unsigned)n_models), dim3(64 * std::max(W, kChainAwakeWaves)), shmem, stream, d_models, tEL, tEM, W);
+  })
+  BATH_HIP_TRY(ctx, hipGetLastError());
+  return BATH_OK;
+}
+
+int launch_fs5_fwd_parser_batch(bath_hip_ctx *ctx, hipStream_t stream, const FsBatchModel *d_models, int n_models, int Mmax, int Cv, int64_t n, float tEL, float tEM) {
+  if (n_models < 1 || n < 1) return BATH_OK;
+  BATH_FS_SWITCH(Cv, {
+    size_t shmem = 0;
+    const int W = batch_waves(n, Mmax, CC, 256, &shmem);
+    BATH_HIP_TRY(ctx, bath::allow_max_lds((const void *)fs5_fwd_parser_batch_kernel<CC, 256>));
+    hipLaunchKernelGGL((fs5_fwd_parser_batch_kernel<CC, 256>), dim3((unsigned)((n + W - 1) / W), (unsigned)n_models), dim3(64 * std::max(W, kChainAwakeWaves)), shmem, stream, d_models, tEL, tEM, W);
   })
   BATH_HIP_TRY(ctx, hipGetLastError());
   return BATH_OK;

@@ -206,6 +206,17 @@ inline void fs_order_by_length_desc(const int32_t *len, int64_t n, std::vector<i
 
 struct FsJobs { const int32_t *order; unsigned *counter; };
 
+// One model of a launch that holds several (fs3_fwd_batch_kernel, fs5_fwd_parser_batch_kernel: calibration, bath_calibrate.hip): what
+// the single-model kernels take as arguments, read by a block from a device array at blockIdx.y.  <jobs.counter> is the model's own.
+struct FsBatchModel {
+  SeqView dna;
+  FsDev p;
+  const float *loop_tab, *move_tab;
+  float *sc;
+  FsJobs jobs;
+  int cfg_len;               // the 5-codon parser's configuration length in amino acids (the 3-codon parser takes a window's own)
+};
+
 // The odds-ratio tables (ensure_odds) cover every node a lane of the C-column kernel owns, 1 .. 64 C, with zeros beyond M: a lane's
 // loads are one vector offset plus immediates, and nodes beyond M come out 0 without a branch or a clamp.  The 5-codon kernels read
 // node k's emission at column k-1, so a lane's C values start at lane*C -- whole 16-byte loads when 4 divides C.
@@ -255,6 +266,10 @@ int launch_fs5_fwd_chain(bath_hip_ctx *ctx, hipStream_t stream, const bath_hip_f
 // the score of launch_fs5_fwd_chain alone: the same kernel instantiated without its stores (calibration, bath_calibrate.hip)
 int launch_fs5_fwd_parser(bath_hip_ctx *ctx, hipStream_t stream, const bath_hip_fsprofile *om, const bath_hip_seqs *dna, int Cv, float tEL, float tEM,
                           float *d_sc, int cfg_len, FsJobs jobs);
+// the two strict score-only parsers over several models per launch: d_models[n_models], all of the tiling <Cv> and none longer than
+// <Mmax>, each with <n> windows (calibration of a batch of models, bath_calibrate.hip)
+int launch_fs3_fwd_batch(bath_hip_ctx *ctx, hipStream_t stream, const FsBatchModel *d_models, int n_models, int Mmax, int Cv, int64_t n, float tEL, float tEM);
+int launch_fs5_fwd_parser_batch(bath_hip_ctx *ctx, hipStream_t stream, const FsBatchModel *d_models, int n_models, int Mmax, int Cv, int64_t n, float tEL, float tEM);
 // ---- the 3-codon parsers in odds-ratio space (bath_fs_odds.hip)
 int launch_fs3_odds(bath_hip_ctx *ctx, hipStream_t stream, const bath_hip_fsprofile *om, const bath_hip_seqs *dna, bool backward,
                     float *d_sc, float *d_xmx, const int64_t *d_xoff, FsJobs jobs);

@@ -99,6 +99,8 @@ enum class Scratch : int {
   kStdRegionFwdMatrix,      // device ensemble: the multi-domain regions' Forward matrices
   kStdEnsembleUpload,       // std_ensemble_kernel: job list, path offsets, start states
   kStdEnsembleOut,          // ... statuses, segments, path codes
+  // ---- frameshift calibration of several models per launch (bath_calibrate.hip: bath_hip_calibrate_fs_batch)
+  kCalibBatchWork,          // a job counter per sample set, the job order, the models' descriptors (FsBatchModel), the windows' scores
   kCount
 };
 
@@ -118,6 +120,7 @@ enum class Pinned : int {
   kFsEnsembleOut,           // ... its statuses, segments and the regions' scores, down
   kStdEnsembleUpload,       // std_ensemble_kernel's upload
   kStdEnsembleOut,          // ... and its results, down
+  kCalibBatchUpload,        // bath_hip_calibrate_fs_batch: zeroed counters, job order and descriptors, up
   kCount
 };
 

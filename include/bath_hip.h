@@ -802,6 +802,25 @@ int bath_calib_fit_scores(uint32_t *rng_state, const float *f, int ncbi_table, i
 #define BATH_ARITH_ODDS   2
 int bath_hip_calibrate_fs_arith(bath_hip_ctx *ctx, const bath_hmm *hmm, int ncbi_table, uint32_t *rng_state, int L, int N, double tailp,
                                 double *tau3, double *tau5, double *xv3, double *xv5, int arith, int *redrawn);
+/* Several models per launch.  One model's 2 x N windows leave most of the device idle for the length of a window's row chain; a batch
+ * gives every parser launch the windows of all its models.
+ * bath_calib_sample_batch: the stream that n_models successive bath_hip_calibrate_fs calls draw, in their order -- model 0's 3-codon
+ * set, model 0's 5-codon set, model 1's 3-codon set, ... each model with its own table; dna[n_models][2][N][3L].  *rng_state is left
+ * alone on error (BATH_EINVAL: an unknown table, or a drawn residue without a codon in a model's table).  Host only.
+ * bath_hip_calibrate_fs_batch: defined by what it equals -- n_models successive bath_hip_calibrate_fs calls with the state carried:
+ * tau3[n_models], tau5[n_models], xv3 / xv5 (NULL or [n_models * N]) and the final state are the same bits.  Strict arithmetic only
+ * (the odds modes' redraw makes a model's stream depend on the scores of the model before it).  1 <= n_models <= BATH_CALIB_BATCH_MAX.
+ * All samples are drawn first, the 2 x n_models profiles built on host threads and uploaded, the models grouped by kernel tiling, one
+ * launch per parser and per tiling present (fs3_fwd_batch_kernel, fs5_fwd_parser_batch_kernel: the spans bath_hip_kernel_times reports
+ * afterwards), the 5-codon launches beside the 3-codon ones, one synchronize, then the fits.  All or nothing: on any error (its message
+ * names the model's position in the batch, from 0) no output is written, *rng_state is unchanged and the context stays usable.
+ * BATH_EINVAL: a model beyond the frameshift kernels' 1280 nodes, an unknown table, n_models out of range, L < 2, N < 2;
+ * BATH_ERANGE: a sequence without a path, as in the single call. */
+#define BATH_CALIB_BATCH_MAX 64
+int bath_calib_sample_batch(uint32_t *rng_state, const float *f, const int *ncbi_tables, int n_models, int L, int N, uint8_t *dna);
+int bath_hip_calibrate_fs_batch(bath_hip_ctx *ctx, const bath_hmm *const *hmms, const int *ncbi_tables, int n_models,
+                                uint32_t *rng_state, int L, int N, double tailp,
+                                double *tau3, double *tau5, double *xv3, double *xv5);
 
 /* ------------------------------------------------------------------------------------------
  * Single-sequence models (bathbuild on an unaligned protein file; p7_SingleBuilder, p7_builder.c:501-569) and their calibration
