@@ -214,6 +214,7 @@ ABI = {
     "bath_hip_synchronize": (C.c_int, [_vp]),
     "bath_hip_stream": (_vp, [_vp]),
     "bath_hip_set_fs_strict": (C.c_int, [_vp, C.c_int]),
+    "bath_hip_set_fwd_group": (C.c_int, [_vp, C.c_int]),
     "bath_hip_set_fs_serial": (C.c_int, [_vp, C.c_int]),
     "bath_hip_set_fs_odds": (C.c_int, [_vp, C.c_int]),
     "bath_hip_set_fs5_odds": (C.c_int, [_vp, C.c_int]),
@@ -272,6 +273,7 @@ ABI = {
     "bath_hip_msvfilter": (C.c_int, [_vp, _vp, _vp, _f32p, _i32p]),
     "bath_hip_vitfilter": (C.c_int, [_vp, _vp, _vp, _f32p, _i32p]),
     "bath_hip_forward_parser": (C.c_int, [_vp, _vp, _vp, _f32p, _i32p]),
+    "bath_hip_fwdparser_group": (C.c_int, [_vp, _vp, _vp, _f32p, _i32p]),
     "bath_hip_bias_filter": (C.c_int, [_vp, _vp, _vp, _f32p, _f32p]),
     "bath_hip_fwdback_parser": (C.c_int, [_vp, _vp, _vp, _i64p, _f32p, _f32p, _i32p, _i32p, _f32p, _f32p]),
     "bath_hip_translate_orfs": (C.c_int, [_vp, _vp, C.c_int, C.c_int, C.POINTER(C.POINTER(Orf)), _i64p, C.POINTER(_u8p)]),
@@ -549,6 +551,12 @@ class Context:
         """True (the library's default): frameshift log-sums along the model in the reference's serial order, bit-identical to the
         generic reference.  False: the fast mode (wavefront scans, scores within O(1e-3) nats)."""
         self._check(lib().bath_hip_set_fs_strict(self._h, 1 if on else 0), "set_fs_strict")
+
+    def set_fwd_group(self, mode):
+        """Which kernel scores the cascade's Forward stage.  0 (the default) and 1: the group kernel (four targets per wave) for models
+        of up to 160 nodes whose Forward rows are not kept for the domain stage, blocks of every size; the wave-per-target kernel
+        otherwise.  2: never.  The two agree within the Forward parser's tolerance, not bit for bit."""
+        self._check(lib().bath_hip_set_fwd_group(self._h, int(mode)), "set_fwd_group")
 
     def set_fs_odds(self, on=True):
         """True: the pipeline's 3-codon Forward and Backward parsers run in odds-ratio space (LOGSUM_ODDS, what the reference's
@@ -965,6 +973,12 @@ def ViterbiFilter(ctx, om, sq):
 def ForwardParser(ctx, om, sq):
     """p7_ForwardParser over a block."""
     return _score_call(lib().bath_hip_forward_parser, "forward_parser", ctx, om, sq)
+
+
+def ForwardParserGroup(ctx, om, sq):
+    """p7_ForwardParser over a block by the cascade's group kernel (a quarter wave per target; models of up to 160 nodes, BathError
+    beyond): scores within the parser's tolerance of ForwardParser's, not bit-identical."""
+    return _score_call(lib().bath_hip_fwdparser_group, "fwdparser_group", ctx, om, sq)
 
 
 def FwdBackParser(ctx, om, sq):

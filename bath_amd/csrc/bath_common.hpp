@@ -173,6 +173,7 @@ struct bath_hip_ctx {
   int fs_strict = 1;                    // frameshift log-sums along the model in the reference's serial order (bit-identical); bath_hip_set_fs_strict(ctx, 0): wavefront scans
   int fs_odds = 0;                      // bath_hip_set_fs_odds(ctx, 1): the 3-codon parsers of the pipeline in odds-ratio space (BATH_LOGSUM_ODDS)
   int fs5_odds = 0;                     // bath_hip_set_fs5_odds(ctx, 1): the 5-codon Forward / Backward (envelopes, regions) in odds-ratio space
+  int fwd_group = 0;                    // bath_hip_set_fwd_group: the cascade's Forward stage by fwd_group_kernel -- 0, 1: whenever the model fits and no rows are kept, 2: never
   int fs_ensemble = 0;                  // bath_hip_set_fs_ensemble: how the frameshift branch samples a multi-domain region's traces (BATH_ENSEMBLE_*)
   // regions of the stream modes that went another way: outside the stream rule (serial ensemble), a trace with more segments than the
   // kernel keeps (host twin); and the bytes of Forward matrices the device mode did not send to the host (bath_hip_fs_ensemble_counters)

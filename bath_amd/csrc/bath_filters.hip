@@ -349,33 +349,7 @@ __global__ __launch_bounds__(256) void vit_wave_kernel(SeqView sq, int M, const 
 // ============================================================================================
 // Forward parser, wave per target (odds-ratio space, sparse rescaling as fwdback.c:418-434).
 // ============================================================================================
-struct FwdConsts { float xfE_loop, xfE_move; };
-
-// Emission rows of the wave-per-target Forward / Backward kernels in LDS: [Kp][S] floats, entry node - 1 (S a multiple of 4, 64 C
-// zeros behind the last row), so that a lane's C consecutive nodes are one or two 16-byte reads at 16-byte-aligned addresses that
-// follow the previous lane's: no bank conflicts.  (Indexed by node with a read per node, the lanes of a wave were C x 4 bytes apart:
-// an 8-way conflict at C = 8 -- and the transitions, 32 bytes per node read as two float4, 64-way: they are in registers now.)
-__host__ __device__ constexpr int wave_em_stride(int M) { return (M + 4) & ~3; }          // >= M + 1: entry M is the zero column of node M + 1
-template <int C>
-__device__ __forceinline__ void wave_em_load(const float *row, int lane, float (&e)[C]) {
-  const float *p = row + lane * C;
-  if constexpr (C % 4 == 0) {
-#pragma unroll
-    for (int q = 0; q < C / 4; q++) { const float4 v = *reinterpret_cast<const float4 *>(p + 4 * q); e[4 * q] = v.x; e[4 * q + 1] = v.y; e[4 * q + 2] = v.z; e[4 * q + 3] = v.w; }
-  } else if constexpr (C % 2 == 0) {
-#pragma unroll
-    for (int q = 0; q < C / 2; q++) { const float2 v = *reinterpret_cast<const float2 *>(p + 2 * q); e[2 * q] = v.x; e[2 * q + 1] = v.y; }
-  } else {
-#pragma unroll
-    for (int q = 0; q < C; q++) e[q] = p[q];
-  }
-}
-template <int C>
-__device__ __forceinline__ void wave_em_fill(float *w_rf, const float *g_rf, int M, int src_stride) {
-  const int S = wave_em_stride(M), n = kKp * S + 64 * C;
-  for (int i = threadIdx.x; i < n; i += blockDim.x) { const int x = i / S, k = i - x * S; w_rf[i] = (x < kKp && k < M) ? g_rf[(size_t)x * src_stride + k + 1] : 0.f; }
-}
-
+// (FwdConsts and the emission rows in LDS, wave_em_stride / wave_em_load / wave_em_fill: bath_kernels.hpp, shared with bath_fwd_group.hip)
 // GT: the tables of a model too long for the LDS (above ~1100 nodes) are read from global memory (L2-resident) instead
 template <int C, bool GT = false>
 __global__ __launch_bounds__(256) void fwd_wave_kernel(SeqView sq, int M, const float *__restrict__ g_rf, const float *__restrict__ g_tf,

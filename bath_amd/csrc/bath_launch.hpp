@@ -44,6 +44,13 @@ int launch_vit_wave(bath_hip_ctx *ctx, const bath_hip_oprofile *om, SeqView v, c
 int launch_fwd_wave(bath_hip_ctx *ctx, const bath_hip_oprofile *om, SeqView v, const int32_t *d_todo, int64_t ntodo, float *d_sc, int32_t *d_status, const int *ntodo_dev,
                     float *d_xmx = nullptr, const int64_t *d_xmx_off = nullptr, float *d_dp = nullptr, const int64_t *d_dp_off = nullptr, int unihit = 0,
                     const int32_t *d_cfg_len = nullptr);
+// Forward with a quarter wave per target, four targets of a length-sorted list per wave (bath_fwd_group.hip): models of up to
+// kFwdGroupMaxNodes nodes, scores only (no rows, no matrix).  <d_sorted>: the list, longest first (launch_len_sort); its length is
+// *ntodo_dev, or <ntodo> where that is null; <ntodo> bounds it either way.  <d_next>: an int that is zero when the kernel starts (its
+// waves count the jobs they take beyond their first in it).
+constexpr int kFwdGroupMaxNodes = 160;
+bool fwd_group_supported(const bath_hip_oprofile *om);
+int launch_fwd_group(bath_hip_ctx *ctx, const bath_hip_oprofile *om, SeqView v, const int32_t *d_sorted, int64_t ntodo, const int *ntodo_dev, int *d_next, float *d_sc, int32_t *d_status);
 int launch_bwd_wave(bath_hip_ctx *ctx, const bath_hip_oprofile *om, SeqView v, int64_t n, const float *d_fwd_xmx, const int64_t *d_xmx_off,
                     float *d_sc, int32_t *d_status, float *d_bck_xmx, float *d_dp = nullptr, const int64_t *d_dp_off = nullptr, int unihit = 0);
 int launch_bias_lane(bath_hip_ctx *ctx, const bath_hip_oprofile *om, SeqView v, const float *d_eo, int eo_stride, const int32_t *d_todo, int64_t ntodo,

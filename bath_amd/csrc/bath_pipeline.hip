@@ -39,7 +39,8 @@ enum { FLAG_VIT_RUN = 1, FLAG_HAS_WIN = 2 };
 
 struct Counters {                     // device-side counters, one struct per pipeline call
   int cand_count, todo_msv, todo_vit, todo_ssvb, todo_vit2, todo_fwd, win_count, overflow;
-  int todo_lb, pad_;                                        // candidates that need the local-composition bias filter
+  int todo_lb;                                              // candidates that need the local-composition bias filter
+  int fwd_next;                                             // fwd_group_kernel: jobs handed out beyond every wave's first (zero when the kernel starts, as all of these)
   unsigned long long n_orfs, orf_res;                       // ORFs >= minlen, their total aa
   unsigned long long n_past_msv, n_past_bias, n_past_vit, n_past_fwd;
   unsigned long long pos_past_msv, pos_past_bias, pos_past_vit, pos_past_fwd;
@@ -1053,7 +1054,17 @@ static int run_filters(bath_hip_ctx *ctx, const bath_hip_oprofile *om, const bat
       hipLaunchKernelGGL(fwd_keep_offsets_kernel, dim3(1), dim3(64), 0, ctx->stream, W.todo_fwd, &W.ctr->todo_fwd, W.cand.len, d_keep_off, kKeepFloats);
       BATH_HIP_TRY(ctx, hipGetLastError());
     }
-    if ((st = launch_fwd_wave(ctx, om, cv, W.todo_fwd, cap, W.cand.fwdsc, W.cand.fwd_status, &W.ctr->todo_fwd, d_keep, d_keep_off)) != BATH_OK) return st;
+    // The candidates of a model of up to 160 nodes: four per wave, a quarter wave each, the list sorted by length so that a wave's four
+    // end together (bath_fwd_group.hip; todo_sorted and len_bins are free since the Viterbi stage joined its side stream).
+    // final_kernel reads the scores by candidate, whatever the list's order.  Blocks of every size take it -- it pays on the tens of
+    // thousands of candidates of a large block, and a small block's few are scored by the same arithmetic: the group kernel and
+    // fwd_wave_kernel agree within the parser's tolerance and not by bits, and an ORF's record does not depend on its block's size.
+    const bool fwd_group = !d_keep && fwd_group_supported(om) && ctx->fwd_group != 2;
+    if (fwd_group) {
+      if ((st = launch_len_sort(ctx, W.todo_fwd, &W.ctr->todo_fwd, W.cand.len, W.len_bins, W.todo_sorted)) != BATH_OK) return st;
+      if ((st = launch_fwd_group(ctx, om, cv, W.todo_sorted, cap, &W.ctr->todo_fwd, &W.ctr->fwd_next, W.cand.fwdsc, W.cand.fwd_status)) != BATH_OK) return st;
+    } else if ((st = launch_fwd_wave(ctx, om, cv, W.todo_fwd, cap, W.cand.fwdsc, W.cand.fwd_status, &W.ctr->todo_fwd, d_keep, d_keep_off)) != BATH_OK) return st;
+    const int64_t fwd_launches = (d_keep ? 1 : 0) + (fwd_group ? 4 : 1) + 1;       // [row offsets,] Forward (the group kernel behind the sort's three), final_kernel
     if (d_keep) { ctx->fwd_rows_kept = d_keep; ctx->fwd_rows_off = d_keep_off; }
     hipLaunchKernelGGL(final_kernel, dim3(dec_blocks), dim3(256), 0, ctx->stream, W.cand, W.ctr, P, W.todo_fwd);
     BATH_HIP_TRY(ctx, hipGetLastError());
@@ -1070,7 +1081,7 @@ static int run_filters(bath_hip_ctx *ctx, const bath_hip_oprofile *om, const bat
       continue;
     }
     static const char *names[] = {"translate_orfs", "ssv_f1", "classify_msv", "f1_bias", "viterbi_windows", "ssv_windows", "post_vit", "forward_final"};
-    const int64_t launches[] = {4, 1, msv_stage ? 1 : 2, msv_stage ? 0 : 1, 4, 1, 3, 2};
+    const int64_t launches[] = {4, 1, msv_stage ? 1 : 2, msv_stage ? 0 : 1, 4, 1, 3, fwd_launches};
     ctx->timings.clear();
     for (int i = 0; i + 1 < e; i++) {
       float ms = 0.f;
@@ -1210,7 +1221,7 @@ static int run_filters_lanes(bath_hip_ctx *ctx, const bath_hip_oprofile *om, con
     }
     ctx->lanes.push_back(lane);
   }
-  for (bath_hip_ctx *lane : ctx->lanes) { lane->fs_strict = ctx->fs_strict; lane->fs_odds = ctx->fs_odds; lane->fs5_odds = ctx->fs5_odds; }
+  for (bath_hip_ctx *lane : ctx->lanes) { lane->fs_strict = ctx->fs_strict; lane->fs_odds = ctx->fs_odds; lane->fs5_odds = ctx->fs5_odds; lane->fwd_group = ctx->fwd_group; }
   if ((st = ensure_parts(ctx, dna, K)) != BATH_OK) return st;
   std::vector<bath_pipeline_stats> pst((size_t)K);
   std::vector<const bath_orf_result *> pres((size_t)K, nullptr);

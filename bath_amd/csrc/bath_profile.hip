@@ -232,6 +232,14 @@ extern "C" int bath_hip_set_fs_strict(bath_hip_ctx *ctx, int on) {
   return BATH_OK;
 }
 
+extern "C" int bath_hip_set_fwd_group(bath_hip_ctx *ctx, int mode) {
+  if (!ctx) return BATH_EINVAL;
+  if (mode < 0 || mode > 2) { ctx->set_error("bath_hip_set_fwd_group: mode must be 0, 1 or 2"); return BATH_EINVAL; }
+  ctx->fwd_group = mode;
+  for (bath_hip_ctx *l : ctx->lanes) l->fwd_group = mode;
+  return BATH_OK;
+}
+
 extern "C" int bath_hip_set_fs_odds(bath_hip_ctx *ctx, int on) {
   if (!ctx) return BATH_EINVAL;
   ctx->fs_odds = on ? 1 : 0;

@@ -90,6 +90,7 @@ enum class Scratch : int {
   kMsvTodo,                 // bath_hip_msvfilter: the targets SSV left undecided
   kFwdbackRowOffsets = kMsvTodo,    // bath_hip_fwdback_parser: row offsets; a call of its own
   kStdRegionWork = kMsvTodo,        // std_domains: std_regions_kernel's three floats per row; a call of its own
+  kFwdGroupWork,            // bath_hip_fwdparser_group: the work list, its copy sorted by length, the sort's bins, the list's length
   kBiasFilterScores,        // bath_hip_bias_filter: the filter scores
   kStdRegionList = kBiasFilterScores,     // std_domains: the ORFs' regions; a call of its own
   kStdRegionCfgLen = kBiasFilterScores,   // the multi-domain regions' configuration lengths: std_domains has copied the region list out and synchronized ("parsers + regions")

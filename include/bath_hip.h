@@ -130,6 +130,12 @@ int         bath_hip_set_fs_strict(bath_hip_ctx *ctx, int on);
  * every other stage (envelopes, the regions' Forward, decoding, optimal accuracy) runs as bath_hip_set_fs_strict selects.
  * 0 (the default): no change.  The first odds-mode call for a 3-codon profile builds its odds-ratio tables on the device. */
 int         bath_hip_set_fs_odds(bath_hip_ctx *ctx, int on);
+/* Which kernel scores the Forward stage of the filter cascade (bath_hip_pipeline_filters and what builds on it).  0 (the default):
+ * fwd_group_kernel, four targets per wave, for a model of up to 160 nodes when the stage's special-state rows are not kept for the
+ * domain stage, whatever the block's size; the wave-per-target kernel otherwise.  1: the same, and it stays so if the default ever
+ * gains a rule of its own (what tests ask for).  2: never.  The two kernels' scores agree within the Forward parser's contract
+ * (1e-4 relative / 2e-4 absolute nats), not bit for bit.  BATH_EINVAL for a null ctx or another mode. */
+int         bath_hip_set_fwd_group(bath_hip_ctx *ctx, int mode);
 /* Odds-ratio mode of the 5-codon Forward and Backward.  1: the envelopes' Forward and Backward (bath_hip_fs5_envelopes[_x] with
  * BATH_LOGSUM_CONTEXT, the pipeline's envelope batches) and the regions' multihit Forward (the domain stage, bath_hip_fs5_forward_full)
  * run in fp32 odds ratios with sparse rescaling, as the reference's p7_Forward_Frameshift / p7_Backward_Frameshift (impl_sse/
@@ -299,6 +305,11 @@ int bath_hip_ssvfilter(bath_hip_ctx *ctx, const bath_hip_oprofile *om, const bat
 int bath_hip_msvfilter(bath_hip_ctx *ctx, const bath_hip_oprofile *om, const bath_hip_seqs *sq, float *sc, int32_t *status);      /* p7_MSVFilter, msvfilter.c:74  */
 int bath_hip_vitfilter(bath_hip_ctx *ctx, const bath_hip_oprofile *om, const bath_hip_seqs *sq, float *sc, int32_t *status);      /* p7_ViterbiFilter, vitfilter.c:83 */
 int bath_hip_forward_parser(bath_hip_ctx *ctx, const bath_hip_oprofile *om, const bath_hip_seqs *sq, float *sc, int32_t *status); /* p7_ForwardParser, fwdback.c:132 */
+/* The same scores by the group kernel of the cascade's Forward stage (fwd_group_kernel: a quarter wave per target, four targets of
+ * a length-sorted list per wave; models of up to 160 nodes, BATH_EINVAL beyond).  Not bit-identical to bath_hip_forward_parser: the
+ * cells' arithmetic is the same, the D scan and the sum over the model associate differently.  Contract: status equal, scores
+ * within 1e-4 relative / 2e-4 absolute nats of p7_ForwardParser. */
+int bath_hip_fwdparser_group(bath_hip_ctx *ctx, const bath_hip_oprofile *om, const bath_hip_seqs *sq, float *sc, int32_t *status);
 /* p7_bg_NullOne + p7_bg_FilterScore (p7_bg.c:356,491) with p7_bg_SetFilter(bg, M, om->compo): nullsc[n], filtersc[n] */
 int bath_hip_bias_filter(bath_hip_ctx *ctx, const bath_hip_oprofile *om, const bath_hip_seqs *sq, float *nullsc, float *filtersc);
 /* p7_ForwardParser followed by p7_BackwardParser (fwdback.c:132,236) with the special-state rows p7_domaindef reads:
