@@ -63,11 +63,8 @@ template <int NR, int G>
 __global__ __launch_bounds__(256, NR <= 76 ? 4 : 1) void ssv_orf_kernel(const uint8_t *__restrict__ aa, const OrfRec *__restrict__ orfs, const int *__restrict__ n_orfs_dev,
                                                       SeqView dna, const int16_t *__restrict__ cost_tab, int row_bytes,
                                                       const int16_t *__restrict__ emit_thresh, int thresh_max,
-                                                      Cand cand, int cand_cap, Counters *__restrict__ ctr, int chunk) {
+                                                      Cand cand, int cand_cap, Counters *__restrict__ ctr) {
   extern __shared__ __attribute__((aligned(16))) char lds[];
-  // chunk > 0: not persistent -- a wave scores <chunk> consecutive groups of the list and exits, so that wave slots come free
-  // all the time and kernels of higher-priority streams get onto the chip while this one is running
-  if (chunk > 0 && (int64_t)blockIdx.x * (blockDim.x >> 6) * chunk * (64 / G) >= (int64_t)*n_orfs_dev) return;
   {
     const int n32 = kSsvRows * row_bytes / 4;
     const uint32_t *src = reinterpret_cast<const uint32_t *>(cost_tab);
@@ -84,24 +81,13 @@ __global__ __launch_bounds__(256, NR <= 76 ? 4 : 1) void ssv_orf_kernel(const ui
   const int64_t wave0 = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
   const int64_t nwaves = ((int64_t)gridDim.x * blockDim.x) >> 6;
   const s16x2 fl = {0, 0};                                      // the begin score
-  const int64_t tb_first = chunk > 0 ? wave0 * chunk * TPW : wave0 * TPW, tb_step = chunk > 0 ? TPW : nwaves * TPW;
-  const int64_t tb_end = chunk > 0 ? (tb_first + (int64_t)chunk * TPW < n_orfs ? tb_first + (int64_t)chunk * TPW : n_orfs) : n_orfs;
-  for (int64_t tb = tb_first; tb < tb_end; tb += tb_step) {
+  for (int64_t tb = wave0 * TPW; tb < n_orfs; tb += nwaves * TPW) {
     const int64_t t = tb + SsvGroups<G>::slot(lane);
     const bool live = t < n_orfs;
     OrfRec rec{0, 0, 0};
     if (live) rec = orfs[t];
     const int L = rec.len_sf & 0x0fffffff;
-#ifdef BATH_SSV_POOL_PROBE
-    // Timing probe (WRONG results; tools/ssv_pool_probe.sh): the residue reads as they would be from a pool written in work-list
-    // order and interleaved per wave -- the 8 bytes of a wave's 64 lanes contiguous (512 B per load instruction), a wave's groups
-    // one after the other -- i.e. with NO over-fetch: what the SSV kernel itself could gain from such a pool, before the pool's cost
-    const uint8_t *s = aa + ((size_t)(tb / TPW) * 8192) % ((size_t)1 << 27) + (size_t)lane * 8;
-#define BATH_SSV_RES(i8) (s + (size_t)(i8) * 64)
-#else
     const uint8_t *s = aa + rec.aa_off;
-#define BATH_SSV_RES(i8) (s + (i8))
-#endif
     const int Lw = wave_max_i32(L);
     s16x2 reg[NR];
 #pragma unroll
@@ -112,10 +98,10 @@ __global__ __launch_bounds__(256, NR <= 76 ? 4 : 1) void ssv_orf_kernel(const ui
     // multiple of 4 rows).  Staging the residues through LDS instead (three global_load_lds_dwordx4 per wave and 32 rows, double
     // buffered) was measured at -2% time and -20% traffic and not kept: most of the excess traffic is 128-byte lines shared by
     // ORFs of different lengths, which no read pattern of this kernel can merge.
-    uint64_t qnext = (0 < L) ? *reinterpret_cast<const uint64_t *>(BATH_SSV_RES(0)) : 0x1d1d1d1d1d1d1d1dull;
+    uint64_t qnext = (0 < L) ? *reinterpret_cast<const uint64_t *>(s) : 0x1d1d1d1d1d1d1d1dull;
     for (int i0 = 0; i0 < Lw; i0 += 8) {
       const uint64_t q = qnext;
-      qnext = (i0 + 8 < L) ? *reinterpret_cast<const uint64_t *>(BATH_SSV_RES(i0 + 8)) : 0x1d1d1d1d1d1d1d1dull;
+      qnext = (i0 + 8 < L) ? *reinterpret_cast<const uint64_t *>(s + i0 + 8) : 0x1d1d1d1d1d1d1d1dull;
       const int nrow = min(8, Lw - i0);                              // wave-uniform
       // the row's overhead is kept to full-rate 32-bit ops: a bit-field extract on the dword holding the residue (no 64-bit
       // shift), a 24-bit multiply for the row offset (v_mul_lo_u32 is quarter rate); bytes inside an ORF are residue codes < 29
@@ -949,17 +935,14 @@ static int run_filters(bath_hip_ctx *ctx, const bath_hip_oprofile *om, const bat
     BATH_HIP_TRY(ctx, hipEventRecord(ev[e++], ctx->stream));
     // 2. SSV + F1 threshold, lane per ORF
     {
-      static const int ssv_chunk = [] { const char *e = std::getenv("BATH_HIP_SSV_CHUNK"); return e ? std::atoi(e) : 0; }();
-      int blocks = ctx->prop.multiProcessorCount * 4;
+      const int blocks = ctx->prop.multiProcessorCount * 4;
       const int ssv_threads = 256;
-      const int wpb = ssv_threads / 64;
-      if (ssv_chunk > 0) blocks = (int)std::min<int64_t>((max_orfs + (int64_t)wpb * (64 / om->G) * ssv_chunk - 1) / ((int64_t)wpb * (64 / om->G) * ssv_chunk), 1 << 30);
       bool launched = false;
 #define BATH_ORF_CASE(N, GG)                                                                                                     \
   if (!launched && NRk == N && om->G == GG) {                                                                                    \
     if (ssv_shmem > 64 * 1024) (void)bath::allow_max_lds((const void *)ssv_orf_kernel<N, GG>); \
     hipLaunchKernelGGL((ssv_orf_kernel<N, GG>), dim3(blocks), dim3(ssv_threads), ssv_shmem, ctx->stream, W.pool, ob.sorted, ob.ntotal,                  \
-                       dna->view(), om->d_ssv, om->ssv_row_bytes, d_emit, max_orf, W.cand, W.cand_cap, W.ctr, ssv_chunk);        \
+                       dna->view(), om->d_ssv, om->ssv_row_bytes, d_emit, max_orf, W.cand, W.cand_cap, W.ctr);                   \
     launched = true;                                                                                                             \
   }
       BATH_SSV_SHAPES(BATH_ORF_CASE)
@@ -968,14 +951,6 @@ static int run_filters(bath_hip_ctx *ctx, const bath_hip_oprofile *om, const bat
       BATH_HIP_TRY(ctx, hipGetLastError());
     }
     BATH_HIP_TRY(ctx, hipEventRecord(ev[e++], ctx->stream));
-    // everything after SSV works on a few 10^5 survivors in chains of latency-bound kernels: on a stream of its own with the
-    // highest priority, so that (with a non-persistent SSV) it runs while another part's translation + SSV fill the chip
-    hipStream_t bulk_stream = ctx->stream;
-    struct StreamRestore { bath_hip_ctx *c; hipStream_t s; ~StreamRestore() { c->stream = s; } } stream_restore{ctx, bulk_stream};
-    if (ctx->tail_stream) {
-      BATH_HIP_TRY(ctx, hipStreamWaitEvent(ctx->tail_stream, ev[e - 1], 0));
-      ctx->stream = ctx->tail_stream;
-    }
     // The lane-per-ORF kernels pay off when the candidates fill the chip's lanes (65 k of them): a block of 10^9 nt leaves 4 x 10^5
     // Viterbi candidates, a 25 Mb query of configs[3] 5 x 10^3 -- 80 waves that each last as long as their longest ORF (0.7 ms whatever
     // their number) where the wave-per-ORF kernel takes 0.2 ms.  The candidate counts live on the device; the block's size is the
@@ -1147,14 +1122,11 @@ static int ensure_parts(bath_hip_ctx *ctx, const bath_hip_seqs *dna, int K) {
   dna->parts.clear();
   int64_t w0 = 0;
   for (int k = 0; k < K; k++) {
-    // cut where the running residue count passes the part's share of the total.  With two parts the shares are unequal: the
-    // second part's tail (decision kernels, Viterbi, Forward on its survivors) is the only work nothing else overlaps, so the
-    // second part is the smaller one (BATH_HIP_LANE_SPLIT = share of the first part, tools/ab_probe.py)
-    static const double split2 = [] { const char *e = std::getenv("BATH_HIP_LANE_SPLIT"); const double v = e ? std::atof(e) : 0.0; return (v > 0.05 && v < 0.95) ? v : 0.5; }();
+    // cut where the running residue count passes the part's share of the total: equal shares
     int64_t w1 = w0;
     if (k == K - 1) w1 = dna->n;
     else {
-      const int64_t target = (K == 2) ? (int64_t)((double)dna->total_aligned * split2) : dna->total_aligned / K * (k + 1);
+      const int64_t target = dna->total_aligned / K * (k + 1);
       w1 = std::lower_bound(dna->h_off.begin() + w0, dna->h_off.end(), target) - dna->h_off.begin();
       w1 = std::max(w1, std::min(w0 + 1, dna->n));
     }
@@ -1205,19 +1177,12 @@ static int run_filters_lanes(bath_hip_ctx *ctx, const bath_hip_oprofile *om, con
     // Descending stream priorities: when two parts have work ready, the earlier part's workgroups are dispatched first.  Left to
     // the hardware queues the interleaving of the parts is a race and about every third process lands on a schedule that is
     // 20% slower (13.4 vs 16 ms per step on the bench block); with priorities it is 13.2-13.9 ms every time (tools/ab_probe.py).
-    // BATH_HIP_LANE_PRIO=0 turns it off.
-    const char *pe = std::getenv("BATH_HIP_LANE_PRIO");
-    if (!(pe && pe[0] == '0')) {
-      int lo = 0, hi = 0;
-      if (hipDeviceGetStreamPriorityRange(&lo, &hi) == hipSuccess && lo != hi) {
-        (void)hipStreamDestroy(lane->stream);
-        const char *te = std::getenv("BATH_HIP_TAIL_PRIO");
-        const bool tails = te && te[0] == '1';
-        // hi is numerically the smallest value = highest priority.  With tail streams: tails highest, the first part's bulk work in the middle
-        const int prio = tails ? (ctx->lanes.empty() ? std::min(lo, hi + 1) : lo) : (ctx->lanes.empty() ? hi : lo);
-        if (hipStreamCreateWithPriority(&lane->stream, hipStreamNonBlocking, prio) != hipSuccess) { ctx->set_error("hipStreamCreateWithPriority"); return BATH_EFAIL; }
-        if (tails && hipStreamCreateWithPriority(&lane->tail_stream, hipStreamNonBlocking, hi) != hipSuccess) { ctx->set_error("hipStreamCreateWithPriority"); return BATH_EFAIL; }
-      }
+    // Where the device reports no priority range the lane keeps the stream it was created with.
+    int lo = 0, hi = 0;
+    if (hipDeviceGetStreamPriorityRange(&lo, &hi) == hipSuccess && lo != hi) {
+      (void)hipStreamDestroy(lane->stream);
+      // hi is numerically the smallest value = highest priority
+      if (hipStreamCreateWithPriority(&lane->stream, hipStreamNonBlocking, ctx->lanes.empty() ? hi : lo) != hipSuccess) { ctx->set_error("hipStreamCreateWithPriority"); return BATH_EFAIL; }
     }
     ctx->lanes.push_back(lane);
   }
@@ -1276,23 +1241,6 @@ static int run_filters_lanes(bath_hip_ctx *ctx, const bath_hip_oprofile *om, con
     }
   }
   return BATH_OK;
-}
-
-// experiment: every lane runs its part <reps> times back to back (what a pipelined block loop would look like in steady state)
-extern "C" int bath_hip_pipeline_filters_repeat(bath_hip_ctx *ctx, const bath_hip_oprofile *om, const bath_hip_seqs *dna,
-                                                const bath_pipeline_params *prm, int reps, bath_pipeline_stats *stats) {
-  std::vector<FilterState> states;
-  int st = run_filters_lanes(ctx, om, dna, prm, stats, nullptr, nullptr, &states,
-                             [&](int, bath_hip_ctx *lane, const bath_hip_seqs *part, const FilterState &) {
-                               for (int r = 1; r < reps; r++) {
-                                 bath_pipeline_stats s2{};
-                                 int64_t n2 = 0;
-                                 const int rc = run_filters(lane, om, part, prm, &s2, nullptr, &n2, nullptr);
-                                 if (rc != BATH_OK) return rc;
-                               }
-                               return (int)BATH_OK;
-                             });
-  return st;
 }
 
 extern "C" int bath_hip_pipeline_filters(bath_hip_ctx *ctx, const bath_hip_oprofile *om, const bath_hip_seqs *dna,

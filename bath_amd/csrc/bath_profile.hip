@@ -148,7 +148,6 @@ extern "C" void bath_hip_finalize(bath_hip_ctx *ctx) {
   for (bath_hip_ctx *lane : ctx->lanes) bath_hip_finalize(lane);
   ctx->lanes.clear();
   if (ctx->ev_lanes) (void)hipEventDestroy(ctx->ev_lanes);
-  if (ctx->tail_stream) (void)hipStreamDestroy(ctx->tail_stream);
   if (ctx->aux) { bath_hip_finalize(ctx->aux); ctx->aux = nullptr; }
   if (ctx->aux2) { bath_hip_finalize(ctx->aux2); ctx->aux2 = nullptr; }
   if (ctx->aux3) { bath_hip_finalize(ctx->aux3); ctx->aux3 = nullptr; }
@@ -181,7 +180,6 @@ extern "C" int bath_hip_trim(bath_hip_ctx *ctx) {
   if (ctx->aux) { bath_hip_finalize(ctx->aux); ctx->aux = nullptr; }
   if (ctx->aux2) { bath_hip_finalize(ctx->aux2); ctx->aux2 = nullptr; }
   if (ctx->aux3) { bath_hip_finalize(ctx->aux3); ctx->aux3 = nullptr; }
-  if (ctx->tail_stream) { (void)hipStreamDestroy(ctx->tail_stream); ctx->tail_stream = nullptr; }
   if (ctx->copy_stream) { (void)hipStreamSynchronize(ctx->copy_stream); (void)hipStreamDestroy(ctx->copy_stream); ctx->copy_stream = nullptr; }
   if (ctx->side_stream) {
     (void)hipStreamSynchronize(ctx->side_stream); (void)hipStreamDestroy(ctx->side_stream); ctx->side_stream = nullptr;
@@ -423,11 +421,8 @@ extern "C" int bath_hip_oprofile_convert(bath_hip_ctx *ctx, const bath_profile *
   // SIMD, where the packed 16-bit ops issue at 4.4e11/s (with 80-152 cell registers a SIMD holds one or two waves:
   // M = 185...247: ssv 0.29-0.38 -> 0.22-0.27 ms on a 12.5 Mb genome).  Beyond 304 nodes the round-1 rule stays -- tiles of up
   // to 208 registers before more lanes are added: two lanes x 112 registers at M = 409, four / eight lanes with narrow tiles
-  // at M = 409 / 1024 were measured and lose.  BATH_HIP_SSV_WIDE=1: one lane up to 416 nodes (rounds 1-2);
-  // BATH_HIP_SSV_G2_MAX: the upper end of the two-lane range, for A/B runs (tools/ssv_shape_probe.py).
-  static const bool wide = [] { const char *e = std::getenv("BATH_HIP_SSV_WIDE"); return e && e[0] == '1'; }();
-  static const int g2max = [] { const char *e = std::getenv("BATH_HIP_SSV_G2_MAX"); return e ? std::atoi(e) : 304; }();
-  int G = (!wide && M > 152 && M <= g2max) ? 2 : 1;             // (305...416 nodes: one lane with 156-208 registers is 1.2x faster than two with 112, measured at M = 409)
+  // at M = 409 / 1024 were measured and lose.
+  int G = (M > 152 && M <= 304) ? 2 : 1;                      // (305...416 nodes: one lane with 156-208 registers is 1.2x faster than two with 112, measured at M = 409)
   while (G < 8 && M > 416 * G) G *= 2;                        // up to 208 registers (416 nodes) per lane
   if (M > 416 * G) { ctx->set_error("model longer than 3328 nodes"); delete om; return BATH_EINVAL; }
   int NR = ((M + G - 1) / G + 1) / 2;

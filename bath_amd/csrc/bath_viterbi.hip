@@ -53,10 +53,7 @@ struct VitLaneConsts {
 typedef uint32_t u32x16 __attribute__((ext_vector_type(16)));
 
 template <int NR>
-#ifndef BATH_VIT_WAVES
-#define BATH_VIT_WAVES 1
-#endif
-__global__ __launch_bounds__(256, (NR <= 76 ? BATH_VIT_WAVES : 1)) void vit_lane_kernel(SeqView sq, VitLaneTables tb, const uint32_t *__restrict__ tw2g, VitLaneConsts c, const int16_t *__restrict__ xwmove_tab,
+__global__ __launch_bounds__(256, 1) void vit_lane_kernel(SeqView sq, VitLaneTables tb, const uint32_t *__restrict__ tw2g, VitLaneConsts c, const int16_t *__restrict__ xwmove_tab,
                                                           const uint8_t *__restrict__ tjb_tab, const int32_t *__restrict__ todo, int64_t ntodo,
                                                           const int *__restrict__ ntodo_dev, const int *__restrict__ skip_dev, float *__restrict__ sc, int32_t *__restrict__ status,
                                                           const float *__restrict__ filtersc, const uint8_t *__restrict__ ssv_scores,
@@ -367,8 +364,7 @@ int launch_vit_sorted(bath_hip_ctx *ctx, const bath_hip_oprofile *om, SeqView v,
     BATH_HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_fork, hipEventDisableTiming));
     BATH_HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_join, hipEventDisableTiming));
   }
-  static const int long_orf = [] { const char *e = std::getenv("BATH_HIP_VIT_LONG"); return e ? std::atoi(e) : kVitLongTarget; }();
-  const int *d_nlong = len_sort_count_longer(d_bins, long_orf);
+  const int *d_nlong = len_sort_count_longer(d_bins, kVitLongTarget);
   BATH_HIP_TRY(ctx, hipEventRecord(ctx->ev_fork, ctx->stream));
   BATH_HIP_TRY(ctx, hipStreamWaitEvent(ctx->side_stream, ctx->ev_fork, 0));
   {

@@ -172,7 +172,7 @@ def test_vit_lane_every_register_tiling(gpu_ctx, tmp_path, M):
 
 
 VIT_WINDOWS_P = 1e-3
-VIT_LONG_TARGET = 128          # bath_viterbi.hip, kVitLongTarget: longer targets of a sorted list go to the wave-per-target kernel
+LONG_VIT_TARGET = 128          # bath_viterbi.hip, kVitLongTarget: longer targets of a sorted list go to the wave-per-target kernel
 
 
 def vit_window_targets(model, M):
@@ -283,8 +283,8 @@ def test_vit_lane_windows_every_register_tiling(gpu_ctx, tmp_path, lane_forced_w
     to_model_end = sum(1 for w in owins if w[2] == M)
     to_target_end = sum(1 for w in owins if w[1] + w[3] - 1 == lens[w[0]])
     print("M=%d NR=%d targets=%d long=%d ERANGE=%d windows=%d multi-window targets=%d to-model-end=%d to-target-end=%d" %
-          (M, vit_lane_nr(M), len(seqs), (lens > VIT_LONG_TARGET).sum(), (ost == ESL_ERANGE).sum(), len(owins), (per_target >= 2).sum(), to_model_end, to_target_end))
-    assert (lens > VIT_LONG_TARGET).sum() >= 5 and (lens <= VIT_LONG_TARGET).sum() >= 50
+          (M, vit_lane_nr(M), len(seqs), (lens > LONG_VIT_TARGET).sum(), (ost == ESL_ERANGE).sum(), len(owins), (per_target >= 2).sum(), to_model_end, to_target_end))
+    assert (lens > LONG_VIT_TARGET).sum() >= 5 and (lens <= LONG_VIT_TARGET).sum() >= 50
     if M >= 33:
         assert len(owins) >= 20 and (per_target >= 2).sum() >= 3
         assert to_model_end >= 1 and to_target_end >= 1

@@ -13,21 +13,13 @@ alone, says that a kernel which breaks a seam changes a score that is compared (
 M's own entry in the table: the padding cells behind it feed no node, so their value, -1.0 or 0, cannot change a maximum."""
 import atexit
 import functools
-import hashlib
-import json
 import os
 import shutil
-import subprocess
-import sys
 import tempfile
 import time
 
 import numpy as np
 import pytest
-
-if __name__ == "__main__":                     # the switch leg's child process: python test_ssv_shapes_gpu.py wide | chunk
-    sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 
 import bath_amd as ba
 import common
@@ -36,7 +28,7 @@ import oracle_lib as ol
 pytestmark = pytest.mark.gpu
 
 # BATH_SSV_SHAPES, in the order of bath_tilings.hpp
-SSV_SHAPES = ([(nr, 1) for nr in range(16, 113, 4)] + [(nr, 1) for nr in range(128, 209, 16)]
+SSV_SHAPES = ([(nr, 1) for nr in range(16, 77, 4)] + [(nr, 1) for nr in range(160, 209, 16)]
               + [(40, 2), (48, 2), (56, 2), (64, 2), (72, 2), (76, 2)] + [(nr, 2) for nr in range(112, 209, 16)]
               + [(nr, 4) for nr in range(112, 209, 16)] + [(112, 8), (128, 8), (144, 8), (160, 8)])
 SSV_MAX_NODES = 2560                           # 8 lanes x 160 registers x 2 nodes: the largest cost table a workgroup's LDS holds
@@ -45,9 +37,9 @@ CASCADE_MAX_NODES = 2048
 LDS_MESSAGE = "model too long for the LDS-resident SSV cost table"
 
 
-def ssv_shape(M, wide=False):
-    """(NR, G) of the SSV kernels for a model of M nodes: the rule of bath_profile.hip restated (wide: BATH_HIP_SSV_WIDE=1)."""
-    G = 2 if (not wide and 152 < M <= 304) else 1
+def ssv_shape(M):
+    """(NR, G) of the SSV kernels for a model of M nodes: the rule of bath_profile.hip restated."""
+    G = 2 if 152 < M <= 304 else 1
     while G < 8 and M > 416 * G:
         G *= 2
     assert M <= 416 * G
@@ -61,23 +53,20 @@ def ssv_shape(M, wide=False):
     return max(NR, 16), G
 
 
-# per shape: the smallest and the largest model that select it, and the switch under which they do
+# per shape: the smallest and the largest model that select it
 SSV_M = {
-    (16, 1): (1, 32, None), (20, 1): (33, 40, None), (24, 1): (41, 48, None), (28, 1): (49, 56, None), (32, 1): (57, 64, None),
-    (36, 1): (65, 72, None), (40, 1): (73, 80, None), (44, 1): (81, 88, None), (48, 1): (89, 96, None), (52, 1): (97, 104, None),
-    (56, 1): (105, 112, None), (60, 1): (113, 120, None), (64, 1): (121, 128, None), (68, 1): (129, 136, None),
-    (72, 1): (137, 144, None), (76, 1): (145, 152, None),
-    (80, 1): (153, 160, "wide"), (84, 1): (161, 168, "wide"), (88, 1): (169, 176, "wide"), (92, 1): (177, 184, "wide"),
-    (96, 1): (185, 192, "wide"), (100, 1): (193, 200, "wide"), (104, 1): (201, 208, "wide"), (108, 1): (209, 216, "wide"),
-    (112, 1): (217, 224, "wide"), (128, 1): (225, 256, "wide"), (144, 1): (257, 288, "wide"),
-    (160, 1): (305, 320, None), (176, 1): (321, 352, None), (192, 1): (353, 384, None), (208, 1): (385, 416, None),
-    (40, 2): (153, 160, None), (48, 2): (161, 192, None), (56, 2): (193, 224, None), (64, 2): (225, 256, None),
-    (72, 2): (257, 288, None), (76, 2): (289, 304, None),
-    (112, 2): (417, 448, None), (128, 2): (449, 512, None), (144, 2): (513, 576, None), (160, 2): (577, 640, None),
-    (176, 2): (641, 704, None), (192, 2): (705, 768, None), (208, 2): (769, 832, None),
-    (112, 4): (833, 896, None), (128, 4): (897, 1024, None), (144, 4): (1025, 1152, None), (160, 4): (1153, 1280, None),
-    (176, 4): (1281, 1408, None), (192, 4): (1409, 1536, None), (208, 4): (1537, 1664, None),
-    (112, 8): (1665, 1792, None), (128, 8): (1793, 2048, None), (144, 8): (2049, 2304, None), (160, 8): (2305, 2560, None),
+    (16, 1): (1, 32), (20, 1): (33, 40), (24, 1): (41, 48), (28, 1): (49, 56), (32, 1): (57, 64),
+    (36, 1): (65, 72), (40, 1): (73, 80), (44, 1): (81, 88), (48, 1): (89, 96), (52, 1): (97, 104),
+    (56, 1): (105, 112), (60, 1): (113, 120), (64, 1): (121, 128), (68, 1): (129, 136),
+    (72, 1): (137, 144), (76, 1): (145, 152),
+    (160, 1): (305, 320), (176, 1): (321, 352), (192, 1): (353, 384), (208, 1): (385, 416),
+    (40, 2): (153, 160), (48, 2): (161, 192), (56, 2): (193, 224), (64, 2): (225, 256),
+    (72, 2): (257, 288), (76, 2): (289, 304),
+    (112, 2): (417, 448), (128, 2): (449, 512), (144, 2): (513, 576), (160, 2): (577, 640),
+    (176, 2): (641, 704), (192, 2): (705, 768), (208, 2): (769, 832),
+    (112, 4): (833, 896), (128, 4): (897, 1024), (144, 4): (1025, 1152), (160, 4): (1153, 1280),
+    (176, 4): (1281, 1408), (192, 4): (1409, 1536), (208, 4): (1537, 1664),
+    (112, 8): (1665, 1792), (128, 8): (1793, 2048), (144, 8): (2049, 2304), (160, 8): (2305, 2560),
 }
 
 
@@ -93,19 +82,8 @@ def ssv_seams(M, NR, G):
     return seams
 
 
-def cases(switch):
-    """(M, NR, G) at both ends of every shape that <switch> selects."""
-    out = []
-    for (nr, g), (lo, hi, sw) in SSV_M.items():
-        if sw == switch:
-            out += [(m, nr, g) for m in sorted({lo, hi})]
-    return out
-
-
-DEFAULT_CASES = cases(None)
-WIDE_CASES = cases("wide")
+DEFAULT_CASES = [(m, nr, g) for (nr, g), (lo, hi) in SSV_M.items() for m in sorted({lo, hi})]      # (M, NR, G) at both ends of every shape
 CASCADE_CASES = [c for c in DEFAULT_CASES if c[0] <= CASCADE_MAX_NODES]
-CHUNK_M = [100, 304, 1024, 1793]               # one model of each G for the non-persistent launch
 case_id = lambda c: "NR%d-G%d-M%d" % (c[1], c[2], c[0])
 
 # ---------------------------------------------------------------------------------------------------------------------------------
@@ -164,11 +142,11 @@ class Inputs:
 
 
 @functools.lru_cache(maxsize=None)
-def inputs(M, wide=False):
+def inputs(M):
     """Model, targets and the oracle's results for the M-node synthetic model, built once per model and left unchanged."""
     t0 = time.time()
     I = Inputs()
-    I.M, (I.NR, I.G) = M, ssv_shape(M, wide)
+    I.M, (I.NR, I.G) = M, ssv_shape(M)
     I.path = common.write_synthetic_bhmm(os.path.join(_tmpdir(), "s%d.bhmm" % M), M, seed=M)
     I.model = model = ol.Model(I.path, 0)
     mat, S = match_bits(model)
@@ -229,9 +207,9 @@ def _bits(a):
     return np.asarray(a, np.float32).view(np.uint32)
 
 
-def check_standalone(ctx, M, wide=False):
+def check_standalone(ctx, M):
     """ba.SSVFilter and ba.MSVFilter against the oracle over the model's targets; the seam targets by name."""
-    I = inputs(M, wide)
+    I = inputs(M)
     seam_condition(I)
     om = ba.OProfile(ctx, ba.Profile(ba.HMM(I.path, 0)))
     blk = ba.SeqBlock(ctx, I.seqs)
@@ -291,9 +269,9 @@ def cascade_windows(I):
     return wins, planted
 
 
-def check_cascade(ctx, M, wide=False):
+def check_cascade(ctx, M):
     """ssv_orf_kernel through the cascade with F1 = 1.0, where every ORF is handed on and reported: status and score of every ORF."""
-    I = inputs(M, wide)
+    I = inputs(M)
     om = ba.OProfile(ctx, ba.Profile(ba.HMM(I.path, 0)))
     wins, planted = cascade_windows(I)
     stats, res = ba.Pipeline(ctx, om, fs_pipe=False, F1=1.0, min_orf_len=5).run(ba.SeqBlock(ctx, wins))
@@ -319,8 +297,6 @@ def check_cascade(ctx, M, wide=False):
     for w, i in planted:
         if len(I.seqs[i]) >= 5:
             assert any(o.n == len(I.seqs[i]) and (ost[i] != 0 or (o.msv_status == 0 and _bits(o.usc) == _bits(osc[i]))) for o in by_window[w]), (M, w, i)
-    rec = np.sort(np.array([(g["window"], g["strand"], g["frame"], g["start"], g["end"], g["msv_status"], int(_bits(g["usc"]))) for g in res], np.int64), axis=0)
-    return hashlib.sha256(np.ascontiguousarray(rec).tobytes()).hexdigest(), len(res)
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------
@@ -347,33 +323,6 @@ def test_ssv_cascade_every_shape(gpu_ctx, case):
     check_cascade(gpu_ctx, M)
 
 
-def _child(mode, env_extra):
-    env = dict(os.environ)
-    for k in ("BATH_HIP_SSV_WIDE", "BATH_HIP_SSV_CHUNK", "BATH_HIP_SSV_G2_MAX", "BATH_HIP_TEST_CANDCAP"):
-        env.pop(k, None)
-    env.update(env_extra)
-    p = subprocess.run([sys.executable, os.path.abspath(__file__), mode], env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=600)
-    print(p.stdout[-4000:])
-    assert p.returncode == 0, p.stdout[-4000:]
-    return json.loads(p.stdout.strip().splitlines()[-1])
-
-
-def test_ssv_wide_shapes_in_a_child_process():
-    """The 11 one-lane shapes of 80 to 144 registers are chosen only under BATH_HIP_SSV_WIDE=1, which is read once per process:
-    both legs at both ends of each of them, in one fresh process."""
-    out = _child("wide", {"BATH_HIP_SSV_WIDE": "1"})
-    assert out["cases"] == [list(c) for c in WIDE_CASES] and len(WIDE_CASES) == 22
-
-
-def test_ssv_chunked_launch_in_child_processes(gpu_ctx):
-    """BATH_HIP_SSV_CHUNK=n: the launch that is not persistent, a wave scoring n groups of the work list.  The cascade leg for one
-    model of each G, with n = 1 and n = 3: the oracle's records in the child, and the records of the persistent launch here."""
-    here = {str(m): list(check_cascade(gpu_ctx, m)) for m in CHUNK_M}
-    assert sorted(ssv_shape(m)[1] for m in CHUNK_M) == [1, 2, 4, 8]
-    for n in ("1", "3"):
-        assert _child("chunk", {"BATH_HIP_SSV_CHUNK": n})["records"] == here, n
-
-
 @pytest.mark.parametrize("M", [SSV_MAX_NODES + 1, OPROFILE_MAX_NODES])
 def test_standalone_filters_refuse_a_table_beyond_the_lds(gpu_ctx, M):
     """An OProfile holds up to 3328 nodes (ssv_bath_kernel<52> needs them), the SSV cost table of a workgroup's 160 KB of LDS 2560:
@@ -387,26 +336,3 @@ def test_standalone_filters_refuse_a_table_beyond_the_lds(gpu_ctx, M):
             f(gpu_ctx, om, blk)
     check_standalone(gpu_ctx, SSV_MAX_NODES)
 
-
-def _main(mode):
-    ctx = ba.Context(0)
-    out = {}
-    if mode == "wide":
-        assert os.environ.get("BATH_HIP_SSV_WIDE") == "1"
-        for M, NR, G in WIDE_CASES:
-            assert ssv_shape(M, True) == (NR, G)
-            check_standalone(ctx, M, True)
-            check_cascade(ctx, M, True)
-            print("wide", case_id((M, NR, G)), "ok", flush=True)
-        out["cases"] = [list(c) for c in WIDE_CASES]
-    elif mode == "chunk":
-        assert int(os.environ["BATH_HIP_SSV_CHUNK"]) > 0
-        out["records"] = {str(m): list(check_cascade(ctx, m)) for m in CHUNK_M}
-    else:
-        raise SystemExit("mode: wide | chunk")
-    ctx.close()
-    print(json.dumps(out))
-
-
-if __name__ == "__main__":
-    _main(sys.argv[1])

@@ -243,7 +243,7 @@ def ssv_shapes():
 
 def test_ssv_tests_reach_every_shape():
     """ssv_lane_kernel<NR, G> (bath_filters.hip) and ssv_orf_kernel<NR, G> (bath_pipeline.hip): both launchers expand BATH_SSV_SHAPES and
-    nothing else instantiates the kernels; the rule of bath_profile.hip, default or under BATH_HIP_SSV_WIDE=1, selects listed shapes
+    nothing else instantiates the kernels; the rule of bath_profile.hip selects listed shapes
     only and every listed shape for some model; every shape's cost table fits a workgroup's LDS; test_ssv_shapes_gpu runs every
     shape at the smallest and the largest model that selects it.  The cascade stops at 2048 nodes, so (144, 8) and (160, 8), 2049 to
     2560 nodes, are reached by the standalone filters alone: test_ssv_standalone_every_shape runs them."""
@@ -262,9 +262,7 @@ def test_ssv_tests_reach_every_shape():
             inst = re.findall(kernel + r"<([^>]*)>", text)
             assert inst == (["N, GG"] * 2 if f == home else []), (f, kernel, inst)
     # the rule, tied to the source's text
-    for line in ('static const bool wide = [] { const char *e = std::getenv("BATH_HIP_SSV_WIDE"); return e && e[0] == \'1\'; }();',
-                 'static const int g2max = [] { const char *e = std::getenv("BATH_HIP_SSV_G2_MAX"); return e ? std::atoi(e) : 304; }();',
-                 "int G = (!wide && M > 152 && M <= g2max) ? 2 : 1;",
+    for line in ("int G = (M > 152 && M <= 304) ? 2 : 1;",
                  "while (G < 8 && M > 416 * G) G *= 2;",
                  'if (M > 416 * G) { ctx->set_error("model longer than 3328 nodes"); delete om; return BATH_EINVAL; }',
                  "int NR = ((M + G - 1) / G + 1) / 2;",
@@ -285,29 +283,26 @@ def test_ssv_tests_reach_every_shape():
     assert pipe.index("ssv_table_fits(ctx, om)") < pipe.index("BATH_SSV_SHAPES(BATH_ORF_CASE)") and sum(text.count(t.LDS_MESSAGE) for text in files.values()) == 1
     # what the rule selects
     by_shape = {}
-    for wide in (False, True):
-        for m in range(1, t.OPROFILE_MAX_NODES + 1):
-            s = t.ssv_shape(m, wide)
-            if table_bytes(*s) <= 160 * 1024:
-                by_shape.setdefault((s, "wide" if wide else None), []).append(m)
-            else:
-                assert m > t.SSV_MAX_NODES and s not in shapes       # refused by ssv_table_fits; ssv_bath_kernel<52> alone takes them
-    assert t.ssv_shape(t.SSV_MAX_NODES) in shapes and max(m for (s, w), ms in by_shape.items() for m in ms) == t.SSV_MAX_NODES
-    selected = {s for s, _ in by_shape}
+    for m in range(1, t.OPROFILE_MAX_NODES + 1):
+        s = t.ssv_shape(m)
+        if table_bytes(*s) <= 160 * 1024:
+            by_shape.setdefault(s, []).append(m)
+        else:
+            assert m > t.SSV_MAX_NODES and s not in shapes           # refused by ssv_table_fits; ssv_bath_kernel<52> alone takes them
+    assert t.ssv_shape(t.SSV_MAX_NODES) in shapes and max(m for ms in by_shape.values() for m in ms) == t.SSV_MAX_NODES
+    selected = set(by_shape)
     assert not selected - set(shapes), "the rule selects shapes that are not instantiated: %s" % sorted(selected - set(shapes))
     assert not set(shapes) - selected, "instantiated shapes that no model selects: %s" % sorted(set(shapes) - selected)
     for s in shapes:
         assert s in t.SSV_M, "SSV shape %s has no entry in test_ssv_shapes_gpu.SSV_M: no test runs it" % (s,)
-        lo, hi, switch = t.SSV_M[s]
-        assert switch == (None if (s, None) in by_shape else "wide"), s      # the default rule where it reaches the shape
-        ms = by_shape[(s, switch)]
+        lo, hi = t.SSV_M[s]
+        ms = by_shape[s]
         assert (lo, hi) == (ms[0], ms[-1]), "SSV shape %s: the tests' models %d, %d are not its smallest and largest, %d, %d" % (s, lo, hi, ms[0], ms[-1])
-    assert set(t.SSV_M) == set(shapes)
+    assert set(t.SSV_M) == set(shapes) and len(shapes) == 44
     # every entry is a test case, and the cascade leg leaves out only what lies beyond its limit
-    assert {(m, nr, g) for (nr, g), (lo, hi, sw) in t.SSV_M.items() for m in (lo, hi)} == set(t.DEFAULT_CASES) | set(t.WIDE_CASES)
+    assert {(m, nr, g) for (nr, g), (lo, hi) in t.SSV_M.items() for m in (lo, hi)} == set(t.DEFAULT_CASES)
     assert {c[1:] for c in t.DEFAULT_CASES} - {c[1:] for c in t.CASCADE_CASES} == {(144, 8), (160, 8)} and t.CASCADE_MAX_NODES == const_nodes("kCascadeMaxNodes", "BATH_WAVE_COLUMNS")
-    assert len(t.WIDE_CASES) == 22 and all(t.ssv_shape(m, True) == (nr, g) and t.ssv_shape(m) != (nr, g) for m, nr, g in t.WIDE_CASES)
-    assert sorted(t.ssv_shape(m)[1] for m in t.CHUNK_M) == [1, 2, 4, 8] and max(t.CHUNK_M) <= t.CASCADE_MAX_NODES
+    assert all(t.ssv_shape(m) == (nr, g) for m, nr, g in t.DEFAULT_CASES)
     # seams: node 1, node M, every multiple of NR below M, odd multiples between the halves, even ones between lanes
     assert t.ssv_seams(1024, 128, 4) == [(1, "first")] + [(128 * i, "half" if i % 2 else "lane") for i in range(1, 8)] + [(1024, "last")]
     assert t.ssv_seams(1, 16, 1) == [(1, "first")] and t.ssv_seams(16, 16, 1) == [(1, "first"), (16, "last")] and t.ssv_seams(17, 16, 1)[1] == (16, "half")

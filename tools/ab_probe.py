@@ -15,8 +15,7 @@ flat, offsets, planted = synth.dna_windows(1000000, 1000, seed=42, hmm=hmm)
 block = ba.SeqBlock(ctx, flat, offsets)
 pipe = ba.Pipeline(ctx, om, fs_pipe=False, ncbi_table=hmm.ct)
 for lanes in (sys.argv[2],):
-    os.environ["BATH_HIP_LANES"] = lanes.rstrip("c")
-    os.environ["BATH_HIP_LANE_PRIO"] = "0" if lanes.endswith("c") else "1"      # "2c": two parts without stream priorities
+    os.environ["BATH_HIP_LANES"] = lanes
     ts = []
     for i in range(13):
         t0 = time.perf_counter(); pipe.run(block, want_results=False); ts.append((time.perf_counter() - t0) * 1e3)
@@ -30,4 +29,6 @@ rounds = [int(a) for a in sys.argv[1:] if a.isdigit()]
 for r in range(rounds[0] if rounds else 3):
     for lanes in (os.environ.get("AB_LANES", "2,1").split(",")):
         for lib in libs:
-            subprocess.run([sys.executable, "-c", CHILD, os.path.abspath(lib), lanes], check=False)
+            rc = subprocess.run([sys.executable, "-c", CHILD, os.path.abspath(lib), lanes], check=False, timeout=300).returncode
+            if rc != 0:                              # a child that failed ends the probe: nothing more is started on that GPU
+                sys.exit("ab_probe: %s with %s parts ended with status %d" % (lib, lanes, rc))
