@@ -142,7 +142,7 @@ struct StageTiming { const char *name; float ms; int64_t launches; };
 // one kernel launch of the frameshift / domain stages, timed with HIP events on the stream it was launched on
 struct KernelSpan { const char *name; hipEvent_t a, b; double cells, bytes; };
 
-// An ORF that passed the Forward filter, as the domain-definition stage needs it (bath_domaindef.hip)
+// An ORF that passed the Forward filter, as the domain-definition stage needs it (bath_std_domains.hip)
 struct PipelineSurvivor {
   int64_t window;          // sequence index in the block
   int64_t aa_off;          // its residues in the amino-acid stream pool
@@ -291,7 +291,9 @@ struct bath_hip_seqs {
   mutable void *d_tile_desc = nullptr;     // int4 per tile: {window offset / 16, window length, window, tile index in the window}
   mutable int32_t *d_tile_first = nullptr;
   // parts of this block (consecutive windows, about equal in residues) for the pipeline's concurrent lanes: views into
-  // d_data / d_len with their own rebased offsets; built on first use
+  // d_data / d_len with their own rebased offsets; built on first use.  The stages' views on the stack (fs_gather_view, the
+  // domain stages) set is_part too: their device arrays are borrowed as well.  This struct has no destructor: only
+  // bath_hip_seqs_destroy frees, only heap blocks reach it, and of a part it frees what is the part's own (d_off).
   bool is_part = false;
   int64_t first_window = 0;
   mutable std::vector<bath_hip_seqs *> parts;

@@ -1,15 +1,19 @@
-// bath_host_threads.hpp -- how many host threads a stage may start (the domain stage's ensembles, bath_domaindef.hip; the profile builds
-// of a calibration batch, bath_calibrate.hip).
+// bath_host_threads.hpp -- how many host threads a stage may start, and run_striped, which starts them over the independent items of
+// a stage (the domain stages' ensembles, bath_domaindef.hip and bath_std_domains.hip; the profile builds of a calibration batch,
+// bath_calibrate.hip).
 // Thread count: the CPUs this process may run on (its affinity mask, not the machine's thread count: a GPU box hands a job a
 // slice of its cores), at most 64, divided by the ranks that share the node -- LOCAL_WORLD_SIZE, which torch.distributed.run
 // exports: one process per GPU, each with its own ensembles; BATH_HIP_HOST_THREADS overrides.
 #pragma once
 #include <algorithm>
+#include <atomic>
+#include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <sched.h>
 #include <thread>
+#include <vector>
 
 namespace bath {
 
@@ -53,6 +57,22 @@ inline int host_thread_count() {
     return std::min(64, std::max(1, usable / ranks));
   }();
   return cached;
+}
+
+// Host threads for n items that are independent of each other (the regions of one block).  work(first, step) handles items first,
+// first + step, ...; the threads draw single items from a shared counter, heaviest first (<weight>), so that they finish together.
+template <class F, class W>
+void run_striped(int64_t n, F &&work, W &&weight) {
+  const int T = (int)std::min<int64_t>(n, host_thread_count());
+  if (T <= 1) { work(0, 1); return; }
+  std::vector<int64_t> order((size_t)n);
+  for (int64_t i = 0; i < n; i++) order[(size_t)i] = i;
+  std::stable_sort(order.begin(), order.end(), [&](int64_t a, int64_t b) { return weight(a) > weight(b); });
+  std::atomic<int64_t> next{0};
+  std::vector<std::thread> th;
+  for (int k = 0; k < T; k++)
+    th.emplace_back([&] { for (int64_t j = next.fetch_add(1); j < n; j = next.fetch_add(1)) work(order[(size_t)j], n); });
+  for (std::thread &t : th) t.join();
 }
 
 }  // namespace bath

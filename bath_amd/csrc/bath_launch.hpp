@@ -1,6 +1,9 @@
 // bath_launch.hpp -- host-side launchers shared between bath_filters.hip and bath_pipeline.hip.
 #pragma once
+#include <cmath>
+#include <string>
 #include <utility>
+#include <vector>
 
 #include "bath_common.hpp"
 
@@ -72,6 +75,47 @@ MsvConsts msv_consts(const bath_hip_oprofile *om);
 // ---- the cascade, returning the ORFs that pass the Forward filter (bath_pipeline.hip); *d_pool stays valid until the next pipeline call on ctx
 int pipeline_filters_survivors(bath_hip_ctx *ctx, const bath_hip_oprofile *om, const bath_hip_seqs *dna, const bath_pipeline_params *prm,
                                bath_pipeline_stats *stats, std::vector<PipelineSurvivor> *out, const uint8_t **d_pool);
+
+// ---- what the two branches' domain stages share (bath_domaindef.hip: the frameshift branch, bath_std_domains.hip: the standard one)
+constexpr double kLn2 = 0.69314718055994529;
+inline double exp_logsurv(double x, double mu, double lambda) { return x < mu ? 0.0 : -lambda * (x - mu); }
+// The --cigar string of an alignment, from one code per column: state | codon length << 4 | indel label << 8 (bath_domaindef.hip)
+std::string cigar_from_columns(const uint16_t *S, int n);
+
+// pli->nres as the reference's serial loop has it when it searches strand s of window w: every earlier window's W on both strands, this
+// window's W once (top strand) or twice (bathsearch.c:1071, :1084; windows under 15 nt are skipped before the count, :1066), on top
+// of what the search counted before this block.  pli->Z = (float) nres / (float) max_length (p7_domaindef.c:1033, p7_pipeline.c:1246).
+struct RunningZ {
+  std::vector<int64_t> before;          // [nwin] residues counted before window w
+  const bath_hip_seqs *dna;
+  int strands;                          // pli->strands: a window's W is counted once per strand SEARCHED (bathsearch.c:1069-1071, :1082-1084)
+  RunningZ(const bath_hip_seqs *d, int64_t nres_before, int strands_ = BATH_STRAND_BOTH) : before((size_t)d->n), dna(d), strands(strands_) {
+    int64_t acc = nres_before;
+    const int per_window = strands == BATH_STRAND_BOTH ? 2 : 1;
+    for (int64_t w = 0; w < d->n; w++) { before[(size_t)w] = acc; acc += per_window * W(w); }
+  }
+  int64_t W(int64_t w) const {
+    const int n = dna->h_len[(size_t)w];
+    return n < 15 ? 0 : (int64_t)(n - (dna->h_context.empty() ? 0 : dna->h_context[(size_t)w]));
+  }
+  float Z(int64_t w, int strand, int max_length) const {
+    return (float)(before[(size_t)w] + ((strand && strands == BATH_STRAND_BOTH) ? 2 : 1) * W(w)) / (float)max_length;
+  }
+};
+
+// What the domain stage reads of the pipeline's option state (bath_pipeline_params + the -E argument)
+struct DomOpts {
+  int64_t nres_before; double E; int do_null2, inc_by_E, strands; uint32_t seed; double T;
+  DomOpts(const bath_pipeline_params &p, double E_report)
+      : nres_before(p.nres_before), E(E_report), do_null2(p.do_null2), inc_by_E(p.inc_by_E), strands(p.strands), seed((uint32_t)p.seed), T(p.T) {}
+  // p7_pipeline.c:1080, :1247: the early reporting test goes by inc_by_E (sic), against E with the running Z or against T
+  bool reportable(double lnP, float Zf, float score) const { return inc_by_E ? (std::exp(lnP) * (double)Zf <= E) : ((double)score >= T); }
+};
+
+// Domain definition and hit scores of the standard branch (bath_std_domains.hip) for ORFs that passed the Forward filter, their
+// residues in <d_pool>; appends to ctx->fs_domains, ctx->cigars and the context's traces
+int std_domains(bath_hip_ctx *ctx, const bath_hip_oprofile *om, const bath_hip_seqs *dna, const std::vector<PipelineSurvivor> &surv,
+                const uint8_t *d_pool, const DomOpts &opt, int64_t *n_clustered_regions);
 
 // ---- DNA regions gathered into a pool for the frameshift kernels (bath_pipeline.hip)
 struct FsWinDev {                  // one DNA window / envelope, device view

@@ -1335,7 +1335,7 @@ int fs_gather_view(bath_hip_ctx *ctx, const bath_hip_seqs *dna, std::vector<FsWi
   BATH_HIP_TRY(ctx, hipMemcpyAsync(d_desc, regs.data(), (size_t)nw * sizeof(FsWinDev), hipMemcpyHostToDevice, ctx->stream));
   hipLaunchKernelGGL(fs_window_gather_kernel, dim3((unsigned)std::max(1, std::min(nw, 65535))), dim3(256), 0, ctx->stream, dna->d_data, d_desc, nw, d_comp, b_pool.as<uint8_t>());
   BATH_HIP_TRY(ctx, hipGetLastError());
-  view->ctx = ctx; view->n = nw; view->d_data = b_pool.as<uint8_t>(); view->is_part = true;   // is_part: the destructor path must not free borrowed memory
+  view->ctx = ctx; view->n = nw; view->d_data = b_pool.as<uint8_t>(); view->is_part = true;
   view->h_off.resize((size_t)nw); view->h_len.resize((size_t)nw);
   view->maxlen = 0; view->total = 0;
   for (int i = 0; i < nw; i++) {
@@ -1595,7 +1595,6 @@ extern "C" int bath_hip_pipeline_frameshift(bath_hip_ctx *ctx, const bath_hip_op
       // for the frameshift-branch windows only (a speculative Backward of the longest windows beside Forward did not pay: DESIGN.md 7)
       st = fs3_forward_scores(ctx, om_fs3, &view, h_fsc.data());
     }
-    view.d_data = nullptr; view.d_off = nullptr; view.d_len = nullptr;     // borrowed pointers: nothing for a destructor to free
     if (st != BATH_OK) return st;
     // ---- scores -> P-values -> branch (fsw_decide_kernel); the host reads the completed records once and keeps the bookkeeping:
     // pos_past_fwd, and the ORFs of the windows that take the standard branch (:1479-1487), from the ordered ORF list

@@ -63,7 +63,7 @@ enum class Scratch : int {
   kFsRegionFwdRows,         // ... and their special-state rows
   kFsEnsembleStates,        // fs_ensemble_kernel's start states
   kFsEnsembleOut,           // ... its statuses and segments
-  // ---- envelopes: full Forward / Backward, decoding, optimal accuracy, traces (bath_frameshift.hip: fs5_envelopes_ex; bath_domaindef.hip: std_domains)
+  // ---- envelopes: full Forward / Backward, decoding, optimal accuracy, traces (bath_frameshift.hip: fs5_envelopes_ex; bath_std_domains.hip: std_domains)
   kEnvBwdMatrix,            // Backward matrices (posteriors after decoding)
   kFs5OaMatrix,             // optimal-accuracy matrices of the 5-codon model
   kEnvFwdRows,              // Forward special-state rows beside kEnvFwdMatrix (fs5_envelopes_ex, fs5_region_forward, bath_hip_forward_full)
@@ -80,7 +80,7 @@ enum class Scratch : int {
   kFs5BwdRing,              // wavefront Backward's ring; Backward runs on the side stream beside Forward
   kFs5BwdTerms,             // ... its terms
   kFs5BwdTermOffsets,       // ... and their offsets
-  // ---- standard branch's domain stage and the stand-alone filter entry points (bath_domaindef.hip, bath_filters.hip): the entry
+  // ---- standard branch's domain stage and the stand-alone filter entry points (bath_std_domains.hip, bath_filters.hip): the entry
   // points are the same stages run alone, so they name the same buffers
   kFilterOrder,             // targets by length (bath_hip_ssvfilter / msvfilter / vitfilter)
   kStdViewArrays = kFilterOrder,    // std_domains: a batch's offsets, row offsets and lengths; the filter entry points are calls of their own

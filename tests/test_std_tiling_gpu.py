@@ -1,4 +1,4 @@
-"""The standard branch's envelope kernels (bath_amd/csrc/bath_domaindef.hip) at every instantiation, matrix by matrix.
+"""The standard branch's envelope kernels (bath_amd/csrc/bath_std_domains.hip) at every instantiation, matrix by matrix.
 
 std_envelope_fill_kernel<C> (a wave per envelope, C = 1, 2, 3, 4, 6, 8, 12, 16 nodes per lane), std_envelope_fill_mw_kernel<C> (a block
 of four waves, C = 1, 2, 4) and the lane-per-envelope std_envelope_kernel each do p7_Decoding, p7_OptimalAccuracy and

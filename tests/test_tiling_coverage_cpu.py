@@ -187,11 +187,11 @@ def test_cascade_and_ssv_window_tests_reach_every_tiling():
 
 
 def test_std_envelope_tests_reach_every_instantiation():
-    """std_envelope_fill_kernel<C> and std_envelope_fill_mw_kernel<C> (bath_domaindef.hip): the instantiations are those of the two
+    """std_envelope_fill_kernel<C> and std_envelope_fill_mw_kernel<C> (bath_std_domains.hip): the instantiations are those of the two
     ladders in std_launch_fill, which the domain stage and bath_hip_std_envelopes_fill both call; test_std_tiling_gpu holds the
     smallest and the largest model of each, and its pipeline test the first model past them and the cascade's last."""
     import test_std_tiling_gpu as t
-    dom = src("bath_domaindef.hip")
+    dom = src("bath_std_domains.hip")
     helper = body(dom, "static int std_launch_fill(")
     fill = [int(x) for x in re.findall(r"\{ BATH_FILL\((\d+)\); \}", helper)]
     mw = [int(x) for x in re.findall(r"\{ BATH_FILL_MW\((\d+)\); \}", helper)]
@@ -203,7 +203,7 @@ def test_std_envelope_tests_reach_every_instantiation():
     assert dom.count("(std_envelope_fill_kernel<CC>,") == 1 and dom.count("(std_envelope_fill_mw_kernel<CC>,") == 1
     assert len(re.findall(r"[ (]std_launch_fill\(ctx, M, fill, ", dom)) == 2                   # std_domains and the stage-level entry
     for f, text in csrc_files().items():
-        assert f == "bath_domaindef.hip" or ("BATH_FILL" not in text and "std_envelope_fill" not in text), f
+        assert f == "bath_std_domains.hip" or ("BATH_FILL" not in text and "std_envelope_fill" not in text), f
     # the pick: ceil(M / 64) nodes per lane takes the first entry that fits; the block kernel ceil(M / 256); its last entry has no test
     assert "const int c = (M + 63) / 64;" in helper and "const int c4 = (M + 255) / 256;" in helper
     for c in fill[:-1]:
