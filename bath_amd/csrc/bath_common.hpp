@@ -182,7 +182,7 @@ struct bath_hip_ctx {
   // from the kernel to the host twin (a trace with more segments than the kernel keeps) (bath_hip_std_ensemble_counters)
   // ... and the regions std_ensemble_kernel walked (the fallbacks to the twin included)
   std::atomic<int64_t> std_ens_serial_fallbacks{0}, std_ens_twin_fallbacks{0}, std_ens_kernel_regions{0};
-  int fs_serial = -1;                   // envelopes' Backward after Forward on one stream instead of beside it (timing probes); -1: BATH_HIP_FS_SERIAL decides
+  int fs_serial = -1;                   // envelopes' Backward after Forward on one stream instead of beside it (timing probes; bath_fs_envelopes.hip); -1: BATH_HIP_FS_SERIAL decides
   uint64_t tabs_uid = 0;                // whose SSV score table sits in Scratch::kSsvScoreTable (bath_pipeline.hip: uploaded once per profile, not per call)
   const void *tabs_ptr = nullptr;
   uint64_t fsw_pad_uid = 0;             // whose window padding fractions sit in Scratch::kFsWindowPadding (bath_fs_windows.hip)
@@ -199,7 +199,6 @@ struct bath_hip_ctx {
     if (hipMemcpyAsync(dst, stage[slot].p, n * sizeof(T), hipMemcpyHostToDevice, s) != hipSuccess) { set_error("staging upload failed"); return BATH_EFAIL; }
     return BATH_OK;
   }
-  bath::HostBuf pinned[4];                // [0,1]: standard-branch region matrices; [2,3]: frameshift-branch ones (read by ensemble threads)
   bath::HostBuf results_pinned;           // bath_hip_pipeline_filters output: the ORF records, page-locked
   bath_orf_result *d_records = nullptr;   // ... as the last cascade pass left them on the device (bath_records.hip)
   int64_t n_records = 0;

@@ -10,7 +10,7 @@
 //   p7_pli_postDomainDef_Frameshift_BATH                (src/p7_pipeline.c:1005-1144): the hit's bit score, bias, P-value
 //
 // Division of labour.  Everything that touches a DP matrix runs on the GPU, batched over all windows / envelopes of the
-// block: the 3-codon parsers (fs3_fwd_kernel, fs_bwd_kernel<.,3,.>), the five envelope kernels of bath_frameshift.hip and
+// block: the 3-codon parsers (fs3_fwd_kernel, fs_bwd_kernel<.,3,.>), the five envelope kernels of bath_fs_envelopes.hip and
 // the optimal-accuracy traceback with the null2 score of the aligned residues (fs5_trace_kernel, a lane per envelope), so
 // the posterior and OA matrices (>1 MB per envelope) never leave the device; the posterior sums over the parsers'
 // special-state rows and the region heuristics run there too (fs_regions_kernel, a lane per window).  What remains for

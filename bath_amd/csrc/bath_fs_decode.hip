@@ -3,7 +3,7 @@
 //   fs5_decode_oa_mw_kernel <- p7_Decoding_Frameshift          generic_decoding_frameshift.c:36-156
 //                              p7_OptimalAccuracy_Frameshift   generic_optacc_frameshift.c:53-324 (the fill; the traceback is fs5_trace_kernel)
 //
-// The one-wave kernel (fs5_decode_oa_kernel, bath_frameshift.hip) gives a lane C = ceil(M / 64) consecutive nodes and walks the
+// The one-wave kernel (fs5_decode_oa_kernel, bath_fs_envelopes.hip) gives a lane C = ceil(M / 64) consecutive nodes and walks the
 // rows of its envelope one after the other: the optimal-accuracy recursion reads E(i) through J and B, so the rows are a chain.
 // At M = 1024 that is 16 nodes per lane -- five rows of {M, I, D} history, the posteriors and the next row's Forward / Backward
 // cells do not fit a lane's registers (the kernel spilled), a row took ~60 us, and a launch lasted as long as its longest

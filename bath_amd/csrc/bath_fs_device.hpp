@@ -1,4 +1,4 @@
-// bath_fs_device.hpp -- device helpers shared by the frameshift kernels (bath_frameshift.hip, bath_fs_wavefront.hip, the odds-ratio
+// bath_fs_device.hpp -- device helpers shared by the frameshift kernels (bath_frameshift.hip, bath_fs_envelopes.hip, bath_fs_wavefront.hip, the odds-ratio
 // kernels): p7_FLogsum with its table in LDS (logsum.c:105), DPP lane moves and scans, the longest-first job queue, the device profile.
 #pragma once
 #include <algorithm>
@@ -242,6 +242,20 @@ __device__ __forceinline__ int64_t fs_next_job(const FsJobs &q, int64_t n, int l
   return (int64_t)j < n ? (int64_t)q.order[j] : (int64_t)-1;
 }
 
+// ---- what the launchers of bath_frameshift.hip and bath_fs_envelopes.hip share
+// the windows of <dna> by decreasing length and <k> zeroed job counters (bath_frameshift.hip)
+int fs_schedule(bath_hip_ctx *ctx, const bath_hip_seqs *dna, int k, FsJobs *jobs);
+template <class K>
+int fs_set_shmem(bath_hip_ctx *ctx, K kernel, size_t shmem) {   // a kernel whose dynamic LDS goes past the 64 KB every kernel may have
+  if (shmem > 64 * 1024) BATH_HIP_TRY(ctx, bath::allow_max_lds((const void *)kernel));
+  return BATH_OK;
+}
+// where window i's rows start when a window of L nucleotides has L + 1 rows of <per_row> floats, packed back to back: n + 1 offsets
+inline std::vector<int64_t> fs_row_offsets(const bath_hip_seqs *dna, int64_t per_row) {
+  std::vector<int64_t> off((size_t)dna->n + 1, 0);
+  for (int64_t i = 0; i < dna->n; i++) off[(size_t)i + 1] = off[(size_t)i] + ((int64_t)dna->h_len[(size_t)i] + 1) * per_row;
+  return off;
+}
 
 // ---- row-per-lane wavefront kernels of the envelopes (bath_fs_wavefront.hip)
 int launch_fs5_fwd_wf(bath_hip_ctx *ctx, hipStream_t stream, const bath_hip_fsprofile *om, const bath_hip_seqs *dna, int exact, int c5_compat,
@@ -251,7 +265,7 @@ int launch_fs5_bwd_wf(bath_hip_ctx *ctx, hipStream_t stream, const bath_hip_fspr
                       FsJobs jobs_sweep, FsJobs jobs_x);
 
 // ---- decoding + optimal-accuracy fill with several waves per envelope, long models (bath_fs_decode.hip)
-int fs5_decode_oa_mw_shape(int M, int *nodes_per_lane);     // waves per envelope (0: the one-wave kernel of bath_frameshift.hip)
+int fs5_decode_oa_mw_shape(int M, int *nodes_per_lane);     // waves per envelope (0: the one-wave kernel of bath_fs_envelopes.hip)
 int launch_fs5_decode_oa_mw(bath_hip_ctx *ctx, hipStream_t stream, const bath_hip_fsprofile *om, const bath_hip_seqs *dna, const float *d_bsc,
                             float *d_fwd, const int64_t *d_foff, float *d_fx, const int64_t *d_xoff, const float *d_bck, const int64_t *d_boff, const float *d_bx,
                             float *d_colsum, float *d_oa, float *d_osc, float *d_ox, FsJobs jobs, int store_pp = 1, float *d_rowden = nullptr);

@@ -172,7 +172,7 @@ int fs_decide(bath_hip_ctx *ctx, const bath_hip_fsprofile *om_fs3, const bath_pi
               const float *d_fsc, const float *h_fsc, bath_fs_window *h_out);
 float flogsum_host(float a, float b);                          // p7_FLogsum with its table, on the host
 
-// ---- frameshift helpers for the pipeline (bath_frameshift.hip)
+// ---- frameshift helpers for the pipeline (bath_frameshift.hip; fs5_envelopes_ex: bath_fs_envelopes.hip)
 int fs_fork(bath_hip_ctx *ctx);   // the context's side stream waits for what the main stream holds so far
 int fs_join(bath_hip_ctx *ctx);   // ... and the main stream for the side stream
 int fs3_forward_scores(bath_hip_ctx *ctx, const bath_hip_fsprofile *om3, const bath_hip_seqs *dna, float *sc);   // table log-sum, host array out

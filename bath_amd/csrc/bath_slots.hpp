@@ -63,7 +63,7 @@ enum class Scratch : int {
   kFsRegionFwdRows,         // ... and their special-state rows
   kFsEnsembleStates,        // fs_ensemble_kernel's start states
   kFsEnsembleOut,           // ... its statuses and segments
-  // ---- envelopes: full Forward / Backward, decoding, optimal accuracy, traces (bath_frameshift.hip: fs5_envelopes_ex; bath_std_domains.hip: std_domains)
+  // ---- envelopes: full Forward / Backward, decoding, optimal accuracy, traces (bath_fs_envelopes.hip: fs5_envelopes_ex; bath_std_domains.hip: std_domains)
   kEnvBwdMatrix,            // Backward matrices (posteriors after decoding)
   kFs5OaMatrix,             // optimal-accuracy matrices of the 5-codon model
   kEnvFwdRows,              // Forward special-state rows beside kEnvFwdMatrix (fs5_envelopes_ex, fs5_region_forward, bath_hip_forward_full)
@@ -107,7 +107,7 @@ enum class Scratch : int {
 
 // Page-locked staging for small tables a launch uploads and small results it brings back: an asynchronous copy from or to here needs
 // no synchronize before the local it was built in goes away.  One role per call site; a site is refilled by its context only after
-// the stage that used it has synchronized its stream.
+// the stage that used it has synchronized its stream.  The multi-domain regions' matrices, which host threads walk, live here too.
 enum class Pinned : int {
   kFsJobOrder,              // fs_schedule's job order, up
   kChainBatchesFwd,         // chain_batches for Forward, up
@@ -115,8 +115,12 @@ enum class Pinned : int {
   kFs5BwdTermOffsets,       // wavefront Backward's term offsets, up
   kStdUploads,              // std_domains: every small upload of a stage, back to back
   kStdDownloads,            // ... and its downloads
+  kStdRegionMatrices,       // std_region_stage: the multi-domain regions' Forward matrices, written by the kernel, read by the ensemble threads
+  kStdRegionRows,           // ... their special-state rows, then their residues
   kFsWindowResult,          // regions A and B of Scratch::kFsWindowResult, down (device build); the whole product (host build)
   kFsDecideDown,            // fs_decide: the completed window records (device build) or the bias terms (host build), down
+  kFsRegionMatrices,        // fs5_region_forward: the regions' Forward matrices, written by the kernel (coherent) or copied down, read by the ensemble threads
+  kFsRegionRows,            // ... their special-state rows, then the done flags and the scores
   kFsEnsembleStates,        // fs_ensemble_kernel's start states, up
   kFsEnsembleOut,           // ... its statuses, segments and the regions' scores, down
   kStdEnsembleUpload,       // std_ensemble_kernel's upload

@@ -1098,14 +1098,14 @@ static int std_region_stage(bath_hip_ctx *ctx, const bath_hip_oprofile *om, SeqV
   BATH_HIP_TRY(ctx, b_fx.reserve((size_t)mxoff[(size_t)nm] * 4 + 64)); BATH_HIP_TRY(ctx, b_sc.reserve((size_t)nm * 8)); BATH_HIP_TRY(ctx, b_st.reserve((size_t)nm * 8));
   // Residues of region e: h_res + roff[e], one row's worth of bytes per residue row (roff = the x-row offsets / 6).
   const size_t x_bytes = ((size_t)mxoff[(size_t)nm] * 4 + 255) / 256 * 256;
-  if (dev) BATH_HIP_TRY(ctx, b_dp.reserve((size_t)mdpoff[(size_t)nm] * 4 + 64)); else BATH_HIP_TRY(ctx, ctx->pinned[0].reserve((size_t)mdpoff[(size_t)nm] * 4 + 64));
-  BATH_HIP_TRY(ctx, ctx->pinned[1].reserve(x_bytes + (size_t)mxoff[(size_t)nm] / 6 + 64));
-  float *h_dp = ctx->pinned[0].as<float>(), *h_x = ctx->pinned[1].as<float>();      // page-locked
-  const uint8_t *h_res = reinterpret_cast<const uint8_t *>(ctx->pinned[1].p) + x_bytes;
+  if (dev) BATH_HIP_TRY(ctx, b_dp.reserve((size_t)mdpoff[(size_t)nm] * 4 + 64)); else BATH_HIP_TRY(ctx, ctx->stage[Pinned::kStdRegionMatrices].reserve((size_t)mdpoff[(size_t)nm] * 4 + 64));
+  BATH_HIP_TRY(ctx, ctx->stage[Pinned::kStdRegionRows].reserve(x_bytes + (size_t)mxoff[(size_t)nm] / 6 + 64));
+  float *h_dp = ctx->stage[Pinned::kStdRegionMatrices].as<float>(), *h_x = ctx->stage[Pinned::kStdRegionRows].as<float>();      // page-locked
+  const uint8_t *h_res = reinterpret_cast<const uint8_t *>(ctx->stage[Pinned::kStdRegionRows].p) + x_bytes;
   std::vector<int64_t> roff((size_t)nm + 1, 0);
   for (int64_t e = 0; e <= nm; e++) roff[(size_t)e] = mxoff[(size_t)e] / 6;
   void *dv_dp = nullptr, *dv_x = nullptr;
-  if ((!dev && hipHostGetDevicePointer(&dv_dp, ctx->pinned[0].p, 0) != hipSuccess) || hipHostGetDevicePointer(&dv_x, ctx->pinned[1].p, 0) != hipSuccess) {
+  if ((!dev && hipHostGetDevicePointer(&dv_dp, ctx->stage[Pinned::kStdRegionMatrices].p, 0) != hipSuccess) || hipHostGetDevicePointer(&dv_x, ctx->stage[Pinned::kStdRegionRows].p, 0) != hipSuccess) {
     ctx->set_error("page-locked host memory is not mapped into the device's address space"); return BATH_EFAIL;
   }
   float *dst_x = dev ? b_fx.as<float>() : static_cast<float *>(dv_x), *dst_dp = dev ? b_dp.as<float>() : static_cast<float *>(dv_dp);

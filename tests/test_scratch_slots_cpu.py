@@ -53,6 +53,7 @@ def test_stage_is_indexed_by_name_only():
     assert occurrences(r"\bstage_upload\(\s*\d") == []
     assert len(occurrences(r"\bPinned stage_slot\b")) == 1
     assert len(occurrences(r"->stage\[Pinned::")) > 10 and len(occurrences(r"\bstage_upload\(Pinned::")) >= 4
+    assert occurrences(r"->pinned\[") == []                        # no numbered page-locked array beside it
 
 
 def test_no_number_names_a_slot():

@@ -67,7 +67,7 @@ def fs_options():
     assert [f for f, text in files.items() if "#define BATH_FS_SWITCH" in text] == ["bath_fs_device.hpp"]
     assert "BATH_TILING_SWITCH(BATH_FS_COLUMNS, Cv," in body(files["bath_fs_device.hpp"], "#define BATH_FS_SWITCH")
     assert "#define BATH_TILING_CASE(N, ...) case N: { constexpr int CC = N; __VA_ARGS__ } break;" in files["bath_tilings.hpp"]
-    for f in ("bath_frameshift.hip", "bath_fs_chain.hip", "bath_fs_odds.hip", "bath_fs5_odds.hip"):
+    for f in ("bath_frameshift.hip", "bath_fs_envelopes.hip", "bath_fs_chain.hip", "bath_fs_odds.hip", "bath_fs5_odds.hip"):
         assert "BATH_FS_SWITCH(" in files[f], f
     for f in ("bath_frameshift.hip", "bath_fs_odds.hip"):
         assert "BATH_TILING_PICK(BATH_FS_COLUMNS, " in files[f], f
