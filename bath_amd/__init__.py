@@ -376,6 +376,8 @@ ABI = {
     "bath_hmm_write_ascii": (C.c_int64, [C.POINTER(_Hmm), C.c_int, C.c_double, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_int64]),
     "bath_calib_sample_amino": (C.c_int, [C.POINTER(C.c_uint32), _f32p, C.c_int, C.c_int, _u8p]),
     "bath_gumbel_fit_complete_loc": (C.c_int, [C.POINTER(C.c_double), C.c_int, C.c_double, C.POINTER(C.c_double)]),
+    "bath_hip_calibrate_batch": (C.c_int, [_vp, C.POINTER(C.POINTER(_Hmm)), C.c_int, C.c_int, C.POINTER(C.c_uint32), _vp, C.c_int, C.c_int, C.c_int, C.c_int,
+                                           C.c_int, C.c_int, C.c_double, C.POINTER(C.c_double)]),
     "bath_hip_calib_samples_create": (C.c_int, [_vp, C.POINTER(C.c_uint32), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(_vp)]),
     "bath_hip_calib_samples_destroy": (None, [_vp]),
     "bath_hip_calibrate": (C.c_int, [_vp, C.POINTER(_Hmm), C.c_int, C.POINTER(C.c_uint32), _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
@@ -2030,3 +2032,26 @@ def calibrate(ctx, hmm, ncbi_table, state, samples=None, EmL=200, EmN=200, EvL=2
         return st.value
     cut = np.cumsum([0] + n)
     return st.value, {k: xv[cut[i]:cut[i + 1]].copy() for i, k in enumerate(("msv", "vit", "fwd", "fs3", "fs5"))}
+
+
+def calibrate_batch(ctx, hmms, ncbi_table, state, samples, EmL=200, EmN=200, EvL=200, EvN=200, EfL=100, EfN=200, Eft=0.04, want_xv=False):
+    """calibrate of several models (at most CALIB_BATCH_MAX) per kernel launch, for a run that reseeds its generator per model: every
+    model starts from <state> and reads the sets of <samples> (a CalibSamples drawn from <state>, required) and one pair of
+    frameshift sets behind them.  What len(hmms) calibrate calls from <state> in strict arithmetic give, bit for bit: evparam is
+    stored in every model.  Returns the generator's state afterwards (the state one calibrate call leaves); with want_xv also a list
+    of the five-key dicts calibrate returns, one per model.  All or nothing: a BathError names the position in the batch of the
+    model it is about, and no model is changed."""
+    hmms = list(hmms)
+    n = len(hmms)
+    st = C.c_uint32(state)
+    ptrs = (C.POINTER(_Hmm) * max(n, 1))(*[h._p for h in hmms])
+    sizes = [EmN, EvN, EfN, EfN, EfN]
+    xv = np.zeros((max(n, 1), sum(sizes)), np.float64) if want_xv else None
+    ctx._check(lib().bath_hip_calibrate_batch(ctx._h, ptrs, n, ncbi_table, C.byref(st), None if samples is None else samples._h,
+                                              EmL, EmN, EvL, EvN, EfL, EfN, Eft, None if xv is None else _f64p(xv)), "calibrate_batch")
+    for h in hmms:
+        h.evparam = np.array(h._p.contents.evparam[:], dtype=np.float32)
+    if not want_xv:
+        return st.value
+    cut = np.cumsum([0] + sizes)
+    return st.value, [{k: xv[m, cut[i]:cut[i + 1]].copy() for i, k in enumerate(("msv", "vit", "fwd", "fs3", "fs5"))} for m in range(n)]

@@ -12,6 +12,10 @@ generator runs on from model to model.  The model is written from memory (bath_a
 
 Options: -n -o --ct --mx --mxfile --popen --pextend --seed --EmL --EmN --EvL --EvN --EfL --EfN --Eft --w_beta --w_length, and
 --arith strict|odds3|odds with bathconvert's meaning (the arithmetic of the two frameshift Forward parsers; odds is the reference's).
+--batch N (1..64, default 1; an extension like --arith, no header line): N models are built, calibrated in one call with the sample
+sets scored against all of them in each kernel launch (bath_amd.calibrate_batch), then written in record order; at most N models are
+alive at once, and the output is the bytes of --batch 1.  It needs the generator reseeded per model and the strict arithmetic:
+--batch above 1 with --seed 0 or with --arith odds3|odds is refused by name.
 Refused by name, status 1: an alignment (Stockholm, or FASTA with gap characters), a nucleotide file, an empty file, a degenerate
 residue code in a query, a built-in matrix other than BLOSUM62, the alignment-only options and --cpu.
 """
@@ -48,6 +52,7 @@ OPTIONS = {
     "--w_beta": (float, None, lambda v: 0 <= v <= 1, "# window length tail mass:          %g bits\n"),
     "--w_length": (int, None, lambda v: v > 0, "# window length :                   %d\n"),
     "--arith": (str, "strict", lambda v: v in ba.ARITH_MODES, None),
+    "--batch": (int, 1, lambda v: 1 <= v <= ba.CALIB_BATCH_MAX, None),
 }
 HEADER_ORDER = ("-n", "-o", "--EmL", "--EmN", "--EvL", "--EvN", "--EfL", "--EfN", "--Eft", "--popen", "--pextend", "--mx", "--mxfile",
                 "--seed", "--w_beta", "--w_length")
@@ -100,6 +105,13 @@ def parse_options(argv):
         raise UsageError("options --mx and --mxfile are incompatible")
     if pos[0] == "-":
         raise UsageError("Can't write <hmmfile_out> to stdout: don't use '-'")
+    if opts["--batch"] > 1:
+        if opts["--seed"] == 0:
+            raise UsageError("option --batch %d with --seed 0: the generator then runs on from model to model, so every model's sample "
+                             "sets differ and there is nothing to share; use --batch 1 or a seed" % opts["--batch"])
+        if opts["--arith"] != "strict":
+            raise UsageError("option --batch %d with --arith %s: a redrawn sequence makes a model's samples depend on its scores; "
+                             "use --batch 1 or --arith strict" % (opts["--batch"], opts["--arith"]))
     return opts, used, pos[0], pos[1]
 
 
@@ -202,6 +214,10 @@ class GpuCalibrator:
         """Stores the eight E-value parameters in the model; returns the generator's state afterwards."""
         return ba.calibrate(self.ctx, hmm, self.opts["--ct"], state, self.samples, Eft=self.opts["--Eft"], arith=self.opts["--arith"], **self.E)
 
+    def calibrate_many(self, hmms, state):
+        """calibrate of every model of a batch (--batch above 1: a seed, strict arithmetic) in one call; the state one call leaves."""
+        return ba.calibrate_batch(self.ctx, hmms, self.opts["--ct"], state, self.samples, Eft=self.opts["--Eft"], **self.E)
+
     def close(self):
         if self.samples is not None:
             self.samples.close()
@@ -210,7 +226,8 @@ class GpuCalibrator:
 
 def run(argv, stdout=None, device=0, date=None, calibrator=None):
     """The whole build; returns the exit status.  calibrator: a callable (options, generator state) -> an object with
-    calibrate(hmm, state) and close(); None: GpuCalibrator on <device>."""
+    calibrate(hmm, state) and close(), and for --batch above 1 calibrate_many(hmms, state), which calibrates every model from <state>
+    (without it the batch goes through calibrate, model by model); None: GpuCalibrator on <device>."""
     t0, c0 = time.time(), os.times()
     ofh = None
     try:
@@ -241,14 +258,27 @@ def run(argv, stdout=None, device=0, date=None, calibrator=None):
     try:
         fh = open(tmp_out, "wb")                                         # models go out one by one: a proteome's text is never held whole
         cal = calibrator(opts, state) if calibrator is not None else GpuCalibrator(opts, state, device)
-        for i, (name, desc, seq) in enumerate(queries):
-            name = opts["-n"] or name
-            hmm = build_model(score, name, seq, opts)
-            after = cal.calibrate(hmm, state)
-            if not seed:                                                 # p7_builder.c:131: no reseeding, the generator runs on
-                state = after
-            fh.write(ba.hmm_text(hmm, date=date or time.strftime("%a %b %e %H:%M:%S %Y")))
-            stdout.write(result_line(i + 1, name, len(seq), hmm.M, opts["--ct"], ba.hmm_relent(hmm), desc))
+        nb = opts["--batch"]
+        for i0 in range(0, len(queries), nb):                            # --batch 1: a model at a time, call for call as without the option
+            part = queries[i0:i0 + nb]
+            hmms = [build_model(score, opts["-n"] or name, seq, opts) for name, _, seq in part]
+            if nb == 1:
+                after = cal.calibrate(hmms[0], state)
+                if not seed:                                             # p7_builder.c:131: no reseeding, the generator runs on
+                    state = after
+            else:                                                        # a seed: every model starts from <state> (parse_options)
+                try:
+                    if hasattr(cal, "calibrate_many"):
+                        cal.calibrate_many(hmms, state)
+                    else:
+                        for hmm in hmms:
+                            cal.calibrate(hmm, state)
+                except ba.BathError as e:
+                    raise ba.BathError("records %d to %d of %s, calibrated as one batch: %s" % (i0 + 1, i0 + len(part), path_in, e))
+            for j, (hmm, (name, desc, seq)) in enumerate(zip(hmms, part)):
+                fh.write(ba.hmm_text(hmm, date=date or time.strftime("%a %b %e %H:%M:%S %Y")))
+                stdout.write(result_line(i0 + j + 1, opts["-n"] or name, len(seq), hmm.M, opts["--ct"], ba.hmm_relent(hmm), desc))
+            del hmms                                                     # at most a batch's models are alive at once
         fh.close()
         os.replace(tmp_out, path_out)                                    # the output appears only when it is whole
     except (ba.BathError, OSError) as e:

@@ -14,7 +14,8 @@
 // instantiation of the regions' chain kernel).  The sampler is a strictly serial consumer of one random-number stream carried from
 // model to model (2 x 200 x 200 steps per model) and its output is 60 KB per parser: host code.  So are the fit (200 numbers) and MAXL.
 // bath_hip_calibrate_fs_batch fits several models with the windows of all of them in each parser launch (the batch kernels of
-// bath_fs_chain.hip); it is told where it stands, behind the single-model calls.
+// bath_fs_chain.hip); it is told where it stands, behind the single-model calls.  bath_hip_calibrate_batch, at the very end, is
+// bath_hip_calibrate for several models that start from one generator state: every sample set scored against all of them per launch.
 //
 // easel is not part of the reference tree, so esl_rsq_xfIID, esl_rnd_FChoose, esl_rnd_Roll, esl_stats_DMean, esl_gumbel_FitComplete
 // and esl_gumbel_invcdf are restated from their published behaviour, as bath_ensemble.hip restates the generator.  The reference
@@ -27,6 +28,7 @@
 #include <cmath>
 #include <cstdint>
 #include <cstring>
+#include <functional>
 #include <string>
 #include <thread>
 #include <vector>
@@ -405,33 +407,19 @@ struct CalibBatch {
 };
 }  // namespace
 
-extern "C" int bath_hip_calibrate_fs_batch(bath_hip_ctx *ctx, const bath_hmm *const *hmms, const int *ncbi_tables, int n_models,
-                                           uint32_t *rng_state, int L, int N, double tailp,
-                                           double *tau3, double *tau5, double *xv3, double *xv5) {
-  if (!ctx) return BATH_EINVAL;
-  // ---- 1. everything that can be refused, before anything is drawn or written
-  if (n_models < 1 || n_models > BATH_CALIB_BATCH_MAX) { ctx->set_error("calibrate_fs_batch: a batch holds 1 to " + std::to_string(BATH_CALIB_BATCH_MAX) + " models (this one " + std::to_string(n_models) + ")"); return BATH_EINVAL; }
-  if (!hmms || !ncbi_tables || !rng_state || !tau3 || !tau5 || L < 2 || N < 2 || !(tailp > 0. && tailp < 1.)) { ctx->set_error("calibrate_fs_batch: needs models, their tables, a generator state, L >= 2, N >= 2 and 0 < tailp < 1"); return BATH_EINVAL; }
-  std::vector<uint8_t> basic((size_t)n_models * 64);
-  for (int k = 0; k < n_models; k++) {
-    const std::string who = "calibrate_fs_batch: model at position " + std::to_string(k) + " of the batch: ";
-    if (!hmms[k] || hmms[k]->M < 1) { ctx->set_error(who + "no model"); return BATH_EINVAL; }
-    if (hmms[k]->M > kFsMaxNodes) { ctx->set_error(who + "frameshift kernels support models up to " + std::to_string(kFsMaxNodes) + " nodes (this one has " + std::to_string(hmms[k]->M) + ")"); return BATH_EINVAL; }
-    if (bath_gencode_basic(ncbi_tables[k], &basic[(size_t)k * 64]) != BATH_OK) { ctx->set_error(who + "unknown NCBI translation table " + std::to_string(ncbi_tables[k])); return BATH_EINVAL; }
-  }
-  BATH_HIP_TRY(ctx, hipSetDevice(ctx->device));
-  ctx->spans_reset();                                      // bath_hip_kernel_times afterwards: the batch's launches
-  // ---- 2. the samples: [model][3-codon set, 5-codon set][N][3L]
-  const int sets = 2 * n_models;
-  const int64_t nwin = (int64_t)sets * N, L3 = 3 * (int64_t)L;
-  std::vector<uint8_t> dna((size_t)nwin * L3);
-  uint32_t state = *rng_state;
-  for (int k = 0; k < n_models; k++) {                     // (model by model only to name the one whose table fails)
-    if (bath_calib_sample_batch(&state, kAminoBg, ncbi_tables + k, 1, L, N, dna.data() + (size_t)k * 2 * N * L3) != BATH_OK) {
-      ctx->set_error("calibrate_fs_batch: model at position " + std::to_string(k) + " of the batch: translation table " + std::to_string(ncbi_tables[k]) + " has no codon for a background residue");
-      return BATH_EINVAL;
-    }
-  }
+// Stages 3 to 5 of a batch, for its two callers: the profiles, the uploads, the grouped launches, the copy and the fits.  <dna> holds
+// <n_pairs> pairs of sample sets, [pair][3-codon set, 5-codon set][N][3L]; model k reads pair pair_of[k] and its fits are anchored
+// with lambda[k].  bath_hip_calibrate_fs_batch: a pair per model (the generator is carried) and the model's float lambda;
+// bath_hip_calibrate_batch: every model on the one pair (the generator is reseeded per model) and p7_Lambda's double.  <who> opens
+// the messages; <basic>: 64 codes per model.  Every model has a job counter of its own, whoever shares its windows.  <queue_more>,
+// if any, is called once the launches are queued and joined, before the one synchronize (the caller's own copies).  Writes its
+// results only when every fit has succeeded.
+static int calibrate_fs_sets(bath_hip_ctx *ctx, const char *who_call, const bath_hmm *const *hmms, const uint8_t *basic, int n_models,
+                             const uint8_t *dna, int n_pairs, const int *pair_of, const double *lambda, int L, int N, double tailp,
+                             double *tau3, double *tau5, double *xv3, double *xv5, const std::function<int()> *queue_more) {
+  const std::string call = who_call;
+  const int sets = 2 * n_models;                           // (model, parser): a profile, a job counter, N scores
+  const int64_t nwin = (int64_t)2 * n_pairs * N, nsc = (int64_t)sets * N, L3 = 3 * (int64_t)L;
   // ---- 3. the 2 x n_models profiles: built on host threads (independent of each other, host code), uploaded by this one
   CalibBatch B;
   B.gm.assign((size_t)sets, nullptr); B.om.assign((size_t)sets, nullptr);
@@ -450,7 +438,7 @@ extern "C" int bath_hip_calibrate_fs_batch(bath_hip_ctx *ctx, const bath_hmm *co
       for (std::thread &t : th) t.join();
     }
     for (int s = 0; s < sets; s++)
-      if (status[(size_t)s] != BATH_OK) { ctx->set_error("calibrate_fs_batch: model at position " + std::to_string(s / 2) + " of the batch: the profile cannot be configured"); return status[(size_t)s]; }
+      if (status[(size_t)s] != BATH_OK) { ctx->set_error(call + ": model at position " + std::to_string(s / 2) + " of the batch: the profile cannot be configured"); return status[(size_t)s]; }
   }
   for (int s = 0; s < sets; s++) {
     int st = bath_hip_fsprofile_convert(ctx, B.gm[(size_t)s], &B.om[(size_t)s]);
@@ -461,17 +449,17 @@ extern "C" int bath_hip_calibrate_fs_batch(bath_hip_ctx *ctx, const bath_hmm *co
   {
     std::vector<int64_t> off((size_t)nwin + 1);
     for (int64_t i = 0; i <= nwin; i++) off[(size_t)i] = i * L3;
-    const int st = bath_hip_seqs_create(ctx, dna.data(), off.data(), nwin, &B.sq);
+    const int st = bath_hip_seqs_create(ctx, dna, off.data(), nwin, &B.sq);
     if (st != BATH_OK) return st;
   }
-  // ---- 4. the grouped launches.  One buffer: a job counter per set, the job order (every window of a set has the set's length:
-  // the identity), the descriptors -- the 3-codon sets' by tiling, then the 5-codon sets' by tiling -- and behind them the scores
+  // ---- 4. the grouped launches.  One buffer: a job counter per (model, parser), the job order (every window of a set has the set's
+  // length: the identity), the descriptors -- the 3-codon parser's by tiling, then the 5-codon parser's by tiling -- and behind them the scores
   std::vector<int> by_tiling((size_t)n_models);
   for (int k = 0; k < n_models; k++) by_tiling[(size_t)k] = k;
   auto tiling = [&](int k) { return BATH_TILING_PICK(BATH_FS_COLUMNS, hmms[k]->M); };
   std::stable_sort(by_tiling.begin(), by_tiling.end(), [&](int a, int b) { return tiling(a) < tiling(b); });
   const size_t o_order = (size_t)sets * sizeof(unsigned), o_desc = (o_order + (size_t)N * sizeof(int32_t) + 15) / 16 * 16;
-  const size_t o_sc = o_desc + (size_t)sets * sizeof(FsBatchModel), total = o_sc + (size_t)nwin * sizeof(float);
+  const size_t o_sc = o_desc + (size_t)sets * sizeof(FsBatchModel), total = o_sc + (size_t)nsc * sizeof(float);
   DevBuf &b_work = ctx->scratch[Scratch::kCalibBatchWork];
   BATH_HIP_TRY(ctx, b_work.reserve(total));
   char *d_base = b_work.as<char>();
@@ -482,9 +470,10 @@ extern "C" int bath_hip_calibrate_fs_batch(bath_hip_ctx *ctx, const bath_hmm *co
   for (int pass = 0; pass < 2; pass++)
     for (int j = 0; j < n_models; j++) {
       const int k = by_tiling[(size_t)j], s = 2 * k + pass;
+      const int64_t w0 = ((int64_t)2 * pair_of[k] + pass) * N;               // the first window of the set this parser reads
       const bath_hip_fsprofile *om = B.om[(size_t)s];
       FsBatchModel m{};
-      m.dna = SeqView{all.data, all.off + (int64_t)s * N, all.len + (int64_t)s * N, N, nullptr};
+      m.dna = SeqView{all.data, all.off + w0, all.len + w0, N, nullptr};
       m.p = FsDev{om->M, om->pitch, om->maxcodons, om->d_rsc, om->d_tf, om->d_tb, om->d_logsum};
       m.loop_tab = om->d_loop[0]; m.move_tab = om->d_move[0];
       m.sc = d_sc + (int64_t)s * N;
@@ -515,23 +504,24 @@ extern "C" int bath_hip_calibrate_fs_batch(bath_hip_ctx *ctx, const bath_hmm *co
   }
   const int stj = fs_join(ctx);                            // (also after a refused launch: the context's streams stay in step)
   // ---- 5. one synchronize, then the fits
-  std::vector<float> sc((size_t)nwin);
-  if (st == BATH_OK && stj == BATH_OK && hipMemcpyAsync(sc.data(), d_sc, (size_t)nwin * sizeof(float), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) { ctx->set_error("calibrate_fs_batch: cannot copy the scores"); st = BATH_EFAIL; }
+  std::vector<float> sc((size_t)nsc);
+  if (st == BATH_OK && stj == BATH_OK && hipMemcpyAsync(sc.data(), d_sc, (size_t)nsc * sizeof(float), hipMemcpyDeviceToHost, ctx->stream) != hipSuccess) { ctx->set_error(call + ": cannot copy the scores"); st = BATH_EFAIL; }
+  if (st == BATH_OK && stj == BATH_OK && queue_more) st = (*queue_more)();
   BATH_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
   if (st != BATH_OK) return st;
   if (stj != BATH_OK) return stj;
   const float nullsc = bath_bg_fs_nullone(L);
-  std::vector<double> xv((size_t)nwin), taus((size_t)sets);
+  std::vector<double> xv((size_t)nsc), taus((size_t)sets);
   for (int s = 0; s < sets; s++) {
     const int cl = s % 2 == 0 ? 3 : 5;
     double *x = &xv[(size_t)s * N];
     for (int i = 0; i < N; i++) {
       const float v = sc[(size_t)s * N + i];
-      if (!std::isfinite(v)) { ctx->set_error("calibrate_fs_batch: model at position " + std::to_string(s / 2) + " of the batch: a sampled sequence has no path through the " + std::to_string(cl) + "-codon model (L too short)"); return BATH_ERANGE; }
+      if (!std::isfinite(v)) { ctx->set_error(call + ": model at position " + std::to_string(s / 2) + " of the batch: a sampled sequence has no path through the " + std::to_string(cl) + "-codon model (L too short)"); return BATH_ERANGE; }
       x[i] = (v - nullsc) / 0.69314718055994529;             // evalues.c:649: float difference, double quotient
     }
-    if ((st = bath_calib_tau(x, N, (double)hmms[s / 2]->evparam[5], tailp, &taus[(size_t)s])) != BATH_OK) {
-      ctx->set_error("calibrate_fs_batch: model at position " + std::to_string(s / 2) + " of the batch: the Gumbel fit did not converge");
+    if ((st = bath_calib_tau(x, N, lambda[s / 2], tailp, &taus[(size_t)s])) != BATH_OK) {
+      ctx->set_error(call + ": model at position " + std::to_string(s / 2) + " of the batch: the Gumbel fit did not converge");
       return st;
     }
   }
@@ -540,6 +530,43 @@ extern "C" int bath_hip_calibrate_fs_batch(bath_hip_ctx *ctx, const bath_hmm *co
     if (xv3) std::copy(&xv[(size_t)2 * k * N], &xv[(size_t)(2 * k + 1) * N], xv3 + (size_t)k * N);
     if (xv5) std::copy(&xv[(size_t)(2 * k + 1) * N], &xv[(size_t)(2 * k + 2) * N], xv5 + (size_t)k * N);
   }
+  return BATH_OK;
+}
+
+extern "C" int bath_hip_calibrate_fs_batch(bath_hip_ctx *ctx, const bath_hmm *const *hmms, const int *ncbi_tables, int n_models,
+                                           uint32_t *rng_state, int L, int N, double tailp,
+                                           double *tau3, double *tau5, double *xv3, double *xv5) {
+  if (!ctx) return BATH_EINVAL;
+  // ---- 1. everything that can be refused, before anything is drawn or written
+  if (n_models < 1 || n_models > BATH_CALIB_BATCH_MAX) { ctx->set_error("calibrate_fs_batch: a batch holds 1 to " + std::to_string(BATH_CALIB_BATCH_MAX) + " models (this one " + std::to_string(n_models) + ")"); return BATH_EINVAL; }
+  if (!hmms || !ncbi_tables || !rng_state || !tau3 || !tau5 || L < 2 || N < 2 || !(tailp > 0. && tailp < 1.)) { ctx->set_error("calibrate_fs_batch: needs models, their tables, a generator state, L >= 2, N >= 2 and 0 < tailp < 1"); return BATH_EINVAL; }
+  std::vector<uint8_t> basic((size_t)n_models * 64);
+  for (int k = 0; k < n_models; k++) {
+    const std::string who = "calibrate_fs_batch: model at position " + std::to_string(k) + " of the batch: ";
+    if (!hmms[k] || hmms[k]->M < 1) { ctx->set_error(who + "no model"); return BATH_EINVAL; }
+    if (hmms[k]->M > kFsMaxNodes) { ctx->set_error(who + "frameshift kernels support models up to " + std::to_string(kFsMaxNodes) + " nodes (this one has " + std::to_string(hmms[k]->M) + ")"); return BATH_EINVAL; }
+    if (bath_gencode_basic(ncbi_tables[k], &basic[(size_t)k * 64]) != BATH_OK) { ctx->set_error(who + "unknown NCBI translation table " + std::to_string(ncbi_tables[k])); return BATH_EINVAL; }
+  }
+  BATH_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  ctx->spans_reset();                                      // bath_hip_kernel_times afterwards: the batch's launches
+  // ---- 2. the samples: [model][3-codon set, 5-codon set][N][3L]
+  const int sets = 2 * n_models;
+  const int64_t nwin = (int64_t)sets * N, L3 = 3 * (int64_t)L;
+  std::vector<uint8_t> dna((size_t)nwin * L3);
+  uint32_t state = *rng_state;
+  for (int k = 0; k < n_models; k++) {                     // (model by model only to name the one whose table fails)
+    if (bath_calib_sample_batch(&state, kAminoBg, ncbi_tables + k, 1, L, N, dna.data() + (size_t)k * 2 * N * L3) != BATH_OK) {
+      ctx->set_error("calibrate_fs_batch: model at position " + std::to_string(k) + " of the batch: translation table " + std::to_string(ncbi_tables[k]) + " has no codon for a background residue");
+      return BATH_EINVAL;
+    }
+  }
+  // ---- 3. to 5.: a pair of sets per model, the slope the model's file gives (bathconvert.c:128-162)
+  std::vector<int> pair_of((size_t)n_models);
+  std::vector<double> lambda((size_t)n_models);
+  for (int k = 0; k < n_models; k++) { pair_of[(size_t)k] = k; lambda[(size_t)k] = (double)hmms[k]->evparam[5]; }   // p7_FLAMBDA
+  const int st = calibrate_fs_sets(ctx, "calibrate_fs_batch", hmms, basic.data(), n_models, dna.data(), n_models, pair_of.data(), lambda.data(), L, N, tailp,
+                                   tau3, tau5, xv3, xv5, nullptr);
+  if (st != BATH_OK) return st;
   *rng_state = state;
   return BATH_OK;
 }
@@ -721,6 +748,163 @@ extern "C" int bath_hip_calibrate(bath_hip_ctx *ctx, bath_hmm *hmm, int ncbi_tab
   st = calibrate_fs_any(ctx, hmm, ncbi_table, &state, EfL, EfN, Eft, &tau3, &tau5, xv3, xv5, arith, redrawn, true, lambda);
   if (st != BATH_OK) { std::memcpy(hmm->evparam, ev, sizeof ev); return st; }
   hmm->evparam[6] = (float)tau3; hmm->evparam[7] = (float)tau5;
+  *rng_state = state;
+  return BATH_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// Several models per call, for a builder that reseeds its generator for every model (p7_builder.c:130-131, evalues.c:94-95): every
+// model starts from the same state, so all of them read the three resident standard sets and, with one translation table for the
+// run, the same two frameshift sets behind them -- five shared sample sets against n_models models.  (bath_hip_calibrate_fs_batch
+// is the other rule: the generator carried from model to model, a pair of frameshift sets each.)  Per standard filter and per tiling
+// present one launch scores the set against the models of that tiling (bath_calib_batch.hip: the wave kernels' own text, a block's
+// model at blockIdx.y; the full MSV kernel for every target, which scores what SSV and its classification decide alone, and the
+// wave kernel's Viterbi, which is the lane kernel's int16 recurrence); the two frameshift parsers follow as calibrate_fs_sets
+// queues them, the standard scores come back behind them, one synchronize, then the fits.  Defined by what it equals: n_models
+// calls of bath_hip_calibrate in strict arithmetic, each from the same state, bit for bit.  All or nothing.
+// ---------------------------------------------------------------------------------------------------------------------------
+namespace {
+struct StdBatch {
+  std::vector<bath_hip_oprofile *> om;
+  ~StdBatch() { for (bath_hip_oprofile *o : om) if (o) bath_hip_oprofile_destroy(o); }
+};
+}  // namespace
+
+extern "C" int bath_hip_calibrate_batch(bath_hip_ctx *ctx, bath_hmm *const *hmms, int n_models, int ncbi_table, uint32_t *rng_state,
+                                        bath_hip_calib_samples *samples, int EmL, int EmN, int EvL, int EvN, int EfL, int EfN, double Eft, double *xv) {
+  if (!ctx) return BATH_EINVAL;
+  // ---- 1. everything that can be refused, before anything is drawn, launched or written
+  if (n_models < 1 || n_models > BATH_CALIB_BATCH_MAX) { ctx->set_error("calibrate_batch: a batch holds 1 to " + std::to_string(BATH_CALIB_BATCH_MAX) + " models (this one " + std::to_string(n_models) + ")"); return BATH_EINVAL; }
+  if (!hmms || !rng_state || !(Eft > 0. && Eft < 1.)) { ctx->set_error("calibrate_batch: needs models, a generator state and 0 < Eft < 1"); return BATH_EINVAL; }
+  for (int k = 0; k < n_models; k++) {
+    const std::string who = "calibrate_batch: model at position " + std::to_string(k) + " of the batch: ";
+    if (!hmms[k] || hmms[k]->M < 1) { ctx->set_error(who + "no model"); return BATH_EINVAL; }
+    if (hmms[k]->M > kFsMaxNodes) { ctx->set_error(who + "frameshift kernels support models up to " + std::to_string(kFsMaxNodes) + " nodes (this one has " + std::to_string(hmms[k]->M) + ")"); return BATH_EINVAL; }
+  }
+  std::vector<uint8_t> basic((size_t)n_models * 64);
+  if (bath_gencode_basic(ncbi_table, basic.data()) != BATH_OK) { ctx->set_error("calibrate_batch: unknown NCBI translation table " + std::to_string(ncbi_table)); return BATH_EINVAL; }
+  for (int k = 1; k < n_models; k++) std::memcpy(&basic[(size_t)k * 64], basic.data(), 64);
+  const int L[3] = {EmL, EvL, EfL}, N[3] = {EmN, EvN, EfN};
+  bath_hip_calib_samples *S = samples;
+  if (!S) { ctx->set_error("calibrate_batch: needs the resident sample sets (bath_hip_calib_samples_create)"); return BATH_EINVAL; }
+  if (S->ctx != ctx || std::memcmp(S->L, L, sizeof L) || std::memcmp(S->N, N, sizeof N) || S->state_before != *rng_state) {
+    ctx->set_error("calibrate: the resident sample sets were drawn for another context, other lengths or counts, or from another generator state");
+    return BATH_EINVAL;
+  }
+  if (EfL < 2) { ctx->set_error("calibrate_batch: the frameshift fits need EfL >= 2"); return BATH_EINVAL; }
+  BATH_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  ctx->spans_reset();                                      // bath_hip_kernel_times afterwards: this batch's launches
+  // ---- 2. the two frameshift sets every model reads: drawn once, behind the standard sets
+  uint32_t state = S->state_after;
+  const size_t fs_set = (size_t)EfN * 3 * EfL;
+  std::vector<uint8_t> dna(2 * fs_set);
+  for (int pass = 0; pass < 2; pass++)
+    if (bath_calib_sample(&state, kAminoBg, ncbi_table, EfL, EfN, dna.data() + (size_t)pass * fs_set) != BATH_OK) {
+      ctx->set_error("calibrate_batch: translation table " + std::to_string(ncbi_table) + " has no codon for a background residue");
+      return BATH_EINVAL;
+    }
+  // ---- 3. the standard profiles, their length tables, the models by tiling (Forward: and by where its tables lie)
+  StdBatch B;
+  B.om.assign((size_t)n_models, nullptr);
+  const int maxL = std::max(L[0], std::max(L[1], L[2]));
+  for (int k = 0; k < n_models; k++) {
+    bath_profile *gm = nullptr;
+    int st = bath_profile_config(hmms[k], EvL, &gm);       // evalues.c:109 (the length does not matter: every fit sets its own)
+    if (st == BATH_OK) st = bath_hip_oprofile_convert(ctx, gm, &B.om[(size_t)k]);
+    if (gm) bath_profile_destroy(gm);
+    if (st == BATH_OK) st = B.om[(size_t)k]->ensure_len_tables(maxL);
+    if (st != BATH_OK) return st;
+  }
+  auto tiling = [&](int k) { return BATH_TILING_PICK(BATH_WAVE_COLUMNS, hmms[k]->M); };
+  auto key = [&](int k) { return 2 * tiling(k) + (fwd_wave_global_tables(B.om[(size_t)k]) ? 1 : 0); };
+  std::vector<int> by_tiling((size_t)n_models);
+  for (int k = 0; k < n_models; k++) by_tiling[(size_t)k] = k;
+  std::stable_sort(by_tiling.begin(), by_tiling.end(), [&](int a, int b) { return key(a) < key(b); });
+  // ---- 4. one buffer: the descriptors in launch order, behind them every model's scores and statuses, set after set
+  const int64_t per_model = (int64_t)N[0] + N[1] + N[2], nres = per_model * n_models;
+  const size_t desc = std_batch_model_bytes(), o_sc = ((size_t)n_models * desc + 15) / 16 * 16, o_st = o_sc + (size_t)nres * sizeof(float);
+  DevBuf &b_work = ctx->scratch[Scratch::kCalibStdBatchWork];
+  BATH_HIP_TRY(ctx, b_work.reserve(o_st + (size_t)nres * sizeof(int32_t)));
+  char *d_base = b_work.as<char>();
+  float *d_sc = reinterpret_cast<float *>(d_base + o_sc);
+  int32_t *d_st = reinterpret_cast<int32_t *>(d_base + o_st);
+  std::vector<char> up((size_t)n_models * desc, 0);
+  for (int j = 0; j < n_models; j++) {
+    const int k = by_tiling[(size_t)j];
+    float *sc3[3]; int32_t *st3[3];
+    int64_t at = (int64_t)k * per_model;
+    for (int s = 0; s < 3; s++) { sc3[s] = d_sc + at; st3[s] = d_st + at; at += N[s]; }
+    std_batch_model_fill(up.data() + (size_t)j * desc, B.om[(size_t)k], sc3, st3);
+  }
+  int st = ctx->stage_upload(Pinned::kCalibStdBatchUpload, d_base, up.data(), up.size(), ctx->stream);
+  static const char *const kKernel[3] = {"msv_wave_batch_kernel", "vit_wave_batch_kernel", "fwd_wave_batch_kernel"};
+  for (int s = 0; s < 3 && st == BATH_OK; s++)
+    for (int j0 = 0; j0 < n_models && st == BATH_OK;) {
+      const int k0 = by_tiling[(size_t)j0], Cv = tiling(k0);
+      const bool gt = fwd_wave_global_tables(B.om[(size_t)k0]);
+      int j1 = j0, Mmax = 0;
+      double nodes = 0.;
+      for (; j1 < n_models && tiling(by_tiling[(size_t)j1]) == Cv && (s < 2 || fwd_wave_global_tables(B.om[(size_t)by_tiling[(size_t)j1]]) == gt); j1++) {
+        const int M = hmms[by_tiling[(size_t)j1]]->M; Mmax = std::max(Mmax, M); nodes += M;
+      }
+      const int sp = ctx->span_begin(kKernel[s], ctx->stream, nodes * L[s] * N[s], 0.);
+      st = launch_std_wave_batch(ctx, ctx->stream, s, d_base + (size_t)j0 * desc, j1 - j0, Mmax, Cv, gt, S->sq[s]->view());
+      ctx->span_end(sp, ctx->stream);
+      j0 = j1;
+    }
+  if (st != BATH_OK) { (void)hipStreamSynchronize(ctx->stream); return st; }
+  // ---- 5. the frameshift taus of the batch: every model on the one pair of sets, anchored with p7_Lambda's double as
+  // bath_hip_calibrate hands it on (evalues.c:142-143); the standard results come back behind its launches, one synchronize
+  std::vector<float> sc((size_t)nres);
+  std::vector<int32_t> status((size_t)nres);
+  const std::function<int()> queue_std = [&]() -> int {
+    BATH_HIP_TRY(ctx, hipMemcpyAsync(sc.data(), d_sc, (size_t)nres * sizeof(float), hipMemcpyDeviceToHost, ctx->stream));
+    BATH_HIP_TRY(ctx, hipMemcpyAsync(status.data(), d_st, (size_t)nres * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    return BATH_OK;
+  };
+  std::vector<int> pair_of((size_t)n_models, 0);
+  std::vector<double> lambda((size_t)n_models), tau3((size_t)n_models), tau5((size_t)n_models), x3, x5;
+  for (int k = 0; k < n_models; k++) lambda[(size_t)k] = bath_hmm_lambda(hmms[k]);        // p7_Lambda
+  if (xv) { x3.resize((size_t)n_models * EfN); x5.resize((size_t)n_models * EfN); }
+  st = calibrate_fs_sets(ctx, "calibrate_batch", hmms, basic.data(), n_models, dna.data(), 1, pair_of.data(), lambda.data(), EfL, EfN, Eft,
+                         tau3.data(), tau5.data(), xv ? x3.data() : nullptr, xv ? x5.data() : nullptr, &queue_std);
+  if (st != BATH_OK) return st;
+  // ---- 6. the standard fits (calibrate_std's, per model), into locals: nothing is written before the last has succeeded
+  static const char *const kWhat[3] = {"msv mu", "vit mu", "fwd tau"};
+  std::vector<double> mu((size_t)n_models * 3), x((size_t)nres);
+  for (int k = 0; k < n_models; k++) {
+    const bath_hip_oprofile *om = B.om[(size_t)k];
+    const std::string who = "calibrate_batch: model at position " + std::to_string(k) + " of the batch: ";
+    const float maxsc[2] = {(float)((255 - om->base_b) / om->scale_b),            // evalues.c:305
+                            (float)((32767.0 - om->base_w) / om->scale_w)};        // evalues.c:374
+    int64_t at = (int64_t)k * per_model;
+    for (int s = 0; s < 3; at += N[s], s++) {
+      const float nullsc = om->lt.h_nullsc[(size_t)L[s]];                          // p7_bg_SetLength(bg, L) + p7_bg_NullOne
+      double *xs = &x[(size_t)at];
+      for (int i = 0; i < N[s]; i++) {
+        float v = sc[(size_t)(at + i)];
+        const int32_t code = status[(size_t)(at + i)];
+        if (code == BATH_ERANGE && s < 2) v = maxsc[s];
+        else if (code != BATH_OK) { ctx->set_error(who + "failed to determine " + kWhat[s] + ": a sampled sequence's filter returned status " + std::to_string(code)); return code == BATH_ERANGE ? BATH_ERANGE : BATH_EFAIL; }
+        xs[i] = (v - nullsc) / 0.69314718055994529;                                 // float difference, double quotient
+      }
+      st = s < 2 ? bath_gumbel_fit_complete_loc(xs, N[s], lambda[(size_t)k], &mu[(size_t)k * 3 + s]) : bath_calib_tau(xs, N[s], lambda[(size_t)k], Eft, &mu[(size_t)k * 3 + s]);
+      if (st != BATH_OK) { ctx->set_error(who + "failed to determine " + kWhat[s] + ": the fit did not converge"); return st; }
+    }
+  }
+  // ---- 7. every fit of every model is there: the parameters, the bit scores, the state one bath_hip_calibrate call leaves
+  for (int k = 0; k < n_models; k++) {
+    float *ev = hmms[k]->evparam;
+    ev[1] = ev[3] = ev[5] = (float)lambda[(size_t)k];                               // evalues.c:148-153
+    ev[0] = (float)mu[(size_t)k * 3]; ev[2] = (float)mu[(size_t)k * 3 + 1]; ev[4] = (float)mu[(size_t)k * 3 + 2];
+    ev[6] = (float)tau3[(size_t)k]; ev[7] = (float)tau5[(size_t)k];
+    if (xv) {
+      double *out = xv + (size_t)k * (size_t)(per_model + 2 * (int64_t)EfN);
+      std::copy(&x[(size_t)k * per_model], &x[(size_t)(k + 1) * per_model], out);
+      std::copy(&x3[(size_t)k * EfN], &x3[(size_t)(k + 1) * EfN], out + per_model);
+      std::copy(&x5[(size_t)k * EfN], &x5[(size_t)(k + 1) * EfN], out + per_model + EfN);
+    }
+  }
   *rng_state = state;
   return BATH_OK;
 }

@@ -94,85 +94,23 @@ __global__ void ssv_classify_kernel(int64_t n, const int32_t *__restrict__ len, 
 
 // ============================================================================================
 // Full MSV with the J state, wave per target (only for targets SSV could not decide).
-// Lane l owns nodes l*C+1 .. l*C+C.
+// Lane l owns nodes l*C+1 .. l*C+C.  The body is text shared with msv_wave_batch_kernel (bath_calib_batch.hip).
 // ============================================================================================
 template <int C>
 __global__ __launch_bounds__(256) void msv_wave_kernel(SeqView sq, int M, const uint8_t *__restrict__ rb, int rb_stride,
                                                        const uint8_t *__restrict__ tjb_tab, MsvConsts c,
                                                        const int32_t *__restrict__ todo, int64_t ntodo, const int *__restrict__ ntodo_dev,
                                                        float *__restrict__ sc, int32_t *__restrict__ status) {
-  const int lane = threadIdx.x & 63;
-  const int64_t wid = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-  const int64_t nw = ((int64_t)gridDim.x * blockDim.x) >> 6;
-  if (ntodo_dev) ntodo = *ntodo_dev;
-  for (int64_t job = wid; job < ntodo; job += nw) {
-    const int64_t sid = todo ? (int64_t)todo[job] : job;
-    const int L = sq.len[sid];
-    const uint8_t *s = sq.data + sq.off[sid];
-    const int tjb = tjb_tab[L];
-    const int tjbm = (uint8_t)((int8_t)tjb + (int8_t)c.tbm);
-    int dp[C];
-#pragma unroll
-    for (int k = 0; k < C; k++) dp[k] = 0;
-    int xJ = 0;
-    int xB = satu8(c.base - tjbm);
-    bool overflow = false;
-    const int ph = threadIdx.x & 63;
-    int rbuf = (ph < L) ? (int)s[ph] : 0, rnext = 0;          // residues 64 rows at a time, a lane each, the next 64 in flight (see fwd_wave_kernel)
-    for (int i = 0; i < L; i++) {
-      const int j = i & 63;
-      if (j == 0) { const int q = i + 64 + ph; rnext = (q < L) ? (int)s[q] : 0; }
-      const int x = min(__builtin_amdgcn_readlane(rbuf, j), kKp - 1);
-      if (j == 63) rbuf = rnext;
-      const uint8_t *row = rb + (size_t)x * rb_stride;
-      int prev = wave_shr1_i32(dp[C - 1], 0);
-      int xE = 0;
-#pragma unroll
-      for (int k = 0; k < C; k++) {
-        const int node = lane * C + k + 1;
-        const int cost = (node <= M) ? (int)row[node] : 255;
-        int sv = max(prev, xB);
-        sv = satu8(sv + c.bias);
-        sv = satu8(sv - cost);
-        prev = dp[k];
-        dp[k] = sv;
-        xE = max(xE, sv);
-      }
-      xE = wave_max_i32(xE);
-      if (satu8(xE + c.bias) == 255) { overflow = true; break; }
-      xE = satu8(xE - c.tec);
-      xJ = max(xJ, xE);
-      xB = satu8(max(c.base, xJ) - tjbm);
-    }
-    if (lane == 0) {
-      if (overflow) { sc[sid] = INFINITY; status[sid] = BATH_ERANGE; }
-      else {
-        float r = ((float)(xJ - tjb) - (float)c.base);
-        r /= c.scale_b;
-        r = (float)((double)r - 3.0);
-        sc[sid] = r; status[sid] = BATH_OK;
-      }
-    }
-  }
+#include "bath_msv_wave_rows.hpp"
 }
 
-__host__ __device__ constexpr int vit_em_stride(int M) { return (M + 7) & ~7; }
 // ============================================================================================
 // Viterbi filter, wave per target.  int16 semantics of the reference kept exactly: every add
 // saturates to [-32768, 32767] (adds_epi16), special states wrap like int16_t assignments.
 // The D->D chain is evaluated exactly every row with a wavefront scan over (max,+) maps; the
 // reference's "lazy F" shortcut only skips work that provably cannot change any M cell.
+// (VitConsts, vit_em_stride: bath_kernels.hpp; the body is text shared with vit_wave_batch_kernel, bath_calib_batch.hip)
 // ============================================================================================
-struct VitConsts {
-  int base_w, xwE_loop, xwE_move;
-  float scale_w;
-  // window finding (p7_ViterbiFilter_BATH), all optional
-  double invP_vit, invP_msv;     // esl_gumbel_invsurv(F2, VMU,VLAMBDA) / (F2, MMU,MLAMBDA), as float->double
-  float scale_b;
-  int base_b, tec_b, bias_b;
-  int Q8;
-};
-
 template <int C>
 __global__ __launch_bounds__(256) void vit_wave_kernel(SeqView sq, int M, const int16_t *__restrict__ g_rw,
                                                        const int16_t *__restrict__ g_tw,
@@ -183,167 +121,7 @@ __global__ __launch_bounds__(256) void vit_wave_kernel(SeqView sq, int M, const 
                                                        const float *__restrict__ filtersc, const uint8_t *__restrict__ ssv_scores,
                                                        WindowRec *__restrict__ wins, int *__restrict__ win_count, int win_cap,
                                                        int32_t *__restrict__ kminmax) {
-  // Emission rows in LDS as [Kp][S] int16, entry node - 1, S a multiple of 8 (a lane's C nodes: aligned vector reads that follow the
-  // previous lane's, no bank conflicts; 64 C entries of padding behind the last row); the lane's transitions in registers, read
-  // once (as 16 bytes per node in LDS they were 16 C bytes apart from lane to lane: a 32-way conflict at C = 8).  See fwd_wave_kernel.
-  extern __shared__ __attribute__((aligned(16))) char lds[];
-  int16_t *s_rw = reinterpret_cast<int16_t *>(lds);
-  const int S = vit_em_stride(M);
-  for (int i = threadIdx.x; i < kKp * S + 64 * C; i += blockDim.x) { const int x = i / S, k = i - x * S; s_rw[i] = (x < kKp && k < M) ? g_rw[(size_t)x * (M + 1) + k + 1] : (int16_t)-32768; }
-  __syncthreads();
-  enum { MM, IM, DM, BM, MD, DD, MI, II };
-  const int lane = threadIdx.x & 63;
-  int4 twq[C];
-#pragma unroll
-  for (int k = 0; k < C; k++) twq[k] = *reinterpret_cast<const int4 *>(g_tw + (size_t)min(lane * C + k + 1, M) * 8);
-  const int64_t wid = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-  const int64_t nw = ((int64_t)gridDim.x * blockDim.x) >> 6;
-  const bool do_win = (wins != nullptr);
-  if (ntodo_dev) ntodo = *ntodo_dev;
-
-  for (int64_t job = wid; job < ntodo; job += nw) {
-    const int64_t sid = todo ? (int64_t)todo[job] : job;
-    const int L = sq.len[sid];
-    const uint8_t *s = sq.data + sq.off[sid];
-    const int xw_move = xwmove_tab[L];
-    int sc_thresh = 0, sc_ext_thresh = 0, skip_until = 0, kmin = 1 << 30, kmax = 0;
-    if (do_win) {
-      const double fsc = (double)filtersc[sid];
-      sc_thresh = (int)(int16_t)(int)ceil(((fsc + 0.69314718055994529 * c.invP_vit + 3.0) * (double)c.scale_w) -
-                                          (double)(float)c.xwE_move - (double)(float)xw_move + (double)(float)c.base_w);
-      sc_ext_thresh = (int)ceil(((fsc + 0.69314718055994529 * c.invP_msv + 3.0) * (double)c.scale_b) + c.base_b + c.tec_b + (int)tjb_tab[L]);
-    }
-    int Mp[C], Ip[C], Dp[C];
-#pragma unroll
-    for (int k = 0; k < C; k++) Mp[k] = Ip[k] = Dp[k] = -32768;
-    int xN = c.base_w;
-    int xB = (int16_t)(xN + xw_move);
-    int xJ = -32768, xC = -32768, xE = -32768;
-    bool overflow = false;
-
-    const int ph = threadIdx.x & 63;
-    int rbuf = (ph < L) ? (int)s[ph] : 0, rnext = 0;          // residues 64 rows at a time, a lane each, the next 64 in flight (see fwd_wave_kernel)
-    for (int i = 1; i <= L; i++) {
-      const int j = (i - 1) & 63;
-      if (j == 0) { const int q = i - 1 + 64 + ph; rnext = (q < L) ? (int)s[q] : 0; }
-      const int x = min(__builtin_amdgcn_readlane(rbuf, j), kKp - 1);
-      if (j == 63) rbuf = rnext;
-      int em[C];
-      {
-        const int16_t *rw = s_rw + (size_t)x * S + lane * C;
-        if constexpr (C % 8 == 0) {
-#pragma unroll
-          for (int q = 0; q < C / 8; q++) {
-            const int4 v = *reinterpret_cast<const int4 *>(rw + 8 * q);
-            const int w[4] = {v.x, v.y, v.z, v.w};
-#pragma unroll
-            for (int h = 0; h < 4; h++) { em[8 * q + 2 * h] = (int16_t)(w[h] & 0xffff); em[8 * q + 2 * h + 1] = w[h] >> 16; }
-          }
-        } else if constexpr (C % 4 == 0) {
-#pragma unroll
-          for (int q = 0; q < C / 4; q++) {
-            const int2 v = *reinterpret_cast<const int2 *>(rw + 4 * q);
-            em[4 * q] = (int16_t)(v.x & 0xffff); em[4 * q + 1] = v.x >> 16; em[4 * q + 2] = (int16_t)(v.y & 0xffff); em[4 * q + 3] = v.y >> 16;
-          }
-        } else if constexpr (C % 2 == 0) {
-#pragma unroll
-          for (int q = 0; q < C / 2; q++) { const int v = *reinterpret_cast<const int *>(rw + 2 * q); em[2 * q] = (int16_t)(v & 0xffff); em[2 * q + 1] = v >> 16; }
-        } else {
-#pragma unroll
-          for (int q = 0; q < C; q++) em[q] = (int)rw[q];
-        }
-      }
-      const int mIn = wave_shr1_i32(Mp[C - 1], -32768), iIn = wave_shr1_i32(Ip[C - 1], -32768), dIn = wave_shr1_i32(Dp[C - 1], -32768);
-      int Mc[C], Ic[C], dcv[C], tdd[C];
-      int xEl = -32768;
-#pragma unroll
-      for (int k = 0; k < C; k++) {
-        const int node = lane * C + k + 1;
-        if (node <= M) {
-          const int4 tq = twq[k];
-          const int tMM = (int16_t)(tq.x & 0xffff), tIM = (int16_t)(tq.x >> 16);
-          const int tDM = (int16_t)(tq.y & 0xffff), tBM = (int16_t)(tq.y >> 16);
-          const int tMD = (int16_t)(tq.z & 0xffff), tDD = (int16_t)(tq.z >> 16);
-          const int tMI = (int16_t)(tq.w & 0xffff), tII = (int16_t)(tq.w >> 16);
-          const int m1 = (k == 0) ? mIn : Mp[k - 1];
-          const int i1 = (k == 0) ? iIn : Ip[k - 1];
-          const int d1 = (k == 0) ? dIn : Dp[k - 1];
-          int sv = sat16(xB + tBM);
-          sv = max(sv, sat16(m1 + tMM));
-          sv = max(sv, sat16(i1 + tIM));
-          sv = max(sv, sat16(d1 + tDM));
-          sv = sat16(sv + em[k]);
-          Mc[k] = sv;
-          xEl = max(xEl, sv);
-          dcv[k] = sat16(sv + tMD);
-          tdd[k] = tDD;
-          Ic[k] = max(sat16(Mp[k] + tMI), sat16(Ip[k] + tII));
-        } else {
-          Mc[k] = -32768; Ic[k] = -32768; dcv[k] = -32768; tdd[k] = -32768;
-        }
-      }
-      xE = wave_max_i32(xEl);
-      if (xE >= 32767) { overflow = true; break; }
-      xN = (int16_t)(xN + 0);
-      xC = (int16_t)max(xC + 0, xE + c.xwE_move);
-      xJ = (int16_t)max(xJ + 0, xE + c.xwE_loop);
-      xB = (int16_t)max(xJ + xw_move, xN + xw_move);
-
-      if (do_win && i > skip_until && xE >= sc_thresh) {           // vitfilter.c:386-424
-        int rank = 1 << 30;
-#pragma unroll
-        for (int k = 0; k < C; k++) {
-          const int node = lane * C + k + 1;
-          if (node <= M && Mc[k] == xE) rank = min(rank, ((node - 1) % c.Q8) * 8 + (node - 1) / c.Q8);
-        }
-        rank = wave_min_i32(rank);
-        const int k_start = (rank / 8) + c.Q8 * (rank % 8) + 1;
-        int max_k_end = k_start, max_i_end = i, sc_ext = sc_ext_thresh, max_sc_ext = sc_ext, since = 0;
-        int kk = k_start + 1, nn = i + 1;
-        while (kk <= M && nn <= L) {
-          sc_ext += c.bias_b - (int)ssv_scores[(size_t)kk * kKp + min((int)s[nn - 1], kKp - 1)];
-          if (sc_ext >= max_sc_ext) { max_sc_ext = sc_ext; max_k_end = kk; max_i_end = nn; since = 0; }
-          else if (++since == 5) break;
-          kk++; nn++;
-        }
-        if (lane == 0) {
-          int slot = atomicAdd(win_count, 1);
-          if (slot < win_cap) wins[slot] = WindowRec{(int32_t)sid, i, max_k_end, max_k_end - k_start + 1, 0.0f};
-        }
-        kmax = max(kmax, max_k_end);
-        kmin = min(kmin, k_start);
-        skip_until = max_i_end;
-      }
-
-      // exact D row: D(node+1) = max(dcv(node), D(node)+tDD(node)); chain across lanes by scan
-      int A = -(1 << 28), B = 0;
-#pragma unroll
-      for (int k = 0; k < C; k++) { A = max(dcv[k], A + tdd[k]); B += tdd[k]; A = max(A, -(1 << 28)); }
-      // inclusive scan of f_l(x) = max(A_l, x + B_l)
-      // by DPP; lanes without a source see the identity map (A = -2^28, B = 0).  Integer (max,+): any scan order gives the same D row
-#define BATH_VIT_STEP(CTRL, MASK) { const int Ap = dpp_i<CTRL, MASK>(A, -(1 << 28)), Bp = dpp_i<CTRL, MASK>(B, 0); A = max(A, max(Ap, -(1 << 28)) + B); B = max(B + Bp, -(1 << 28)); }
-      BATH_VIT_STEP(0x111, 0xf) BATH_VIT_STEP(0x112, 0xf) BATH_VIT_STEP(0x114, 0xf) BATH_VIT_STEP(0x118, 0xf) BATH_VIT_STEP(0x142, 0xa) BATH_VIT_STEP(0x143, 0xc)
-#undef BATH_VIT_STEP
-      int din = wave_shr1_i32(A, -32768);
-      din = max(din, -32768);
-      int Dc[C];
-      Dc[0] = din;
-#pragma unroll
-      for (int k = 1; k < C; k++) Dc[k] = max(dcv[k - 1], sat16(Dc[k - 1] + tdd[k - 1]));
-#pragma unroll
-      for (int k = 0; k < C; k++) { Mp[k] = Mc[k]; Ip[k] = Ic[k]; Dp[k] = Dc[k]; }
-    }
-    if (lane == 0) {
-      if (overflow) { sc[sid] = INFINITY; status[sid] = BATH_ERANGE; }
-      else if (xC > -32768) {
-        float r = (float)xC + (float)xw_move - (float)c.base_w;
-        r /= c.scale_w;
-        r = (float)((double)r - 3.0);
-        sc[sid] = r; status[sid] = BATH_OK;
-      } else { sc[sid] = -INFINITY; status[sid] = BATH_OK; }
-      if (do_win && kminmax) { kminmax[2 * sid] = kmin; kminmax[2 * sid + 1] = kmax; }
-    }
-  }
+#include "bath_vit_wave_rows.hpp"
 }
 
 // ============================================================================================
@@ -351,6 +129,7 @@ __global__ __launch_bounds__(256) void vit_wave_kernel(SeqView sq, int M, const 
 // ============================================================================================
 // (FwdConsts and the emission rows in LDS, wave_em_stride / wave_em_load / wave_em_fill: bath_kernels.hpp, shared with bath_fwd_group.hip)
 // GT: the tables of a model too long for the LDS (above ~1100 nodes) are read from global memory (L2-resident) instead
+// (the body is text shared with fwd_wave_batch_kernel, bath_calib_batch.hip)
 template <int C, bool GT = false>
 __global__ __launch_bounds__(256) void fwd_wave_kernel(SeqView sq, int M, const float *__restrict__ g_rf, const float *__restrict__ g_tf,
                                                        const float *__restrict__ pmove_tab, FwdConsts c,
@@ -359,130 +138,7 @@ __global__ __launch_bounds__(256) void fwd_wave_kernel(SeqView sq, int M, const 
                                                        float *__restrict__ xmx, const int64_t *__restrict__ xmx_off,
                                                        float *__restrict__ dp, const int64_t *__restrict__ dp_off, int unihit,
                                                        const int32_t *__restrict__ cfg_len) {
-  extern __shared__ __attribute__((aligned(16))) char lds[];
-  const float *s_rf = reinterpret_cast<const float *>(lds);                      // !GT: [Kp][wave_em_stride(M)], entry node - 1
-  const int S = wave_em_stride(M);
-  if (ntodo_dev) ntodo = *ntodo_dev;
-  if (!GT) {
-    wave_em_fill<C>(reinterpret_cast<float *>(lds), g_rf, M, M + 1);
-    __syncthreads();
-  }
-  const int lane = threadIdx.x & 63;
-  const int64_t wid = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) >> 6;
-  const int64_t nw = ((int64_t)gridDim.x * blockDim.x) >> 6;
-  // the lane's transitions, once (!GT): MM IM DM BM / MD DD MI II of its C nodes
-  float4 tra[GT ? 1 : C], trb[GT ? 1 : C];
-  if constexpr (!GT) {
-#pragma unroll
-    for (int k = 0; k < C; k++) {
-      const int node = min(lane * C + k + 1, M);
-      tra[k] = *reinterpret_cast<const float4 *>(g_tf + (size_t)node * 8); trb[k] = *reinterpret_cast<const float4 *>(g_tf + (size_t)node * 8 + 4);
-    }
-  }
-
-  for (int64_t job = wid; job < ntodo; job += nw) {
-    const int64_t sid = todo ? (int64_t)todo[job] : job;
-    const int L = sq.len[sid];
-    const uint8_t *s = sq.data + sq.off[sid];
-    // unihit (envelope rescoring, p7_oprofile_ReconfigUnihit): nj = 0, so pmove = 2/(L+2); a plain float division, as on the host
-    // cfg_len: the length the model was configured for when that is not this target's (a region of an ORF, p7_domaindef.c:553)
-    const float pmove = unihit ? (2.0f / ((float)L + 2.0f)) : pmove_tab[cfg_len ? cfg_len[sid] : L], ploop = 1.0f - pmove;
-    float *dprow = dp ? dp + dp_off[sid] : nullptr;        // full matrix (p7_Forward): (L+1) x (M+1) x {M, D, I}
-    if (dprow) for (int k = lane; k <= M; k += 64) { dprow[(size_t)k * 3] = dprow[(size_t)k * 3 + 1] = dprow[(size_t)k * 3 + 2] = 0.f; }
-    float Mp[C], Ip[C], Dp[C];
-#pragma unroll
-    for (int k = 0; k < C; k++) Mp[k] = Ip[k] = Dp[k] = 0.f;
-    float xN = 1.f, xE = 0.f, xJ = 0.f, xC = 0.f, xB = pmove;
-    float totscale = 0.f;
-    float *xrow = (xmx && xmx_off[sid] >= 0) ? xmx + xmx_off[sid] : nullptr;      // (L+1) x {E,N,J,B,C,SCALE}, P7_OMX xmx (impl_sse.h:253-262); a negative offset: not wanted for this target
-    if (xrow && lane == 0) { xrow[0] = xE; xrow[1] = xN; xrow[2] = xJ; xrow[3] = xB; xrow[4] = xC; xrow[5] = 1.0f; }
-
-    // The residues arrive 64 rows at a time, a lane each, the next 64 in flight: with a load per row every row of a launch of a
-    // few dozen targets (one query's envelopes) waited for its own trip to memory
-    int rbuf = (lane < L) ? (int)s[lane] : 0, rnext = 0;
-    for (int i = 1; i <= L; i++) {
-      const int j = (i - 1) & 63;
-      if (j == 0) { const int q = i - 1 + 64 + lane; rnext = (q < L) ? (int)s[q] : 0; }
-      const int x = min(__builtin_amdgcn_readlane(rbuf, j), kKp - 1);
-      if (j == 63) rbuf = rnext;
-      float em[C];
-      if constexpr (!GT) wave_em_load<C>(s_rf + (size_t)x * S, lane, em);
-      else {
-#pragma unroll
-        for (int k = 0; k < C; k++) em[k] = g_rf[(size_t)x * (M + 1) + min(lane * C + k + 1, M)];
-      }
-      const float mIn = wave_shr1_f32(Mp[C - 1], 0.f), iIn = wave_shr1_f32(Ip[C - 1], 0.f), dIn = wave_shr1_f32(Dp[C - 1], 0.f);
-      float Mc[C], Ic[C], md[C], tdd[C];
-      float sumE = 0.f;
-#pragma unroll
-      for (int k = 0; k < C; k++) {
-        const int node = lane * C + k + 1;
-        if (node <= M) {
-          float4 ta, tb;                                                                      // MM IM DM BM / MD DD MI II
-          if constexpr (GT) { ta = *reinterpret_cast<const float4 *>(g_tf + (size_t)node * 8); tb = *reinterpret_cast<const float4 *>(g_tf + (size_t)node * 8 + 4); }
-          else { ta = tra[k]; tb = trb[k]; }
-          const float m1 = (k == 0) ? mIn : Mp[k - 1];
-          const float i1 = (k == 0) ? iIn : Ip[k - 1];
-          const float d1 = (k == 0) ? dIn : Dp[k - 1];
-          float sv = xB * ta.w;
-          sv = sv + m1 * ta.x;
-          sv = sv + i1 * ta.y;
-          sv = sv + d1 * ta.z;
-          sv = sv * em[k];
-          Mc[k] = sv;
-          sumE += sv;
-          md[k] = sv * tb.x;
-          tdd[k] = tb.y;
-          Ic[k] = Mp[k] * tb.z + Ip[k] * tb.w;
-        } else { Mc[k] = 0.f; Ic[k] = 0.f; md[k] = 0.f; tdd[k] = 0.f; }
-      }
-      // D(node+1) = md(node) + D(node)*tDD(node): affine maps composed by wavefront scan
-      float A = 0.f, B = 1.f;
-#pragma unroll
-      for (int k = 0; k < C; k++) { A = md[k] + A * tdd[k]; B *= tdd[k]; }
-      // by DPP; lanes without a source see the identity map (A = 0, B = 1): A + 0 * B = A, B * 1 = B
-#define BATH_FWD_STEP(CTRL, MASK) { const float Ap = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, A), CTRL, MASK, 0xf, false)), \
-                                                 Bp = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0x3f800000, __builtin_bit_cast(int, B), CTRL, MASK, 0xf, false)); \
-                                    A = A + Ap * B; B = B * Bp; }
-      BATH_FWD_STEP(0x111, 0xf) BATH_FWD_STEP(0x112, 0xf) BATH_FWD_STEP(0x114, 0xf) BATH_FWD_STEP(0x118, 0xf) BATH_FWD_STEP(0x142, 0xa) BATH_FWD_STEP(0x143, 0xc)
-#undef BATH_FWD_STEP
-      const float din = wave_shr1_f32(A, 0.f);
-      float Dc[C];
-      Dc[0] = din;
-#pragma unroll
-      for (int k = 1; k < C; k++) Dc[k] = md[k - 1] + Dc[k - 1] * tdd[k - 1];
-#pragma unroll
-      for (int k = 0; k < C; k++) sumE += Dc[k];
-      xE = wave_sum_f32(sumE);
-      xN = xN * ploop;
-      xC = (xC * ploop) + (xE * c.xfE_move);
-      xJ = (xJ * ploop) + (xE * c.xfE_loop);
-      xB = (xJ * pmove) + (xN * pmove);
-      float scale = 1.0f;
-      if (xE > 1.0e4f) {
-        xN = xN / xE; xC = xC / xE; xJ = xJ / xE; xB = xB / xE;
-        const float inv = (float)(1.0 / (double)xE);
-#pragma unroll
-        for (int k = 0; k < C; k++) { Mc[k] *= inv; Dc[k] *= inv; Ic[k] *= inv; }
-        totscale += (float)log((double)xE);
-        scale = xE;
-        xE = 1.0f;
-      }
-      if (xrow && lane == 0) { float *r = xrow + (size_t)i * 6; r[0] = xE; r[1] = xN; r[2] = xJ; r[3] = xB; r[4] = xC; r[5] = scale; }
-      if (dprow) {
-        float *r = dprow + (size_t)i * (M + 1) * 3;
-        if (lane == 0) r[0] = r[1] = r[2] = 0.f;
-#pragma unroll
-        for (int k = 0; k < C; k++) { const int node = lane * C + k + 1; if (node <= M) { r[(size_t)node * 3] = Mc[k]; r[(size_t)node * 3 + 1] = Dc[k]; r[(size_t)node * 3 + 2] = Ic[k]; } }
-      }
-#pragma unroll
-      for (int k = 0; k < C; k++) { Mp[k] = Mc[k]; Ip[k] = Ic[k]; Dp[k] = Dc[k]; }
-    }
-    if (lane == 0) {
-      if (isnan(xC) || (L > 0 && xC == 0.0f) || isinf(xC)) { sc[sid] = -INFINITY; status[sid] = BATH_ERANGE; }
-      else { sc[sid] = (float)((double)totscale + log((double)(xC * pmove))); status[sid] = BATH_OK; }
-    }
-  }
+#include "bath_fwd_wave_rows.hpp"
 }
 
 // ============================================================================================
@@ -750,7 +406,6 @@ int launch_ssv_lane(bath_hip_ctx *ctx, const bath_hip_oprofile *om, SeqView v, c
   return BATH_OK;
 }
 
-constexpr size_t kWaveTableLdsMax = 150 * 1024;      // Forward / Backward tables above this stay in global memory (160 KB of LDS per CU)
 
 // nodes per lane of the wave-per-target kernels; the body sees them as the constant CC
 #define BATH_C_SWITCH(C, ...) BATH_TILING_SWITCH(BATH_WAVE_COLUMNS, C, { ctx->set_error("model too long (> 2048 nodes)"); return BATH_EINVAL; }, __VA_ARGS__)
@@ -794,6 +449,12 @@ int launch_vit_wave(bath_hip_ctx *ctx, const bath_hip_oprofile *om, SeqView v, c
   return BATH_OK;
 }
 
+// the Forward tables stay in global memory (beyond 16 nodes per lane the transitions do not fit the registers either)
+bool fwd_wave_global_tables(const bath_hip_oprofile *om) {
+  const int C = BATH_TILING_PICK(BATH_WAVE_COLUMNS, om->M);
+  return ((size_t)kKp * wave_em_stride(om->M) + 64 * (size_t)C) * sizeof(float) > kWaveTableLdsMax || C > 16;
+}
+
 int launch_fwd_wave(bath_hip_ctx *ctx, const bath_hip_oprofile *om, SeqView v, const int32_t *d_todo, int64_t ntodo, float *d_sc, int32_t *d_status, const int *ntodo_dev,
                     float *d_xmx, const int64_t *d_xmx_off, float *d_dp, const int64_t *d_dp_off, int unihit, const int32_t *d_cfg_len) {
   if (ntodo == 0) return BATH_OK;
@@ -802,7 +463,7 @@ int launch_fwd_wave(bath_hip_ctx *ctx, const bath_hip_oprofile *om, SeqView v, c
   const size_t shmem = ((size_t)kKp * wave_em_stride(om->M) + 64 * (size_t)C) * sizeof(float);
   FwdConsts c{om->xf_E[0], om->xf_E[1]};
   if (unihit) { c.xfE_loop = 0.0f; c.xfE_move = 1.0f; }         // p7_oprofile_ReconfigUnihit, p7_oprofile.c:1421-1422
-  if (shmem > kWaveTableLdsMax || C > 16) {                     // tables stay in global memory (beyond 16 nodes per lane the transitions do not fit the registers either)
+  if (fwd_wave_global_tables(om)) {
     BATH_C_SWITCH(C, {
       hipLaunchKernelGGL((fwd_wave_kernel<CC, true>), dim3(grid), dim3(256), 0, ctx->stream, v, om->M, om->d_rf, om->d_tf, om->lt.d_pmove, c, d_todo, ntodo, ntodo_dev, d_sc, d_status, d_xmx, d_xmx_off, d_dp, d_dp_off, unihit, d_cfg_len);
     })

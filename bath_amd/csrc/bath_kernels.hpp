@@ -50,7 +50,19 @@ __device__ __forceinline__ float wave_sum_f32(float v) {
 __device__ __forceinline__ int sat16(int v) { return min(max(v, -32768), 32767); }
 __device__ __forceinline__ int satu8(int v) { return min(max(v, 0), 255); }
 
-// ---- Forward / Backward: what the wave-per-target kernels (bath_filters.hip) and the group kernel (bath_fwd_group.hip) share ----
+// ---- Viterbi: what vit_wave_kernel (bath_filters.hip) and vit_wave_batch_kernel (bath_calib_batch.hip) share ----
+__host__ __device__ constexpr int vit_em_stride(int M) { return (M + 7) & ~7; }
+struct VitConsts {
+  int base_w, xwE_loop, xwE_move;
+  float scale_w;
+  // window finding (p7_ViterbiFilter_BATH), all optional
+  double invP_vit, invP_msv;     // esl_gumbel_invsurv(F2, VMU,VLAMBDA) / (F2, MMU,MLAMBDA), as float->double
+  float scale_b;
+  int base_b, tec_b, bias_b;
+  int Q8;
+};
+
+// ---- Forward / Backward: what the wave-per-target kernels (bath_filters.hip, bath_calib_batch.hip) and the group kernel (bath_fwd_group.hip) share ----
 struct FwdConsts { float xfE_loop, xfE_move; };
 
 // Emission rows of the wave-per-target Forward / Backward kernels in LDS: [Kp][S] floats, entry node - 1 (S a multiple of 4, 64 C

@@ -71,6 +71,21 @@ int launch_vit_sorted(bath_hip_ctx *ctx, const bath_hip_oprofile *om, SeqView v,
                       int *d_bins, int32_t *d_sorted, float *d_sc, int32_t *d_status, const VitWindowArgs *wa, const std::function<int(hipStream_t)> &beside);
 struct MsvConsts;
 MsvConsts msv_consts(const bath_hip_oprofile *om);
+struct VitConsts;
+VitConsts vit_consts(const bath_hip_oprofile *om);
+constexpr size_t kWaveTableLdsMax = 150 * 1024;      // Forward / Backward tables above this stay in global memory (160 KB of LDS per CU)
+
+// ---- one standard sample set against several models per launch (bath_calib_batch.hip: calibration of a batch, bath_calibrate.hip)
+// One model of such a launch is a StdBatchModel: what msv_wave_kernel, vit_wave_kernel and fwd_wave_kernel take as arguments, read by
+// a block from a device array at blockIdx.y.  std_batch_model_fill writes one (std_batch_model_bytes bytes) for the host to upload;
+// d_sc / d_status: [0] MSV, [1] Viterbi, [2] Forward, a value per target of that filter's set.  The model's length tables are there.
+size_t std_batch_model_bytes();
+void std_batch_model_fill(void *dst, const bath_hip_oprofile *om, float *const d_sc[3], int32_t *const d_status[3]);
+// launch_fwd_wave's choice for this model: its tables stay in global memory (fwd_wave_kernel<C, true>)
+bool fwd_wave_global_tables(const bath_hip_oprofile *om);
+// d_models[n_models], all of the wave tiling <Cv> (Forward: and all with the same fwd_wave_global_tables, <gt>) and none longer
+// than <Mmax>; filter 0 MSV, 1 Viterbi, 2 Forward, over the set <v>: one launch, grid (blocks over v.n, n_models)
+int launch_std_wave_batch(bath_hip_ctx *ctx, hipStream_t stream, int filter, const void *d_models, int n_models, int Mmax, int Cv, bool gt, SeqView v);
 
 // ---- the cascade, returning the ORFs that pass the Forward filter (bath_pipeline.hip); *d_pool stays valid until the next pipeline call on ctx
 int pipeline_filters_survivors(bath_hip_ctx *ctx, const bath_hip_oprofile *om, const bath_hip_seqs *dna, const bath_pipeline_params *prm,

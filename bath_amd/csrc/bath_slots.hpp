@@ -101,7 +101,9 @@ enum class Scratch : int {
   kStdEnsembleUpload,       // std_ensemble_kernel: job list, path offsets, start states
   kStdEnsembleOut,          // ... statuses, segments, path codes
   // ---- frameshift calibration of several models per launch (bath_calibrate.hip: bath_hip_calibrate_fs_batch)
-  kCalibBatchWork,          // a job counter per sample set, the job order, the models' descriptors (FsBatchModel), the windows' scores
+  kCalibBatchWork,          // a job counter per (model, parser), the job order, the models' descriptors (FsBatchModel), the windows' scores
+  // ---- the standard filters of several models per launch (bath_calibrate.hip: bath_hip_calibrate_batch; bath_calib_batch.hip)
+  kCalibStdBatchWork,       // the models' descriptors (StdBatchModel), every model's scores and statuses; beside kCalibBatchWork in one call
   kCount
 };
 
@@ -125,7 +127,8 @@ enum class Pinned : int {
   kFsEnsembleOut,           // ... its statuses, segments and the regions' scores, down
   kStdEnsembleUpload,       // std_ensemble_kernel's upload
   kStdEnsembleOut,          // ... and its results, down
-  kCalibBatchUpload,        // bath_hip_calibrate_fs_batch: zeroed counters, job order and descriptors, up
+  kCalibBatchUpload,        // bath_hip_calibrate_fs_batch, bath_hip_calibrate_batch: zeroed counters, job order and descriptors, up
+  kCalibStdBatchUpload,     // bath_hip_calibrate_batch: the standard filters' descriptors, up (in flight beside kCalibBatchUpload)
   kCount
 };
 

@@ -888,6 +888,23 @@ void bath_hip_calib_samples_destroy(bath_hip_calib_samples *s);
  * model's launches ("calib_msv", "calib_vit", "calib_fwd" and the frameshift parsers). */
 int  bath_hip_calibrate(bath_hip_ctx *ctx, bath_hmm *hmm, int ncbi_table, uint32_t *rng_state, bath_hip_calib_samples *samples,
                         int EmL, int EmN, int EvL, int EvN, int EfL, int EfN, double Eft, int arith, double *xv, int *redrawn);
+/* bath_hip_calibrate of several models per kernel launch, for a builder that reseeds its generator for every model: every model
+ * starts from the state *rng_state holds, so all of them read the three sets of <samples> (required) and, with the one table of
+ * the run, the same two frameshift sets drawn behind them -- five shared sample sets against n_models models.  Per standard filter
+ * and per kernel tiling present one launch scores its set against the models of that tiling (a block reads its model at
+ * blockIdx.y); the two frameshift parsers follow as bath_hip_calibrate_fs_batch launches them, every model on the one pair of
+ * sets; one synchronize, then the fits.  Defined by what it equals: n_models calls of bath_hip_calibrate(ctx, hmms[k], ncbi_table,
+ * &copy_of_state, samples, ..., BATH_ARITH_STRICT, xv_k, NULL), each from the same state -- the eight evparam floats of every
+ * model bit for bit, xv (NULL, or [n_models][EmN + EvN + 3 EfN] bit scores) bit for bit, *rng_state what one such call leaves.
+ * Strict arithmetic only (the odds modes' redraw makes a model's stream depend on its scores).  1 <= n_models <=
+ * BATH_CALIB_BATCH_MAX.  BATH_EINVAL before anything is drawn, launched or written: n_models out of range, a missing model or
+ * M < 1, a model beyond the frameshift kernels' 1280 nodes (the message names its position in the batch), an unknown table,
+ * <samples> missing or not drawn from *rng_state for this context with these lengths and counts.  All or nothing: on any failure
+ * no model's evparam, *rng_state and xv are touched, and the context stays usable.  bath_hip_kernel_times afterwards: the batch's
+ * launches, "msv_wave_batch_kernel", "vit_wave_batch_kernel", "fwd_wave_batch_kernel", "fs3_fwd_batch_kernel" and
+ * "fs5_fwd_parser_batch_kernel", one per tiling present. */
+int  bath_hip_calibrate_batch(bath_hip_ctx *ctx, bath_hmm *const *hmms, int n_models, int ncbi_table, uint32_t *rng_state,
+                              bath_hip_calib_samples *samples, int EmL, int EmN, int EvL, int EvN, int EfL, int EfN, double Eft, double *xv);
 
 /* The multi-domain region stage on its own: the multihit Forward of every sequence of <regions> (each one region, configuration
  * length 100 as the pipeline's) and its trace ensemble in the context's bath_hip_set_fs_ensemble mode.  Per region r:
