@@ -880,7 +880,7 @@ int fs3_regions(bath_hip_ctx *ctx, const bath_hip_fsprofile *om, const bath_hip_
   return BATH_OK;
 }
 
-// used by the pipeline's frameshift stage (bath_pipeline.hip)
+// used by the pipeline's frameshift stage (bath_fs_stage.hip)
 int fs3_forward_scores(bath_hip_ctx *ctx, const bath_hip_fsprofile *om3, const bath_hip_seqs *dna, float *sc) {
   ctx->fs_keep_xoff.clear();
   const int mode = fs3_ctx_mode(ctx);

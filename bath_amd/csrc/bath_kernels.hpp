@@ -329,4 +329,46 @@ __device__ __forceinline__ float bias_forward(const uint8_t *s, int L, int M, co
   return logsc;
 }
 
+// p7_pli_ComputeLocalCompo (p7_pipeline.c:427-458) + p7_bg_SetFilter + esl_hmm_Configure for one candidate (the cascade's
+// post_vit_local_kernel, bath_pipeline.hip) or one DNA window (fs_bias_kernel, bath_fs_stage.hip)
+// p7_pli_ComputeLocalCompo's sum for ONE residue x over the (widened) node range: the 20 sums are independent of each other
+__device__ __forceinline__ float local_compo_x(const uint8_t *ssv_scores, int M, int base_b, float scale_b, const float *bgf, int k_start, int k_end, int x) {
+  const int k_len = k_end - k_start + 1;
+  if (k_len < 20) { k_start -= (20 - k_len) / 2; k_end += (20 - k_len) / 2; }
+  k_start = max(1, k_start); k_end = min(M, k_end);
+  float acc = 0.0f;
+  for (int k = k_start; k <= k_end; k++) {
+    const float lo = ((float)base_b - (float)ssv_scores[(size_t)k * kKp + x]) / scale_b;
+    acc += bgf[x] * expf(lo);
+  }
+  return acc;
+}
+__device__ inline void local_compo_finish(float *compo /* [20], the sums */, const float *bgf, float *eo /* [Kp][2] */);
+__device__ inline void local_compo_eo(const uint8_t *ssv_scores, int M, int base_b, float scale_b, const float *bgf, int k_start, int k_end, float *eo /* [Kp][2] */) {
+  float compo[20];
+  for (int x = 0; x < 20; x++) compo[x] = local_compo_x(ssv_scores, M, base_b, scale_b, bgf, k_start, k_end, x);
+  local_compo_finish(compo, bgf, eo);
+}
+__device__ inline void local_compo_finish(float *compo, const float *bgf, float *eo) {
+  float sum = 0.f, cc = 0.f;
+  for (int x = 0; x < 20; x++) { const float y = compo[x] - cc; const float t = sum + y; cc = (t - sum) - y; sum = t; }
+  if (sum != 0.0f) for (int x = 0; x < 20; x++) compo[x] /= sum;
+  else for (int x = 0; x < 20; x++) compo[x] = 1.0f / 20.0f;
+  for (int x = 0; x < 20; x++) { eo[2 * x] = bgf[x] / bgf[x]; eo[2 * x + 1] = compo[x] / bgf[x]; }
+  eo[2 * 20] = eo[2 * 20 + 1] = 1.0f; eo[2 * 27] = eo[2 * 27 + 1] = 1.0f; eo[2 * 28] = eo[2 * 28 + 1] = 1.0f;
+  // degenerate residues 21..26: B=DN J=IL Z=EQ O=K U=C X=all
+  const int mem[6][2] = {{2, 11}, {7, 9}, {3, 13}, {8, 8}, {1, 1}, {-1, -1}};
+  for (int dx = 0; dx < 6; dx++) {
+    float n0 = 0.f, n1 = 0.f, den = 0.f;
+    if (dx == 5) { for (int y = 0; y < 20; y++) { n0 += bgf[y]; n1 += compo[y]; den += bgf[y]; } }
+    else {
+      const int a = min(mem[dx][0], mem[dx][1]), b = max(mem[dx][0], mem[dx][1]);
+      n0 += bgf[a]; n1 += compo[a]; den += bgf[a];
+      if (b != a) { n0 += bgf[b]; n1 += compo[b]; den += bgf[b]; }
+    }
+    eo[2 * (21 + dx)] = den > 0.f ? n0 / den : 0.f;
+    eo[2 * (21 + dx) + 1] = den > 0.f ? n1 / den : 0.f;
+  }
+}
+
 }  // namespace bath

@@ -1,4 +1,5 @@
-// bath_launch.hpp -- host-side launchers shared between bath_filters.hip and bath_pipeline.hip.
+// bath_launch.hpp -- host-side launchers and stage entry points shared between the units (bath_filters.hip, bath_pipeline.hip,
+// bath_fs_stage.hip and the stages behind them).
 #pragma once
 #include <cmath>
 #include <string>
@@ -87,10 +88,6 @@ bool fwd_wave_global_tables(const bath_hip_oprofile *om);
 // than <Mmax>; filter 0 MSV, 1 Viterbi, 2 Forward, over the set <v>: one launch, grid (blocks over v.n, n_models)
 int launch_std_wave_batch(bath_hip_ctx *ctx, hipStream_t stream, int filter, const void *d_models, int n_models, int Mmax, int Cv, bool gt, SeqView v);
 
-// ---- the cascade, returning the ORFs that pass the Forward filter (bath_pipeline.hip); *d_pool stays valid until the next pipeline call on ctx
-int pipeline_filters_survivors(bath_hip_ctx *ctx, const bath_hip_oprofile *om, const bath_hip_seqs *dna, const bath_pipeline_params *prm,
-                               bath_pipeline_stats *stats, std::vector<PipelineSurvivor> *out, const uint8_t **d_pool);
-
 // ---- what the two branches' domain stages share (bath_domaindef.hip: the frameshift branch, bath_std_domains.hip: the standard one)
 constexpr double kLn2 = 0.69314718055994529;
 inline double exp_logsurv(double x, double mu, double lambda) { return x < mu ? 0.0 : -lambda * (x - mu); }
@@ -132,7 +129,7 @@ struct DomOpts {
 int std_domains(bath_hip_ctx *ctx, const bath_hip_oprofile *om, const bath_hip_seqs *dna, const std::vector<PipelineSurvivor> &surv,
                 const uint8_t *d_pool, const DomOpts &opt, int64_t *n_clustered_regions);
 
-// ---- DNA regions gathered into a pool for the frameshift kernels (bath_pipeline.hip)
+// ---- DNA regions gathered into a pool for the frameshift kernels (bath_fs_stage.hip)
 struct FsWinDev {                  // one DNA window / envelope, device view
   int64_t src_off;                 // offset of its sequence in the DNA block
   int64_t dst_off;                 // offset of the region's copy in the pool
@@ -299,5 +296,33 @@ struct OrfBuffers {               // device buffers of one translation pass
 void orf_buffers_carve(OrfBuffers *ob, void *aa, void *slots, void *sorted, void *misc /* 5*nent + kOrfMiscInts ints */, size_t nent);
 int launch_orf_scan(bath_hip_ctx *ctx, const bath_hip_seqs *dna, const OrfTablesDev &tt, int minlen, const OrfBuffers &b,
                     unsigned long long *d_n_orfs, unsigned long long *d_orf_res, int strands = 0);
+
+// ---- the cascade, returning the ORFs that pass the Forward filter (bath_pipeline.hip); *d_pool stays valid until the next pipeline call on ctx
+int pipeline_filters_survivors(bath_hip_ctx *ctx, const bath_hip_oprofile *om, const bath_hip_seqs *dna, const bath_pipeline_params *prm,
+                               bath_pipeline_stats *stats, std::vector<PipelineSurvivor> *out, const uint8_t **d_pool);
+// The ORFs that passed F4 and (frameshift pipeline) their hit windows, from every lane of the cascade: candidate ids are made
+// unique over the lanes, windows are the block's, and aa_off addresses the residues relative to <pool> (the first lane's pool;
+// another lane's pool is another allocation in the same flat address space, its ORFs carry the distance between the two).
+struct SurvivorSet {
+  std::vector<FsCandRec> sel;        // by candidate id
+  std::vector<WindowRec> wins;       // by (candidate id, n)
+  int nc_total = 0;
+  const uint8_t *pool = nullptr;
+  // the first lane's device tables, which any lane holds alike: the codon tables, the model's SSV scores, the background frequencies
+  OrfTablesDev tt{};
+  const uint8_t *d_ssvsc = nullptr;
+  const float *d_bgf = nullptr;
+  // device_only: the lists stayed in the lanes' device memory (counts known, nothing copied): what bath_fs_windows.hip reads;
+  // survivors_to_host() completes sel / wins from them when the host path must run after all
+  bool on_device = false;
+  std::vector<FsLaneSurv> lanes;
+  std::vector<bath_hip_ctx *> lane_ctx;
+  int n_states = 0;
+};
+int filters_with_survivors(bath_hip_ctx *ctx, const bath_hip_oprofile *om, const bath_hip_seqs *dna, const bath_pipeline_params *prm,
+                           bath_pipeline_stats *stats, const bath_orf_result **results, int64_t *n_results, bool want_wins, SurvivorSet *out,
+                           bool device_only = false);
+// the host path after a device-only cascade (an input bath_fs_windows.hip does not take): the lanes' lists come over after all
+int survivors_to_host(SurvivorSet *sv);
 
 }  // namespace bath

@@ -18,8 +18,6 @@
 #include <cmath>
 #include <cstring>
 #include <cstdlib>
-#include <map>
-#include <thread>
 
 #include "bath_common.hpp"
 #include "bath_kernels.hpp"
@@ -447,47 +445,6 @@ __global__ __launch_bounds__(256) void ssv_bath_kernel(Cand cand, const Counters
   }
 }
 
-// p7_pli_ComputeLocalCompo (p7_pipeline.c:427-458) + p7_bg_SetFilter + esl_hmm_Configure for one candidate
-// p7_pli_ComputeLocalCompo's sum for ONE residue x over the (widened) node range: the 20 sums are independent of each other
-__device__ __forceinline__ float local_compo_x(const uint8_t *ssv_scores, int M, int base_b, float scale_b, const float *bgf, int k_start, int k_end, int x) {
-  const int k_len = k_end - k_start + 1;
-  if (k_len < 20) { k_start -= (20 - k_len) / 2; k_end += (20 - k_len) / 2; }
-  k_start = max(1, k_start); k_end = min(M, k_end);
-  float acc = 0.0f;
-  for (int k = k_start; k <= k_end; k++) {
-    const float lo = ((float)base_b - (float)ssv_scores[(size_t)k * kKp + x]) / scale_b;
-    acc += bgf[x] * expf(lo);
-  }
-  return acc;
-}
-__device__ void local_compo_finish(float *compo /* [20], the sums */, const float *bgf, float *eo /* [Kp][2] */);
-__device__ void local_compo_eo(const uint8_t *ssv_scores, int M, int base_b, float scale_b, const float *bgf, int k_start, int k_end, float *eo /* [Kp][2] */) {
-  float compo[20];
-  for (int x = 0; x < 20; x++) compo[x] = local_compo_x(ssv_scores, M, base_b, scale_b, bgf, k_start, k_end, x);
-  local_compo_finish(compo, bgf, eo);
-}
-__device__ void local_compo_finish(float *compo, const float *bgf, float *eo) {
-  float sum = 0.f, cc = 0.f;
-  for (int x = 0; x < 20; x++) { const float y = compo[x] - cc; const float t = sum + y; cc = (t - sum) - y; sum = t; }
-  if (sum != 0.0f) for (int x = 0; x < 20; x++) compo[x] /= sum;
-  else for (int x = 0; x < 20; x++) compo[x] = 1.0f / 20.0f;
-  for (int x = 0; x < 20; x++) { eo[2 * x] = bgf[x] / bgf[x]; eo[2 * x + 1] = compo[x] / bgf[x]; }
-  eo[2 * 20] = eo[2 * 20 + 1] = 1.0f; eo[2 * 27] = eo[2 * 27 + 1] = 1.0f; eo[2 * 28] = eo[2 * 28 + 1] = 1.0f;
-  // degenerate residues 21..26: B=DN J=IL Z=EQ O=K U=C X=all
-  const int mem[6][2] = {{2, 11}, {7, 9}, {3, 13}, {8, 8}, {1, 1}, {-1, -1}};
-  for (int dx = 0; dx < 6; dx++) {
-    float n0 = 0.f, n1 = 0.f, den = 0.f;
-    if (dx == 5) { for (int y = 0; y < 20; y++) { n0 += bgf[y]; n1 += compo[y]; den += bgf[y]; } }
-    else {
-      const int a = min(mem[dx][0], mem[dx][1]), b = max(mem[dx][0], mem[dx][1]);
-      n0 += bgf[a]; n1 += compo[a]; den += bgf[a];
-      if (b != a) { n0 += bgf[b]; n1 += compo[b]; den += bgf[b]; }
-    }
-    eo[2 * (21 + dx)] = den > 0.f ? n0 / den : 0.f;
-    eo[2 * (21 + dx) + 1] = den > 0.f ? n1 / den : 0.f;
-  }
-}
-
 // after Viterbi / SSV windows: F2 test, local-composition re-filter (p7_pipeline.c:1672-1718)
 enum { PV_TODO_LB = 0, PV_TODO_FWD = 1, PV_NL = 2 };
 enum { PV_N_VIT = 0, PV_POS_VIT, PV_RES_FWD, PV_NS };
@@ -642,9 +599,6 @@ __global__ __launch_bounds__(256) void final_kernel(Cand cand, Counters *__restr
   tally_finish(tally, out);
 }
 
-// wave-per-candidate kernels take their work list length from device memory
-__global__ void copy_count_kernel(const int *src, int64_t *dst) { *dst = *src; }
-
 }  // namespace bath
 
 
@@ -788,10 +742,12 @@ extern "C" int bath_hip_pipeline_timings(const bath_hip_ctx *ctx, int max, const
 }
 
 namespace bath {
-struct FilterState {               // what the frameshift stage reads after the cascade (device memory stays in ctx->scratch)
-  PipelineWork W;
-  Counters hc{};                     // zero when the block is empty and the cascade returns before running
-  const uint8_t *d_ssvsc = nullptr;
+struct FilterState {               // what select_survivors reads after a lane's cascade (device memory stays in ctx->scratch)
+  Cand cand{};
+  const WindowRec *wins = nullptr;
+  int cand_count = 0, win_count = 0, win_cap = 0;   // zero when the block is empty and the cascade returns before running
+  // ... and what filters_with_survivors hands on with the survivors: the lane's pool and its model-dependent tables
+  const uint8_t *pool = nullptr, *d_ssvsc = nullptr;
   const float *d_bgf = nullptr;
   OrfTablesDev tt{};
 };
@@ -823,10 +779,351 @@ static int cascade_model_ok(bath_hip_ctx *ctx, const bath_hip_oprofile *om) {
   return BATH_EINVAL;
 }
 
-// p7_SSVFilter_BATH's windows for the <todo> candidates (their number: ctr->todo_ssvb), a wave per candidate, on <stream> (defined beside its
-// other caller, bath_hip_ssvfilter_bath)
+// p7_SSVFilter_BATH's windows for the <todo> candidates (their number: ctr->todo_ssvb), a wave per candidate, on <stream>: for the
+// cascade's Viterbi stage and for bath_hip_ssvfilter_bath
 static int launch_ssv_bath(bath_hip_ctx *ctx, hipStream_t stream, const bath_hip_oprofile *om, const Cand &cand, Counters *ctr, const int32_t *todo, const uint8_t *pool,
-                           const uint8_t *ssv_scores, const MsvConsts &mc, double invP, WindowRec *wins, int win_cap);
+                           const uint8_t *ssv_scores, const MsvConsts &mc, double invP, WindowRec *wins, int win_cap) {
+  BATH_TILING_SWITCH(BATH_SSVB_COLUMNS, BATH_TILING_PICK(BATH_SSVB_COLUMNS, om->M), { ctx->set_error("model too long for the SSV window kernel"); return BATH_EINVAL; },
+    hipLaunchKernelGGL(ssv_bath_kernel<CC>, dim3(wave_grid_blocks(ctx) / 4), dim3(256), 0, stream, cand, ctr, todo, pool, om->M, om->d_rb, om->rb_stride, ssv_scores,
+                       om->lt.d_tjb, om->lt.d_nullsc, mc, invP, wins, win_cap, ctr);)
+  BATH_HIP_TRY(ctx, hipGetLastError());
+  return BATH_OK;
+}
+
+// the model's SSV scores by node and residue, [(M + 1) * Kp], as the window kernels and the local composition read them
+static std::vector<uint8_t> host_ssv_scores(const bath_hip_oprofile *om) {
+  std::vector<uint8_t> tab((size_t)(om->M + 1) * kKp, 0);
+  bath_hip_oprofile_get_ssv_scores(om, tab.data());
+  return tab;
+}
+
+static void stats_from_counters(bath_pipeline_stats *s, const Counters &hc, int64_t nres, int M) {
+  s->nres = nres; s->n_orfs = (int64_t)hc.n_orfs;
+  s->n_past_msv = (int64_t)hc.n_past_msv; s->n_past_bias = (int64_t)hc.n_past_bias;
+  s->n_past_vit = (int64_t)hc.n_past_vit; s->n_past_fwd = (int64_t)hc.n_past_fwd;
+  s->pos_past_msv = (int64_t)hc.pos_past_msv; s->pos_past_bias = (int64_t)hc.pos_past_bias;
+  s->pos_past_vit = (int64_t)hc.pos_past_vit; s->pos_past_fwd = (int64_t)hc.pos_past_fwd;
+  s->cells_msv = (int64_t)(hc.orf_res - hc.res_seen) * M; s->cells_vit = (int64_t)hc.res_vit * M; s->cells_fwd = (int64_t)hc.res_fwd * M;
+}
+static void stats_add(bath_pipeline_stats *tot, const bath_pipeline_stats &a) {
+  tot->nres += a.nres; tot->n_orfs += a.n_orfs; tot->n_past_msv += a.n_past_msv; tot->n_past_bias += a.n_past_bias; tot->n_past_vit += a.n_past_vit;
+  tot->n_past_fwd += a.n_past_fwd; tot->pos_past_msv += a.pos_past_msv; tot->pos_past_bias += a.pos_past_bias; tot->pos_past_vit += a.pos_past_vit;
+  tot->pos_past_fwd += a.pos_past_fwd; tot->cells_msv += a.cells_msv; tot->cells_vit += a.cells_vit; tot->cells_fwd += a.cells_fwd;
+}
+
+namespace bath {
+// What the stages of one cascade call share: run_filters builds it once, the attempts only read it.
+struct Cascade {
+  bath_hip_ctx *ctx; const bath_hip_oprofile *om; const bath_hip_seqs *dna; const bath_pipeline_params *prm;   // the model and the block
+  int max_orf;                                    // the longest ORF the block can hold, in residues
+  int64_t nres, max_orfs;                         // the block's residues as the reference counts them; the most ORFs it can hold
+  Params P; MsvConsts mc;
+  double invP_f1, invP_vit, invP_msv;             // the score thresholds of the window filters, from F1 and F2
+  OrfTablesDev tt; const int16_t *d_emit; const uint8_t *d_ssvsc; const float *d_bgf;   // device tables
+  OrfBuffers ob; size_t ssv_shmem; int dec_blocks;
+  bool few_cands, few_msv, msv_stage;             // the block's path through the MSV and Viterbi stages (cascade_constants)
+};
+
+// Device time per stage: an event of ctx->ev_pool on the context's stream at begin() and at every lap(), which names the stage that
+// ends there and says how many kernels it launched; finish() makes ctx->timings of them, for the attempt that did not overflow.
+struct StageLaps {
+  bath_hip_ctx *ctx;
+  std::vector<StageTiming> laps;
+  int begin() { laps.clear(); return record(); }
+  int lap(const char *name, int64_t launches) { laps.push_back(StageTiming{name, 0.f, launches}); return record(); }
+  int finish() {
+    for (size_t i = 0; i < laps.size(); i++) BATH_HIP_TRY(ctx, hipEventElapsedTime(&laps[i].ms, ctx->ev_pool[i], ctx->ev_pool[i + 1]));
+    ctx->timings = laps;
+    return BATH_OK;
+  }
+ private:
+  int record() {                                  // the event after laps.size() laps
+    std::vector<hipEvent_t> &ev = ctx->ev_pool;
+    while (ev.size() <= laps.size()) { hipEvent_t e; BATH_HIP_TRY(ctx, hipEventCreate(&e)); ev.push_back(e); }
+    BATH_HIP_TRY(ctx, hipEventRecord(ev[laps.size()], ctx->stream));
+    return BATH_OK;
+  }
+};
+}  // namespace bath
+
+// Per-call tables: the genetic code's codon tables, the SSV emission thresholds by ORF length (kept with the profile), and the SSV
+// score table with the background frequencies behind it
+static int cascade_tables(Cascade &C) {
+  bath_hip_ctx *ctx = C.ctx; const bath_hip_oprofile *om = C.om;
+  const bath_pipeline_params *prm = C.prm;
+  int st;
+  if (prm->strands < 0 || prm->strands > 2 || prm->initiator < 0 || prm->initiator > 2) { ctx->set_error("bath_pipeline_params: strands / initiator out of range"); return BATH_EINVAL; }
+  if ((st = orf_tables_upload(ctx, prm->ncbi_table, &C.tt, prm->initiator)) != BATH_OK) return st;
+  if ((st = ensure_emit_table(ctx, om, prm->F1, C.max_orf)) != BATH_OK) return st;
+  DevBuf &b_tabs = ctx->scratch[Scratch::kSsvScoreTable];
+  const size_t ssv_bytes = (size_t)(om->M + 1) * kKp;
+  const size_t tabs_bytes = 8192 + ssv_bytes + 256 + 20 * 4 + 256;
+  if (tabs_bytes > b_tabs.cap) ctx->tabs_uid = 0;                 // the buffer is about to be replaced: whatever it held is gone
+  BATH_HIP_TRY(ctx, b_tabs.reserve(tabs_bytes));
+  char *tp = b_tabs.as<char>();
+  uint8_t *d_ssvsc = reinterpret_cast<uint8_t *>(tp); tp += (ssv_bytes + 255) / 256 * 256;
+  float *d_bgf = reinterpret_cast<float *>(tp);
+  if (ctx->tabs_uid != om->uid || ctx->tabs_ptr != b_tabs.p) {   // once per (context, profile): a database pass of small queries repeats this call per query
+    const std::vector<uint8_t> ssv_scores = host_ssv_scores(om);
+    BATH_HIP_TRY(ctx, hipMemcpyAsync(d_ssvsc, ssv_scores.data(), ssv_scores.size(), hipMemcpyHostToDevice, ctx->stream));
+    BATH_HIP_TRY(ctx, hipMemcpyAsync(d_bgf, kAminoBg, 20 * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
+    BATH_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));   // the host vector goes out of scope here
+    ctx->tabs_uid = om->uid; ctx->tabs_ptr = b_tabs.p;
+  }
+  C.d_emit = om->d_emit; C.d_ssvsc = d_ssvsc; C.d_bgf = d_bgf;
+  return BATH_OK;
+}
+
+// The thresholds and constants the kernels take by value, and the block's path through the MSV and Viterbi stages
+static void cascade_constants(Cascade &C) {
+  const bath_hip_oprofile *om = C.om; const bath_pipeline_params *prm = C.prm;
+  C.P = Params{};
+  C.P.F1 = prm->F1; C.P.F2 = prm->F2; C.P.F3 = prm->F3; C.P.F4 = prm->F4;
+  C.P.do_bias = prm->do_biasfilter; C.P.fs_pipe = prm->fs_pipe; C.P.minlen = prm->min_orf_len;
+  std::memcpy(C.P.evparam, om->evparam, sizeof C.P.evparam);
+  C.mc = msv_consts(om);
+  C.invP_f1 = gumbel_invsurv(prm->F1, om->evparam[0], om->evparam[1]);                    // p7_SSVFilter_BATH's threshold, msvfilter.c:302
+  C.invP_vit = (double)(float)gumbel_invsurv(prm->F2, om->evparam[2], om->evparam[3]);   // vitfilter.c:314 (float invP)
+  C.invP_msv = (double)(float)gumbel_invsurv(prm->F2, om->evparam[0], om->evparam[1]);   // vitfilter.c:319
+  // The lane-per-ORF kernels pay off when the candidates fill the chip's lanes (65 k of them): a block of 10^9 nt leaves 4 x 10^5
+  // Viterbi candidates, a 25 Mb query of configs[3] 5 x 10^3 -- 80 waves that each last as long as their longest ORF (0.7 ms whatever
+  // their number) where the wave-per-ORF kernel takes 0.2 ms.  The candidate counts live on the device; the block's size is the
+  // host's proxy.  tools/lane_crossover.py, M = 145, windows of 1 kb: Viterbi 0.72 (lane) / 0.19 (wave) ms at 12.5 k windows,
+  // 0.71 / 0.63 at 100 k, 0.75 / 1.11 at 200 k; MSV 0.19 / 0.08, 0.22 / 0.10, 0.23 / 0.13, and 1.08 / 1.41 at 400 k.
+  C.few_cands = C.dna->total < lane_min_nt(); C.few_msv = C.dna->total < 2 * lane_min_nt();
+  C.msv_stage = !C.few_msv && msv_stage_supported(om);
+}
+
+// Capacity guess: all ORFs that could exist, scaled by the expected MSV pass rate (+ slack); retried on overflow.  The sums over the
+// block's windows behind it are kept with the block (dna->cache_*) and leave C.nres and C.max_orfs.
+static int cascade_capacity(Cascade &C, int64_t *cap_out) {
+  const bath_hip_seqs *dna = C.dna; const bath_pipeline_params *prm = C.prm;
+  if (dna->cache_minlen != prm->min_orf_len) {
+    int64_t nres_c = 0, max_orfs_c = 0;
+    for (int64_t i = 0; i < dna->n; i++) {
+      const int n = dna->h_len[i];
+      if (n < 15) continue;
+      nres_c += 2 * (int64_t)(n - (dna->h_context.empty() ? 0 : dna->h_context[(size_t)i]));    // dnaSeq->W per strand
+      max_orfs_c += 6 * (int64_t)((n / 3 + 1) / (prm->min_orf_len + 1) + 1);
+    }
+    dna->cache_minlen = prm->min_orf_len; dna->cache_nres = nres_c; dna->cache_max_orfs = max_orfs_c;
+  }
+  C.nres = prm->strands == BATH_STRAND_BOTH ? dna->cache_nres : dna->cache_nres / 2;   // W once per strand searched (bathsearch.c:1071, :1084)
+  C.max_orfs = dna->cache_max_orfs;
+  if (C.max_orfs >= (int64_t)INT32_MAX) { C.ctx->set_error("DNA block too large for one pipeline call (ORF list indices are 32-bit): split it"); return BATH_EINVAL; }
+  int64_t cap = std::max<int64_t>(4096, (int64_t)((double)C.max_orfs * std::min(1.0, prm->F1 * 4.0 + 0.01)));
+  cap = std::min<int64_t>(cap, std::max<int64_t>(C.max_orfs, 4096));
+  {                                                         // tests: start with a candidate list that is too small (BATH_HIP_TEST_CANDCAP)
+    static const int forced = [] { const char *e = std::getenv("BATH_HIP_TEST_CANDCAP"); return e ? std::atoi(e) : 0; }();
+    if (forced > 0) cap = forced;                           // the first attempt only: a pass that overflows doubles it
+  }
+  *cap_out = cap;
+  return BATH_OK;
+}
+
+// Translation / ORF work-list buffers (bath_orfs.hip), carved into C.ob; the SSV cost table's share of a workgroup's LDS
+static int cascade_orf_buffers(Cascade &C) {
+  bath_hip_ctx *ctx = C.ctx; const bath_hip_oprofile *om = C.om;
+  const bath_hip_seqs *dna = C.dna;
+  int st;
+  if ((st = orf_tiles_ensure(ctx, dna)) != BATH_OK) return st;
+  const size_t nent = (size_t)dna->ntiles * 6;
+  DevBuf &b_aa = ctx->scratch[Scratch::kOrfAminoPool], &b_slots = ctx->scratch[Scratch::kOrfSlots], &b_orfs = ctx->scratch[Scratch::kOrfRecords], &b_misc = ctx->scratch[Scratch::kOrfMisc];
+  BATH_HIP_TRY(ctx, b_aa.reserve(orf_aa_bytes(dna)));
+  BATH_HIP_TRY(ctx, b_slots.reserve(((size_t)dna->ntiles * (size_t)orf_slot_cap(C.prm->min_orf_len) + 64) * 8));
+  BATH_HIP_TRY(ctx, b_orfs.reserve((size_t)(C.max_orfs + 64) * sizeof(OrfRec)));
+  BATH_HIP_TRY(ctx, b_misc.reserve((5 * nent + kOrfMiscInts) * sizeof(int32_t)));
+  C.ob = OrfBuffers{};
+  orf_buffers_carve(&C.ob, b_aa.p, b_slots.p, b_orfs.p, b_misc.p, nent);
+  C.ssv_shmem = (size_t)kSsvRows * om->ssv_row_bytes;
+  if ((st = ssv_table_fits(ctx, om)) != BATH_OK) return st;
+  C.dec_blocks = ctx->prop.multiProcessorCount * 4;
+  return BATH_OK;
+}
+
+// ---- the six stages of one attempt.  Each enqueues on the context's stream and ends with its lap.
+static SeqView cand_view(const PipelineWork &W) { return SeqView{W.pool, W.cand.off, W.cand.len, W.cand_cap}; }   // the candidates as a sequence block
+
+// 1. six-frame translation, ORFs, length-sorted work list
+static int stage_translate(const Cascade &C, const PipelineWork &W, StageLaps &laps) {
+  const int st = launch_orf_scan(C.ctx, C.dna, C.tt, C.prm->min_orf_len, C.ob, &W.ctr->n_orfs, &W.ctr->orf_res, C.prm->strands);
+  return st != BATH_OK ? st : laps.lap("translate_orfs", 4);
+}
+
+// 2. SSV + F1 threshold, lane per ORF
+static int stage_ssv_f1(const Cascade &C, const PipelineWork &W, StageLaps &laps) {
+  bath_hip_ctx *ctx = C.ctx; const bath_hip_oprofile *om = C.om;
+  const bath_hip_seqs *dna = C.dna; const OrfBuffers &ob = C.ob; const int16_t *d_emit = C.d_emit;   // (the names the dispatch macro uses)
+  const int NRk = om->NR, max_orf = C.max_orf, blocks = ctx->prop.multiProcessorCount * 4, ssv_threads = 256;
+  const size_t ssv_shmem = C.ssv_shmem;
+  bool launched = false;
+#define BATH_ORF_CASE(N, GG)                                                                                                     \
+  if (!launched && NRk == N && om->G == GG) {                                                                                    \
+    if (ssv_shmem > 64 * 1024) (void)bath::allow_max_lds((const void *)ssv_orf_kernel<N, GG>); \
+    hipLaunchKernelGGL((ssv_orf_kernel<N, GG>), dim3(blocks), dim3(ssv_threads), ssv_shmem, ctx->stream, W.pool, ob.sorted, ob.ntotal,                  \
+                       dna->view(), om->d_ssv, om->ssv_row_bytes, d_emit, max_orf, W.cand, W.cand_cap, W.ctr);                   \
+    launched = true;                                                                                                             \
+  }
+  BATH_SSV_SHAPES(BATH_ORF_CASE)
+#undef BATH_ORF_CASE
+  if (!launched) { ctx->set_error("SSV kernel: no tile shape for this model length"); return BATH_EINVAL; }
+  BATH_HIP_TRY(ctx, hipGetLastError());
+  return laps.lap("ssv_f1", 1);
+}
+
+// 3. SSV status, full MSV for the undecided, F1 on the MSV score and the bias filter: one kernel with a lane per candidate for a large
+// block, three for a small one.  Both leave the laps "classify_msv" and "f1_bias", the second empty on the one-kernel path.
+static int stage_msv(const Cascade &C, const PipelineWork &W, StageLaps &laps) {
+  bath_hip_ctx *ctx = C.ctx; const bath_hip_oprofile *om = C.om;
+  const Params &P = C.P; const MsvConsts &mc = C.mc;
+  const int M = om->M, NRk = om->NR;
+  const size_t ssv_shmem = C.ssv_shmem;
+  const F1Tables f1t{om->d_bias_eo, om->lt.d_nullsc, om->lt.d_p1, om->lt.d_lt1, om->lt.d_lt2};
+  int st;
+  if (C.msv_stage) {
+    bool launched = false;
+#define BATH_MSV_STAGE_CASE(N, ...)                                                                                                         \
+  if (!launched && NRk == N) {                                                                                                              \
+    hipLaunchKernelGGL((msv_stage_kernel<N>), dim3((unsigned)((W.cand_cap + 255) / 256)), dim3(256), ssv_shmem, ctx->stream, W.cand, W.cand_cap, W.ctr, om->d_msv, \
+                       om->ssv_row_bytes, om->lt.d_tjb, mc, P, W.pool, M, f1t, W.todo_vit, W.todo_ssvb);                                      \
+    launched = true;                                                                                                                        \
+  }
+    BATH_MSV_LANE_NR(BATH_MSV_STAGE_CASE)
+#undef BATH_MSV_STAGE_CASE
+    if (!launched) { ctx->set_error("MSV stage kernel: no tile shape for this model length"); return BATH_EINVAL; }
+    BATH_HIP_TRY(ctx, hipGetLastError());
+    if ((st = laps.lap("classify_msv", 1)) != BATH_OK) return st;
+    return laps.lap("f1_bias", 0);                            // the stage keeps its entry in the timings
+  }
+  hipLaunchKernelGGL(classify_kernel, dim3(C.dec_blocks), dim3(256), 0, ctx->stream, W.cand, W.cand_cap, W.ctr, om->lt.d_tjb, mc, W.todo_msv);
+  BATH_HIP_TRY(ctx, hipGetLastError());
+  if ((st = launch_msv_wave(ctx, om, cand_view(W), W.todo_msv, W.cand_cap, W.cand.usc, W.cand.msv_status, &W.ctr->todo_msv, !C.few_msv)) != BATH_OK) return st;
+  if ((st = laps.lap("classify_msv", 2)) != BATH_OK) return st;
+  hipLaunchKernelGGL(f1_bias_kernel, dim3(C.dec_blocks), dim3(256), 0, ctx->stream, W.cand, W.cand_cap, W.ctr, P, W.pool, M, f1t, W.todo_vit, W.todo_ssvb);
+  BATH_HIP_TRY(ctx, hipGetLastError());
+  return laps.lap("f1_bias", 1);
+}
+
+// 4. Viterbi filter with windows (P > F2) / SSV windows (P <= F2)
+static int stage_viterbi(const Cascade &C, const PipelineWork &W, StageLaps &laps) {
+  bath_hip_ctx *ctx = C.ctx; const bath_hip_oprofile *om = C.om;
+  const int64_t cap = W.cand_cap;
+  VitWindowArgs wa{};
+  wa.invP_vit = C.invP_vit; wa.invP_msv = C.invP_msv;
+  wa.d_filtersc = W.cand.filtersc; wa.d_ssv_scores = C.d_ssvsc; wa.d_wins = W.wins; wa.d_win_count = &W.ctr->win_count; wa.win_cap = W.win_cap;
+  wa.d_kminmax = W.cand.kminmax;
+  // p7_SSVFilter_BATH's windows for the candidates with P <= F2: other candidates than the Viterbi kernels', so it runs beside them
+  auto launch_ssvb = [&](hipStream_t stream) -> int {
+    return launch_ssv_bath(ctx, stream, om, W.cand, W.ctr, W.todo_ssvb, W.pool, C.d_ssvsc, C.mc, C.invP_f1, W.wins, W.win_cap);
+  };
+  int st;
+  bool ssvb_done = false;
+  if (vit_lane_supported(om) && !C.few_cands) {       // lane per ORF, ORFs bucketed by length, the long ones to the wave kernel (bath_viterbi.hip)
+    if ((st = launch_vit_sorted(ctx, om, cand_view(W), W.todo_vit, cap, &W.ctr->todo_vit, W.cand.len, W.len_bins, W.todo_sorted, W.cand.vfsc, W.cand.vit_status, &wa,
+                                launch_ssvb)) != BATH_OK) return st;      // ... and the SSV windows, all under the lane kernel
+    ssvb_done = true;
+  } else if ((st = launch_vit_wave(ctx, om, cand_view(W), W.todo_vit, cap, W.cand.vfsc, W.cand.vit_status, &wa, &W.ctr->todo_vit)) != BATH_OK) return st;
+  if ((st = laps.lap("viterbi_windows", 4)) != BATH_OK) return st;
+  if (!ssvb_done && (st = launch_ssvb(ctx->stream)) != BATH_OK) return st;
+  BATH_HIP_TRY(ctx, hipGetLastError());
+  return laps.lap("ssv_windows", 1);
+}
+
+// 5. F2, local composition re-filter, optional plain Viterbi re-run
+static int stage_post_vit(const Cascade &C, const PipelineWork &W, StageLaps &laps) {
+  bath_hip_ctx *ctx = C.ctx; const bath_hip_oprofile *om = C.om;
+  const Params &P = C.P;
+  int st;
+  hipLaunchKernelGGL(post_vit_kernel, dim3(C.dec_blocks), dim3(256), 0, ctx->stream, W.cand, W.cand_cap, W.ctr, P, W.todo_msv /* free by now */, W.todo_fwd);
+  if (P.do_bias) {
+    DevBuf &b_compo = ctx->scratch[Scratch::kLocalCompoSums];                                       // 20 sums per candidate (the 20 x 256 terms are the profile's)
+    BATH_HIP_TRY(ctx, b_compo.reserve((size_t)W.cand_cap * 20 * 4 + 256));
+    float *d_compo = b_compo.as<float>();
+    hipLaunchKernelGGL(local_compo_kernel, dim3(16384), dim3(64), 0, ctx->stream, W.cand, W.ctr, om->M, C.d_ssvsc, om->d_compo_terms, W.todo_msv, d_compo);
+    hipLaunchKernelGGL(post_vit_local_kernel, dim3(std::max(1, C.dec_blocks)), dim3(64), 0, ctx->stream, W.cand, W.ctr, P, W.pool, om->M, C.d_bgf, d_compo,
+                       om->lt.d_p1, om->lt.d_lt1, om->lt.d_lt2, W.todo_msv, W.todo_vit2, W.todo_fwd);
+  }
+  BATH_HIP_TRY(ctx, hipGetLastError());
+  if ((st = launch_vit_wave(ctx, om, cand_view(W), W.todo_vit2, W.cand_cap, W.cand.vfsc, W.cand.vit_status, nullptr, &W.ctr->todo_vit2)) != BATH_OK) return st;
+  hipLaunchKernelGGL(post_vit2_kernel, dim3(64), dim3(256), 0, ctx->stream, W.cand, W.ctr, P, W.todo_vit2, W.todo_fwd);
+  BATH_HIP_TRY(ctx, hipGetLastError());
+  return laps.lap("post_vit", 3);
+}
+
+// 6. Forward parser, F3/F4 (for the domain stage of a one-lane block it also leaves its special-state rows: ctx->keep_fwd_rows)
+static int stage_forward(const Cascade &C, const PipelineWork &W, StageLaps &laps) {
+  bath_hip_ctx *ctx = C.ctx; const bath_hip_oprofile *om = C.om;
+  const int64_t cap = W.cand_cap;
+  int st;
+  ctx->fwd_rows_kept = nullptr; ctx->fwd_rows_off = nullptr;
+  float *d_keep = nullptr; int64_t *d_keep_off = nullptr;
+  if (ctx->keep_fwd_rows) {
+    constexpr int64_t kKeepFloats = (int64_t)8 << 20;                        // 32 MB: ~1.4 M residue rows; what does not fit is computed again by the domain stage
+    DevBuf &b_rows = ctx->scratch[Scratch::kCascadeFwdRows], &b_roff = ctx->scratch[Scratch::kCascadeFwdRowOffsets];
+    BATH_HIP_TRY(ctx, b_rows.reserve((size_t)kKeepFloats * sizeof(float) + 64)); BATH_HIP_TRY(ctx, b_roff.reserve((size_t)cap * sizeof(int64_t) + 64));
+    d_keep = b_rows.as<float>(); d_keep_off = b_roff.as<int64_t>();
+    hipLaunchKernelGGL(fwd_keep_offsets_kernel, dim3(1), dim3(64), 0, ctx->stream, W.todo_fwd, &W.ctr->todo_fwd, W.cand.len, d_keep_off, kKeepFloats);
+    BATH_HIP_TRY(ctx, hipGetLastError());
+  }
+  // The candidates of a model of up to 160 nodes: four per wave, a quarter wave each, the list sorted by length so that a wave's four
+  // end together (bath_fwd_group.hip; todo_sorted and len_bins are free since the Viterbi stage joined its side stream).
+  // final_kernel reads the scores by candidate, whatever the list's order.  Blocks of every size take it -- it pays on the tens of
+  // thousands of candidates of a large block, and a small block's few are scored by the same arithmetic: the group kernel and
+  // fwd_wave_kernel agree within the parser's tolerance and not by bits, and an ORF's record does not depend on its block's size.
+  const bool fwd_group = !d_keep && fwd_group_supported(om) && ctx->fwd_group != 2;
+  if (fwd_group) {
+    if ((st = launch_len_sort(ctx, W.todo_fwd, &W.ctr->todo_fwd, W.cand.len, W.len_bins, W.todo_sorted)) != BATH_OK) return st;
+    if ((st = launch_fwd_group(ctx, om, cand_view(W), W.todo_sorted, cap, &W.ctr->todo_fwd, &W.ctr->fwd_next, W.cand.fwdsc, W.cand.fwd_status)) != BATH_OK) return st;
+  } else if ((st = launch_fwd_wave(ctx, om, cand_view(W), W.todo_fwd, cap, W.cand.fwdsc, W.cand.fwd_status, &W.ctr->todo_fwd, d_keep, d_keep_off)) != BATH_OK) return st;
+  if (d_keep) { ctx->fwd_rows_kept = d_keep; ctx->fwd_rows_off = d_keep_off; }
+  hipLaunchKernelGGL(final_kernel, dim3(C.dec_blocks), dim3(256), 0, ctx->stream, W.cand, W.ctr, C.P, W.todo_fwd);
+  BATH_HIP_TRY(ctx, hipGetLastError());
+  return laps.lap("forward_final", (d_keep ? 1 : 0) + (fwd_group ? 4 : 1) + 1);   // [row offsets,] Forward (the group kernel behind the sort's three), final_kernel
+}
+
+// One pass over the block with room for <cap> candidates and <win_need> hit windows (0: the default, twice the candidates): W laid out
+// afresh in Scratch::kCascadeWork, the counters zeroed, the six stages, the counters in *hc once the stream is idle
+static int cascade_attempt(const Cascade &C, int64_t cap, int win_need, PipelineWork &W, Counters *hc, StageLaps &laps) {
+  bath_hip_ctx *ctx = C.ctx;
+  DevBuf &b_work = ctx->scratch[Scratch::kCascadeWork];
+  const size_t need = layout(W, nullptr, (int)cap, win_need);
+  BATH_HIP_TRY(ctx, b_work.reserve(need + 4096));
+  layout(W, b_work.as<char>(), (int)cap, win_need);
+  W.pool = C.ob.aa;
+  BATH_HIP_TRY(ctx, hipMemsetAsync(W.ctr, 0, sizeof(Counters), ctx->stream));
+  int st;
+  if ((st = laps.begin()) != BATH_OK) return st;
+  if ((st = stage_translate(C, W, laps)) != BATH_OK) return st;
+  if ((st = stage_ssv_f1(C, W, laps)) != BATH_OK) return st;
+  if ((st = stage_msv(C, W, laps)) != BATH_OK) return st;
+  if ((st = stage_viterbi(C, W, laps)) != BATH_OK) return st;
+  if ((st = stage_post_vit(C, W, laps)) != BATH_OK) return st;
+  if ((st = stage_forward(C, W, laps)) != BATH_OK) return st;
+  BATH_HIP_TRY(ctx, hipMemcpyAsync(hc, W.ctr, sizeof(Counters), hipMemcpyDeviceToHost, ctx->stream));
+  BATH_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+  return BATH_OK;
+}
+
+// One record per ORF past MSV, assembled and ordered on the device (bath_records.hip).  A part of a larger block leaves them
+// there: bath_hip_pipeline_filters copies every part's records straight into their place in one page-locked array.
+static int cascade_records(const Cascade &C, const Cand &cand, int cand_count, const bath_orf_result **results, int64_t *n_results) {
+  bath_hip_ctx *ctx = C.ctx; const bath_hip_seqs *dna = C.dna;
+  bath_orf_result *d_rec = nullptr;
+  int64_t nrec = 0;
+  int st;
+  // the records' sort key holds the window in 32 bits and the ORF's first codon in 28 (bath_records.hip)
+  if (dna->n > (int64_t)UINT32_MAX || dna->maxlen / 3 >= (1 << 28)) { ctx->set_error("block too large for the ORF records' sort key (2^32 windows, 805 Mnt per window)"); return BATH_ERANGE; }
+  if ((st = build_orf_records(ctx, cand, cand_count, dna->is_part ? dna->first_window : 0, &d_rec, &nrec)) != BATH_OK) return st;
+  ctx->d_records = d_rec; ctx->n_records = nrec;
+  if (!dna->is_part) {
+    BATH_HIP_TRY(ctx, ctx->results_pinned.reserve((size_t)std::max<int64_t>(nrec, 1) * sizeof(bath_orf_result)));
+    if (nrec > 0) BATH_HIP_TRY(ctx, hipMemcpyAsync(ctx->results_pinned.p, d_rec, (size_t)nrec * sizeof(bath_orf_result), hipMemcpyDeviceToHost, ctx->stream));
+    BATH_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    *results = ctx->results_pinned.as<bath_orf_result>();
+  } else *results = nullptr;
+  if (n_results) *n_results = nrec;
+  return BATH_OK;
+}
 
 static int run_filters(bath_hip_ctx *ctx, const bath_hip_oprofile *om, const bath_hip_seqs *dna,
                        const bath_pipeline_params *prm, bath_pipeline_stats *stats,
@@ -837,262 +1134,41 @@ static int run_filters(bath_hip_ctx *ctx, const bath_hip_oprofile *om, const bat
   if (n_results) *n_results = 0;
   if (results) *results = nullptr;
   if (stats) std::memset(stats, 0, sizeof *stats);
-  const int64_t nwin = dna->n;
-  if (nwin == 0) return BATH_OK;
-  const int M = om->M;
-  const int max_orf = dna->maxlen / 3 + 1;
-  int st = om->ensure_len_tables(max_orf);
+  if (dna->n == 0) return BATH_OK;
+  Cascade C{};
+  C.ctx = ctx; C.om = om; C.dna = dna; C.prm = prm;
+  C.max_orf = dna->maxlen / 3 + 1;
+  int st = om->ensure_len_tables(C.max_orf);
   if (st != BATH_OK) return st;
-
-  // ---- per-call tables
-  OrfTablesDev tt{};
-  if (prm->strands < 0 || prm->strands > 2 || prm->initiator < 0 || prm->initiator > 2) { ctx->set_error("bath_pipeline_params: strands / initiator out of range"); return BATH_EINVAL; }
-  if ((st = orf_tables_upload(ctx, prm->ncbi_table, &tt, prm->initiator)) != BATH_OK) return st;
-  if ((st = ensure_emit_table(ctx, om, prm->F1, max_orf)) != BATH_OK) return st;
-  DevBuf &b_tabs = ctx->scratch[Scratch::kSsvScoreTable], &b_work = ctx->scratch[Scratch::kCascadeWork];
-  const size_t ssv_bytes = (size_t)(M + 1) * kKp;
-  const size_t tabs_bytes = 8192 + ssv_bytes + 256 + 20 * 4 + 256;
-  if (tabs_bytes > b_tabs.cap) ctx->tabs_uid = 0;                 // the buffer is about to be replaced: whatever it held is gone
-  BATH_HIP_TRY(ctx, b_tabs.reserve(tabs_bytes));
-  char *tp = b_tabs.as<char>();
-  const int16_t *d_emit = om->d_emit;
-  uint8_t *d_ssvsc = reinterpret_cast<uint8_t *>(tp); tp += (ssv_bytes + 255) / 256 * 256;
-  float *d_bgf = reinterpret_cast<float *>(tp);
-  if (ctx->tabs_uid != om->uid || ctx->tabs_ptr != b_tabs.p) {   // once per (context, profile): a database pass of small queries repeats this call per query
-    std::vector<uint8_t> ssv_scores(ssv_bytes, 0);
-    bath_hip_oprofile_get_ssv_scores(om, ssv_scores.data());
-    BATH_HIP_TRY(ctx, hipMemcpyAsync(d_ssvsc, ssv_scores.data(), ssv_scores.size(), hipMemcpyHostToDevice, ctx->stream));
-    BATH_HIP_TRY(ctx, hipMemcpyAsync(d_bgf, kAminoBg, 20 * sizeof(float), hipMemcpyHostToDevice, ctx->stream));
-    BATH_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));   // the host vector goes out of scope here
-    ctx->tabs_uid = om->uid; ctx->tabs_ptr = b_tabs.p;
-  }
-
-  Params P{};
-  P.F1 = prm->F1; P.F2 = prm->F2; P.F3 = prm->F3; P.F4 = prm->F4;
-  P.do_bias = prm->do_biasfilter; P.fs_pipe = prm->fs_pipe; P.minlen = prm->min_orf_len;
-  std::memcpy(P.evparam, om->evparam, sizeof P.evparam);
-  const MsvConsts mc = msv_consts(om);
-  const double invP_f1 = gumbel_invsurv(prm->F1, om->evparam[0], om->evparam[1]);   // p7_SSVFilter_BATH's threshold, msvfilter.c:302
-  VitWindowArgs wa{};
-  wa.invP_vit = (double)(float)gumbel_invsurv(prm->F2, om->evparam[2], om->evparam[3]);   // vitfilter.c:314 (float invP)
-  wa.invP_msv = (double)(float)gumbel_invsurv(prm->F2, om->evparam[0], om->evparam[1]);   // vitfilter.c:319
-
-  // ---- capacity guess: all ORFs that could exist, scaled by the expected MSV pass rate (+ slack); retried on overflow
-  if (dna->cache_minlen != prm->min_orf_len) {
-    int64_t nres_c = 0, max_orfs_c = 0;
-    for (int64_t i = 0; i < nwin; i++) {
-      const int n = dna->h_len[i];
-      if (n < 15) continue;
-      nres_c += 2 * (int64_t)(n - (dna->h_context.empty() ? 0 : dna->h_context[(size_t)i]));    // dnaSeq->W per strand
-      max_orfs_c += 6 * (int64_t)((n / 3 + 1) / (prm->min_orf_len + 1) + 1);
-    }
-    dna->cache_minlen = prm->min_orf_len; dna->cache_nres = nres_c; dna->cache_max_orfs = max_orfs_c;
-  }
-  const int64_t nres = prm->strands == BATH_STRAND_BOTH ? dna->cache_nres : dna->cache_nres / 2;   // W once per strand searched (bathsearch.c:1071, :1084)
-  const int64_t max_orfs = dna->cache_max_orfs;
-  if (max_orfs >= (int64_t)INT32_MAX) { ctx->set_error("DNA block too large for one pipeline call (ORF list indices are 32-bit): split it"); return BATH_EINVAL; }
-  int64_t cap = std::max<int64_t>(4096, (int64_t)((double)max_orfs * std::min(1.0, prm->F1 * 4.0 + 0.01)));
-  cap = std::min<int64_t>(cap, std::max<int64_t>(max_orfs, 4096));
-  {                                                         // tests: start with a candidate list that is too small (BATH_HIP_TEST_CANDCAP)
-    static const int forced = [] { const char *e = std::getenv("BATH_HIP_TEST_CANDCAP"); return e ? std::atoi(e) : 0; }();
-    if (forced > 0) cap = forced;                           // the first attempt only: a pass that overflows doubles it
-  }
-
-  // ---- translation / ORF work-list buffers (bath_orfs.hip)
-  if ((st = orf_tiles_ensure(ctx, dna)) != BATH_OK) return st;
-  const size_t nent = (size_t)dna->ntiles * 6;
-  DevBuf &b_aa = ctx->scratch[Scratch::kOrfAminoPool], &b_slots = ctx->scratch[Scratch::kOrfSlots], &b_orfs = ctx->scratch[Scratch::kOrfRecords], &b_misc = ctx->scratch[Scratch::kOrfMisc];
-  BATH_HIP_TRY(ctx, b_aa.reserve(orf_aa_bytes(dna)));
-  BATH_HIP_TRY(ctx, b_slots.reserve(((size_t)dna->ntiles * (size_t)orf_slot_cap(prm->min_orf_len) + 64) * 8));
-  BATH_HIP_TRY(ctx, b_orfs.reserve((size_t)(max_orfs + 64) * sizeof(OrfRec)));
-  BATH_HIP_TRY(ctx, b_misc.reserve((5 * nent + kOrfMiscInts) * sizeof(int32_t)));
-  OrfBuffers ob{};
-  orf_buffers_carve(&ob, b_aa.p, b_slots.p, b_orfs.p, b_misc.p, nent);
-
-  const int NRk = om->NR;
-  const size_t ssv_shmem = (size_t)kSsvRows * om->ssv_row_bytes;
-  if ((st = ssv_table_fits(ctx, om)) != BATH_OK) return st;
-  const int dec_blocks = ctx->prop.multiProcessorCount * 4;
-
-  std::vector<hipEvent_t> &ev = ctx->ev_pool;
-  while (ev.size() < 12) { hipEvent_t e; BATH_HIP_TRY(ctx, hipEventCreate(&e)); ev.push_back(e); }
+  if ((st = cascade_tables(C)) != BATH_OK) return st;
+  cascade_constants(C);
+  int64_t cap = 0;
+  if ((st = cascade_capacity(C, &cap)) != BATH_OK) return st;
+  if ((st = cascade_orf_buffers(C)) != BATH_OK) return st;
 
   PipelineWork W;
   Counters hc{};
+  StageLaps laps{ctx, {}};
   int win_need = 0;                                         // hit windows seen by a pass that ran out of room for them
   for (int attempt = 0;; attempt++) {
-    size_t need = layout(W, nullptr, (int)cap, win_need);
-    BATH_HIP_TRY(ctx, b_work.reserve(need + 4096));
-    layout(W, b_work.as<char>(), (int)cap, win_need);
-    W.pool = b_aa.as<uint8_t>();
-    BATH_HIP_TRY(ctx, hipMemsetAsync(W.ctr, 0, sizeof(Counters), ctx->stream));
-    SeqView cv{W.pool, W.cand.off, W.cand.len, cap};
-
-    int e = 0;
-    BATH_HIP_TRY(ctx, hipEventRecord(ev[e++], ctx->stream));
-    // 1. six-frame translation, ORFs, length-sorted work list
-    if ((st = launch_orf_scan(ctx, dna, tt, prm->min_orf_len, ob, &W.ctr->n_orfs, &W.ctr->orf_res, prm->strands)) != BATH_OK) return st;
-    BATH_HIP_TRY(ctx, hipEventRecord(ev[e++], ctx->stream));
-    // 2. SSV + F1 threshold, lane per ORF
-    {
-      const int blocks = ctx->prop.multiProcessorCount * 4;
-      const int ssv_threads = 256;
-      bool launched = false;
-#define BATH_ORF_CASE(N, GG)                                                                                                     \
-  if (!launched && NRk == N && om->G == GG) {                                                                                    \
-    if (ssv_shmem > 64 * 1024) (void)bath::allow_max_lds((const void *)ssv_orf_kernel<N, GG>); \
-    hipLaunchKernelGGL((ssv_orf_kernel<N, GG>), dim3(blocks), dim3(ssv_threads), ssv_shmem, ctx->stream, W.pool, ob.sorted, ob.ntotal,                  \
-                       dna->view(), om->d_ssv, om->ssv_row_bytes, d_emit, max_orf, W.cand, W.cand_cap, W.ctr);                   \
-    launched = true;                                                                                                             \
-  }
-      BATH_SSV_SHAPES(BATH_ORF_CASE)
-#undef BATH_ORF_CASE
-      if (!launched) { ctx->set_error("SSV kernel: no tile shape for this model length"); return BATH_EINVAL; }
-      BATH_HIP_TRY(ctx, hipGetLastError());
-    }
-    BATH_HIP_TRY(ctx, hipEventRecord(ev[e++], ctx->stream));
-    // The lane-per-ORF kernels pay off when the candidates fill the chip's lanes (65 k of them): a block of 10^9 nt leaves 4 x 10^5
-    // Viterbi candidates, a 25 Mb query of configs[3] 5 x 10^3 -- 80 waves that each last as long as their longest ORF (0.7 ms whatever
-    // their number) where the wave-per-ORF kernel takes 0.2 ms.  The candidate counts live on the device; the block's size is the
-    // host's proxy.  tools/lane_crossover.py, M = 145, windows of 1 kb: Viterbi 0.72 (lane) / 0.19 (wave) ms at 12.5 k windows,
-    // 0.71 / 0.63 at 100 k, 0.75 / 1.11 at 200 k; MSV 0.19 / 0.08, 0.22 / 0.10, 0.23 / 0.13, and 1.08 / 1.41 at 400 k.
-    const bool few_cands = dna->total < lane_min_nt(), few_msv = dna->total < 2 * lane_min_nt();
-    const F1Tables f1t{om->d_bias_eo, om->lt.d_nullsc, om->lt.d_p1, om->lt.d_lt1, om->lt.d_lt2};
-    // (the lane-per-ORF kernels pay off when the candidates fill the chip's lanes: see few_cands at the Viterbi stage below)
-    const bool msv_stage = !few_msv && msv_stage_supported(om);
-    if (msv_stage) {
-      // 3. a large block: SSV status, full MSV, F1 and the bias filter in one kernel, a lane per candidate
-      bool launched = false;
-#define BATH_MSV_STAGE_CASE(N, ...)                                                                                                         \
-  if (!launched && NRk == N) {                                                                                                              \
-    hipLaunchKernelGGL((msv_stage_kernel<N>), dim3((unsigned)((W.cand_cap + 255) / 256)), dim3(256), ssv_shmem, ctx->stream, W.cand, W.cand_cap, W.ctr, om->d_msv, \
-                       om->ssv_row_bytes, om->lt.d_tjb, mc, P, W.pool, M, f1t, W.todo_vit, W.todo_ssvb);                                      \
-    launched = true;                                                                                                                        \
-  }
-      BATH_MSV_LANE_NR(BATH_MSV_STAGE_CASE)
-#undef BATH_MSV_STAGE_CASE
-      if (!launched) { ctx->set_error("MSV stage kernel: no tile shape for this model length"); return BATH_EINVAL; }
-      BATH_HIP_TRY(ctx, hipGetLastError());
-      BATH_HIP_TRY(ctx, hipEventRecord(ev[e++], ctx->stream));
-      BATH_HIP_TRY(ctx, hipEventRecord(ev[e++], ctx->stream));         // the stage "f1_bias" keeps its entry in the timings: empty on this path
-    } else {
-      // 3. SSV status; full MSV for the undecided
-      hipLaunchKernelGGL(classify_kernel, dim3(dec_blocks), dim3(256), 0, ctx->stream, W.cand, W.cand_cap, W.ctr, om->lt.d_tjb, mc, W.todo_msv);
-      BATH_HIP_TRY(ctx, hipGetLastError());
-      if ((st = launch_msv_wave(ctx, om, cv, W.todo_msv, cap, W.cand.usc, W.cand.msv_status, &W.ctr->todo_msv, !few_msv)) != BATH_OK) return st;
-      BATH_HIP_TRY(ctx, hipEventRecord(ev[e++], ctx->stream));
-      // 3. F1 on the MSV score, bias filter
-      hipLaunchKernelGGL(f1_bias_kernel, dim3(dec_blocks), dim3(256), 0, ctx->stream, W.cand, W.cand_cap, W.ctr, P, W.pool, M, f1t, W.todo_vit, W.todo_ssvb);
-      BATH_HIP_TRY(ctx, hipGetLastError());
-      BATH_HIP_TRY(ctx, hipEventRecord(ev[e++], ctx->stream));
-    }
-    // 4. Viterbi filter with windows (P > F2) / SSV windows (P <= F2)
-    wa.d_filtersc = W.cand.filtersc; wa.d_ssv_scores = d_ssvsc; wa.d_wins = W.wins; wa.d_win_count = &W.ctr->win_count; wa.win_cap = W.win_cap;
-    wa.d_kminmax = W.cand.kminmax;
-    // p7_SSVFilter_BATH's windows for the candidates with P <= F2: other candidates than the Viterbi kernels', so it runs beside them
-    auto launch_ssvb = [&](hipStream_t stream) -> int {
-      return launch_ssv_bath(ctx, stream, om, W.cand, W.ctr, W.todo_ssvb, W.pool, d_ssvsc, mc, invP_f1, W.wins, W.win_cap);
-    };
-    bool ssvb_done = false;
-    if (vit_lane_supported(om) && !few_cands) {       // lane per ORF, ORFs bucketed by length, the long ones to the wave kernel (bath_viterbi.hip)
-      if ((st = launch_vit_sorted(ctx, om, cv, W.todo_vit, cap, &W.ctr->todo_vit, W.cand.len, W.len_bins, W.todo_sorted, W.cand.vfsc, W.cand.vit_status, &wa,
-                                  launch_ssvb)) != BATH_OK) return st;      // ... and the SSV windows, all under the lane kernel
-      ssvb_done = true;
-    } else if ((st = launch_vit_wave(ctx, om, cv, W.todo_vit, cap, W.cand.vfsc, W.cand.vit_status, &wa, &W.ctr->todo_vit)) != BATH_OK) return st;
-    BATH_HIP_TRY(ctx, hipEventRecord(ev[e++], ctx->stream));
-    if (!ssvb_done && (st = launch_ssvb(ctx->stream)) != BATH_OK) return st;
-    BATH_HIP_TRY(ctx, hipGetLastError());
-    BATH_HIP_TRY(ctx, hipEventRecord(ev[e++], ctx->stream));
-    // 5. F2, local composition re-filter, optional plain Viterbi re-run
-    hipLaunchKernelGGL(post_vit_kernel, dim3(dec_blocks), dim3(256), 0, ctx->stream, W.cand, W.cand_cap, W.ctr, P, W.todo_msv /* free by now */, W.todo_fwd);
-    if (P.do_bias) {
-      DevBuf &b_compo = ctx->scratch[Scratch::kLocalCompoSums];                                       // 20 sums per candidate (the 20 x 256 terms are the profile's)
-      BATH_HIP_TRY(ctx, b_compo.reserve((size_t)W.cand_cap * 20 * 4 + 256));
-      float *d_compo = b_compo.as<float>();
-      hipLaunchKernelGGL(local_compo_kernel, dim3(16384), dim3(64), 0, ctx->stream, W.cand, W.ctr, M, d_ssvsc, om->d_compo_terms, W.todo_msv, d_compo);
-      hipLaunchKernelGGL(post_vit_local_kernel, dim3(std::max(1, dec_blocks)), dim3(64), 0, ctx->stream, W.cand, W.ctr, P, W.pool, M, d_bgf, d_compo,
-                         om->lt.d_p1, om->lt.d_lt1, om->lt.d_lt2, W.todo_msv, W.todo_vit2, W.todo_fwd);
-    }
-    BATH_HIP_TRY(ctx, hipGetLastError());
-    if ((st = launch_vit_wave(ctx, om, cv, W.todo_vit2, cap, W.cand.vfsc, W.cand.vit_status, nullptr, &W.ctr->todo_vit2)) != BATH_OK) return st;
-    hipLaunchKernelGGL(post_vit2_kernel, dim3(64), dim3(256), 0, ctx->stream, W.cand, W.ctr, P, W.todo_vit2, W.todo_fwd);
-    BATH_HIP_TRY(ctx, hipGetLastError());
-    BATH_HIP_TRY(ctx, hipEventRecord(ev[e++], ctx->stream));
-    // 6. Forward parser, F3/F4 (for the domain stage of a one-lane block it also leaves its special-state rows: ctx->keep_fwd_rows)
-    ctx->fwd_rows_kept = nullptr; ctx->fwd_rows_off = nullptr;
-    float *d_keep = nullptr; int64_t *d_keep_off = nullptr;
-    if (ctx->keep_fwd_rows) {
-      constexpr int64_t kKeepFloats = (int64_t)8 << 20;                        // 32 MB: ~1.4 M residue rows; what does not fit is computed again by the domain stage
-      DevBuf &b_rows = ctx->scratch[Scratch::kCascadeFwdRows], &b_roff = ctx->scratch[Scratch::kCascadeFwdRowOffsets];
-      BATH_HIP_TRY(ctx, b_rows.reserve((size_t)kKeepFloats * sizeof(float) + 64)); BATH_HIP_TRY(ctx, b_roff.reserve((size_t)cap * sizeof(int64_t) + 64));
-      d_keep = b_rows.as<float>(); d_keep_off = b_roff.as<int64_t>();
-      hipLaunchKernelGGL(fwd_keep_offsets_kernel, dim3(1), dim3(64), 0, ctx->stream, W.todo_fwd, &W.ctr->todo_fwd, W.cand.len, d_keep_off, kKeepFloats);
-      BATH_HIP_TRY(ctx, hipGetLastError());
-    }
-    // The candidates of a model of up to 160 nodes: four per wave, a quarter wave each, the list sorted by length so that a wave's four
-    // end together (bath_fwd_group.hip; todo_sorted and len_bins are free since the Viterbi stage joined its side stream).
-    // final_kernel reads the scores by candidate, whatever the list's order.  Blocks of every size take it -- it pays on the tens of
-    // thousands of candidates of a large block, and a small block's few are scored by the same arithmetic: the group kernel and
-    // fwd_wave_kernel agree within the parser's tolerance and not by bits, and an ORF's record does not depend on its block's size.
-    const bool fwd_group = !d_keep && fwd_group_supported(om) && ctx->fwd_group != 2;
-    if (fwd_group) {
-      if ((st = launch_len_sort(ctx, W.todo_fwd, &W.ctr->todo_fwd, W.cand.len, W.len_bins, W.todo_sorted)) != BATH_OK) return st;
-      if ((st = launch_fwd_group(ctx, om, cv, W.todo_sorted, cap, &W.ctr->todo_fwd, &W.ctr->fwd_next, W.cand.fwdsc, W.cand.fwd_status)) != BATH_OK) return st;
-    } else if ((st = launch_fwd_wave(ctx, om, cv, W.todo_fwd, cap, W.cand.fwdsc, W.cand.fwd_status, &W.ctr->todo_fwd, d_keep, d_keep_off)) != BATH_OK) return st;
-    const int64_t fwd_launches = (d_keep ? 1 : 0) + (fwd_group ? 4 : 1) + 1;       // [row offsets,] Forward (the group kernel behind the sort's three), final_kernel
-    if (d_keep) { ctx->fwd_rows_kept = d_keep; ctx->fwd_rows_off = d_keep_off; }
-    hipLaunchKernelGGL(final_kernel, dim3(dec_blocks), dim3(256), 0, ctx->stream, W.cand, W.ctr, P, W.todo_fwd);
-    BATH_HIP_TRY(ctx, hipGetLastError());
-    BATH_HIP_TRY(ctx, hipEventRecord(ev[e++], ctx->stream));
-
-    BATH_HIP_TRY(ctx, hipMemcpyAsync(&hc, W.ctr, sizeof(Counters), hipMemcpyDeviceToHost, ctx->stream));
-    BATH_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    if ((st = cascade_attempt(C, cap, win_need, W, &hc, laps)) != BATH_OK) return st;
     // the reference's window list grows without limit (p7_hmmwindow.c:83); here the kernels count every window they find and
     // drop those beyond the buffer, so a pass that found more windows than fit is repeated with room for all of them
-    if (hc.overflow || hc.cand_count > cap || hc.win_count > W.win_cap) {
-      if (attempt >= 4) { ctx->set_error("candidate / window buffers overflowed repeatedly"); return BATH_EMEM; }
-      if (hc.overflow || hc.cand_count > cap) cap = std::max<int64_t>(cap * 2, (int64_t)hc.cand_count + 1024);
-      if (hc.win_count > W.win_cap) win_need = hc.win_count + hc.win_count / 4 + 1024;
-      continue;
-    }
-    static const char *names[] = {"translate_orfs", "ssv_f1", "classify_msv", "f1_bias", "viterbi_windows", "ssv_windows", "post_vit", "forward_final"};
-    const int64_t launches[] = {4, 1, msv_stage ? 1 : 2, msv_stage ? 0 : 1, 4, 1, 3, fwd_launches};
-    ctx->timings.clear();
-    for (int i = 0; i + 1 < e; i++) {
-      float ms = 0.f;
-      BATH_HIP_TRY(ctx, hipEventElapsedTime(&ms, ev[i], ev[i + 1]));
-      ctx->timings.push_back(StageTiming{names[i], ms, launches[i]});
-    }
-    break;
+    if (!(hc.overflow || hc.cand_count > cap || hc.win_count > W.win_cap)) break;
+    if (attempt >= 4) { ctx->set_error("candidate / window buffers overflowed repeatedly"); return BATH_EMEM; }
+    if (hc.overflow || hc.cand_count > cap) cap = std::max<int64_t>(cap * 2, (int64_t)hc.cand_count + 1024);
+    if (hc.win_count > W.win_cap) win_need = hc.win_count + hc.win_count / 4 + 1024;
   }
+  if ((st = laps.finish()) != BATH_OK) return st;
 
-  if (stats) {
-    stats->nres = nres; stats->n_orfs = (int64_t)hc.n_orfs;
-    stats->n_past_msv = (int64_t)hc.n_past_msv; stats->n_past_bias = (int64_t)hc.n_past_bias;
-    stats->n_past_vit = (int64_t)hc.n_past_vit; stats->n_past_fwd = (int64_t)hc.n_past_fwd;
-    stats->pos_past_msv = (int64_t)hc.pos_past_msv; stats->pos_past_bias = (int64_t)hc.pos_past_bias;
-    stats->pos_past_vit = (int64_t)hc.pos_past_vit; stats->pos_past_fwd = (int64_t)hc.pos_past_fwd;
-    stats->cells_msv = (int64_t)(hc.orf_res - hc.res_seen) * M; stats->cells_vit = (int64_t)hc.res_vit * M; stats->cells_fwd = (int64_t)hc.res_fwd * M;
-  }
-
+  if (stats) stats_from_counters(stats, hc, C.nres, om->M);
   if (results) {
-    // one record per ORF past MSV, assembled and ordered on the device (bath_records.hip).  A part of a larger block leaves them
-    // there: bath_hip_pipeline_filters copies every part's records straight into their place in one page-locked array.
-    bath_orf_result *d_rec = nullptr;
-    int64_t nrec = 0;
-    // the records' sort key holds the window in 32 bits and the ORF's first codon in 28 (bath_records.hip)
-    if (dna->n > (int64_t)UINT32_MAX || dna->maxlen / 3 >= (1 << 28)) { ctx->set_error("block too large for the ORF records' sort key (2^32 windows, 805 Mnt per window)"); return BATH_ERANGE; }
-    if ((st = build_orf_records(ctx, W.cand, hc.cand_count, dna->is_part ? dna->first_window : 0, &d_rec, &nrec)) != BATH_OK) return st;
-    ctx->d_records = d_rec; ctx->n_records = nrec;
-    if (!dna->is_part) {
-      BATH_HIP_TRY(ctx, ctx->results_pinned.reserve((size_t)std::max<int64_t>(nrec, 1) * sizeof(bath_orf_result)));
-      if (nrec > 0) BATH_HIP_TRY(ctx, hipMemcpyAsync(ctx->results_pinned.p, d_rec, (size_t)nrec * sizeof(bath_orf_result), hipMemcpyDeviceToHost, ctx->stream));
-      BATH_HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-      *results = ctx->results_pinned.as<bath_orf_result>();
-    } else *results = nullptr;
-    if (n_results) *n_results = nrec;
+    if ((st = cascade_records(C, W.cand, hc.cand_count, results, n_results)) != BATH_OK) return st;
   } else if (n_results) *n_results = (int64_t)hc.n_past_msv;
-  if (state) { state->W = W; state->hc = hc; state->d_ssvsc = d_ssvsc; state->d_bgf = d_bgf; state->tt = tt; }
+  if (state) {
+    state->cand = W.cand; state->wins = W.wins; state->cand_count = hc.cand_count; state->win_count = hc.win_count; state->win_cap = W.win_cap;
+    state->pool = W.pool; state->d_ssvsc = C.d_ssvsc; state->d_bgf = C.d_bgf; state->tt = C.tt;
+  }
   return BATH_OK;
 }
 
@@ -1189,7 +1265,6 @@ static int run_filters_lanes(bath_hip_ctx *ctx, const bath_hip_oprofile *om, con
   for (bath_hip_ctx *lane : ctx->lanes) { lane->fs_strict = ctx->fs_strict; lane->fs_odds = ctx->fs_odds; lane->fs5_odds = ctx->fs5_odds; lane->fwd_group = ctx->fwd_group; }
   if ((st = ensure_parts(ctx, dna, K)) != BATH_OK) return st;
   std::vector<bath_pipeline_stats> pst((size_t)K);
-  std::vector<const bath_orf_result *> pres((size_t)K, nullptr);
   std::vector<int64_t> pn((size_t)K, 0);
   std::vector<int> rc((size_t)K, BATH_OK);
   states->assign((size_t)K, FilterState{});
@@ -1201,7 +1276,8 @@ static int run_filters_lanes(bath_hip_ctx *ctx, const bath_hip_oprofile *om, con
   if (!ctx->lane_pool) ctx->lane_pool = new LanePool();            // the lanes' host threads live as long as the context
   ctx->lane_pool->run(K, [&](int k) {
     bath_hip_ctx *lane = ctx->lanes[(size_t)k];
-    rc[(size_t)k] = run_filters(lane, om, dna->parts[(size_t)k], prm, &pst[(size_t)k], results ? &pres[(size_t)k] : nullptr, &pn[(size_t)k], &(*states)[(size_t)k]);
+    const bath_orf_result *left_on_device = nullptr;               // a part's records stay in lane->d_records
+    rc[(size_t)k] = run_filters(lane, om, dna->parts[(size_t)k], prm, &pst[(size_t)k], results ? &left_on_device : nullptr, &pn[(size_t)k], &(*states)[(size_t)k]);
     if (rc[(size_t)k] == BATH_OK) rc[(size_t)k] = after(k, lane, dna->parts[(size_t)k], (*states)[(size_t)k]);
   });
   for (int k = 0; k < K; k++)
@@ -1210,10 +1286,7 @@ static int run_filters_lanes(bath_hip_ctx *ctx, const bath_hip_oprofile *om, con
   bath_pipeline_stats tot{};
   int64_t ntot = 0;
   for (int k = 0; k < K; k++) {
-    const bath_pipeline_stats &a = pst[(size_t)k];
-    tot.nres += a.nres; tot.n_orfs += a.n_orfs; tot.n_past_msv += a.n_past_msv; tot.n_past_bias += a.n_past_bias; tot.n_past_vit += a.n_past_vit;
-    tot.n_past_fwd += a.n_past_fwd; tot.pos_past_msv += a.pos_past_msv; tot.pos_past_bias += a.pos_past_bias; tot.pos_past_vit += a.pos_past_vit;
-    tot.pos_past_fwd += a.pos_past_fwd; tot.cells_msv += a.cells_msv; tot.cells_vit += a.cells_vit; tot.cells_fwd += a.cells_fwd;
+    stats_add(&tot, pst[(size_t)k]);
     ntot += pn[(size_t)k];
   }
   if (stats) *stats = tot;
@@ -1251,131 +1324,8 @@ extern "C" int bath_hip_pipeline_filters(bath_hip_ctx *ctx, const bath_hip_oprof
                            [](int, bath_hip_ctx *, const bath_hip_seqs *, const FilterState &) { return (int)BATH_OK; });
 }
 
-// =================================================================================================
-// Frameshift stage: p7_pli_BuildDNAWindows + p7_pli_Frameshift up to the branch decision
-// (p7_pipeline.c:462-572, 1339-1470).  The ORFs that passed F4 are few (10^-4 of all ORFs): window building is
-// the reference's own serial logic on the host; the DNA windows' bias filter and 3-codon frameshift Forward run
-// on the GPU, batched over all windows of the block.
-// =================================================================================================
+// ---- the cascade's survivors, for the hits path (pipeline_filters_survivors) and the frameshift stage (bath_fs_stage.hip) -------
 namespace bath {
-
-
-// copy each window out of its sequence, reverse-complemented for the bottom strand
-__global__ void fs_window_gather_kernel(const uint8_t *__restrict__ dna, const FsWinDev *__restrict__ wins, int nw, const uint8_t *__restrict__ comp,
-                                        uint8_t *__restrict__ pool) {
-  for (int w = blockIdx.x; w < nw; w += gridDim.x) {
-    const FsWinDev d = wins[w];
-    const uint8_t *src = dna + d.src_off;
-    uint8_t *dst = pool + d.dst_off;
-    for (int i = threadIdx.x; i < d.len; i += blockDim.x) {
-      const int r = d.start - 1 + i;                     // 0-based position on the strand being read
-      dst[i] = d.strand ? comp[min((int)src[d.seq_n - 1 - r], 17)] : src[r];
-    }
-  }
-}
-
-// p7_bg_fs_FilterScore (p7_bg.c:522-561) without its length term: esl_hmm_Forward of the 2-state filter HMM over the
-// canonical residues of each of the three frames.  Lane per (window, pass): pass 0 uses the model's composition,
-// pass 1 the local composition of nodes kmin..kmax (p7_pli_ComputeLocalCompo).  out[(w*2+pass)*3 + frame].
-__global__ void fs_bias_kernel(const uint8_t *__restrict__ pool, const FsWinDev *__restrict__ wins, int nw, const uint8_t *__restrict__ aa_full, int M,
-                               const float *__restrict__ eo_global, const uint8_t *__restrict__ ssv_scores, int base_b, float scale_b,
-                               const float *__restrict__ bgf, float *__restrict__ out) {
-  const int t = blockIdx.x * blockDim.x + threadIdx.x;
-  if (t >= 2 * nw) return;
-  const int w = t >> 1, pass = t & 1;
-  const FsWinDev d = wins[w];
-  float eo_local[2 * kKp];
-  const float *e = eo_global;
-  if (pass == 1) {
-    if (d.kmin > d.kmax) { out[t * 3] = out[t * 3 + 1] = out[t * 3 + 2] = -INFINITY; return; }
-    local_compo_eo(ssv_scores, M, base_b, scale_b, bgf, d.kmin, d.kmax, eo_local);
-    e = eo_local;
-  }
-  const uint8_t *s = pool + d.dst_off;
-  const int L = d.len, L3 = L / 3;
-  const float p1 = (float)L3 / (float)(L3 + 1);                             // p7_bg_SetLength(bg, length/3), p7_bg.c:193
-  const float L1 = (float)M / 8.0f;
-  const float t00 = p1, t01 = 1.0f - p1, t10 = 1.0f / (L1 + 1.0f), t11 = L1 / (L1 + 1.0f);
-  for (int f = 0; f < 3; f++) {
-    float logsc = 0.0f, d0 = 0.f, d1 = 0.f;
-    int cnt = 0;
-    for (int i = f; i + 2 < L; i += 3) {
-      const int a = min((int)s[i], 17), b = min((int)s[i + 1], 17), c = min((int)s[i + 2], 17);
-      const int x = aa_full[(a * 18 + b) * 18 + c];
-      if (x >= 20) continue;                                                // esl_abc_XIsCanonical
-      float n0, n1;
-      if (cnt == 0) { n0 = e[2 * x] * 0.999f; n1 = e[2 * x + 1] * 0.001f; }
-      else {
-        n0 = 0.0f + d0 * t00; n0 = n0 + d1 * t10; n0 *= e[2 * x];
-        n1 = 0.0f + d0 * t01; n1 = n1 + d1 * t11; n1 *= e[2 * x + 1];
-      }
-      const float mx = fmaxf(fmaxf(n0, 0.0f), n1);
-      d0 = n0 / mx; d1 = n1 / mx;
-      logsc += (float)log((double)mx);
-      cnt++;
-    }
-    if (cnt == 0) logsc = -INFINITY;                                         // esl_hmm_Forward, L = 0: log(pi[M]) = log 0
-    else { float end = 0.0f + d0 * 1.0f; end = end + d1 * 1.0f; logsc += (float)log((double)end); }
-    out[t * 3 + f] = logsc;
-  }
-}
-
-// Copies the regions described by <regs> (dst_off is filled in here) into one pool on the device, reverse-complemented
-// for the bottom strand, and returns a sequence-block view of the pool (borrowed pointers: clear them before <view> dies).
-int fs_gather_view(bath_hip_ctx *ctx, const bath_hip_seqs *dna, std::vector<FsWinDev> &regs, const uint8_t *d_comp, bath_hip_seqs *view, const FsWinDev **d_desc_out) {
-  const int nw = (int)regs.size();
-  int64_t pool_bytes = 0;
-  for (FsWinDev &d : regs) { d.dst_off = pool_bytes; pool_bytes += ((int64_t)d.len + 15) / 16 * 16 + 16; }
-  DevBuf &b_pool = ctx->scratch[Scratch::kFsGatherPool], &b_desc = ctx->scratch[Scratch::kFsGatherDesc];
-  BATH_HIP_TRY(ctx, b_pool.reserve((size_t)pool_bytes + 256));
-  const size_t desc_bytes = ((size_t)nw * sizeof(FsWinDev) + 255) / 256 * 256;
-  BATH_HIP_TRY(ctx, b_desc.reserve(desc_bytes + (size_t)nw * 12 + 64));          // descriptors, then the view's off[] and len[]
-  BATH_HIP_TRY(ctx, hipMemsetAsync(b_pool.p, 0x1d, (size_t)pool_bytes + 256, ctx->stream));
-  FsWinDev *d_desc = b_desc.as<FsWinDev>();
-  BATH_HIP_TRY(ctx, hipMemcpyAsync(d_desc, regs.data(), (size_t)nw * sizeof(FsWinDev), hipMemcpyHostToDevice, ctx->stream));
-  hipLaunchKernelGGL(fs_window_gather_kernel, dim3((unsigned)std::max(1, std::min(nw, 65535))), dim3(256), 0, ctx->stream, dna->d_data, d_desc, nw, d_comp, b_pool.as<uint8_t>());
-  BATH_HIP_TRY(ctx, hipGetLastError());
-  view->ctx = ctx; view->n = nw; view->d_data = b_pool.as<uint8_t>(); view->is_part = true;
-  view->h_off.resize((size_t)nw); view->h_len.resize((size_t)nw);
-  view->maxlen = 0; view->total = 0;
-  for (int i = 0; i < nw; i++) {
-    view->h_off[(size_t)i] = regs[(size_t)i].dst_off; view->h_len[(size_t)i] = regs[(size_t)i].len;
-    view->maxlen = std::max(view->maxlen, regs[(size_t)i].len); view->total += regs[(size_t)i].len;
-  }
-  view->total_aligned = pool_bytes;
-  int64_t *d_voff = reinterpret_cast<int64_t *>(reinterpret_cast<char *>(d_desc) + desc_bytes);
-  int32_t *d_vlen = reinterpret_cast<int32_t *>(d_voff + nw);
-  BATH_HIP_TRY(ctx, hipMemcpyAsync(d_voff, view->h_off.data(), (size_t)nw * 8, hipMemcpyHostToDevice, ctx->stream));
-  BATH_HIP_TRY(ctx, hipMemcpyAsync(d_vlen, view->h_len.data(), (size_t)nw * 4, hipMemcpyHostToDevice, ctx->stream));
-  view->d_off = d_voff; view->d_len = d_vlen;
-  if (d_desc_out) *d_desc_out = d_desc;
-  return BATH_OK;
-}
-
-// the same for windows built on the device (bath_fs_windows.hip): descriptors with their pool offsets, the view's off[] and
-// len[] are already there; only the pool is reserved and the copy kernel launched
-int fs_gather_view_built(bath_hip_ctx *ctx, const bath_hip_seqs *dna, const FsWinBuild &B, const uint8_t *d_comp, bath_hip_seqs *view, const FsWinDev **d_desc_out) {
-  const int nw = B.nw;
-  DevBuf &b_pool = ctx->scratch[Scratch::kFsWindowPool];             // its own pool, apart from the one the domain stage gathers into (kFsGatherPool)
-  BATH_HIP_TRY(ctx, b_pool.reserve((size_t)B.pool_bytes + 256));
-  BATH_HIP_TRY(ctx, hipMemsetAsync(b_pool.p, 0x1d, (size_t)B.pool_bytes + 256, ctx->stream));
-  hipLaunchKernelGGL(fs_window_gather_kernel, dim3((unsigned)std::max(1, std::min(nw, 65535))), dim3(256), 0, ctx->stream, dna->d_data, B.d_desc, nw, d_comp, b_pool.as<uint8_t>());
-  BATH_HIP_TRY(ctx, hipGetLastError());
-  view->ctx = ctx; view->n = nw; view->d_data = b_pool.as<uint8_t>(); view->is_part = true;
-  view->h_off.resize((size_t)nw); view->h_len.resize((size_t)nw);
-  for (int i = 0; i < nw; i++) { view->h_off[(size_t)i] = B.h_voff[i]; view->h_len[(size_t)i] = B.h_vlen[i]; }
-  view->maxlen = B.maxlen; view->total = B.total; view->total_aligned = B.pool_bytes;
-  view->d_off = const_cast<int64_t *>(B.d_voff); view->d_len = const_cast<int32_t *>(B.d_vlen);
-  if (d_desc_out) *d_desc_out = B.d_desc;
-  return BATH_OK;
-}
-
-float flogsum_host(float a, float b) {               // p7_FLogsum, logsum.c:105-111 (table of logsum.c:89)
-  // (a function-local static with an initialiser: built once, thread-safe -- worker contexts and the window threads call this concurrently)
-  static const std::vector<float> tbl = [] { std::vector<float> t(16000); for (int i = 0; i < 16000; i++) t[i] = (float)std::log(1. + std::exp((double)-i / 1000.f)); return t; }();
-  const float mx = std::max(a, b), mn = std::min(a, b);
-  return (mn == -INFINITY || (mx - mn) >= 15.7f) ? mx : mx + tbl[(int)((mx - mn) * 1000.f)];
-}
 
 // The frameshift stage needs only the ORFs that passed F4 (a few thousand of the block's 10^5-10^6 MSV survivors) and their
 // hit windows: select them on the device, so that what crosses PCIe is a few hundred KB instead of every candidate array.
@@ -1395,23 +1345,6 @@ __global__ void fs_select_wins_kernel(const WindowRec *__restrict__ wins, int nw
   }
 }
 
-// The ORFs that passed F4 and (frameshift pipeline) their hit windows, from every lane of the cascade: candidate ids are made
-// unique over the lanes, windows are the block's, and aa_off addresses the residues relative to <pool> (the first lane's pool;
-// another lane's pool is another allocation in the same flat address space, its ORFs carry the distance between the two).
-struct SurvivorSet {
-  std::vector<FsCandRec> sel;        // by candidate id
-  std::vector<WindowRec> wins;       // by (candidate id, n)
-  int nc_total = 0;
-  const uint8_t *pool = nullptr;
-  FilterState S0;                    // the first lane's state: the model-dependent tables any lane holds alike
-  // device_only: the lists stayed in the lanes' device memory (counts known, nothing copied): what bath_fs_windows.hip reads;
-  // survivors_to_host() completes sel / wins from them when the host path must run after all
-  bool on_device = false;
-  std::vector<FsLaneSurv> lanes;
-  std::vector<bath_hip_ctx *> lane_ctx;
-  int n_states = 0;
-};
-
 static int fetch_survivors(bath_hip_ctx *lane, const FsLaneSurv &ls, std::vector<FsCandRec> *sel, std::vector<WindowRec> *wins) {
   sel->resize((size_t)ls.n_c); wins->resize((size_t)ls.n_w);
   if (ls.n_c) BATH_HIP_TRY(lane, hipMemcpyAsync(sel->data(), ls.d_c, sel->size() * sizeof(FsCandRec), hipMemcpyDeviceToHost, lane->stream));
@@ -1425,9 +1358,9 @@ static int select_survivors(bath_hip_ctx *lane, const FilterState &S, bool want_
                             FsLaneSurv *dev = nullptr /* non-null: leave the lists on the device, report where */) {
   sel->clear(); wins->clear();
   if (dev) *dev = FsLaneSurv{};
-  const int nc = S.hc.cand_count;
+  const int nc = S.cand_count;
   if (nc <= 0) return BATH_OK;
-  const int nwins = want_wins ? std::min(S.hc.win_count, S.W.win_cap) : 0;
+  const int nwins = want_wins ? std::min(S.win_count, S.win_cap) : 0;
   DevBuf &b_sel = lane->scratch[Scratch::kSurvivorSelect];
   const size_t o_c = 256, o_w = o_c + ((size_t)nc * sizeof(FsCandRec) + 255) / 256 * 256;
   BATH_HIP_TRY(lane, b_sel.reserve(o_w + (size_t)std::max(nwins, 1) * sizeof(WindowRec) + 256));
@@ -1436,8 +1369,8 @@ static int select_survivors(bath_hip_ctx *lane, const FilterState &S, bool want_
   WindowRec *d_w = reinterpret_cast<WindowRec *>(b_sel.as<char>() + o_w);
   BATH_HIP_TRY(lane, hipMemsetAsync(d_cnt, 0, 256, lane->stream));
   const int blocks = lane->prop.multiProcessorCount * 4;
-  hipLaunchKernelGGL(fs_select_cands_kernel, dim3(blocks), dim3(256), 0, lane->stream, S.W.cand, nc, d_c, d_cnt, lane->fwd_rows_kept ? lane->fwd_rows_off : nullptr);
-  if (nwins > 0) hipLaunchKernelGGL(fs_select_wins_kernel, dim3(blocks), dim3(256), 0, lane->stream, S.W.wins, nwins, S.W.cand.stage, d_w, d_cnt + 1);
+  hipLaunchKernelGGL(fs_select_cands_kernel, dim3(blocks), dim3(256), 0, lane->stream, S.cand, nc, d_c, d_cnt, lane->fwd_rows_kept ? lane->fwd_rows_off : nullptr);
+  if (nwins > 0) hipLaunchKernelGGL(fs_select_wins_kernel, dim3(blocks), dim3(256), 0, lane->stream, S.wins, nwins, S.cand.stage, d_w, d_cnt + 1);
   BATH_HIP_TRY(lane, hipGetLastError());
   int h_cnt[2] = {0, 0};
   BATH_HIP_TRY(lane, hipMemcpyAsync(h_cnt, d_cnt, sizeof h_cnt, hipMemcpyDeviceToHost, lane->stream));
@@ -1452,8 +1385,7 @@ static void merge_lane_lists(SurvivorSet *out, const std::vector<std::vector<FsC
   fs_merge_survivors(out->lanes.data(), out->n_states, lsel, lwin, &out->sel, &out->wins);
 }
 
-// the host path after a device-only cascade (an input bath_fs_windows.hip does not take): the lanes' lists come over after all
-static int survivors_to_host(SurvivorSet *sv) {
+int survivors_to_host(SurvivorSet *sv) {
   if (!sv->on_device) return BATH_OK;
   std::vector<std::vector<FsCandRec>> lsel((size_t)sv->n_states);
   std::vector<std::vector<WindowRec>> lwin((size_t)sv->n_states);
@@ -1466,9 +1398,8 @@ static int survivors_to_host(SurvivorSet *sv) {
   return BATH_OK;
 }
 
-static int filters_with_survivors(bath_hip_ctx *ctx, const bath_hip_oprofile *om, const bath_hip_seqs *dna, const bath_pipeline_params *prm,
-                                  bath_pipeline_stats *stats, const bath_orf_result **results, int64_t *n_results, bool want_wins, SurvivorSet *out,
-                                  bool device_only = false) {
+int filters_with_survivors(bath_hip_ctx *ctx, const bath_hip_oprofile *om, const bath_hip_seqs *dna, const bath_pipeline_params *prm,
+                           bath_pipeline_stats *stats, const bath_orf_result **results, int64_t *n_results, bool want_wins, SurvivorSet *out, bool device_only) {
   std::vector<FilterState> states;
   const size_t nl = (size_t)std::max(1, pipeline_lane_count(dna));
   std::vector<std::vector<FsCandRec>> lsel(nl);
@@ -1485,8 +1416,8 @@ static int filters_with_survivors(bath_hip_ctx *ctx, const bath_hip_oprofile *om
                              });
   if (st != BATH_OK) return st;
   out->sel.clear(); out->wins.clear(); out->nc_total = 0;
-  out->S0 = states.empty() ? FilterState{} : states[0];
-  out->pool = out->S0.W.pool;
+  const FilterState S0 = states.empty() ? FilterState{} : states[0];          // the first lane's tables: any lane holds them alike
+  out->pool = S0.pool; out->tt = S0.tt; out->d_ssvsc = S0.d_ssvsc; out->d_bgf = S0.d_bgf;
   out->n_states = (int)states.size();
   out->lanes.assign(ldev.begin(), ldev.begin() + (ptrdiff_t)states.size());
   out->lane_ctx.assign(lctx.begin(), lctx.begin() + (ptrdiff_t)states.size());
@@ -1494,8 +1425,8 @@ static int filters_with_survivors(bath_hip_ctx *ctx, const bath_hip_oprofile *om
     FsLaneSurv &ls = out->lanes[k];
     ls.cand_base = out->nc_total;
     ls.first_window = first[k];
-    ls.dpool = (int64_t)(reinterpret_cast<intptr_t>(states[k].W.pool) - reinterpret_cast<intptr_t>(out->pool));
-    out->nc_total += std::max(states[k].hc.cand_count, 0);
+    ls.dpool = (int64_t)(reinterpret_cast<intptr_t>(states[k].pool) - reinterpret_cast<intptr_t>(out->pool));
+    out->nc_total += std::max(states[k].cand_count, 0);
   }
   out->on_device = device_only;
   if (!device_only) merge_lane_lists(out, lsel, lwin);                     // (the lanes fetched and ordered their lists as they finished)
@@ -1523,107 +1454,6 @@ int bath::pipeline_filters_survivors(bath_hip_ctx *ctx, const bath_hip_oprofile 
     if (a.strand != b.strand) return a.strand < b.strand;
     return a.start < b.start;
   });
-  return BATH_OK;
-}
-
-extern "C" int bath_hip_pipeline_frameshift(bath_hip_ctx *ctx, const bath_hip_oprofile *om, const bath_hip_fsprofile *om_fs3, const bath_hip_seqs *dna,
-                                            const bath_pipeline_params *prm_in, bath_pipeline_stats *stats,
-                                            const bath_orf_result **results, int64_t *n_results,
-                                            const bath_fs_window **fs_windows, int64_t *n_fs_windows) {
-  if (!ctx || !om || !om_fs3 || !dna || !prm_in || !fs_windows || !n_fs_windows) return BATH_EINVAL;
-  if (fsprofile_codon_lengths(om_fs3) != 3) { ctx->set_error("the frameshift stage needs the 3-codon frameshift profile"); return BATH_EINVAL; }
-  if (fs_model_ok(ctx, om_fs3) != BATH_OK) return BATH_EINVAL;
-  *fs_windows = nullptr; *n_fs_windows = 0;
-  ctx->fs_windows.clear();
-  bath_pipeline_params prm = *prm_in;
-  prm.fs_pipe = 1;
-  bath_pipeline_stats st_local{};
-  StageClock clk;
-  SurvivorSet sv;
-  const bool try_device = fs_windows_on_device();
-  int st = filters_with_survivors(ctx, om, dna, &prm, &st_local, results, n_results, true, &sv, try_device);
-  if (st != BATH_OK) return st;
-  clk.lap("fs:   cascade + F4 survivors selected");
-  const FilterState &S = sv.S0;
-  const int nc = sv.nc_total;
-  const int M = om->M;
-
-  // ---- p7_pli_BuildDNAWindows + the per-window ORF summary of p7_pli_Frameshift (bath_fs_windows.hip): by kernels, from the lists the
-  // cascade's lanes left on the device; on the host, from the lists fetched after all, for the blocks the kernels hand back
-  FsWinBuild B;
-  st = try_device ? fs_build_windows_device(ctx, om, om_fs3, dna, &prm, sv.lanes.data(), sv.n_states, nc, &B) : (int)BATH_ENORESULT;
-  if (st == BATH_OK) clk.lap("fs:   DNA windows (device)");
-  else if (st != BATH_ENORESULT) return st;
-  else {
-    if ((st = survivors_to_host(&sv)) != BATH_OK) return st;
-    if ((st = fs_build_windows_host(ctx, om, dna, &prm, sv.sel.data(), (int)sv.sel.size(), sv.wins.data(), (int)sv.wins.size(), &B)) != BATH_OK) return st;
-    clk.lap("fs:   DNA windows (host)");
-  }
-  const int nw = B.nw;
-  std::vector<bath_fs_window> out((size_t)nw);                              // (the records arrive completed, after the branch decision)
-  int64_t pos_fwd = 0;
-  ctx->fs_std_orfs.clear();
-  ctx->fs_std_pool = sv.pool;
-  if (nw > 0) {
-    // ---- the windows' copies, bias filter and 3-codon frameshift Forward for all of them
-    DevBuf &b_out = ctx->scratch[Scratch::kFsWindowBias];
-    bath_hip_seqs view;
-    const FsWinDev *d_desc = nullptr;
-    if ((st = fs_gather_view_built(ctx, dna, B, S.tt.comp, &view, &d_desc)) != BATH_OK) return st;   // descriptors, offsets and lengths are on the device
-    BATH_HIP_TRY(ctx, b_out.reserve((size_t)nw * 6 * sizeof(float) + 64));
-    // the bias filter (a lane per window and pass, serial over the window) and the Forward parser are independent: the bias
-    // kernel goes to the side stream, behind the gather
-    if ((st = fs_fork(ctx)) != BATH_OK) return st;
-    hipLaunchKernelGGL(fs_bias_kernel, dim3((unsigned)((2 * nw + 63) / 64)), dim3(64), 0, ctx->side_stream, view.d_data, d_desc, nw, S.tt.full, M, om->d_bias_eo,
-                       S.d_ssvsc, (int)om->base_b, om->scale_b, S.d_bgf, b_out.as<float>());
-    BATH_HIP_TRY(ctx, hipGetLastError());
-    std::vector<float> h_fsc((size_t)nw);
-    ctx->fs_regions_all.clear();
-    ctx->fs_keep_xoff.clear();
-    if (ctx->fs_want_regions && nw <= (int64_t)ctx->prop.multiProcessorCount * 16) {
-      // The domain stage follows: its Backward parser, domain decoding and region heuristics run here, for every window,
-      // next to the Forward parser whose score decides the branch.  These kernels are bound by the row chain of the longest
-      // window as long as every window has a wave of its own (16 waves per CU), so up to that many windows the ones that will
-      // take the standard branch cost nothing extra and the frameshift-branch windows have their regions before the decision
-      // is made.  Beyond it the kernels take a second round of windows and the Backward parser of the windows that turn out
-      // not to need it costs more than it saves (bench block, 7.6 k windows: 49.6 ms instead of 35 + 11.6 ms).
-      ctx->fs_regions_all.assign((size_t)nw * (size_t)(1 + 3 * fs_max_regions()), 0);
-      const float pmove = (2.0f + 1.0f) / (100.0f + 2.0f + 1.0f);              // p7_fs_ReconfigLength(L = 100, nj = 1): the saved length (p7_domaindef.c:318)
-      st = fs3_regions(ctx, om_fs3, &view, (float)std::log((double)(1.0f - pmove)), ctx->fs_regions_all.data(), h_fsc.data());
-    } else {
-      // more windows than both parsers can run side by side for: Forward for all of them, the domain stage runs the Backward parser
-      // for the frameshift-branch windows only (a speculative Backward of the longest windows beside Forward did not pay: DESIGN.md 7)
-      st = fs3_forward_scores(ctx, om_fs3, &view, h_fsc.data());
-    }
-    if (st != BATH_OK) return st;
-    // ---- scores -> P-values -> branch (fsw_decide_kernel); the host reads the completed records once and keeps the bookkeeping:
-    // pos_past_fwd, and the ORFs of the windows that take the standard branch (:1479-1487), from the ordered ORF list
-    if ((st = fs_join(ctx)) != BATH_OK) return st;                            // the bias kernel's side stream
-    if ((st = fs_decide(ctx, om_fs3, &prm, B, b_out.as<float>(), ctx->scratch[Scratch::kFs3FwdScores].as<float>(), h_fsc.data(), out.data())) != BATH_OK) return st;
-    clk.lap("fs:   gather + bias + 3-codon Forward + branch decision (device)");
-    std::vector<char> aligned((size_t)std::max(nc, 1), 0);                   // oxf_holder[i] == NULL: an overlapping window already took the ORF (:1485)
-    for (int i = 0; i < nw; i++) {
-      const bath_fs_window &r = out[(size_t)i];
-      if (r.branch == 1) { pos_fwd += r.length; continue; }
-      if (r.branch != 2) continue;
-      const int n_seq = dna->h_len[(size_t)r.window];
-      for (int32_t z = B.h_grp[2 * i]; z < B.h_grp[2 * i + 1]; z++) {
-        const FsOrfDev &o = B.h_orfs[z];
-        if (!fs_orf_in_window(o, r, n_seq) || o.P > prm.F3) continue;         // :1405, :1483
-        if (aligned[(size_t)o.cand]) continue;
-        aligned[(size_t)o.cand] = 1;
-        pos_fwd += (int64_t)o.n * 3;
-        PipelineSurvivor ps;
-        ps.window = r.window; ps.aa_off = o.aa_off; ps.strand = r.strand; ps.start = o.start; ps.n = o.n; ps.win_start = r.n; ps.fs_window = i;
-        ctx->fs_std_orfs.push_back(ps);
-      }
-    }
-  }
-  clk.lap("fs:   branch decision");
-  st_local.pos_past_fwd = pos_fwd;                                         // in the fs pipeline only this stage counts it (:1468, :1490)
-  if (stats) *stats = st_local;
-  ctx->fs_windows = out;
-  *fs_windows = ctx->fs_windows.data(); *n_fs_windows = nw;
   return BATH_OK;
 }
 
@@ -1658,8 +1488,7 @@ extern "C" int bath_hip_vitfilter_bath(bath_hip_ctx *ctx, const bath_hip_oprofil
   const int M = om->M;
   int st = om->ensure_len_tables(sq->maxlen + 1);
   if (st != BATH_OK) return st;
-  std::vector<uint8_t> ssv_scores((size_t)(M + 1) * kKp, 0);
-  bath_hip_oprofile_get_ssv_scores(om, ssv_scores.data());
+  const std::vector<uint8_t> ssv_scores = host_ssv_scores(om);
   const int cap = (int)std::min<int64_t>((int64_t)1 << 26, sq->total / 2 + 16 * n + 1024);      // a window ends at least one residue after the last
   DevBuf &b = ctx->scratch[Scratch::kFilterBathWork];
   // The cascade's switch (run_filters): a batch as large as the ORFs of a block of lane_min_nt() nucleotides takes the lane-per-target
@@ -1701,15 +1530,6 @@ extern "C" int bath_hip_vitfilter_bath(bath_hip_ctx *ctx, const bath_hip_oprofil
   return windows_out(ctx, reinterpret_cast<const WindowRec *>(p + o_w), wa.d_win_count, cap, wins, nwins);
 }
 
-static int launch_ssv_bath(bath_hip_ctx *ctx, hipStream_t stream, const bath_hip_oprofile *om, const Cand &cand, Counters *ctr, const int32_t *todo, const uint8_t *pool,
-                           const uint8_t *ssv_scores, const MsvConsts &mc, double invP, WindowRec *wins, int win_cap) {
-  BATH_TILING_SWITCH(BATH_SSVB_COLUMNS, BATH_TILING_PICK(BATH_SSVB_COLUMNS, om->M), { ctx->set_error("model too long for the SSV window kernel"); return BATH_EINVAL; },
-    hipLaunchKernelGGL(ssv_bath_kernel<CC>, dim3(wave_grid_blocks(ctx) / 4), dim3(256), 0, stream, cand, ctr, todo, pool, om->M, om->d_rb, om->rb_stride, ssv_scores,
-                       om->lt.d_tjb, om->lt.d_nullsc, mc, invP, wins, win_cap, ctr);)
-  BATH_HIP_TRY(ctx, hipGetLastError());
-  return BATH_OK;
-}
-
 extern "C" int bath_hip_ssvfilter_bath(bath_hip_ctx *ctx, const bath_hip_oprofile *om, const bath_hip_seqs *sq, double P,
                                        const bath_hmm_window **wins, int64_t *nwins) {
   if (!ctx || !om || !sq || !wins || !nwins) return BATH_EINVAL;
@@ -1718,11 +1538,9 @@ extern "C" int bath_hip_ssvfilter_bath(bath_hip_ctx *ctx, const bath_hip_oprofil
   const int64_t n = sq->n;
   if (n == 0) return BATH_OK;
   if (n >= (int64_t)INT32_MAX) return BATH_EINVAL;
-  const int M = om->M;
   int st = om->ensure_len_tables(sq->maxlen + 1);
   if (st != BATH_OK) return st;
-  std::vector<uint8_t> ssv_scores((size_t)(M + 1) * kKp, 0);
-  bath_hip_oprofile_get_ssv_scores(om, ssv_scores.data());
+  const std::vector<uint8_t> ssv_scores = host_ssv_scores(om);
   const int cap = (int)std::min<int64_t>((int64_t)1 << 26, sq->total / 2 + 16 * n + 1024);
   DevBuf &b = ctx->scratch[Scratch::kFilterBathWork];
   const size_t o_todo = 0, o_km = o_todo + (size_t)n * 4, o_ctr = (o_km + (size_t)n * 8 + 255) / 256 * 256, o_ssv = o_ctr + 256 + sizeof(Counters),

@@ -30,7 +30,7 @@ enum class Scratch : int {
   kRecordSortTemp,          // rocprim's temporary storage
   kRecords,                 // the records (ctx->d_records), until the next cascade call
   kSurvivorSelect,          // a lane's F4 survivors and their hit windows
-  // ---- frameshift pipeline: DNA windows, bias filter, branch decision (bath_fs_windows.hip, bath_pipeline.hip)
+  // ---- frameshift pipeline: DNA windows, bias filter, branch decision (bath_fs_windows.hip, bath_fs_stage.hip)
   kFsWindowPadding,         // the profile's window padding fractions, kept while ctx->fsw_pad_uid names the profile
   kFsWindowWork,            // the device-side window builder's workspace
   kFsWindowResult,          // what a build leaves: header, view arrays, ordered ORFs, groups, window records, descriptors (ResLayout)
