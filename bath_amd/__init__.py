@@ -382,6 +382,10 @@ ABI = {
     "bath_hip_calib_samples_destroy": (None, [_vp]),
     "bath_hip_calibrate": (C.c_int, [_vp, C.POINTER(_Hmm), C.c_int, C.POINTER(C.c_uint32), _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                      C.c_double, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_int)]),
+    "bath_hip_calibrate_std": (C.c_int, [_vp, C.POINTER(_Hmm), C.POINTER(C.c_uint32), _vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                         C.c_double, C.POINTER(C.c_double)]),
+    "bath_hip_calibrate_std_batch": (C.c_int, [_vp, C.POINTER(C.POINTER(_Hmm)), C.c_int, C.POINTER(C.c_uint32), _vp, C.c_int, C.c_int, C.c_int, C.c_int,
+                                               C.c_int, C.c_int, C.c_double, C.POINTER(C.c_double)]),
 }
 
 _lib = None
@@ -2014,44 +2018,59 @@ class CalibSamples:
 
 
 def calibrate(ctx, hmm, ncbi_table, state, samples=None, EmL=200, EmN=200, EvL=200, EvN=200, EfL=100, EfN=200, Eft=0.04, arith="strict",
-              want_xv=False):
+              want_xv=False, fs=True):
     """p7_Calibrate of a model in memory, on the GPU: lambda, the MSV and Viterbi mus, the Forward tau and the two frameshift taus
     are stored in the model (hmm.evparam).  Returns the generator's state afterwards; with want_xv also the bit scores the five
     fits saw, {"msv", "vit", "fwd", "fs3", "fs5"}.  samples: a CalibSamples drawn from <state> with these lengths and counts, or
-    None to draw the three standard sets for this call."""
+    None to draw the three standard sets for this call.
+    fs=False: the standard fits alone (bath_hip_calibrate_std), what the reference's search-time builder runs without --fs and
+    --hmmout: evparam[0:6] as with fs=True bit for bit, evparam[6:8] unset (FS_UNSET), no frameshift sample drawn and no frameshift
+    parser launched; the state returned is the one behind the three standard sets, want_xv gives {"msv", "vit", "fwd"}, and
+    ncbi_table and arith are not read."""
     if arith not in ARITH_MODES:
         raise ValueError("arith: expected one of %s" % ", ".join(ARITH_MODES))
     st = C.c_uint32(state)
-    n = [EmN, EvN, EfN, EfN, EfN]
+    n = [EmN, EvN, EfN, EfN, EfN] if fs else [EmN, EvN, EfN]
     xv = np.zeros(sum(n), np.float64) if want_xv else None
     re2 = (C.c_int * 2)(0, 0)
-    ctx._check(lib().bath_hip_calibrate(ctx._h, hmm._p, ncbi_table, C.byref(st), None if samples is None else samples._h,
-                                        EmL, EmN, EvL, EvN, EfL, EfN, Eft, ARITH_MODES[arith], None if xv is None else _f64p(xv), re2), "calibrate")
+    if fs:
+        ctx._check(lib().bath_hip_calibrate(ctx._h, hmm._p, ncbi_table, C.byref(st), None if samples is None else samples._h,
+                                            EmL, EmN, EvL, EvN, EfL, EfN, Eft, ARITH_MODES[arith], None if xv is None else _f64p(xv), re2), "calibrate")
+    else:
+        ctx._check(lib().bath_hip_calibrate_std(ctx._h, hmm._p, C.byref(st), None if samples is None else samples._h,
+                                                EmL, EmN, EvL, EvN, EfL, EfN, Eft, None if xv is None else _f64p(xv)), "calibrate")
     hmm.evparam = np.array(hmm._p.contents.evparam[:], dtype=np.float32)
     if not want_xv:
         return st.value
     cut = np.cumsum([0] + n)
-    return st.value, {k: xv[cut[i]:cut[i + 1]].copy() for i, k in enumerate(("msv", "vit", "fwd", "fs3", "fs5"))}
+    return st.value, {k: xv[cut[i]:cut[i + 1]].copy() for i, k in enumerate(("msv", "vit", "fwd", "fs3", "fs5")[:len(n)])}
 
 
-def calibrate_batch(ctx, hmms, ncbi_table, state, samples, EmL=200, EmN=200, EvL=200, EvN=200, EfL=100, EfN=200, Eft=0.04, want_xv=False):
+def calibrate_batch(ctx, hmms, ncbi_table, state, samples, EmL=200, EmN=200, EvL=200, EvN=200, EfL=100, EfN=200, Eft=0.04, want_xv=False,
+                    fs=True):
     """calibrate of several models (at most CALIB_BATCH_MAX) per kernel launch, for a run that reseeds its generator per model: every
     model starts from <state> and reads the sets of <samples> (a CalibSamples drawn from <state>, required) and one pair of
     frameshift sets behind them.  What len(hmms) calibrate calls from <state> in strict arithmetic give, bit for bit: evparam is
     stored in every model.  Returns the generator's state afterwards (the state one calibrate call leaves); with want_xv also a list
     of the five-key dicts calibrate returns, one per model.  All or nothing: a BathError names the position in the batch of the
-    model it is about, and no model is changed."""
+    model it is about, and no model is changed.
+    fs=False: what len(hmms) calibrate(fs=False) calls give (bath_hip_calibrate_std_batch): the three standard launches per tiling
+    and nothing else; models up to the filter cascade's 2048 nodes."""
     hmms = list(hmms)
     n = len(hmms)
     st = C.c_uint32(state)
     ptrs = (C.POINTER(_Hmm) * max(n, 1))(*[h._p for h in hmms])
-    sizes = [EmN, EvN, EfN, EfN, EfN]
+    sizes = [EmN, EvN, EfN, EfN, EfN] if fs else [EmN, EvN, EfN]
     xv = np.zeros((max(n, 1), sum(sizes)), np.float64) if want_xv else None
-    ctx._check(lib().bath_hip_calibrate_batch(ctx._h, ptrs, n, ncbi_table, C.byref(st), None if samples is None else samples._h,
-                                              EmL, EmN, EvL, EvN, EfL, EfN, Eft, None if xv is None else _f64p(xv)), "calibrate_batch")
+    if fs:
+        ctx._check(lib().bath_hip_calibrate_batch(ctx._h, ptrs, n, ncbi_table, C.byref(st), None if samples is None else samples._h,
+                                                  EmL, EmN, EvL, EvN, EfL, EfN, Eft, None if xv is None else _f64p(xv)), "calibrate_batch")
+    else:
+        ctx._check(lib().bath_hip_calibrate_std_batch(ctx._h, ptrs, n, C.byref(st), None if samples is None else samples._h,
+                                                      EmL, EmN, EvL, EvN, EfL, EfN, Eft, None if xv is None else _f64p(xv)), "calibrate_batch")
     for h in hmms:
         h.evparam = np.array(h._p.contents.evparam[:], dtype=np.float32)
     if not want_xv:
         return st.value
     cut = np.cumsum([0] + sizes)
-    return st.value, [{k: xv[m, cut[i]:cut[i + 1]].copy() for i, k in enumerate(("msv", "vit", "fwd", "fs3", "fs5"))} for m in range(n)]
+    return st.value, [{k: xv[m, cut[i]:cut[i + 1]].copy() for i, k in enumerate(("msv", "vit", "fwd", "fs3", "fs5")[:len(sizes)])} for m in range(n)]

@@ -210,18 +210,50 @@ class GpuCalibrator:
         if opts["--seed"]:                                               # reseeded per model: the same three sets for every model
             self.samples = ba.CalibSamples(self.ctx, state, **self.E)
 
-    def calibrate(self, hmm, state):
-        """Stores the eight E-value parameters in the model; returns the generator's state afterwards."""
-        return ba.calibrate(self.ctx, hmm, self.opts["--ct"], state, self.samples, Eft=self.opts["--Eft"], arith=self.opts["--arith"], **self.E)
+    def calibrate(self, hmm, state, fs=True):
+        """Stores the eight E-value parameters in the model (fs=False: the six standard ones, the two taus unset); returns the
+        generator's state afterwards."""
+        return ba.calibrate(self.ctx, hmm, self.opts["--ct"], state, self.samples, Eft=self.opts["--Eft"], arith=self.opts["--arith"], fs=fs, **self.E)
 
-    def calibrate_many(self, hmms, state):
+    def calibrate_many(self, hmms, state, fs=True):
         """calibrate of every model of a batch (--batch above 1: a seed, strict arithmetic) in one call; the state one call leaves."""
-        return ba.calibrate_batch(self.ctx, hmms, self.opts["--ct"], state, self.samples, Eft=self.opts["--Eft"], **self.E)
+        return ba.calibrate_batch(self.ctx, hmms, self.opts["--ct"], state, self.samples, Eft=self.opts["--Eft"], fs=fs, **self.E)
 
     def close(self):
         if self.samples is not None:
             self.samples.close()
         self.ctx.close()
+
+
+def build_models(queries, score, opts, cal, state, fh, path_in, fs=True, date=None, report=None):
+    """The build loop bathbuild and bathsearch --qformat fasta share: the models of <queries> (read_queries' records) built
+    (build_model), calibrated by <cal> in batches of opts["--batch"] from <state> (a seed: every model from <state>; --seed 0: the
+    generator runs on), and their text written to the open binary file <fh> in record order; at most a batch's models are alive
+    at once.  fs=False: the standard fits only (calibrate's fs), handed to the calibrator only then, so a calibrator without the
+    argument serves every fs=True caller.  report(index from 0, record, model), when given, is called after a model is written."""
+    nb, seed = opts["--batch"], opts["--seed"]
+    kw = {} if fs else {"fs": False}
+    for i0 in range(0, len(queries), nb):                                # --batch 1: a model at a time, call for call as without the option
+        part = queries[i0:i0 + nb]
+        hmms = [build_model(score, opts["-n"] or name, seq, opts) for name, _, seq in part]
+        if nb == 1:
+            after = cal.calibrate(hmms[0], state, **kw)
+            if not seed:                                                 # p7_builder.c:131: no reseeding, the generator runs on
+                state = after
+        else:                                                            # a seed: every model starts from <state> (parse_options)
+            try:
+                if hasattr(cal, "calibrate_many"):
+                    cal.calibrate_many(hmms, state, **kw)
+                else:
+                    for hmm in hmms:
+                        cal.calibrate(hmm, state, **kw)
+            except ba.BathError as e:
+                raise ba.BathError("records %d to %d of %s, calibrated as one batch: %s" % (i0 + 1, i0 + len(part), path_in, e))
+        for j, (hmm, rec) in enumerate(zip(hmms, part)):
+            fh.write(ba.hmm_text(hmm, date=date or time.strftime("%a %b %e %H:%M:%S %Y")))
+            if report is not None:
+                report(i0 + j, rec, hmm)
+        del hmms                                                         # at most a batch's models are alive at once
 
 
 def run(argv, stdout=None, device=0, date=None, calibrator=None):
@@ -258,27 +290,8 @@ def run(argv, stdout=None, device=0, date=None, calibrator=None):
     try:
         fh = open(tmp_out, "wb")                                         # models go out one by one: a proteome's text is never held whole
         cal = calibrator(opts, state) if calibrator is not None else GpuCalibrator(opts, state, device)
-        nb = opts["--batch"]
-        for i0 in range(0, len(queries), nb):                            # --batch 1: a model at a time, call for call as without the option
-            part = queries[i0:i0 + nb]
-            hmms = [build_model(score, opts["-n"] or name, seq, opts) for name, _, seq in part]
-            if nb == 1:
-                after = cal.calibrate(hmms[0], state)
-                if not seed:                                             # p7_builder.c:131: no reseeding, the generator runs on
-                    state = after
-            else:                                                        # a seed: every model starts from <state> (parse_options)
-                try:
-                    if hasattr(cal, "calibrate_many"):
-                        cal.calibrate_many(hmms, state)
-                    else:
-                        for hmm in hmms:
-                            cal.calibrate(hmm, state)
-                except ba.BathError as e:
-                    raise ba.BathError("records %d to %d of %s, calibrated as one batch: %s" % (i0 + 1, i0 + len(part), path_in, e))
-            for j, (hmm, (name, desc, seq)) in enumerate(zip(hmms, part)):
-                fh.write(ba.hmm_text(hmm, date=date or time.strftime("%a %b %e %H:%M:%S %Y")))
-                stdout.write(result_line(i0 + j + 1, opts["-n"] or name, len(seq), hmm.M, opts["--ct"], ba.hmm_relent(hmm), desc))
-            del hmms                                                     # at most a batch's models are alive at once
+        build_models(queries, score, opts, cal, state, fh, path_in, date=date, report=lambda i, rec, hmm: stdout.write(
+            result_line(i + 1, opts["-n"] or rec[0], len(rec[2]), hmm.M, opts["--ct"], ba.hmm_relent(hmm), rec[1])))
         fh.close()
         os.replace(tmp_out, path_out)                                    # the output appears only when it is whole
     except (ba.BathError, OSError) as e:

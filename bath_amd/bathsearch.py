@@ -13,8 +13,20 @@ same tail as the --tblout file, in every run mode.  Its header lines come with t
 list is not empty (the reference's rule).  --notrans adds its header line and changes nothing else: the reference sets
 pli->show_translated_sequence and never reads it, so the translation line of the alignment blocks is printed regardless.
 
-Every option the library implements is mapped; every other bathsearch option, a sequence or alignment query and a target file that
-is not plain FASTA are refused (exit status 1, a message naming it).
+Every option the library implements is mapped; every other bathsearch option, an alignment query and a target file that is not
+plain FASTA are refused (exit status 1, a message naming it).
+
+--qformat fasta takes an unaligned protein FASTA file as the query (the tutorial's bathsearch --hmmout AMP_N.bhmm -o AMP_N.out
+AMP_N.fa target-AMP_N.fa): one single-sequence model per record, built by bathbuild's builder (bathbuild.build_models: --mx /
+--mxfile / --popen / --pextend, --ct, --w_beta / --w_length with bathbuild's meaning; the builder's seed is 42 with reseeding,
+whatever --seed says; the default calibration sizes), calibrated on the GPU in batches of 16 (one by one with --arith odds3|odds),
+written to --hmmout's file or to a temporary file that is removed on every exit path, and searched as read back from that text.
+The two frameshift taus are fitted only with --fs or --hmmout (bath_amd.calibrate fs=False otherwise: the standard filters alone);
+--fsonly without either is refused.  Every record is checked before any file is opened or the GPU touched.  The header names the
+query file as given; the tabular tails name --hmmout's file when given (the reference prints the name of the /tmp file it leaves
+behind there; this driver leaves none and names the query file).  Unlike the reference, which detects a single-record FASTA query
+by itself, the format must be asserted: a sequence file without --qformat is refused, and so is a model file with it.  With
+--gpus N the parent starts one child that builds the file and ends, then the ranks.
 
 --gpus N (1..16) runs one search over N ranks, one process per GPU (rank r on device r): the parent checks the command line and the
 inputs, opens no GPU and starts N fresh children (launch_ranks).  Every rank ingests the whole target file, the (query, window group)
@@ -47,12 +59,14 @@ import os
 import socket
 import subprocess
 import sys
+import tempfile
 import threading
 import time
 
 import numpy as np
 
 import bath_amd as ba
+from bath_amd import bathbuild as bb
 from bath_amd import dist
 
 BANNER = ("# bathsearch :: search protein profile(s) against DNA sequence database\n"
@@ -71,18 +85,25 @@ OPTIONS = {"-o": str, "--tblout": str, "--fstblout": str, "--fs": "flag", "--cig
            "--workers": int,       # an extension (no header line): queries searched side by side on N contexts of one GPU
            "--arith": str,         # an extension (no header line): the arithmetic of the --fs Forward / Backward recursions (ba.ARITH_MODES)
            "--ensemble": str,      # an extension, not a reference option (no header line): how --fs samples a multi-domain region's traces
-           "--ensemble-std": str}  # ... and how the standard branch does (a search without --fs; the --fs windows that take that branch)
+           "--ensemble-std": str,  # ... and how the standard branch does (a search without --fs; the --fs windows that take that branch)
+           # a sequence query (--qformat fasta) and how its models are built; all but --qformat itself require it
+           "--qformat": str, "--hmmout": str, "--popen": float, "--pextend": float, "--mx": str, "--mxfile": str, "--w_beta": float,
+           "--w_length": int}
 MAX_GPUS = 16
 MAX_WORKERS = 8
 # bathsearch options this driver does not implement: refused, never ignored (--crick and --watson too: the reference declares them
 # and never reads them)
-REFUSED = ["-h", "--splice", "--exontblout", "--hmmout", "--acc", "--noali", "--min_intron", "--max_intron",
-           "--incE", "--qformat", "--tformat", "--singlemx", "--popen", "--pextend", "--mx", "--mxfile", "--w_beta", "--w_length", "--cpu",
+REFUSED = ["-h", "--splice", "--exontblout", "--acc", "--noali", "--min_intron", "--max_intron",
+           "--incE", "--tformat", "--singlemx", "--cpu",
            "--restrictdb_stkey", "--restrictdb_n", "--ssifile", "--domZ", "--domE", "--domT", "--incdomE", "--incdomT", "--crick", "--watson",
            "--nodeinfo"]
 EXCLUSIVE = [("-m", "-M"), ("--textw", "--notextw"), ("-E", "-T"), ("--max", "--F1"), ("--max", "--F2"), ("--max", "--F3"), ("--max", "--F4"),
-             ("--max", "--nobias")]
-REQUIRES = {"--frameline": "--fs", "--cigar": "--tblout", "--F4": "--fs", "--arith": "--fs", "--fstblout": "--fs"}
+             ("--max", "--nobias"), ("--mx", "--mxfile")]
+BUILD_OPTIONS = ("--hmmout", "--popen", "--pextend", "--mx", "--mxfile", "--w_beta", "--w_length")     # how a sequence query's models are built
+REQUIRES = {"--frameline": "--fs", "--cigar": "--tblout", "--F4": "--fs", "--arith": "--fs", "--fstblout": "--fs",
+            **{o: "--qformat" for o in BUILD_OPTIONS}}
+BUILD_BATCH = 16            # a sequence query's models calibrated per bath_amd.calibrate_batch call (strict arithmetic)
+BUILD_SEED = 42             # p7_search_builder creates its builder without options (p7_builder.c:67-73): seed 42, reseeded per model
 
 
 # bathsearch.c:748-750 (the reference's spelling): a model without the frameshift taus, such as a plain HMMER3 file's
@@ -133,6 +154,19 @@ def parse_args(argv):
     for a, b in REQUIRES.items():
         if a in opts and b not in opts:
             raise UsageError("option %s requires %s" % (a, b))
+    if "--qformat" in opts:
+        if opts["--qformat"] in ("afa", "stockholm"):
+            raise UsageError("option --qformat %s: alignment queries are not supported; --qformat fasta searches with unaligned protein "
+                             "sequences" % opts["--qformat"])
+        if opts["--qformat"] != "fasta":
+            raise UsageError("option --qformat: %r is not a query format this bathsearch takes (fasta)" % opts["--qformat"])
+        if "--fsonly" in opts and "--fs" not in opts and "--hmmout" not in opts:
+            raise UsageError("option --fsonly with a sequence query needs --fs or --hmmout: the frameshift taus are fitted only then")
+        for o in BUILD_OPTIONS[1:]:                      # bathbuild's ranges
+            if o in opts and bb.OPTIONS[o][2] is not None and not bb.OPTIONS[o][2](opts[o]):
+                raise UsageError("option %s: %s is out of range" % (o, opts[o]))
+        if "--hmmout" in opts and any(os.path.abspath(opts["--hmmout"]) == os.path.abspath(f) for f in pos):
+            raise UsageError("option --hmmout: %s is an input of this search" % opts["--hmmout"])
     if "--strand" in opts and opts["--strand"] not in ("plus", "minus", "both"):
         raise UsageError("option --strand: expected plus, minus or both")
     for o in ("--ensemble", "--ensemble-std"):
@@ -156,7 +190,8 @@ def parse_args(argv):
 
 
 def output_header(opts, hmmfile, seqfile):
-    """The banner and option lines of the main output (bathsearch.c output_header)."""
+    """The banner and option lines of the main output (bathsearch.c output_header); <hmmfile>: the query file as given on the
+    command line, a model file or (--qformat fasta) a sequence file."""
     o = opts
     s = BANNER
     s += "# query HMM file:                                %s\n" % hmmfile
@@ -167,12 +202,18 @@ def output_header(opts, hmmfile, seqfile):
     for k, f in lines:
         if k in o:
             s += f % o[k]
+    if "--hmmout" in o:
+        s += "# hmm output:                                    %s\n" % o["--hmmout"]
     if "--notextw" in o:
         s += "# max ASCII text line length:                    unlimited\n"
     if "--textw" in o:
         s += "# max ASCII text line length:                    %d\n" % o["--textw"]
     if "--notrans" in o:
         s += "# show translated DNA sequence:                  no\n"
+    for k, f in [("--popen", "# gap open probability:                          %f\n"), ("--pextend", "# gap extend probability:                        %f\n"),
+                 ("--mx", "# subst score matrix (built-in):                 %s\n"), ("--mxfile", "# subst score matrix (file):                     %s\n")]:
+        if k in o:
+            s += f % o[k]
     for k, f in [("-E", "# sequence reporting threshold:       E-value <= %g\n"), ("-T", "# sequence reporting threshold:         score >= %g\n"),
                  ("--incT", "# sequence inclusion threshold:         score >= %g\n")]:
         if k in o:
@@ -196,6 +237,10 @@ def output_header(opts, hmmfile, seqfile):
     if "--seed" in o:
         s += ("# random number seed:                            one-time arbitrary\n" if o["--seed"] == 0 else
               "# random number seed set to:                     %d\n" % o["--seed"])
+    for k, f in [("--qformat", "# query format asserted:                         %s\n"), ("--w_beta", "# window length beta value:                      %g\n"),
+                 ("--w_length", "# window length :                                %d\n")]:
+        if k in o:
+            s += f % o[k]
     if "-l" in o:
         s += "# minimum ORF length:                            %d\n" % o["-l"]
     if "-m" in o:
@@ -415,7 +460,9 @@ class Output:
     banner is written on entry, and on every exit the files it opened are closed and a stream it was given is flushed."""
 
     def __init__(self, argv, opts, hmmfile, seqfile, stdout):
-        self.header, self.tail_args, self.stdout = output_header(opts, hmmfile, seqfile), (hmmfile, seqfile, argv), stdout
+        # <hmmfile>: the query file as given.  The tails name the file the models were read from when the run keeps it
+        # (bathsearch.c:728 replaces cfg->queryfile with the file it built; that is --hmmout's, or a temporary one this run removes)
+        self.header, self.tail_args, self.stdout = output_header(opts, hmmfile, seqfile), (opts.get("--hmmout", hmmfile), seqfile, argv), stdout
         self.ofp = open(opts["-o"], "w") if "-o" in opts else stdout
         self.tblfp = open(opts["--tblout"], "w") if "--tblout" in opts else None
         self.fstblfp = open(opts["--fstblout"], "w") if "--fstblout" in opts else None
@@ -1054,14 +1101,15 @@ def feed_batches(pool, nq, size, prepare):
     pool.wait()
 
 
-def _rank_search(argv, opts, hmmfile, seqfile, rank, world, device, dev, chunk_bytes, block_nt, resident_bytes, laps):
+def _rank_search(argv, opts, hmmfile, seqfile, rank, world, device, dev, chunk_bytes, block_nt, resident_bytes, laps, queryfile=None):
     """One rank's share of the search: per batch of queries and piece of the targets (plan_pieces, the same on every rank) its own
     items go through its pool of --workers contexts (one by default), a query per worker, longest first; the batch's results
-    travel to the queries' owners, which render them, and rank 0 writes the texts in query order."""
+    travel to the queries' owners, which render them, and rank 0 writes the texts in query order.  <hmmfile>: the model file;
+    <queryfile>: the query file as given when it is another (a sequence query, whose models the parent had built)."""
     nq = ba.HMM.count(hmmfile)
     qdescs = model_descriptions(hmmfile)
     with contextlib.ExitStack() as stack:                # leaves in reverse order: the pool's threads joined, then the files closed
-        out = stack.enter_context(Output(argv, opts, hmmfile, seqfile, sys.stdout)) if rank == 0 else None
+        out = stack.enter_context(Output(argv, opts, queryfile or hmmfile, seqfile, sys.stdout)) if rank == 0 else None
         t = time.perf_counter()
         ctxs = [new_context(device, opts) for _ in range(opts.get("--workers", 1))]
         laps["context_s"] = time.perf_counter() - t
@@ -1129,9 +1177,10 @@ def _rank_search(argv, opts, hmmfile, seqfile, rank, world, device, dev, chunk_b
     return 0
 
 
-def rank_main(argv, chunk_bytes=64 << 20, block_nt=256_000_000, resident_bytes=8 << 30):
+def rank_main(argv, chunk_bytes=64 << 20, block_nt=256_000_000, resident_bytes=8 << 30, models=None):
     """One rank of a --gpus N search (a child of launch_ranks: RANK, WORLD_SIZE and the rendezvous address in its environment).
-    BATH_SEARCH_SHARE_DEVICE=1: every rank on device 0; BATH_SEARCH_BACKEND: nccl (default) or gloo (collectives on CPU tensors)."""
+    BATH_SEARCH_SHARE_DEVICE=1: every rank on device 0; BATH_SEARCH_BACKEND: nccl (default) or gloo (collectives on CPU tensors).
+    models: the model file the parent built from a sequence query (--qformat fasta); the ranks search it."""
     t_main = time.perf_counter()
     laps = dict(launch_s=0.0, context_s=0.0, ingest_s=0.0, search_s=0.0, merge_write_s=0.0, items=0)
     rank, world = int(os.environ["RANK"]), int(os.environ["WORLD_SIZE"])
@@ -1167,7 +1216,8 @@ def rank_main(argv, chunk_bytes=64 << 20, block_nt=256_000_000, resident_bytes=8
     if t_start:
         laps["launch_s"] = time.time() - t_start
     try:
-        status = _rank_search(argv, opts, hmmfile, seqfile, rank, world, device, dev, chunk_bytes, block_nt, resident_bytes, laps)
+        status = _rank_search(argv, opts, models or hmmfile, seqfile, rank, world, device, dev, chunk_bytes, block_nt, resident_bytes, laps,
+                              queryfile=hmmfile)
     except ba.FastaFormatError as e:
         sys.stderr.write("Error: %s: %s\n" % (seqfile, e))
         status = 1
@@ -1182,26 +1232,146 @@ def rank_main(argv, chunk_bytes=64 << 20, block_nt=256_000_000, resident_bytes=8
     return status
 
 
+# ---------------------------------------------------------------------------------------------------------------------------
+# --qformat fasta: a protein sequence file as the query.  What p7_search_builder does with an unaligned file
+# (p7_search_builder.c:97-308): one single-sequence model per record, built and calibrated by bathbuild's builder
+# (bathbuild.build_models), written to --hmmout's file or to a temporary one, and searched as read back from that text
+# (bathsearch.c:727-731), so the search sees the five-decimal probabilities of a model file.  The two frameshift taus are fitted
+# only when --fs or --hmmout is given (p7_search_builder.c:182).
+# ---------------------------------------------------------------------------------------------------------------------------
+
+class SeqQuery:
+    """A checked sequence query: its records, the score system and the options of bathbuild's builder, fs (whether the taus are fitted)."""
+
+    def __init__(self, opts, path):
+        if not os.path.isfile(path):
+            raise UsageError("query file %s not found" % path)
+        if ba.HMM.count(path) > 0:
+            raise UsageError("query file %s is a profile HMM file: --qformat fasta asserts a protein sequence file" % path)
+        try:
+            self.queries = bb.read_queries(path)
+        except bb.UsageError as e:
+            raise UsageError(str(e))
+        try:
+            self.score = ba.ScoreSystem(opts.get("--mx") or "BLOSUM62", opts.get("--mxfile"), opts.get("--popen", 0.02), opts.get("--pextend", 0.4))
+        except ba.BathError as e:
+            raise UsageError("Failed to set single query seq score system:\n%s" % e)
+        for name, _, seq in self.queries:
+            if len(name.encode("latin-1")) > 127:
+                raise UsageError("%s: record %s: a model's name holds at most 127 bytes" % (path, name))
+            try:
+                ba.strip_query(seq)
+            except ba.BathError as e:
+                raise UsageError("%s: record %s: %s" % (path, name, e))
+        self.path, self.fs = path, "--fs" in opts or "--hmmout" in opts
+        arith = opts.get("--arith", "strict")
+        self.opts = {k: v[1] for k, v in bb.OPTIONS.items()}             # the builder's defaults; bathsearch's own --seed stays out
+        self.opts.update({"--ct": opts.get("--ct", 1), "--w_beta": opts.get("--w_beta"), "--w_length": opts.get("--w_length"), "--seed": BUILD_SEED,
+                          "--arith": arith, "--batch": BUILD_BATCH if arith == "strict" else 1})
+
+    def build(self, path_out, device=0, calibrator=None):
+        """The models' text in <path_out>, whole or not at all (a temporary name beside it, then a rename)."""
+        state = ba.rng_state(BUILD_SEED)
+        cal, tmp = None, path_out + ".tmp%d" % os.getpid()
+        try:
+            with open(tmp, "wb") as fh:
+                cal = calibrator(self.opts, state) if calibrator is not None else bb.GpuCalibrator(self.opts, state, device)
+                bb.build_models(self.queries, self.score, self.opts, cal, state, fh, self.path, fs=self.fs)
+            os.replace(tmp, path_out)
+        finally:
+            if cal is not None:
+                cal.close()
+            if os.path.exists(tmp):
+                os.remove(tmp)
+
+
+BUILD_TIMEOUT_S = (600.0, 1.0)      # the build child of a --gpus search: this long, and this much more per record
+
+
+def build_main(argv, path_out):
+    """The build of a --gpus N search with a sequence query, in a child process of its own (the parent opens no GPU)."""
+    try:
+        opts, qfile, _ = parse_args(argv)
+        SeqQuery(opts, qfile).build(path_out)
+    except (UsageError, ba.BathError, OSError) as e:
+        sys.stderr.write("Error: %s\n" % e)
+        return 1
+    return 0
+
+
+def build_in_child(argv, path_out, n_records):
+    """build_main in one fresh child process, under a time limit; returns its exit status (1 with a message when the limit ran out)."""
+    code = "import sys; from bath_amd import bathsearch as b; sys.exit(b.build_main(sys.argv[2:], sys.argv[1]))"
+    cmd = [sys.executable] + (["-s"] if sys.flags.no_user_site else []) + ["-c", code, path_out] + list(argv)
+    limit = BUILD_TIMEOUT_S[0] + BUILD_TIMEOUT_S[1] * n_records
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    env = dict(os.environ, PYTHONPATH=root + (os.pathsep + os.environ["PYTHONPATH"] if os.environ.get("PYTHONPATH") else ""))
+    p = subprocess.Popen(cmd, env=env, stdin=subprocess.DEVNULL, stdout=subprocess.DEVNULL)
+    try:
+        return 1 if p.wait(limit) else 0
+    except subprocess.TimeoutExpired:
+        _stop([p])
+        sys.stderr.write("Error: building the models of the sequence query took more than %d s\n" % limit)
+        return 1
+
+
 def run(argv, stdout=None, chunk_bytes=64 << 20, block_nt=256_000_000, resident_bytes=8 << 30, device=0):
     """The whole search; returns the exit status.  chunk_bytes: FASTA bytes per upload; block_nt: nucleotides per pipeline call;
     resident_bytes: the device-memory budget for the digitised targets kept across queries.  With --workers N > 1 and no
     BATH_HIP_HOST_THREADS in the environment, the variable is set in os.environ (process-wide: the library reads it at every
     ensemble) for the time of the search and removed afterwards; a caller with threads of its own that read or set it sees that."""
     stdout = stdout or sys.stdout
+    seqquery = None
     try:
         opts, hmmfile, seqfile = parse_args(argv)
-        nq = ba.HMM.count(hmmfile) if os.path.exists(hmmfile) else -1
-        if nq <= 0:
-            raise UsageError("query file %s is not a profile HMM file (sequence and alignment queries are not supported)" % hmmfile)
+        if "--qformat" in opts:
+            seqquery = SeqQuery(opts, hmmfile)
+        else:
+            nq = ba.HMM.count(hmmfile) if os.path.exists(hmmfile) else -1
+            if nq <= 0:
+                raise UsageError("query file %s is not a profile HMM file; give --qformat fasta to search with sequence queries "
+                                 "(alignment queries are not supported)" % hmmfile)
         if not os.path.exists(seqfile):
             raise UsageError("target file %s not found" % seqfile)
         check_target_file(seqfile)
-        for q in range(nq):                          # before any GPU work: P-values from an unset tau mean nothing
+        for q in range(0 if seqquery else nq):       # before any GPU work: P-values from an unset tau mean nothing
             if (ba.HMM(hmmfile, q).evparam[6:8] == np.float32(ba.FS_UNSET)).any():
                 raise UsageError(NOT_FORMATED % hmmfile)
     except UsageError as e:
         sys.stderr.write("Error: %s\n" % e)
         return 1
+    if seqquery is None:
+        return _search(argv, opts, hmmfile, hmmfile, seqfile, nq, stdout, chunk_bytes, block_nt, resident_bytes, device)
+    # a sequence query: its models into --hmmout's file, or into a temporary one that no exit path leaves behind
+    keep = "--hmmout" in opts
+    try:
+        if keep:
+            built = opts["--hmmout"]
+        else:
+            fd, built = tempfile.mkstemp(prefix="bathsearch_", suffix=".bhmm")
+            os.close(fd)
+    except OSError as e:
+        sys.stderr.write("Error: %s\n" % e)
+        return 1
+    try:
+        if opts.get("--gpus", 1) > 1:                # the parent opens no GPU: one child builds, and has ended before the ranks start
+            if build_in_child(argv, built, len(seqquery.queries)):
+                return 1
+        else:
+            try:
+                seqquery.build(built, device)
+            except (ba.BathError, OSError) as e:
+                sys.stderr.write("Error: %s\n" % e)
+                return 1
+        return _search(argv, opts, hmmfile, built, seqfile, len(seqquery.queries), stdout, chunk_bytes, block_nt, resident_bytes, device)
+    finally:
+        if not keep and os.path.exists(built):
+            os.remove(built)
+
+
+def _search(argv, opts, queryfile, hmmfile, seqfile, nq, stdout, chunk_bytes, block_nt, resident_bytes, device):
+    """The search of the <nq> models of <hmmfile>, in the run mode the options ask for; <queryfile>: the query file as given (the
+    model file itself, or the sequence file the models were built from)."""
     ct = opts.get("--ct", 1)
     if opts.get("--gpus", 1) > 1:
         for q in range(nq):                      # the ranks start only on inputs the single-GPU search would not refuse
@@ -1209,16 +1379,19 @@ def run(argv, stdout=None, chunk_bytes=64 << 20, block_nt=256_000_000, resident_
             if hmm.ct != ct:
                 if "-o" in opts:
                     with open(opts["-o"], "w") as fh:
-                        fh.write(output_header(opts, hmmfile, seqfile))
+                        fh.write(output_header(opts, queryfile, seqfile))
                 else:
-                    stdout.write(output_header(opts, hmmfile, seqfile))
+                    stdout.write(output_header(opts, queryfile, seqfile))
                 sys.stderr.write(CT_MISMATCH % (ct, hmmfile, hmm.ct, ct))
                 return 1
-        return launch_ranks(opts["--gpus"], argv, stdout, dict(chunk_bytes=chunk_bytes, block_nt=block_nt, resident_bytes=resident_bytes))
+        run_kw = dict(chunk_bytes=chunk_bytes, block_nt=block_nt, resident_bytes=resident_bytes)
+        if hmmfile != queryfile:
+            run_kw["models"] = hmmfile
+        return launch_ranks(opts["--gpus"], argv, stdout, run_kw)
     workers = opts.get("--workers", 1)
     threads = host_threads_per_worker(workers) if workers > 1 else None
     try:
-        with Output(argv, opts, hmmfile, seqfile, stdout) as out:
+        with Output(argv, opts, queryfile, seqfile, stdout) as out:
             if threads is not None:                  # the library reads it at every ensemble: each worker context's share
                 os.environ["BATH_HIP_HOST_THREADS"] = str(threads)
             _workers_search(opts, hmmfile, seqfile, nq, out.write_query, device, chunk_bytes, block_nt, resident_bytes)

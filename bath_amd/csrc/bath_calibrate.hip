@@ -41,6 +41,8 @@
 
 using namespace bath;
 
+static constexpr float kEvparamUnset = -99999.0f;           // p7_EVPARAM_UNSET
+
 // p7_codontable_Create: for each amino acid its codons in x, y, z order over ACGT; num[a] of them (at most 6)
 static void codon_table(const uint8_t basic[64], uint8_t table[20][6], int num[20]) {
   for (int a = 0; a < 20; a++) num[a] = 0;
@@ -708,11 +710,17 @@ static int calibrate_std(bath_hip_ctx *ctx, const bath_hip_oprofile *om, bath_hi
   return BATH_OK;
 }
 
-extern "C" int bath_hip_calibrate(bath_hip_ctx *ctx, bath_hmm *hmm, int ncbi_table, uint32_t *rng_state, bath_hip_calib_samples *samples,
-                                  int EmL, int EmN, int EvL, int EvN, int EfL, int EfN, double Eft, int arith, double *xv, int *redrawn) {
+// fs: the two frameshift taus behind the three standard fits (bath_hip_calibrate); without them (bath_hip_calibrate_std) no
+// frameshift sample is drawn, no parser launched, and the two taus are left unset
+static int calibrate_model(bath_hip_ctx *ctx, bath_hmm *hmm, int ncbi_table, uint32_t *rng_state, bath_hip_calib_samples *samples,
+                           int EmL, int EmN, int EvL, int EvN, int EfL, int EfN, double Eft, int arith, double *xv, int *redrawn, bool fs) {
   if (!ctx) return BATH_EINVAL;
   if (!hmm || hmm->M < 1 || !rng_state || !(Eft > 0. && Eft < 1.)) { ctx->set_error("calibrate: needs a model, a generator state and 0 < Eft < 1"); return BATH_EINVAL; }
   if (arith < BATH_ARITH_STRICT || arith > BATH_ARITH_ODDS) { ctx->set_error("calibrate: arith is 0 (strict), 1 (3-codon parser in odds ratios) or 2 (both parsers)"); return BATH_EINVAL; }
+  if (!fs && hmm->M > kCascadeMaxNodes) {                  // before anything is drawn or launched (with fs the parsers' own limit is lower)
+    ctx->set_error("calibrate: the filter cascade supports models up to " + std::to_string(kCascadeMaxNodes) + " nodes (this one has " + std::to_string(hmm->M) + ")");
+    return BATH_EINVAL;
+  }
   const int L[3] = {EmL, EvL, EfL}, N[3] = {EmN, EvN, EfN};
   uint32_t state = *rng_state;
   bath_hip_calib_samples *S = samples, *own = nullptr;
@@ -743,6 +751,11 @@ extern "C" int bath_hip_calibrate(bath_hip_ctx *ctx, bath_hmm *hmm, int ncbi_tab
   std::memcpy(ev, hmm->evparam, sizeof ev);
   hmm->evparam[1] = hmm->evparam[3] = hmm->evparam[5] = (float)lambda;           // evalues.c:148-153
   hmm->evparam[0] = (float)mu[0]; hmm->evparam[2] = (float)mu[1]; hmm->evparam[4] = (float)mu[2];
+  if (!fs) {                                               // evalues.c:124-155 without hmm->fs: the standard fits are the whole call
+    hmm->evparam[6] = hmm->evparam[7] = kEvparamUnset;
+    *rng_state = state;
+    return BATH_OK;
+  }
   double tau3 = 0., tau5 = 0.;
   double *xv3 = xv ? xv + EmN + EvN + EfN : nullptr, *xv5 = xv3 ? xv3 + EfN : nullptr;
   st = calibrate_fs_any(ctx, hmm, ncbi_table, &state, EfL, EfN, Eft, &tau3, &tau5, xv3, xv5, arith, redrawn, true, lambda);
@@ -750,6 +763,16 @@ extern "C" int bath_hip_calibrate(bath_hip_ctx *ctx, bath_hmm *hmm, int ncbi_tab
   hmm->evparam[6] = (float)tau3; hmm->evparam[7] = (float)tau5;
   *rng_state = state;
   return BATH_OK;
+}
+
+extern "C" int bath_hip_calibrate(bath_hip_ctx *ctx, bath_hmm *hmm, int ncbi_table, uint32_t *rng_state, bath_hip_calib_samples *samples,
+                                  int EmL, int EmN, int EvL, int EvN, int EfL, int EfN, double Eft, int arith, double *xv, int *redrawn) {
+  return calibrate_model(ctx, hmm, ncbi_table, rng_state, samples, EmL, EmN, EvL, EvN, EfL, EfN, Eft, arith, xv, redrawn, true);
+}
+
+extern "C" int bath_hip_calibrate_std(bath_hip_ctx *ctx, bath_hmm *hmm, uint32_t *rng_state, bath_hip_calib_samples *samples,
+                                      int EmL, int EmN, int EvL, int EvN, int EfL, int EfN, double Eft, double *xv) {
+  return calibrate_model(ctx, hmm, 0, rng_state, samples, EmL, EmN, EvL, EvN, EfL, EfN, Eft, BATH_ARITH_STRICT, xv, nullptr, false);
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------
@@ -770,8 +793,10 @@ struct StdBatch {
 };
 }  // namespace
 
-extern "C" int bath_hip_calibrate_batch(bath_hip_ctx *ctx, bath_hmm *const *hmms, int n_models, int ncbi_table, uint32_t *rng_state,
-                                        bath_hip_calib_samples *samples, int EmL, int EmN, int EvL, int EvN, int EfL, int EfN, double Eft, double *xv) {
+// fs: as calibrate_model's.  Without it (bath_hip_calibrate_std_batch) the batch is the three standard launches per tiling, the
+// copies behind them and one synchronize; the limit is the wave kernels' own, not the frameshift kernels'.
+static int calibrate_models(bath_hip_ctx *ctx, bath_hmm *const *hmms, int n_models, int ncbi_table, uint32_t *rng_state,
+                            bath_hip_calib_samples *samples, int EmL, int EmN, int EvL, int EvN, int EfL, int EfN, double Eft, double *xv, bool fs) {
   if (!ctx) return BATH_EINVAL;
   // ---- 1. everything that can be refused, before anything is drawn, launched or written
   if (n_models < 1 || n_models > BATH_CALIB_BATCH_MAX) { ctx->set_error("calibrate_batch: a batch holds 1 to " + std::to_string(BATH_CALIB_BATCH_MAX) + " models (this one " + std::to_string(n_models) + ")"); return BATH_EINVAL; }
@@ -779,10 +804,11 @@ extern "C" int bath_hip_calibrate_batch(bath_hip_ctx *ctx, bath_hmm *const *hmms
   for (int k = 0; k < n_models; k++) {
     const std::string who = "calibrate_batch: model at position " + std::to_string(k) + " of the batch: ";
     if (!hmms[k] || hmms[k]->M < 1) { ctx->set_error(who + "no model"); return BATH_EINVAL; }
-    if (hmms[k]->M > kFsMaxNodes) { ctx->set_error(who + "frameshift kernels support models up to " + std::to_string(kFsMaxNodes) + " nodes (this one has " + std::to_string(hmms[k]->M) + ")"); return BATH_EINVAL; }
+    if (fs && hmms[k]->M > kFsMaxNodes) { ctx->set_error(who + "frameshift kernels support models up to " + std::to_string(kFsMaxNodes) + " nodes (this one has " + std::to_string(hmms[k]->M) + ")"); return BATH_EINVAL; }
+    if (hmms[k]->M > kCascadeMaxNodes) { ctx->set_error(who + "the filter cascade supports models up to " + std::to_string(kCascadeMaxNodes) + " nodes (this one has " + std::to_string(hmms[k]->M) + ")"); return BATH_EINVAL; }
   }
   std::vector<uint8_t> basic((size_t)n_models * 64);
-  if (bath_gencode_basic(ncbi_table, basic.data()) != BATH_OK) { ctx->set_error("calibrate_batch: unknown NCBI translation table " + std::to_string(ncbi_table)); return BATH_EINVAL; }
+  if (fs && bath_gencode_basic(ncbi_table, basic.data()) != BATH_OK) { ctx->set_error("calibrate_batch: unknown NCBI translation table " + std::to_string(ncbi_table)); return BATH_EINVAL; }
   for (int k = 1; k < n_models; k++) std::memcpy(&basic[(size_t)k * 64], basic.data(), 64);
   const int L[3] = {EmL, EvL, EfL}, N[3] = {EmN, EvN, EfN};
   bath_hip_calib_samples *S = samples;
@@ -791,14 +817,14 @@ extern "C" int bath_hip_calibrate_batch(bath_hip_ctx *ctx, bath_hmm *const *hmms
     ctx->set_error("calibrate: the resident sample sets were drawn for another context, other lengths or counts, or from another generator state");
     return BATH_EINVAL;
   }
-  if (EfL < 2) { ctx->set_error("calibrate_batch: the frameshift fits need EfL >= 2"); return BATH_EINVAL; }
+  if (fs && EfL < 2) { ctx->set_error("calibrate_batch: the frameshift fits need EfL >= 2"); return BATH_EINVAL; }
   BATH_HIP_TRY(ctx, hipSetDevice(ctx->device));
   ctx->spans_reset();                                      // bath_hip_kernel_times afterwards: this batch's launches
   // ---- 2. the two frameshift sets every model reads: drawn once, behind the standard sets
   uint32_t state = S->state_after;
-  const size_t fs_set = (size_t)EfN * 3 * EfL;
+  const size_t fs_set = fs ? (size_t)EfN * 3 * EfL : 0;
   std::vector<uint8_t> dna(2 * fs_set);
-  for (int pass = 0; pass < 2; pass++)
+  for (int pass = 0; fs && pass < 2; pass++)
     if (bath_calib_sample(&state, kAminoBg, ncbi_table, EfL, EfN, dna.data() + (size_t)pass * fs_set) != BATH_OK) {
       ctx->set_error("calibrate_batch: translation table " + std::to_string(ncbi_table) + " has no codon for a background residue");
       return BATH_EINVAL;
@@ -865,9 +891,15 @@ extern "C" int bath_hip_calibrate_batch(bath_hip_ctx *ctx, bath_hmm *const *hmms
   std::vector<int> pair_of((size_t)n_models, 0);
   std::vector<double> lambda((size_t)n_models), tau3((size_t)n_models), tau5((size_t)n_models), x3, x5;
   for (int k = 0; k < n_models; k++) lambda[(size_t)k] = bath_hmm_lambda(hmms[k]);        // p7_Lambda
-  if (xv) { x3.resize((size_t)n_models * EfN); x5.resize((size_t)n_models * EfN); }
-  st = calibrate_fs_sets(ctx, "calibrate_batch", hmms, basic.data(), n_models, dna.data(), 1, pair_of.data(), lambda.data(), EfL, EfN, Eft,
-                         tau3.data(), tau5.data(), xv ? x3.data() : nullptr, xv ? x5.data() : nullptr, &queue_std);
+  if (fs) {
+    if (xv) { x3.resize((size_t)n_models * EfN); x5.resize((size_t)n_models * EfN); }
+    st = calibrate_fs_sets(ctx, "calibrate_batch", hmms, basic.data(), n_models, dna.data(), 1, pair_of.data(), lambda.data(), EfL, EfN, Eft,
+                           tau3.data(), tau5.data(), xv ? x3.data() : nullptr, xv ? x5.data() : nullptr, &queue_std);
+  } else {                                                 // the standard results alone: the copies, the one synchronize
+    st = queue_std();
+    const hipError_t sync = hipStreamSynchronize(ctx->stream);
+    if (st == BATH_OK) BATH_HIP_TRY(ctx, sync);
+  }
   if (st != BATH_OK) return st;
   // ---- 6. the standard fits (calibrate_std's, per model), into locals: nothing is written before the last has succeeded
   static const char *const kWhat[3] = {"msv mu", "vit mu", "fwd tau"};
@@ -897,14 +929,25 @@ extern "C" int bath_hip_calibrate_batch(bath_hip_ctx *ctx, bath_hmm *const *hmms
     float *ev = hmms[k]->evparam;
     ev[1] = ev[3] = ev[5] = (float)lambda[(size_t)k];                               // evalues.c:148-153
     ev[0] = (float)mu[(size_t)k * 3]; ev[2] = (float)mu[(size_t)k * 3 + 1]; ev[4] = (float)mu[(size_t)k * 3 + 2];
-    ev[6] = (float)tau3[(size_t)k]; ev[7] = (float)tau5[(size_t)k];
+    ev[6] = fs ? (float)tau3[(size_t)k] : kEvparamUnset; ev[7] = fs ? (float)tau5[(size_t)k] : kEvparamUnset;
     if (xv) {
-      double *out = xv + (size_t)k * (size_t)(per_model + 2 * (int64_t)EfN);
+      double *out = xv + (size_t)k * (size_t)(per_model + (fs ? 2 * (int64_t)EfN : 0));
       std::copy(&x[(size_t)k * per_model], &x[(size_t)(k + 1) * per_model], out);
+      if (!fs) continue;
       std::copy(&x3[(size_t)k * EfN], &x3[(size_t)(k + 1) * EfN], out + per_model);
       std::copy(&x5[(size_t)k * EfN], &x5[(size_t)(k + 1) * EfN], out + per_model + EfN);
     }
   }
   *rng_state = state;
   return BATH_OK;
+}
+
+extern "C" int bath_hip_calibrate_batch(bath_hip_ctx *ctx, bath_hmm *const *hmms, int n_models, int ncbi_table, uint32_t *rng_state,
+                                        bath_hip_calib_samples *samples, int EmL, int EmN, int EvL, int EvN, int EfL, int EfN, double Eft, double *xv) {
+  return calibrate_models(ctx, hmms, n_models, ncbi_table, rng_state, samples, EmL, EmN, EvL, EvN, EfL, EfN, Eft, xv, true);
+}
+
+extern "C" int bath_hip_calibrate_std_batch(bath_hip_ctx *ctx, bath_hmm *const *hmms, int n_models, uint32_t *rng_state,
+                                            bath_hip_calib_samples *samples, int EmL, int EmN, int EvL, int EvN, int EfL, int EfN, double Eft, double *xv) {
+  return calibrate_models(ctx, hmms, n_models, 0, rng_state, samples, EmL, EmN, EvL, EvN, EfL, EfN, Eft, xv, false);
 }

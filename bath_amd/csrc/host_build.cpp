@@ -320,9 +320,11 @@ extern "C" int64_t bath_hmm_write_ascii(const bath_hmm *hmm, int nseq, double ef
     line("STATS LOCAL MSV         %8.4f %8.5f\n", (double)e[0], (double)e[1]);
     line("STATS LOCAL VITERBI     %8.4f %8.5f\n", (double)e[2], (double)e[3]);
     line("STATS LOCAL FORWARD     %8.4f %8.5f\n", (double)e[4], (double)e[5]);
-    line("STATS LOCAL FS3 FORWARD %8.4f %8.5f\n", (double)e[6], (double)e[5]);
-    line("STATS LOCAL FS5 FORWARD %8.4f %8.5f\n", (double)e[7], (double)e[5]);
-    line("FRAMESHIFT PROB  %8.4f\n", (double)hmm->fsprob);
+    if (e[6] != -99999.0f && e[7] != -99999.0f) {                             // hmm->fs (p7_hmmfile.c:620-622): the taus were fitted
+      line("STATS LOCAL FS3 FORWARD %8.4f %8.5f\n", (double)e[6], (double)e[5]);
+      line("STATS LOCAL FS5 FORWARD %8.4f %8.5f\n", (double)e[7], (double)e[5]);
+      line("FRAMESHIFT PROB  %8.4f\n", (double)hmm->fsprob);
+    }
     if (hmm->ct) line("CODON TABLE  %d\n", hmm->ct);
   }
   o += "HMM     ";

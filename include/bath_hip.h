@@ -859,7 +859,9 @@ double bath_hmm_mean_match_relent(const bath_hmm *hmm);   /* p7_MeanMatchRelativ
 double bath_hmm_lambda(const bath_hmm *hmm);              /* p7_Lambda (evalues.c:244): ln 2 + 1.44 / (M * relent); 0 without a model */
 /* p7_hmmfile_WriteASCII(fp, p7_BATH_3f, hmm) (p7_hmmfile.c:565-689): the whole model's text, fields in the reference's order and
  * widths.  What bath_hmm does not hold comes as arguments: NSEQ (> 0), EFFN (>= 0), DESC, DATE and the command log, one line per
- * command (NULL or "": the line is left out).  The STATS block is written when the model is calibrated (evparam set).  Returns the
+ * command (NULL or "": the line is left out).  The STATS block is written when the model is calibrated (evparam set); a calibrated
+ * model whose two frameshift taus are unset (bath_hip_calibrate_std) is written as the reference writes hmm->fs == FALSE
+ * (p7_hmmfile.c:620-623): the three standard STATS lines and CODON TABLE, without the FS3, FS5 and FRAMESHIFT PROB lines.  Returns the
  * text's size in bytes and copies at most <cap> of them to <buf>; < 0 on error. */
 int64_t bath_hmm_write_ascii(const bath_hmm *hmm, int nseq, double eff_nseq, const char *desc, const char *date, const char *comlog,
                              char *buf, int64_t cap);
@@ -905,6 +907,19 @@ int  bath_hip_calibrate(bath_hip_ctx *ctx, bath_hmm *hmm, int ncbi_table, uint32
  * "fs5_fwd_parser_batch_kernel", one per tiling present. */
 int  bath_hip_calibrate_batch(bath_hip_ctx *ctx, bath_hmm *const *hmms, int n_models, int ncbi_table, uint32_t *rng_state,
                               bath_hip_calib_samples *samples, int EmL, int EmN, int EvL, int EvN, int EfL, int EfN, double Eft, double *xv);
+/* The standard half of the two calls above: what p7_Calibrate does for a model without hmm->fs (evalues.c:124-155), as the
+ * reference's search-time builder runs it when neither --fs nor --hmmout is given (p7_search_builder.c:182).  Lambda, the MSV mu, the
+ * Viterbi mu and the Forward tau exactly as bath_hip_calibrate / bath_hip_calibrate_batch fit them -- evparam[0..5] bit for bit,
+ * the same launches -- and nothing else: no frameshift sample is drawn, no frameshift parser launched, no translation table read,
+ * and on success evparam[6] and evparam[7] hold the unset value (-99999).  *rng_state ends where the three standard draws end; with
+ * <samples> that is the state behind them.  xv: NULL or, per model, EmN + EvN + EfN bit scores (MSV, Viterbi, Forward).  The other
+ * rules are those of the full calls (<samples> as there, required by the batch call; all or nothing; the batch call names a failing
+ * model's position), but the limit is the filter cascade's 2048 nodes, not the frameshift kernels' 1280.  bath_hip_kernel_times
+ * afterwards: "calib_msv", "calib_vit", "calib_fwd"; for the batch call the three "*_wave_batch_kernel" names, one per tiling. */
+int  bath_hip_calibrate_std(bath_hip_ctx *ctx, bath_hmm *hmm, uint32_t *rng_state, bath_hip_calib_samples *samples,
+                            int EmL, int EmN, int EvL, int EvN, int EfL, int EfN, double Eft, double *xv);
+int  bath_hip_calibrate_std_batch(bath_hip_ctx *ctx, bath_hmm *const *hmms, int n_models, uint32_t *rng_state,
+                                  bath_hip_calib_samples *samples, int EmL, int EmN, int EvL, int EvN, int EfL, int EfN, double Eft, double *xv);
 
 /* The multi-domain region stage on its own: the multihit Forward of every sequence of <regions> (each one region, configuration
  * length 100 as the pipeline's) and its trace ensemble in the context's bath_hip_set_fs_ensemble mode.  Per region r:
