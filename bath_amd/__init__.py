@@ -364,6 +364,10 @@ ABI = {
     "bath_calib_sample_batch": (C.c_int, [C.POINTER(C.c_uint32), _f32p, C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, _u8p]),
     "bath_hip_calibrate_fs_batch": (C.c_int, [_vp, C.POINTER(C.POINTER(_Hmm)), C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_uint32), C.c_int, C.c_int,
                                               C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
+    "bath_calib_skip": (C.c_int, [C.POINTER(C.c_uint32), _f32p, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "bath_hip_calibrate_fs_batch_at": (C.c_int, [_vp, C.POINTER(C.POINTER(_Hmm)), C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
+                                                 C.c_int, C.c_int, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(C.c_double),
+                                                 C.POINTER(C.c_double)]),
     # single-sequence models and their calibration (bathbuild)
     "bath_scorematrix_builtin": (C.c_char_p, [C.c_char_p]),
     "bath_scoresystem_create": (C.c_int, [C.c_char_p, C.c_char_p, C.c_double, C.c_double, C.POINTER(_vp), C.c_char_p, C.c_int]),
@@ -372,6 +376,7 @@ ABI = {
     "bath_scoresystem_conditionals": (C.c_int, [_vp, C.POINTER(C.c_double)]),
     "bath_hmm_from_sequence": (C.c_int, [_vp, _u8p, C.c_int, C.c_char_p, C.c_int, C.POINTER(C.POINTER(_Hmm))]),
     "bath_hmm_mean_match_relent": (C.c_double, [C.POINTER(_Hmm)]),
+    "bath_hmm_mean_position_relent": (C.c_double, [C.POINTER(_Hmm)]),
     "bath_hmm_lambda": (C.c_double, [C.POINTER(_Hmm)]),
     "bath_hmm_write_ascii": (C.c_int64, [C.POINTER(_Hmm), C.c_int, C.c_double, C.c_char_p, C.c_char_p, C.c_char_p, C.c_char_p, C.c_int64]),
     "bath_calib_sample_amino": (C.c_int, [C.POINTER(C.c_uint32), _f32p, C.c_int, C.c_int, _u8p]),
@@ -1745,6 +1750,17 @@ def calib_sample(state, L=CALIB_L, N=CALIB_N, ncbi_table=1, f=None):
     return dna, st.value
 
 
+def calib_skip(state, n_sets=2, L=CALIB_L, N=CALIB_N, ncbi_table=1, f=None):
+    """The generator's state after n_sets successive calib_sample calls from <state>, nothing stored: what a model that is passed
+    over costs a file's carried generator (its 3-codon and its 5-codon set)."""
+    st = C.c_uint32(state)
+    fa = None if f is None else np.ascontiguousarray(f, dtype=np.float32)
+    assert fa is None or fa.shape == (20,)
+    if lib().bath_calib_skip(C.byref(st), _f32(fa), ncbi_table, L, N, n_sets) != OK:
+        raise BathError("calib_skip failed: unknown translation table %d, or a residue without a codon in it" % ncbi_table)
+    return st.value
+
+
 def gumbel_fit_complete(x):
     """Maximum-likelihood Gumbel (mu, lambda) of complete data (esl_gumbel_FitComplete)."""
     x = np.ascontiguousarray(x, dtype=np.float64)
@@ -1876,6 +1892,32 @@ def calibrate_fs_batch(ctx, hmms, ncbi_tables, state, L=CALIB_L, N=CALIB_N, tail
     return (t3[:n], t5[:n], st.value, x3[:n], x5[:n]) if want_xv else (t3[:n], t5[:n], st.value)
 
 
+def calibrate_fs_batch_at(ctx, hmms, ncbi_tables, states, L=CALIB_L, N=CALIB_N, tailp=CALIB_TAILP, want_xv=False):
+    """calibrate_fs of several models (at most CALIB_BATCH_MAX), each from a generator state of its own, with the windows of all of
+    them in each parser launch: per model what calibrate_fs(ctx, hmms[k], ncbi_tables[k], states[k]) returns, bit for bit, strict
+    arithmetic only.  Models with one (state, table) share one pair of sample sets on the device.  (tau3 [n], tau5 [n], the state
+    behind each model's samples [n]), with want_xv also xv3 [n, N], xv5 [n, N].  All or nothing: a BathError names the position in
+    the batch of the model it is about."""
+    hmms = list(hmms)
+    n = len(hmms)
+    tabs = np.ascontiguousarray(ncbi_tables, dtype=np.int32).reshape(-1)
+    s_in = np.ascontiguousarray(states, dtype=np.uint32).reshape(-1)
+    if len(tabs) != n or len(s_in) != n:
+        raise ValueError("calibrate_fs_batch_at: %d models, %d translation tables, %d generator states" % (n, len(tabs), len(s_in)))
+    tabs, s_in = np.append(tabs, np.int32(1)), np.append(s_in, np.uint32(0))                # (n = 0: the library refuses, not a null pointer)
+    s_out = np.zeros(n + 1, np.uint32)
+    ptrs = (C.POINTER(_Hmm) * max(n, 1))(*[h._p for h in hmms])
+    t3, t5 = np.zeros(max(n, 1), np.float64), np.zeros(max(n, 1), np.float64)
+    x3 = np.zeros((max(n, 1), N), np.float64) if want_xv else None
+    x5 = np.zeros((max(n, 1), N), np.float64) if want_xv else None
+    u32p = C.POINTER(C.c_uint32)
+    ctx._check(lib().bath_hip_calibrate_fs_batch_at(ctx._h, ptrs, tabs.ctypes.data_as(C.POINTER(C.c_int)), n, s_in.ctypes.data_as(u32p), s_out.ctypes.data_as(u32p),
+                                                    L, N, tailp, _f64p(t3), _f64p(t5), None if x3 is None else _f64p(x3), None if x5 is None else _f64p(x5)),
+               "calibrate_fs_batch_at")
+    out = [int(s) for s in s_out[:n]]
+    return (t3[:n], t5[:n], out, x3[:n], x5[:n]) if want_xv else (t3[:n], t5[:n], out)
+
+
 # ---- single-sequence models and their calibration: what bath_amd.bathbuild calls
 CALIB_DEFAULTS = {"EmL": 200, "EmN": 200, "EvL": 200, "EvN": 200, "EfL": 100, "EfN": 200, "Eft": 0.04}   # p7_builder.c:116-122
 SEQ_COMLOG = "[HMM created from a query sequence]"                     # seqmodel.c:54
@@ -1947,6 +1989,11 @@ def seq_model(score, seq, name, ct=1):
 def hmm_relent(hmm):
     """p7_MeanMatchRelativeEntropy: bits per match state (the summary's re/pos)."""
     return lib().bath_hmm_mean_match_relent(hmm._p)
+
+
+def hmm_position_relent(hmm):
+    """p7_MeanPositionRelativeEntropy: bits per match position weighted by occupancy, entry transitions counted (bathstat's re/pos)."""
+    return lib().bath_hmm_mean_position_relent(hmm._p)
 
 
 def hmm_lambda(hmm):

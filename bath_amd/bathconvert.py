@@ -161,10 +161,11 @@ def model_plan(model, ct_opt, path="the input"):
             "tau3": tau3, "tau5": tau5, "need_maxl": "MAXL" not in f}
 
 
-def rewrite_model(model, ct, tau3, tau5, maxl=None):
+def rewrite_model(model, ct, tau3, tau5, maxl=None, add_maxl=True):
     """One model's text as p7_hmmfile_WriteASCII(fp, p7_BATH_3f, hmm) writes it after bathconvert: the header line BATH3/f, MAXL <maxl>
     after LENG when the text has none, the three STATS lines in the writer's spacing, then FS3, FS5, FRAMESHIFT PROB and CODON TABLE
-    (p7_hmmfile.c:617-623; taus as the floats the model record holds).  Every other line is the input's, byte for byte."""
+    (p7_hmmfile.c:617-623; taus as the floats the model record holds).  Every other line is the input's, byte for byte.
+    add_maxl=False (bathfetch, which computes no MAXL): a text without a MAXL line stays without one."""
     f32 = lambda s: float(np.float32(float(s)))
     lines = model.splitlines(keepends=True)
     has_maxl = any(ln.startswith("MAXL ") for ln in lines)
@@ -178,7 +179,7 @@ def rewrite_model(model, ct, tau3, tau5, maxl=None):
         elif ln.startswith("HMM "):
             head = False
             out.append(ln)
-        elif ln.startswith("LENG ") and not has_maxl:
+        elif ln.startswith("LENG ") and not has_maxl and add_maxl:
             out.append(ln)
             if maxl is None:
                 raise ValueError("the model has no MAXL line and none was given")

@@ -74,6 +74,24 @@ extern "C" int bath_calib_sample_amino(uint32_t *rng_state, const float *f, int 
   return BATH_OK;
 }
 
+// N sequences of the stream from <rng>; dna NULL: the draws alone (the generator moves as if they had been stored)
+static int sample_sets(FastRng &rng, const float *f, const uint8_t table[20][6], const int num[20], int L, int N, uint8_t *dna) {
+  std::vector<uint8_t> aa((size_t)L);
+  for (int s = 0; s < N; s++) {
+    draw_amino(rng, f, L, aa.data());
+    uint8_t *d = dna ? dna + (size_t)s * 3 * L : nullptr;
+    for (int i = 0; i < L; i++) {                          // p7_codontable_GetCodon: esl_rnd_Roll(r, num_codons[a])
+      const int a = aa[(size_t)i];
+      if (num[a] == 0) return BATH_EINVAL;                 // (eslEINVAL: the table has no codon for a residue the background emits)
+      const int x = (int)(rng.next() * num[a]);
+      if (!d) continue;
+      const int c = table[a][x];
+      d[3 * i] = (uint8_t)(c >> 4); d[3 * i + 1] = (uint8_t)((c >> 2) & 3); d[3 * i + 2] = (uint8_t)(c & 3);
+    }
+  }
+  return BATH_OK;
+}
+
 extern "C" int bath_calib_sample(uint32_t *rng_state, const float *f, int ncbi_table, int L, int N, uint8_t *dna) {
   if (!rng_state || !dna || L < 0 || N < 0) return BATH_EINVAL;
   if (!f) f = kAminoBg;
@@ -82,17 +100,26 @@ extern "C" int bath_calib_sample(uint32_t *rng_state, const float *f, int ncbi_t
   if (bath_gencode_basic(ncbi_table, basic) != BATH_OK) return BATH_EINVAL;
   codon_table(basic, table, num);
   FastRng rng = FastRng::from_state(*rng_state);
-  std::vector<uint8_t> aa((size_t)L);
-  for (int s = 0; s < N; s++) {
-    draw_amino(rng, f, L, aa.data());
-    uint8_t *d = dna + (size_t)s * 3 * L;
-    for (int i = 0; i < L; i++) {                          // p7_codontable_GetCodon: esl_rnd_Roll(r, num_codons[a])
-      const int a = aa[(size_t)i];
-      if (num[a] == 0) return BATH_EINVAL;                 // (eslEINVAL: the table has no codon for a residue the background emits)
-      const int x = (int)(rng.next() * num[a]);
-      const int c = table[a][x];
-      d[3 * i] = (uint8_t)(c >> 4); d[3 * i + 1] = (uint8_t)((c >> 2) & 3); d[3 * i + 2] = (uint8_t)(c & 3);
-    }
+  const int st = sample_sets(rng, f, table, num, L, N, dna);
+  if (st != BATH_OK) return st;
+  *rng_state = rng.x;
+  return BATH_OK;
+}
+
+// What a model that is passed over costs a file's carried generator (bathfetch without an index): the draws of <n_sets> sample
+// sets, nothing stored.  The draw count of a sequence is not fixed (a roll beyond the frequencies' sum is drawn again), so the
+// generator is stepped, not jumped.
+extern "C" int bath_calib_skip(uint32_t *rng_state, const float *f, int ncbi_table, int L, int N, int n_sets) {
+  if (!rng_state || L < 0 || N < 0 || n_sets < 0) return BATH_EINVAL;
+  if (!f) f = kAminoBg;
+  uint8_t basic[64], table[20][6];
+  int num[20];
+  if (bath_gencode_basic(ncbi_table, basic) != BATH_OK) return BATH_EINVAL;
+  codon_table(basic, table, num);
+  FastRng rng = FastRng::from_state(*rng_state);
+  for (int s = 0; s < n_sets; s++) {
+    const int st = sample_sets(rng, f, table, num, L, N, nullptr);
+    if (st != BATH_OK) return st;
   }
   *rng_state = rng.x;
   return BATH_OK;
@@ -570,6 +597,57 @@ extern "C" int bath_hip_calibrate_fs_batch(bath_hip_ctx *ctx, const bath_hmm *co
                                    tau3, tau5, xv3, xv5, nullptr);
   if (st != BATH_OK) return st;
   *rng_state = state;
+  return BATH_OK;
+}
+
+// Several models, each from a generator state of its own (bathfetch: with an index every key starts from a fresh generator; without
+// one the caller has walked the file's generator to each selected model with bath_calib_skip).  Models with one (state, table) read
+// one pair of sets: the sets are drawn once per distinct pair, in the order of first appearance.
+extern "C" int bath_hip_calibrate_fs_batch_at(bath_hip_ctx *ctx, const bath_hmm *const *hmms, const int *ncbi_tables, int n_models,
+                                              const uint32_t *states_in, uint32_t *states_out, int L, int N, double tailp,
+                                              double *tau3, double *tau5, double *xv3, double *xv5) {
+  if (!ctx) return BATH_EINVAL;
+  // ---- 1. everything that can be refused, before anything is drawn or written
+  if (n_models < 1 || n_models > BATH_CALIB_BATCH_MAX) { ctx->set_error("calibrate_fs_batch_at: a batch holds 1 to " + std::to_string(BATH_CALIB_BATCH_MAX) + " models (this one " + std::to_string(n_models) + ")"); return BATH_EINVAL; }
+  if (!hmms || !ncbi_tables || !states_in || !states_out || !tau3 || !tau5 || L < 2 || N < 2 || !(tailp > 0. && tailp < 1.)) { ctx->set_error("calibrate_fs_batch_at: needs models, their tables, a generator state per model in and out, L >= 2, N >= 2 and 0 < tailp < 1"); return BATH_EINVAL; }
+  std::vector<uint8_t> basic((size_t)n_models * 64);
+  for (int k = 0; k < n_models; k++) {
+    const std::string who = "calibrate_fs_batch_at: model at position " + std::to_string(k) + " of the batch: ";
+    if (!hmms[k] || hmms[k]->M < 1) { ctx->set_error(who + "no model"); return BATH_EINVAL; }
+    if (hmms[k]->M > kFsMaxNodes) { ctx->set_error(who + "frameshift kernels support models up to " + std::to_string(kFsMaxNodes) + " nodes (this one has " + std::to_string(hmms[k]->M) + ")"); return BATH_EINVAL; }
+    if (bath_gencode_basic(ncbi_tables[k], &basic[(size_t)k * 64]) != BATH_OK) { ctx->set_error(who + "unknown NCBI translation table " + std::to_string(ncbi_tables[k])); return BATH_EINVAL; }
+  }
+  BATH_HIP_TRY(ctx, hipSetDevice(ctx->device));
+  ctx->spans_reset();                                      // bath_hip_kernel_times afterwards: the batch's launches
+  // ---- 2. the samples: [pair][3-codon set, 5-codon set][N][3L], a pair per distinct (state, table)
+  const int64_t L3 = 3 * (int64_t)L;
+  const size_t pair_bytes = (size_t)2 * N * L3;
+  std::vector<int> pair_of((size_t)n_models), first_of;    // first_of[p]: the first model that reads pair p
+  std::vector<uint32_t> after;                             // after[p]: the generator behind pair p
+  std::vector<uint8_t> dna;
+  for (int k = 0; k < n_models; k++) {
+    int p = 0;
+    for (; p < (int)first_of.size(); p++)
+      if (states_in[first_of[(size_t)p]] == states_in[k] && ncbi_tables[first_of[(size_t)p]] == ncbi_tables[k]) break;
+    if (p == (int)first_of.size()) {
+      first_of.push_back(k);
+      dna.resize((size_t)(p + 1) * pair_bytes);
+      uint32_t state = states_in[k];
+      if (bath_calib_sample_batch(&state, kAminoBg, ncbi_tables + k, 1, L, N, dna.data() + (size_t)p * pair_bytes) != BATH_OK) {
+        ctx->set_error("calibrate_fs_batch_at: model at position " + std::to_string(k) + " of the batch: translation table " + std::to_string(ncbi_tables[k]) + " has no codon for a background residue");
+        return BATH_EINVAL;
+      }
+      after.push_back(state);
+    }
+    pair_of[(size_t)k] = p;
+  }
+  // ---- 3. to 5.: the slope the model's file gives (bathfetch.c:321-325)
+  std::vector<double> lambda((size_t)n_models);
+  for (int k = 0; k < n_models; k++) lambda[(size_t)k] = (double)hmms[k]->evparam[5];   // p7_FLAMBDA
+  const int st = calibrate_fs_sets(ctx, "calibrate_fs_batch_at", hmms, basic.data(), n_models, dna.data(), (int)first_of.size(), pair_of.data(), lambda.data(), L, N, tailp,
+                                   tau3, tau5, xv3, xv5, nullptr);
+  if (st != BATH_OK) return st;
+  for (int k = 0; k < n_models; k++) states_out[k] = after[(size_t)pair_of[(size_t)k]];
   return BATH_OK;
 }
 

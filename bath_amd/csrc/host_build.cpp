@@ -276,6 +276,48 @@ extern "C" double bath_hmm_mean_match_relent(const bath_hmm *hmm) {
   return KL / (double)hmm->M;
 }
 
+static float fsum(const float *v, int n) {                                    // esl_vec_FSum: a compensated float sum
+  float sum = 0.f, c = 0.f;
+  for (int i = 0; i < n; i++) { const float y = v[i] - c, t = sum + y; c = (t - sum) - y; sum = t; }
+  return sum;
+}
+
+// p7_MeanPositionRelativeEntropy (modelstats.c:163): the match emissions' relative entropy weighted by match occupancy
+// (p7_hmm_CalculateOccupancy, p7_hmm.c:1348), plus the occupancy-weighted cost in bits of the transitions into nodes 2..M against
+// the background's p1 = 350/351.  bathstat's last column; not the unweighted figure above that bathbuild prints.
+extern "C" double bath_hmm_mean_position_relent(const bath_hmm *hmm) {
+  if (!hmm || hmm->M < 1) return 0.;
+  const int M = hmm->M;
+  const float p1 = 350.f / 351.f;                                            // p7_bg_Create
+  const float *t = hmm->t;                                                   // [k][MM MI MD IM II DM DD]
+  std::vector<float> mocc((size_t)M + 1);
+  mocc[0] = 0.f;
+  mocc[1] = t[1] + t[0];
+  for (int k = 2; k <= M; k++) {
+    const float *tk = t + (size_t)(k - 1) * 7;
+    mocc[(size_t)k] = (float)(mocc[(size_t)k - 1] * (tk[0] + tk[1]) + (1.0 - mocc[(size_t)k - 1]) * tk[5]);
+  }
+  double mre = 0., tre = 0.;
+  for (int k = 1; k <= M; k++) {                                             // esl_vec_FRelEntropy, as above
+    const float *p = hmm->mat + (size_t)k * 20;
+    float kl = 0.f;
+    for (int x = 0; x < 20; x++)
+      if (p[x] > 0.f) kl = (float)(kl + p[x] * std::log((double)(p[x] / kAminoBg[x])));
+    mre += mocc[(size_t)k] * (float)(1.44269504 * kl);
+  }
+  mre /= fsum(mocc.data() + 1, M);
+  for (int k = 2; k <= M; k++) {
+    const float *tk = t + (size_t)(k - 1) * 7;
+    const float m1 = mocc[(size_t)k - 1];
+    const double xm = m1 * tk[0] * std::log((double)(tk[0] / p1));
+    const double xi = m1 * tk[1] * (std::log((double)(tk[0] / p1)) + std::log((double)(tk[3] / p1)));
+    const double xd = (1. - m1) * tk[5] * std::log((double)(tk[5] / p1));
+    tre += (xm + xi + xd) / 0.69314718055994529;
+  }
+  tre /= fsum(mocc.data() + 2, M - 1);                                       // (M = 1: 0 / 0, as the reference has it)
+  return mre + tre;
+}
+
 extern "C" double bath_hmm_lambda(const bath_hmm *hmm) {
   if (!hmm || hmm->M < 1) return 0.;
   return 0.69314718055994529 + 1.44 / ((double)hmm->M * bath_hmm_mean_match_relent(hmm));

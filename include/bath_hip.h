@@ -832,6 +832,20 @@ int bath_calib_sample_batch(uint32_t *rng_state, const float *f, const int *ncbi
 int bath_hip_calibrate_fs_batch(bath_hip_ctx *ctx, const bath_hmm *const *hmms, const int *ncbi_tables, int n_models,
                                 uint32_t *rng_state, int L, int N, double tailp,
                                 double *tau3, double *tau5, double *xv3, double *xv5);
+/* Fits from given generator states (bathfetch: the reference fits only what it fetches when the file has an index, every key from a
+ * fresh generator, and carries one generator through the whole file when it has none, bathfetch.c:282-347).
+ * bath_calib_skip: advances *rng_state exactly as n_sets successive bath_calib_sample calls with these arguments would, and stores
+ * nothing: what a model that is passed over costs the carried generator (n_sets = 2: its 3-codon and its 5-codon set).  BATH_EINVAL
+ * where bath_calib_sample returns it; *rng_state is left alone then.  Host only.
+ * bath_hip_calibrate_fs_batch_at: defined by what it equals -- for every k, bath_hip_calibrate_fs of hmms[k] with ncbi_tables[k] from a
+ * state equal to states_in[k]: tau3[k], tau5[k], xv3 / xv5 (NULL or [n_models * N]) and states_out[k], the state behind the model's
+ * 5-codon set, are the same bits.  Models with one (states_in[k], ncbi_tables[k]) read one pair of sample sets, drawn once and held
+ * once on the device; otherwise the launches are bath_hip_calibrate_fs_batch's.  Strict arithmetic only.  The same refusals, all or
+ * nothing, messages by position in the batch. */
+int bath_calib_skip(uint32_t *rng_state, const float *f, int ncbi_table, int L, int N, int n_sets);
+int bath_hip_calibrate_fs_batch_at(bath_hip_ctx *ctx, const bath_hmm *const *hmms, const int *ncbi_tables, int n_models,
+                                   const uint32_t *states_in, uint32_t *states_out, int L, int N, double tailp,
+                                   double *tau3, double *tau5, double *xv3, double *xv5);
 
 /* ------------------------------------------------------------------------------------------
  * Single-sequence models (bathbuild on an unaligned protein file; p7_SingleBuilder, p7_builder.c:501-569) and their calibration
@@ -856,7 +870,10 @@ int    bath_scoresystem_conditionals(const bath_scoresystem *s, double *Q /* [20
  * evparam unset, max_length -1, fsprob 0.01, ct as given.  BATH_ERANGE: a name of more than 127 bytes (bath_hmm.name would cut it).  The model is in memory as the reference's is when it calibrates it. */
 int    bath_hmm_from_sequence(const bath_scoresystem *s, const uint8_t *dsq, int n, const char *name, int ct, bath_hmm **ret);
 double bath_hmm_mean_match_relent(const bath_hmm *hmm);   /* p7_MeanMatchRelativeEntropy (modelstats.c:80), bits per match state */
-double bath_hmm_lambda(const bath_hmm *hmm);              /* p7_Lambda (evalues.c:244): ln 2 + 1.44 / (M * relent); 0 without a model */
+/* p7_MeanPositionRelativeEntropy (modelstats.c:163), bathstat's re/pos: match emissions weighted by match occupancy, plus the cost of
+ * the transitions into each node; 0 without a model */
+double bath_hmm_mean_position_relent(const bath_hmm *hmm);
+double bath_hmm_lambda(const bath_hmm *hmm);           /* p7_Lambda (evalues.c:244): ln 2 + 1.44 / (M * relent); 0 without a model */
 /* p7_hmmfile_WriteASCII(fp, p7_BATH_3f, hmm) (p7_hmmfile.c:565-689): the whole model's text, fields in the reference's order and
  * widths.  What bath_hmm does not hold comes as arguments: NSEQ (> 0), EFFN (>= 0), DESC, DATE and the command log, one line per
  * command (NULL or "": the line is left out).  The STATS block is written when the model is calibrated (evparam set); a calibrated
